@@ -9,7 +9,11 @@ work), render all 64 samples of this rank's pixel tiles, and -- for N > 1 -- com
 RCCL reduce of the accumulation buffer to rank 0.  Inputs are resident in HBM before the timed region.
 `rays` = Scene::hit invocations, counted exactly by the kernel.
 
-  python bench.py [--gpus N --steps K --warmup W] [--scaling strong|weak|samples]
+  python bench.py [--gpus N --steps K --warmup W] [--scaling strong|weak|samples] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed -- the RGBA32F frame (DIR/frame.npy) and
+its ray count (DIR/rays_per_step.npy, float64) -- at most 64 MB (a larger frame keeps a fixed, seeded sample of its pixels,
+DIR/frame_sample.npy).  The inputs are fixed (scene, camera, seed), so two builds can be compared output for output.
 
 N > 1 is launched either by the driver (python -m torch.distributed.run ... bench.py --gpus N: RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment) or by bench.py itself: with WORLD_SIZE unset, `--gpus N` spawns N fresh
@@ -286,6 +290,29 @@ def fast_math_leg(scene, cam, steps):
         t.close()
 
 
+DUMP_BUDGET = 60_000_000     # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dump_dir, arrays, budget=DUMP_BUDGET):
+    """Writes each array as dump_dir/<name>.npy (float32 stays float32, anything else becomes float64).  When they are larger than
+    `budget` together, the largest keeps a fixed sample of its rows (pixels, for a frame): drawn with a fixed seed and kept in order,
+    the same rows on every run, so that two builds compare the same elements."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        name = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays[name]
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+        keep = max(1, (budget - (total - a.nbytes)) // rows.strides[0])
+        idx = np.sort(np.random.default_rng(0x5EED).choice(len(rows), size=min(keep, len(rows)), replace=False))
+        arrays[name + "_sample"] = np.ascontiguousarray(rows[idx])
+        del arrays[name]
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
 def _code_only(text):
     """C / C++ source without comments and with white space collapsed: what the compiler sees of it."""
     import re
@@ -504,10 +531,15 @@ def main(argv=None):
     ap.add_argument("--force-group", action="store_true",
                     help="exercise the rendezvous + RCCL compose path even with one rank (plumbing check)")
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)     # test hook: this rank exits with 3 at once
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's frame, RGBA float32, and its ray "
+                         "count, float64) as DIR/<name>.npy: the same arguments give the same inputs, so two builds compare output for output")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="ranks only rendezvous (sockets), exchange their ranks and print the line skeleton: the launcher "
                          "/ relay / reduction plumbing without a GPU (tests/test_bench_helpers.py)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, argv))
@@ -646,8 +678,9 @@ def main(argv=None):
         if group is not None:
             group.barrier()
 
-    def measure(mode, steps, warmup):
-        """K timed steps of one workload; returns the rank-0 view of it (dict) -- every rank must call it."""
+    def measure(mode, steps, warmup, dump_dir=None):
+        """K timed steps of one workload; returns the rank-0 view of it (dict) -- every rank must call it.  dump_dir: rank 0 writes
+        the last timed step's outputs there (dump_outputs)."""
         stacked = mode == "weak" and world > 1
         sharded = mode == "samples" and world > 1
         FH = H * world if stacked else H
@@ -742,6 +775,8 @@ def main(argv=None):
                                       rays=None if world > 1 else rays_per_launch)
             if os.environ.get("TRC_BENCH_EXPECT_GOLDEN"):           # test hook: hold the frame to another entry (a wrong one must fail)
                 crc_check = check_against(goldens, os.environ["TRC_BENCH_EXPECT_GOLDEN"], crc=frame_crc(frame))
+            if dump_dir:
+                dump_outputs(dump_dir, {"frame": frame, "rays_per_step": [st.rays / steps]})
 
         # the same K steps with a DIFFERENT seed each (a progressive renderer never replays a frame: the adaptive
         # launch order then works from the previous frame's costs, not from this frame's own)
@@ -801,7 +836,7 @@ def main(argv=None):
             "oracle_check": crc_check, "composed_crc_ok": None if crc_check is None else crc_check.get("crc_ok"),
         }
 
-    primary = measure(args.scaling, args.steps, args.warmup)
+    primary = measure(args.scaling, args.steps, args.warmup, dump_dir=args.dump_outputs)
     info = trc.device_info()                   # before any optional leg: the watchdog thread must never touch the context
 
     def build_line(primary):

@@ -223,10 +223,11 @@ def test_sixteen_processes_share_the_gpu_and_every_download_arrives():
     processes on one GPU a D2H copy into freshly mapped pageable memory left whole ranges of the destination untouched while the device
     buffer, downloaded again, had the data (tests/campaigns/sppm_stress.py reproduced it 380 times in 9 000 scenes).  Every transfer to /
     from caller memory now goes through the context's pinned staging buffer (trc_copy_to_host / trc_copy_to_device).  Here: the same
-    harness, 16 workers x 12 scenes x 3 frames, the photon records downloaded after every frame -- no mismatch."""
+    harness, the same 192 scenes x 3 frames, the photon records downloaded after every frame -- no mismatch.  15 workers: with this
+    process, which holds the session's Tracer, 16 processes have the GPU open, the most a shared machine allows."""
     import subprocess, sys
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "campaigns", "sppm_stress.py"), "5000", "5192", "--procs", "16"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "campaigns", "sppm_stress.py"), "5000", "5192", "--procs", "15"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "MISMATCH" not in out.stdout and "0 workers saw a mismatch" in out.stdout, out.stdout[-3000:]
