@@ -41,8 +41,10 @@ extern "C" {
  *    all-reduce); trc_device_pci_bus_id; the test hooks moved to include/tracer_test_hooks.h and libtracer_amd_hooks.so
  * 6: launch lists may hold single-pixel parts (trc_debug_block_costs: bit 29; trc_launch_shape counts them as items); knob
  *    camera_policy; trc_download_composed on a non-root rank of a sample-sharded compose returns TRC_ERR_NO_FRAME (it used to
- *    hand out that rank's partial slices) */
-#define TRC_ABI_VERSION 6
+ *    hand out that rank's partial slices)
+ * 7: SVGF denoiser stage: trc_gbuffer_texel, trc_denoise_params, trc_denoise_default_params, trc_denoise, trc_download_denoised,
+ *    trc_tonemap_denoised, trc_download_gbuffer, trc_denoise_reset (nothing existing changed) */
+#define TRC_ABI_VERSION 7
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -432,7 +434,8 @@ trc_status trc_clear_accum(trc_ctx* ctx);
  * expose = 1 - clamp(CETone(luma, 1), 0, 0.9999) (Render.hh:91-95), ACESTone(rgb, expose) (Render.hh:78-89),
  * no sRGB curve (commented out at :73), 8-bit = (uint8)(clamp(x, 0, 1) * 255 + 0.5), alpha 255.  Rows are
  * written top-down (the shader flips v, :51-56): out row 0 = frame row H-1.  The reference feeds its SVGF-denoised
- * texture here; this takes the raw accumulator.  rgba8: host buffer of 4*W*H bytes; exposure_out may be NULL. */
+ * texture here; this takes the raw accumulator (trc_tonemap_denoised below takes the denoised one).  rgba8: host buffer of
+ * 4*W*H bytes; exposure_out may be NULL. */
 trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out);
 
 /* replaces -[AAPLRenderer render:] + kernelPathTracing dispatch
@@ -468,6 +471,85 @@ trc_status trc_trace_rays(trc_ctx* ctx, const trc_ray* rays, size_t n, trc_hit* 
 
 trc_status trc_get_stats(trc_ctx* ctx, trc_stats* out);   /* synchronises the stream */
 trc_status trc_reset_stats(trc_ctx* ctx);
+
+/* ------------------------------------------------------------------ */
+/* SVGF denoiser (tracer_amd/csrc/trc_denoise.hip)                     */
+/* ------------------------------------------------------------------ */
+/* The reference filters the SPPM running mean (sourceSVGF, Photon.metal:622) with MPSSVGFDenoiser before display
+ * (AAPLRenderer.mm:818-850, :1027), guided by a depth / normal G-buffer its camera pass writes (Photon.metal:23-24,154).
+ * MPS is closed; this is the published filter, Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017,
+ * stated here exactly (tests/svgf_ref/svgf_ref.cpp restates it operation by operation; every operation is binary32,
+ * no contraction, division and sqrt correctly rounded, exp = dm_expf of trc_detmath.h, sums in the order written).
+ *
+ * G-buffer, one texel per pixel: the ray of pixel (x, y) through the lens centre, u = x / W, v = y / H,
+ *   d = normalize((cornerLowLeft + horizontal * u) + vertical * v - lookFrom)  (kernelCameraRecording, Photon.metal:132-139),
+ * walked by the render kernels' production scene_hit.  depth = t (+inf on a miss), normal = HitRecord.sn (0 on a miss),
+ * albedo = texture_value of the hit material (1 for emitters -- DiffuseLight -- and misses), id = material index
+ * (TRC_GBUFFER_MISS on a miss).  Rebuilt by trc_denoise only when the scene, the camera or the frame size changed.
+ *
+ * Notation: L(c) = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b (trc_tonemap's weights); "hit" = id != TRC_GBUFFER_MISS;
+ * w8(x) = x squared log2(normal_exponent) times; taps are visited row by row (dy outer, dx inner), in-bounds hit taps only.
+ * Miss pixels pass the accumulator through unchanged, never enter a hit pixel's sums and take none (history 1).
+ *
+ * 1. Input c = accumulator rgb; with TRC_DENOISE_DEMODULATE c = c / max(albedo, TRC_DENOISE_ALBEDO_EPS) per channel.
+ * 2. Temporal pass (one kernel with 3).  Previous camera = the camera of the last trc_denoise.  Same camera (lookFrom,
+ *    horizontal, vertical, cornerLowLeft bitwise equal): the one tap (x, y) with weight 1, depth to compare zq = depth.
+ *    Otherwise P = lookFrom + d * depth, q = P - lookFrom', a = cornerLowLeft' - lookFrom', m = cross(horizontal', vertical'),
+ *    s = dot(a, m) / dot(q, m) (invalid unless s > 0 and finite), u' = (dot(q, h') * s - dot(a, h')) / dot(h', h'),
+ *    v' = (dot(q, v') * s - dot(a, v')) / dot(v', v') (h' = horizontal', v' = vertical'), px = u' W, py = v' H, valid
+ *    only for -1 < px < W, -1 < py < H; zq = length(q); taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), x0 = floor(px),
+ *    fx = px - x0, weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy.  A tap is consistent when it is in bounds, its
+ *    previous texel has the same id, |depth' - zq| <= 0.1 zq and dot(normal', normal) >= 0.9.  Over the consistent taps
+ *    W = sum w, C = sum w colour', M1, M2, N likewise (history colour, moments, history length); the history is valid
+ *    when W >= 0.01, and then prev = C / W etc.  n = valid ? min(N / W + 1, 64) : 1,
+ *    a = valid ? max(1 / n, alpha_color) : 1, am = valid ? max(1 / n, alpha_moments) : 1,
+ *    colour = valid ? prev + (c - prev) * a : c, mu1 = valid ? m1 + (L(c) - m1) * am : L(c) (m1 = M1 / W), mu2 likewise
+ *    with L(c)^2 (the blends and the sums below are written as corrections of the centre value: a constant stays exact).
+ * 3. Variance: n >= min_history: max(0, mu2 - mu1 * mu1).  Otherwise the 7x7 estimate around p over the demodulated
+ *    input: w = dm_expf(-(|z - z'| / D)) * w8(max(0, dot(n, n'))), D = sigma_z * (gx |dx| + gy |dy|) + 0.001 z, sums
+ *    W, S1 = sum w L', S2 = sum w L'^2, variance = max(0, S2 / W - (S1 / W)^2) (0 when W = 0).
+ *    Depth gradient stencil: gx = min(|z(x+1) - z|, |z(x-1) - z|) over the horizontal neighbours that are in bounds and
+ *    hit (0 when neither is), gy the same vertically -- one-sided across a depth step, so the step does not widen it.
+ * 4. A-trous iteration i (0-based, step 2^i), on (colour, variance): first the 3x3 Gaussian of the variance around p,
+ *    weights 0.25 centre, 0.125 edge, 0.0625 corner, vf = sum g var' / sum g; phi = sigma_l * sqrt(max(0, vf)) + 1e-10.
+ *    Then the 5x5 taps q = p + step (dx, dy), h = {1/16, 1/4, 3/8, 1/4, 1/16}: w = ((h[dx] h[dy]) * wn) * dm_expf(-(wz + wl)),
+ *    wn = w8(max(0, dot(n, n'))), wz = |z - z'| / D (D as in 3 with the offsets step dx, step dy), wl = |L - L'| / phi;
+ *    W += w, C += w (colour' - colour), V += (w w) var'; result colour = colour + C / W, variance = V / (W W) (the
+ *    input when W = 0).
+ *    Iteration 0's output is the next frame's colour history (Schied et al. section 4.2).
+ * 5. Output rgb = the last iteration's colour (the temporal colour for 0 iterations), times max(albedo, eps) when
+ *    demodulated; alpha = the accumulator's.  History is dropped by trc_resize, trc_upload_scene*, trc_set_environment*
+ *    and trc_denoise_reset: the next frame has n = 1 everywhere.
+ */
+#define TRC_GBUFFER_MISS        0xFFFFFFFFu
+#define TRC_DENOISE_DEMODULATE  1u          /* filter colour / albedo, remodulate at the end */
+#define TRC_DENOISE_ALBEDO_EPS  0.001f
+#define TRC_DENOISE_MAX_ITERATIONS 5u
+typedef struct trc_gbuffer_texel {
+    float    depth;                /* hit distance along the normalised camera ray, +inf on a miss */
+    float    normal[3];            /* HitRecord.sn */
+    float    albedo[3];            /* texture_value of the hit material; 1 for emitters and misses */
+    uint32_t id;                   /* material index, TRC_GBUFFER_MISS on a miss */
+} trc_gbuffer_texel;
+typedef struct trc_denoise_params {
+    uint32_t flags;                /* TRC_DENOISE_* */
+    uint32_t iterations;           /* a-trous iterations, 0 .. 5 (5) */
+    float    alpha_color;          /* (0, 1]: 0.1 (temporalReprojectionBlendFactor, AAPLRenderer.mm) */
+    float    alpha_moments;        /* (0, 1]: 0.2 */
+    float    sigma_z;              /* > 0: 1 */
+    uint32_t normal_exponent;      /* power of two, 1 .. 1024: 128 */
+    float    sigma_l;              /* > 0: 4 */
+    uint32_t min_history;          /* 1 .. 64: 4 (below it the variance is the 7x7 estimate) */
+} trc_denoise_params;
+void       trc_denoise_default_params(trc_denoise_params* out);
+/* Denoises the accumulator as it stands into the context's RGBA32F output; asynchronous on the context stream like
+ * trc_render.  TRC_ERR_NO_FRAME without trc_resize, TRC_ERR_NO_SCENE without a scene (or camera), TRC_ERR_UNSUPPORTED on a
+ * context in a group, TRC_ERR_INVALID_ARG on bad parameters.  Never touches the accumulator or the RNG texture. */
+trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* params);
+trc_status trc_download_denoised(trc_ctx* ctx, float* rgba /* 4*W*H */);            /* TRC_ERR_NO_FRAME before a trc_denoise */
+trc_status trc_tonemap_denoised(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out);  /* trc_tonemap's output stage on it */
+trc_status trc_download_gbuffer(trc_ctx* ctx, trc_gbuffer_texel* out /* W*H */);
+trc_status trc_denoise_reset(trc_ctx* ctx);
 /* developer diagnostic: the pixel blocks of the last trc_render (x | y << 16, in units of the block edge 1 << *blk_shift)
  * and the duration each one's wavefront measured per sample (shader clocks / (4 spp) -- the sort key of the adaptive launch order); with
  * strips (spp < 8) the costs are per strip; a block that ran in parts (four 4x4 quarters, some of them as four 2x2
@@ -831,5 +913,8 @@ TRC_SA(sizeof(trc_CameraRecord) == 112 && offsetof(trc_CameraRecord, position) =
        offsetof(trc_CameraRecord, valid) == 48 && offsetof(trc_CameraRecord, alternative) == 64 &&
        offsetof(trc_CameraRecord, flux) == 80 && offsetof(trc_CameraRecord, radius) == 96 &&
        offsetof(trc_CameraRecord, photonCount) == 100, "CameraRecord");
+TRC_SA(sizeof(trc_gbuffer_texel) == 32 && offsetof(trc_gbuffer_texel, normal) == 4 && offsetof(trc_gbuffer_texel, albedo) == 16 &&
+       offsetof(trc_gbuffer_texel, id) == 28, "gbuffer texel");
+TRC_SA(sizeof(trc_denoise_params) == 32, "trc_denoise_params");
 
 #endif /* TRACER_ABI_H */

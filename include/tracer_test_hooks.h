@@ -34,6 +34,12 @@ trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t 
  * RN(1 / c) and one residual correction, against the compiler's x / c */
 trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch);
 
+/* test hook of the SVGF stage (tracer_abi.h, trc_denoise): the state the last trc_denoise left, W*H float4 each (any pointer may
+ * be NULL): integrated = the temporal pass's (colour, variance), history = the colour history the next frame reprojects
+ * (a-trous iteration 0's (colour, variance), or the integrated colour at 0 iterations), moments = (mu1, mu2, history length, 0).
+ * TRC_ERR_NO_FRAME before a trc_denoise. */
+trc_status trc_debug_denoise_state(trc_ctx* ctx, float* integrated, float* history, float* moments);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ Triangle,Texture,Material,Camera}.hh (see the header for file:line).
 """
 import ctypes as C
 
-TRC_ABI_VERSION = 6
+TRC_ABI_VERSION = 7
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
@@ -192,6 +192,23 @@ class Hit(C.Structure):
                 ("n_descend", C.c_uint32), ("n_return", C.c_uint32), ("n_leaf", C.c_uint32)]
 
 
+class GBufferTexel(C.Structure):
+    """trc_gbuffer_texel: one pixel of the denoiser's G-buffer"""
+    _fields_ = [("depth", C.c_float), ("normal", C.c_float * 3), ("albedo", C.c_float * 3), ("id", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    """trc_denoise_params"""
+    _fields_ = [("flags", C.c_uint32), ("iterations", C.c_uint32), ("alpha_color", C.c_float), ("alpha_moments", C.c_float),
+                ("sigma_z", C.c_float), ("normal_exponent", C.c_uint32), ("sigma_l", C.c_float), ("min_history", C.c_uint32)]
+
+
+GBUFFER_MISS = 0xFFFFFFFF
+DENOISE_DEMODULATE = 1
+DENOISE_ALBEDO_EPS = 0.001
+DENOISE_MAX_ITERATIONS = 5
+
+
 class LaunchShape(C.Structure):
     """trc_launch_shape"""
     _fields_ = [("entries", C.c_uint32), ("wave_slots", C.c_uint32), ("longest_entry_ms", C.c_double),
@@ -211,7 +228,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32,
+                   TriangleVertex: 32, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -225,9 +242,10 @@ DEVICE_SYMBOLS = [
     "trc_sppm_init", "trc_sppm_frames", "trc_sppm_download",
     "trc_device_info", "trc_device_pci_bus_id", "trc_shard_seed", "trc_group_compose_samples", "trc_group_compose_samples_async", "trc_group_unique_id", "trc_group_init", "trc_group_reduce_accum", "trc_group_reduce_accum_async", "trc_group_allreduce_mean_accum", "trc_download_composed", "trc_group_finalize",
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape",
+    "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
-HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test"]
+HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",

@@ -1143,6 +1143,7 @@ void trc_destroy(trc_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     trc_sppm_release(ctx);
+    trc_denoise_release(ctx);
     collect_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
@@ -1186,6 +1187,7 @@ trc_status trc_upload_scene(trc_ctx* ctx, const trc_scene* scene) {
     ctx->lds_scene = ks.sc.n_lds_nodes == ks.sc.n_nodes;      // whole tree staged in LDS
     ctx->lds_prefix_ok = true;
     ctx->has_scene = true;
+    trc_denoise_invalidate(ctx);
     ctx->cost_valid = false; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;      // another scene: the recorded block costs say nothing about it
     return TRC_OK;
 }
@@ -1275,6 +1277,7 @@ trc_status trc_set_environment(trc_ctx* ctx, const float rgb[3]) {
     { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
     if (!ctx || !rgb) return TRC_ERR_INVALID_ARG;
     ctx->ambient[0] = rgb[0]; ctx->ambient[1] = rgb[1]; ctx->ambient[2] = rgb[2];
+    trc_denoise_invalidate(ctx);
     return TRC_OK;
 }
 
@@ -1284,6 +1287,7 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(ctx->d_envmap); ctx->d_envmap = nullptr; ctx->env_w = ctx->env_h = 0;
+    trc_denoise_invalidate(ctx);
     if (!rgb) return TRC_OK;                                             // back to the constant environment
     if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_set_environment_map: bad size");
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
@@ -1308,6 +1312,7 @@ trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->d_shard_in = ctx->d_shard_out = ctx->d_shard_src = nullptr; ctx->shard_px = 0; ctx->shard_nranks = 0; ctx->snapshot_busy = false;
     ctx->busy = ctx->busy_alt = false;
     trc_sppm_release(ctx);          // per-pixel camera records depend on the frame size
+    trc_denoise_release(ctx);       // ... and so do the denoiser's planes
     ctx->n_tiles = 0; ctx->tiles_nranks = 0;
     ctx->width = ctx->height = 0;
     const size_t n = (size_t)width * height;
@@ -1362,6 +1367,11 @@ trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
     if (!ctx || !rgba8) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_accum) return fail(ctx, TRC_ERR_NO_FRAME, "trc_tonemap before trc_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return trc_tonemap_plane(ctx, ctx->d_accum, rgba8, exposure_out);
+}
+}  // extern "C"
+
+trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, float* exposure_out) {
     const uint32_t n = ctx->width * ctx->height;
     unsigned long long* d_sums = nullptr;
     uchar4* d_out = nullptr;
@@ -1372,7 +1382,7 @@ trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
         unsigned long long sums[3];
         if (hipMemsetAsync(d_sums, 0, sizeof sums, ctx->stream) != hipSuccess) { st = fail(ctx, TRC_ERR_HIP, "tonemap memset"); break; }
         hipLaunchKernelGGL(k_tonemap_sum, dim3(std::min<uint32_t>((n + 255) / 256, 2048u)), dim3(256), 0, ctx->stream,
-                           reinterpret_cast<const float4*>(ctx->d_accum), n, d_sums);
+                           reinterpret_cast<const float4*>(plane), n, d_sums);
         if (hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) { st = fail(ctx, TRC_ERR_HIP, "tonemap sums"); break; }
         // same binary32 / binary64 steps as oracle/oracle.cpp orc_tonemap (exp through trc_detmath.h)
@@ -1383,7 +1393,7 @@ trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
         mapped = std::fmin(std::fmax(mapped, 0.0f), 0.9999f);
         const float expose = 1.0f - mapped;
         if (exposure_out) *exposure_out = expose;
-        hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(ctx->d_accum),
+        hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(plane),
                            ctx->width, ctx->height, expose, d_out);
         if (hipGetLastError() != hipSuccess || trc_copy_to_host(ctx, rgba8, d_out, (size_t)n * 4, ctx->stream) != TRC_OK ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) { st = fail(ctx, TRC_ERR_HIP, "tonemap kernel"); break; }
@@ -1391,6 +1401,7 @@ trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
     (void)hipFree(d_sums); (void)hipFree(d_out);
     return st;
 }
+extern "C" {
 
 // One pass of kernelPathTracing over the caller's share of the frame.  `inner`: this pass is one half of a first launch that
 // trc_render split in two (below).

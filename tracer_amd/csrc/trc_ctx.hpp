@@ -121,6 +121,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 
 // ======================================================================= context
 struct SppmState;   // trc_sppm.hip
+struct DenoiseState;   // trc_denoise.hip
 
 struct trc_ctx {
     int device = -1;
@@ -217,6 +218,7 @@ struct trc_ctx {
     float* d_shard_src = nullptr; hipEvent_t ev_snapshot_free = nullptr; bool snapshot_busy = false;
 
     SppmState* sppm = nullptr;       // trc_sppm.hip
+    DenoiseState* denoise = nullptr; // trc_denoise.hip (allocated by the first trc_denoise after trc_resize)
 
     // caller-supplied collectives (trc_group_set_collectives) instead of an RCCL communicator
     trc_collectives coll{};
@@ -296,7 +298,11 @@ size_t trc_dyn_lds_bytes(const trc_ctx* ctx, bool stats);
 // trc_lbvh.hip: stable 24-bit radix sort of (key, value) pairs
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result);
 uint32_t trc_sort_hist_words(uint32_t n);
+// trc_tonemap's output stage on any W*H RGBA32F plane of the context (the accumulator, the denoised frame); synchronous
+trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, float* exposure_out);
 trc_status trc_flush(trc_ctx* ctx);       // launches what trc_render kept back (every other entry point calls it first)
 hipEvent_t trc_get_event(trc_ctx* ctx);   // from the context's pool (null on failure); pairs go to ctx->pending
 void trc_sppm_release(trc_ctx* ctx);   // frees ctx->sppm (no-op when absent)
+void trc_denoise_release(trc_ctx* ctx);      // frees ctx->denoise: its G-buffers, planes and history (no-op when absent)
+void trc_denoise_invalidate(trc_ctx* ctx);   // another scene or environment: the G-buffer is stale and the history dropped
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)

@@ -533,6 +533,7 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     if (ctx->d_blob) { (void)hipFree(ctx->d_blob); ctx->d_blob = nullptr; }
     if (ctx->d_bvh_ref) { (void)hipFree(ctx->d_bvh_ref); ctx->d_bvh_ref = nullptr; }
     ctx->has_scene = false; ctx->n_bvh_ref = 0;
+    trc_denoise_invalidate(ctx);
     ctx->blob_bytes = (size_t)total * 4;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bvh_ref, sizeof(trc_BVH) * n_nodes));

@@ -110,19 +110,28 @@ def _load(path, hooks=False):
     L.trc_debug_set.argtypes = [vp, C.c_char_p, C.c_int]
     L.trc_debug_block_costs.argtypes = [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.trc_debug_launch_shape.argtypes = [vp, C.POINTER(abi.LaunchShape)]
+    L.trc_denoise_default_params.argtypes = [C.POINTER(abi.DenoiseParams)]
+    L.trc_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
+    L.trc_download_denoised.argtypes = [vp, vp]
+    L.trc_tonemap_denoised.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.trc_download_gbuffer.argtypes = [vp, vp]
+    L.trc_denoise_reset.argtypes = [vp]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
         L.trc_div_by_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
         L.trc_unary_test.argtypes = [vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32)]
+        L.trc_debug_denoise_state.argtypes = [vp, vp, vp, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
     for name in abi.DEVICE_SYMBOLS:
         f = getattr(L, name)
-        if name not in ("trc_abi_version", "trc_build_flavor", "trc_has_test_hooks", "trc_status_string", "trc_last_error", "trc_destroy", "trc_shard_seed"):
+        if name not in ("trc_abi_version", "trc_build_flavor", "trc_has_test_hooks", "trc_status_string", "trc_last_error", "trc_destroy", "trc_shard_seed",
+                        "trc_denoise_default_params"):
             f.restype = i32
     L.trc_shard_seed.restype = u64
+    L.trc_denoise_default_params.restype = None
     if L.trc_abi_version() != abi.TRC_ABI_VERSION:
         raise RuntimeError("libtracer_amd.so ABI version mismatch")
     return L
@@ -276,6 +285,50 @@ class Tracer:
                                            (abi.TRACE_ANY_HIT if any_hit else 0) | (abi.TRACE_PRODUCTION if production else 0)),
                     "trc_trace_rays")
         return hits
+
+    # --- SVGF denoiser (include/tracer_abi.h "SVGF denoiser") ----------------------------------------------------
+    def denoise_params(self, **overrides):
+        """trc_denoise_default_params, then the named fields replaced (demodulate=True sets TRC_DENOISE_DEMODULATE)."""
+        p = abi.DenoiseParams()
+        self._L.trc_denoise_default_params(C.byref(p))
+        if overrides.pop("demodulate", False):
+            p.flags |= abi.DENOISE_DEMODULATE
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+    def denoise(self, params=None, **overrides):
+        """trc_denoise on the accumulator as it stands (asynchronous); params: abi.DenoiseParams or field overrides."""
+        p = params if params is not None else self.denoise_params(**overrides)
+        self._check(self._L.trc_denoise(self._h, C.byref(p)), "trc_denoise")
+
+    def download_denoised(self):
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self._L.trc_download_denoised(self._h, out.ctypes.data), "trc_download_denoised")
+        return out
+
+    def tonemap_denoised(self):
+        """trc_tonemap's output stage on the denoised frame -> ((H, W, 4) uint8, rows top-down; exposure)."""
+        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        e = C.c_float(0)
+        self._check(self._L.trc_tonemap_denoised(self._h, out.ctypes.data, C.byref(e)), "trc_tonemap_denoised")
+        return out, e.value
+
+    def download_gbuffer(self):
+        """(H, W) structured array of trc_gbuffer_texel (tracer_amd.dtypes.GBUFFER_DTYPE)."""
+        from .dtypes import GBUFFER_DTYPE
+        out = np.empty((self.height, self.width), dtype=GBUFFER_DTYPE)
+        self._check(self._L.trc_download_gbuffer(self._h, out.ctypes.data), "trc_download_gbuffer")
+        return out
+
+    def denoise_reset(self):
+        self._check(self._L.trc_denoise_reset(self._h), "trc_denoise_reset")
+
+    def denoise_state(self):
+        """hooks build only: (integrated, history, moments), (H, W, 4) float32 each, as the last trc_denoise left them."""
+        planes = [np.empty((self.height, self.width, 4), dtype=np.float32) for _ in range(3)]
+        self._check(self._L.trc_debug_denoise_state(self._h, *(p.ctypes.data for p in planes)), "trc_debug_denoise_state")
+        return tuple(planes)
 
     def stats(self):
         s = abi.Stats()

@@ -29,3 +29,8 @@ CAMREC_DTYPE = np.dtype([("ratio", np.float32, 4), ("position", np.float32, 4), 
 PHOTON_DTYPE = np.dtype([("flux", np.float32, 4), ("normal", np.float32, 4), ("position", np.float32, 4),
                          ("direction", np.float32, 4), ("step", np.uint8), ("active", np.uint8), ("_pad", np.uint8, 14)])
 assert CAMREC_DTYPE.itemsize == C.sizeof(abi.CameraRecord) and PHOTON_DTYPE.itemsize == C.sizeof(abi.PhotonRecord)
+
+
+# trc_gbuffer_texel (include/tracer_abi.h): one pixel of the denoiser's G-buffer
+GBUFFER_DTYPE = np.dtype([("depth", np.float32), ("normal", np.float32, 3), ("albedo", np.float32, 3), ("id", np.uint32)])
+assert GBUFFER_DTYPE.itemsize == 32
