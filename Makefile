@@ -17,7 +17,7 @@ CXXFLAGS  := -std=c++17 -O2 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 HIPFLAGS  := -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude -Itracer_amd/csrc \
              -Wall -Wno-unused-function
 
-HOST_SRC  := tracer_amd/host/bvh_builder.cpp tracer_amd/host/scene.cpp tracer_amd/host/mesh.cpp tracer_amd/host/pbrt_scene.cpp
+HOST_SRC  := tracer_amd/host/bvh_builder.cpp tracer_amd/host/scene.cpp tracer_amd/host/mesh.cpp tracer_amd/host/pbrt_scene.cpp tracer_amd/host/png_reader.cpp
 HOST_HDR  := tracer_amd/host/host_math.hpp tracer_amd/host/host_scene.hpp tracer_amd/host/pbrt_text.hpp include/tracer_abi.h include/trc_sobol.h
 HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_lds.hip tracer_amd/csrc/trc_render_lds_mis.hip tracer_amd/csrc/trc_render_mem.hip tracer_amd/csrc/trc_render_mem_path.hip tracer_amd/csrc/trc_render_mem_volume.hip tracer_amd/csrc/trc_sppm.hip tracer_amd/csrc/trc_lbvh.hip tracer_amd/csrc/trc_denoise.hip
 # per translation unit: backend options that pay for ONE kernel family (profiles/r05/ab_flags*.txt: eight scheduler / sinking / LICM options
@@ -25,7 +25,7 @@ HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_lds.hip trac
 EXTRA_trc_render_mem_path := -mllvm -disable-machine-sink
 EXTRA_trc_render_mem_volume := -mllvm -disable-machine-sink
 EXTRA_trc_render_lds      := -mllvm -amdgpu-use-amdgpu-trackers
-HIP_HDR   := $(wildcard tracer_amd/csrc/*.hpp) include/tracer_abi.h include/tracer_test_hooks.h include/trc_detmath.h include/trc_sobol.h
+HIP_HDR   := $(wildcard tracer_amd/csrc/*.hpp) $(wildcard tracer_amd/csrc/*.inc) include/tracer_abi.h include/tracer_test_hooks.h include/trc_detmath.h include/trc_sobol.h
 
 .PHONY: all host hip hip_fast hip_hooks oracle example clean variant asan tsan sanitize design_table
 all: host hip hip_fast hip_hooks oracle example

@@ -3,7 +3,9 @@
 // output stage, PNG.  Nothing but the two shared libraries is involved.
 //
 //   trc_render [--scene cornell|spheres|volume] [--integrator path|mis|volume] [--size W H] [--spp N]
-//              [--mesh file.obj|file.pbrt] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
+//              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
+//              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
+//              as the reference's host binds uv_test.png (AAPLRenderer.mm:385-390)
 //   trc_render --pbrt scene.pbrt [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
 //              a whole pbrt-v3 scene (camera, film, lights, materials, spheres, meshes: trc_host_scene_load_pbrt)
 #include <chrono>
@@ -25,7 +27,7 @@
     } while (0)
 
 int main(int argc, char** argv) {
-    std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path;
+    std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false;
     for (int i = 1; i < argc; ++i) {
@@ -37,6 +39,7 @@ int main(int argc, char** argv) {
         else if (a == "--spp" && i + 1 < argc) spp = (uint32_t)std::atoi(argv[++i]);
         else if (a == "--mesh" && i + 1 < argc) mesh_path = argv[++i];          // Wavefront OBJ, PLY or pbrt-v3 trianglemeshes
         else if (a == "--hdr" && i + 1 < argc) hdr_path = argv[++i];            // Radiance .hdr backdrop (the reference's texHDR)
+        else if (a == "--albedo-map" && i + 1 < argc) albedo_path = argv[++i];  // PNG image texture on the mesh material
         else if (a == "--density" && i + 1 < argc) density_path = argv[++i];    // pbrt-v3 heterogeneous medium
         else if (a == "--lbvh") lbvh = true;
         else if (a == "--device-sah") device_sah = true;
@@ -85,6 +88,18 @@ int main(int argc, char** argv) {
     }
     trc_scene scene;
     trc_host_scene_view(hs, &scene);
+    std::vector<trc_Material> materials;         // --albedo-map: the scene's materials with the mesh's (19, dev_intersect.hpp) as Image 0
+    constexpr uint32_t kMeshMaterial = 19;
+    if (!albedo_path.empty()) {
+        if (scene.n_material <= kMeshMaterial || !pbrt_path.empty() || mesh_path.empty()) {
+            std::fprintf(stderr, "--albedo-map textures the mesh material of a --mesh scene\n");
+            return 2;
+        }
+        materials.assign(scene.materials, scene.materials + scene.n_material);
+        materials[kMeshMaterial].textureInfo.type = TRC_TEX_IMAGE;
+        materials[kMeshMaterial].textureInfo.textureIndex = 0;
+        scene.materials = materials.data();
+    }
 
     CHECK(trc_create(0, &ctx));
     if (device_sah && pbrt_path.empty()) {        // triangle leaves + BVH::buildTree itself, both on the device
@@ -124,6 +139,18 @@ int main(int argc, char** argv) {
         const trc_status es = trc_set_environment_map(ctx, ew, eh, env);
         trc_host_free(env);
         CHECK(es);
+    }
+    if (!albedo_path.empty()) {                  // MTKTextureLoader with sRGB off, flipped vertically (AAPLRenderer.mm:349-447)
+        trc_image img;
+        float* rgb = nullptr;
+        if (trc_host_load_png(albedo_path.c_str(), &img.width, &img.height, &rgb) != TRC_OK) {
+            std::fprintf(stderr, "cannot read an 8-bit PNG image from %s\n", albedo_path.c_str());
+            return 1;
+        }
+        img.rgb = rgb;
+        const trc_status ts = trc_upload_textures(ctx, &img, 1);
+        trc_host_free(rgb);
+        CHECK(ts);
     }
     CHECK(trc_set_camera(ctx, &cam));
     CHECK(trc_resize(ctx, W, H));

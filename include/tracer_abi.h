@@ -43,8 +43,9 @@ extern "C" {
  *    camera_policy; trc_download_composed on a non-root rank of a sample-sharded compose returns TRC_ERR_NO_FRAME (it used to
  *    hand out that rank's partial slices)
  * 7: SVGF denoiser stage: trc_gbuffer_texel, trc_denoise_params, trc_denoise_default_params, trc_denoise, trc_download_denoised,
- *    trc_tonemap_denoised, trc_download_gbuffer, trc_denoise_reset (nothing existing changed) */
-#define TRC_ABI_VERSION 7
+ *    trc_tonemap_denoised, trc_download_gbuffer, trc_denoise_reset (nothing existing changed)
+ * 8: image textures: trc_image, trc_upload_textures, trc_host_load_png (nothing existing changed) */
+#define TRC_ABI_VERSION 8
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -267,14 +268,16 @@ enum trc_integrator {
                                        dimensions of the pixel's sample, random() (light pick, Russian roulette)
                                        draws from the copy, and the texel keeps the stream as castRay left it.
                                        TRC_INTEGRATOR_PATH / _MIS only, 2 * max_depth <= 40 dimensions; with
-                                       view_height the sampler sees the pixel and size of its own view. */
+                                       view_height the sampler sees the pixel and size of its own view.  Not with an
+                                       active image texture (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
 #define TRC_FLAG_SMALL_BLOCKS    8u  /* one 4x4 pixel block on 16 lanes per wavefront instead of 8x8 on 64 (a scheduling
                                        choice only: pixels are independent).  Pays when a launch has about as many
                                        blocks as the GPU has wavefront slots, i.e. a rank's share of a strong-scaled
                                        frame; chosen automatically there unless TRC_FLAG_LARGE_BLOCKS is set */
 #define TRC_FLAG_LARGE_BLOCKS   16u
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
-                                       N_descend / N_return / leaf-test counters */
+                                       N_descend / N_return / leaf-test counters.  Not with an active image texture
+                                       (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
 
 typedef struct trc_params {
     uint32_t spp;                /* samples per pixel this call; the reference does 1 per launch */
@@ -416,6 +419,32 @@ trc_status trc_set_environment(trc_ctx* ctx, const float rgb[3]);
  * 3*w*h floats, row 0 at v = 0.  A ray that leaves the scene returns SampleSphericalMap (Render.hh:42-48) + a bilinear,
  * clamp-to-edge lookup (Common.hh:11) instead of the constant of trc_set_environment; rgb == NULL clears the map. */
 trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const float* rgb);
+
+/* Image textures (TextureInfo::value, Texture.hh:29-35, over texture2d's of PackageEnv, Render.hh:26; the reference's host
+ * loads them with MTKTextureLoader, sRGB off, origin flipped vertically: AAPLRenderer.mm:349-447).  An image is 3*w*h
+ * float RGB, rows bottom-up (row 0 at v = 0: what trc_host_load_png returns).
+ *  - A material with textureInfo.type == TRC_TEX_IMAGE and textureIndex < n (an ACTIVE image) takes sample.rgb of image
+ *    textureIndex as its colour, NOT multiplied by albedo (Texture.hh:33-34).  textureIndex >= n, or nothing uploaded: the
+ *    colour is the albedo, as without textures (the reference's nullptr branch).
+ *  - uv: where Checker's comes from -- spheres and squares derive theirs from the hit (Sphere.hh:19-31, Square.hh), cubes
+ *    and triangles take the hit record's.  A non-finite component is replaced by 0 before the lookup, and a finite one is
+ *    clamped to [-1, 2] (so that u*w stays finite for any vt of a mesh).
+ *  - Lookup (trc_set_environment_map's, level 0, clamp to edge, float32, no contraction): x = u*w - 0.5, y = v*h - 0.5,
+ *    x0 = floor(x), fx = x - x0, column indices x0 and x0 + 1 clamped to [0, w-1] (y likewise);
+ *    top = (1 - fx) * t(x0, y0) + fx * t(x1, y0), bottom likewise on row y1, result (1 - fy) * top + fy * bottom.
+ *    No mip chain, no wrap modes, no sRGB decoding.
+ *  - Emitters keep Le = textureInfo.albedo (Render.metal:109): a texture on a light material changes nothing.
+ *  - Textures are context state like the environment map: they survive trc_upload_scene* and do not depend on the order
+ *    of the two uploads.  Every call replaces the whole set; n == 0 clears it.  The call drops the denoiser history and
+ *    the G-buffer (its albedo plane depends on the textures).
+ *  - TRC_ERR_INVALID_ARG: images == NULL with n > 0, a zero size, a NULL rgb or a non-finite texel; TRC_ERR_OOM when the
+ *    device allocation fails (the previous set is then cleared).  While an image is active, trc_render refuses
+ *    TRC_FLAG_SOBOL and TRC_FLAG_COLLECT_STATS with TRC_ERR_UNSUPPORTED. */
+typedef struct trc_image {
+    uint32_t     width, height;
+    const float* rgb;            /* 3 * width * height floats, rows bottom-up */
+} trc_image;
+trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -518,8 +547,8 @@ trc_status trc_reset_stats(trc_ctx* ctx);
  *    input when W = 0).
  *    Iteration 0's output is the next frame's colour history (Schied et al. section 4.2).
  * 5. Output rgb = the last iteration's colour (the temporal colour for 0 iterations), times max(albedo, eps) when
- *    demodulated; alpha = the accumulator's.  History is dropped by trc_resize, trc_upload_scene*, trc_set_environment*
- *    and trc_denoise_reset: the next frame has n = 1 everywhere.
+ *    demodulated; alpha = the accumulator's.  History is dropped by trc_resize, trc_upload_scene*, trc_set_environment*,
+ *    trc_upload_textures and trc_denoise_reset: the next frame has n = 1 everywhere.
  */
 #define TRC_GBUFFER_MISS        0xFFFFFFFFu
 #define TRC_DENOISE_DEMODULATE  1u          /* filter colour / albedo, remodulate at the end */
@@ -774,6 +803,13 @@ void trc_host_free(void* p);
  * vertically flipped HDR texture holds: vulture_hide_4k.hdr, AAPLRenderer.mm:352-383, sampled through Render.hh:42-48);
  * flat and run-length-encoded scanlines; *rgb is malloc'ed (3 * w * h floats), free with trc_host_free */
 trc_status trc_host_load_hdr(const char* path, uint32_t* width, uint32_t* height, float** rgb);
+
+/* PNG -> float RGB for trc_upload_textures, in trc_host_load_hdr's layout (rows bottom-up: the reference's
+ * MTKTextureLoaderOriginFlippedVertically): channel = byte / 255 (no gamma: MTKTextureLoaderOptionSRGB NO), grey replicated,
+ * alpha dropped.  Bit depth 8, colour types 0 / 2 / 4 / 6, not interlaced, filters 0-4; palette, 16-bit and Adam7 files:
+ * TRC_ERR_UNSUPPORTED; bad chunk CRC, bad Adler-32, truncated stream, more than 2^28 pixels: TRC_ERR_INVALID_ARG.
+ * *rgb is malloc'ed (3 * w * h floats), free with trc_host_free */
+trc_status trc_host_load_png(const char* path, uint32_t* width, uint32_t* height, float** rgb);
 
 /* "Export as PNG file" (the reference's unchecked to-do, RT_Metal/README.md:61): 8-bit RGBA, rows top-down,
  * stored (uncompressed) deflate blocks -- no zlib dependency */

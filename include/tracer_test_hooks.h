@@ -40,6 +40,11 @@ trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64
  * TRC_ERR_NO_FRAME before a trc_denoise. */
 trc_status trc_debug_denoise_state(trc_ctx* ctx, float* integrated, float* history, float* moments);
 
+/* test hook of the image textures (tracer_abi.h, trc_upload_textures): the render kernels' lookup of image `index` at n uv
+ * pairs (the non-finite rule included), one lane per pair: rgb receives 3 n floats.  TRC_ERR_INVALID_ARG when index is not
+ * below the number of uploaded images. */
+trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv /* 2 n */, size_t n, float* rgb /* 3 n */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,7 @@ static int load_obj(const std::string& p) { trc_host_mesh* m = nullptr; const tr
 static int load_ply(const std::string& p) { trc_host_mesh* m = nullptr; const trc_status st = trc_host_mesh_load_ply(p.c_str(), &m); if (st == TRC_OK) trc_host_mesh_destroy(m); return st; }
 static int load_density(const std::string& p) { uint32_t nx, ny, nz; float* g = nullptr; const trc_status st = trc_host_load_density_pbrt(p.c_str(), &nx, &ny, &nz, &g); if (st == TRC_OK) trc_host_free(g); return st; }
 static int load_hdr(const std::string& p) { uint32_t w, h; float* g = nullptr; const trc_status st = trc_host_load_hdr(p.c_str(), &w, &h, &g); if (st == TRC_OK) trc_host_free(g); return st; }
+static int load_png(const std::string& p) { uint32_t w, h; float* g = nullptr; const trc_status st = trc_host_load_png(p.c_str(), &w, &h, &g); if (st == TRC_OK) trc_host_free(g); return st; }
 
 int main(int argc, char** argv) {
     int n_fuzz = 2000;
@@ -182,9 +183,10 @@ int main(int argc, char** argv) {
     std::vector<Reader> readers = {
         {"pbrt scene", dir + "/scene.pbrt", load_scene}, {"pbrt meshes", dir + "/scene.pbrt", load_mesh_pbrt}, {"pbrt density", dir + "/medium.pbrt", load_density},
         {"ply ascii", dir + "/a.ply", load_ply}, {"ply little", dir + "/mesh.ply", load_ply}, {"ply big", dir + "/b.ply", load_ply},
-        {"obj", dir + "/m.obj", load_obj}, {"hdr", dir + "/sky.hdr", load_hdr}};
+        {"obj", dir + "/m.obj", load_obj}, {"hdr", dir + "/sky.hdr", load_hdr}, {"png", dir + "/tex.png", load_png}};
     write_file(dir + "/a.ply", make_ply(0)); write_file(dir + "/b.ply", make_ply(2));
     write_file(dir + "/m.obj", kObj); write_file(dir + "/sky.hdr", make_hdr());
+    { std::vector<uint8_t> px(7 * 5 * 4); for (size_t i = 0; i < px.size(); ++i) px[i] = (uint8_t)(i * 37); EXPECT(trc_host_write_png((dir + "/tex.png").c_str(), px.data(), 7, 5) == TRC_OK); }
     for (const Reader& r : readers) { const int st = r.load(r.file); if (st != TRC_OK) { std::fprintf(stderr, "%s: well-formed file rejected (%d)\n", r.name, st); ++g_fail; } }
 
     std::mt19937 gen(12345);

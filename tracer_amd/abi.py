@@ -7,7 +7,7 @@ Triangle,Texture,Material,Camera}.hh (see the header for file:line).
 """
 import ctypes as C
 
-TRC_ABI_VERSION = 7
+TRC_ABI_VERSION = 8
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
@@ -99,6 +99,10 @@ class TriangleVertex(C.Structure):
 
 class TextureInfo(C.Structure):
     _fields_ = [("type", C.c_int32), ("textureIndex", C.c_uint32), ("_pad", C.c_uint32 * 2), ("albedo", float3)]
+
+
+class Image(C.Structure):        # trc_image: 3*w*h float RGB, rows bottom-up (trc_upload_textures)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float))]
 
 
 class Material(C.Structure):
@@ -243,14 +247,15 @@ DEVICE_SYMBOLS = [
     "trc_device_info", "trc_device_pci_bus_id", "trc_shard_seed", "trc_group_compose_samples", "trc_group_compose_samples_async", "trc_group_unique_id", "trc_group_init", "trc_group_reduce_accum", "trc_group_reduce_accum_async", "trc_group_allreduce_mean_accum", "trc_download_composed", "trc_group_finalize",
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape",
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
+    "trc_upload_textures",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
-HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state"]
+HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",
     "trc_host_scene_view", "trc_host_scene_load_pbrt", "trc_host_mesh_load_obj", "trc_host_mesh_load_pbrt", "trc_host_mesh_load_ply", "trc_host_load_hdr", "trc_host_mesh_make_ball", "trc_host_mesh_replicate", "trc_host_mesh_from_arrays",
     "trc_host_mesh_view", "trc_host_mesh_destroy", "trc_host_make_density_info", "trc_host_make_cloud",
     "trc_host_load_density_pbrt", "trc_host_free", "trc_host_write_png", "trc_host_sobol_matrices32",
-    "trc_host_sobol_interval_tables",
+    "trc_host_sobol_interval_tables", "trc_host_load_png",
 ]

@@ -590,7 +590,7 @@ typedef MicroRefl<TrowbridgeReitzD<Alpha_01_02>, FrCond> MetalLobe;       // alp
 
 // material types (Material.hh:18-20) and texture types (Texture.hh:6) by ordinal
 constexpr int kMatDiffuse = 0, kMatLambert = 1, kMatPlastic = 3, kMatMetal = 4, kMatGlass = 5, kMatNil = 10;
-constexpr int kTexConstant = 0, kTexChecker = 1;
+constexpr int kTexConstant = 0, kTexChecker = 1, kTexImage = 3;
 
 TRC_DEV F3 texture_value(int tex_type, F3 albedo, F2 uv) {           // Texture.hh:17-43
     if (tex_type == kTexChecker) {
@@ -600,7 +600,8 @@ TRC_DEV F3 texture_value(int tex_type, F3 albedo, F2 uv) {           // Texture.
         float sines = s * c2;
         return albedo * (0.5f * (sines < 0 ? 0.0f : 1.0f) + 0.5f);
     }
-    // Constant; Image with a null texture and Noise resolve to albedo (see oracle/oracle.cpp texture_value)
+    // Constant; Image with a null texture and Noise resolve to albedo (see oracle/oracle.cpp texture_value); an uploaded image
+    // is sampled by hit_color<true> (dev_integrator.hpp) before this is reached
     return (tex_type >= 0 && tex_type <= 3) ? albedo : f3(1.0f);
 }
 

@@ -8,6 +8,8 @@
 #include "dev_intersect.hpp"
 #include "trc_sobol.h"
 
+#include <type_traits>
+
 // traceVolume: steps of the GridDensity medium's delta tracker a lane takes per iteration of the render loop before the other lanes
 // get their next Scene::hit (dev_integrator.hpp grid_sample); 0 = the whole tracker at once
 #ifndef TRC_TRACK_SLICE
@@ -34,8 +36,11 @@ struct LdsCount { uint32_t* p; };
 TRC_DEV void bump(uint32_t& c) { c++; }
 TRC_DEV void bump(LdsCount& c) { (void)__hip_atomic_fetch_add(c.p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 
+// image textures (trc_upload_textures): one pool of RGB float texels, rows bottom-up, and per image {first texel, w, h, 0};
+// n = images uploaded.  Read only by the TEX instantiations (hit_color<true>).
+struct TexTable { const float* texels; const uint4* desc; uint32_t n; };
 struct Shade {            // what the integrators need from the material table
-    const uint32_t* mats; // kMaterialDwords per material: type, texType, albedo.rgb
+    const uint32_t* mats; // kMaterialDwords per material: type, texType, albedo.rgb, specular, medium, textureIndex
 };
 TRC_DEV int mat_type(const Shade& sh, uint32_t m) { return (int)sh.mats[m * kMaterialDwords]; }
 TRC_DEV int mat_tex(const Shade& sh, uint32_t m) { return (int)sh.mats[m * kMaterialDwords + 1]; }
@@ -45,17 +50,51 @@ TRC_DEV F3 mat_albedo(const Shade& sh, uint32_t m) {
     const uint32_t* p = sh.mats + m * kMaterialDwords;
     return f3(__uint_as_float(p[2]), __uint_as_float(p[3]), __uint_as_float(p[4]));
 }
+// bilinear, clamp-to-edge lookup of level 0 of an RGB float image whose row 0 is at v = 0 (the reference's textureSampler,
+// Common.hh:11): texHDR through env_radiance and the image textures through hit_color<true>
+struct RgbImage { const float* rgb; uint32_t w, h; };        // 3*w*h floats, row 0 at v = 0
+TRC_DEV F3 bilinear_rgb(const RgbImage& em, float u, float v) {
+    const float x = u * (float)em.w - 0.5f, y = v * (float)em.h - 0.5f;
+    const float fx0 = floorf(x), fy0 = floorf(y);
+    const float fx = x - fx0, fy = y - fy0;
+    auto clampi = [](float f, uint32_t n) { return f < 0.0f ? 0u : (f > (float)(n - 1) ? n - 1 : (uint32_t)f); };
+    const uint32_t x0 = clampi(fx0, em.w), x1 = clampi(fx0 + 1.0f, em.w);
+    const uint32_t y0 = clampi(fy0, em.h), y1 = clampi(fy0 + 1.0f, em.h);
+    auto texel = [&](uint32_t xx, uint32_t yy) { const float* t = em.rgb + 3 * ((size_t)yy * em.w + xx); return f3(t[0], t[1], t[2]); };
+    const F3 top = (1 - fx) * texel(x0, y0) + fx * texel(x1, y0);
+    const F3 bot = (1 - fx) * texel(x0, y1) + fx * texel(x1, y1);
+    return (1 - fy) * top + fy * bot;
+}
+// sample.rgb of image `index` at uv (TextureInfo::value, Texture.hh:29-35); a non-finite component is looked up as 0, and a finite
+// one is clamped to [-1, 2] (u * w must stay finite; the clamp-to-edge result of any |u| beyond that is the edge texel's anyway)
+TRC_DEV F3 image_sample(const TexTable& tt, uint32_t index, F2 uv) {
+    const uint4 d = tt.desc[index];
+    const float u = (is_nan(uv.x) || is_inf(uv.x)) ? 0.0f : fminf(fmaxf(uv.x, -1.0f), 2.0f);
+    const float v = (is_nan(uv.y) || is_inf(uv.y)) ? 0.0f : fminf(fmaxf(uv.y, -1.0f), 2.0f);
+    return bilinear_rgb(RgbImage{tt.texels + 3 * (size_t)d.x, d.y, d.z}, u, v);
+}
+
 // texture colour of a hit; the sphere's uv (atan2 + asin, Sphere.hh:19-31) is only materialised here,
 // and only when a texture consumes it -- same value as computing it inside hit_test
 // ... and so is a square's (two divisions of rec.p's in-plane coordinates, Square.hh; square_uv)
-TRC_DEV F3 hit_color(const SceneRef& S, const Shade& sh, const HitRec& rec) {
+// TEX: an Image material whose textureIndex names an uploaded image takes that image's sample, not scaled by albedo
+// (Texture.hh:33-34); any other Image material resolves to its albedo as without TEX (the reference's nullptr branch)
+template <bool TEX = false>
+TRC_DEV F3 hit_color(const SceneRef& S, const Shade& sh, const HitRec& rec, const TexTable* tt = nullptr) {
     const int tex = mat_tex(sh, rec.material);
     F2 uv = rec.uv;
-    if (tex == kTexChecker) {
+    uint32_t index = 0;
+    bool image = false;
+    if (TEX) {
+        index = sh.mats[rec.material * kMaterialDwords + 7];
+        image = tex == kTexImage && index < tt->n;
+    }
+    if (tex == kTexChecker || image) {
         const uint32_t type = rec.tag >> kTagIndexBits;
         if (type == 0u) uv = sphere_uv(rec.gn);
         else if (type == 1u) uv = square_uv(S, rec.tag & kTagIndexMask, rec.p);
     }
+    if (TEX && image) return image_sample(*tt, index, uv);
     return texture_value(tex, mat_albedo(sh, rec.material), uv);
 }
 
@@ -81,22 +120,13 @@ TRC_DEV Ray cast_ray(const DCamera& cam, float s, float t, Pcg& rng) {
 }
 
 // texHDR (Render.hh:25,42-48) as an equirectangular RGB float image; null -> constant radiance `ambient`
-struct EnvMap { const float* rgb; uint32_t w, h; };
+typedef RgbImage EnvMap;         // (the lookup reads it through this struct: the env-mapped kernels keep their code)
 TRC_DEV F3 env_radiance(const EnvMap& em, F3 ambient, F3 direction) {
     if (!em.rgb) return ambient;
     const F3 v = normalize(direction);
     const float u = dm_atan2f(v.z, v.x) * 0.1591f + 0.5f;        // SampleSphericalMap
     const float w = dm_asinf(v.y) * 0.3183f + 0.5f;
-    const float x = u * (float)em.w - 0.5f, y = w * (float)em.h - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    const float fx = x - fx0, fy = y - fy0;
-    auto clampi = [](float f, uint32_t n) { return f < 0.0f ? 0u : (f > (float)(n - 1) ? n - 1 : (uint32_t)f); };
-    const uint32_t x0 = clampi(fx0, em.w), x1 = clampi(fx0 + 1.0f, em.w);
-    const uint32_t y0 = clampi(fy0, em.h), y1 = clampi(fy0 + 1.0f, em.h);
-    auto texel = [&](uint32_t xx, uint32_t yy) { const float* t = em.rgb + 3 * ((size_t)yy * em.w + xx); return f3(t[0], t[1], t[2]); };
-    const F3 top = (1 - fx) * texel(x0, y0) + fx * texel(x1, y0);
-    const F3 bot = (1 - fx) * texel(x0, y1) + fx * texel(x1, y1);
-    return (1 - fy) * top + fy * bot;
+    return bilinear_rgb(em, u, w);
 }
 
 struct PathCtx {
@@ -118,6 +148,12 @@ struct PathCtx {
     uint32_t sobol_m, sobol_res;  // log2Resolution, resolution (SobolSampler.hh:56-58)
     uint32_t sobol_xy[2];         // thread_pos within its view
 };
+// ... of the TEX instantiations (image textures): a struct of its own, so that the others' context keeps its layout
+struct PathCtxTex : PathCtx { TexTable tex; };
+template <bool TEX> using PathCtxOf = typename std::conditional<TEX, PathCtxTex, PathCtx>::type;
+template <bool TEX> TRC_DEV const TexTable* ctx_tex(const PathCtx& cx) {
+    if constexpr (TEX) return &static_cast<const PathCtxTex&>(cx).tex; else return nullptr;
+}
 
 // ---------------------------------------------------------------- path state machine
 // The reference runs, per pixel and per frame, castRay -> tracePath/traceMIS (a bounce loop around
@@ -202,7 +238,7 @@ TRC_DEV void path_begin(PathState& ps, const Ray& camera_ray, uint32_t max_depth
 
 // What happens between two Scene::hit calls of tracePath (Render.metal:432-489).  Returns true when the
 // path is finished; `result` is then the sample's radiance.
-template <bool STATS, bool SOBOL = false, class COUNT = uint32_t>
+template <bool STATS, bool SOBOL = false, bool TEX = false, class COUNT = uint32_t>
 TRC_DEV bool path_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_shaded, F3& result) {
     if (!ps.primary) {                                               // } while ((--depth) > 0), :489
         if (--ps.depth_left <= 0) { result = ps.color; return true; }
@@ -228,7 +264,7 @@ TRC_DEV bool path_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, 
     float bxPDF = 0;                                                 // uninitialised in the reference (B-3)
     bump(n_shaded);
     prof<STATS>(cnt, kProfShade);
-    F3 attenuation = material_S_F<STATS>(mtype, hit_color(cx.S, cx.sh, rec), wo, wi, uu, bxPDF, cnt);
+    F3 attenuation = material_S_F<STATS>(mtype, hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx)), wo, wi, uu, bxPDF, cnt);
     if (bxPDF <= 0) { result = ps.color; return true; }
     F3 wiw = (nx * wi.x + ny * wi.y) + rec.sn * wi.z;                // stw * wi
     if (wi.z < 0) ps.ray = make_ray(offset_ray(hit_origin, -rec.sn), wiw);   // transmission
@@ -377,7 +413,7 @@ TRC_DEV float grid_sample(const PathCtx& cx, const HitRec& rec, MediumHit& mi, P
 // Same for traceMIS (Render.metal:298-406) and, with VOLUME, traceVolume (Render.metal:78-275 = traceMIS + the
 // medium block :114-158).  Lights are literally squareList[5] and [6] (:320-324, B-12).
 // The shadow ray (any-hit Scene::hit) is traced here, inside the step.
-template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, class COUNT = uint32_t>
+template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, class COUNT = uint32_t>
 TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_rays,
                       COUNT& n_shaded, F3& result) {
     HitRec& rec = ps.rec;
@@ -471,7 +507,7 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
         blocked = scene_occluded<ALL_LDS, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, _dis, cx.stack, cx.S.stack_cap);
     }
     const F3 minus_d = -ps.ray.d;
-    const F3 base_color = hit_color(cx.S, cx.sh, rec);
+    const F3 base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
     if (!blocked) {                                                  // light sampling, :339-356
         F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
         F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));

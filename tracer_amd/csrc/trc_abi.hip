@@ -930,7 +930,11 @@ void launch_render(trc_ctx* ctx, const KRender& kp, bool stats, uint32_t integra
     if (dense) { hipLaunchKernelGGL(k_render_dense, grid, block, lds, ctx->stream, kp); return; }
     if (kp.strip > 1) {                      // few samples per pixel: a strip of blocks per wavefront (production kernels)
         dim3 sgrid((ctx->n_tiles + kp.strip - 1) / kp.strip);
-        if (kp.sobol32) {
+        if (kp.tex_desc) {                   // an active image texture (trc_upload_textures; never with Sobol' or statistics)
+            if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_VOLUME>), sgrid, block, lds, ctx->stream, kp);
+            else if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_MIS>), sgrid, block, lds, ctx->stream, kp);
+            else hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_PATH>), sgrid, block, lds, ctx->stream, kp);
+        } else if (kp.sobol32) {
             if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_MIS, true>), sgrid, block, lds, ctx->stream, kp);
             else hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_PATH, true>), sgrid, block, lds, ctx->stream, kp);
         } else if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_VOLUME, false>), sgrid, block, lds, ctx->stream, kp);
@@ -938,7 +942,11 @@ void launch_render(trc_ctx* ctx, const KRender& kp, bool stats, uint32_t integra
         else hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_PATH, false>), sgrid, block, lds, ctx->stream, kp);
         return;
     }
-    if (kp.sobol32) {                        // TRC_FLAG_SOBOL (production kernels of tracePath / traceMIS only)
+    if (kp.tex_desc) {                       // an active image texture: k_render<LDS, false, integrator, false> with hit_color<true>
+        if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_VOLUME>), grid, block, lds, ctx->stream, kp);
+        else if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_MIS>), grid, block, lds, ctx->stream, kp);
+        else hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_PATH>), grid, block, lds, ctx->stream, kp);
+    } else if (kp.sobol32) {                 // TRC_FLAG_SOBOL (production kernels of tracePath / traceMIS only)
         if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_MIS, true>), grid, block, lds, ctx->stream, kp);
         else hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_PATH, true>), grid, block, lds, ctx->stream, kp);
     } else if (integrator == TRC_INTEGRATOR_VOLUME) {
@@ -954,20 +962,27 @@ void launch_render(trc_ctx* ctx, const KRender& kp, bool stats, uint32_t integra
 }
 
 // persistent workgroups (k_render_pwg): grid = workgroups the GPU holds at once, block = the workgroup's wavefronts
-template <int INTEGRATOR, bool SOBOL>
+// TEX: the image-texture twin k_render_pwg_tex (never with SOBOL), whose grant is bit 8 + INTEGRATOR
+template <int INTEGRATOR, bool SOBOL, bool TEX = false>
 hipError_t launch_pwg_one(trc_ctx* ctx, const KRender& kp, uint32_t grid, size_t lds) {
+    static_assert(!(SOBOL && TEX), "no Sobol' twin of the texture kernels");
+    const void* const kern = TEX ? reinterpret_cast<const void*>(&k_render_pwg_tex<INTEGRATOR>) : reinterpret_cast<const void*>(&k_render_pwg<INTEGRATOR, SOBOL>);
     // more than 64 KB of dynamic LDS has to be asked for once per kernel AND per device (the attribute is set on the
     // current device's copy of the function): remembered in the context, which is bound to one device
-    const uint32_t bit = 1u << (INTEGRATOR * 2 + (SOBOL ? 1 : 0));
+    const uint32_t bit = 1u << (TEX ? 8 + INTEGRATOR : INTEGRATOR * 2 + (SOBOL ? 1 : 0));
     if (lds > 64 * 1024 && !(ctx->pwg_lds_granted & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_render_pwg<INTEGRATOR, SOBOL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         if (e != hipSuccess) return e;
         ctx->pwg_lds_granted |= bit;
     }
-    hipLaunchKernelGGL((k_render_pwg<INTEGRATOR, SOBOL>), dim3(grid), dim3(64 * pwg_waves(INTEGRATOR)), lds, ctx->stream, kp);
+    if (TEX) hipLaunchKernelGGL((k_render_pwg_tex<INTEGRATOR>), dim3(grid), dim3(64 * pwg_waves(INTEGRATOR)), lds, ctx->stream, kp);
+    else hipLaunchKernelGGL((k_render_pwg<INTEGRATOR, SOBOL>), dim3(grid), dim3(64 * pwg_waves(INTEGRATOR)), lds, ctx->stream, kp);
     return hipSuccess;
 }
 hipError_t launch_render_pwg(trc_ctx* ctx, const KRender& kp, uint32_t integrator, uint32_t grid, size_t lds) {
+    if (kp.tex_desc) return integrator == TRC_INTEGRATOR_VOLUME ? launch_pwg_one<TRC_INTEGRATOR_VOLUME, false, true>(ctx, kp, grid, lds)
+                          : integrator == TRC_INTEGRATOR_MIS ? launch_pwg_one<TRC_INTEGRATOR_MIS, false, true>(ctx, kp, grid, lds)
+                                                             : launch_pwg_one<TRC_INTEGRATOR_PATH, false, true>(ctx, kp, grid, lds);
     if (kp.sobol32) return integrator == TRC_INTEGRATOR_MIS ? launch_pwg_one<TRC_INTEGRATOR_MIS, true>(ctx, kp, grid, lds)
                                                             : launch_pwg_one<TRC_INTEGRATOR_PATH, true>(ctx, kp, grid, lds);
     if (integrator == TRC_INTEGRATOR_VOLUME) return launch_pwg_one<TRC_INTEGRATOR_VOLUME, false>(ctx, kp, grid, lds);
@@ -1146,7 +1161,7 @@ void trc_destroy(trc_ctx* ctx) {
     trc_denoise_release(ctx);
     collect_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
+    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
     (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_stats); (void)hipFree(ctx->d_stats_sum); (void)hipFree(ctx->d_reduce_recv);
     (void)hipFree(ctx->d_block_cost); (void)hipFree(ctx->d_order_hist); (void)hipFree(ctx->d_split); (void)hipFree(ctx->d_whole); (void)hipFree(ctx->d_cost_est); (void)hipFree(ctx->d_qsplit); (void)hipFree(ctx->d_qwhole); (void)hipFree(ctx->d_swhole); (void)hipFree(ctx->d_launch); (void)hipFree(ctx->d_plan); (void)hipFree(ctx->d_plan_gather); (void)hipFree(ctx->d_cost_scratch);
     for (int k = 0; k < 2; ++k) { (void)hipFree(ctx->d_order_keys[k]); (void)hipFree(ctx->d_order_vals[k]); }
@@ -1187,6 +1202,7 @@ trc_status trc_upload_scene(trc_ctx* ctx, const trc_scene* scene) {
     ctx->lds_scene = ks.sc.n_lds_nodes == ks.sc.n_nodes;      // whole tree staged in LDS
     ctx->lds_prefix_ok = true;
     ctx->has_scene = true;
+    ctx->scene_min_image = trc_scene_min_image(scene);
     trc_denoise_invalidate(ctx);
     ctx->cost_valid = false; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;      // another scene: the recorded block costs say nothing about it
     return TRC_OK;
@@ -1295,6 +1311,55 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
     { const trc_status cs = trc_copy_to_device(ctx, ctx->d_envmap, rgb, bytes, ctx->stream); if (cs != TRC_OK) return cs; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->env_w = w; ctx->env_h = h;
+    return TRC_OK;
+}
+
+// image textures: all images in one pool of RGB float texels (3 per texel, each image's rows bottom-up, the layout the caller
+// gives), and a descriptor {first texel, w, h, 0} per image; hit_color<true> (dev_integrator.hpp) reads both
+trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (n && !images) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: images == NULL");
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const trc_image& im = images[i];
+        if (im.width == 0 || im.height == 0 || !im.rgb) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: zero size or NULL rgb");
+        if ((uint64_t)im.width * im.height > (1ull << 28)) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: image larger than 2^28 texels");
+        const size_t count = (size_t)im.width * im.height * 3;
+        for (size_t k = 0; k < count; ++k)
+            if (!std::isfinite(im.rgb[k])) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: non-finite texel");
+        total += (uint64_t)im.width * im.height;
+    }
+    if (total > 0xFFFFFFFFull) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: more than 2^32 texels in all");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc);
+    ctx->d_tex_texels = nullptr; ctx->d_tex_desc = nullptr; ctx->n_tex = 0;
+    trc_denoise_invalidate(ctx);
+    if (n == 0) return TRC_OK;
+    std::vector<uint4> desc(n);
+    uint64_t first = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        desc[i] = make_uint4((uint32_t)first, images[i].width, images[i].height, 0u);
+        first += (uint64_t)images[i].width * images[i].height;
+    }
+    if (hipMalloc((void**)&ctx->d_tex_texels, (size_t)total * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&ctx->d_tex_desc, n * sizeof(uint4)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc);
+        ctx->d_tex_texels = nullptr; ctx->d_tex_desc = nullptr;
+        return fail(ctx, TRC_ERR_OOM, "trc_upload_textures: device allocation failed");
+    }
+    trc_status cs = trc_copy_to_device(ctx, ctx->d_tex_desc, desc.data(), n * sizeof(uint4), ctx->stream);
+    for (uint32_t i = 0; i < n && cs == TRC_OK; ++i)
+        cs = trc_copy_to_device(ctx, ctx->d_tex_texels + 3 * (size_t)desc[i].x, images[i].rgb, (size_t)images[i].width * images[i].height * 3 * sizeof(float), ctx->stream);
+    if (cs == TRC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) cs = fail(ctx, TRC_ERR_HIP, "trc_upload_textures: copy");
+    if (cs != TRC_OK) {
+        (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc);
+        ctx->d_tex_texels = nullptr; ctx->d_tex_desc = nullptr;
+        return cs;
+    }
+    ctx->n_tex = n;
     return TRC_OK;
 }
 
@@ -1427,6 +1492,8 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p) {
     if (p->integrator > TRC_INTEGRATOR_VOLUME) return fail(ctx, TRC_ERR_INVALID_ARG, "unknown integrator");
     if (p->integrator != TRC_INTEGRATOR_PATH && ctx->ks.sc.n_squares < 7)
         return fail(ctx, TRC_ERR_INVALID_ARG, "traceMIS / traceVolume sample squareList[5] and [6] (Render.metal:320-324,172-176)");
+    if (ctx->tex_active() && (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS)))
+        return fail(ctx, TRC_ERR_UNSUPPORTED, "image textures: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS kernels (trc_upload_textures)");
     if (p->flags & TRC_FLAG_SOBOL) {
         if (p->integrator == TRC_INTEGRATOR_VOLUME || (p->flags & TRC_FLAG_COLLECT_STATS))
             return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: tracePath / traceMIS, production kernels only");
@@ -1516,6 +1583,7 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     kp.cam = ctx->cam;
     kp.ambient[0] = ctx->ambient[0]; kp.ambient[1] = ctx->ambient[1]; kp.ambient[2] = ctx->ambient[2];
     kp.env_rgb = ctx->d_envmap; kp.env_w = ctx->env_w; kp.env_h = ctx->env_h;
+    if (ctx->tex_active()) { kp.tex_texels = ctx->d_tex_texels; kp.tex_desc = ctx->d_tex_desc; kp.n_tex = ctx->n_tex; }   // launch_render: the _tex kernels
     kp.fr.rng = ctx->d_rng; kp.fr.accum = ctx->d_accum; kp.fr.width = ctx->width; kp.fr.height = ctx->height;
     kp.spp = p->spp; kp.max_depth = p->max_depth; kp.frame0 = p->frame0;
     kp.view_height = (p->view_height != 0 && p->view_height < ctx->height) ? p->view_height : ctx->height;
@@ -1581,7 +1649,7 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
                            !(p->flags & (TRC_FLAG_LARGE_BLOCKS | TRC_FLAG_FIXED_ORDER));
     // wavefront slots of the kernel this launch runs (the plan's model; the launch bounds of k_render / k_render_pwg)
     // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD
-    const bool dense = ctx->lds_scene && p->integrator == TRC_INTEGRATOR_PATH && !stats && !sobol && kp.strip == 1 && !ctx->knobs.no_dense &&
+    const bool dense = ctx->lds_scene && p->integrator == TRC_INTEGRATOR_PATH && !stats && !sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
                        ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * TRC_PATH_WAVES_DENSE &&
                        ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)TRC_PARK_DENSE * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * TRC_PATH_WAVES_DENSE <= 160u * 1024u;
     const uint32_t waves_per_simd = dense ? TRC_PATH_WAVES_DENSE : p->integrator == TRC_INTEGRATOR_PATH ? (ctx->lds_scene ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL)
@@ -1826,6 +1894,39 @@ trc_status trc_debug_profile(trc_ctx* ctx, uint64_t* out, uint32_t n_sites) {
     for (uint32_t i = 0; i < n_sites && i < (uint32_t)kProfCount; ++i)
         for (int k = 0; k < 3; ++k) out[3 * i + k] = h[kStatCount + 3 * i + k];
     return TRC_OK;
+}
+
+// the render kernels' image lookup (dev_integrator.hpp image_sample), one lane per uv pair
+__global__ void __launch_bounds__(256) k_texture_sample_test(const float* texels, const uint4* desc, uint32_t n_tex, uint32_t index,
+                                                             const float* uv, uint32_t n, float* rgb) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    TexTable tt; tt.texels = texels; tt.desc = desc; tt.n = n_tex;
+    F2 p; p.x = uv[2 * i]; p.y = uv[2 * i + 1];
+    const F3 c = image_sample(tt, index, p);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv, size_t n, float* rgb) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    if (!ctx || (n && (!uv || !rgb))) return TRC_ERR_INVALID_ARG;
+    if (index >= ctx->n_tex) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: no such image");
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 3u) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: too many pairs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float* d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d, n * 5 * sizeof(float)));
+    float *d_uv = d, *d_rgb = d + 2 * n;
+    trc_status ts = trc_copy_to_device(ctx, d_uv, uv, n * 8, ctx->stream);
+    if (ts == TRC_OK) {
+        hipLaunchKernelGGL(k_texture_sample_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->d_tex_texels, ctx->d_tex_desc, ctx->n_tex, index, d_uv, (uint32_t)n, d_rgb);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) ts = fail(ctx, TRC_ERR_HIP, std::string("trc_texture_sample_test: ") + hipGetErrorString(e));
+    }
+    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, rgb, d_rgb, n * 12, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return ts;
 }
 #endif  // TRC_TEST_HOOKS
 

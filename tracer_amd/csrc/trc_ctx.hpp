@@ -62,6 +62,9 @@ struct KRender {
     const uint32_t* sobol32;            // TRC_FLAG_SOBOL: [40][52] generator matrices (null otherwise)
     const uint64_t* sobol_vdc;          // ... [52] VdCSobolMatrices[m - 1] + [52] VdCSobolMatricesInv[m - 1]
     uint32_t sobol_m;                   // ... log2Resolution
+    const float* tex_texels;            // image textures (k_render*_tex only): texel pool, RGB float, rows bottom-up ...
+    const uint4* tex_desc;              // ... {first texel, w, h, 0} per image
+    uint32_t n_tex;                     // ... images uploaded
 };
 
 struct KTrace {
@@ -151,6 +154,10 @@ struct trc_ctx {
     float ambient[3] = {0, 0, 0};
     float* d_envmap = nullptr; uint32_t env_w = 0, env_h = 0;
     uint32_t* d_sobol32 = nullptr; uint64_t* d_sobol_vdc = nullptr; uint32_t sobol_m = ~0u;   // TRC_FLAG_SOBOL tables
+    // image textures (trc_upload_textures): texel pool + descriptors, and the smallest textureIndex of the scene's Image
+    // materials (~0u: none) -- an image is active, and the _tex kernels launched, when it is below n_tex
+    float* d_tex_texels = nullptr; uint4* d_tex_desc = nullptr; uint32_t n_tex = 0; uint32_t scene_min_image = ~0u;
+    bool tex_active() const { return scene_min_image < n_tex; }
 
     // frame
     uint32_t width = 0, height = 0;
@@ -304,5 +311,12 @@ trc_status trc_flush(trc_ctx* ctx);       // launches what trc_render kept back 
 hipEvent_t trc_get_event(trc_ctx* ctx);   // from the context's pool (null on failure); pairs go to ctx->pending
 void trc_sppm_release(trc_ctx* ctx);   // frees ctx->sppm (no-op when absent)
 void trc_denoise_release(trc_ctx* ctx);      // frees ctx->denoise: its G-buffers, planes and history (no-op when absent)
+// smallest textureIndex of the scene's Image materials (~0u: none); recorded by every scene upload (trc_ctx::scene_min_image)
+inline uint32_t trc_scene_min_image(const trc_scene* s) {
+    uint32_t m = ~0u;
+    for (uint32_t i = 0; i < s->n_material; ++i)
+        if (s->materials[i].textureInfo.type == TRC_TEX_IMAGE && s->materials[i].textureInfo.textureIndex < m) m = s->materials[i].textureInfo.textureIndex;
+    return m;
+}
 void trc_denoise_invalidate(trc_ctx* ctx);   // another scene or environment: the G-buffer is stale and the history dropped
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)

@@ -68,8 +68,9 @@ TRC_DEV void depth_grad(const float4* gb, uint32_t W, uint32_t H, uint32_t x, ui
 
 // ---------------------------------------------------------------- G-buffer: the camera pass's primary hit, walked by the
 // production scene_hit (the same instantiation trc_trace_rays' TRC_TRACE_PRODUCTION runs); no RNG is consumed
-template <bool LDS>
-__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb) {
+// TEX: image textures (trc_upload_textures; hit_color<true> over `tt`, which the other instantiations do not read)
+template <bool LDS, bool TEX = false>
+__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt) {
     const DScene& sc = ks.sc;
     const uint32_t* small_base = stage_scene(sc);
     uint32_t* stack = lane_stack(sc);
@@ -95,7 +96,7 @@ __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam
     }
     Shade sh;
     sh.mats = small_base + sc.off_materials;
-    const F3 alb = mat_type(sh, rec.material) == kMatDiffuse ? f3(1.0f) : hit_color(S, sh, rec);     // emitters: 1
+    const F3 alb = mat_type(sh, rec.material) == kMatDiffuse ? f3(1.0f) : hit_color<TEX>(S, sh, rec, &tt);     // emitters: 1
     gb[2 * i] = make_float4(rec.t, rec.sn.x, rec.sn.y, rec.sn.z);
     gb[2 * i + 1] = make_float4(alb.x, alb.y, alb.z, __uint_as_float(rec.material));
 }
@@ -426,8 +427,13 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
         s->gb_cur ^= 1;
         const size_t lds = trc_dyn_lds_bytes(ctx, true);
         const DnCam cam = dn_cam(ctx->cam);
-        if (ctx->lds_scene) hipLaunchKernelGGL(k_gbuffer<true>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur]);
-        else hipLaunchKernelGGL(k_gbuffer<false>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur]);
+        TexTable tt{};
+        if (ctx->tex_active()) { tt.texels = ctx->d_tex_texels; tt.desc = ctx->d_tex_desc; tt.n = ctx->n_tex; }
+        if (ctx->tex_active()) {            // an active image texture (trc_upload_textures): the albedo plane samples it
+            if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
+            else hipLaunchKernelGGL((k_gbuffer<false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
+        } else if (ctx->lds_scene) hipLaunchKernelGGL(k_gbuffer<true>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
+        else hipLaunchKernelGGL(k_gbuffer<false>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
         HIP_TRY(ctx, hipGetLastError());
         s->gb_cam = ctx->cam;
         s->gb_valid = true;

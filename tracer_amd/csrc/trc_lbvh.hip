@@ -666,6 +666,7 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     ctx->lbvh_height = height;
     ctx->lbvh_build_ms = ms;
     ctx->has_scene = true;
+    ctx->scene_min_image = trc_scene_min_image(s);
     ctx->cost_valid = false; ctx->d_last_order = nullptr;      // another scene: the recorded block costs say nothing about it
     return TRC_OK;
 }

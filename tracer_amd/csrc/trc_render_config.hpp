@@ -138,3 +138,11 @@ template <int INTEGRATOR, bool SOBOL>
 __global__ void k_render_pwg(const KRender kp);
 template <bool LDS, int INTEGRATOR, bool SOBOL>
 __global__ void k_render_strip(const KRender kp);
+// image textures (trc_upload_textures): the production kernels of the PCG sampler with hit_color<true>, in the same translation units
+template <bool LDS, int INTEGRATOR>
+__global__ void k_render_tex(const KRender kp);
+template <bool LDS, int INTEGRATOR>
+__global__ void k_render_strip_tex(const KRender kp);
+template <int INTEGRATOR>
+__global__ void k_render_pwg_tex(const KRender kp);
+

@@ -16,7 +16,13 @@
 // of the lane's LDS column `park` (row r at park[r * kBlock]) instead of registers: that many values fewer to carry through the walk and
 // the shading code of every iteration, i.e. fewer spills to scratch -- which on a mesh scene streams through the L2 the node fetches
 // live in, and on the LDS-resident headline scene are issue slots.  Same loads, same arithmetic, same stores per lane.
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, class COUNT = uint32_t>
+// TEX: image textures (trc_upload_textures; hit_color<true>): instantiated only for what a scene with an active image launches --
+// the production kernels under the PCG sampler (k_render_tex, k_render_strip_tex, k_render_pwg_tex) -- so the others stay as they are.
+template <bool TEX, class CX>
+__device__ __forceinline__ void set_ctx_tex(CX& cx, const KRender& kp) {       // TEX: the image table of the launch (PathCtxTex)
+    if constexpr (TEX) { cx.tex.texels = kp.tex_texels; cx.tex.desc = kp.tex_desc; cx.tex.n = kp.n_tex; }
+}
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, class COUNT = uint32_t>
 __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                              uint32_t* ovf, uint32_t* park, const uint32_t slot, const uint32_t lane,
                                              COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt) {
@@ -40,12 +46,13 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
     const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
 
     if (active) {
-        PathCtx cx;
+        PathCtxOf<TEX> cx;
         cx.S = make_scene_ref(sc, small_base);
         cx.S.ovf = ovf;
         cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
         cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
         cx.sh.mats = small_base + sc.off_materials;
+        set_ctx_tex<TEX>(cx, kp);
         cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
         cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
         cx.stack = stack;
@@ -148,8 +155,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
             }
             F3 color;
             const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
-                                      ? path_step<STATS, SOBOL>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, STATS, kVolume, SOBOL, HYB>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                      ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
+                                      : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
             if (finished) finish_sample(color);
         }
         if constexpr (PARK) {       // the loop is left by the last finish_sample only (trc_render launches spp >= 1): what that one would
@@ -184,7 +191,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
 }
 
 // the body of k_render (one one-wavefront workgroup = one entry of the launch list)
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0>
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false>
 __device__ __forceinline__ void render_workgroup(const KRender& kp) {
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
@@ -202,10 +209,10 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp) {
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
-        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt);
+        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt);
         n_rays = park[kParkRays * kBlock]; n_shaded = park[kParkShaded * kBlock];
     } else
-    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt);
+    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
@@ -240,6 +247,9 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp) {
 }
 template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(kBlock, STATS ? 1 : (INTEGRATOR == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES : (INTEGRATOR == TRC_INTEGRATOR_MIS ? (LDS ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (LDS ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL)))) k_render(const KRender kp) { render_workgroup<LDS, STATS, INTEGRATOR, SOBOL>(kp); }
+// ... k_render<LDS, false, INTEGRATOR, false> with image textures
+template <bool LDS, int INTEGRATOR>
+__global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES : (INTEGRATOR == TRC_INTEGRATOR_MIS ? (LDS ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (LDS ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL))) k_render_tex(const KRender kp) { render_workgroup<LDS, false, INTEGRATOR, false, 0, true>(kp); }
 
 // kernelPathTracing on a tree that is READ FROM MEMORY (mesh scenes), production launches of >= 8 spp: persistent
 // workgroups.  With one wavefront per workgroup every wavefront stages its own copy of the top of the tree, and 16-24 copies
@@ -251,57 +261,16 @@ __global__ void __launch_bounds__(kBlock, STATS ? 1 : (INTEGRATOR == TRC_INTEGRA
 // of a mesh ray's steps are deep in the tree, below any prefix.  Workgroup shapes (trc_render_config.hpp): tracePath 4 wavefronts x 7
 // per CU -- seven waves per SIMD at 72 registers, the one shape of 28 wavefronts that packs (round 5; rounds 2-4 ran 12 x 2 and 16 x 2) --,
 // traceMIS 16 x 2 with 8 stack entries per lane in LDS, traceVolume 16 x 1.
+// TEX (image textures): k_render_pwg_tex<INTEGRATOR>, the same body (trc_render_pwg_body.inc) with hit_color<true>
 template <int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRATOR) * pwg_per_cu(INTEGRATOR) / 4) k_render_pwg(const KRender kp) {
-    const DScene& sc = kp.ks.sc;
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(sc.blob);
-        uint4* dst = reinterpret_cast<uint4*>(trc_smem);
-        const uint32_t n16 = sc.lds_dwords >> 2;
-        for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    constexpr bool kHybridStack = hybrid_stack(INTEGRATOR);
-    constexpr uint32_t kRows = pwg_park_rows(INTEGRATOR);       // a wavefront's LDS: stack_lds stack rows, then the park rows (render_block)
-    constexpr bool kPark = kRows != 0u;
-    uint32_t* stack = trc_smem + sc.lds_dwords + wave * (sc.stack_lds + kRows) * kBlock + lane;
-    uint32_t* park = stack + sc.stack_lds * kBlock;
-    uint32_t* ovf = kHybridStack ? kp.stack_ovf + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * sc.stack_ovf_rows * kBlock + lane : nullptr;
-    uint32_t n_paths = 0;
-    TravCounters cnt;
-    counters_zero(cnt);
-    const uint32_t n_entries = kp.n_launch ? *kp.n_launch : kp.n_tiles;
-    uint32_t r_rays, r_shaded;
-    if constexpr (kPark) {
-        park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
-        LdsCount n_rays{park + kParkRays * kBlock}, n_shaded{park + kParkShaded * kBlock};
-        for (;;) {
-            uint32_t slot = 0;
-            if (lane == 0) slot = atomicAdd(kp.queue, 1u);
-            slot = __builtin_amdgcn_readfirstlane(slot);
-            if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt);
-        }
-        r_rays = wave_sum(park[kParkRays * kBlock]); r_shaded = wave_sum(park[kParkShaded * kBlock]);
-    } else {
-        uint32_t n_rays = 0, n_shaded = 0;
-        for (;;) {
-            uint32_t slot = 0;
-            if (lane == 0) slot = atomicAdd(kp.queue, 1u);
-            slot = __builtin_amdgcn_readfirstlane(slot);
-            if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt);
-        }
-        r_rays = wave_sum(n_rays); r_shaded = wave_sum(n_shaded);
-    }
-    const uint32_t r_paths = wave_sum(n_paths);
-    if (lane == 0) {
-        unsigned long long* const stats = stat_row(kp.stats, blockIdx.x * (blockDim.x >> 6) + wave);
-        atomicAdd(&stats[kStatPaths], (unsigned long long)r_paths);
-        atomicAdd(&stats[kStatRays], (unsigned long long)r_rays);
-        atomicAdd(&stats[kStatShaded], (unsigned long long)r_shaded);
-    }
+    constexpr bool TEX = false;
+#include "trc_render_pwg_body.inc"
+}
+template <int INTEGRATOR>
+__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRATOR) * pwg_per_cu(INTEGRATOR) / 4) k_render_pwg_tex(const KRender kp) {
+    constexpr bool SOBOL = false, TEX = true;
+#include "trc_render_pwg_body.inc"
 }
 
 // kernelPathTracing for launches of FEW samples per pixel (the reference's own pattern is one per dispatch): with one 8x8
@@ -310,135 +279,14 @@ __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRAT
 // blocks of the list and every lane walks its own pixel of block after block, so a lane whose pixel is done starts
 // the same pixel of the next block at once (path regeneration across pixels instead of across samples).  The strip
 // is the unit of the adaptive launch order.  Pixels are independent: the frame is k_render's, bit for bit.
+// TEX (image textures): k_render_strip_tex<LDS, INTEGRATOR>, the same body (trc_render_strip_body.inc) with hit_color<true>
 template <bool LDS, int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? 3 : (INTEGRATOR == TRC_INTEGRATOR_PATH ? TRC_STRIP_PATH_WAVES : 4)) k_render_strip(const KRender kp) {
-    const DScene& sc = kp.ks.sc;
-    const uint32_t* small_base = stage_scene(sc);
-    uint32_t* stack = lane_stack(sc);
-    const uint64_t t_start = clock64();
-    const uint32_t canon = kp.order ? kp.order[blockIdx.x] : blockIdx.x;     // strip index
-    const uint32_t lane = threadIdx.x;
-    const uint32_t W = kp.fr.width, H = kp.fr.height;
-    // the strip's pixels form one pool: pixel p = lane (p mod block size) of block (p / block size); a lane whose pixel is
-    // done takes the next unclaimed one, so no lane waits for "its" pixel of the next block while others still trace
-    const uint32_t blk0 = canon * kp.strip;
-    const uint32_t bshift = 2u * kp.blk_shift;                               // log2(pixels per block): 6 or 4
-    const uint32_t pool_end = (min(blk0 + kp.strip, kp.n_tiles) - blk0) << bshift;
-    uint32_t pool_next = 0;                                                  // wave-uniform: next unclaimed pool index
-
-    uint32_t n_rays = 0, n_shaded = 0, n_paths = 0;
-    TravCounters cnt;
-    counters_zero(cnt);
-
-    PathCtx cx;
-    cx.S = make_scene_ref(sc, small_base);
-    constexpr bool kHybridStack = !LDS && hybrid_stack(INTEGRATOR);
-    if (kHybridStack) cx.S.ovf = kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane;
-    cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
-    cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
-    cx.sh.mats = small_base + sc.off_materials;
-    cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
-    cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
-    cx.stack = stack;
-    cx.lvstack = stack;
-    cx.max_depth = kp.max_depth;
-    cx.density = kp.density;
-    cx.dinfo = kp.dinfo;
-    cx.occupancy = kp.occupancy;
-    if (SOBOL) { cx.sobol32 = kp.sobol32; cx.sobol_vdc = kp.sobol_vdc; cx.sobol_m = kp.sobol_m; cx.sobol_res = 1u << kp.sobol_m; }
-
-    PathState ps;
-    Pcg rng;
-    uint4 texel;
-    F3 cached = f3(0);
-    float u = 0, v = 0;
-    uint32_t s = 0, pix = 0;
-    uint64_t state_after_cast = 0;
-    bool alive = false, want = true;                  // want: this lane needs a (new) pixel
-
-    auto begin_sample = [&]() {                       // castRay, then (SOBOL) the sampler of this frame: Render.metal:527-530
-        rng.state = ((uint64_t)texel.z << 32) | texel.w;      // the two words trade roles every frame (B-1)
-        rng.inc = ((uint64_t)texel.x << 32) | texel.y;
-        path_begin(ps, cast_ray(kp.cam, u, v, rng), kp.max_depth);
-        if (SOBOL) {
-            state_after_cast = rng.state;
-            ps.sobol_index = sobol_interval_to_index(cx, (uint64_t)(kp.frame0 + s));
-            ps.sobol_dim = 0;
-        }
-    };
-    // hands pool indices to the lanes that want one (called where the whole wavefront is converged); a lane whose index
-    // falls outside the frame (ragged edge blocks) simply asks again in the next round
-    auto deal_pixels = [&]() {
-        const unsigned long long m = __ballot(want);
-        if (m == 0ull) return;
-        const uint32_t mine = pool_next + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        pool_next += (uint32_t)__popcll(m);
-        if (!want) return;
-        if (mine >= pool_end) { want = false; return; }                        // the pool is empty: this lane is done
-        const uint32_t tile = kp.tiles[blk0 + (mine >> bshift)];
-        const uint32_t l = mine & ((1u << bshift) - 1u), bs = kp.blk_shift;
-        const uint32_t px = ((tile & 0xFFFFu) << bs) + (l & ((1u << bs) - 1u));
-        const uint32_t py = ((tile >> 16) << bs) + (l >> bs);
-        if (px >= W || py >= H) return;                                        // not a pixel: ask again
-        pix = py * W + px;
-        texel = reinterpret_cast<const uint4*>(kp.fr.rng)[pix];
-        const float4 acc = reinterpret_cast<const float4*>(kp.fr.accum)[pix];
-        cached = f3(acc.x, acc.y, acc.z);
-        u = (float)px / (float)W;                                              // no sub-pixel jitter (B-2)
-        v = (float)(py % kp.view_height) / (float)kp.view_height;
-        if (SOBOL) { cx.sobol_xy[0] = px; cx.sobol_xy[1] = py % kp.view_height; }
-        s = 0;
-        want = false;
-        alive = true;
-        begin_sample();
-    };
-    auto finish_sample = [&](F3 color) {
-        const bool bad = is_inf(color.x) || is_nan(color.x) || is_inf(color.y) || is_nan(color.y) ||
-                         is_inf(color.z) || is_nan(color.z);
-        if (bad) color = f3(0);                                         // :537-538
-        const uint32_t frame = kp.frame0 + s;
-        cached = (cached * (float)frame + color) / (float)(frame + 1);  // running mean, :540-541
-        if (SOBOL) rng.state = state_after_cast;
-        texel.y = (uint32_t)rng.state; texel.x = (uint32_t)(rng.state >> 32);
-        texel.w = (uint32_t)rng.inc;   texel.z = (uint32_t)(rng.inc >> 32);
-        n_paths++;
-        if (++s == kp.spp) {                                            // pixel done: write it back, take the next block's
-            float4 out; out.x = cached.x; out.y = cached.y; out.z = cached.z; out.w = 1.0f;
-            reinterpret_cast<float4*>(kp.fr.accum)[pix] = out;
-            reinterpret_cast<uint4*>(kp.fr.rng)[pix] = texel;
-            alive = false;
-            want = true;
-        } else {
-            begin_sample();
-        }
-    };
-
-    for (;;) {                                        // wave-uniform loop: every lane stays in it until nobody has or wants work
-        deal_pixels();
-        if (__ballot(alive || want) == 0ull) break;
-        if (alive) {
-            constexpr bool kVolume = INTEGRATOR == TRC_INTEGRATOR_VOLUME;
-            constexpr int kDefer = LDS ? TRC_DEFER_LDS : TRC_DEFER_GLOBAL;
-            bool hitted = true;
-            if (!(kVolume && TRC_TRACK_SLICE > 0 && ps.tracking)) {       // render_block's loop above
-                n_rays++;
-                hitted = scene_hit<LDS, false, false, false, kVolume, kHybridStack, kDefer>(cx.S, cx.root_min, cx.root_max, ps.ray, ps.rec, FLT_MAX,
-                                                                          cx.stack, cx.lvstack, cnt);
-            }
-            F3 color;
-            const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
-                                      ? path_step<false, SOBOL>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, false, kVolume, SOBOL, kHybridStack>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
-            if (finished) finish_sample(color);
-        }
-    }
-    uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
-    if (lane == 0) {
-        kp.block_cost[canon] = (uint32_t)min((unsigned long long)(clock64() - t_start) / kp.cost_div, 0xFFFFFFull);
-        unsigned long long* const stats = stat_row(kp.stats, blockIdx.x);
-        atomicAdd(&stats[kStatPaths], (unsigned long long)r_paths);
-        atomicAdd(&stats[kStatRays], (unsigned long long)r_rays);
-        atomicAdd(&stats[kStatShaded], (unsigned long long)r_shaded);
-    }
+    constexpr bool TEX = false;
+#include "trc_render_strip_body.inc"
 }
-
+template <bool LDS, int INTEGRATOR>
+__global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? 3 : (INTEGRATOR == TRC_INTEGRATOR_PATH ? TRC_STRIP_PATH_WAVES : 4)) k_render_strip_tex(const KRender kp) {
+    constexpr bool SOBOL = false, TEX = true;
+#include "trc_render_strip_body.inc"
+}

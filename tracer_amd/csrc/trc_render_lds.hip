@@ -18,3 +18,6 @@ __global__ void __launch_bounds__(kBlock, TRC_PATH_WAVES_DENSE) k_render_dense(c
 // exactly the instantiations launch_render<> picks from (trc_abi.hip)
 TRC_INST_RENDER(false, TRC_INTEGRATOR_PATH, false);   TRC_INST_RENDER(true, TRC_INTEGRATOR_PATH, false);   TRC_INST_RENDER(false, TRC_INTEGRATOR_PATH, true);
 TRC_INST_STRIP(TRC_INTEGRATOR_PATH, false);  TRC_INST_STRIP(TRC_INTEGRATOR_PATH, true);
+// image textures (trc_upload_textures): what a textured scene launches; k_render_dense has no such twin (k_render_tex is taken instead)
+template __global__ void k_render_tex<true, TRC_INTEGRATOR_PATH>(const KRender);
+template __global__ void k_render_strip_tex<true, TRC_INTEGRATOR_PATH>(const KRender);

@@ -11,3 +11,8 @@ TRC_INST_RENDER(false, TRC_INTEGRATOR_MIS, false);    TRC_INST_RENDER(true, TRC_
 TRC_INST_RENDER(false, TRC_INTEGRATOR_VOLUME, false); TRC_INST_RENDER(true, TRC_INTEGRATOR_VOLUME, false);
 TRC_INST_STRIP(TRC_INTEGRATOR_MIS, false);   TRC_INST_STRIP(TRC_INTEGRATOR_MIS, true);
 TRC_INST_STRIP(TRC_INTEGRATOR_VOLUME, false);
+// image textures (trc_upload_textures)
+template __global__ void k_render_tex<true, TRC_INTEGRATOR_MIS>(const KRender);
+template __global__ void k_render_tex<true, TRC_INTEGRATOR_VOLUME>(const KRender);
+template __global__ void k_render_strip_tex<true, TRC_INTEGRATOR_MIS>(const KRender);
+template __global__ void k_render_strip_tex<true, TRC_INTEGRATOR_VOLUME>(const KRender);

@@ -15,3 +15,7 @@ TRC_INST_RENDER(false, TRC_INTEGRATOR_PATH, false);   TRC_INST_RENDER(true, TRC_
 TRC_INST_STRIP(TRC_INTEGRATOR_PATH, false);  TRC_INST_STRIP(TRC_INTEGRATOR_PATH, true);
 template __global__ void k_render_pwg<TRC_INTEGRATOR_PATH, false>(const KRender);
 template __global__ void k_render_pwg<TRC_INTEGRATOR_PATH, true>(const KRender);
+// image textures (trc_upload_textures)
+template __global__ void k_render_tex<false, TRC_INTEGRATOR_PATH>(const KRender);
+template __global__ void k_render_strip_tex<false, TRC_INTEGRATOR_PATH>(const KRender);
+template __global__ void k_render_pwg_tex<TRC_INTEGRATOR_PATH>(const KRender);

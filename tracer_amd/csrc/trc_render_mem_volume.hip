@@ -13,3 +13,7 @@
 TRC_INST_RENDER(false, TRC_INTEGRATOR_VOLUME, false); TRC_INST_RENDER(true, TRC_INTEGRATOR_VOLUME, false);
 TRC_INST_STRIP(TRC_INTEGRATOR_VOLUME, false);
 template __global__ void k_render_pwg<TRC_INTEGRATOR_VOLUME, false>(const KRender);
+// image textures (trc_upload_textures)
+template __global__ void k_render_tex<false, TRC_INTEGRATOR_VOLUME>(const KRender);
+template __global__ void k_render_strip_tex<false, TRC_INTEGRATOR_VOLUME>(const KRender);
+template __global__ void k_render_pwg_tex<TRC_INTEGRATOR_VOLUME>(const KRender);

@@ -150,6 +150,7 @@ inline void fill_primitives(const trc_scene* s, const DScene& sc, uint32_t* blob
         q[2] = f2u(m.textureInfo.albedo.x); q[3] = f2u(m.textureInfo.albedo.y); q[4] = f2u(m.textureInfo.albedo.z);
         q[5] = m.specular ? 1u : 0u;
         q[6] = (uint32_t)m.medium;
+        q[7] = m.textureInfo.textureIndex;      // read by hit_color<true> only (image textures, trc_upload_textures)
     }
 }
 

@@ -64,6 +64,9 @@ struct KSppm {
     const float4* cells;     // gather table of k_sppm_table: array A (1 float4 per hash cell + 1 for out-of-range reads), then array B (2 each)
     DComplex* cx;
     unsigned long long* stats;   // ctx counters: rays += Scene::hit calls of the camera and photon passes
+    const float* tex_texels;     // image textures (k_sppm_*_tex only; trc_ctx: d_tex_*)
+    const uint4* tex_desc;
+    uint32_t n_tex;
 };
 
 constexpr uint32_t kPhotonSlack = 64u * kBlock;      // records past the 512 x 512 photons in the buffers the ranks all-gather into: an uneven split pads its last chunks
@@ -151,9 +154,15 @@ struct SppmCtx {
     uint32_t* stack;
     uint32_t* lvstack;
 };
-__device__ __forceinline__ SppmCtx make_sppm_ctx(const KSppm& kp, const uint32_t* small_base) {
+struct SppmCtxTex : SppmCtx { TexTable tex; };      // image textures (TEX instantiations): the others keep SppmCtx's layout
+template <bool TEX> using SppmCtxOf = typename std::conditional<TEX, SppmCtxTex, SppmCtx>::type;
+template <bool TEX> __device__ __forceinline__ const TexTable* sppm_tex(const SppmCtx& cx) {
+    if constexpr (TEX) return &static_cast<const SppmCtxTex&>(cx).tex; else return nullptr;
+}
+template <bool TEX = false>
+__device__ __forceinline__ SppmCtxOf<TEX> make_sppm_ctx(const KSppm& kp, const uint32_t* small_base) {
     const DScene& sc = kp.ks.sc;
-    SppmCtx cx;
+    SppmCtxOf<TEX> cx;
     cx.S = make_scene_ref(sc, small_base);
     cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
     cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
@@ -162,6 +171,7 @@ __device__ __forceinline__ SppmCtx make_sppm_ctx(const KSppm& kp, const uint32_t
     cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
     cx.stack = lane_stack(sc);
     cx.lvstack = lane_lvstack(sc);
+    if constexpr (TEX) { cx.tex.texels = kp.tex_texels; cx.tex.desc = kp.tex_desc; cx.tex.n = kp.n_tex; }
     return cx;
 }
 template <bool ALL_LDS>
@@ -181,10 +191,11 @@ __device__ __forceinline__ bool sppm_hit(const SppmCtx& cx, const Ray& ray, HitR
 #ifndef TRC_SPPM_REFINE_WAVES
 #define TRC_SPPM_REFINE_WAVES 5
 #endif
-template <bool ALL_LDS>
+// TEX: image textures (trc_upload_textures; hit_color<true>)
+template <bool ALL_LDS, bool TEX = false>
 __global__ void __launch_bounds__(kBlock, TRC_SPPM_CAMERA_WAVES) k_sppm_camera(const KSppm kp) {
     const uint32_t* small_base = stage_scene(kp.ks.sc);
-    const SppmCtx cx = make_sppm_ctx(kp, small_base);
+    const SppmCtxOf<TEX> cx = make_sppm_ctx<TEX>(kp, small_base);
     const uint32_t tile = kp.tiles[blockIdx.x];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t px = (tile & 0xFFFFu) * 8u + (lane & 7u);
@@ -228,7 +239,7 @@ __global__ void __launch_bounds__(kBlock, TRC_SPPM_CAMERA_WAVES) k_sppm_camera(c
             F3 minus_d = -ray.d;
             F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
             F2 uu; uu.x = pcg_float(rng); uu.y = pcg_float(rng);
-            F3 attenuation = material_S_F(mtype, hit_color(cx.S, cx.sh, rec), wo, wi, uu, bxPDF);
+            F3 attenuation = material_S_F(mtype, hit_color<TEX>(cx.S, cx.sh, rec, sppm_tex<TEX>(cx)), wo, wi, uu, bxPDF);
             if (bxPDF <= 0) break;
             F3 pn = rec.sn * copysignf(1.0f, wi.z);
             F3 _origin = offset_ray(rec.p, pn);
@@ -291,10 +302,10 @@ __global__ void __launch_bounds__(256) k_sppm_radius(float4* flux_radius, uint32
 }
 
 // kernelPhotonRecording, Photon.metal:286-355 + tracePhotonRecord :220-285
-template <bool ALL_LDS>
+template <bool ALL_LDS, bool TEX = false>    // TEX: image textures
 __global__ void __launch_bounds__(kBlock, TRC_SPPM_PHOTON_WAVES) k_sppm_photon(const KSppm kp) {
     const uint32_t* small_base = stage_scene(kp.ks.sc);
-    const SppmCtx cx = make_sppm_ctx(kp, small_base);
+    const SppmCtxOf<TEX> cx = make_sppm_ctx<TEX>(kp, small_base);
     const uint32_t idx = kp.photon_first + blockIdx.x * kBlock + threadIdx.x;     // grid covers exactly this rank's photon range
     uint32_t n_rays = 0;
     trc_PhotonRecord& slot = kp.pho_rec[idx];
@@ -335,7 +346,7 @@ __global__ void __launch_bounds__(kBlock, TRC_SPPM_PHOTON_WAVES) k_sppm_photon(c
             F3 minus_d = -ray.d;
             F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
             F2 uu; uu.x = pcg_float(rng); uu.y = pcg_float(rng);
-            F3 attenuation = material_S_F(mtype, hit_color(cx.S, cx.sh, rec), wo, wi, uu, bxPDF);
+            F3 attenuation = material_S_F(mtype, hit_color<TEX>(cx.S, cx.sh, rec, sppm_tex<TEX>(cx)), wo, wi, uu, bxPDF);
             if (bxPDF <= 0) alive = false;
             else {
                 ratio = ratio * (attenuation / fmaxf(FLT_EPSILON, bxPDF));
@@ -714,6 +725,8 @@ trc_status trc_sppm_frames(trc_ctx* ctx, uint32_t n_frames) {
     kp.canvas_rng = ctx->d_rng; kp.accum = ctx->d_accum; kp.photon_rng = s->d_photon_rng;
     kp.vp = kp.vp_prev = s->vp[s->cur]; kp.pho_rec = s->d_pho; kp.mark = s->d_mark; kp.count = s->d_count; kp.cells = s->d_cells; kp.cx = s->d_cx;
     kp.stats = ctx->d_stats;
+    const bool tex = ctx->tex_active();         // an active image texture: k_sppm_camera / _photon<..., true>
+    if (tex) { kp.tex_texels = ctx->d_tex_texels; kp.tex_desc = ctx->d_tex_desc; kp.n_tex = ctx->n_tex; }
     const size_t lds = trc_dyn_lds_bytes(ctx, false);
     const bool all_lds = ctx->lds_scene;
     // a frame that fails after its first launch leaves RNG texels advanced and a camera pass possibly in flight: no
@@ -725,7 +738,10 @@ trc_status trc_sppm_frames(trc_ctx* ctx, uint32_t n_frames) {
     };
     auto camera_launch = [&](const KSppm& k, hipStream_t st) {
         if (!has_tiles) return;
-        if (all_lds) hipLaunchKernelGGL((k_sppm_camera<true>), dim3(ctx->n_tiles), dim3(kBlock), lds, st, k);
+        if (tex) {
+            if (all_lds) hipLaunchKernelGGL((k_sppm_camera<true, true>), dim3(ctx->n_tiles), dim3(kBlock), lds, st, k);
+            else hipLaunchKernelGGL((k_sppm_camera<false, true>), dim3(ctx->n_tiles), dim3(kBlock), lds, st, k);
+        } else if (all_lds) hipLaunchKernelGGL((k_sppm_camera<true>), dim3(ctx->n_tiles), dim3(kBlock), lds, st, k);
         else hipLaunchKernelGGL((k_sppm_camera<false>), dim3(ctx->n_tiles), dim3(kBlock), lds, st, k);
     };
     // The camera pass of an odd frame depends on nothing the photon / refine passes produce (its RNG texels, the scene,
@@ -777,6 +793,10 @@ trc_status trc_sppm_frames(trc_ctx* ctx, uint32_t n_frames) {
             (void)hipEventRecord(seg[0], ctx->stream);
         }
         if (mine == 0) {}
+        else if (tex) {
+            if (all_lds) hipLaunchKernelGGL((k_sppm_photon<true, true>), dim3(mine / kBlock), dim3(kBlock), lds, ctx->stream, kp);
+            else hipLaunchKernelGGL((k_sppm_photon<false, true>), dim3(mine / kBlock), dim3(kBlock), lds, ctx->stream, kp);
+        }
         else if (all_lds) hipLaunchKernelGGL((k_sppm_photon<true>), dim3(mine / kBlock), dim3(kBlock), lds, ctx->stream, kp);
         else hipLaunchKernelGGL((k_sppm_photon<false>), dim3(mine / kBlock), dim3(kBlock), lds, ctx->stream, kp);
         if (timing) (void)hipEventRecord(seg[1], ctx->stream);

@@ -116,12 +116,14 @@ def _load(path, hooks=False):
     L.trc_tonemap_denoised.argtypes = [vp, vp, C.POINTER(C.c_float)]
     L.trc_download_gbuffer.argtypes = [vp, vp]
     L.trc_denoise_reset.argtypes = [vp]
+    L.trc_upload_textures.argtypes = [vp, C.POINTER(abi.Image), u32]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
         L.trc_div_by_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
         L.trc_unary_test.argtypes = [vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32)]
         L.trc_debug_denoise_state.argtypes = [vp, vp, vp, vp]
+        L.trc_texture_sample_test.argtypes = [vp, u32, vp, C.c_size_t, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -186,6 +188,25 @@ class Tracer:
         assert rgb.dtype == np.float32 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.flags.c_contiguous
         self._check(self._L.trc_set_environment_map(self._h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data),
                     "trc_set_environment_map")
+
+    def upload_textures(self, images):
+        """Image textures: a list of (h, w, 3) float32 arrays, rows bottom-up (what host.load_png returns); a material with
+        textureInfo.type == TEX_IMAGE samples image textureInfo.textureIndex.  An empty list (or None) clears them."""
+        images = [np.ascontiguousarray(a, dtype=np.float32) for a in (images or [])]
+        for a in images:
+            assert a.ndim == 3 and a.shape[2] == 3, a.shape
+        arr = (abi.Image * max(1, len(images)))()
+        for k, a in enumerate(images):
+            arr[k].width, arr[k].height = a.shape[1], a.shape[0]
+            arr[k].rgb = a.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self._L.trc_upload_textures(self._h, arr if images else None, len(images)), "trc_upload_textures")
+
+    def texture_sample(self, index, uv):
+        """hooks build only: the render kernels' lookup of image `index` at (n, 2) float32 uv -> (n, 3) float32."""
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        out = np.empty((uv.shape[0], 3), dtype=np.float32)
+        self._check(self._L.trc_texture_sample_test(self._h, index, uv.ctypes.data, uv.shape[0], out.ctypes.data), "trc_texture_sample_test")
+        return out
 
     def tonemap(self):
         """fragmentShader's auto-exposure + ACES on the accumulator -> ((H, W, 4) uint8, rows top-down; exposure)."""

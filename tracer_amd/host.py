@@ -58,6 +58,8 @@ def lib():
         L.trc_host_mesh_load_ply.restype = C.c_int32
         L.trc_host_load_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float))]
         L.trc_host_load_hdr.restype = C.c_int32
+        L.trc_host_load_png.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float))]
+        L.trc_host_load_png.restype = C.c_int32
         L.trc_host_mesh_make_ball.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_void_p)]
         L.trc_host_mesh_make_ball.restype = C.c_int32
         L.trc_host_mesh_from_arrays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
@@ -269,6 +271,18 @@ def load_hdr(path):
     w, h = C.c_uint32(), C.c_uint32()
     p = C.POINTER(C.c_float)()
     _check(lib().trc_host_load_hdr(os.fsencode(path), C.byref(w), C.byref(h), C.byref(p)), f"trc_host_load_hdr({path})")
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).astype(np.float32).copy()
+    finally:
+        lib().trc_host_free(p)
+
+
+def load_png(path):
+    """PNG (8-bit grey / grey + alpha / RGB / RGBA) -> (h, w, 3) float32 = byte / 255, rows bottom-up: what Tracer.upload_textures
+    takes (trc_host_load_png)."""
+    w, h = C.c_uint32(), C.c_uint32()
+    p = C.POINTER(C.c_float)()
+    _check(lib().trc_host_load_png(os.fsencode(path), C.byref(w), C.byref(h), C.byref(p)), f"trc_host_load_png({path})")
     try:
         return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).astype(np.float32).copy()
     finally:
