@@ -924,70 +924,26 @@ trc_status ensure_sobol_tables(trc_ctx* ctx, uint32_t m) {
     return TRC_OK;
 }
 
-template <bool LDS>
-void launch_render(trc_ctx* ctx, const KRender& kp, bool stats, uint32_t integrator, size_t lds, uint32_t n_workgroups, bool dense = false) {
-    dim3 grid(n_workgroups), block(kBlock);
-    if (dense) { hipLaunchKernelGGL(k_render_dense, grid, block, lds, ctx->stream, kp); return; }
-    if (kp.strip > 1) {                      // few samples per pixel: a strip of blocks per wavefront (production kernels)
-        dim3 sgrid((ctx->n_tiles + kp.strip - 1) / kp.strip);
-        if (kp.tex_desc) {                   // an active image texture (trc_upload_textures; never with Sobol' or statistics)
-            if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_VOLUME>), sgrid, block, lds, ctx->stream, kp);
-            else if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_MIS>), sgrid, block, lds, ctx->stream, kp);
-            else hipLaunchKernelGGL((k_render_strip_tex<LDS, TRC_INTEGRATOR_PATH>), sgrid, block, lds, ctx->stream, kp);
-        } else if (kp.sobol32) {
-            if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_MIS, true>), sgrid, block, lds, ctx->stream, kp);
-            else hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_PATH, true>), sgrid, block, lds, ctx->stream, kp);
-        } else if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_VOLUME, false>), sgrid, block, lds, ctx->stream, kp);
-        else if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_MIS, false>), sgrid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render_strip<LDS, TRC_INTEGRATOR_PATH, false>), sgrid, block, lds, ctx->stream, kp);
-        return;
-    }
-    if (kp.tex_desc) {                       // an active image texture: k_render<LDS, false, integrator, false> with hit_color<true>
-        if (integrator == TRC_INTEGRATOR_VOLUME) hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_VOLUME>), grid, block, lds, ctx->stream, kp);
-        else if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_MIS>), grid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render_tex<LDS, TRC_INTEGRATOR_PATH>), grid, block, lds, ctx->stream, kp);
-    } else if (kp.sobol32) {                 // TRC_FLAG_SOBOL (production kernels of tracePath / traceMIS only)
-        if (integrator == TRC_INTEGRATOR_MIS) hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_MIS, true>), grid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_PATH, true>), grid, block, lds, ctx->stream, kp);
-    } else if (integrator == TRC_INTEGRATOR_VOLUME) {
-        if (stats) hipLaunchKernelGGL((k_render<LDS, true, TRC_INTEGRATOR_VOLUME>), grid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_VOLUME>), grid, block, lds, ctx->stream, kp);
-    } else if (integrator == TRC_INTEGRATOR_MIS) {
-        if (stats) hipLaunchKernelGGL((k_render<LDS, true, TRC_INTEGRATOR_MIS>), grid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_MIS>), grid, block, lds, ctx->stream, kp);
-    } else {
-        if (stats) hipLaunchKernelGGL((k_render<LDS, true, TRC_INTEGRATOR_PATH>), grid, block, lds, ctx->stream, kp);
-        else hipLaunchKernelGGL((k_render<LDS, false, TRC_INTEGRATOR_PATH>), grid, block, lds, ctx->stream, kp);
-    }
+// The render kernels a scene's launches pick from (trc_render_config.hpp: one table per tree residence and integrator)
+const RenderKernels& render_family(bool lds_scene, uint32_t integrator) {
+    static const RenderKernels* const lds[3] = {&render_lds_path, &render_lds_mis, &render_lds_volume};
+    static const RenderKernels* const mem[3] = {&render_mem_path, &render_mem_mis, &render_mem_volume};
+    return *(lds_scene ? lds : mem)[integrator];
 }
 
-// persistent workgroups (k_render_pwg): grid = workgroups the GPU holds at once, block = the workgroup's wavefronts
-// TEX: the image-texture twin k_render_pwg_tex (never with SOBOL), whose grant is bit 8 + INTEGRATOR
-template <int INTEGRATOR, bool SOBOL, bool TEX = false>
-hipError_t launch_pwg_one(trc_ctx* ctx, const KRender& kp, uint32_t grid, size_t lds) {
-    static_assert(!(SOBOL && TEX), "no Sobol' twin of the texture kernels");
-    const void* const kern = TEX ? reinterpret_cast<const void*>(&k_render_pwg_tex<INTEGRATOR>) : reinterpret_cast<const void*>(&k_render_pwg<INTEGRATOR, SOBOL>);
-    // more than 64 KB of dynamic LDS has to be asked for once per kernel AND per device (the attribute is set on the
-    // current device's copy of the function): remembered in the context, which is bound to one device
-    const uint32_t bit = 1u << (TEX ? 8 + INTEGRATOR : INTEGRATOR * 2 + (SOBOL ? 1 : 0));
-    if (lds > 64 * 1024 && !(ctx->pwg_lds_granted & bit)) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+// One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
+// device (the attribute is set on the current device's copy of the function): remembered in the context, which is bound to one device.
+hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, uint32_t grid, uint32_t block, size_t lds) {
+    const void* const fn = reinterpret_cast<const void*>(kern.fn);
+    if (lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         if (e != hipSuccess) return e;
-        ctx->pwg_lds_granted |= bit;
+        ctx->lds_granted.push_back(fn);
     }
-    if (TEX) hipLaunchKernelGGL((k_render_pwg_tex<INTEGRATOR>), dim3(grid), dim3(64 * pwg_waves(INTEGRATOR)), lds, ctx->stream, kp);
-    else hipLaunchKernelGGL((k_render_pwg<INTEGRATOR, SOBOL>), dim3(grid), dim3(64 * pwg_waves(INTEGRATOR)), lds, ctx->stream, kp);
-    return hipSuccess;
-}
-hipError_t launch_render_pwg(trc_ctx* ctx, const KRender& kp, uint32_t integrator, uint32_t grid, size_t lds) {
-    if (kp.tex_desc) return integrator == TRC_INTEGRATOR_VOLUME ? launch_pwg_one<TRC_INTEGRATOR_VOLUME, false, true>(ctx, kp, grid, lds)
-                          : integrator == TRC_INTEGRATOR_MIS ? launch_pwg_one<TRC_INTEGRATOR_MIS, false, true>(ctx, kp, grid, lds)
-                                                             : launch_pwg_one<TRC_INTEGRATOR_PATH, false, true>(ctx, kp, grid, lds);
-    if (kp.sobol32) return integrator == TRC_INTEGRATOR_MIS ? launch_pwg_one<TRC_INTEGRATOR_MIS, true>(ctx, kp, grid, lds)
-                                                            : launch_pwg_one<TRC_INTEGRATOR_PATH, true>(ctx, kp, grid, lds);
-    if (integrator == TRC_INTEGRATOR_VOLUME) return launch_pwg_one<TRC_INTEGRATOR_VOLUME, false>(ctx, kp, grid, lds);
-    if (integrator == TRC_INTEGRATOR_MIS) return launch_pwg_one<TRC_INTEGRATOR_MIS, false>(ctx, kp, grid, lds);
-    return launch_pwg_one<TRC_INTEGRATOR_PATH, false>(ctx, kp, grid, lds);
+    void* args[] = {const_cast<KRender*>(&kp)};
+    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(block), args, lds, ctx->stream);
+    const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
+    return e != hipSuccess ? e : last;
 }
 
 }  // namespace
@@ -1466,7 +1422,6 @@ trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, f
     (void)hipFree(d_sums); (void)hipFree(d_out);
     return st;
 }
-extern "C" {
 
 // One pass of kernelPathTracing over the caller's share of the frame.  `inner`: this pass is one half of a first launch that
 // trc_render split in two (below).
@@ -1482,7 +1437,8 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner);
 // away, no pixel changes; the only price is the head's own short tail.  Knob no_cold_probe switches it off.
 constexpr uint32_t kPlanSettled = 8, kPlanReuse = 3;   // a settled list re-plans every fourth launch
 constexpr uint32_t kColdHeadSpp = 8;           // >= 8: the head must run the same kernel and block list as the rest (k_render_strip below)
-static trc_status render_check(trc_ctx* ctx, const trc_params* p) {
+// `sobol_m` (TRC_FLAG_SOBOL): where the view's log2Resolution goes
+static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobol_m = nullptr) {
     if (!ctx || !p) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return fail(ctx, TRC_ERR_NO_SCENE, "trc_render before trc_upload_scene");
     if (!ctx->d_accum) return fail(ctx, TRC_ERR_NO_FRAME, "trc_render before trc_resize");
@@ -1499,10 +1455,12 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p) {
             return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: tracePath / traceMIS, production kernels only");
         if (2ull * p->max_depth > TRC_SOBOL_DIMS)
             return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: 2 * max_depth exceeds the 40 generated dimensions");
+        // resolution = RoundUpPow2(max(wh.x, wh.y)) of the view, log2Resolution = Log2Int(resolution) (SobolSampler.hh:56-58)
         uint32_t m = 0;
         const uint32_t vh = (p->view_height != 0 && p->view_height < ctx->height) ? p->view_height : ctx->height;
         while ((1u << m) < std::max(ctx->width, vh)) ++m;
         if (m > TRC_SOBOL_MAX_LOG2RES) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: frame too large");
+        if (sobol_m) *sobol_m = m;
     }
     return TRC_OK;
 }
@@ -1517,7 +1475,6 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p) {
 // displays every frame (one trc_render, one trc_tonemap) gets exactly the launches it asked for; one that renders a run of
 // samples before it looks gets them at the fused rate: 64 x 1 spp 34.8 -> 2x.x ms.  Knob no_coalesce switches it off.
 constexpr uint32_t kCoalesceBelow = 8, kCoalesceUpTo = 16;
-}  // extern "C" (trc_flush is internal: C++ linkage, declared in trc_ctx.hpp)
 trc_status trc_flush(trc_ctx* ctx) {
     if (!ctx || !ctx->has_deferred) return TRC_OK;
     ctx->has_deferred = false;
@@ -1553,53 +1510,68 @@ trc_status trc_render(trc_ctx* ctx, const trc_params* p) {
     return render_pass(ctx, p, false);
 }
 
-static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
-    { const trc_status st = render_check(ctx, p); if (st != TRC_OK) return st; }
-    const uint32_t nranks = p->tile_nranks ? p->tile_nranks : 1;
-    if (p->spp == 0) return TRC_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    collect_finished_events(ctx);        // before any launch of this call: it may consume a "not ready" sticky error
+}  // extern "C"
 
-    // Launch geometry.  One 8x8 block per wavefront fills the GPU when there are many more blocks than wavefront slots
-    // (32 400 blocks for 4 096 slots at 1080p).  A rank that owns 1/N of the frame (strong scaling) has about one block
-    // per slot: the launch then lasts as long as its slowest wavefront, and a wavefront is as slow as the union of its
-    // 64 pixels' branches.  4x4 blocks on 16 lanes give 4x the wavefronts, each with a quarter of the pixels to wait
-    // for -- the same pixels, the same arithmetic per pixel (TRC_FLAG_SMALL_BLOCKS forces it, _LARGE_BLOCKS forbids it).
-    uint32_t blk_shift = 3;
-    const uint64_t blocks8 = (uint64_t)((ctx->width + 7) / 8) * ((ctx->height + 7) / 8) / nranks;
-    const bool fits = ctx->width <= 65535u * 4u && ctx->height <= 65535u * 4u;
-    if ((p->flags & TRC_FLAG_SMALL_BLOCKS) && fits) blk_shift = 2;
-    if (ctx->knobs.force_blk_shift > 0) blk_shift = std::min(3u, (uint32_t)ctx->knobs.force_blk_shift - 1u);   // measurement knob: 2^k x 2^k pixel blocks
-    { trc_status ts = trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift); if (ts != TRC_OK) return ts; }
-    if (ctx->n_tiles == 0) return TRC_OK;
+// ----------------------------------------------------------------------- render_pass, step by step
+// What render_pass decides for one launch.  Each step reads what the steps before it decided.
+struct RenderLaunch {
+    KRender kp{};                       // the kernel's parameters
+    bool stats = false, sobol = false;  // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL
+    bool fits = false;                  // launch_geometry: the frame's edges allow 4x4 blocks ...
+    uint64_t blocks8 = 0;               // ... 8x8 blocks in this rank's share
+    bool quarters_ok = false;           // ... the list's blocks are 8x8: costs live in kCostSlots slots per block
+    bool dense = false, pwg = false;    // choose_kernel: k_render_dense, persistent workgroups ...
+    RenderKernel kern{};                // ... the entry of the kernel table that runs
+    uint32_t wave_slots = 0;            // ... wavefront slots of the split plan's model
+    uint32_t pwg_waves = 0;             // ... wavefronts per persistent workgroup
+    size_t lds = 0;                     // ... dynamic LDS per workgroup
+    uint32_t grid_cap = 0;              // schedule_blocks: workgroups of a one-block-per-workgroup launch
+    bool planned = false;               // ... the split plan (or every block as quarters) makes this launch's list
+    uint32_t grid = 0, block = kBlock;  // launch_buffers
+};
 
-    const bool stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
-    const bool sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
-    if (trc_dyn_lds_bytes(ctx, stats) > 160 * 1024) return fail(ctx, TRC_ERR_UNSUPPORTED, "traversal stack exceeds the 160 KB LDS of a CU");
-
-    KRender kp{};
+// The kernel's view of the context and of the call
+static void launch_params(const trc_ctx* ctx, const trc_params* p, KRender& kp) {
     kp.ks = ctx->ks;
     if (ctx->knobs.descend_min > 0) kp.ks.sc.descend_min = (uint32_t)ctx->knobs.descend_min;      // A/B knob
     kp.cam = ctx->cam;
     kp.ambient[0] = ctx->ambient[0]; kp.ambient[1] = ctx->ambient[1]; kp.ambient[2] = ctx->ambient[2];
     kp.env_rgb = ctx->d_envmap; kp.env_w = ctx->env_w; kp.env_h = ctx->env_h;
-    if (ctx->tex_active()) { kp.tex_texels = ctx->d_tex_texels; kp.tex_desc = ctx->d_tex_desc; kp.n_tex = ctx->n_tex; }   // launch_render: the _tex kernels
+    if (ctx->tex_active()) { kp.tex_texels = ctx->d_tex_texels; kp.tex_desc = ctx->d_tex_desc; kp.n_tex = ctx->n_tex; }   // the _tex kernels
     kp.fr.rng = ctx->d_rng; kp.fr.accum = ctx->d_accum; kp.fr.width = ctx->width; kp.fr.height = ctx->height;
     kp.spp = p->spp; kp.max_depth = p->max_depth; kp.frame0 = p->frame0;
     kp.view_height = (p->view_height != 0 && p->view_height < ctx->height) ? p->view_height : ctx->height;
-    kp.tiles = ctx->d_tiles;
-    kp.blk_shift = blk_shift;
     kp.stats = ctx->d_stats;
     // An instrumented launch (one wavefront per SIMD, counters in every loop) is no measurement of the production kernels'
     // blocks: its durations go to a scratch array, and it neither reads nor changes what the context knows about block costs.
     kp.block_cost = (p->flags & TRC_FLAG_COLLECT_STATS) ? ctx->d_cost_scratch : ctx->d_block_cost;
     kp.cost_div = std::max(1u, 4u * std::min(p->spp, 1u << 28));
-    kp.order = nullptr;
+    kp.density = ctx->d_density;
+    kp.dinfo = ctx->dinfo;
+    kp.occupancy = ctx->d_occupancy;
+}
+
+// Launch geometry.  One 8x8 block per wavefront fills the GPU when there are many more blocks than wavefront slots
+// (32 400 blocks for 4 096 slots at 1080p).  A rank that owns 1/N of the frame (strong scaling) has about one block
+// per slot: the launch then lasts as long as its slowest wavefront, and a wavefront is as slow as the union of its
+// 64 pixels' branches.  4x4 blocks on 16 lanes give 4x the wavefronts, each with a quarter of the pixels to wait
+// for -- the same pixels, the same arithmetic per pixel (TRC_FLAG_SMALL_BLOCKS forces it, _LARGE_BLOCKS forbids it).
+static trc_status launch_geometry(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
+    const uint32_t nranks = p->tile_nranks ? p->tile_nranks : 1;
+    uint32_t blk_shift = 3;
+    r.blocks8 = (uint64_t)((ctx->width + 7) / 8) * ((ctx->height + 7) / 8) / nranks;
+    r.fits = ctx->width <= 65535u * 4u && ctx->height <= 65535u * 4u;
+    if ((p->flags & TRC_FLAG_SMALL_BLOCKS) && r.fits) blk_shift = 2;
+    if (ctx->knobs.force_blk_shift > 0) blk_shift = std::min(3u, (uint32_t)ctx->knobs.force_blk_shift - 1u);   // measurement knob: 2^k x 2^k pixel blocks
+    { trc_status ts = trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift); if (ts != TRC_OK) return ts; }
+    KRender& kp = r.kp;
+    kp.tiles = ctx->d_tiles;
+    kp.blk_shift = blk_shift;
     // launches of few samples per pixel give every wavefront a strip of consecutive blocks (k_render_strip); the unit of the
     // adaptive order is then the strip, and durations recorded for another strip length say nothing
     kp.n_tiles = ctx->n_tiles;
     kp.strip = 1;
-    if (!stats) {
+    if (!r.stats) {
         // blocks per wavefront, measured at 1920x1080 (wall ms for 64 samples in launches of 1 / 4 spp) with the pooled
         // pixels of k_render_strip: strip 2: 37.6 / 28.4, 3: 36.6 / 29.7, 4: 37.5 / 31.5, >= 5: 38.8 / 35.6 -- longer strips
         // leave too few workgroups (the frame has 32 400 blocks for 4 096 wavefront slots); one block per wavefront: 80.8 / 33.0
@@ -1609,56 +1581,94 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
         const uint32_t room = ctx->n_tiles / (slots + slots / 2u);          // keep >= 1.5 workgroups per slot
         kp.strip = std::max(1u, std::min(want, room));
     }
-    // Launch list.  (1) Order: most expensive blocks of the previous launch first (longest-processing-time order; cost = the
-    // wavefront's measured duration): a block's samples are a sequential chain, so whatever starts last decides how long
-    // the GPU drains.  Measured: config 2 25.2 -> 22.3 ms (ray counts as the key: 23.7), the 1 M-triangle scene 18.7 ->
-    // 16.8 ms.  (2) Cost-adaptive block size (k_plan_split): the blocks that would decide the launch run as four 4x4
-    // quarters.  Pixels depend on neither.
-    const bool quarters_ok = kp.strip == 1 && blk_shift == 3;             // the list's blocks are 8x8: costs live in 4 slots per block
-    kp.cost_stride = quarters_ok ? kCostSlots : 1u;
-    if (!stats && (ctx->cost_strip != kp.strip || ctx->cost_quarters != quarters_ok)) {
-        ctx->cost_valid = false; ctx->cost_strip = kp.strip; ctx->cost_quarters = quarters_ok; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
+    r.quarters_ok = kp.strip == 1 && blk_shift == 3;
+    kp.cost_stride = r.quarters_ok ? kCostSlots : 1u;
+    return TRC_OK;
+}
+
+// Durations recorded for another strip length, block size or integrator say nothing about this launch's list
+static void drop_stale_costs(trc_ctx* ctx, const trc_params* p, const RenderLaunch& r) {
+    if (r.stats) return;
+    if (ctx->cost_strip != r.kp.strip || ctx->cost_quarters != r.quarters_ok) {
+        ctx->cost_valid = false; ctx->cost_strip = r.kp.strip; ctx->cost_quarters = r.quarters_ok; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
     }
-    if (!stats && ctx->cost_integrator != p->integrator) { ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr; }
-    {
-        const uint32_t head = std::max(kColdHeadSpp, (uint32_t)ctx->knobs.probe_spp);
-        if (!inner && !ctx->cost_valid && !stats && !ctx->knobs.no_cold_probe && !(p->flags & TRC_FLAG_FIXED_ORDER) && kp.strip == 1 &&
-            p->spp >= 2u * head) {
-            // Stages: the cold head, then -- where plenty of samples remain (four times the stage's) -- up to two more passes of
-            // doubling length, each ordered and planned by its predecessor, then the rest.  A 64-sample launch is head + rest
-            // (a third pass costs its drain: 21.8 -> 22.1 ms); a 256-sample launch is 8 + 16 + 32 + 200, which lets the split
-            // plan's K ramp 16 -> 40 -> 76 INSIDE the first launch: config 3 431 -> 362 ms (and 331 at the second launch
-            // instead of 368), config 4 220 -> 210, an eighth of config 3 290 -> 221 (knob head_stages = n caps the passes)
-            trc_params r = *p;
-            uint32_t stage = head, done = 0;
-            const uint32_t max_stages = ctx->knobs.head_stages > 0 ? (uint32_t)ctx->knobs.head_stages : 3u;
-            for (uint32_t k = 0; k < max_stages && p->spp - done >= (k == 0 ? 2u : 4u) * stage; ++k, stage *= 2u) {
-                trc_params h = *p;
-                h.spp = stage; h.frame0 = p->frame0 + done;
-                trc_status st = render_pass(ctx, &h, true);
-                if (st != TRC_OK) return st;
-                ctx->launches--;                   // one trc_render call = one launch in trc_stats
-                if (k == 0) ctx->cost_head_age = 1;
-                done += stage;
-            }
-            r.spp = p->spp - done; r.frame0 = p->frame0 + done;
-            return render_pass(ctx, &r, true);
-        }
+    if (ctx->cost_integrator != p->integrator) { ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr; }
+}
+
+// Samples of the cold head this pass is split into (see kColdHeadSpp), or 0: the pass runs as one launch
+static uint32_t cold_head_spp(const trc_ctx* ctx, const trc_params* p, const RenderLaunch& r, bool inner) {
+    const uint32_t head = std::max(kColdHeadSpp, (uint32_t)ctx->knobs.probe_spp);
+    const bool cold = !inner && !ctx->cost_valid && !r.stats && !ctx->knobs.no_cold_probe && !(p->flags & TRC_FLAG_FIXED_ORDER) && r.kp.strip == 1 &&
+                      p->spp >= 2u * head;
+    return cold ? head : 0u;
+}
+// Stages: the cold head, then -- where plenty of samples remain (four times the stage's) -- up to two more passes of
+// doubling length, each ordered and planned by its predecessor, then the rest.  A 64-sample launch is head + rest
+// (a third pass costs its drain: 21.8 -> 22.1 ms); a 256-sample launch is 8 + 16 + 32 + 200, which lets the split
+// plan's K ramp 16 -> 40 -> 76 INSIDE the first launch: config 3 431 -> 362 ms (and 331 at the second launch
+// instead of 368), config 4 220 -> 210, an eighth of config 3 290 -> 221 (knob head_stages = n caps the passes)
+static trc_status render_cold_head(trc_ctx* ctx, const trc_params* p, uint32_t head) {
+    trc_params r = *p;
+    uint32_t stage = head, done = 0;
+    const uint32_t max_stages = ctx->knobs.head_stages > 0 ? (uint32_t)ctx->knobs.head_stages : 3u;
+    for (uint32_t k = 0; k < max_stages && p->spp - done >= (k == 0 ? 2u : 4u) * stage; ++k, stage *= 2u) {
+        trc_params h = *p;
+        h.spp = stage; h.frame0 = p->frame0 + done;
+        trc_status st = render_pass(ctx, &h, true);
+        if (st != TRC_OK) return st;
+        ctx->launches--;                   // one trc_render call = one launch in trc_stats
+        if (k == 0) ctx->cost_head_age = 1;
+        done += stage;
     }
-    const bool may_split = quarters_ok && !stats && p->spp >= 8 && !ctx->knobs.no_split &&
-                           !(p->flags & (TRC_FLAG_LARGE_BLOCKS | TRC_FLAG_FIXED_ORDER));
-    // wavefront slots of the kernel this launch runs (the plan's model; the launch bounds of k_render / k_render_pwg)
+    r.spp = p->spp - done; r.frame0 = p->frame0 + done;
+    return render_pass(ctx, &r, true);
+}
+
+// Kernel choice: k_render_dense, persistent workgroups, strips or one block per one-wavefront workgroup; the entry of the kernel
+// table that runs it; its LDS (the plan of a tree read from memory, the rows of parked per-pixel state, the bytes per workgroup).
+static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
+    KRender& kp = r.kp;
+    const int integrator = (int)p->integrator;
+    const RenderKernels& family = render_family(ctx->lds_scene, p->integrator);
     // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD
-    const bool dense = ctx->lds_scene && p->integrator == TRC_INTEGRATOR_PATH && !stats && !sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
-                       ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * TRC_PATH_WAVES_DENSE &&
-                       ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)TRC_PARK_DENSE * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * TRC_PATH_WAVES_DENSE <= 160u * 1024u;
-    const uint32_t waves_per_simd = dense ? TRC_PATH_WAVES_DENSE : p->integrator == TRC_INTEGRATOR_PATH ? (ctx->lds_scene ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL)
-                                  : p->integrator == TRC_INTEGRATOR_MIS ? (ctx->lds_scene ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : TRC_VOLUME_WAVES;
-    const uint32_t wave_slots = (uint32_t)ctx->cu_count * 4u * waves_per_simd;
+    r.dense = ctx->lds_scene && integrator == TRC_INTEGRATOR_PATH && !r.stats && !r.sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
+              ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * render_dense.waves &&
+              ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)TRC_PARK_DENSE * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * render_dense.waves <= 160u * 1024u;
+    // wavefront slots of the kernel this launch runs (the split plan's model).  Strip and persistent-workgroup launches count
+    // the one-wavefront kernel's waves, as they always have (a strip launch plans nothing; the persistent ones' default is the same).
+    r.wave_slots = (uint32_t)ctx->cu_count * 4u * (uint32_t)(r.dense ? render_dense : family.one[kVariantPlain]).waves;
+    uint32_t park_rows = r.dense ? (uint32_t)TRC_PARK_DENSE : 0u;      // LDS rows of parked per-pixel state (render_block)
+    const bool mem_plan = !r.stats && !ctx->lds_scene;                   // trees read from memory: the LDS is planned per launch
+    if (mem_plan && !ctx->knobs.no_pwg && kp.strip == 1 && ctx->lds_prefix_ok) {       // no_pwg: A/B knob
+        r.pwg_waves = (uint32_t)pwg_waves(integrator);
+        park_rows = pwg_park_rows(integrator);
+        r.pwg = plan_pwg_lds(ctx, kp.ks.sc, r.pwg_waves, (uint32_t)pwg_per_cu(integrator), hybrid_stack(integrator), pwg_stack_lds_levels(integrator), park_rows);
+        if (!r.pwg) park_rows = 0u;
+    }
+    const RenderVariant variant = ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
+    r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
+    if (!r.kern.fn) return fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
+    if (mem_plan && !r.pwg) plan_launch_lds(ctx, kp.ks.sc, (uint32_t)r.kern.waves, hybrid_stack(integrator));
+    r.lds = r.pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)r.pwg_waves * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
+                  : dyn_lds_bytes(kp.ks.sc, r.stats) + (r.dense ? (size_t)park_rows * kBlock * 4 : 0u);
+    return TRC_OK;
+}
+
+// Block schedule.  (1) Order: most expensive blocks of the previous launch first (longest-processing-time order; cost = the
+// wavefront's measured duration): a block's samples are a sequential chain, so whatever starts last decides how long
+// the GPU drains.  Measured: config 2 25.2 -> 22.3 ms (ray counts as the key: 23.7), the 1 M-triangle scene 18.7 ->
+// 16.8 ms.  (2) Cost-adaptive block size (k_plan_split): the blocks that would decide the launch run as four 4x4
+// quarters.  Pixels depend on neither.
+static trc_status schedule_blocks(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
+    KRender& kp = r.kp;
+    const bool stats = r.stats;
+    const uint32_t wave_slots = r.wave_slots;
+    const bool may_split = r.quarters_ok && !stats && p->spp >= 8 && !ctx->knobs.no_split &&
+                           !(p->flags & (TRC_FLAG_LARGE_BLOCKS | TRC_FLAG_FIXED_ORDER));
     if (!stats) { ctx->last_cost_div = kp.cost_div; ctx->last_wave_slots = wave_slots; }
     if (stats) {} else if (!ctx->cost_valid || (p->flags & TRC_FLAG_FIXED_ORDER) || kp.strip > 1) ctx->plan_streak = 0;      // nothing settled to reuse
-    uint32_t grid_cap = ctx->n_tiles;                                     // workgroups of a one-block-per-workgroup launch
-    bool planned = false;
+    r.grid_cap = ctx->n_tiles;
+    r.planned = false;
     if (stats) {
         // row-major, every block whole, nothing recorded
     } else if (ctx->cost_valid && !(p->flags & TRC_FLAG_FIXED_ORDER) && kp.strip > 1 && ctx->d_last_order && ctx->order_age < 4) {
@@ -1677,7 +1687,7 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
                            ctx->plan_wave_slots == wave_slots && !ctx->knobs.no_plan_reuse;
         if (reuse) {
             ctx->plan_reused++;
-            if (may_split) { kp.order = ctx->d_launch; kp.n_launch = ctx->d_plan + 1; grid_cap = ctx->plan_grid_cap; planned = true; }
+            if (may_split) { kp.order = ctx->d_launch; kp.n_launch = ctx->d_plan + 1; r.grid_cap = ctx->plan_grid_cap; r.planned = true; }
             else kp.order = ctx->d_last_order;
         } else {
         hipEvent_t s0 = get_event(ctx), s1 = get_event(ctx);
@@ -1707,15 +1717,15 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
                                ctx->d_plan, ctx->d_launch, ctx->d_split, ctx->d_whole, ctx->d_qsplit, ctx->d_qwhole, ctx->d_swhole, filtered);
             kp.order = ctx->d_launch;
             kp.n_launch = ctx->d_plan + 1;
-            grid_cap = max_entries;
-            planned = true;
+            r.grid_cap = max_entries;
+            r.planned = true;
         }
         if (s0 && s1 && hipEventRecord(s1, ctx->stream) == hipSuccess) ctx->pending_sched.emplace_back(s0, s1);
         else { if (s0) ctx->event_pool.push_back(s0); if (s1) ctx->event_pool.push_back(s1); }
         ctx->plan_streak = (ctx->plan_n == n && ctx->plan_split_mode == may_split && ctx->plan_wave_slots == wave_slots) ? ctx->plan_streak + 1 : 1;
-        ctx->plan_reused = 0; ctx->plan_n = n; ctx->plan_split_mode = may_split; ctx->plan_wave_slots = wave_slots; ctx->plan_grid_cap = grid_cap;
+        ctx->plan_reused = 0; ctx->plan_n = n; ctx->plan_split_mode = may_split; ctx->plan_wave_slots = wave_slots; ctx->plan_grid_cap = r.grid_cap;
         }
-    } else if (may_split && !ctx->cost_valid && kAutoSmallBlocks && fits && blocks8 <= (uint64_t)ctx->cu_count * 16u &&
+    } else if (may_split && !ctx->cost_valid && kAutoSmallBlocks && r.fits && r.blocks8 <= (uint64_t)ctx->cu_count * 16u &&
                p->integrator == TRC_INTEGRATOR_PATH && ctx->lds_scene) {
         // nothing is known about the blocks yet and there are no more of them than wavefront slots (a small frame, or an
         // eighth of a 1080p frame): every block as quarters -- measured on whole small frames at 64 spp (920 / 2 040 / 3 600
@@ -1723,60 +1733,43 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
         hipLaunchKernelGGL(k_build_launch_all_quarters, dim3((ctx->n_tiles + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_tiles, ctx->d_plan, ctx->d_launch, ctx->d_split, ctx->d_whole, ctx->d_qsplit);
         kp.order = ctx->d_launch;
         kp.n_launch = ctx->d_plan + 1;
-        grid_cap = 4u * ctx->n_tiles;
-        planned = true;
+        r.grid_cap = 4u * ctx->n_tiles;
+        r.planned = true;
     }
-    if (!stats && !ctx->cost_valid && !planned && !kp.order && ctx->d_stale_order && kp.strip == 1 && !(p->flags & TRC_FLAG_FIXED_ORDER))
+    if (!stats && !ctx->cost_valid && !r.planned && !kp.order && ctx->d_stale_order && kp.strip == 1 && !(p->flags & TRC_FLAG_FIXED_ORDER))
         kp.order = ctx->d_stale_order;              // a cold pass after a camera move: the previous view's order beats row-major
     if (!stats) ctx->d_stale_order = nullptr;       // (the buffer belongs to the next sort)
-    if (!stats && !planned && ctx->split_live) {                          // this launch runs every block whole
+    if (!stats && !r.planned && ctx->split_live) {                        // this launch runs every block whole
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_split, 0, (size_t)ctx->n_tiles * 4, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_qsplit, 0, (size_t)ctx->n_tiles * 16, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_cost_est, 0, (size_t)ctx->n_tiles * 4 * kCostSlots, ctx->stream));   // slot 0 held first quarters
     }
-    if (!stats) ctx->split_live = planned;
+    if (!stats) ctx->split_live = r.planned;
     if (!stats && !ctx->cost_valid) HIP_TRY(ctx, hipMemsetAsync(ctx->d_cost_est, 0, (size_t)ctx->n_tiles * 4 * kCostSlots, ctx->stream));
     if (!stats) {
         ctx->cost_head_age = (ctx->cost_valid && ctx->cost_head_age == 1) ? 2 : 0;     // head -> the launch on its costs -> settled
         ctx->cost_valid = true;
     }
-    kp.density = ctx->d_density;
-    kp.dinfo = ctx->dinfo;
-    kp.occupancy = ctx->d_occupancy;
-    if (sobol) {
-        // resolution = RoundUpPow2(max(wh.x, wh.y)) of the view, log2Resolution = Log2Int(resolution) (SobolSampler.hh:56-58)
-        const uint32_t longest = ctx->width > kp.view_height ? ctx->width : kp.view_height;
-        uint32_t m = 0;
-        while ((1u << m) < longest) ++m;
-        if (m > TRC_SOBOL_MAX_LOG2RES) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: frame too large");
-        trc_status ts = ensure_sobol_tables(ctx, m);
+    return TRC_OK;
+}
+
+// Per-launch buffers and the grid: the Sobol' tables, the traversal-stack rows of a tree read from memory (per wavefront), the
+// persistent workgroups' block queue
+static trc_status launch_buffers(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
+    KRender& kp = r.kp;
+    if (r.sobol) {
+        trc_status ts = ensure_sobol_tables(ctx, kp.sobol_m);
         if (ts != TRC_OK) return ts;
         kp.sobol32 = ctx->d_sobol32;
         kp.sobol_vdc = ctx->d_sobol_vdc;
-        kp.sobol_m = m;
     }
-
-    bool pwg = false;
-    uint32_t pwg_waves_n = 0, pwg_grid = 0, park_rows = dense ? (uint32_t)TRC_PARK_DENSE : 0u;      // LDS rows of parked per-pixel state (render_block)
-    if (!stats && !ctx->lds_scene) {
-        const bool strip = kp.strip > 1;
-        const bool is_path = p->integrator == TRC_INTEGRATOR_PATH;
-        const bool hybrid = hybrid_stack((int)p->integrator);
-        if (!ctx->knobs.no_pwg && !strip && ctx->lds_prefix_ok) {                       // no_pwg: A/B knob
-            pwg_waves_n = (uint32_t)pwg_waves((int)p->integrator);
-            const uint32_t per_cu = (uint32_t)pwg_per_cu((int)p->integrator);
-            park_rows = pwg_park_rows((int)p->integrator);
-            pwg = plan_pwg_lds(ctx, kp.ks.sc, pwg_waves_n, per_cu, hybrid, pwg_stack_lds_levels((int)p->integrator), park_rows);
-            if (!pwg) park_rows = 0u;
-            pwg_grid = std::min((uint32_t)ctx->cu_count * per_cu, (grid_cap + pwg_waves_n - 1) / pwg_waves_n);   // small frames: no idle workgroups
-        }
-        if (!pwg) {
-            const uint32_t waves = is_path ? (strip ? TRC_STRIP_PATH_WAVES : TRC_PATH_WAVES_GLOBAL)
-                                 : p->integrator == TRC_INTEGRATOR_MIS ? (strip ? 4 : TRC_MIS_WAVES) : (strip ? 3 : TRC_VOLUME_WAVES);
-            plan_launch_lds(ctx, kp.ks.sc, waves, hybrid);
-        }
+    if (r.pwg) {                    // workgroups the GPU holds at once, of the workgroup's wavefronts
+        r.block = 64u * r.pwg_waves;
+        r.grid = std::min((uint32_t)ctx->cu_count * (uint32_t)pwg_per_cu((int)p->integrator), (r.grid_cap + r.pwg_waves - 1) / r.pwg_waves);   // small frames: no idle workgroups
+    } else r.grid = kp.strip > 1 ? (ctx->n_tiles + kp.strip - 1) / kp.strip : r.grid_cap;
+    if (!r.stats && !ctx->lds_scene) {
         const size_t rows = kp.ks.sc.stack_ovf_rows;
-        const size_t need = rows * kBlock * sizeof(uint32_t) * (pwg ? (size_t)pwg_grid * pwg_waves_n : (size_t)grid_cap);   // rows per wavefront
+        const size_t need = rows * kBlock * sizeof(uint32_t) * (r.pwg ? (size_t)r.grid * r.pwg_waves : (size_t)r.grid_cap);   // rows per wavefront
         if (need > ctx->stack_ovf_bytes) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (ctx->d_stack_ovf) { (void)hipFree(ctx->d_stack_ovf); ctx->d_stack_ovf = nullptr; }
@@ -1786,25 +1779,22 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
         }
         kp.stack_ovf = ctx->d_stack_ovf;
     }
-    const size_t lds = pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)pwg_waves_n * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
-                           : dyn_lds_bytes(kp.ks.sc, stats) + (dense ? (size_t)park_rows * kBlock * 4 : 0u);
-    if (pwg) {
+    if (r.pwg) {
         if (!ctx->d_queue && hipMalloc((void**)&ctx->d_queue, sizeof(uint32_t)) != hipSuccess) return fail(ctx, TRC_ERR_OOM, "hipMalloc block queue");
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
         kp.queue = ctx->d_queue;
     }
+    return TRC_OK;
+}
 
+// The launch, between two events (its duration: trc_stats.kernel_ms, and the block costs' clock)
+static trc_status timed_launch(trc_ctx* ctx, const RenderLaunch& r) {
     HIP_TRY(ctx, hipGetLastError());     // the order / sort / memset launches above
     hipEvent_t e0 = get_event(ctx), e1 = get_event(ctx);
     auto give_back = [&]() { if (e0) ctx->event_pool.push_back(e0); if (e1) ctx->event_pool.push_back(e1); };
     if (!e0 || !e1) { give_back(); return fail(ctx, TRC_ERR_HIP, "hipEventCreate failed"); }
     hipError_t le = hipEventRecord(e0, ctx->stream);
-    if (le == hipSuccess) {
-        if (pwg) le = launch_render_pwg(ctx, kp, p->integrator, pwg_grid, lds);
-        else if (ctx->lds_scene) launch_render<true>(ctx, kp, stats, p->integrator, lds, grid_cap, dense);
-        else launch_render<false>(ctx, kp, stats, p->integrator, lds, grid_cap);
-        if (le == hipSuccess) le = hipGetLastError();
-    }
+    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.grid, r.block, r.lds);
     if (le == hipSuccess) le = hipEventRecord(e1, ctx->stream);
     if (le != hipSuccess) { give_back(); return fail(ctx, TRC_ERR_HIP, std::string("k_render launch: ") + hipGetErrorString(le)); }
     ctx->pending.emplace_back(e0, e1);
@@ -1812,6 +1802,27 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     return TRC_OK;
 }
 
+static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
+    RenderLaunch r;
+    { const trc_status st = render_check(ctx, p, &r.kp.sobol_m); if (st != TRC_OK) return st; }
+    if (p->spp == 0) return TRC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    collect_finished_events(ctx);        // before any launch of this call: it may consume a "not ready" sticky error
+    r.stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
+    r.sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
+    { const trc_status st = launch_geometry(ctx, p, r); if (st != TRC_OK) return st; }
+    if (ctx->n_tiles == 0) return TRC_OK;
+    if (trc_dyn_lds_bytes(ctx, r.stats) > 160 * 1024) return fail(ctx, TRC_ERR_UNSUPPORTED, "traversal stack exceeds the 160 KB LDS of a CU");
+    launch_params(ctx, p, r.kp);
+    drop_stale_costs(ctx, p, r);
+    if (const uint32_t head = cold_head_spp(ctx, p, r, inner)) return render_cold_head(ctx, p, head);
+    { const trc_status st = choose_kernel(ctx, p, r); if (st != TRC_OK) return st; }
+    { const trc_status st = schedule_blocks(ctx, p, r); if (st != TRC_OK) return st; }
+    { const trc_status st = launch_buffers(ctx, p, r); if (st != TRC_OK) return st; }
+    return timed_launch(ctx, r);
+}
+
+extern "C" {
 trc_status trc_synchronize(trc_ctx* ctx) {
     { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
     if (!ctx) return TRC_ERR_INVALID_ARG;

@@ -52,7 +52,7 @@ struct KRender {
     uint32_t* queue;                    // k_render_pwg: next position of the launch order to hand out
     uint32_t blk_shift;                 // log2 of the pixel-block edge of one wavefront: 3 (8x8, 64 lanes) or 2 (4x4, 16 lanes)
     uint32_t n_tiles, strip;            // k_render_strip: blocks in `tiles`, consecutive blocks per wavefront (1: k_render)
-    const uint32_t* order;              // launch list: order[slot] = index into `tiles` | part code << 27 (null: identity; codes
+    const uint32_t* order;              // launch list: order[slot] = index into `tiles` | part code << kLaunchCodeShift (null: identity; codes
                                         // above: cost-adaptive block size, k_plan_split).  k_render_strip: strip indices, no codes.
     const uint32_t* n_launch;           // device word: entries of `order` in this launch (null: n_tiles); workgroups past it exit
     uint32_t cost_div;                  // a block's cost = its wavefront's duration in shader clocks / cost_div (= 4 x spp: per sample)
@@ -239,9 +239,9 @@ struct trc_ctx {
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
     struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0; } knobs;
-    // k_render_pwg instantiations that were granted > 64 KB of dynamic LDS on THIS context's device (bit = integrator * 2 +
-    // sobol): hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
-    uint32_t pwg_lds_granted = 0;
+    // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_abi.hip: launch_render):
+    // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
+    std::vector<const void*> lds_granted;
 
     bool grouped() const { return comm != nullptr || coll_active; }
 };

@@ -124,6 +124,15 @@ static_assert((TRC_PARK_PATH == 0 || TRC_PARK_PATH == 8 || TRC_PARK_PATH == 10) 
 constexpr uint32_t pwg_stack_lds_levels(int integrator) { return integrator == TRC_INTEGRATOR_MIS ? TRC_PWG_STACK_LDS_MIS : (integrator == TRC_INTEGRATOR_PATH ? TRC_PWG_STACK_LDS_PATH : TRC_PWG_STACK_LDS_VOLUME); }
 constexpr int pwg_per_cu(int integrator) { return integrator == TRC_INTEGRATOR_PATH ? TRC_PWG_PER_CU_PATH : (integrator == TRC_INTEGRATOR_MIS ? TRC_PWG_PER_CU_MIS : TRC_PWG_PER_CU_VOLUME); }
 
+// wavefronts per SIMD each kernel kind is compiled for: its __launch_bounds__ (trc_render_kernels.hpp) and what the host plans
+// with (trc_abi.hip: the LDS plan, the split plan's wavefront slots) -- one value, read from the kernel table
+constexpr int render_waves(bool lds, bool stats, int integrator) {      // k_render, k_render_tex (statistics: one wavefront)
+    return stats ? 1 : integrator == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES
+                     : integrator == TRC_INTEGRATOR_MIS ? (lds ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (lds ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL);
+}
+constexpr int strip_waves(int integrator) { return integrator == TRC_INTEGRATOR_VOLUME ? 3 : (integrator == TRC_INTEGRATOR_PATH ? TRC_STRIP_PATH_WAVES : 4); }
+constexpr int pwg_simd_waves(int integrator) { return pwg_waves(integrator) * pwg_per_cu(integrator) / 4; }      // k_render_pwg
+
 // The kernels themselves (trc_render_kernels.hpp) are instantiated in five translation units -- by tree residence and integrator family,
 // so that each can be compiled with the backend options that pay for it (Makefile: EXTRA_*), and in parallel:
 //   trc_render_lds.hip        tracePath, whole tree staged in LDS (Cornell scenes; the bench's kernel)       -amdgpu-use-amdgpu-trackers
@@ -131,18 +140,17 @@ constexpr int pwg_per_cu(int integrator) { return integrator == TRC_INTEGRATOR_P
 //   trc_render_mem_path.hip   tracePath, trees read from memory (mesh scenes)                                 -disable-machine-sink
 //   trc_render_mem.hip        traceMIS, trees read from memory
 //   trc_render_mem_volume.hip traceVolume, trees read from memory                                             -disable-machine-sink
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL = false>
-__global__ void k_render(const KRender kp);
-__global__ void k_render_dense(const KRender kp);      // trc_render_lds.hip
-template <int INTEGRATOR, bool SOBOL>
-__global__ void k_render_pwg(const KRender kp);
-template <bool LDS, int INTEGRATOR, bool SOBOL>
-__global__ void k_render_strip(const KRender kp);
-// image textures (trc_upload_textures): the production kernels of the PCG sampler with hit_color<true>, in the same translation units
-template <bool LDS, int INTEGRATOR>
-__global__ void k_render_tex(const KRender kp);
-template <bool LDS, int INTEGRATOR>
-__global__ void k_render_strip_tex(const KRender kp);
-template <int INTEGRATOR>
-__global__ void k_render_pwg_tex(const KRender kp);
-
+// Each exports the kernel table of its families (render_kernels<LDS, INTEGRATOR>), which instantiates exactly the kernels in it;
+// trc_abi.hip launches whatever entry a launch picks.  A null entry is a variant that does not exist.
+struct RenderKernel {
+    void (*fn)(KRender);                // the kernel
+    int waves;                          // wavefronts per SIMD of its launch bounds
+};
+enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariants };     // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures
+struct RenderKernels {
+    RenderKernel one[kVariants];        // one pixel block per one-wavefront workgroup: k_render<.., STATS, .., SOBOL>, k_render_tex
+    RenderKernel strip[kVariants];      // a strip of blocks per wavefront: k_render_strip<.., SOBOL>, k_render_strip_tex (no statistics)
+    RenderKernel pwg[kVariants];        // persistent workgroups, trees read from memory: k_render_pwg<.., SOBOL>, k_render_pwg_tex (no statistics)
+};
+extern const RenderKernels render_lds_path, render_lds_mis, render_lds_volume, render_mem_path, render_mem_mis, render_mem_volume;
+extern const RenderKernel render_dense;      // k_render_dense (trc_render_lds.hip): tracePath, LDS-resident tree, production, PCG

@@ -1,5 +1,6 @@
 // trc_render_kernels.hpp -- kernelPathTracing (RT_Metal/Metal/Render.metal:495-558) as HIP kernels: DEFINITIONS.  Included by the
-// two translation units that instantiate them (trc_render_config.hpp says which and why); trc_abi.hip only launches them.
+// five translation units that instantiate them through their kernel tables (render_kernels below; trc_render_config.hpp says which
+// and why); trc_abi.hip only launches them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -246,10 +247,10 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp) {
     }
 }
 template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL>
-__global__ void __launch_bounds__(kBlock, STATS ? 1 : (INTEGRATOR == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES : (INTEGRATOR == TRC_INTEGRATOR_MIS ? (LDS ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (LDS ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL)))) k_render(const KRender kp) { render_workgroup<LDS, STATS, INTEGRATOR, SOBOL>(kp); }
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, STATS, INTEGRATOR)) k_render(const KRender kp) { render_workgroup<LDS, STATS, INTEGRATOR, SOBOL>(kp); }
 // ... k_render<LDS, false, INTEGRATOR, false> with image textures
 template <bool LDS, int INTEGRATOR>
-__global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES : (INTEGRATOR == TRC_INTEGRATOR_MIS ? (LDS ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (LDS ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL))) k_render_tex(const KRender kp) { render_workgroup<LDS, false, INTEGRATOR, false, 0, true>(kp); }
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_tex(const KRender kp) { render_workgroup<LDS, false, INTEGRATOR, false, 0, true>(kp); }
 
 // kernelPathTracing on a tree that is READ FROM MEMORY (mesh scenes), production launches of >= 8 spp: persistent
 // workgroups.  With one wavefront per workgroup every wavefront stages its own copy of the top of the tree, and 16-24 copies
@@ -263,12 +264,12 @@ __global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? 
 // traceMIS 16 x 2 with 8 stack entries per lane in LDS, traceVolume 16 x 1.
 // TEX (image textures): k_render_pwg_tex<INTEGRATOR>, the same body (trc_render_pwg_body.inc) with hit_color<true>
 template <int INTEGRATOR, bool SOBOL>
-__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRATOR) * pwg_per_cu(INTEGRATOR) / 4) k_render_pwg(const KRender kp) {
+__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg(const KRender kp) {
     constexpr bool TEX = false;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR>
-__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRATOR) * pwg_per_cu(INTEGRATOR) / 4) k_render_pwg_tex(const KRender kp) {
+__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_tex(const KRender kp) {
     constexpr bool SOBOL = false, TEX = true;
 #include "trc_render_pwg_body.inc"
 }
@@ -281,12 +282,36 @@ __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_waves(INTEGRAT
 // is the unit of the adaptive launch order.  Pixels are independent: the frame is k_render's, bit for bit.
 // TEX (image textures): k_render_strip_tex<LDS, INTEGRATOR>, the same body (trc_render_strip_body.inc) with hit_color<true>
 template <bool LDS, int INTEGRATOR, bool SOBOL>
-__global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? 3 : (INTEGRATOR == TRC_INTEGRATOR_PATH ? TRC_STRIP_PATH_WAVES : 4)) k_render_strip(const KRender kp) {
+__global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip(const KRender kp) {
     constexpr bool TEX = false;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR>
-__global__ void __launch_bounds__(kBlock, INTEGRATOR == TRC_INTEGRATOR_VOLUME ? 3 : (INTEGRATOR == TRC_INTEGRATOR_PATH ? TRC_STRIP_PATH_WAVES : 4)) k_render_strip_tex(const KRender kp) {
+__global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_tex(const KRender kp) {
     constexpr bool SOBOL = false, TEX = true;
 #include "trc_render_strip_body.inc"
+}
+
+// The kernel table of one tree residence and integrator (trc_render_config.hpp: RenderKernels).  Taking a kernel's address is what
+// instantiates it, so this is also the list of what each translation unit compiles: Sobol' for tracePath / traceMIS only,
+// persistent workgroups on trees read from memory only; no statistics twin of the strip / persistent kernels or of the texture ones.
+template <bool LDS, int INTEGRATOR>
+constexpr RenderKernels render_kernels() {
+    constexpr bool kSobol = INTEGRATOR != TRC_INTEGRATOR_VOLUME;
+    RenderKernels t{};
+    t.one[kVariantPlain] = {&k_render<LDS, false, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR)};
+    t.one[kVariantStats] = {&k_render<LDS, true, INTEGRATOR, false>, render_waves(LDS, true, INTEGRATOR)};
+    t.one[kVariantTex] = {&k_render_tex<LDS, INTEGRATOR>, render_waves(LDS, false, INTEGRATOR)};
+    t.strip[kVariantPlain] = {&k_render_strip<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR)};
+    t.strip[kVariantTex] = {&k_render_strip_tex<LDS, INTEGRATOR>, strip_waves(INTEGRATOR)};
+    if constexpr (kSobol) {
+        t.one[kVariantSobol] = {&k_render<LDS, false, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR)};
+        t.strip[kVariantSobol] = {&k_render_strip<LDS, INTEGRATOR, true>, strip_waves(INTEGRATOR)};
+    }
+    if constexpr (!LDS) {
+        t.pwg[kVariantPlain] = {&k_render_pwg<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR)};
+        t.pwg[kVariantTex] = {&k_render_pwg_tex<INTEGRATOR>, pwg_simd_waves(INTEGRATOR)};
+        if constexpr (kSobol) t.pwg[kVariantSobol] = {&k_render_pwg<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR)};
+    }
+    return t;
 }

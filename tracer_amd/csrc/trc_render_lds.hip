@@ -13,11 +13,6 @@ __global__ void __launch_bounds__(kBlock, TRC_PATH_WAVES_DENSE) k_render_dense(c
     render_workgroup<true, false, TRC_INTEGRATOR_PATH, false, TRC_PARK_DENSE>(kp);      // + per-pixel state parked in LDS rows (render_block)
 }
 
-#define TRC_INST_RENDER(S, I, B) template __global__ void k_render<true, S, I, B>(const KRender)
-#define TRC_INST_STRIP(I, B) template __global__ void k_render_strip<true, I, B>(const KRender)
-// exactly the instantiations launch_render<> picks from (trc_abi.hip)
-TRC_INST_RENDER(false, TRC_INTEGRATOR_PATH, false);   TRC_INST_RENDER(true, TRC_INTEGRATOR_PATH, false);   TRC_INST_RENDER(false, TRC_INTEGRATOR_PATH, true);
-TRC_INST_STRIP(TRC_INTEGRATOR_PATH, false);  TRC_INST_STRIP(TRC_INTEGRATOR_PATH, true);
-// image textures (trc_upload_textures): what a textured scene launches; k_render_dense has no such twin (k_render_tex is taken instead)
-template __global__ void k_render_tex<true, TRC_INTEGRATOR_PATH>(const KRender);
-template __global__ void k_render_strip_tex<true, TRC_INTEGRATOR_PATH>(const KRender);
+// the kernel table (trc_render_config.hpp); k_render_dense has no texture twin (a textured scene takes k_render_tex instead)
+const RenderKernels render_lds_path = render_kernels<true, TRC_INTEGRATOR_PATH>();
+const RenderKernel render_dense = {&k_render_dense, TRC_PATH_WAVES_DENSE};

@@ -8,14 +8,5 @@
 #endif
 #include "trc_render_kernels.hpp"
 
-#define TRC_INST_RENDER(S, I, B) template __global__ void k_render<false, S, I, B>(const KRender)
-#define TRC_INST_STRIP(I, B) template __global__ void k_render_strip<false, I, B>(const KRender)
-// exactly the instantiations launch_render<> picks from (trc_abi.hip)
-TRC_INST_RENDER(false, TRC_INTEGRATOR_MIS, false);    TRC_INST_RENDER(true, TRC_INTEGRATOR_MIS, false);    TRC_INST_RENDER(false, TRC_INTEGRATOR_MIS, true);
-TRC_INST_STRIP(TRC_INTEGRATOR_MIS, false);   TRC_INST_STRIP(TRC_INTEGRATOR_MIS, true);
-template __global__ void k_render_pwg<TRC_INTEGRATOR_MIS, false>(const KRender);
-template __global__ void k_render_pwg<TRC_INTEGRATOR_MIS, true>(const KRender);
-// image textures (trc_upload_textures)
-template __global__ void k_render_tex<false, TRC_INTEGRATOR_MIS>(const KRender);
-template __global__ void k_render_strip_tex<false, TRC_INTEGRATOR_MIS>(const KRender);
-template __global__ void k_render_pwg_tex<TRC_INTEGRATOR_MIS>(const KRender);
+// the kernel table (trc_render_config.hpp)
+const RenderKernels render_mem_mis = render_kernels<false, TRC_INTEGRATOR_MIS>();

@@ -7,13 +7,5 @@
 #endif
 #include "trc_render_kernels.hpp"
 
-#define TRC_INST_RENDER(S, I, B) template __global__ void k_render<false, S, I, B>(const KRender)
-#define TRC_INST_STRIP(I, B) template __global__ void k_render_strip<false, I, B>(const KRender)
-// exactly the instantiations launch_render<> picks from (trc_abi.hip)
-TRC_INST_RENDER(false, TRC_INTEGRATOR_VOLUME, false); TRC_INST_RENDER(true, TRC_INTEGRATOR_VOLUME, false);
-TRC_INST_STRIP(TRC_INTEGRATOR_VOLUME, false);
-template __global__ void k_render_pwg<TRC_INTEGRATOR_VOLUME, false>(const KRender);
-// image textures (trc_upload_textures)
-template __global__ void k_render_tex<false, TRC_INTEGRATOR_VOLUME>(const KRender);
-template __global__ void k_render_strip_tex<false, TRC_INTEGRATOR_VOLUME>(const KRender);
-template __global__ void k_render_pwg_tex<TRC_INTEGRATOR_VOLUME>(const KRender);
+// the kernel table (trc_render_config.hpp)
+const RenderKernels render_mem_volume = render_kernels<false, TRC_INTEGRATOR_VOLUME>();
