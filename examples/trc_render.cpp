@@ -4,6 +4,7 @@
 //
 //   trc_render [--scene cornell|spheres|volume] [--integrator path|mis|volume] [--size W H] [--spp N]
 //              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
+//              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
 //              as the reference's host binds uv_test.png (AAPLRenderer.mm:385-390)
 //   trc_render --pbrt scene.pbrt [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
@@ -29,7 +30,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false;
+    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -44,6 +45,7 @@ int main(int argc, char** argv) {
         else if (a == "--lbvh") lbvh = true;
         else if (a == "--device-sah") device_sah = true;
         else if (a == "--sobol") sobol = true;
+        else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -74,8 +76,9 @@ int main(int argc, char** argv) {
             return 1;
         }
         if (!size_given) { W = info.xres; H = info.yres; }         // the camera's aspect is the film's
-        if (integrator != TRC_INTEGRATOR_PATH && !info.mis_ready) {
-            std::fprintf(stderr, "%s has no rectangular area light: traceMIS samples squareList[5] / [6]; use --integrator path\n", pbrt_path.c_str());
+        if (integrator != TRC_INTEGRATOR_PATH && !info.mis_ready && !(env_light && !hdr_path.empty())) {
+            std::fprintf(stderr, "%s has no rectangular area light: traceMIS samples squareList[5] / [6]; use --integrator path, or --hdr with --env-light\n",
+                         pbrt_path.c_str());
             return 1;
         }
         scene_name = pbrt_path;
@@ -160,6 +163,7 @@ int main(int argc, char** argv) {
     std::memset(&prm, 0, sizeof prm);
     prm.spp = spp; prm.max_depth = 8; prm.integrator = integrator; prm.tile_nranks = 1;
     if (sobol) prm.flags |= TRC_FLAG_SOBOL;      // pbrt::SobolSampler instead of the random sampler (Render.metal:529-530)
+    if (env_light) prm.flags |= TRC_FLAG_ENV_LIGHT;  // the --hdr map as an importance-sampled light of traceMIS
     const auto t0 = std::chrono::steady_clock::now();
     CHECK(trc_render(ctx, &prm));
     CHECK(trc_synchronize(ctx));

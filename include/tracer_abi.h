@@ -44,8 +44,9 @@ extern "C" {
  *    hand out that rank's partial slices)
  * 7: SVGF denoiser stage: trc_gbuffer_texel, trc_denoise_params, trc_denoise_default_params, trc_denoise, trc_download_denoised,
  *    trc_tonemap_denoised, trc_download_gbuffer, trc_denoise_reset (nothing existing changed)
- * 8: image textures: trc_image, trc_upload_textures, trc_host_load_png (nothing existing changed) */
-#define TRC_ABI_VERSION 8
+ * 8: image textures: trc_image, trc_upload_textures, trc_host_load_png (nothing existing changed)
+ * 9: TRC_FLAG_ENV_LIGHT: the environment map as an importance-sampled light of traceMIS (nothing existing changed) */
+#define TRC_ABI_VERSION 9
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -275,6 +276,34 @@ enum trc_integrator {
                                        blocks as the GPU has wavefront slots, i.e. a rank's share of a strong-scaled
                                        frame; chosen automatically there unless TRC_FLAG_LARGE_BLOCKS is set */
 #define TRC_FLAG_LARGE_BLOCKS   16u
+#define TRC_FLAG_ENV_LIGHT      32u /* traceMIS treats the environment map as a light, sampled by importance and combined with
+                                       BSDF sampling by MIS (an extension beyond the reference, which lights with the map only
+                                       where a BSDF-sampled ray escapes).  Without the flag nothing changes.
+   - Accepted with TRC_INTEGRATOR_MIS and a map set (trc_set_environment_map; the constant of trc_set_environment is not
+     sampled), with or without active image textures.  With tracePath / traceVolume, TRC_FLAG_SOBOL, TRC_FLAG_COLLECT_STATS or
+     without a map, trc_render returns TRC_ERR_UNSUPPORTED and renders nothing.  Scenes without squareList[5] / [6] are accepted.
+   - Distribution over the map's W x H cells (row j at w in [j/H, (j+1)/H), rows bottom-up like the map's): cell weight = the
+     largest rgb_to_y among the texels the bilinear lookup can read inside the cell (3 x 3, clamped at the edges; negative or
+     non-finite texels count 0) times cos(latitude of the cell centre).  Direction of (u, w): phi = 2 pi (u - 1/2),
+     latitude = pi (w - 1/2), d = (cos lat cos phi, sin lat, cos lat sin phi); solid-angle pdf = p_uw / (2 pi^2 cos lat).
+     The radiance lookup keeps the reference's SampleSphericalMap constants (0.1591 / 0.3183).
+   - Light pick: the reference's one pcg_float draw.  p_env = 1/2 with square lights, 1 without, 0 when every weight is 0.  A
+     draw below p_env picks the map, else square 5 below p_env + (1 - p_env) / 2 and square 6 above; a square's contribution
+     is divided by 1 - p_env (the reference's expectation, its missing 1/2 pick factor included).
+   - The map's sample: a two-level alias table (rows, then the picked row's cells), six extra PCG draws taken only when the
+     map is picked: a multiply-shift index and a 32-bit alias decision per level, two floats inside the cell.  Its shadow ray
+     is an any-hit walk to infinity from where a BSDF ray of that direction would start.  Contribution: ratio * F * L_env *
+     w / (p_env pdf), w = power heuristic(p_env pdf, bsdf pdf).  The map's sample counts only where the BSDF sample is a
+     cosine lobe (Lambert, or the Lambert lobe of Plastic, picked by the vertex's sample2D) and has support (wo.z > 0,
+     wi.z > 0).  Beckmann, Metal and Glass lobes report per-lobe pdfs with the reference's lobe-pick conventions
+     (Material.hh), not the density to weigh against: at such a vertex a pick of the map takes no sample and the escape keeps
+     weight 1, so the flag reduces no variance there.  No map sample at a vertex whose BSDF ray would not be counted if it
+     escaped (max_depth), so the flag changes no expectation at any max_depth.
+   - A BSDF-sampled ray from a cosine lobe that escapes is weighted by power heuristic(bsdf pdf, p_env pdf(d)), exactly 1
+     where pdf(d) = 0; any other escape (a camera ray, a ray from another material) is not weighted.  Without square lights a BSDF-sampled emitter hit has weight 1.
+   - The tables are built at the first flagged render after trc_set_environment_map (TRC_ERR_OOM if they cannot be
+     allocated; flag-off renders keep working) and freed when the map changes or is cleared, and by trc_destroy.  A change
+     of the flag, like one of the integrator, drops the recorded block costs of the launch planner. */
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
                                        N_descend / N_return / leaf-test counters.  Not with an active image texture
                                        (trc_upload_textures): TRC_ERR_UNSUPPORTED. */

@@ -45,6 +45,17 @@ trc_status trc_debug_denoise_state(trc_ctx* ctx, float* integrated, float* histo
  * below the number of uploaded images. */
 trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv /* 2 n */, size_t n, float* rgb /* 3 n */);
 
+/* test hooks of TRC_FLAG_ENV_LIGHT (tracer_abi.h); both build the current map's sampling tables if they are not built
+ * (TRC_ERR_UNSUPPORTED without a map).  trc_debug_env_tables downloads them (any pointer may be NULL): the W*H cell weights, the
+ * rows' alias tables (W*H {threshold, alias} pairs, row after row), the marginal's (H pairs), the float64 total weight and the
+ * build's GPU time.  trc_env_light_test runs the render kernels' sampler and pdf (tracer_amd/csrc/dev_envlight.hpp), one lane
+ * per item: for n draws (six words each: row index, row alias, cell index, cell alias as 32-bit integers, then two float bit
+ * patterns for the point inside the cell) dir_pdf receives the direction and pdf (4 floats each); for m directions (3 floats
+ * each) pdf receives the density the sampler gives them. */
+trc_status trc_debug_env_tables(trc_ctx* ctx, float* weight, uint32_t* rows, uint32_t* marg, double* total, float* build_ms);
+trc_status trc_env_light_test(trc_ctx* ctx, const uint32_t* draws /* 6 n */, size_t n, float* dir_pdf /* 4 n */,
+                              const float* dirs /* 3 m */, size_t m, float* pdf /* m */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,70 @@
+"""Builds tests/envlight_ref/envlight_ref.cpp (the CPU restatement of TRC_FLAG_ENV_LIGHT's tables, sampler and pdf) into a
+directory of the caller's and wraps it."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+class Ref:
+    def __init__(self, L):
+        self.L = L
+
+    def tables(self, rgb):
+        """(h, w, 3) float32 map, rows bottom-up -> dict(weight (h, w), rows (h, w, 2), marg (h, 2), total)"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        H, W = rgb.shape[:2]
+        weight = np.empty((H, W), np.float32)
+        rows = np.empty((H, W, 2), np.uint32)
+        marg = np.empty((H, 2), np.uint32)
+        total = C.c_double()
+        self.L.envlight_ref_tables(rgb.ctypes.data, W, H, weight.ctypes.data, rows.ctypes.data, marg.ctypes.data, C.byref(total))
+        return dict(weight=weight, rows=rows, marg=marg, total=total.value)
+
+    def sample(self, t, draws):
+        draws = np.ascontiguousarray(draws, dtype=np.uint32).reshape(-1, 6)
+        H, W = t["weight"].shape
+        out = np.empty((draws.shape[0], 4), np.float32)
+        self.L.envlight_ref_sample(W, H, t["weight"].ctypes.data, t["rows"].ctypes.data, t["marg"].ctypes.data, t["total"],
+                                   draws.ctypes.data, draws.shape[0], out.ctypes.data)
+        return out
+
+    def pdf(self, t, dirs):
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        H, W = t["weight"].shape
+        out = np.empty(dirs.shape[0], np.float32)
+        self.L.envlight_ref_pdf(W, H, t["weight"].ctypes.data, t["total"], dirs.ctypes.data, dirs.shape[0], out.ctypes.data)
+        return out
+
+
+def build(out_dir):
+    so = os.path.join(str(out_dir), "libenvlight_ref.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I", os.path.join(ROOT, "include"),
+                           "-o", so, os.path.join(ROOT, "tests", "envlight_ref", "envlight_ref.cpp")])
+    L = C.CDLL(so)
+    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
+    L.envlight_ref_tables.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(C.c_double)]
+    L.envlight_ref_sample.argtypes = [u32, u32, vp, vp, vp, C.c_double, vp, sz, vp]
+    L.envlight_ref_pdf.argtypes = [u32, u32, vp, C.c_double, vp, sz, vp]
+    L.envlight_ref_scale.argtypes = [u32, u32, C.c_double]
+    L.envlight_ref_scale.restype = C.c_float
+    return Ref(L)
+
+
+def sun_sky(W, H, sun=(0.3, 0.7), sun_radius=0.03, sun_power=2000.0, sky=(0.4, 0.6, 1.0)):
+    """a synthetic sun-and-sky map: a blue upper hemisphere fading to a dim ground and a small very bright disc at (u, w) = sun"""
+    u = (np.arange(W, dtype=np.float64) + 0.5) / W
+    w = (np.arange(H, dtype=np.float64) + 0.5) / H
+    uu, ww = np.meshgrid(u, w)
+    lat = np.pi * (ww - 0.5)
+    up = np.clip(np.sin(lat), 0.0, 1.0)[..., None]
+    img = 0.05 + up * np.array(sky)[None, None, :]
+    phi, slat = 2 * np.pi * (uu - 0.5), lat
+    d = np.stack([np.cos(slat) * np.cos(phi), np.sin(slat), np.cos(slat) * np.sin(phi)], -1)
+    sp, sl = 2 * np.pi * (sun[0] - 0.5), np.pi * (sun[1] - 0.5)
+    s = np.array([np.cos(sl) * np.cos(sp), np.sin(sl), np.cos(sl) * np.sin(sp)])
+    img = img + (d @ s > np.cos(sun_radius))[..., None] * sun_power
+    return np.ascontiguousarray(img, dtype=np.float32)

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "dev_bsdf.hpp"
+#include "dev_envlight.hpp"
 #include "dev_intersect.hpp"
 #include "trc_sobol.h"
 
@@ -150,9 +151,17 @@ struct PathCtx {
 };
 // ... of the TEX instantiations (image textures): a struct of its own, so that the others' context keeps its layout
 struct PathCtxTex : PathCtx { TexTable tex; };
-template <bool TEX> using PathCtxOf = typename std::conditional<TEX, PathCtxTex, PathCtx>::type;
+// ... and of the ENV instantiations (TRC_FLAG_ENV_LIGHT): the map's sampling tables (dev_envlight.hpp)
+struct PathCtxEnv : PathCtx { EnvLight envl; };
+struct PathCtxEnvTex : PathCtxTex { EnvLight envl; };
+template <bool TEX, bool ENV = false>
+using PathCtxOf = typename std::conditional<ENV, typename std::conditional<TEX, PathCtxEnvTex, PathCtxEnv>::type,
+                                            typename std::conditional<TEX, PathCtxTex, PathCtx>::type>::type;
 template <bool TEX> TRC_DEV const TexTable* ctx_tex(const PathCtx& cx) {
     if constexpr (TEX) return &static_cast<const PathCtxTex&>(cx).tex; else return nullptr;
+}
+template <bool TEX, bool ENV> TRC_DEV const EnvLight* ctx_env(const PathCtx& cx) {
+    if constexpr (ENV) return &static_cast<const PathCtxOf<TEX, true>&>(cx).envl; else return nullptr;
 }
 
 // ---------------------------------------------------------------- path state machine
@@ -177,6 +186,7 @@ struct PathState {
     int trk_step;
     uint64_t sobol_index;    // TRC_FLAG_SOBOL: mSobolIndex of this sample and the next dimension (SobolSampler.hh:37-41)
     uint32_t sobol_dim;
+    bool env_mis;            // TRC_FLAG_ENV_LIGHT: the map's light sample shares the escape of the ray in flight (a cosine lobe, env_nee)
 };
 
 // ---------------------------------------------------------------- pbrt::SobolSampler (SobolSampler.hh:26-167)
@@ -413,7 +423,83 @@ TRC_DEV float grid_sample(const PathCtx& cx, const HitRec& rec, MediumHit& mi, P
 // Same for traceMIS (Render.metal:298-406) and, with VOLUME, traceVolume (Render.metal:78-275 = traceMIS + the
 // medium block :114-158).  Lights are literally squareList[5] and [6] (:320-324, B-12).
 // The shadow ray (any-hit Scene::hit) is traced here, inside the step.
-template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, class COUNT = uint32_t>
+// The light sample of a traceMIS vertex with the environment map as a light (TRC_FLAG_ENV_LIGHT; mis_step<.., ENV>): the light pick,
+// then the map's or a square's sample, its shadow ray and its MIS-weighted contribution; leaves the shading frame, -wo and the
+// hit's colour for the BSDF sample.  A square's sample is the reference's (:320-356) with its contribution divided by 1 - p_env.
+// The map's shadow ray is an any-hit walk to infinity from where a BSDF ray of the same direction would start (_origin: only
+// directions above the surface are taken).
+template <bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
+TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
+                     const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
+    const HitRec& rec = ps.rec;
+    const EnvLight& L = *ctx_env<TEX, true>(cx);
+    const float pick = pcg_float(rng);
+    // 0: no light sample; 1: a square; 2: the map -- only where the BSDF ray's escape would count (mis_step's depth cutoff), and only
+    // where the BSDF sample is a cosine lobe: a Lambert vertex, or the Lambert lobe a Plastic vertex picks with uu.x < 1/2 (the same uu
+    // picks the same lobe in material_F and material_S_F; that lobe's F and pdf are the value and density it samples with).  The other
+    // lobes (Beckmann, Metal, Glass) report per-lobe pdfs with the reference's lobe-pick conventions, not the density the map's
+    // strategy would have to be weighed against: there a pick of the map takes no sample and the escape keeps weight 1.
+    ps.env_mis = mtype == kMatLambert || (mtype == kMatPlastic && uu.x < 0.5f);
+    const int kind = pick < L.p_env ? (ps.depth_left > 1 && ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
+    coordinate_system(rec.sn, nx, ny);
+    Ray _ray = make_ray(_origin, f3(0.0f, 0.0f, 1.0f));
+    float _dis = FLT_MAX;
+    F3 light_term = f3(0.0f);
+    float liPDF = 0.0f;
+    if (kind == 1) {
+        LightSample lsr;
+        square_sample(cx.S, pick < L.p_env + (1.0f - L.p_env) * 0.5f ? 5 : 6, uu, _origin, lsr);
+        const F3 _dir = lsr.p - _origin;
+        const F3 _nor = normalize(_dir);
+        _dis = length(_dir);
+        _ray = make_ray(_origin, _nor);
+        const float cosOnLight = fabsf(dot(lsr.n, -_nor));
+        light_term = mat_albedo(cx.sh, lsr.material) * cosOnLight;
+        liPDF = (_dis * _dis) * lsr.areaPDF / cosOnLight;
+    } else if (kind == 2) {
+        const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng), r2 = pcg_next(rng), r3 = pcg_next(rng);
+        const float f0 = pcg_float(rng), f1 = pcg_float(rng);
+        float pdf;
+        const F3 dir = env_light_sample(L, r0, r1, r2, r3, f0, f1, pdf);
+        // only where the BSDF strategy has support -- the cosine lobe samples wi.z > 0 and reports pdf 0 unless wo.z > 0 -- does the
+        // map's sample carry weight: below the surface Lambert::F = wi.z / pi is negative, and nothing on the BSDF side covers it
+        const float wi_z = dot(rec.sn, dir), wo_z = -dot(rec.sn, ps.ray.d);
+        liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? L.p_env * pdf : 0.0f;
+        if (liPDF > 0.0f) {
+            _ray = make_ray(_origin, dir);               // where the BSDF ray of this direction starts (wi.z > 0)
+            light_term = env_radiance(cx.env, cx.ambient, _ray.d);
+        }
+    }
+    bool blocked = true;
+    if (kind == 1 || (kind == 2 && liPDF > 0.0f)) {              // (a square's sample walks whatever its pdf, as the reference's does)
+        bump(n_rays);
+        if (STATS) {
+            HitRec shr;
+            hit_init(shr);
+            blocked = scene_hit<ALL_LDS, STATS, true, false, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, shr, _dis, cx.stack, cx.lvstack, cnt);
+        } else {
+            blocked = scene_occluded<ALL_LDS, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, _dis, cx.stack, cx.S.stack_cap);
+        }
+    }
+    minus_d = -ps.ray.d;
+    base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
+    if (!blocked) {
+        const F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
+        const F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
+        float bxPDF = 0;
+        bump(n_shaded);
+        F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF) * light_term;
+        if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - L.p_env));
+        else ps.color = ps.color + ps.ratio * (weight * env_mis_weight(liPDF, bxPDF)) / liPDF;
+    }
+}
+
+// ENV (TRC_FLAG_ENV_LIGHT, traceMIS only): the environment map is a light too (dev_envlight.hpp).  The light pick's one draw takes
+// the map below p_env, else square 5 below p_env + (1 - p_env) / 2 and square 6 above; a square's contribution is divided by
+// 1 - p_env (the reference's expectation, its missing 1/2 included).  The map's sample draws six more numbers, only when it is
+// picked, and only at a vertex whose BSDF ray would be counted if it escaped; an escaping BSDF ray is weighted against it.
+// With p_env = 0 (a black map) every operation and draw is the flag-off kernel's.
+template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, bool ENV = false, class COUNT = uint32_t>
 TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_rays,
                       COUNT& n_shaded, F3& result) {
     HitRec& rec = ps.rec;
@@ -427,11 +513,25 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
             F3 d = rec.p - ps.ray.o;
             float dist2 = dot(d, d);
             float lightPDF = rec.PDF * dist2 / cosOnLight;
-            weight = weight * power_heuristic(1, ps.scat_bxPDF, 1, lightPDF);
+            if (!ENV || ctx_env<TEX, ENV>(cx)->squares)          // (without square lights no light strategy shares the hit: weight 1)
+                weight = weight * power_heuristic(1, ps.scat_bxPDF, 1, lightPDF);
             result = ps.color + ps.ratio * weight / ps.scat_bxPDF;
             return true;
         }
         if (--ps.depth_left <= 0) { result = ps.color; return true; }   // } while ((--depth) > 0), :406
+    }
+    if constexpr (ENV) {
+        if (!hitted) {                                               // a BSDF-sampled ray that escapes, against the map's own strategy
+            const EnvLight& L = *ctx_env<TEX, ENV>(cx);
+            F3 le = env_radiance(cx.env, cx.ambient, ps.ray.d);
+            if (!ps.primary && ps.env_mis) {
+                const float pe = L.p_env * env_light_pdf(L, ps.ray.d);
+                if (pe > 0.0f) le = le * env_mis_weight(ps.scat_bxPDF, pe);
+            }
+            ps.primary = false;
+            result = ps.color + ps.ratio * le;
+            return true;
+        }
     }
     ps.primary = false;
     if (!hitted) { result = ps.color + ps.ratio * env_radiance(cx.env, cx.ambient, ps.ray.d); return true; }
@@ -482,11 +582,14 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     const F2 uu = sample_2d<SOBOL>(cx, ps, rng);                     // :314
     const F3 hit_origin = rec.p;
     F3 _origin = offset_ray(rec.p, rec.sn);
+    F3 nx, ny, minus_d, base_color;
+    if constexpr (ENV) {
+        env_nee<ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
+    } else {
     if (pcg_float(rng) < 0.5f) square_sample(cx.S, 5, uu, _origin, lsr);
     else square_sample(cx.S, 6, uu, _origin, lsr);
     F3 _dir = lsr.p - _origin;
     F3 _nor = normalize(_dir);
-    F3 nx, ny;
     coordinate_system(rec.sn, nx, ny);
     const float _tr = 1.0f;
     const float _dis = length(_dir);
@@ -506,8 +609,8 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     } else {                                                          // any-hit: the answer does not depend on the order (dev_intersect.hpp)
         blocked = scene_occluded<ALL_LDS, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, _dis, cx.stack, cx.S.stack_cap);
     }
-    const F3 minus_d = -ps.ray.d;
-    const F3 base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
+    minus_d = -ps.ray.d;
+    base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
     if (!blocked) {                                                  // light sampling, :339-356
         F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
         F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
@@ -517,6 +620,7 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
         weight = weight * light_term;
         weight = weight * power_heuristic(1, liPDF, 1, bxPDF);
         ps.color = ps.color + _tr * ps.ratio * weight / liPDF;
+    }
     }
     // BXDF sampling, :358-378
     F3 wi = f3(0);

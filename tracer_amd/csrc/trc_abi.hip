@@ -933,14 +933,16 @@ const RenderKernels& render_family(bool lds_scene, uint32_t integrator) {
 
 // One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
 // device (the attribute is set on the current device's copy of the function): remembered in the context, which is bound to one device.
-hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, uint32_t grid, uint32_t block, size_t lds) {
-    const void* const fn = reinterpret_cast<const void*>(kern.fn);
+hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, const EnvLight& el, uint32_t grid, uint32_t block, size_t lds) {
+    const void* const fn = kern.fn_env ? reinterpret_cast<const void*>(kern.fn_env) : reinterpret_cast<const void*>(kern.fn);
     if (lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         if (e != hipSuccess) return e;
         ctx->lds_granted.push_back(fn);
     }
-    void* args[] = {const_cast<KRender*>(&kp)};
+    KRenderEnv kpe;                                     // the k_render*_env kernels' parameters: the launch's and the map's tables
+    if (kern.fn_env) { kpe.kp = kp; kpe.el = el; }
+    void* args[] = {kern.fn_env ? static_cast<void*>(&kpe) : const_cast<KRender*>(&kp)};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(block), args, lds, ctx->stream);
     const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
     return e != hipSuccess ? e : last;
@@ -1117,7 +1119,7 @@ void trc_destroy(trc_ctx* ctx) {
     trc_denoise_release(ctx);
     collect_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
+    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); trc_env_light_free(ctx); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
     (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_stats); (void)hipFree(ctx->d_stats_sum); (void)hipFree(ctx->d_reduce_recv);
     (void)hipFree(ctx->d_block_cost); (void)hipFree(ctx->d_order_hist); (void)hipFree(ctx->d_split); (void)hipFree(ctx->d_whole); (void)hipFree(ctx->d_cost_est); (void)hipFree(ctx->d_qsplit); (void)hipFree(ctx->d_qwhole); (void)hipFree(ctx->d_swhole); (void)hipFree(ctx->d_launch); (void)hipFree(ctx->d_plan); (void)hipFree(ctx->d_plan_gather); (void)hipFree(ctx->d_cost_scratch);
     for (int k = 0; k < 2; ++k) { (void)hipFree(ctx->d_order_keys[k]); (void)hipFree(ctx->d_order_vals[k]); }
@@ -1259,6 +1261,7 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(ctx->d_envmap); ctx->d_envmap = nullptr; ctx->env_w = ctx->env_h = 0;
+    trc_env_light_free(ctx);                                             // TRC_FLAG_ENV_LIGHT: rebuilt for the new map when a launch asks
     trc_denoise_invalidate(ctx);
     if (!rgb) return TRC_OK;                                             // back to the constant environment
     if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_set_environment_map: bad size");
@@ -1446,7 +1449,14 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
     const uint32_t nranks = p->tile_nranks ? p->tile_nranks : 1;
     if (p->tile_rank >= nranks) return fail(ctx, TRC_ERR_INVALID_ARG, "tile_rank >= tile_nranks");
     if (p->integrator > TRC_INTEGRATOR_VOLUME) return fail(ctx, TRC_ERR_INVALID_ARG, "unknown integrator");
-    if (p->integrator != TRC_INTEGRATOR_PATH && ctx->ks.sc.n_squares < 7)
+    const bool env_light = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
+    if (env_light) {
+        if (p->integrator != TRC_INTEGRATOR_MIS) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_ENV_LIGHT: traceMIS only");
+        if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS))
+            return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_ENV_LIGHT: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS kernels");
+        if (!ctx->d_envmap) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_ENV_LIGHT: no environment map (trc_set_environment_map)");
+    }
+    if (p->integrator != TRC_INTEGRATOR_PATH && ctx->ks.sc.n_squares < 7 && !env_light)
         return fail(ctx, TRC_ERR_INVALID_ARG, "traceMIS / traceVolume sample squareList[5] and [6] (Render.metal:320-324,172-176)");
     if (ctx->tex_active() && (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS)))
         return fail(ctx, TRC_ERR_UNSUPPORTED, "image textures: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS kernels (trc_upload_textures)");
@@ -1462,6 +1472,7 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
         if (m > TRC_SOBOL_MAX_LOG2RES) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_SOBOL: frame too large");
         if (sobol_m) *sobol_m = m;
     }
+    if (env_light) return trc_env_light_build(ctx);      // the map's sampling tables, once per map (TRC_ERR_OOM: this render does not run)
     return TRC_OK;
 }
 
@@ -1517,6 +1528,8 @@ trc_status trc_render(trc_ctx* ctx, const trc_params* p) {
 struct RenderLaunch {
     KRender kp{};                       // the kernel's parameters
     bool stats = false, sobol = false;  // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL
+    bool env = false;                   // TRC_FLAG_ENV_LIGHT ...
+    EnvLight el{};                      // ... and the map's sampling tables (the k_render*_env kernels' second half of KRenderEnv)
     bool fits = false;                  // launch_geometry: the frame's edges allow 4x4 blocks ...
     uint64_t blocks8 = 0;               // ... 8x8 blocks in this rank's share
     bool quarters_ok = false;           // ... the list's blocks are 8x8: costs live in kCostSlots slots per block
@@ -1592,7 +1605,9 @@ static void drop_stale_costs(trc_ctx* ctx, const trc_params* p, const RenderLaun
     if (ctx->cost_strip != r.kp.strip || ctx->cost_quarters != r.quarters_ok) {
         ctx->cost_valid = false; ctx->cost_strip = r.kp.strip; ctx->cost_quarters = r.quarters_ok; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
     }
-    if (ctx->cost_integrator != p->integrator) { ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr; }
+    if (ctx->cost_integrator != p->integrator || ctx->cost_env != r.env) {
+        ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->cost_env = r.env; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
+    }
 }
 
 // Samples of the cold head this pass is split into (see kColdHeadSpp), or 0: the pass runs as one launch
@@ -1645,9 +1660,10 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
         r.pwg = plan_pwg_lds(ctx, kp.ks.sc, r.pwg_waves, (uint32_t)pwg_per_cu(integrator), hybrid_stack(integrator), pwg_stack_lds_levels(integrator), park_rows);
         if (!r.pwg) park_rows = 0u;
     }
-    const RenderVariant variant = ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
+    const RenderVariant variant = r.env ? (ctx->tex_active() ? kVariantEnvTex : kVariantEnv)
+                                        : ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
-    if (!r.kern.fn) return fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
+    if (!r.kern.fn && !r.kern.fn_env) return fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
     if (mem_plan && !r.pwg) plan_launch_lds(ctx, kp.ks.sc, (uint32_t)r.kern.waves, hybrid_stack(integrator));
     r.lds = r.pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)r.pwg_waves * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
                   : dyn_lds_bytes(kp.ks.sc, r.stats) + (r.dense ? (size_t)park_rows * kBlock * 4 : 0u);
@@ -1794,7 +1810,7 @@ static trc_status timed_launch(trc_ctx* ctx, const RenderLaunch& r) {
     auto give_back = [&]() { if (e0) ctx->event_pool.push_back(e0); if (e1) ctx->event_pool.push_back(e1); };
     if (!e0 || !e1) { give_back(); return fail(ctx, TRC_ERR_HIP, "hipEventCreate failed"); }
     hipError_t le = hipEventRecord(e0, ctx->stream);
-    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.grid, r.block, r.lds);
+    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.el, r.grid, r.block, r.lds);
     if (le == hipSuccess) le = hipEventRecord(e1, ctx->stream);
     if (le != hipSuccess) { give_back(); return fail(ctx, TRC_ERR_HIP, std::string("k_render launch: ") + hipGetErrorString(le)); }
     ctx->pending.emplace_back(e0, e1);
@@ -1810,6 +1826,8 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     collect_finished_events(ctx);        // before any launch of this call: it may consume a "not ready" sticky error
     r.stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
     r.sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
+    r.env = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
+    if (r.env) r.el = trc_env_light_view(ctx);
     { const trc_status st = launch_geometry(ctx, p, r); if (st != TRC_OK) return st; }
     if (ctx->n_tiles == 0) return TRC_OK;
     if (trc_dyn_lds_bytes(ctx, r.stats) > 160 * 1024) return fail(ctx, TRC_ERR_UNSUPPORTED, "traversal stack exceeds the 160 KB LDS of a CU");

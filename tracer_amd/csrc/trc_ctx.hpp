@@ -67,6 +67,13 @@ struct KRender {
     uint32_t n_tex;                     // ... images uploaded
 };
 
+// the kernels of TRC_FLAG_ENV_LIGHT (k_render*_env) take the environment map's sampling tables besides: a struct of their own, so
+// that every other kernel keeps its parameter block
+struct KRenderEnv {
+    KRender kp;
+    EnvLight el;
+};
+
 struct KTrace {
     KScene ks;
     const trc_ray* rays;
@@ -158,6 +165,9 @@ struct trc_ctx {
     // materials (~0u: none) -- an image is active, and the _tex kernels launched, when it is below n_tex
     float* d_tex_texels = nullptr; uint4* d_tex_desc = nullptr; uint32_t n_tex = 0; uint32_t scene_min_image = ~0u;
     bool tex_active() const { return scene_min_image < n_tex; }
+    // TRC_FLAG_ENV_LIGHT: the map's sampling tables (trc_envlight.hip), built at the first flagged render after trc_set_environment_map
+    uint8_t* d_envl = nullptr; double envl_total = 0.0; float envl_build_ms = 0.0f;
+    bool cost_env = false;              // the flag of the launches whose block costs are recorded (drop_stale_costs)
 
     // frame
     uint32_t width = 0, height = 0;
@@ -319,4 +329,9 @@ inline uint32_t trc_scene_min_image(const trc_scene* s) {
     return m;
 }
 void trc_denoise_invalidate(trc_ctx* ctx);   // another scene or environment: the G-buffer is stale and the history dropped
+// TRC_FLAG_ENV_LIGHT (trc_envlight.hip): build the current map's sampling tables if they are not built (TRC_ERR_OOM: nothing kept), free
+// them, and the kernels' view of them
+trc_status trc_env_light_build(trc_ctx* ctx);
+void trc_env_light_free(trc_ctx* ctx);
+EnvLight trc_env_light_view(const trc_ctx* ctx);
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)

@@ -23,10 +23,15 @@ template <bool TEX, class CX>
 __device__ __forceinline__ void set_ctx_tex(CX& cx, const KRender& kp) {       // TEX: the image table of the launch (PathCtxTex)
     if constexpr (TEX) { cx.tex.texels = kp.tex_texels; cx.tex.desc = kp.tex_desc; cx.tex.n = kp.n_tex; }
 }
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, class COUNT = uint32_t>
+// ENV (TRC_FLAG_ENV_LIGHT, traceMIS): the environment map is a light too (mis_step<.., ENV>); `envl` = its sampling tables
+template <bool ENV, class CX>
+__device__ __forceinline__ void set_ctx_env(CX& cx, const EnvLight* envl) {
+    if constexpr (ENV) cx.envl = *envl;
+}
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, class COUNT = uint32_t>
 __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                              uint32_t* ovf, uint32_t* park, const uint32_t slot, const uint32_t lane,
-                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt) {
+                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt, const EnvLight* envl = nullptr) {
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
     const uint32_t entry = kp.order ? kp.order[slot] : slot;     // adaptive launch order / cost-adaptive block size (trc_render)
     const uint32_t index = entry & kLaunchIndexMask, code = entry >> kLaunchCodeShift;
@@ -47,13 +52,14 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
     const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
 
     if (active) {
-        PathCtxOf<TEX> cx;
+        PathCtxOf<TEX, ENV> cx;
         cx.S = make_scene_ref(sc, small_base);
         cx.S.ovf = ovf;
         cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
         cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
         cx.sh.mats = small_base + sc.off_materials;
         set_ctx_tex<TEX>(cx, kp);
+        set_ctx_env<ENV>(cx, envl);
         cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
         cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
         cx.stack = stack;
@@ -157,7 +163,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
             F3 color;
             const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                       ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                      : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
             if (finished) finish_sample(color);
         }
         if constexpr (PARK) {       // the loop is left by the last finish_sample only (trc_render launches spp >= 1): what that one would
@@ -192,8 +198,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
 }
 
 // the body of k_render (one one-wavefront workgroup = one entry of the launch list)
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false>
-__device__ __forceinline__ void render_workgroup(const KRender& kp) {
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false>
+__device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLight* envl = nullptr) {
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
     const uint32_t* small_base = stage_scene(sc);
@@ -210,10 +216,10 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp) {
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
-        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt);
+        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl);
         n_rays = park[kParkRays * kBlock]; n_shaded = park[kParkShaded * kBlock];
     } else
-    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt);
+    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
@@ -251,6 +257,11 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, STATS, INTEGRATOR)) 
 // ... k_render<LDS, false, INTEGRATOR, false> with image textures
 template <bool LDS, int INTEGRATOR>
 __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_tex(const KRender kp) { render_workgroup<LDS, false, INTEGRATOR, false, 0, true>(kp); }
+// ... with the environment map as a light (TRC_FLAG_ENV_LIGHT), without and with image textures
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_env(const KRenderEnv kpe) {
+    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, true>(kpe.kp, &kpe.el);
+}
 
 // kernelPathTracing on a tree that is READ FROM MEMORY (mesh scenes), production launches of >= 8 spp: persistent
 // workgroups.  With one wavefront per workgroup every wavefront stages its own copy of the top of the tree, and 16-24 copies
@@ -265,12 +276,21 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) 
 // TEX (image textures): k_render_pwg_tex<INTEGRATOR>, the same body (trc_render_pwg_body.inc) with hit_color<true>
 template <int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg(const KRender kp) {
-    constexpr bool TEX = false;
+    constexpr bool TEX = false, ENV = false;
+    const EnvLight* const envl = nullptr;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_tex(const KRender kp) {
-    constexpr bool SOBOL = false, TEX = true;
+    constexpr bool SOBOL = false, TEX = true, ENV = false;
+    const EnvLight* const envl = nullptr;
+#include "trc_render_pwg_body.inc"
+}
+template <int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_env(const KRenderEnv kpe) {
+    constexpr bool SOBOL = false, ENV = true;
+    const KRender& kp = kpe.kp;
+    const EnvLight* const envl = &kpe.el;
 #include "trc_render_pwg_body.inc"
 }
 
@@ -283,12 +303,21 @@ __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INT
 // TEX (image textures): k_render_strip_tex<LDS, INTEGRATOR>, the same body (trc_render_strip_body.inc) with hit_color<true>
 template <bool LDS, int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip(const KRender kp) {
-    constexpr bool TEX = false;
+    constexpr bool TEX = false, ENV = false;
+    const EnvLight* const envl = nullptr;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_tex(const KRender kp) {
-    constexpr bool SOBOL = false, TEX = true;
+    constexpr bool SOBOL = false, TEX = true, ENV = false;
+    const EnvLight* const envl = nullptr;
+#include "trc_render_strip_body.inc"
+}
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_env(const KRenderEnv kpe) {
+    constexpr bool SOBOL = false, ENV = true;
+    const KRender& kp = kpe.kp;
+    const EnvLight* const envl = &kpe.el;
 #include "trc_render_strip_body.inc"
 }
 
@@ -312,6 +341,16 @@ constexpr RenderKernels render_kernels() {
         t.pwg[kVariantPlain] = {&k_render_pwg<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR)};
         t.pwg[kVariantTex] = {&k_render_pwg_tex<INTEGRATOR>, pwg_simd_waves(INTEGRATOR)};
         if constexpr (kSobol) t.pwg[kVariantSobol] = {&k_render_pwg<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR)};
+    }
+    if constexpr (INTEGRATOR == TRC_INTEGRATOR_MIS) {        // TRC_FLAG_ENV_LIGHT: traceMIS only
+        t.one[kVariantEnv] = {nullptr, render_waves(LDS, false, INTEGRATOR), &k_render_env<LDS, INTEGRATOR, false>};
+        t.one[kVariantEnvTex] = {nullptr, render_waves(LDS, false, INTEGRATOR), &k_render_env<LDS, INTEGRATOR, true>};
+        t.strip[kVariantEnv] = {nullptr, strip_waves(INTEGRATOR), &k_render_strip_env<LDS, INTEGRATOR, false>};
+        t.strip[kVariantEnvTex] = {nullptr, strip_waves(INTEGRATOR), &k_render_strip_env<LDS, INTEGRATOR, true>};
+        if constexpr (!LDS) {
+            t.pwg[kVariantEnv] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, false>};
+            t.pwg[kVariantEnvTex] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, true>};
+        }
     }
     return t;
 }

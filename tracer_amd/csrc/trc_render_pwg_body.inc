@@ -1,6 +1,6 @@
 // trc_render_pwg_body.inc -- the body of k_render_pwg / k_render_pwg_tex, included as the body of each kernel (trc_render_kernels.hpp) rather than
 // called from a helper: the kernel of the parent commit keeps its code and its name, and the image-texture twin shares the source.
-// Expects in scope: kp, INTEGRATOR, SOBOL, TEX.
+// Expects in scope: kp, INTEGRATOR, SOBOL, TEX, ENV and envl (the environment map's sampling tables of ENV, else null).
     const DScene& sc = kp.ks.sc;
     {
         const uint4* src = reinterpret_cast<const uint4*>(sc.blob);
@@ -29,7 +29,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX, ENV>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt, envl);
         }
         r_rays = wave_sum(park[kParkRays * kBlock]); r_shaded = wave_sum(park[kParkShaded * kBlock]);
     } else {
@@ -39,7 +39,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt, envl);
         }
         r_rays = wave_sum(n_rays); r_shaded = wave_sum(n_shaded);
     }

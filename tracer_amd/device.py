@@ -124,6 +124,8 @@ def _load(path, hooks=False):
         L.trc_unary_test.argtypes = [vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32)]
         L.trc_debug_denoise_state.argtypes = [vp, vp, vp, vp]
         L.trc_texture_sample_test.argtypes = [vp, u32, vp, C.c_size_t, vp]
+        L.trc_debug_env_tables.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_float)]
+        L.trc_env_light_test.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -152,6 +154,7 @@ class Tracer:
 
     def __init__(self, device=0, fast_math=False, hooks=False):
         self._L = lib(fast_math, hooks)
+        self._env_shape = (0, 0)         # (h, w) of the environment map set through this object
         self._h = C.c_void_p()
         st = self._L.trc_create(device, C.byref(self._h))
         if st != abi.OK:
@@ -184,10 +187,12 @@ class Tracer:
         """(h, w, 3) float32 equirectangular environment; None returns to the constant one."""
         if rgb is None:
             self._check(self._L.trc_set_environment_map(self._h, 0, 0, None), "trc_set_environment_map")
+            self._env_shape = (0, 0)
             return
         assert rgb.dtype == np.float32 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.flags.c_contiguous
         self._check(self._L.trc_set_environment_map(self._h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data),
                     "trc_set_environment_map")
+        self._env_shape = rgb.shape[:2]
 
     def upload_textures(self, images):
         """Image textures: a list of (h, w, 3) float32 arrays, rows bottom-up (what host.load_png returns); a material with
@@ -207,6 +212,29 @@ class Tracer:
         out = np.empty((uv.shape[0], 3), dtype=np.float32)
         self._check(self._L.trc_texture_sample_test(self._h, index, uv.ctypes.data, uv.shape[0], out.ctypes.data), "trc_texture_sample_test")
         return out
+
+    def env_tables(self):
+        """hooks build only: the sampling tables of TRC_FLAG_ENV_LIGHT for the current map -> dict of weight (H, W) float32,
+        rows (H, W, 2) uint32 {threshold, alias}, marg (H, 2) uint32, total (float), build_ms (float)."""
+        H, W = self._env_shape
+        weight = np.empty((H, W), np.float32)
+        rows = np.empty((H, W, 2), np.uint32)
+        marg = np.empty((H, 2), np.uint32)
+        total, ms = C.c_double(), C.c_float()
+        self._check(self._L.trc_debug_env_tables(self._h, weight.ctypes.data, rows.ctypes.data, marg.ctypes.data, C.byref(total), C.byref(ms)),
+                    "trc_debug_env_tables")
+        return dict(weight=weight, rows=rows, marg=marg, total=total.value, build_ms=ms.value)
+
+    def env_light_test(self, draws=None, dirs=None):
+        """hooks build only: the render kernels' environment-light sampler on (n, 6) uint32 draws (row index, row alias, cell index,
+        cell alias, then two float32 bit patterns) -> (n, 4) float32 direction + pdf, and its pdf of (m, 3) float32 directions -> (m,)"""
+        d = np.ascontiguousarray(np.zeros((0, 6), np.uint32) if draws is None else draws, dtype=np.uint32).reshape(-1, 6)
+        v = np.ascontiguousarray(np.zeros((0, 3), np.float32) if dirs is None else dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((d.shape[0], 4), np.float32)
+        pdf = np.empty(v.shape[0], np.float32)
+        self._check(self._L.trc_env_light_test(self._h, d.ctypes.data, d.shape[0], out.ctypes.data, v.ctypes.data, v.shape[0], pdf.ctypes.data),
+                    "trc_env_light_test")
+        return out, pdf
 
     def tonemap(self):
         """fragmentShader's auto-exposure + ACES on the accumulator -> ((H, W, 4) uint8, rows top-down; exposure)."""
@@ -285,9 +313,9 @@ class Tracer:
 
     # --- the hot path --------------------------------------------------------------
     def render(self, spp=1, max_depth=8, integrator=abi.INTEGRATOR_PATH, frame0=0, tile_rank=0, tile_nranks=1,
-               collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None):
+               collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None, env_light=False):
         flags = ((abi.FLAG_COLLECT_STATS if collect_stats else 0) | (abi.FLAG_FIXED_ORDER if fixed_order else 0) |
-                 (abi.FLAG_SOBOL if sobol else 0) |
+                 (abi.FLAG_SOBOL if sobol else 0) | (abi.FLAG_ENV_LIGHT if env_light else 0) |
                  (0 if small_blocks is None else (abi.FLAG_SMALL_BLOCKS if small_blocks else abi.FLAG_LARGE_BLOCKS)))
         prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0, tile_rank=tile_rank,
                          tile_nranks=tile_nranks, flags=flags, view_height=view_height)
