@@ -7,8 +7,9 @@
 //              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
 //              as the reference's host binds uv_test.png (AAPLRenderer.mm:385-390)
-//   trc_render --pbrt scene.pbrt [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
+//   trc_render --pbrt scene.pbrt [--triangle-materials] [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
 //              a whole pbrt-v3 scene (camera, film, lights, materials, spheres, meshes: trc_host_scene_load_pbrt)
+//              --triangle-materials: every mesh keeps its own material (TRC_PBRT_TRIANGLE_MATERIALS + trc_upload_triangle_materials)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,7 +31,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false;
+    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -46,6 +47,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-sah") device_sah = true;
         else if (a == "--sobol") sobol = true;
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
+        else if (a == "--triangle-materials") tri_materials = true;            // --pbrt: per-mesh materials instead of material 19
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -69,9 +71,10 @@ int main(int argc, char** argv) {
         trc_host_mesh_view(mesh, &mv, &n_mv, &mi, &n_mi);
     }
     trc_Camera cam;
+    if (tri_materials && pbrt_path.empty()) { std::fprintf(stderr, "--triangle-materials needs --pbrt\n"); return 2; }
     if (!pbrt_path.empty()) {
         trc_pbrt_info info;
-        if (trc_host_scene_load_pbrt(pbrt_path.c_str(), &hs, &cam, &info, nullptr, 0) != TRC_OK) {
+        if (trc_host_scene_load_pbrt_flags(pbrt_path.c_str(), tri_materials ? TRC_PBRT_TRIANGLE_MATERIALS : 0u, &hs, &cam, &info, nullptr, 0) != TRC_OK) {
             std::fprintf(stderr, "cannot read a scene from %s\n", pbrt_path.c_str());
             return 1;
         }
@@ -115,6 +118,12 @@ int main(int argc, char** argv) {
         else CHECK(trc_upload_scene_lbvh(ctx, &leaves));
     } else {
         CHECK(trc_upload_scene(ctx, &scene));
+    }
+    if (tri_materials) {                          // one material per triangle instead of the reference's 19 for all
+        const uint32_t* tm = nullptr;
+        uint32_t n_tm = 0;
+        trc_host_scene_triangle_materials(hs, &tm, &n_tm);
+        if (n_tm) CHECK(trc_upload_triangle_materials(ctx, tm, n_tm));
     }
     std::vector<float> cloud;
     if (kind == TRC_SCENE_CORNELL_VOLUME) {

@@ -45,8 +45,10 @@ extern "C" {
  * 7: SVGF denoiser stage: trc_gbuffer_texel, trc_denoise_params, trc_denoise_default_params, trc_denoise, trc_download_denoised,
  *    trc_tonemap_denoised, trc_download_gbuffer, trc_denoise_reset (nothing existing changed)
  * 8: image textures: trc_image, trc_upload_textures, trc_host_load_png (nothing existing changed)
- * 9: TRC_FLAG_ENV_LIGHT: the environment map as an importance-sampled light of traceMIS (nothing existing changed) */
-#define TRC_ABI_VERSION 9
+ * 9: TRC_FLAG_ENV_LIGHT: the environment map as an importance-sampled light of traceMIS (nothing existing changed)
+ * 10: per-triangle materials: trc_upload_triangle_materials, trc_host_scene_load_pbrt_flags (TRC_PBRT_TRIANGLE_MATERIALS),
+ *    trc_host_scene_triangle_materials (nothing existing changed) */
+#define TRC_ABI_VERSION 10
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -474,6 +476,20 @@ typedef struct trc_image {
     const float* rgb;            /* 3 * width * height floats, rows bottom-up */
 } trc_image;
 trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n);
+
+/* Per-triangle materials.  The reference hard-codes material 19 for every triangle (Triangle.hh:82), and so does every scene
+ * upload here; this call gives triangle t (the t-th of idxList, the pIndex of its leaf) the material material[t] instead.
+ *  - Everything that reads a hit's material follows: tracePath, traceMIS, traceVolume (the medium of a material), the SPPM
+ *    camera and photon passes, the G-buffer's id and albedo planes, trc_trace_rays' hit.material, the work counters.
+ *  - n_triangles must equal the scene's n_index / 3 and every index must be below its n_material: TRC_ERR_INVALID_ARG
+ *    otherwise, and nothing changes.  TRC_ERR_NO_SCENE before any trc_upload_scene*.
+ *  - material == NULL with n_triangles == 0 restores 19 everywhere; every trc_upload_scene* restores it too.
+ *  - Launches kept back for coalescing run first; the G-buffer and the denoiser history are dropped, as are the recorded block
+ *    costs of the launch planner.  trc_sppm_frames sees the new materials at its next call: a consistent SPPM pass restarts
+ *    with trc_sppm_init.  Image textures stay active as before (the whole material table decides that).
+ *  - traceMIS still samples squareList[5] / [6] only: an emissive triangle is reached by BSDF sampling alone, with the
+ *    emitter-hit weighting an emissive material 19 gets. */
+trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material, uint32_t n_triangles);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -873,7 +889,7 @@ trc_status trc_host_mesh_load_ply(const char* path, trc_host_mesh** out);
  * (tessellated) through the transformation and attribute stacks, Include.  Mapping onto the reference's primitives
  * (tracer_amd/host/pbrt_scene.cpp): sphere -> trc_Sphere; a trianglemesh that is an axis-aligned rectangle ->
  * trc_Square, emitters placed at squareList[5] / [6] (the two lights traceMIS samples); any other mesh -> triangles with
- * material 19.
+ * material 19 (the first mesh's material; per-mesh materials: trc_host_scene_load_pbrt_flags below).
  * `info` / `shapes` (optional, up to `capacity` entries in file order) describe what was parsed and what it became;
  * the scene handle is used like one from trc_host_scene_create. */
 enum trc_pbrt_material { TRC_PBRT_MATTE = 0, TRC_PBRT_PLASTIC = 1, TRC_PBRT_METAL = 2, TRC_PBRT_MIRROR = 3,
@@ -917,6 +933,18 @@ typedef struct trc_pbrt_shape {
 } trc_pbrt_shape;
 trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene** out_scene, trc_Camera* out_camera,
                                     trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity);
+/* trc_host_scene_load_pbrt with options; flags == 0 is trc_host_scene_load_pbrt, output for output.
+ * TRC_PBRT_TRIANGLE_MATERIALS: every mesh shape (trianglemesh, plymesh, tessellated quadrics, instance copies; emitters and
+ * checkerboards included) also gets its own material, interned into the table after index 19 -- the materials of today's
+ * load keep their indices, 19 included, so a caller that ignores the array renders the same scene.  Its shape record's
+ * mapped_material names that material, n_triangle_material_conflicts stays 0, and trc_host_scene_triangle_materials returns
+ * one index per triangle for trc_upload_triangle_materials.  Unknown flag bits: TRC_ERR_INVALID_ARG. */
+#define TRC_PBRT_TRIANGLE_MATERIALS 1u
+trc_status trc_host_scene_load_pbrt_flags(const char* path, uint32_t flags, trc_host_scene** out_scene, trc_Camera* out_camera,
+                                          trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity);
+/* the per-triangle material indices of a scene loaded with TRC_PBRT_TRIANGLE_MATERIALS (valid until destroy); *n = 0 for
+ * any other handle */
+void       trc_host_scene_triangle_materials(const trc_host_scene* s, const uint32_t** out, uint32_t* n);
 
 /* procedural stand-in for the missing/untravelling assets: a displaced
  * UV-sphere "ball" with n_lat x n_lon quads (2 triangles each) */

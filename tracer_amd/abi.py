@@ -7,7 +7,7 @@ Triangle,Texture,Material,Camera}.hh (see the header for file:line).
 """
 import ctypes as C
 
-TRC_ABI_VERSION = 9
+TRC_ABI_VERSION = 10
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
@@ -162,6 +162,7 @@ PBRT_MATTE, PBRT_PLASTIC, PBRT_METAL, PBRT_MIRROR, PBRT_GLASS, PBRT_OTHER = rang
 PBRT_SHAPE_SPHERE, PBRT_SHAPE_TRIANGLEMESH, PBRT_SHAPE_DISK, PBRT_SHAPE_CYLINDER, PBRT_SHAPE_PLYMESH = 0, 3, 6, 7, 8
 PBRT_SHAPE_CONE, PBRT_SHAPE_PARABOLOID, PBRT_SHAPE_HYPERBOLOID = 9, 10, 11
 PBRT_TEX_NONE, PBRT_TEX_CHECKERBOARD, PBRT_TEX_OTHER = 0, 1, 2
+PBRT_TRIANGLE_MATERIALS = 1         # trc_host_scene_load_pbrt_flags
 
 
 class PbrtInfo(C.Structure):
@@ -248,7 +249,7 @@ DEVICE_SYMBOLS = [
     "trc_device_info", "trc_device_pci_bus_id", "trc_shard_seed", "trc_group_compose_samples", "trc_group_compose_samples_async", "trc_group_unique_id", "trc_group_init", "trc_group_reduce_accum", "trc_group_reduce_accum_async", "trc_group_allreduce_mean_accum", "trc_download_composed", "trc_group_finalize",
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape",
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
-    "trc_upload_textures",
+    "trc_upload_textures", "trc_upload_triangle_materials",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
@@ -259,5 +260,5 @@ HOST_SYMBOLS = [
     "trc_host_scene_view", "trc_host_scene_load_pbrt", "trc_host_mesh_load_obj", "trc_host_mesh_load_pbrt", "trc_host_mesh_load_ply", "trc_host_load_hdr", "trc_host_mesh_make_ball", "trc_host_mesh_replicate", "trc_host_mesh_from_arrays",
     "trc_host_mesh_view", "trc_host_mesh_destroy", "trc_host_make_density_info", "trc_host_make_cloud",
     "trc_host_load_density_pbrt", "trc_host_free", "trc_host_write_png", "trc_host_sobol_matrices32",
-    "trc_host_sobol_interval_tables", "trc_host_load_png",
+    "trc_host_sobol_interval_tables", "trc_host_load_png", "trc_host_scene_load_pbrt_flags", "trc_host_scene_triangle_materials",
 ]

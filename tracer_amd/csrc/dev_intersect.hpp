@@ -348,6 +348,13 @@ TRC_DEV bool cube_hit_test(const SceneRef& S, uint32_t index, const Ray& ray, fl
     return true;
 }
 
+// A triangle's material: the reference hard-codes 19 (Triangle.hh:82); trc_upload_triangle_materials puts one per triangle in dword 15
+// of the attribute record (every scene upload writes 19 there).  TRC_TRIANGLE_MATERIALS 0 keeps the constant: the production render
+// kernels (trc_render_*.hip), whose register allocation the read would disturb (config 3: +1.4 %, profiles/r07/trimat.txt); their
+// twins (trc_render_*_tm.hip) read the dword and are launched only while per-triangle materials are set.  Every other kernel reads it.
+#ifndef TRC_TRIANGLE_MATERIALS
+#define TRC_TRIANGLE_MATERIALS 1
+#endif
 struct TriPos { float4 a, b, c; };       // the 48-byte position record of one triangle
 TRC_DEV TriPos load_tripos(const SceneRef& S, uint32_t index) {
     const uint32_t* tp = S.blob + S.off_tripos + (size_t)index * kTriPosDwords;
@@ -384,7 +391,7 @@ TRC_DEV bool triangle_hit_test(const SceneRef& S, uint32_t index, const TriPos& 
     rec.uv.x = (u * q2.w + v * q3.y) + w * q2.y;            // uv0 = q2.yz, uv1 = q2.w q3.x, uv2 = q3.yz
     rec.uv.y = (u * q3.x + v * q3.z) + w * q2.z;
     check_face(rec, ray);
-    rec.material = 19;                                      // hard-coded, Triangle.hh:82
+    rec.material = TRC_TRIANGLE_MATERIALS ? __float_as_uint(q3.w) : 19u;      // Triangle.hh:82 hard-codes 19 (see above)
     return true;
 }
 
@@ -415,7 +422,7 @@ TRC_DEV void triangle_record(const SceneRef& S, uint32_t index, const Ray& ray, 
     rec.uv.x = (u * q2.w + v * q3.y) + w * q2.y;
     rec.uv.y = (u * q3.x + v * q3.z) + w * q2.z;
     check_face(rec, ray);
-    rec.material = 19;                                      // hard-coded, Triangle.hh:82
+    rec.material = TRC_TRIANGLE_MATERIALS ? __float_as_uint(q3.w) : 19u;
 }
 
 // ---------------------------------------------------------------- Scene::hit

@@ -17,7 +17,9 @@
 //   cube    160 B : inverse c0..c3 (12), model c0..c3 (12), normal c0..c2 (9), box min/max (6), material
 //   material 32 B : type, texture type, albedo.rgb
 //   triangle positions 48 B : v0, v1, v2 as float4 (what a TEST reads)
-//   triangle attributes 64 B: n0 n1 n2 (9), uv0 uv1 uv2 (6)  (read only on an accepted hit)
+//   triangle attributes 64 B: n0 n1 n2 (9), uv0 uv1 uv2 (6), material (read only on an accepted hit).  The reference
+//                             hard-codes material 19 for every triangle (Triangle.hh:82): every scene upload writes 19,
+//                             trc_upload_triangle_materials replaces it per triangle (dword 15, the .w of the uv load)
 //
 // Blob order: spheres, squares, cubes, materials, fat nodes (BFS), triangle positions, triangle
 // attributes.  Every workgroup stages the PREFIX that fits kLdsSceneBytes into LDS: always the

@@ -39,7 +39,9 @@ __global__ void __launch_bounds__(256) k_seed(uint32_t* rng, uint32_t n_pixels, 
 }
 
 // blob triangle records from the caller's arrays (trc_scene_prep.hpp): one thread per triangle, 3 gathered 32-byte
-// vertices in, 7 float4 out
+// vertices in, 7 float4 out.  The attribute record's last dword is the triangle's material: 19 (Triangle.hh:82) until
+// trc_upload_triangle_materials says otherwise
+constexpr uint32_t kTriangleMaterial = 19u;
 __global__ void __launch_bounds__(256) k_repack_triangles(const trc_TriangleVertex* __restrict__ verts, const uint32_t* __restrict__ idx,
                                                           uint32_t n_tri, float4* __restrict__ tripos, float4* __restrict__ triattr) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -51,7 +53,15 @@ __global__ void __launch_bounds__(256) k_repack_triangles(const trc_TriangleVert
     triattr[4 * (size_t)t] = make_float4(a.n[0], a.n[1], a.n[2], b.n[0]);
     triattr[4 * (size_t)t + 1] = make_float4(b.n[1], b.n[2], c.n[0], c.n[1]);
     triattr[4 * (size_t)t + 2] = make_float4(c.n[2], a.uv[0], a.uv[1], b.uv[0]);
-    triattr[4 * (size_t)t + 3] = make_float4(b.uv[1], c.uv[0], c.uv[1], 0.0f);
+    triattr[4 * (size_t)t + 3] = make_float4(b.uv[1], c.uv[0], c.uv[1], __uint_as_float(kTriangleMaterial));
+}
+
+// trc_upload_triangle_materials: dword 15 of every triangle's attribute record, from the caller's array (checked on the host:
+// every index below n_material) or 19 for all (material == nullptr)
+__global__ void __launch_bounds__(256) k_triangle_materials(const uint32_t* __restrict__ material, uint32_t n_tri, uint32_t* __restrict__ triattr) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_tri) return;
+    triattr[(size_t)t * kTriAttrDwords + 15u] = material ? material[t] : kTriangleMaterial;
 }
 
 // BVH::buildNode for the triangles (AAPLRenderer.mm:575-589 + BVH.hh:273-314): the box of the three vertices -- std::max({a, b, c}) /
@@ -93,6 +103,7 @@ __global__ void __launch_bounds__(256) k_triangle_leaves(const trc_TriangleVerte
 
 trc_status trc_repack_triangles(trc_ctx* ctx, const trc_scene* s, const DScene& sc, uint32_t* d_blob, trc_BVH* d_tri_leaves) {
     const uint32_t n_tri = s->n_index / 3;
+    ctx->tri_materials = false;                  // every triangle is material 19 again
     if (n_tri == 0) return TRC_OK;
     trc_TriangleVertex* d_verts = nullptr;
     uint32_t* d_idx = nullptr;
@@ -925,10 +936,13 @@ trc_status ensure_sobol_tables(trc_ctx* ctx, uint32_t m) {
 }
 
 // The render kernels a scene's launches pick from (trc_render_config.hpp: one table per tree residence and integrator)
-const RenderKernels& render_family(bool lds_scene, uint32_t integrator) {
+// (tri_materials: their twins that read each triangle's material, trc_render_*_tm.hip)
+const RenderKernels& render_family(bool lds_scene, uint32_t integrator, bool tri_materials) {
     static const RenderKernels* const lds[3] = {&render_lds_path, &render_lds_mis, &render_lds_volume};
     static const RenderKernels* const mem[3] = {&render_mem_path, &render_mem_mis, &render_mem_volume};
-    return *(lds_scene ? lds : mem)[integrator];
+    static const RenderKernels* const lds_tm[3] = {&trimat::render_lds_path, &trimat::render_lds_mis, &trimat::render_lds_volume};
+    static const RenderKernels* const mem_tm[3] = {&trimat::render_mem_path, &trimat::render_mem_mis, &trimat::render_mem_volume};
+    return *(tri_materials ? (lds_scene ? lds_tm : mem_tm) : (lds_scene ? lds : mem))[integrator];
 }
 
 // One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
@@ -1322,6 +1336,40 @@ trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n
     return TRC_OK;
 }
 
+// per-triangle materials: dword 15 of the triangle attribute records (dev_scene.hpp), which every scene upload sets to 19
+trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material, uint32_t n_triangles) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return fail(ctx, TRC_ERR_NO_SCENE, "trc_upload_triangle_materials: no scene");
+    const DScene& sc = ctx->ks.sc;
+    if (material || n_triangles) {
+        if (!material) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_triangle_materials: material == NULL with n_triangles > 0");
+        if (n_triangles != sc.n_triangles) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_triangle_materials: n_triangles != the scene's n_index / 3");
+        for (uint32_t t = 0; t < n_triangles; ++t)
+            if (material[t] >= sc.n_materials) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_triangle_materials: material index out of range");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (sc.n_triangles) {
+        uint32_t* d_mat = nullptr;
+        if (material) HIP_TRY(ctx, hipMalloc((void**)&d_mat, (size_t)sc.n_triangles * 4));
+        trc_status st = material ? trc_copy_to_device(ctx, d_mat, material, (size_t)sc.n_triangles * 4, ctx->stream) : TRC_OK;
+        if (st == TRC_OK) {
+            hipLaunchKernelGGL(k_triangle_materials, dim3((sc.n_triangles + 255) / 256), dim3(256), 0, ctx->stream, d_mat, sc.n_triangles,
+                               ctx->d_blob + sc.off_triattr);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) st = fail(ctx, TRC_ERR_HIP, "k_triangle_materials");
+        }
+        (void)hipFree(d_mat);
+        if (st != TRC_OK) return st;
+    }
+    ctx->tri_materials = material != nullptr && sc.n_triangles != 0;
+    // what the frame shows changed: the G-buffer and the denoiser's history are stale, and the recorded block costs are another
+    // picture's (as after trc_upload_scene)
+    trc_denoise_invalidate(ctx);
+    ctx->cost_valid = false; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
+    return TRC_OK;
+}
+
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height) {
     { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
     if (!ctx || width == 0 || height == 0 || width > 65535u * 8u || height > 65535u * 8u) return TRC_ERR_INVALID_ARG;
@@ -1644,7 +1692,8 @@ static trc_status render_cold_head(trc_ctx* ctx, const trc_params* p, uint32_t h
 static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
     KRender& kp = r.kp;
     const int integrator = (int)p->integrator;
-    const RenderKernels& family = render_family(ctx->lds_scene, p->integrator);
+    const RenderKernels& family = render_family(ctx->lds_scene, p->integrator, ctx->tri_materials);
+    const RenderKernel& render_dense = ctx->tri_materials ? trimat::render_dense : ::render_dense;
     // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD
     r.dense = ctx->lds_scene && integrator == TRC_INTEGRATOR_PATH && !r.stats && !r.sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
               ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * render_dense.waves &&

@@ -165,6 +165,7 @@ struct trc_ctx {
     // materials (~0u: none) -- an image is active, and the _tex kernels launched, when it is below n_tex
     float* d_tex_texels = nullptr; uint4* d_tex_desc = nullptr; uint32_t n_tex = 0; uint32_t scene_min_image = ~0u;
     bool tex_active() const { return scene_min_image < n_tex; }
+    bool tri_materials = false;         // trc_upload_triangle_materials holds an array: launch the render kernels' trimat twins
     // TRC_FLAG_ENV_LIGHT: the map's sampling tables (trc_envlight.hip), built at the first flagged render after trc_set_environment_map
     uint8_t* d_envl = nullptr; double envl_total = 0.0; float envl_build_ms = 0.0f;
     bool cost_env = false;              // the flag of the launches whose block costs are recorded (drop_stale_costs)

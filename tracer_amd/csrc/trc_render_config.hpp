@@ -156,3 +156,8 @@ struct RenderKernels {
 };
 extern const RenderKernels render_lds_path, render_lds_mis, render_lds_volume, render_mem_path, render_mem_mis, render_mem_volume;
 extern const RenderKernel render_dense;      // k_render_dense (trc_render_lds.hip): tracePath, LDS-resident tree, production, PCG
+// the same tables over the twins that read each triangle's material (trc_render_*_tm.hip; dev_intersect.hpp TRC_TRIANGLE_MATERIALS)
+namespace trimat {
+extern const RenderKernels render_lds_path, render_lds_mis, render_lds_volume, render_mem_path, render_mem_mis, render_mem_volume;
+extern const RenderKernel render_dense;
+}

@@ -7,6 +7,16 @@
 
 #include "trc_render_config.hpp"
 
+// the per-triangle-material twins (TRC_TRIANGLE_MATERIALS 1: trc_render_*_tm.hip) are the same kernels and tables in namespace trimat
+#if TRC_TRIANGLE_MATERIALS
+#define TRC_RENDER_NS_BEGIN namespace trimat {
+#define TRC_RENDER_NS_END }
+#else
+#define TRC_RENDER_NS_BEGIN
+#define TRC_RENDER_NS_END
+#endif
+TRC_RENDER_NS_BEGIN
+
 // One pixel block (8x8 pixels on 64 lanes, or 4x4 on 16) of kernelPathTracing: all `spp` samples of every pixel, RNG texel
 // and accumulator read and written once.  `slot` = position of the block in the launch order; `stack` / `lvstack` / `ovf` =
 // this lane's columns of the wavefront's traversal stack.  Shared by k_render (one block per one-wavefront workgroup) and
@@ -354,3 +364,4 @@ constexpr RenderKernels render_kernels() {
     }
     return t;
 }
+TRC_RENDER_NS_END

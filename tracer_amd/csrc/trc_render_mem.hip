@@ -3,10 +3,15 @@
 // trc_render_mem_volume.hip, translation units of their own since round 5 because the families want different compiler options
 // (Makefile: EXTRA_*; this one keeps the defaults: -disable-machine-sink costs traceMIS 1.5 %).  Compiled WITH dev_vec.hpp's guard-free forms since their guards became one or two instructions
 // (profiles/r04/guard_cost_ab.txt).  Definitions: trc_render_kernels.hpp; launched from trc_abi.hip.
+#ifndef TRC_TRIANGLE_MATERIALS
+#define TRC_TRIANGLE_MATERIALS 0      // triangles keep material 19; the twins reading per-triangle materials: trc_render_*_tm.hip
+#endif
 #ifndef TRC_FAST_UNARY
 #define TRC_FAST_UNARY 1
 #endif
 #include "trc_render_kernels.hpp"
 
+TRC_RENDER_NS_BEGIN
 // the kernel table (trc_render_config.hpp)
 const RenderKernels render_mem_mis = render_kernels<false, TRC_INTEGRATOR_MIS>();
+TRC_RENDER_NS_END

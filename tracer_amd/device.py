@@ -117,6 +117,7 @@ def _load(path, hooks=False):
     L.trc_download_gbuffer.argtypes = [vp, vp]
     L.trc_denoise_reset.argtypes = [vp]
     L.trc_upload_textures.argtypes = [vp, C.POINTER(abi.Image), u32]
+    L.trc_upload_triangle_materials.argtypes = [vp, vp, u32]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -205,6 +206,17 @@ class Tracer:
             arr[k].width, arr[k].height = a.shape[1], a.shape[0]
             arr[k].rgb = a.ctypes.data_as(C.POINTER(C.c_float))
         self._check(self._L.trc_upload_textures(self._h, arr if images else None, len(images)), "trc_upload_textures")
+
+    def upload_triangle_materials(self, material):
+        """Per-triangle materials (trc_upload_triangle_materials): one uint32 material index per triangle of the uploaded scene, in
+        index-list order; None restores material 19 on every triangle."""
+        if material is None:
+            self._check(self._L.trc_upload_triangle_materials(self._h, None, 0), "trc_upload_triangle_materials")
+            return
+        m = np.ascontiguousarray(material, dtype=np.uint32).ravel()
+        # an empty array is an array of the wrong length for a scene with triangles (refused), not None: never pass it as NULL
+        buf = m if m.size else np.zeros(1, np.uint32)
+        self._check(self._L.trc_upload_triangle_materials(self._h, buf.ctypes.data, m.size), "trc_upload_triangle_materials")
 
     def texture_sample(self, index, uv):
         """hooks build only: the render kernels' lookup of image `index` at (n, 2) float32 uv -> (n, 3) float32."""

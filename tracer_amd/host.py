@@ -48,6 +48,11 @@ def lib():
         L.trc_host_scene_load_pbrt.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(abi.Camera),
                                                C.POINTER(abi.PbrtInfo), C.POINTER(abi.PbrtShape), C.c_uint32]
         L.trc_host_scene_load_pbrt.restype = C.c_int32
+        L.trc_host_scene_load_pbrt_flags.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(abi.Camera),
+                                                     C.POINTER(abi.PbrtInfo), C.POINTER(abi.PbrtShape), C.c_uint32]
+        L.trc_host_scene_load_pbrt_flags.restype = C.c_int32
+        L.trc_host_scene_triangle_materials.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+        L.trc_host_scene_triangle_materials.restype = None
         L.trc_host_scene_destroy.argtypes = [C.c_void_p]
         L.trc_host_scene_destroy.restype = None
         L.trc_host_scene_view.argtypes = [C.c_void_p, C.POINTER(abi.Scene)]
@@ -193,17 +198,33 @@ class HostScene:
         lib().trc_host_scene_view(self._h, C.byref(self.view))
 
     @classmethod
-    def from_pbrt(cls, path, max_shapes=4096):
-        """A whole scene from a pbrt-v3 file (trc_host_scene_load_pbrt) -> (scene, camera, info, [shape descriptions])."""
+    def from_pbrt(cls, path, max_shapes=4096, triangle_materials=False, flags=None):
+        """A whole scene from a pbrt-v3 file (trc_host_scene_load_pbrt) -> (scene, camera, info, [shape descriptions]).
+        triangle_materials=True loads with TRC_PBRT_TRIANGLE_MATERIALS (trc_host_scene_load_pbrt_flags): every mesh keeps its own
+        material, and the result gains a fifth item, the (n_triangles,) uint32 array for Tracer.upload_triangle_materials.
+        flags: the raw flag word of trc_host_scene_load_pbrt_flags (result without the array)."""
         self = cls.__new__(cls)
         self._h, self._mesh = C.c_void_p(), None
         cam, info = abi.Camera(), abi.PbrtInfo()
         shapes = (abi.PbrtShape * max_shapes)()
-        _check(lib().trc_host_scene_load_pbrt(os.fsencode(path), C.byref(self._h), C.byref(cam), C.byref(info), shapes,
-                                              max_shapes), f"trc_host_scene_load_pbrt({path})")
+        if triangle_materials or flags is not None:
+            f = (abi.PBRT_TRIANGLE_MATERIALS if triangle_materials else 0) | (flags or 0)
+            _check(lib().trc_host_scene_load_pbrt_flags(os.fsencode(path), f, C.byref(self._h), C.byref(cam), C.byref(info), shapes,
+                                                        max_shapes), f"trc_host_scene_load_pbrt_flags({path})")
+        else:
+            _check(lib().trc_host_scene_load_pbrt(os.fsencode(path), C.byref(self._h), C.byref(cam), C.byref(info), shapes,
+                                                  max_shapes), f"trc_host_scene_load_pbrt({path})")
         self.view = abi.Scene()
         lib().trc_host_scene_view(self._h, C.byref(self.view))
-        return self, cam, info, [shapes[i] for i in range(min(info.n_shapes, max_shapes))]
+        out = (self, cam, info, [shapes[i] for i in range(min(info.n_shapes, max_shapes))])
+        return out + (self.triangle_materials(),) if triangle_materials else out
+
+    def triangle_materials(self):
+        """(n,) uint32 copy of trc_host_scene_triangle_materials: one material per triangle, n = 0 unless loaded with
+        TRC_PBRT_TRIANGLE_MATERIALS."""
+        p, n = C.POINTER(C.c_uint32)(), C.c_uint32()
+        lib().trc_host_scene_triangle_materials(self._h, C.byref(p), C.byref(n))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
 
     @property
     def n_leaves(self):

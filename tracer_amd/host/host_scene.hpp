@@ -15,6 +15,7 @@ struct trc_host_scene {
     std::vector<trc_TriangleVertex> vertices;
     std::vector<uint32_t> indices;
     std::vector<trc_Material> materials;
+    std::vector<uint32_t> triangle_materials;     // one per triangle: pbrt scenes loaded with TRC_PBRT_TRIANGLE_MATERIALS only
 };
 
 namespace trc {

@@ -173,11 +173,11 @@ bool as_axis_aligned_rectangle(const std::vector<trc_float3>& P, const std::vect
     return false;
 }
 
-}  // namespace
-
-extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene** out_scene, trc_Camera* out_camera,
-                                              trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity) {
+trc_status load_pbrt(const char* path, uint32_t flags, trc_host_scene** out_scene, trc_Camera* out_camera,
+                     trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity) {
     if (!path || !out_scene) return TRC_ERR_INVALID_ARG;
+    if (flags & ~TRC_PBRT_TRIANGLE_MATERIALS) return TRC_ERR_INVALID_ARG;
+    const bool per_triangle = (flags & TRC_PBRT_TRIANGLE_MATERIALS) != 0;
     *out_scene = nullptr;
     std::string text;
     if (!read_pbrt_text(path, 0, text)) return TRC_ERR_INVALID_ARG;
@@ -238,6 +238,10 @@ extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene*
     bool have_tri_material = false;
     trc_Material tri_material = make_material(TRC_MAT_LAMBERT);
     tri_material.textureInfo.albedo = f3(0.5f);
+    // TRC_PBRT_TRIANGLE_MATERIALS: every mesh's own material, interned after the file is read (behind index 19, so that the
+    // table of the plain load is a prefix of this one)
+    struct PendingMesh { int32_t type; float color[3]; bool checker; size_t desc; uint32_t first, count; };
+    std::vector<PendingMesh> meshes;
 
     auto fail = [&](trc_status st = TRC_ERR_INVALID_ARG) { delete s; return st; };
     for (;;) {
@@ -534,7 +538,9 @@ extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene*
                         if (checker) tri_material.textureInfo.type = TRC_TEX_CHECKER;
                         if (mtype == TRC_MAT_METAL || mtype == TRC_MAT_GLASS) tri_material.specular = 1;
                         have_tri_material = true;
-                    } else if (tri_material.type != mtype) inf.n_triangle_material_conflicts++;
+                    } else if (tri_material.type != mtype && !per_triangle) inf.n_triangle_material_conflicts++;
+                    if (per_triangle)
+                        meshes.push_back(PendingMesh{mtype, {mcolor[0], mcolor[1], mcolor[2]}, checker, descs.size(), ds.mapped_index, (uint32_t)(idx.size() / 3)});
                     M4 inv;
                     const bool has_inv = m4_inverse(world, inv);
                     const uint32_t base = (uint32_t)s->vertices.size();
@@ -577,6 +583,14 @@ extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene*
     // materials: index 19 is what every triangle uses (Triangle.hh:82)
     while (s->materials.size() < 19) s->materials.push_back(make_material(TRC_MAT_LAMBERT));
     if (s->materials.size() == 19) s->materials.push_back(tri_material); else s->materials[19] = tri_material;
+    if (per_triangle) {
+        s->triangle_materials.assign(s->indices.size() / 3, 19u);
+        for (const PendingMesh& m : meshes) {
+            const uint32_t mat = intern_material(m.type, m.color, m.checker);
+            descs[m.desc].mapped_material = mat;
+            std::fill(s->triangle_materials.begin() + m.first, s->triangle_materials.begin() + m.first + m.count, mat);
+        }
+    }
 
     // squares: non-emitters first, emitters from index 5 on (squareList[5] / [6] are THE lights of traceMIS)
     std::vector<const PendingSquare*> plain, lights;
@@ -644,4 +658,16 @@ extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene*
     if (shapes) for (uint32_t k = 0; k < capacity && k < descs.size(); ++k) shapes[k] = descs[k];
     *out_scene = s;
     return TRC_OK;
+}
+
+}  // namespace
+
+extern "C" trc_status trc_host_scene_load_pbrt(const char* path, trc_host_scene** out_scene, trc_Camera* out_camera,
+                                              trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity) {
+    return load_pbrt(path, 0u, out_scene, out_camera, info, shapes, capacity);
+}
+
+extern "C" trc_status trc_host_scene_load_pbrt_flags(const char* path, uint32_t flags, trc_host_scene** out_scene, trc_Camera* out_camera,
+                                                    trc_pbrt_info* info, trc_pbrt_shape* shapes, uint32_t capacity) {
+    return load_pbrt(path, flags, out_scene, out_camera, info, shapes, capacity);
 }

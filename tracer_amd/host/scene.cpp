@@ -287,6 +287,11 @@ void trc_host_scene_view(const trc_host_scene* s, trc_scene* out) {
     out->materials = s->materials.data();   out->n_material = (uint32_t)s->materials.size();
 }
 
+void trc_host_scene_triangle_materials(const trc_host_scene* s, const uint32_t** out, uint32_t* n) {
+    if (out) *out = s && !s->triangle_materials.empty() ? s->triangle_materials.data() : nullptr;
+    if (n) *n = s ? (uint32_t)s->triangle_materials.size() : 0u;
+}
+
 
 // GridDensityInfo::GridDensityInfo, Medium.hh:92-105
 void trc_host_make_density_info(float sigma_a, float sigma_s, float g, uint32_t nx, uint32_t ny, uint32_t nz,
