@@ -47,8 +47,10 @@ extern "C" {
  * 8: image textures: trc_image, trc_upload_textures, trc_host_load_png (nothing existing changed)
  * 9: TRC_FLAG_ENV_LIGHT: the environment map as an importance-sampled light of traceMIS (nothing existing changed)
  * 10: per-triangle materials: trc_upload_triangle_materials, trc_host_scene_load_pbrt_flags (TRC_PBRT_TRIANGLE_MATERIALS),
- *    trc_host_scene_triangle_materials (nothing existing changed) */
-#define TRC_ABI_VERSION 10
+ *    trc_host_scene_triangle_materials (nothing existing changed)
+ * 11: primary replay: trc_debug_primary_replays, knob no_primary_replay; trc_stats.rays keeps counting every Scene::hit of the
+ *    algorithm, the camera rays answered from the memo included (nothing existing changed) */
+#define TRC_ABI_VERSION 11
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -357,7 +359,9 @@ typedef struct trc_hit {
  * TRC_FLAG_COLLECT_STATS was set for the call. */
 typedef struct trc_stats {
     uint64_t paths;              /* W*H*spp of the tiles rendered */
-    uint64_t rays;               /* Scene::hit invocations (primary + bounce + shadow) */
+    uint64_t rays;               /* Scene::hit invocations of the reference's algorithm (primary + bounce + shadow).  The tracePath
+                                  * production kernels answer a pixel's repeated camera ray from a memo of its first walk instead of
+                                  * walking again (trc_debug_primary_replays counts those); such a ray is counted here all the same */
     uint64_t shaded;             /* material lookups (S_F / F evaluations' hits) */
     uint64_t n_descend, n_return;
     uint64_t n_leaf_sphere, n_leaf_square, n_leaf_cube, n_leaf_triangle;
@@ -644,6 +648,12 @@ typedef struct trc_launch_shape {
     double   clock_mhz;           /* hipDeviceAttributeClockRate, used for the conversion */
 } trc_launch_shape;
 trc_status trc_debug_launch_shape(trc_ctx* ctx, trc_launch_shape* out);
+/* Camera rays that were answered from the memo of the pixel's first walk instead of being walked, since the last trc_reset_stats.
+ * The reference's camera has no sub-pixel jitter, and with aperture 0 every sample of a pixel casts the same ray: k_render_dense
+ * and the persistent-workgroup tracePath kernels keep the first hit per pixel and launch, and replay it for every later sample
+ * whose origin has the same bits (never across launches; a lens, TRC_FLAG_SOBOL, TRC_FLAG_COLLECT_STATS, traceMIS / traceVolume and launches of fewer than 8
+ * samples always walk).  Included in trc_stats.rays.  Knob "no_primary_replay" (trc_debug_set) makes every camera ray walk. */
+trc_status trc_debug_primary_replays(trc_ctx* ctx, uint64_t* out);
 
 /* device info for the bench line */
 trc_status trc_device_info(trc_ctx* ctx, char* name, size_t name_len, int* cu_count, size_t* hbm_bytes);
@@ -772,7 +782,10 @@ trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table,
  * trc_stats.kernel_ms; one `launch` per frame), "descend_min" (n > 0: on trees read from memory the box-step loop of a wavefront goes on
  * while at least n lanes are still descending and others wait with a leaf; 0 = the scene's own value, 12, or 6 beyond 256 MiB), "camera_policy" (what trc_set_camera does with the recorded block costs: 0 = keeps them when the camera moved a little -- the view turned by
  * at most 5 degrees and the eye moved by at most 5 % of the scene's diagonal: the next launch is one pass ordered by the last launch's raw durations -- and forgets them
- * otherwise -- the next launch runs as a head + the rest; 1 always forgets, 2 always keeps the filtered costs, 3 always keeps and takes the raw durations: tools/moving_camera.py).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
+ * otherwise -- the next launch runs as a head + the rest; 1 always forgets, 2 always keeps the filtered costs, 3 always keeps and takes the raw durations: tools/moving_camera.py),
+ * "no_primary_replay" (every camera ray is walked: trc_debug_primary_replays), "replay_min_lanes" / "replay_chain" (measurement only: a trip of
+ * the render loop shades replayed hits alone where at least n lanes of the wavefront hold one, at most m such trips between two walks; 0 = the
+ * defaults, 1 and 1; 65 lanes = never).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
 
 /* ------------------------------------------------------------------ */

@@ -76,7 +76,7 @@ struct DFrame {
 enum StatSlot {
     kStatPaths = 0, kStatRays, kStatShaded, kStatDescend, kStatReturn,
     kStatLeafSphere, kStatLeafSquare, kStatLeafCube, kStatLeafTriangle,
-    kStatHitTriangle, kStatHitCube, kStatCount
+    kStatHitTriangle, kStatHitCube, kStatReplays, kStatCount
 };
 
 }  // namespace trcdev

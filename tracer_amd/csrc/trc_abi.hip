@@ -1137,7 +1137,7 @@ void trc_destroy(trc_ctx* ctx) {
     (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_stats); (void)hipFree(ctx->d_stats_sum); (void)hipFree(ctx->d_reduce_recv);
     (void)hipFree(ctx->d_block_cost); (void)hipFree(ctx->d_order_hist); (void)hipFree(ctx->d_split); (void)hipFree(ctx->d_whole); (void)hipFree(ctx->d_cost_est); (void)hipFree(ctx->d_qsplit); (void)hipFree(ctx->d_qwhole); (void)hipFree(ctx->d_swhole); (void)hipFree(ctx->d_launch); (void)hipFree(ctx->d_plan); (void)hipFree(ctx->d_plan_gather); (void)hipFree(ctx->d_cost_scratch);
     for (int k = 0; k < 2; ++k) { (void)hipFree(ctx->d_order_keys[k]); (void)hipFree(ctx->d_order_vals[k]); }
-    (void)hipFree(ctx->d_accum_alt); (void)hipFree(ctx->d_stack_ovf); (void)hipFree(ctx->d_queue);
+    (void)hipFree(ctx->d_accum_alt); (void)hipFree(ctx->d_stack_ovf); (void)hipFree(ctx->d_memo); (void)hipFree(ctx->d_queue);
     (void)hipFree(ctx->d_shard_in); (void)hipFree(ctx->d_shard_out); (void)hipFree(ctx->d_shard_src);
     if (ctx->ev_snapshot_free) (void)hipEventDestroy(ctx->ev_snapshot_free);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -1697,11 +1697,11 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
     // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD
     r.dense = ctx->lds_scene && integrator == TRC_INTEGRATOR_PATH && !r.stats && !r.sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
               ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * render_dense.waves &&
-              ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)TRC_PARK_DENSE * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * render_dense.waves <= 160u * 1024u;
+              ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)dense_lds_rows() * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * render_dense.waves <= 160u * 1024u;
     // wavefront slots of the kernel this launch runs (the split plan's model).  Strip and persistent-workgroup launches count
     // the one-wavefront kernel's waves, as they always have (a strip launch plans nothing; the persistent ones' default is the same).
     r.wave_slots = (uint32_t)ctx->cu_count * 4u * (uint32_t)(r.dense ? render_dense : family.one[kVariantPlain]).waves;
-    uint32_t park_rows = r.dense ? (uint32_t)TRC_PARK_DENSE : 0u;      // LDS rows of parked per-pixel state (render_block)
+    uint32_t park_rows = r.dense ? dense_lds_rows() : 0u;      // LDS rows of parked per-pixel state and of the primary-replay memo (render_block)
     const bool mem_plan = !r.stats && !ctx->lds_scene;                   // trees read from memory: the LDS is planned per launch
     if (mem_plan && !ctx->knobs.no_pwg && kp.strip == 1 && ctx->lds_prefix_ok) {       // no_pwg: A/B knob
         r.pwg_waves = (uint32_t)pwg_waves(integrator);
@@ -1844,6 +1844,21 @@ static trc_status launch_buffers(trc_ctx* ctx, const trc_params* p, RenderLaunch
         }
         kp.stack_ovf = ctx->d_stack_ovf;
     }
+    // the primary-replay memo rows of the kernels that keep them in global memory (trc_render_config.hpp), per wavefront as above
+    const size_t memo_rows = r.stats || r.sobol || r.env ? 0u : r.pwg ? pwg_memo_rows((int)p->integrator) : (r.dense && TRC_REPLAY_DENSE_GLOBAL) ? (size_t)TRC_REPLAY_DENSE : 0u;
+    if (memo_rows) {
+        const size_t need = memo_rows * kBlock * sizeof(uint32_t) * (r.pwg ? (size_t)r.grid * r.pwg_waves : (size_t)r.grid_cap);
+        if (need > ctx->memo_bytes) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_memo) { (void)hipFree(ctx->d_memo); ctx->d_memo = nullptr; }
+            ctx->memo_bytes = 0;
+            if (hipMalloc((void**)&ctx->d_memo, need) != hipSuccess) return fail(ctx, TRC_ERR_OOM, "hipMalloc primary-replay memo rows");
+            ctx->memo_bytes = need;
+        }
+        kp.memo = ctx->d_memo;
+    }
+    kp.replay = ctx->knobs.no_primary_replay ? 0u : (uint32_t)(ctx->knobs.replay_min_lanes > 0 ? ctx->knobs.replay_min_lanes : TRC_REPLAY_MIN_LANES);
+    kp.replay_chain = (uint32_t)(ctx->knobs.replay_chain > 0 ? ctx->knobs.replay_chain : TRC_REPLAY_CHAIN);
     if (r.pwg) {
         if (!ctx->d_queue && hipMalloc((void**)&ctx->d_queue, sizeof(uint32_t)) != hipSuccess) return fail(ctx, TRC_ERR_OOM, "hipMalloc block queue");
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_queue, 0, sizeof(uint32_t), ctx->stream));
@@ -2007,6 +2022,19 @@ trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv
     return ts;
 }
 #endif  // TRC_TEST_HOOKS
+
+// developer diagnostic: camera rays answered from the primary-replay memo since the last trc_reset_stats (tracer_abi.h)
+trc_status trc_debug_primary_replays(trc_ctx* ctx, uint64_t* out) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    if (!ctx || !out) return TRC_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long h[kStatCount];
+    hipLaunchKernelGGL(k_stats_sum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_stats, ctx->d_stats_sum);
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *out = h[kStatReplays];
+    return TRC_OK;
+}
 
 // developer diagnostic: the chain bound and the work bound of the last launch (tracer_abi.h)
 trc_status trc_debug_launch_shape(trc_ctx* ctx, trc_launch_shape* out) {
@@ -2461,7 +2489,8 @@ trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value) {
               : k == "force_blk_shift" ? &ctx->knobs.force_blk_shift : k == "no_split" ? &ctx->knobs.no_split : k == "no_cost_filter" ? &ctx->knobs.no_cost_filter
               : k == "no_cold_probe" ? &ctx->knobs.no_cold_probe : k == "probe_spp" ? &ctx->knobs.probe_spp
               : k == "no_plan_reuse" ? &ctx->knobs.no_plan_reuse : k == "no_coalesce" ? &ctx->knobs.no_coalesce : k == "no_dense" ? &ctx->knobs.no_dense : k == "head_stages" ? &ctx->knobs.head_stages : k == "descend_min" ? &ctx->knobs.descend_min
-              : k == "camera_policy" ? &ctx->knobs.camera_policy : nullptr;
+              : k == "camera_policy" ? &ctx->knobs.camera_policy : k == "no_primary_replay" ? &ctx->knobs.no_primary_replay
+              : k == "replay_min_lanes" ? &ctx->knobs.replay_min_lanes : k == "replay_chain" ? &ctx->knobs.replay_chain : nullptr;
     if (!slot) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_debug_set: unknown knob " + k);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // a launch in flight keeps the plan it was made with

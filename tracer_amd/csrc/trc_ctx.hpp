@@ -65,6 +65,9 @@ struct KRender {
     const float* tex_texels;            // image textures (k_render*_tex only): texel pool, RGB float, rows bottom-up ...
     const uint4* tex_desc;              // ... {first texel, w, h, 0} per image
     uint32_t n_tex;                     // ... images uploaded
+    uint32_t* memo;                     // primary replay (trc_render_config.hpp): the memo rows per wavefront of the kernels that keep them in global memory
+    uint32_t replay;                    // ... 0: every camera ray walks (knob no_primary_replay); n: a trip of the loop shades replayed hits alone where >= n lanes hold one
+    uint32_t replay_chain;              // ... and at most this many such trips in a row
 };
 
 // the kernels of TRC_FLAG_ENV_LIGHT (k_render*_env) take the environment map's sampling tables besides: a struct of their own, so
@@ -148,6 +151,8 @@ struct trc_ctx {
     bool lds_prefix_ok = false;         // the fat nodes are in top-of-tree-first order: any prefix may be staged
     uint32_t* d_stack_ovf = nullptr;    // traversal-stack overflow rows of the render launches (deep trees only)
     size_t stack_ovf_bytes = 0;
+    uint32_t* d_memo = nullptr;         // primary-replay memo rows of the render launches that keep them in global memory
+    size_t memo_bytes = 0;
     uint32_t* d_queue = nullptr;        // block queue head of the persistent-workgroup launches
     trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh, reference array layout (trc_download_bvh)
     uint32_t n_bvh_ref = 0, lbvh_height = 0;
@@ -249,7 +254,7 @@ struct trc_ctx {
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
-    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0; } knobs;
+    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0; } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_abi.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;

@@ -112,6 +112,41 @@ enum : uint32_t { kParkCachedX = 0, kParkCachedY, kParkCachedZ, kParkU, kParkV, 
 constexpr uint32_t pwg_park_rows(int integrator) { return integrator == TRC_INTEGRATOR_PATH ? TRC_PARK_PATH : (integrator == TRC_INTEGRATOR_MIS ? TRC_PARK_MIS : TRC_PARK_VOLUME); }
 static_assert((TRC_PARK_PATH == 0 || TRC_PARK_PATH == 8 || TRC_PARK_PATH == 10) && (TRC_PARK_MIS == 0 || TRC_PARK_MIS == 8 || TRC_PARK_MIS == 10) &&
               (TRC_PARK_VOLUME == 0 || TRC_PARK_VOLUME == 8 || TRC_PARK_VOLUME == 10) && (TRC_PARK_DENSE == 0 || TRC_PARK_DENSE == 8 || TRC_PARK_DENSE == 10), "park rows: 0, 8 or 10");
+// PRIMARY REPLAY (round 8, trc_render_kernels.hpp::render_block): the reference's camera has no sub-pixel jitter and its default lens has
+// radius 0, so every sample of a pixel casts the same camera ray, bit for bit, and Scene::hit of it is a pure function of (scene, ray).
+// A lane keeps what the integrator reads of that hit -- p, gn, tag, material | the side sn took, with 10 rows uv -- in MEMO words of a
+// column of its own (row r at memo[r * kBlock]) after the first walk of a block, and a later sample whose origin has the eye's bits takes
+// the record from there instead of walking.  Per kernel family, 0 = compiled out:
+//   k_render_dense       8 rows of LDS behind the stack rows (what six waves per SIMD leave).  uv has no row: a hit whose colour reads
+//                        rec.uv (a checker texture on a cube or a triangle) is not kept, and that pixel walks every sample
+//   k_render_pwg<path>   10 rows per wavefront in global memory, sized per launch like the overflow rows of the stack (coalesced 256 B)
+// TRC_REPLAY_DENSE_GLOBAL 1 puts the dense kernel's rows in global memory too (the storage A/B).  Scheduling (knobs replay_min_lanes /
+// replay_chain): where at least TRC_REPLAY_MIN_LANES lanes of a wavefront hold a replayed hit, a trip of the loop shades those lanes alone, at
+// most TRC_REPLAY_CHAIN such trips between two walks; 65 lanes = the plain variant, a replayed lane sits out the next walk and nothing else.
+// Config 2, ms per 64-spp launch (profiles/r08/ab_primary_replay.txt): replay off 17.5; 1 lane x 1 trip 15.6; 8 / 16 / 24 / 32 / 48 lanes 15.6 /
+// 15.7 / 15.7 / 16.2 / 17.4; plain 17.6; 1 lane, trips unbounded 21.0 (pixels that replay 63 times in a row starve the walkers).
+// traceMIS / traceVolume, Sobol', k_render, the strip and the instrumented kernels always walk.
+enum : uint32_t { kMemoPx = 0, kMemoPy, kMemoPz, kMemoNx, kMemoNy, kMemoNz, kMemoTag, kMemoMat, kMemoU, kMemoV };
+constexpr uint32_t kMemoNone = 0xFFFFFFFFu;        // the material word of a column that holds no record (its tag word: replays so far)
+constexpr uint32_t kMemoSameSide = 0x80000000u;    // material word: sn == gn (else sn == -gn: check_face)
+#ifndef TRC_REPLAY_DENSE
+#define TRC_REPLAY_DENSE 8
+#endif
+#ifndef TRC_REPLAY_DENSE_GLOBAL
+#define TRC_REPLAY_DENSE_GLOBAL 0
+#endif
+#ifndef TRC_REPLAY_PWG_PATH
+#define TRC_REPLAY_PWG_PATH 10
+#endif
+#ifndef TRC_REPLAY_MIN_LANES
+#define TRC_REPLAY_MIN_LANES 1
+#endif
+#ifndef TRC_REPLAY_CHAIN
+#define TRC_REPLAY_CHAIN 1
+#endif
+static_assert((TRC_REPLAY_DENSE == 0 || TRC_REPLAY_DENSE == 8 || TRC_REPLAY_DENSE == 10) && (TRC_REPLAY_PWG_PATH == 0 || TRC_REPLAY_PWG_PATH == 10), "memo rows: 0, 8 or 10 (10 wherever image textures may be live)");
+constexpr uint32_t dense_lds_rows() { return (uint32_t)TRC_PARK_DENSE + (TRC_REPLAY_DENSE_GLOBAL ? 0u : (uint32_t)TRC_REPLAY_DENSE); }      // LDS rows of k_render_dense behind its stack
+constexpr uint32_t pwg_memo_rows(int integrator) { return integrator == TRC_INTEGRATOR_PATH ? (uint32_t)TRC_REPLAY_PWG_PATH : 0u; }
 #ifndef TRC_PWG_STACK_LDS_PATH
 #define TRC_PWG_STACK_LDS_PATH (TRC_PARK_PATH == 10 ? 10 : (TRC_PARK_PATH == 8 ? 12 : 16))
 #endif

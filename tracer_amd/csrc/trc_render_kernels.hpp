@@ -38,10 +38,19 @@ template <bool ENV, class CX>
 __device__ __forceinline__ void set_ctx_env(CX& cx, const EnvLight* envl) {
     if constexpr (ENV) cx.envl = *envl;
 }
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, class COUNT = uint32_t>
+// MEMO = 8 | 10 (round 8, tracePath production kernels; trc_render_config.hpp: primary replay): the hit of the pixel's camera ray, kept
+// after the block's first walk in MEMO words of the lane's column `memo` (LDS or global rows).  A later sample whose camera ray has the
+// same origin bits -- the direction follows from (origin, u, v, camera) -- takes its record from there: no walk, and (kp.replay lanes) it is
+// shaded before the wavefront's next walk, so that a lane needs one trip round the loop per BOUNCE ray.  The ray is still counted
+// (trc_stats.rays is the algorithm's Scene::hit count); what was answered from the memo is summed into kStatReplays.
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, class COUNT = uint32_t>
 __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                              uint32_t* ovf, uint32_t* park, const uint32_t slot, const uint32_t lane,
-                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt, const EnvLight* envl = nullptr) {
+                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt, const EnvLight* envl = nullptr,
+                                             uint32_t* memo = nullptr) {
+    static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && !ENV), "primary replay: tracePath production kernels");
+    static_assert(MEMO == 0 || MEMO == 10 || !TEX, "an image texture reads rec.uv: 10 memo rows");
+    uint32_t replays = 0;                        // camera rays of this lane answered from the memo
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
     const uint32_t entry = kp.order ? kp.order[slot] : slot;     // adaptive launch order / cost-adaptive block size (trc_render)
     const uint32_t index = entry & kLaunchIndexMask, code = entry >> kLaunchCodeShift;
@@ -112,10 +121,44 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
         PathState ps;
         Pcg rng;
         uint64_t state_after_cast = 0;       // SOBOL: the sampler draws from a copy, the texel keeps this (SobolSampler.hh:50)
+        // MEMO: `first` -- the lane's next walk is its first of the block, the camera ray of the launch's first sample: its result is kept;
+        // `have` -- ps.rec already holds the hit of ps.ray (taken from the memo by begin_sample); `terminal` -- the memoised camera ray
+        // ends the sample by itself (it escapes, or meets an emitter): its radiance, a function of the ray alone, is in the memo too.
+        // The memo never outlives the block.
+        const bool replay_on = MEMO != 0 && kp.replay != 0u;
+        bool first = replay_on, have = false, terminal = false;
+        auto memo_f = [&](uint32_t r) { return __uint_as_float(memo[r * kBlock]); };
+        auto at_eye = [&](const F3& o) {      // bits, not values: a NaN offset or a zero of the other sign is another ray
+            return __float_as_uint(o.x) == __float_as_uint(kp.cam.lookFrom[0]) && __float_as_uint(o.y) == __float_as_uint(kp.cam.lookFrom[1]) &&
+                   __float_as_uint(o.z) == __float_as_uint(kp.cam.lookFrom[2]);
+        };
         // castRay, then (SOBOL) the sampler of this frame: Render.metal:527-530
         auto begin_sample = [&](uint32_t s) {
             const float u = PARK ? row_f(kParkU) : u_r, v = PARK ? row_f(kParkV) : v_r;
             path_begin(ps, cast_ray(kp.cam, u, v, rng), kp.max_depth);
+            if constexpr (MEMO != 0) {
+                if (replay_on && s != 0u) {
+                    const uint32_t mat = memo[kMemoMat * kBlock];
+                    if (mat != kMemoNone) {
+                        if (at_eye(ps.ray.o)) {                 // the memoised ray: its record, as Scene::hit left it for the integrator
+                            const uint32_t tag = memo[kMemoTag * kBlock];
+                            if (tag == kTagNone) terminal = true;
+                            else {
+                                ps.rec.p = f3(memo_f(kMemoPx), memo_f(kMemoPy), memo_f(kMemoPz));
+                                ps.rec.gn = f3(memo_f(kMemoNx), memo_f(kMemoNy), memo_f(kMemoNz));
+                                ps.rec.sn = (mat & kMemoSameSide) ? ps.rec.gn : -ps.rec.gn;
+                                ps.rec.material = mat & ~kMemoSameSide;
+                                ps.rec.tag = tag;
+                                if constexpr (MEMO >= 10) { ps.rec.uv.x = memo_f(kMemoU); ps.rec.uv.y = memo_f(kMemoV); }
+                                have = true;
+                            }
+                            bump(n_rays);                       // still one Scene::hit of the algorithm
+                        } else {                                // another ray (a lens): the pixel walks from here on; s - 1 samples replayed
+                            memo[kMemoMat * kBlock] = kMemoNone; memo[kMemoTag * kBlock] = s - 1u;
+                        }
+                    }
+                }
+            }
             if (SOBOL) {
                 state_after_cast = rng.state;
                 ps.sobol_index = sobol_interval_to_index(cx, (uint64_t)(kp.frame0 + s));
@@ -133,48 +176,101 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
         // end of a sample: accumulate, hand the RNG words back to the texel, start the next sample (or stop)
         auto finish_sample = [&](F3 color) {
             ProfScope<STATS> scope(cnt, kProfFinish);
-            const bool bad = is_inf(color.x) || is_nan(color.x) || is_inf(color.y) || is_nan(color.y) ||
-                             is_inf(color.z) || is_nan(color.z);
-            if (bad) color = f3(0);                                         // :537-538
-            uint32_t s = get_sample();
-            const uint32_t frame = kp.frame0 + s;
-            set_cached(div_shared(get_cached() * (float)frame + color, (float)(frame + 1)));  // running mean, :540-541
-            if (SOBOL) rng.state = state_after_cast;
-            // PARK: the texel is not carried through the loop -- the last sample's write-back is the RNG's own words (below)
-            if constexpr (!PARK) {
-                texel.y = (uint32_t)rng.state; texel.x = (uint32_t)(rng.state >> 32);
-                texel.w = (uint32_t)rng.inc;   texel.z = (uint32_t)(rng.inc >> 32);
-                n_paths++;
-            }
-            ++s;
-            set_sample(s);
-            if (s == kp.spp) {
-                alive = false;
-            } else {
-                if constexpr (PARK) { const uint64_t t = rng.state; rng.state = rng.inc; rng.inc = t; }      // the words trade roles (B-1)
-                else {
-                    rng.state = ((uint64_t)texel.z << 32) | texel.w;
-                    rng.inc = ((uint64_t)texel.x << 32) | texel.y;
+            for (;;) {
+                const bool bad = is_inf(color.x) || is_nan(color.x) || is_inf(color.y) || is_nan(color.y) ||
+                                 is_inf(color.z) || is_nan(color.z);
+                if (bad) color = f3(0);                                         // :537-538
+                uint32_t s = get_sample();
+                const uint32_t frame = kp.frame0 + s;
+                set_cached(div_shared(get_cached() * (float)frame + color, (float)(frame + 1)));  // running mean, :540-541
+                if (SOBOL) rng.state = state_after_cast;
+                // PARK: the texel is not carried through the loop -- the last sample's write-back is the RNG's own words (below)
+                if constexpr (!PARK) {
+                    texel.y = (uint32_t)rng.state; texel.x = (uint32_t)(rng.state >> 32);
+                    texel.w = (uint32_t)rng.inc;   texel.z = (uint32_t)(rng.inc >> 32);
+                    n_paths++;
                 }
-                begin_sample(s);
+                ++s;
+                set_sample(s);
+                if (s == kp.spp) {
+                    alive = false;
+                } else {
+                    if constexpr (PARK) { const uint64_t t = rng.state; rng.state = rng.inc; rng.inc = t; }      // the words trade roles (B-1)
+                    else {
+                        rng.state = ((uint64_t)texel.z << 32) | texel.w;
+                        rng.inc = ((uint64_t)texel.x << 32) | texel.y;
+                    }
+                    begin_sample(s);
+                }
+                if constexpr (MEMO != 0) {      // a sample that its memoised camera ray ends: the same radiance again, and on to the next one
+                    if (terminal) { terminal = false; color = f3(memo_f(kMemoPx), memo_f(kMemoPy), memo_f(kMemoPz)); continue; }
+                }
+                break;
             }
         };
+        // what the integrator reads of the first walk's result goes to the memo -- if the ray left the eye itself, and the record fits the
+        // rows.  Returns whether the ray ends its sample by itself: its radiance then follows the step (the rows of p)
+        auto memo_store = [&](bool hitted) {
+            uint32_t mat = kMemoNone, tag = 0u;                  // no record: the tag word counts the replays so far
+            bool ends = false;
+            if (at_eye(ps.ray.o)) {
+                ends = !hitted || mat_type(cx.sh, ps.rec.material) == kMatDiffuse;         // path_step: :434-445
+                if (ends) { mat = 0u; tag = kTagNone; }
+                else {
+                    // 8 rows have no room for uv, which only a checker texture on a cube or a triangle reads (hit_color): such a hit is not kept
+                    const bool uv_read = MEMO < 10 && (ps.rec.tag >> kTagIndexBits) >= 2u && mat_tex(cx.sh, ps.rec.material) == kTexChecker;
+                    if (!uv_read && ps.rec.material < kMemoSameSide - 1u) {
+                        const bool same = __float_as_uint(ps.rec.sn.x) == __float_as_uint(ps.rec.gn.x);      // sn is gn or -gn (check_face)
+                        mat = ps.rec.material | (same ? kMemoSameSide : 0u); tag = ps.rec.tag;
+                        memo[kMemoPx * kBlock] = __float_as_uint(ps.rec.p.x); memo[kMemoPy * kBlock] = __float_as_uint(ps.rec.p.y);
+                        memo[kMemoPz * kBlock] = __float_as_uint(ps.rec.p.z);
+                        memo[kMemoNx * kBlock] = __float_as_uint(ps.rec.gn.x); memo[kMemoNy * kBlock] = __float_as_uint(ps.rec.gn.y);
+                        memo[kMemoNz * kBlock] = __float_as_uint(ps.rec.gn.z);
+                        if constexpr (MEMO >= 10) { memo[kMemoU * kBlock] = __float_as_uint(ps.rec.uv.x); memo[kMemoV * kBlock] = __float_as_uint(ps.rec.uv.y); }
+                    }
+                }
+            }
+            memo[kMemoMat * kBlock] = mat; memo[kMemoTag * kBlock] = tag;
+            return ends;
+        };
         // flat loop: one Scene::hit per iteration; a finished path immediately regenerates the next sample
+        uint32_t drained = 0;                                   // MEMO: trips in a row that shaded replayed hits only (wave-uniform)
         while (alive) {
             ProfScope<STATS> loop_scope(cnt, kProfLoop);
             constexpr bool kVolume = INTEGRATOR == TRC_INTEGRATOR_VOLUME;
             constexpr int kDefer = STATS ? 0 : (LDS ? TRC_DEFER_LDS : TRC_DEFER_GLOBAL);      // dev_intersect.hpp: trav_test_leaf
-            bool hitted = true;
-            if (!(kVolume && TRC_TRACK_SLICE > 0 && ps.tracking)) {       // a lane between two slices of its delta tracker has no ray to trace
+            bool hitted = true;                                  // (a replayed hit in hand is a hit: a memoised miss ends in finish_sample)
+            // MEMO: a lane that holds a replayed hit has nothing to walk.  Where at least kp.replay lanes of the wavefront do, this trip shades
+            // them alone -- they are then level with the lanes whose ray is a bounce, one trip per BOUNCE ray -- but no more than
+            // kp.replay_chain such trips in a row (every one costs the whole wavefront a shading pass); otherwise those lanes sit out the walk
+            // and are shaded with everybody.  Wave-uniform decisions; which trip shades a lane changes nothing the lane computes.
+            bool drain = false, ends = false;
+            if constexpr (MEMO != 0) {
+                drain = (uint32_t)__popcll(__ballot(have)) >= kp.replay && drained < kp.replay_chain && replay_on;
+                drained = drain ? drained + 1u : 0u;
+            }
+            if (!drain && !have && !(kVolume && TRC_TRACK_SLICE > 0 && ps.tracking)) {       // a lane between two slices of its delta tracker has no ray to trace
                 bump(n_rays);
                 hitted = scene_hit<LDS, STATS, false, false, kVolume, HYB, kDefer>(cx.S, cx.root_min, cx.root_max, ps.ray, ps.rec, FLT_MAX,
                                                                                   cx.stack, cx.lvstack, cnt);
+                if constexpr (MEMO != 0) {
+                    if (first) { ends = memo_store(hitted); first = false; }
+                }
             }
-            F3 color;
-            const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
-                                      ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
-            if (finished) finish_sample(color);
+            if (!drain || have) {
+                have = false;
+                F3 color;
+                const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
+                                          ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
+                                          : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                if constexpr (MEMO != 0) {
+                    if (ends) { memo[kMemoPx * kBlock] = __float_as_uint(color.x); memo[kMemoPy * kBlock] = __float_as_uint(color.y); memo[kMemoPz * kBlock] = __float_as_uint(color.z); }
+                }
+                if (finished) finish_sample(color);
+            }
+        }
+        if constexpr (MEMO != 0) {      // a column that still holds its record answered every sample but the first; one that lost it says how many
+            if (replay_on) replays = memo[kMemoMat * kBlock] != kMemoNone ? kp.spp - 1u : memo[kMemoTag * kBlock];
         }
         if constexpr (PARK) {       // the loop is left by the last finish_sample only (trc_render launches spp >= 1): what that one would
             n_paths += kp.spp;      // have put into the texel, and one finished sample per call of it
@@ -205,10 +301,15 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
 
     // per SAMPLE (cost_div = 4 x spp), so that launches of different lengths speak of the same quantity
     if (lane == 0) kp.block_cost[canon] = (uint32_t)min((unsigned long long)(clock64() - t_start) / kp.cost_div, 0xFFFFFFull);
+    if constexpr (MEMO != 0) {
+        const uint32_t r_replays = wave_sum(replays);
+        if (lane == 0 && r_replays) atomicAdd(&stat_row(kp.stats, slot)[kStatReplays], (unsigned long long)r_replays);
+    }
 }
 
 // the body of k_render (one one-wavefront workgroup = one entry of the launch list)
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false>
+// MEMO, MEMO_GLOBAL: the primary-replay rows (render_block) -- behind the stack and park rows of this workgroup's LDS, or rows of its own in kp.memo
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MEMO_GLOBAL = false>
 __device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLight* envl = nullptr) {
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
@@ -222,14 +323,17 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLig
     counters_zero(cnt);
     constexpr bool kHybridStack = !LDS && !STATS && hybrid_stack(INTEGRATOR);     // plan_launch_lds
     uint32_t* ovf = kHybridStack ? kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane : nullptr;
+    uint32_t* memo = nullptr;
+    if constexpr (MEMO != 0 && MEMO_GLOBAL) memo = kp.memo + (size_t)blockIdx.x * MEMO * kBlock + lane;
+    else if constexpr (MEMO != 0) memo = stack + (sc.stack_lds + PARK) * kBlock;
     if constexpr (PARK != 0) {                  // the park rows follow the stack rows of this one-wavefront workgroup (trc_abi.hip: dense_lds_bytes)
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
-        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl);
+        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV, MEMO>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl, memo);
         n_rays = park[kParkRays * kBlock]; n_shaded = park[kParkShaded * kBlock];
     } else
-    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl);
+    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, MEMO>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl, memo);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);

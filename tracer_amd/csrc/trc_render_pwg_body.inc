@@ -16,6 +16,9 @@
     uint32_t* stack = trc_smem + sc.lds_dwords + wave * (sc.stack_lds + kRows) * kBlock + lane;
     uint32_t* park = stack + sc.stack_lds * kBlock;
     uint32_t* ovf = kHybridStack ? kp.stack_ovf + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * sc.stack_ovf_rows * kBlock + lane : nullptr;
+    // primary replay (render_block): MEMO rows per wavefront in global memory, this lane's column
+    constexpr int kMemo = (!SOBOL && !ENV) ? (int)pwg_memo_rows(INTEGRATOR) : 0;
+    uint32_t* memo = kMemo ? kp.memo + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * kMemo * kBlock + lane : nullptr;
     uint32_t n_paths = 0;
     TravCounters cnt;
     counters_zero(cnt);
@@ -29,7 +32,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX, ENV>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt, envl);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX, ENV, kMemo>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt, envl, memo);
         }
         r_rays = wave_sum(park[kParkRays * kBlock]); r_shaded = wave_sum(park[kParkShaded * kBlock]);
     } else {
@@ -39,7 +42,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt, envl);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, kMemo>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt, envl, memo);
         }
         r_rays = wave_sum(n_rays); r_shaded = wave_sum(n_shaded);
     }

@@ -110,6 +110,7 @@ def _load(path, hooks=False):
     L.trc_debug_set.argtypes = [vp, C.c_char_p, C.c_int]
     L.trc_debug_block_costs.argtypes = [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.trc_debug_launch_shape.argtypes = [vp, C.POINTER(abi.LaunchShape)]
+    L.trc_debug_primary_replays.argtypes = [vp, C.POINTER(u64)]
     L.trc_denoise_default_params.argtypes = [C.POINTER(abi.DenoiseParams)]
     L.trc_denoise.argtypes = [vp, C.POINTER(abi.DenoiseParams)]
     L.trc_download_denoised.argtypes = [vp, vp]
@@ -518,6 +519,12 @@ class Tracer:
         s = abi.LaunchShape()
         self._check(self._L.trc_debug_launch_shape(self._h, C.byref(s)), "trc_debug_launch_shape")
         return {k: getattr(s, k) for k, _ in abi.LaunchShape._fields_}
+
+    def primary_replays(self):
+        """camera rays answered from the memo of the pixel's first walk since the last reset_stats (trc_debug_primary_replays)"""
+        n = C.c_uint64(0)
+        self._check(self._L.trc_debug_primary_replays(self._h, C.byref(n)), "trc_debug_primary_replays")
+        return n.value
 
     def group_finalize(self):
         self._check(self._L.trc_group_finalize(self._h), "trc_group_finalize")
