@@ -5,6 +5,8 @@
 //   trc_render [--scene cornell|spheres|volume] [--integrator path|mis|volume] [--size W H] [--spp N]
 //              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
 //              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
+//              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
+//                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
 //              as the reference's host binds uv_test.png (AAPLRenderer.mm:385-390)
 //   trc_render --pbrt scene.pbrt [--triangle-materials] [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
@@ -31,7 +33,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, tri_materials = false;
+    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -46,6 +48,7 @@ int main(int argc, char** argv) {
         else if (a == "--lbvh") lbvh = true;
         else if (a == "--device-sah") device_sah = true;
         else if (a == "--sobol") sobol = true;
+        else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
         else if (a == "--triangle-materials") tri_materials = true;            // --pbrt: per-mesh materials instead of material 19
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -79,8 +82,13 @@ int main(int argc, char** argv) {
             return 1;
         }
         if (!size_given) { W = info.xres; H = info.yres; }         // the camera's aspect is the film's
-        if (integrator != TRC_INTEGRATOR_PATH && !info.mis_ready && !(env_light && !hdr_path.empty())) {
-            std::fprintf(stderr, "%s has no rectangular area light: traceMIS samples squareList[5] / [6]; use --integrator path, or --hdr with --env-light\n",
+        if (integrator != TRC_INTEGRATOR_PATH && !info.mis_ready && !(env_light && !hdr_path.empty()) && !mesh_lights) {
+            std::fprintf(stderr, "%s has no rectangular area light: traceMIS samples squareList[5] / [6]; use --integrator path, --hdr with --env-light, or --mesh-lights\n",
+                         pbrt_path.c_str());
+            return 1;
+        }
+        if (mesh_lights && !tri_materials && !info.mis_ready) {      // every triangle is material 19: no light triangle, and no square either
+            std::fprintf(stderr, "%s has no rectangular area light, and without --triangle-materials no triangle is an emitter: --mesh-lights would render black\n",
                          pbrt_path.c_str());
             return 1;
         }
@@ -172,6 +180,7 @@ int main(int argc, char** argv) {
     std::memset(&prm, 0, sizeof prm);
     prm.spp = spp; prm.max_depth = 8; prm.integrator = integrator; prm.tile_nranks = 1;
     if (sobol) prm.flags |= TRC_FLAG_SOBOL;      // pbrt::SobolSampler instead of the random sampler (Render.metal:529-530)
+    if (mesh_lights) prm.flags |= TRC_FLAG_MESH_LIGHTS;   // the mesh's emissive triangles as area-sampled lights of traceMIS
     if (env_light) prm.flags |= TRC_FLAG_ENV_LIGHT;  // the --hdr map as an importance-sampled light of traceMIS
     const auto t0 = std::chrono::steady_clock::now();
     CHECK(trc_render(ctx, &prm));

@@ -49,8 +49,10 @@ extern "C" {
  * 10: per-triangle materials: trc_upload_triangle_materials, trc_host_scene_load_pbrt_flags (TRC_PBRT_TRIANGLE_MATERIALS),
  *    trc_host_scene_triangle_materials (nothing existing changed)
  * 11: primary replay: trc_debug_primary_replays, knob no_primary_replay; trc_stats.rays keeps counting every Scene::hit of the
- *    algorithm, the camera rays answered from the memo included (nothing existing changed) */
-#define TRC_ABI_VERSION 11
+ *    algorithm, the camera rays answered from the memo included (nothing existing changed)
+ * 12: TRC_FLAG_MESH_LIGHTS: the emissive triangles of a mesh as sampled lights of traceMIS, knob mesh_light_pick (nothing existing
+ *    changed) */
+#define TRC_ABI_VERSION 12
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -308,6 +310,44 @@ enum trc_integrator {
    - The tables are built at the first flagged render after trc_set_environment_map (TRC_ERR_OOM if they cannot be
      allocated; flag-off renders keep working) and freed when the map changes or is cleared, and by trc_destroy.  A change
      of the flag, like one of the integrator, drops the recorded block costs of the launch planner. */
+#define TRC_FLAG_MESH_LIGHTS    64u /* traceMIS treats the emissive triangles of the mesh as lights, sampled by area and combined
+                                       with BSDF sampling by MIS (an extension beyond the reference, whose traceMIS samples
+                                       squareList[5] / [6] only).  Without the flag nothing changes.
+   - Accepted with TRC_INTEGRATOR_MIS, with or without active image textures, with or without trc_upload_triangle_materials
+     (without it every triangle has material 19), with or without squareList[5] / [6].  With tracePath / traceVolume,
+     TRC_FLAG_SOBOL, TRC_FLAG_COLLECT_STATS or TRC_FLAG_ENV_LIGHT, trc_render returns TRC_ERR_UNSUPPORTED and renders nothing.
+   - Light set: triangle t is a light when its material has type TRC_MAT_DIFFUSE (the emitter), y = rgb_to_y(albedo) is finite
+     and > 0, and its area A is finite and > 0; binary32 on the vertices as uploaded, in this order: e1 = v1 - v0, e2 = v2 - v0,
+     c = cross(e1, e2), A = sqrt(c.x c.x + c.y c.y + c.z c.z) / 2.  Its weight is y * A (the exact float64 product); the total is
+     the float64 sum over the lights by ascending triangle index.  A one-level alias table over the lights in triangle order
+     (entries {threshold, alias}: a 32-bit draw below the threshold keeps the entry; Vose's method in the order stated for
+     TRC_FLAG_ENV_LIGHT's tables) and, per triangle, pdfA[t] = weight / (total * A) rounded once to binary32, 0 for a triangle
+     that is no light.
+   - Light pick: the reference's one pcg_float draw.  p_mesh = 1/2 with square lights, 1 without, 0 without a light triangle.
+     A draw below p_mesh picks the mesh, else square 5 below p_mesh + (1 - p_mesh) / 2 and square 6 above; a square's
+     contribution is divided by 1 - p_mesh.  With p_mesh = 0 every operation and draw is the flag-off kernel's: the frame and
+     the RNG texture are the flag-off ones bit for bit.
+   - The mesh's sample: four extra PCG draws, taken only when the mesh is picked: r0, r1 pick the light (multiply-shift index,
+     alias decision), floats f0, f1 the point: s = sqrt(f0), b0 = 1 - s, b1 = f1 s, p = (v0 b0 + v1 b1) + v2 ((1 - b0) - b1).
+     n = the normalised geometric normal cross(e1, e2) on the shading point's side; the shadow ray is the any-hit walk to
+     offset_ray(p, n), as for a square.  cosL = |dot(n, -dir)|, liPDF = p_mesh pdfA dist^2 / cosL, contribution = ratio * F *
+     (albedo cosL) * w / liPDF with w = power heuristic(liPDF, bsdf pdf): radiance keeps the reference's Le * cos convention,
+     so squares and triangles emit alike.  As for TRC_FLAG_ENV_LIGHT the sample counts only where the BSDF sample is a cosine
+     lobe (Lambert, or the Lambert lobe of Plastic) with wo.z > 0 and wi.z > 0; at any other vertex a pick of the mesh takes no
+     sample and draws nothing more.
+   - A BSDF-sampled hit on a TRIANGLE emitter, while the scene has a light triangle, is ratio * (albedo cosOnLight) * w with
+     cosOnLight = |dot(geometric normal, -d)| and w = power heuristic(bsdf pdf, p_mesh pdfA[t] dist^2 / cosOnLight) where the
+     previous vertex sampled a cosine lobe and that density is > 0, else 1.  This is a DEFINED DIFFERENCE from flag-off for
+     triangle emitters: the reference's formula multiplies the emitter hit by scat_attenuation / scat_bxPDF a second time (the
+     path throughput holds it already) and weighs it against hitRecord.PDF, which only a square writes -- on a triangle it is
+     whatever the last accepted square left there; neither describes the integrand the mesh's light sample estimates.  A
+     square emitter hit keeps the reference's formula, and camera-ray hits on emitters are unchanged.
+   - Knob mesh_light_pick (trc_debug_set; default 1): 0 forces p_mesh = 0 while the triangle-emitter formula above is kept
+     (w = 1): the BSDF-only estimator of the same integrand.  Measurement and tests only.
+   - The tables are built on the device at the first flagged render after a scene or triangle-material upload (TRC_ERR_OOM
+     if they cannot be allocated; flag-off renders keep working) and freed by every trc_upload_scene*, by
+     trc_upload_triangle_materials and by trc_destroy.  A change of the flag drops the recorded block costs of the launch
+     planner. */
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
                                        N_descend / N_return / leaf-test counters.  Not with an active image texture
                                        (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
@@ -491,8 +531,10 @@ trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n
  *  - Launches kept back for coalescing run first; the G-buffer and the denoiser history are dropped, as are the recorded block
  *    costs of the launch planner.  trc_sppm_frames sees the new materials at its next call: a consistent SPPM pass restarts
  *    with trc_sppm_init.  Image textures stay active as before (the whole material table decides that).
- *  - traceMIS still samples squareList[5] / [6] only: an emissive triangle is reached by BSDF sampling alone, with the
- *    emitter-hit weighting an emissive material 19 gets. */
+ *  - Without TRC_FLAG_MESH_LIGHTS traceMIS samples squareList[5] / [6] only: an emissive triangle is reached by BSDF sampling
+ *    alone, with the reference's emitter-hit weighting (against hitRecord.PDF, which a triangle does not write).  With the
+ *    flag the emissive triangles are sampled lights with a weighting of their own (TRC_FLAG_MESH_LIGHTS above); their tables
+ *    are rebuilt after this call. */
 trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material, uint32_t n_triangles);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):

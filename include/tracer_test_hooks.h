@@ -56,6 +56,19 @@ trc_status trc_debug_env_tables(trc_ctx* ctx, float* weight, uint32_t* rows, uin
 trc_status trc_env_light_test(trc_ctx* ctx, const uint32_t* draws /* 6 n */, size_t n, float* dir_pdf /* 4 n */,
                               const float* dirs /* 3 m */, size_t m, float* pdf /* m */);
 
+/* test hooks of TRC_FLAG_MESH_LIGHTS (tracer_abi.h); both build the scene's tables if they are not built (TRC_ERR_NO_SCENE without a
+ * scene).  trc_debug_mesh_light_tables downloads them (any pointer may be NULL): the alias table over the lights ({threshold, alias}
+ * pairs, n_lights of them), the lights' triangle indices (n_lights), pdfA (one float per triangle of the scene), the float64 total
+ * weight and the light count -- call it once for the count, then with arrays of that size.  trc_mesh_light_test runs the render
+ * kernels' sampler (tracer_amd/csrc/dev_meshlight.hpp), one lane per item: for n draws (four words each: light index and alias
+ * decision as 32-bit integers, then two float bit patterns for the point) and n shading points (3 floats each) tri receives the
+ * triangle and out 7 floats: the point on it (before offset_ray), the normal turned to the shading point, and pdfA.
+ * TRC_ERR_UNSUPPORTED when the scene has no light triangle. */
+trc_status trc_debug_mesh_light_tables(trc_ctx* ctx, uint32_t* alias /* 2 n_lights */, uint32_t* tri /* n_lights */, float* pdfA /* n_triangles */,
+                                       double* total, uint32_t* n_lights);
+trc_status trc_mesh_light_test(trc_ctx* ctx, const uint32_t* draws /* 4 n */, const float* pos /* 3 n */, size_t n, uint32_t* tri /* n */,
+                               float* out /* 7 n */);
+
 #ifdef __cplusplus
 }
 #endif

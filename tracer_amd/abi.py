@@ -7,7 +7,7 @@ Triangle,Texture,Material,Camera}.hh (see the header for file:line).
 """
 import ctypes as C
 
-TRC_ABI_VERSION = 11
+TRC_ABI_VERSION = 12
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
@@ -33,6 +33,7 @@ FLAG_FIXED_ORDER = 2
 FLAG_SOBOL = 4
 FLAG_SMALL_BLOCKS, FLAG_LARGE_BLOCKS = 8, 16
 FLAG_ENV_LIGHT = 32
+FLAG_MESH_LIGHTS = 64
 TRACE_ANY_HIT, TRACE_PRODUCTION = 1, 2
 SOBOL_DIMS, SOBOL_MATRIX_SIZE = 40, 52
 
@@ -253,7 +254,7 @@ DEVICE_SYMBOLS = [
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
-                "trc_debug_env_tables", "trc_env_light_test"]
+                "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",

@@ -7,6 +7,7 @@
 #include "dev_bsdf.hpp"
 #include "dev_envlight.hpp"
 #include "dev_intersect.hpp"
+#include "dev_meshlight.hpp"
 #include "trc_sobol.h"
 
 #include <type_traits>
@@ -154,14 +155,21 @@ struct PathCtxTex : PathCtx { TexTable tex; };
 // ... and of the ENV instantiations (TRC_FLAG_ENV_LIGHT): the map's sampling tables (dev_envlight.hpp)
 struct PathCtxEnv : PathCtx { EnvLight envl; };
 struct PathCtxEnvTex : PathCtxTex { EnvLight envl; };
-template <bool TEX, bool ENV = false>
-using PathCtxOf = typename std::conditional<ENV, typename std::conditional<TEX, PathCtxEnvTex, PathCtxEnv>::type,
-                                            typename std::conditional<TEX, PathCtxTex, PathCtx>::type>::type;
+// ... and of the MESH instantiations (TRC_FLAG_MESH_LIGHTS): the emissive triangles' sampling tables (dev_meshlight.hpp)
+struct PathCtxMesh : PathCtx { MeshLight meshl; };
+struct PathCtxMeshTex : PathCtxTex { MeshLight meshl; };
+template <bool TEX, bool ENV = false, bool MESH = false>
+using PathCtxOf = typename std::conditional<MESH, typename std::conditional<TEX, PathCtxMeshTex, PathCtxMesh>::type,
+                  typename std::conditional<ENV, typename std::conditional<TEX, PathCtxEnvTex, PathCtxEnv>::type,
+                                            typename std::conditional<TEX, PathCtxTex, PathCtx>::type>::type>::type;
 template <bool TEX> TRC_DEV const TexTable* ctx_tex(const PathCtx& cx) {
     if constexpr (TEX) return &static_cast<const PathCtxTex&>(cx).tex; else return nullptr;
 }
 template <bool TEX, bool ENV> TRC_DEV const EnvLight* ctx_env(const PathCtx& cx) {
     if constexpr (ENV) return &static_cast<const PathCtxOf<TEX, true>&>(cx).envl; else return nullptr;
+}
+template <bool TEX, bool MESH> TRC_DEV const MeshLight* ctx_mesh(const PathCtx& cx) {
+    if constexpr (MESH) return &static_cast<const PathCtxOf<TEX, false, true>&>(cx).meshl; else return nullptr;
 }
 
 // ---------------------------------------------------------------- path state machine
@@ -187,6 +195,7 @@ struct PathState {
     uint64_t sobol_index;    // TRC_FLAG_SOBOL: mSobolIndex of this sample and the next dimension (SobolSampler.hh:37-41)
     uint32_t sobol_dim;
     bool env_mis;            // TRC_FLAG_ENV_LIGHT: the map's light sample shares the escape of the ray in flight (a cosine lobe, env_nee)
+                             // TRC_FLAG_MESH_LIGHTS (never both): ... the mesh's light sample shares the emitter hit of the ray in flight (mesh_nee)
 };
 
 // ---------------------------------------------------------------- pbrt::SobolSampler (SobolSampler.hh:26-167)
@@ -494,12 +503,92 @@ TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& c
     }
 }
 
+// The light sample of a traceMIS vertex with the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; mis_step<.., MESH>), env_nee's
+// twin: the light pick's one draw takes the mesh below p_mesh, else square 5 below p_mesh + (1 - p_mesh) / 2 and square 6 above; a
+// square's sample is the reference's (:320-356) with its contribution divided by 1 - p_mesh.  The mesh's sample (dev_meshlight.hpp) draws
+// four more numbers, only when it is picked and only where the BSDF sample is a cosine lobe (env_nee's rule, for its reason); its shadow
+// ray is the any-hit walk to the sample's distance, as a square's.  Radiance keeps the reference's Le * cos convention.
+template <bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
+TRC_DEV void mesh_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
+                      const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
+    const HitRec& rec = ps.rec;
+    const MeshLight& L = *ctx_mesh<TEX, true>(cx);
+    const float pick = pcg_float(rng);
+    ps.env_mis = mtype == kMatLambert || (mtype == kMatPlastic && uu.x < 0.5f);
+    // 0: no light sample; 1: a square; 2: the mesh
+    const int kind = pick < L.p_mesh ? (ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
+    coordinate_system(rec.sn, nx, ny);
+    Ray _ray = make_ray(_origin, f3(0.0f, 0.0f, 1.0f));
+    float _dis = FLT_MAX;
+    F3 light_term = f3(0.0f);
+    float liPDF = 0.0f;
+    if (kind == 1) {
+        LightSample lsr;
+        square_sample(cx.S, pick < L.p_mesh + (1.0f - L.p_mesh) * 0.5f ? 5 : 6, uu, _origin, lsr);
+        const F3 _dir = lsr.p - _origin;
+        const F3 _nor = normalize(_dir);
+        _dis = length(_dir);
+        _ray = make_ray(_origin, _nor);
+        const float cosOnLight = fabsf(dot(lsr.n, -_nor));
+        light_term = mat_albedo(cx.sh, lsr.material) * cosOnLight;
+        liPDF = (_dis * _dis) * lsr.areaPDF / cosOnLight;
+    } else if (kind == 2) {
+        const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng);
+        const float f0 = pcg_float(rng), f1 = pcg_float(rng);
+        MeshSample ms;
+        mesh_light_sample(L, cx.S.blob + cx.S.off_tripos, r0, r1, f0, f1, _origin, ms);
+        const F3 _dir = offset_ray(ms.p, ms.n) - _origin;
+        const F3 _nor = normalize(_dir);
+        const float dist = length(_dir);
+        const float cosL = fabsf(dot(ms.n, -_nor));
+        // only where the BSDF strategy has support (the cosine lobe samples wi.z > 0 and reports pdf 0 unless wo.z > 0), as env_nee
+        const float wi_z = dot(rec.sn, _nor), wo_z = -dot(rec.sn, ps.ray.d);
+        liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? L.p_mesh * ms.pdfA * (dist * dist) / cosL : 0.0f;
+        if (!(liPDF > 0.0f && liPDF <= FLT_MAX)) liPDF = 0.0f;          // (a grazing or coincident sample: cosL or dist 0)
+        if (liPDF > 0.0f) {
+            _dis = dist;
+            _ray = make_ray(_origin, _nor);
+            // the material of triangle ms.tri, as the hit test reads it (dev_intersect.hpp: TRC_TRIANGLE_MATERIALS)
+            const uint32_t material = TRC_TRIANGLE_MATERIALS ? ld1_global(cx.S.blob + cx.S.off_triattr + (size_t)ms.tri * kTriAttrDwords + 15u) : 19u;
+            light_term = mat_albedo(cx.sh, material) * cosL;
+        }
+    }
+    bool blocked = true;
+    if (kind == 1 || (kind == 2 && liPDF > 0.0f)) {              // (a square's sample walks whatever its pdf, as the reference's does)
+        bump(n_rays);
+        if (STATS) {
+            HitRec shr;
+            hit_init(shr);
+            blocked = scene_hit<ALL_LDS, STATS, true, false, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, shr, _dis, cx.stack, cx.lvstack, cnt);
+        } else {
+            blocked = scene_occluded<ALL_LDS, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, _dis, cx.stack, cx.S.stack_cap);
+        }
+    }
+    minus_d = -ps.ray.d;
+    base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
+    if (!blocked) {
+        const F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
+        const F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
+        float bxPDF = 0;
+        bump(n_shaded);
+        F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF) * light_term;
+        if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - L.p_mesh));
+        else ps.color = ps.color + ps.ratio * (weight * env_mis_weight(liPDF, bxPDF)) / liPDF;
+    }
+}
+
 // ENV (TRC_FLAG_ENV_LIGHT, traceMIS only): the environment map is a light too (dev_envlight.hpp).  The light pick's one draw takes
 // the map below p_env, else square 5 below p_env + (1 - p_env) / 2 and square 6 above; a square's contribution is divided by
 // 1 - p_env (the reference's expectation, its missing 1/2 included).  The map's sample draws six more numbers, only when it is
 // picked, and only at a vertex whose BSDF ray would be counted if it escaped; an escaping BSDF ray is weighted against it.
 // With p_env = 0 (a black map) every operation and draw is the flag-off kernel's.
-template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, bool ENV = false, class COUNT = uint32_t>
+// MESH (TRC_FLAG_MESH_LIGHTS, traceMIS only, never with ENV): the mesh's emissive triangles are lights too (mesh_nee).  A BSDF-sampled hit
+// on a TRIANGLE emitter is then ps.color + ps.ratio * (albedo * cosOnLight) * w, cosOnLight = |dot(geometric normal, -d)| and
+// w = env_mis_weight(scat_bxPDF, p_mesh * pdfA[triangle] * dist^2 / cosOnLight) where the previous vertex took its BSDF sample from a
+// cosine lobe, else 1: the estimator of the integrand the mesh's light sample estimates -- without the reference's second
+// scat_attenuation / scat_bxPDF factor, and without rec.PDF, which only a square writes (tracer_abi.h).  A square emitter hit keeps the
+// reference's formula.  Without a light triangle (p_mesh = 0, no tables) every operation and draw is the flag-off kernel's.
+template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, bool ENV = false, bool MESH = false, class COUNT = uint32_t>
 TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_rays,
                       COUNT& n_shaded, F3& result) {
     HitRec& rec = ps.rec;
@@ -508,6 +597,23 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     if (!ps.primary) {
         if ((!VOLUME || ps.from_bsdf) && hitted && mat_type(cx.sh, rec.material) == kMatDiffuse) {   // MIS-weighted emitter hit, :390-404
             F3 Li = mat_albedo(cx.sh, rec.material);
+            if constexpr (MESH) {
+                const MeshLight& L = *ctx_mesh<TEX, MESH>(cx);
+                if (L.n_lights != 0u && (rec.tag >> kTagIndexBits) == kTagTriangle) {      // a triangle emitter, and a mesh strategy exists
+                    const uint32_t t = rec.tag & kTagIndexMask;
+                    F3 v0, v1, v2;
+                    mesh_tri_load(cx.S.blob + cx.S.off_tripos, t, v0, v1, v2);
+                    const float cosL = fabsf(dot(mesh_tri_normal(v0, v1, v2), -ps.ray.d));
+                    const F3 d = rec.p - ps.ray.o;
+                    float w = 1.0f;
+                    if (ps.env_mis) {
+                        const float lightPDF = L.p_mesh * L.pdfA[t] * dot(d, d) / cosL;
+                        if (lightPDF > 0.0f && lightPDF <= FLT_MAX) w = env_mis_weight(ps.scat_bxPDF, lightPDF);
+                    }
+                    result = ps.color + ps.ratio * (Li * cosL) * w;
+                    return true;
+                }
+            }
             float cosOnLight = dot(-ps.ray.d, rec.sn);
             F3 weight = ps.scat_attenuation * Li * cosOnLight;
             F3 d = rec.p - ps.ray.o;
@@ -585,6 +691,8 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     F3 nx, ny, minus_d, base_color;
     if constexpr (ENV) {
         env_nee<ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
+    } else if constexpr (MESH) {
+        mesh_nee<ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
     } else {
     if (pcg_float(rng) < 0.5f) square_sample(cx.S, 5, uu, _origin, lsr);
     else square_sample(cx.S, 6, uu, _origin, lsr);

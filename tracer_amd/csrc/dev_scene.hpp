@@ -41,6 +41,7 @@ constexpr uint32_t kTriPosDwords = 12;
 constexpr uint32_t kTriAttrDwords = 16;
 
 constexpr uint32_t kTagInterior = 4u;
+constexpr uint32_t kTagTriangle = 3u;            // a leaf's tag type is its trc_PrimitiveType: TRC_PRIM_TRIANGLE
 constexpr uint32_t kTagIndexBits = 29u;
 constexpr uint32_t kTagIndexMask = (1u << kTagIndexBits) - 1u;
 constexpr uint32_t kTagNone = 0xFFFFFFFFu;

@@ -104,6 +104,7 @@ __global__ void __launch_bounds__(256) k_triangle_leaves(const trc_TriangleVerte
 trc_status trc_repack_triangles(trc_ctx* ctx, const trc_scene* s, const DScene& sc, uint32_t* d_blob, trc_BVH* d_tri_leaves) {
     const uint32_t n_tri = s->n_index / 3;
     ctx->tri_materials = false;                  // every triangle is material 19 again
+    trc_mesh_light_free(ctx);                    // TRC_FLAG_MESH_LIGHTS: rebuilt for the new scene when a launch asks
     if (n_tri == 0) return TRC_OK;
     trc_TriangleVertex* d_verts = nullptr;
     uint32_t* d_idx = nullptr;
@@ -947,8 +948,9 @@ const RenderKernels& render_family(bool lds_scene, uint32_t integrator, bool tri
 
 // One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
 // device (the attribute is set on the current device's copy of the function): remembered in the context, which is bound to one device.
-hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, const EnvLight& el, uint32_t grid, uint32_t block, size_t lds) {
-    const void* const fn = kern.fn_env ? reinterpret_cast<const void*>(kern.fn_env) : reinterpret_cast<const void*>(kern.fn);
+hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, const EnvLight& el, const MeshLight& ml, uint32_t grid, uint32_t block, size_t lds) {
+    const void* const fn = kern.fn_mesh ? reinterpret_cast<const void*>(kern.fn_mesh)
+                         : kern.fn_env ? reinterpret_cast<const void*>(kern.fn_env) : reinterpret_cast<const void*>(kern.fn);
     if (lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         if (e != hipSuccess) return e;
@@ -956,7 +958,9 @@ hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& 
     }
     KRenderEnv kpe;                                     // the k_render*_env kernels' parameters: the launch's and the map's tables
     if (kern.fn_env) { kpe.kp = kp; kpe.el = el; }
-    void* args[] = {kern.fn_env ? static_cast<void*>(&kpe) : const_cast<KRender*>(&kp)};
+    KRenderMesh kpm;                                    // ... the k_render*_mesh kernels': the launch's and the emissive triangles' tables
+    if (kern.fn_mesh) { kpm.kp = kp; kpm.ml = ml; }
+    void* args[] = {kern.fn_mesh ? static_cast<void*>(&kpm) : kern.fn_env ? static_cast<void*>(&kpe) : const_cast<KRender*>(&kp)};
     const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(block), args, lds, ctx->stream);
     const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
     return e != hipSuccess ? e : last;
@@ -1133,7 +1137,7 @@ void trc_destroy(trc_ctx* ctx) {
     trc_denoise_release(ctx);
     collect_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); trc_env_light_free(ctx); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
+    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); trc_env_light_free(ctx); trc_mesh_light_free(ctx); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
     (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_stats); (void)hipFree(ctx->d_stats_sum); (void)hipFree(ctx->d_reduce_recv);
     (void)hipFree(ctx->d_block_cost); (void)hipFree(ctx->d_order_hist); (void)hipFree(ctx->d_split); (void)hipFree(ctx->d_whole); (void)hipFree(ctx->d_cost_est); (void)hipFree(ctx->d_qsplit); (void)hipFree(ctx->d_qwhole); (void)hipFree(ctx->d_swhole); (void)hipFree(ctx->d_launch); (void)hipFree(ctx->d_plan); (void)hipFree(ctx->d_plan_gather); (void)hipFree(ctx->d_cost_scratch);
     for (int k = 0; k < 2; ++k) { (void)hipFree(ctx->d_order_keys[k]); (void)hipFree(ctx->d_order_vals[k]); }
@@ -1363,6 +1367,7 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
         if (st != TRC_OK) return st;
     }
     ctx->tri_materials = material != nullptr && sc.n_triangles != 0;
+    trc_mesh_light_free(ctx);                    // TRC_FLAG_MESH_LIGHTS: another set of emissive triangles, rebuilt when a launch asks
     // what the frame shows changed: the G-buffer and the denoiser's history are stale, and the recorded block costs are another
     // picture's (as after trc_upload_scene)
     trc_denoise_invalidate(ctx);
@@ -1504,7 +1509,13 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
             return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_ENV_LIGHT: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS kernels");
         if (!ctx->d_envmap) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_ENV_LIGHT: no environment map (trc_set_environment_map)");
     }
-    if (p->integrator != TRC_INTEGRATOR_PATH && ctx->ks.sc.n_squares < 7 && !env_light)
+    const bool mesh_lights = (p->flags & TRC_FLAG_MESH_LIGHTS) != 0;
+    if (mesh_lights) {
+        if (p->integrator != TRC_INTEGRATOR_MIS) return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MESH_LIGHTS: traceMIS only");
+        if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS | TRC_FLAG_ENV_LIGHT))
+            return fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MESH_LIGHTS: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS / TRC_FLAG_ENV_LIGHT kernels");
+    }
+    if (p->integrator != TRC_INTEGRATOR_PATH && ctx->ks.sc.n_squares < 7 && !env_light && !mesh_lights)
         return fail(ctx, TRC_ERR_INVALID_ARG, "traceMIS / traceVolume sample squareList[5] and [6] (Render.metal:320-324,172-176)");
     if (ctx->tex_active() && (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS)))
         return fail(ctx, TRC_ERR_UNSUPPORTED, "image textures: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS kernels (trc_upload_textures)");
@@ -1521,6 +1532,7 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
         if (sobol_m) *sobol_m = m;
     }
     if (env_light) return trc_env_light_build(ctx);      // the map's sampling tables, once per map (TRC_ERR_OOM: this render does not run)
+    if (mesh_lights) return trc_mesh_light_build(ctx);   // the emissive triangles' tables, once per scene and triangle-material array (likewise)
     return TRC_OK;
 }
 
@@ -1578,6 +1590,8 @@ struct RenderLaunch {
     bool stats = false, sobol = false;  // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL
     bool env = false;                   // TRC_FLAG_ENV_LIGHT ...
     EnvLight el{};                      // ... and the map's sampling tables (the k_render*_env kernels' second half of KRenderEnv)
+    bool mesh = false;                  // TRC_FLAG_MESH_LIGHTS ...
+    MeshLight ml{};                     // ... and the emissive triangles' sampling tables (the k_render*_mesh kernels' second half of KRenderMesh)
     bool fits = false;                  // launch_geometry: the frame's edges allow 4x4 blocks ...
     uint64_t blocks8 = 0;               // ... 8x8 blocks in this rank's share
     bool quarters_ok = false;           // ... the list's blocks are 8x8: costs live in kCostSlots slots per block
@@ -1653,8 +1667,8 @@ static void drop_stale_costs(trc_ctx* ctx, const trc_params* p, const RenderLaun
     if (ctx->cost_strip != r.kp.strip || ctx->cost_quarters != r.quarters_ok) {
         ctx->cost_valid = false; ctx->cost_strip = r.kp.strip; ctx->cost_quarters = r.quarters_ok; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
     }
-    if (ctx->cost_integrator != p->integrator || ctx->cost_env != r.env) {
-        ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->cost_env = r.env; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
+    if (ctx->cost_integrator != p->integrator || ctx->cost_env != r.env || ctx->cost_mesh != r.mesh) {
+        ctx->cost_valid = false; ctx->cost_integrator = p->integrator; ctx->cost_env = r.env; ctx->cost_mesh = r.mesh; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
     }
 }
 
@@ -1709,10 +1723,11 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
         r.pwg = plan_pwg_lds(ctx, kp.ks.sc, r.pwg_waves, (uint32_t)pwg_per_cu(integrator), hybrid_stack(integrator), pwg_stack_lds_levels(integrator), park_rows);
         if (!r.pwg) park_rows = 0u;
     }
-    const RenderVariant variant = r.env ? (ctx->tex_active() ? kVariantEnvTex : kVariantEnv)
+    const RenderVariant variant = r.mesh ? (ctx->tex_active() ? kVariantMeshTex : kVariantMesh)
+                                : r.env ? (ctx->tex_active() ? kVariantEnvTex : kVariantEnv)
                                         : ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
-    if (!r.kern.fn && !r.kern.fn_env) return fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
+    if (!r.kern.fn && !r.kern.fn_env && !r.kern.fn_mesh) return fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
     if (mem_plan && !r.pwg) plan_launch_lds(ctx, kp.ks.sc, (uint32_t)r.kern.waves, hybrid_stack(integrator));
     r.lds = r.pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)r.pwg_waves * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
                   : dyn_lds_bytes(kp.ks.sc, r.stats) + (r.dense ? (size_t)park_rows * kBlock * 4 : 0u);
@@ -1845,7 +1860,7 @@ static trc_status launch_buffers(trc_ctx* ctx, const trc_params* p, RenderLaunch
         kp.stack_ovf = ctx->d_stack_ovf;
     }
     // the primary-replay memo rows of the kernels that keep them in global memory (trc_render_config.hpp), per wavefront as above
-    const size_t memo_rows = r.stats || r.sobol || r.env ? 0u : r.pwg ? pwg_memo_rows((int)p->integrator) : (r.dense && TRC_REPLAY_DENSE_GLOBAL) ? (size_t)TRC_REPLAY_DENSE : 0u;
+    const size_t memo_rows = r.stats || r.sobol || r.env || r.mesh ? 0u : r.pwg ? pwg_memo_rows((int)p->integrator) : (r.dense && TRC_REPLAY_DENSE_GLOBAL) ? (size_t)TRC_REPLAY_DENSE : 0u;
     if (memo_rows) {
         const size_t need = memo_rows * kBlock * sizeof(uint32_t) * (r.pwg ? (size_t)r.grid * r.pwg_waves : (size_t)r.grid_cap);
         if (need > ctx->memo_bytes) {
@@ -1874,7 +1889,7 @@ static trc_status timed_launch(trc_ctx* ctx, const RenderLaunch& r) {
     auto give_back = [&]() { if (e0) ctx->event_pool.push_back(e0); if (e1) ctx->event_pool.push_back(e1); };
     if (!e0 || !e1) { give_back(); return fail(ctx, TRC_ERR_HIP, "hipEventCreate failed"); }
     hipError_t le = hipEventRecord(e0, ctx->stream);
-    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.el, r.grid, r.block, r.lds);
+    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.el, r.ml, r.grid, r.block, r.lds);
     if (le == hipSuccess) le = hipEventRecord(e1, ctx->stream);
     if (le != hipSuccess) { give_back(); return fail(ctx, TRC_ERR_HIP, std::string("k_render launch: ") + hipGetErrorString(le)); }
     ctx->pending.emplace_back(e0, e1);
@@ -1892,6 +1907,8 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     r.sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
     r.env = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
     if (r.env) r.el = trc_env_light_view(ctx);
+    r.mesh = (p->flags & TRC_FLAG_MESH_LIGHTS) != 0;
+    if (r.mesh) r.ml = trc_mesh_light_view(ctx);
     { const trc_status st = launch_geometry(ctx, p, r); if (st != TRC_OK) return st; }
     if (ctx->n_tiles == 0) return TRC_OK;
     if (trc_dyn_lds_bytes(ctx, r.stats) > 160 * 1024) return fail(ctx, TRC_ERR_UNSUPPORTED, "traversal stack exceeds the 160 KB LDS of a CU");
@@ -2490,7 +2507,8 @@ trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value) {
               : k == "no_cold_probe" ? &ctx->knobs.no_cold_probe : k == "probe_spp" ? &ctx->knobs.probe_spp
               : k == "no_plan_reuse" ? &ctx->knobs.no_plan_reuse : k == "no_coalesce" ? &ctx->knobs.no_coalesce : k == "no_dense" ? &ctx->knobs.no_dense : k == "head_stages" ? &ctx->knobs.head_stages : k == "descend_min" ? &ctx->knobs.descend_min
               : k == "camera_policy" ? &ctx->knobs.camera_policy : k == "no_primary_replay" ? &ctx->knobs.no_primary_replay
-              : k == "replay_min_lanes" ? &ctx->knobs.replay_min_lanes : k == "replay_chain" ? &ctx->knobs.replay_chain : nullptr;
+              : k == "replay_min_lanes" ? &ctx->knobs.replay_min_lanes : k == "replay_chain" ? &ctx->knobs.replay_chain
+              : k == "mesh_light_pick" ? &ctx->knobs.mesh_light_pick : nullptr;
     if (!slot) return fail(ctx, TRC_ERR_INVALID_ARG, "trc_debug_set: unknown knob " + k);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // a launch in flight keeps the plan it was made with

@@ -77,6 +77,12 @@ struct KRenderEnv {
     EnvLight el;
 };
 
+// ... and the kernels of TRC_FLAG_MESH_LIGHTS (k_render*_mesh) the emissive triangles' sampling tables
+struct KRenderMesh {
+    KRender kp;
+    MeshLight ml;
+};
+
 struct KTrace {
     KScene ks;
     const trc_ray* rays;
@@ -174,6 +180,10 @@ struct trc_ctx {
     // TRC_FLAG_ENV_LIGHT: the map's sampling tables (trc_envlight.hip), built at the first flagged render after trc_set_environment_map
     uint8_t* d_envl = nullptr; double envl_total = 0.0; float envl_build_ms = 0.0f;
     bool cost_env = false;              // the flag of the launches whose block costs are recorded (drop_stale_costs)
+    // TRC_FLAG_MESH_LIGHTS: the emissive triangles' sampling tables (trc_meshlight.hip), built at the first flagged render after a scene
+    // or triangle-material upload.  mesh_built with d_meshl null: a scene without a light triangle (or without a triangle)
+    uint8_t* d_meshl = nullptr; bool mesh_built = false; uint32_t mesh_n_lights = 0; double mesh_total = 0.0;
+    bool cost_mesh = false;             // ... and its flag of the launches whose block costs are recorded
 
     // frame
     uint32_t width = 0, height = 0;
@@ -254,7 +264,7 @@ struct trc_ctx {
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
-    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0; } knobs;
+    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1; } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_abi.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;
@@ -340,4 +350,8 @@ void trc_denoise_invalidate(trc_ctx* ctx);   // another scene or environment: th
 trc_status trc_env_light_build(trc_ctx* ctx);
 void trc_env_light_free(trc_ctx* ctx);
 EnvLight trc_env_light_view(const trc_ctx* ctx);
+// TRC_FLAG_MESH_LIGHTS (trc_meshlight.hip): the same three for the scene's emissive triangles
+trc_status trc_mesh_light_build(trc_ctx* ctx);
+void trc_mesh_light_free(trc_ctx* ctx);
+MeshLight trc_mesh_light_view(const trc_ctx* ctx);
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)

@@ -8,6 +8,7 @@
 // restate them: q_i = w_i n / sum in float64; worklists filled by ascending index; both are stacks (LIFO); a pair sets
 // threshold(q_small) / alias = the large entry and q_large = (q_large + q_small) - 1; what is left on either list has probability 1
 // and is its own alias.  threshold(q) = floor(q 2^32), 2^32 - 1 for q >= 1: an entry is kept when a 32-bit draw is below it.
+#include "trc_alias.hpp"
 #include "trc_ctx.hpp"
 
 #include <cfloat>
@@ -33,30 +34,6 @@ __global__ void __launch_bounds__(256) k_env_weights(const float* rgb, uint32_t 
     weight[c] = m * fmaxf(cl, 0.0f);
 }
 
-__device__ uint32_t env_threshold(double q) {
-    return q >= 1.0 ? 0xFFFFFFFFu : (q <= 0.0 ? 0u : (uint32_t)(q * 4294967296.0));
-}
-// Vose's alias table of n weights w (sum = their float64 sum, ascending): q / list are n words of scratch each
-template <class T>
-__device__ void env_vose(const T* w, uint32_t n, double sum, double* q, uint32_t* list, uint2* out) {
-    for (uint32_t i = 0; i < n; ++i) q[i] = sum > 0.0 ? ((double)w[i] * (double)n) / sum : 1.0;
-    uint32_t ns = 0, nl = 0;                    // small: list[0 .. ns), large: list[n - nl .. n), top at list[n - nl]
-    for (uint32_t i = 0; i < n; ++i) {
-        if (q[i] < 1.0) list[ns++] = i;
-        else list[n - 1 - nl++] = i;
-    }
-    while (ns != 0 && nl != 0) {
-        const uint32_t l = list[--ns];
-        const uint32_t g = list[n - 1 - --nl];
-        out[l] = make_uint2(env_threshold(q[l]), g);
-        q[g] = (q[g] + q[l]) - 1.0;
-        if (q[g] < 1.0) list[ns++] = g;
-        else list[n - 1 - nl++] = g;
-    }
-    while (nl != 0) { const uint32_t g = list[n - 1 - --nl]; out[g] = make_uint2(0xFFFFFFFFu, g); }
-    while (ns != 0) { const uint32_t l = list[--ns]; out[l] = make_uint2(0xFFFFFFFFu, l); }
-}
-
 __global__ void __launch_bounds__(64) k_env_rows(const float* weight, uint32_t W, uint32_t H, double* q, uint32_t* list, uint2* rows, double* rowsum) {
     const uint32_t j = blockIdx.x * 64u + threadIdx.x;
     if (j >= H) return;
@@ -64,7 +41,7 @@ __global__ void __launch_bounds__(64) k_env_rows(const float* weight, uint32_t W
     double sum = 0.0;
     for (uint32_t i = 0; i < W; ++i) sum += (double)weight[o + i];
     rowsum[j] = sum;
-    env_vose(weight + o, W, sum, q + o, list + o, rows + o);
+    alias_vose(weight + o, W, sum, q + o, list + o, rows + o);
 }
 
 __global__ void __launch_bounds__(64) k_env_marginal(const double* rowsum, uint32_t H, double* q, uint32_t* list, uint2* marg, double* total) {
@@ -72,7 +49,7 @@ __global__ void __launch_bounds__(64) k_env_marginal(const double* rowsum, uint3
     double sum = 0.0;
     for (uint32_t j = 0; j < H; ++j) sum += rowsum[j];
     *total = sum;
-    env_vose(rowsum, H, sum, q, list, marg);
+    alias_vose(rowsum, H, sum, q, list, marg);
 }
 
 // byte offsets in the one allocation of the tables: rows (W H uint2), marg (H uint2), total (double), weight (W H float)

@@ -181,9 +181,11 @@ struct RenderKernel {
     void (*fn)(KRender);                // the kernel
     int waves;                          // wavefronts per SIMD of its launch bounds
     void (*fn_env)(KRenderEnv);         // ... or the kernel, when it takes the environment map's sampling tables too (TRC_FLAG_ENV_LIGHT)
+    void (*fn_mesh)(KRenderMesh);       // ... or the emissive triangles' (TRC_FLAG_MESH_LIGHTS)
 };
-// TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures, TRC_FLAG_ENV_LIGHT (traceMIS only) without and with image textures
-enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariantEnv, kVariantEnvTex, kVariants };
+// TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures, TRC_FLAG_ENV_LIGHT (traceMIS only) without and with image textures,
+// TRC_FLAG_MESH_LIGHTS (traceMIS only) without and with image textures
+enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariantEnv, kVariantEnvTex, kVariantMesh, kVariantMeshTex, kVariants };
 struct RenderKernels {
     RenderKernel one[kVariants];        // one pixel block per one-wavefront workgroup: k_render<.., STATS, .., SOBOL>, k_render_tex
     RenderKernel strip[kVariants];      // a strip of blocks per wavefront: k_render_strip<.., SOBOL>, k_render_strip_tex (no statistics)

@@ -38,17 +38,22 @@ template <bool ENV, class CX>
 __device__ __forceinline__ void set_ctx_env(CX& cx, const EnvLight* envl) {
     if constexpr (ENV) cx.envl = *envl;
 }
+// MESH (TRC_FLAG_MESH_LIGHTS, traceMIS): the mesh's emissive triangles are lights too (mis_step<.., MESH>); `meshl` = their sampling tables
+template <bool MESH, class CX>
+__device__ __forceinline__ void set_ctx_mesh(CX& cx, const MeshLight* meshl) {
+    if constexpr (MESH) cx.meshl = *meshl;
+}
 // MEMO = 8 | 10 (round 8, tracePath production kernels; trc_render_config.hpp: primary replay): the hit of the pixel's camera ray, kept
 // after the block's first walk in MEMO words of the lane's column `memo` (LDS or global rows).  A later sample whose camera ray has the
 // same origin bits -- the direction follows from (origin, u, v, camera) -- takes its record from there: no walk, and (kp.replay lanes) it is
 // shaded before the wavefront's next walk, so that a lane needs one trip round the loop per BOUNCE ray.  The ray is still counted
 // (trc_stats.rays is the algorithm's Scene::hit count); what was answered from the memo is summed into kStatReplays.
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, class COUNT = uint32_t>
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MESH = false, class COUNT = uint32_t>
 __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                              uint32_t* ovf, uint32_t* park, const uint32_t slot, const uint32_t lane,
                                              COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt, const EnvLight* envl = nullptr,
-                                             uint32_t* memo = nullptr) {
-    static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && !ENV), "primary replay: tracePath production kernels");
+                                             uint32_t* memo = nullptr, const MeshLight* meshl = nullptr) {
+    static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && !ENV && !MESH), "primary replay: tracePath production kernels");
     static_assert(MEMO == 0 || MEMO == 10 || !TEX, "an image texture reads rec.uv: 10 memo rows");
     uint32_t replays = 0;                        // camera rays of this lane answered from the memo
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
@@ -71,7 +76,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
     const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
 
     if (active) {
-        PathCtxOf<TEX, ENV> cx;
+        PathCtxOf<TEX, ENV, MESH> cx;
         cx.S = make_scene_ref(sc, small_base);
         cx.S.ovf = ovf;
         cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
@@ -79,6 +84,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
         cx.sh.mats = small_base + sc.off_materials;
         set_ctx_tex<TEX>(cx, kp);
         set_ctx_env<ENV>(cx, envl);
+        set_ctx_mesh<MESH>(cx, meshl);
         cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
         cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
         cx.stack = stack;
@@ -262,7 +268,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
                 F3 color;
                 const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                           ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                          : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                          : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV, MESH>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
                 if constexpr (MEMO != 0) {
                     if (ends) { memo[kMemoPx * kBlock] = __float_as_uint(color.x); memo[kMemoPy * kBlock] = __float_as_uint(color.y); memo[kMemoPz * kBlock] = __float_as_uint(color.z); }
                 }
@@ -309,8 +315,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
 
 // the body of k_render (one one-wavefront workgroup = one entry of the launch list)
 // MEMO, MEMO_GLOBAL: the primary-replay rows (render_block) -- behind the stack and park rows of this workgroup's LDS, or rows of its own in kp.memo
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MEMO_GLOBAL = false>
-__device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLight* envl = nullptr) {
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MEMO_GLOBAL = false, bool MESH = false>
+__device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLight* envl = nullptr, const MeshLight* meshl = nullptr) {
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
     const uint32_t* small_base = stage_scene(sc);
@@ -330,10 +336,10 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLig
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
-        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV, MEMO>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl, memo);
+        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV, MEMO, MESH>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl, memo, meshl);
         n_rays = park[kParkRays * kBlock]; n_shaded = park[kParkShaded * kBlock];
     } else
-    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, MEMO>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl, memo);
+    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, MEMO, MESH>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl, memo, meshl);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
@@ -376,6 +382,11 @@ template <bool LDS, int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_env(const KRenderEnv kpe) {
     render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, true>(kpe.kp, &kpe.el);
 }
+// ... with the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS), without and with image textures
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_mesh(const KRenderMesh kpm) {
+    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, false, 0, false, true>(kpm.kp, nullptr, &kpm.ml);
+}
 
 // kernelPathTracing on a tree that is READ FROM MEMORY (mesh scenes), production launches of >= 8 spp: persistent
 // workgroups.  With one wavefront per workgroup every wavefront stages its own copy of the top of the tree, and 16-24 copies
@@ -392,12 +403,16 @@ template <int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg(const KRender kp) {
     constexpr bool TEX = false, ENV = false;
     const EnvLight* const envl = nullptr;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_tex(const KRender kp) {
     constexpr bool SOBOL = false, TEX = true, ENV = false;
     const EnvLight* const envl = nullptr;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR, bool TEX>
@@ -405,6 +420,17 @@ __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INT
     constexpr bool SOBOL = false, ENV = true;
     const KRender& kp = kpe.kp;
     const EnvLight* const envl = &kpe.el;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
+#include "trc_render_pwg_body.inc"
+}
+
+template <int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_mesh(const KRenderMesh kpm) {
+    constexpr bool SOBOL = false, ENV = false, MESH = true;
+    const KRender& kp = kpm.kp;
+    const EnvLight* const envl = nullptr;
+    const MeshLight* const meshl = &kpm.ml;
 #include "trc_render_pwg_body.inc"
 }
 
@@ -419,12 +445,16 @@ template <bool LDS, int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip(const KRender kp) {
     constexpr bool TEX = false, ENV = false;
     const EnvLight* const envl = nullptr;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_tex(const KRender kp) {
     constexpr bool SOBOL = false, TEX = true, ENV = false;
     const EnvLight* const envl = nullptr;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR, bool TEX>
@@ -432,6 +462,17 @@ __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_stri
     constexpr bool SOBOL = false, ENV = true;
     const KRender& kp = kpe.kp;
     const EnvLight* const envl = &kpe.el;
+    constexpr bool MESH = false;
+    const MeshLight* const meshl = nullptr;
+#include "trc_render_strip_body.inc"
+}
+
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_mesh(const KRenderMesh kpm) {
+    constexpr bool SOBOL = false, ENV = false, MESH = true;
+    const KRender& kp = kpm.kp;
+    const EnvLight* const envl = nullptr;
+    const MeshLight* const meshl = &kpm.ml;
 #include "trc_render_strip_body.inc"
 }
 
@@ -464,6 +505,15 @@ constexpr RenderKernels render_kernels() {
         if constexpr (!LDS) {
             t.pwg[kVariantEnv] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, false>};
             t.pwg[kVariantEnvTex] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, true>};
+        }
+        // TRC_FLAG_MESH_LIGHTS: traceMIS only
+        t.one[kVariantMesh] = {nullptr, render_waves(LDS, false, INTEGRATOR), nullptr, &k_render_mesh<LDS, INTEGRATOR, false>};
+        t.one[kVariantMeshTex] = {nullptr, render_waves(LDS, false, INTEGRATOR), nullptr, &k_render_mesh<LDS, INTEGRATOR, true>};
+        t.strip[kVariantMesh] = {nullptr, strip_waves(INTEGRATOR), nullptr, &k_render_strip_mesh<LDS, INTEGRATOR, false>};
+        t.strip[kVariantMeshTex] = {nullptr, strip_waves(INTEGRATOR), nullptr, &k_render_strip_mesh<LDS, INTEGRATOR, true>};
+        if constexpr (!LDS) {
+            t.pwg[kVariantMesh] = {nullptr, pwg_simd_waves(INTEGRATOR), nullptr, &k_render_pwg_mesh<INTEGRATOR, false>};
+            t.pwg[kVariantMeshTex] = {nullptr, pwg_simd_waves(INTEGRATOR), nullptr, &k_render_pwg_mesh<INTEGRATOR, true>};
         }
     }
     return t;

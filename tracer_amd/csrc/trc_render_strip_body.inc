@@ -1,6 +1,7 @@
 // trc_render_strip_body.inc -- the body of k_render_strip / k_render_strip_tex, included as the body of each kernel (trc_render_kernels.hpp) rather than
 // called from a helper: the kernel of the parent commit keeps its code and its name, and the image-texture twin shares the source.
-// Expects in scope: kp, LDS, INTEGRATOR, SOBOL, TEX, ENV and envl (the environment map's sampling tables of ENV, else null).
+// Expects in scope: kp, LDS, INTEGRATOR, SOBOL, TEX, ENV and envl (the environment map's sampling tables of ENV, else null), MESH and meshl
+// (the emissive triangles' sampling tables of MESH, else null).
     const DScene& sc = kp.ks.sc;
     const uint32_t* small_base = stage_scene(sc);
     uint32_t* stack = lane_stack(sc);
@@ -19,7 +20,7 @@
     TravCounters cnt;
     counters_zero(cnt);
 
-    PathCtxOf<TEX, ENV> cx;
+    PathCtxOf<TEX, ENV, MESH> cx;
     cx.S = make_scene_ref(sc, small_base);
     constexpr bool kHybridStack = !LDS && hybrid_stack(INTEGRATOR);
     if (kHybridStack) cx.S.ovf = kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane;
@@ -28,6 +29,7 @@
     cx.sh.mats = small_base + sc.off_materials;
     set_ctx_tex<TEX>(cx, kp);
     set_ctx_env<ENV>(cx, envl);
+    set_ctx_mesh<MESH>(cx, meshl);
     cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
     cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
     cx.stack = stack;
@@ -119,7 +121,7 @@
             F3 color;
             const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                       ? path_step<false, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, false, kVolume, SOBOL, kHybridStack, TEX, ENV>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                      : mis_step<LDS, false, kVolume, SOBOL, kHybridStack, TEX, ENV, MESH>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
             if (finished) finish_sample(color);
         }
     }

@@ -128,6 +128,8 @@ def _load(path, hooks=False):
         L.trc_texture_sample_test.argtypes = [vp, u32, vp, C.c_size_t, vp]
         L.trc_debug_env_tables.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_float)]
         L.trc_env_light_test.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp]
+        L.trc_debug_mesh_light_tables.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(u32)]
+        L.trc_mesh_light_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -249,6 +251,31 @@ class Tracer:
                     "trc_env_light_test")
         return out, pdf
 
+    def mesh_light_tables(self, n_triangles):
+        """hooks build only: the sampling tables of TRC_FLAG_MESH_LIGHTS for the uploaded scene (of n_triangles triangles) -> dict of
+        alias (n_lights, 2) uint32 {threshold, alias}, tri (n_lights,) uint32, pdfA (n_triangles,) float32, total (float), n_lights."""
+        total, n = C.c_double(), C.c_uint32()
+        self._check(self._L.trc_debug_mesh_light_tables(self._h, None, None, None, C.byref(total), C.byref(n)), "trc_debug_mesh_light_tables")
+        alias = np.zeros((n.value, 2), np.uint32)
+        tri = np.zeros(n.value, np.uint32)
+        pdfA = np.zeros(n_triangles, np.float32)
+        self._check(self._L.trc_debug_mesh_light_tables(self._h, alias.ctypes.data if n.value else None, tri.ctypes.data if n.value else None,
+                                                        pdfA.ctypes.data if n_triangles else None, C.byref(total), C.byref(n)),
+                    "trc_debug_mesh_light_tables")
+        return dict(alias=alias, tri=tri, pdfA=pdfA, total=total.value, n_lights=n.value)
+
+    def mesh_light_test(self, draws, pos):
+        """hooks build only: the render kernels' mesh-light sampler on (n, 4) uint32 draws (light index, alias decision, then two
+        float32 bit patterns) seen from (n, 3) float32 shading points -> (tri (n,) uint32, out (n, 7) float32: point, normal, pdfA)"""
+        d = np.ascontiguousarray(draws, dtype=np.uint32).reshape(-1, 4)
+        v = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+        assert d.shape[0] == v.shape[0]
+        tri = np.empty(d.shape[0], np.uint32)
+        out = np.empty((d.shape[0], 7), np.float32)
+        self._check(self._L.trc_mesh_light_test(self._h, d.ctypes.data, v.ctypes.data, d.shape[0], tri.ctypes.data, out.ctypes.data),
+                    "trc_mesh_light_test")
+        return tri, out
+
     def tonemap(self):
         """fragmentShader's auto-exposure + ACES on the accumulator -> ((H, W, 4) uint8, rows top-down; exposure)."""
         out = np.empty((self.height, self.width, 4), dtype=np.uint8)
@@ -326,9 +353,10 @@ class Tracer:
 
     # --- the hot path --------------------------------------------------------------
     def render(self, spp=1, max_depth=8, integrator=abi.INTEGRATOR_PATH, frame0=0, tile_rank=0, tile_nranks=1,
-               collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None, env_light=False):
+               collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None, env_light=False,
+               mesh_lights=False):
         flags = ((abi.FLAG_COLLECT_STATS if collect_stats else 0) | (abi.FLAG_FIXED_ORDER if fixed_order else 0) |
-                 (abi.FLAG_SOBOL if sobol else 0) | (abi.FLAG_ENV_LIGHT if env_light else 0) |
+                 (abi.FLAG_SOBOL if sobol else 0) | (abi.FLAG_ENV_LIGHT if env_light else 0) | (abi.FLAG_MESH_LIGHTS if mesh_lights else 0) |
                  (0 if small_blocks is None else (abi.FLAG_SMALL_BLOCKS if small_blocks else abi.FLAG_LARGE_BLOCKS)))
         prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0, tile_rank=tile_rank,
                          tile_nranks=tile_nranks, flags=flags, view_height=view_height)
