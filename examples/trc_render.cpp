@@ -5,6 +5,8 @@
 //   trc_render [--scene cornell|spheres|volume] [--integrator path|mis|volume] [--size W H] [--spp N]
 //              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
 //              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
+//              [--spin N]  after the frame, N more frames of the mesh turned about its own vertical axis (360 / N degrees per frame) through
+//                          trc_update_vertices: no second upload, the tree is refitted in place; frame k goes to <out>.k.png
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -12,7 +14,9 @@
 //   trc_render --pbrt scene.pbrt [--triangle-materials] [--integrator path|mis] [--spp N] [--size W H] [--out frame.png]
 //              a whole pbrt-v3 scene (camera, film, lights, materials, spheres, meshes: trc_host_scene_load_pbrt)
 //              --triangle-materials: every mesh keeps its own material (TRC_PBRT_TRIANGLE_MATERIALS + trc_upload_triangle_materials)
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +37,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
+    uint32_t spin = 0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -48,6 +53,11 @@ int main(int argc, char** argv) {
         else if (a == "--lbvh") lbvh = true;
         else if (a == "--device-sah") device_sah = true;
         else if (a == "--sobol") sobol = true;
+        else if (a == "--spin" && i + 1 < argc) {                               // moving geometry: trc_update_vertices per frame
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > 100000) { std::fprintf(stderr, "--spin wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
+            spin = (uint32_t)n;
+        }
         else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
         else if (a == "--triangle-materials") tri_materials = true;            // --pbrt: per-mesh materials instead of material 19
@@ -196,6 +206,35 @@ int main(int argc, char** argv) {
     std::printf("%s %ux%u %u spp %s: %llu rays, kernel %.2f ms (wall %.2f ms), %.1f Mrays/s, exposure %.4f -> %s\n",
                 scene_name.c_str(), W, H, spp, integ_name.c_str(), (unsigned long long)st.rays, st.kernel_ms, wall_ms,
                 st.rays / st.kernel_ms / 1e3, exposure, out.c_str());
+    if (spin && scene.n_vertex) {
+        // the mesh's world-space vertices, turned about the vertical axis through the centre of their box; normals alike
+        const std::vector<trc_TriangleVertex> rest(scene.triList, scene.triList + scene.n_vertex);
+        std::vector<trc_TriangleVertex> turned(rest);
+        float lo[3] = {rest[0].v[0], rest[0].v[1], rest[0].v[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+        for (const trc_TriangleVertex& q : rest)
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], q.v[k]); hi[k] = std::max(hi[k], q.v[k]); }
+        const float cx = 0.5f * (lo[0] + hi[0]), cz = 0.5f * (lo[2] + hi[2]);
+        for (uint32_t f = 1; f <= spin; ++f) {
+            const double a = 6.283185307179586 * f / spin;
+            const float ca = (float)std::cos(a), sa = (float)std::sin(a);
+            for (size_t i = 0; i < rest.size(); ++i) {
+                const float x = rest[i].v[0] - cx, z = rest[i].v[2] - cz;
+                turned[i].v[0] = cx + ca * x + sa * z; turned[i].v[2] = cz - sa * x + ca * z;
+                turned[i].n[0] = ca * rest[i].n[0] + sa * rest[i].n[2]; turned[i].n[2] = -sa * rest[i].n[0] + ca * rest[i].n[2];
+            }
+            const auto u0 = std::chrono::steady_clock::now();
+            CHECK(trc_update_vertices(ctx, turned.data(), 0, scene.n_vertex));
+            const double update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(trc_clear_accum(ctx));
+            CHECK(trc_render(ctx, &prm));
+            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            const std::string name = out + "." + std::to_string(f) + ".png";
+            if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+            std::printf("spin %u / %u: trc_update_vertices %.2f ms -> %s\n", f, spin, update_ms, name.c_str());
+        }
+    } else if (spin) {
+        std::fprintf(stderr, "--spin turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+    }
     trc_destroy(ctx);
     trc_host_scene_destroy(hs);
     trc_host_mesh_destroy(mesh);

@@ -51,8 +51,9 @@ extern "C" {
  * 11: primary replay: trc_debug_primary_replays, knob no_primary_replay; trc_stats.rays keeps counting every Scene::hit of the
  *    algorithm, the camera rays answered from the memo included (nothing existing changed)
  * 12: TRC_FLAG_MESH_LIGHTS: the emissive triangles of a mesh as sampled lights of traceMIS, knob mesh_light_pick (nothing existing
- *    changed) */
-#define TRC_ABI_VERSION 12
+ *    changed)
+ * 13: moving geometry: trc_update_vertices, trc_debug_refit_ms, knob refit_single (nothing existing changed) */
+#define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
 /* vector / matrix PODs (Apple simd layout)                            */
@@ -536,6 +537,45 @@ trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n
  *    flag the emissive triangles are sampled lights with a weighting of their own (TRC_FLAG_MESH_LIGHTS above); their tables
  *    are rebuilt after this call. */
 trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material, uint32_t n_triangles);
+/* Moving geometry: replaces vertices [first, first + count) of the uploaded scene's triList by new positions, normals and uv, and
+ * refits the tree in place.  The host of an animation calls it once per frame instead of uploading the scene again.
+ *  - The topology does not change: parent, left, right, axis, pType and pIndex of every record stay, and so does the child order
+ *    of the device's nodes.  The index list and the triangle count stay; spheres, squares and cubes do not move.
+ *  - A triangle leaf's box becomes what trc_host_build_node gives, under the identity matrix, for the box of its three CURRENT
+ *    vertices (what TRC_TREE_TRIANGLE_LEAVES writes at an upload).  An interior box becomes the component-wise min / max of its two
+ *    children's boxes; where the two bounds compare equal (-0 against +0) the right child's is kept, as by trc_host_build_tree.  The
+ *    root's box is the union of its two children.  Leaves of analytic primitives keep their boxes.  Only min and max of the
+ *    children are involved, so the result does not depend on the order of execution.  A tree of trc_host_build_tree refitted with
+ *    unchanged vertices is that tree again, bit for bit (tests/test_refit_cpu.py).
+ *  - Rendering after the call is rendering through that tree with those vertices: the same frame, RNG texture and ray counts as
+ *    uploading that tree with trc_upload_scene.
+ *  - It works on the tree of any upload: trc_upload_scene (the caller's tree), trc_upload_scene_lbvh / _sah / _device with or
+ *    without TRC_TREE_TRIANGLE_LEAVES.  For the device-built trees trc_download_bvh returns the refitted records afterwards; the
+ *    padding lane of a rewritten box corner is 0.
+ *  - The per-triangle materials of trc_upload_triangle_materials survive.
+ *  - TRC_ERR_NO_SCENE before any upload.  TRC_ERR_INVALID_ARG: vertices == NULL with count > 0, first + count > the scene's
+ *    n_vertex, a position that is not finite or has a coordinate beyond 1e37 in magnitude (trc_upload_scene_sah's bound), or
+ *    count > 0 on a scene without triangles.  On any of these errors nothing has changed (state
+ *    derived from the old geometry is dropped only once the new vertices are on their way to the device).  count == 0 is TRC_OK and changes nothing.
+ *  - Launches kept back for coalescing run first.  The G-buffer and the denoiser history are dropped, as by trc_upload_scene*.  The
+ *    tables of TRC_FLAG_MESH_LIGHTS are freed and rebuilt at the next flagged render (the areas changed).  trc_sppm_frames sees the
+ *    new geometry at its next call: a consistent SPPM pass restarts with trc_sppm_init.  The accumulator and the RNG texture are
+ *    not touched: the caller clears.  Textures, the environment, the camera, the density grid and the triangle materials stay.
+ *  - The launch planner's block costs are KEPT, as after a small camera move: the next launch is one pass ordered by the last
+ *    launch's raw durations.  Scheduling only, never a pixel.
+ *  - The new vertices are copied out of the caller's array before the call returns; the kernels run behind it on the context's
+ *    stream, like trc_render's.  (The root's box is an argument of every later launch: 24 bytes are copied back behind the refit,
+ *    and the next entry point that is entered waits for them.  The first update of a scene also waits once for its maps.)
+ *  - In a group every rank calls it for itself; it is not collective.
+ *  - It repairs nothing: after a large deformation the tree is valid but slow to walk, and a host that wants a fresh one calls
+ *    trc_upload_scene_device.  Only the triangles that name a changed vertex get their records rewritten; every box of the tree is
+ *    recomputed.
+ * The scene's vertex and index arrays stay on the device for this call (32 B per vertex + 12 B per triangle beside the blob),
+ * freed by the next trc_upload_scene* and by trc_destroy.
+ * Knob refit_single (trc_debug_set): 0 = one launch per depth of the tree (the default), 1 = one launch with a counter per node. */
+trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices, uint32_t first, uint32_t count);
+/* device time in ms of the kernels of the last trc_update_vertices (record rewrite + refit, without the transfer) */
+trc_status trc_debug_refit_ms(trc_ctx* ctx, float* ms);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),

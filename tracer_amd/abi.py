@@ -7,7 +7,7 @@ Triangle,Texture,Material,Camera}.hh (see the header for file:line).
 """
 import ctypes as C
 
-TRC_ABI_VERSION = 12
+TRC_ABI_VERSION = 13
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
@@ -250,7 +250,7 @@ DEVICE_SYMBOLS = [
     "trc_device_info", "trc_device_pci_bus_id", "trc_shard_seed", "trc_group_compose_samples", "trc_group_compose_samples_async", "trc_group_unique_id", "trc_group_init", "trc_group_reduce_accum", "trc_group_reduce_accum_async", "trc_group_allreduce_mean_accum", "trc_download_composed", "trc_group_finalize",
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape", "trc_debug_primary_replays",
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
-    "trc_upload_textures", "trc_upload_triangle_materials",
+    "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",

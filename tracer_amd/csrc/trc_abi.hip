@@ -68,6 +68,8 @@ __global__ void __launch_bounds__(256) k_triangle_materials(const uint32_t* __re
 // std::min({a, b, c}) keep the first of equals -- taken corner by corner through the identity matrix (column sums in the reference's
 // order, so a -0 comes out as the host's arithmetic leaves it) into fmin / fmax from +-FLT_MAX (the second operand on a tie, as the
 // host's minss / maxss).  One thread per triangle, one 64-byte leaf record out.
+// dev_trileaf.hpp triangle_leaf_box restates this arithmetic as a function for trc_update_vertices: keep the two alike
+// (tests/test_gpu_update_vertices_single.py holds them together).
 __global__ void __launch_bounds__(256) k_triangle_leaves(const trc_TriangleVertex* __restrict__ verts, const uint32_t* __restrict__ idx,
                                                          uint32_t n_tri, trc_BVH* __restrict__ leaves) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -105,21 +107,23 @@ trc_status trc_repack_triangles(trc_ctx* ctx, const trc_scene* s, const DScene& 
     const uint32_t n_tri = s->n_index / 3;
     ctx->tri_materials = false;                  // every triangle is material 19 again
     trc_mesh_light_free(ctx);                    // TRC_FLAG_MESH_LIGHTS: rebuilt for the new scene when a launch asks
+    trc_refit_free(ctx);                         // trc_update_vertices: the arrays and maps of the scene before
     if (n_tri == 0) return TRC_OK;
-    trc_TriangleVertex* d_verts = nullptr;
-    uint32_t* d_idx = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_verts, (size_t)s->n_vertex * sizeof(trc_TriangleVertex)));
-    if (hipMalloc((void**)&d_idx, (size_t)s->n_index * 4) != hipSuccess) { (void)hipFree(d_verts); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc triangle indices"); }
+    // the vertex and index arrays stay on the device beside the blob (32 B per vertex + 12 B per triangle): trc_update_vertices
+    // rewrites the triangle records and the leaf boxes from them
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_verts, (size_t)s->n_vertex * sizeof(trc_TriangleVertex)));
+    if (hipMalloc((void**)&ctx->d_idx, (size_t)s->n_index * 4) != hipSuccess) { trc_refit_free(ctx); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc triangle indices"); }
+    ctx->n_vertex = s->n_vertex;
     trc_status st = TRC_OK;
     do {
-        if (trc_copy_to_device(ctx, d_verts, s->triList, (size_t)s->n_vertex * sizeof(trc_TriangleVertex), ctx->stream) != TRC_OK ||
-            trc_copy_to_device(ctx, d_idx, s->idxList, (size_t)s->n_index * 4, ctx->stream) != TRC_OK) { st = trc_fail(ctx, TRC_ERR_HIP, "H2D triangles"); break; }
-        hipLaunchKernelGGL(k_repack_triangles, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, d_verts, d_idx, n_tri,
+        if (trc_copy_to_device(ctx, ctx->d_verts, s->triList, (size_t)s->n_vertex * sizeof(trc_TriangleVertex), ctx->stream) != TRC_OK ||
+            trc_copy_to_device(ctx, ctx->d_idx, s->idxList, (size_t)s->n_index * 4, ctx->stream) != TRC_OK) { st = trc_fail(ctx, TRC_ERR_HIP, "H2D triangles"); break; }
+        hipLaunchKernelGGL(k_repack_triangles, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri,
                            reinterpret_cast<float4*>(d_blob + sc.off_tripos), reinterpret_cast<float4*>(d_blob + sc.off_triattr));
-        if (d_tri_leaves) hipLaunchKernelGGL(k_triangle_leaves, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, d_verts, d_idx, n_tri, d_tri_leaves);
+        if (d_tri_leaves) hipLaunchKernelGGL(k_triangle_leaves, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri, d_tri_leaves);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, "k_repack_triangles"); break; }
     } while (0);
-    (void)hipFree(d_verts); (void)hipFree(d_idx);
+    if (st != TRC_OK) trc_refit_free(ctx);
     return st;
 }
 
@@ -1137,7 +1141,7 @@ void trc_destroy(trc_ctx* ctx) {
     trc_denoise_release(ctx);
     collect_events(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); trc_env_light_free(ctx); trc_mesh_light_free(ctx); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
+    (void)hipFree(ctx->d_blob); (void)hipFree(ctx->d_bvh_ref); (void)hipFree(ctx->d_density); (void)hipFree(ctx->d_occupancy); (void)hipFree(ctx->d_envmap); trc_env_light_free(ctx); trc_mesh_light_free(ctx); trc_refit_free(ctx); (void)hipFree(ctx->d_tex_texels); (void)hipFree(ctx->d_tex_desc); (void)hipFree(ctx->d_sobol32); (void)hipFree(ctx->d_sobol_vdc); (void)hipFree(ctx->d_rng); (void)hipFree(ctx->d_accum);
     (void)hipFree(ctx->d_tiles); (void)hipFree(ctx->d_stats); (void)hipFree(ctx->d_stats_sum); (void)hipFree(ctx->d_reduce_recv);
     (void)hipFree(ctx->d_block_cost); (void)hipFree(ctx->d_order_hist); (void)hipFree(ctx->d_split); (void)hipFree(ctx->d_whole); (void)hipFree(ctx->d_cost_est); (void)hipFree(ctx->d_qsplit); (void)hipFree(ctx->d_qwhole); (void)hipFree(ctx->d_swhole); (void)hipFree(ctx->d_launch); (void)hipFree(ctx->d_plan); (void)hipFree(ctx->d_plan_gather); (void)hipFree(ctx->d_cost_scratch);
     for (int k = 0; k < 2; ++k) { (void)hipFree(ctx->d_order_keys[k]); (void)hipFree(ctx->d_order_vals[k]); }
@@ -1547,7 +1551,9 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
 // samples before it looks gets them at the fused rate: 64 x 1 spp 34.8 -> 2x.x ms.  Knob no_coalesce switches it off.
 constexpr uint32_t kCoalesceBelow = 8, kCoalesceUpTo = 16;
 trc_status trc_flush(trc_ctx* ctx) {
-    if (!ctx || !ctx->has_deferred) return TRC_OK;
+    if (!ctx) return TRC_OK;
+    { const trc_status rs = trc_refit_settle(ctx); if (rs != TRC_OK) return rs; }      // trc_update_vertices returns before its root box has
+    if (!ctx->has_deferred) return TRC_OK;
     ctx->has_deferred = false;
     const trc_params q = ctx->deferred;
     const uint64_t calls = ctx->deferred_calls;
@@ -1901,6 +1907,7 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     RenderLaunch r;
     { const trc_status st = render_check(ctx, p, &r.kp.sobol_m); if (st != TRC_OK) return st; }
     if (p->spp == 0) return TRC_OK;
+    { const trc_status st = trc_refit_settle(ctx); if (st != TRC_OK) return st; }      // ks.root_box of a trc_update_vertices just before
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     collect_finished_events(ctx);        // before any launch of this call: it may consume a "not ready" sticky error
     r.stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
@@ -2500,7 +2507,7 @@ trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value) {
     { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
     if (!ctx || !knob) return TRC_ERR_INVALID_ARG;
     const std::string k(knob);
-    int* slot = k == "no_lds_fit" ? &ctx->knobs.no_lds_fit : k == "stack_lds_levels" ? &ctx->knobs.stack_lds_levels
+    int* slot = k == "refit_single" ? &ctx->knobs.refit_single : k == "no_lds_fit" ? &ctx->knobs.no_lds_fit : k == "stack_lds_levels" ? &ctx->knobs.stack_lds_levels
               : k == "strip_len" ? &ctx->knobs.strip_len : k == "no_pwg" ? &ctx->knobs.no_pwg
               : k == "sppm_serial_camera" ? &ctx->knobs.sppm_serial_camera : k == "sppm_timing" ? &ctx->knobs.sppm_timing
               : k == "force_blk_shift" ? &ctx->knobs.force_blk_shift : k == "no_split" ? &ctx->knobs.no_split : k == "no_cost_filter" ? &ctx->knobs.no_cost_filter

@@ -163,6 +163,17 @@ struct trc_ctx {
     trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh, reference array layout (trc_download_bvh)
     uint32_t n_bvh_ref = 0, lbvh_height = 0;
     float lbvh_build_ms = 0.0f;
+    // trc_update_vertices (trc_refit.hip): the scene's vertex and index arrays, kept beside the blob by every upload
+    // (trc_repack_triangles), and the refit maps, made at the first update of a scene; all freed with the blob (trc_refit_free)
+    trc_TriangleVertex* d_verts = nullptr; uint32_t* d_idx = nullptr; uint32_t n_vertex = 0;
+    uint32_t* d_refit_parent = nullptr;     // [n_nodes] fat node that holds this fat node's box (root: itself)
+    uint32_t* d_refit_refnode = nullptr;    // [n_nodes] device-built trees: this fat node's record in d_bvh_ref
+    uint32_t* d_refit_arrive = nullptr;     // [n_nodes] arrival counters of the single-launch climb (zero between updates)
+    float* d_refit_root = nullptr;          // [8] the refitted root box
+    std::vector<uint32_t> refit_levels;     // first fat node of every depth, and n_nodes behind them (the fat nodes are numbered by depth)
+    float refit_ms = 0.0f;                  // device time of the last update's kernels (trc_debug_refit_ms)
+    hipEvent_t refit_ev[3] = {nullptr, nullptr, nullptr};      // around the update's kernels; behind the root box's copy to h_readback
+    bool refit_pending = false;             // ks.root_box and refit_ms still wait for refit_ev[2] (trc_refit_settle)
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -258,13 +269,17 @@ struct trc_ctx {
     bool coll_active = false;
     void* h_stage = nullptr;            // pinned staging buffer of host-staged collectives
     size_t h_stage_bytes = 0;
-    uint32_t* h_readback = nullptr;     // 1 KB of pinned host memory for the per-level counter read-back of trc_upload_scene_sah
+    // 1 KB of pinned host memory (trc_readback_alloc) for small read-backs: the per-level counter block of trc_upload_scene_sah, and of
+    // trc_update_vertices the level table (first update of a scene) and the refitted root box.  The root box's copy is still in flight
+    // when trc_update_vertices returns; that is safe only because every entry point calls trc_flush first, which settles it
+    // (trc_refit_settle) before anything else writes or reads the buffer
+    uint32_t* h_readback = nullptr;
     char* h_xfer = nullptr;             // 2 x kXferChunk bytes of pinned host memory: every transfer to / from caller memory goes through it (trc_copy_*)
     hipEvent_t ev_xfer[2] = {nullptr, nullptr};
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
-    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1; } knobs;
+    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1, refit_single = 0; } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_abi.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;
@@ -354,4 +369,12 @@ EnvLight trc_env_light_view(const trc_ctx* ctx);
 trc_status trc_mesh_light_build(trc_ctx* ctx);
 void trc_mesh_light_free(trc_ctx* ctx);
 MeshLight trc_mesh_light_view(const trc_ctx* ctx);
+constexpr size_t kReadbackBytes = 1024;
+inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once per context; freed by trc_destroy
+    if (!ctx->h_readback) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_readback, kReadbackBytes, hipHostMallocDefault));
+    return TRC_OK;
+}
+trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices left for later (ks.root_box)
+inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
+void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays and the refit maps (no-op when absent)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)

@@ -119,6 +119,8 @@ def _load(path, hooks=False):
     L.trc_denoise_reset.argtypes = [vp]
     L.trc_upload_textures.argtypes = [vp, C.POINTER(abi.Image), u32]
     L.trc_upload_triangle_materials.argtypes = [vp, vp, u32]
+    L.trc_update_vertices.argtypes = [vp, vp, u32, u32]
+    L.trc_debug_refit_ms.argtypes = [vp, C.POINTER(C.c_float)]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -220,6 +222,19 @@ class Tracer:
         # an empty array is an array of the wrong length for a scene with triangles (refused), not None: never pass it as NULL
         buf = m if m.size else np.zeros(1, np.uint32)
         self._check(self._L.trc_upload_triangle_materials(self._h, buf.ctypes.data, m.size), "trc_upload_triangle_materials")
+
+    def update_vertices(self, vertices, first=0):
+        """trc_update_vertices: (n, 8) float32 rows of trc_TriangleVertex (position, normal, uv) replace vertices [first, first + n) of
+        the uploaded scene's triList, and the tree is refitted in place.  The accumulator is not cleared."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 8)
+        buf = v if v.size else np.zeros((1, 8), np.float32)      # an empty array is count == 0, never NULL with a count
+        self._check(self._L.trc_update_vertices(self._h, buf.ctypes.data, first, v.shape[0]), "trc_update_vertices")
+
+    def refit_ms(self):
+        """device time in ms of the kernels of the last update_vertices (trc_debug_refit_ms)"""
+        ms = C.c_float(0)
+        self._check(self._L.trc_debug_refit_ms(self._h, C.byref(ms)), "trc_debug_refit_ms")
+        return ms.value
 
     def texture_sample(self, index, uv):
         """hooks build only: the render kernels' lookup of image `index` at (n, 2) float32 uv -> (n, 3) float32."""
