@@ -19,7 +19,7 @@ HIPFLAGS  := -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-s
 
 HOST_SRC  := tracer_amd/host/bvh_builder.cpp tracer_amd/host/scene.cpp tracer_amd/host/mesh.cpp tracer_amd/host/pbrt_scene.cpp tracer_amd/host/png_reader.cpp
 HOST_HDR  := tracer_amd/host/host_math.hpp tracer_amd/host/host_scene.hpp tracer_amd/host/pbrt_text.hpp include/tracer_abi.h include/trc_sobol.h
-HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_lds.hip tracer_amd/csrc/trc_render_lds_mis.hip tracer_amd/csrc/trc_render_mem.hip tracer_amd/csrc/trc_render_mem_path.hip tracer_amd/csrc/trc_render_mem_volume.hip tracer_amd/csrc/trc_sppm.hip tracer_amd/csrc/trc_lbvh.hip tracer_amd/csrc/trc_denoise.hip tracer_amd/csrc/trc_envlight.hip tracer_amd/csrc/trc_meshlight.hip tracer_amd/csrc/trc_refit.hip \
+HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_pass.hip tracer_amd/csrc/trc_schedule.hip tracer_amd/csrc/trc_group.hip tracer_amd/csrc/trc_hooks.hip tracer_amd/csrc/trc_render_lds.hip tracer_amd/csrc/trc_render_lds_mis.hip tracer_amd/csrc/trc_render_mem.hip tracer_amd/csrc/trc_render_mem_path.hip tracer_amd/csrc/trc_render_mem_volume.hip tracer_amd/csrc/trc_sppm.hip tracer_amd/csrc/trc_lbvh.hip tracer_amd/csrc/trc_denoise.hip tracer_amd/csrc/trc_envlight.hip tracer_amd/csrc/trc_meshlight.hip tracer_amd/csrc/trc_refit.hip \
              $(patsubst %,tracer_amd/csrc/trc_render_%_tm.hip,lds lds_mis mem mem_path mem_volume)
 # per translation unit: backend options that pay for ONE kernel family (profiles/r05/ab_flags*.txt: eight scheduler / sinking / LICM options
 # tried on configs 2 / 3 / 4; everything else is within +-1 % or worse).  Scheduling only: the parity suites run on this build.
@@ -60,7 +60,7 @@ $(LIBDIR)/libtracer_amd.so: $(HIP_OBJ)
 # Product and laboratory apart: the entry points of include/tracer_test_hooks.h (exhaustive arithmetic checks, the SPPM hash,
 # the per-site cycle profile) exist only in this build of the SAME sources.  Only the translation units that define them are
 # compiled again; the render kernels are the product's objects, byte for byte.
-HOOK_TU      := trc_abi trc_sppm trc_denoise trc_envlight trc_meshlight
+HOOK_TU      := trc_hooks trc_sppm trc_denoise trc_envlight trc_meshlight
 HIP_OBJ_HOOKS := $(foreach o,$(HIP_OBJ),$(if $(filter $(HOOK_TU),$(basename $(notdir $(o)))),build/obj/hooks/$(notdir $(o)),$(o)))
 build/obj/hooks/%.o: tracer_amd/csrc/%.hip $(HIP_HDR) Makefile
 	@mkdir -p build/obj/hooks

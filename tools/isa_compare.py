@@ -1,6 +1,7 @@
 """Compare the gfx950 code of every kernel of two device-only assembly builds (hipcc --cuda-device-only -S, one .s per translation
 unit): per kernel, the instruction stream with comments and branch-target labels masked, and the registers / scratch / occupancy
-of its metadata.  Usage: isa_compare.py OLD_DIR NEW_DIR  (prints one line per kernel; kernels only in NEW_DIR are listed as new)."""
+of its metadata.  A kernel that moved to another translation unit is matched by its mangled name across the units of OLD_DIR.
+Usage: isa_compare.py OLD_DIR NEW_DIR  (prints one line per kernel; kernels only in NEW_DIR are listed as new)."""
 import os
 import re
 import subprocess
@@ -53,12 +54,13 @@ def occupancy(vgpr, agpr):
 
 def main(old_dir, new_dir):
     rows = []
-    for f in sorted(os.listdir(new_dir)):
-        if not f.endswith(".s"):
-            continue
-        tu = f[:-2]
-        new = kernels(os.path.join(new_dir, f))
-        old = kernels(os.path.join(old_dir, f)) if os.path.exists(os.path.join(old_dir, f)) else {}
+    old_units = {f[:-2]: kernels(os.path.join(old_dir, f)) for f in sorted(os.listdir(old_dir)) if f.endswith(".s")}
+    new_units = {f[:-2]: kernels(os.path.join(new_dir, f)) for f in sorted(os.listdir(new_dir)) if f.endswith(".s")}
+    elsewhere = lambda units, tu, k: next((v[k] for u, v in units.items() if u != tu and k in v), None)
+    for tu, new in new_units.items():
+        # the unit's own kernels of OLD_DIR, and -- by mangled name -- the ones that came here from another unit
+        old = dict(old_units.get(tu, {}))
+        old.update({k: elsewhere(old_units, tu, k) for k in new if k not in old and elsewhere(old_units, tu, k)})
         names = demangle(list(new))
         for k, (body, (v, s, p, a)) in sorted(new.items(), key=lambda kv: (kv[0] not in old, names[kv[0]])):
             if k in old:
@@ -67,8 +69,11 @@ def main(old_dir, new_dir):
                 state = "new"
             rows.append((tu, names[k], state, len(body), v, s, p, occupancy(v, a)))
         for k in old:
-            if k not in new:
+            if k not in new and not elsewhere(new_units, tu, k):
                 rows.append((tu, demangle([k])[k], "MISSING", 0, "-", "-", "-", "-"))
+    for tu, old in old_units.items():           # a unit that is gone: what it held and no unit holds now
+        if tu not in new_units:
+            rows += [(tu, demangle([k])[k], "MISSING", 0, "-", "-", "-", "-") for k in old if not elsewhere(new_units, tu, k)]
     print(f"{'translation unit':22} {'kernel':70} {'code':10} {'instructions':>12} {'vgpr':>5} {'sgpr':>5} {'scratch':>8} {'occ':>4}")
     for r in rows:
         print(f"{r[0]:22} {r[1][:70]:70} {r[2]:10} {r[3]:12} {r[4]:>5} {r[5]:>5} {r[6]:>8} {r[7]:>4}")

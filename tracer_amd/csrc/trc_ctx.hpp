@@ -1,5 +1,6 @@
-// trc_ctx.hpp -- pieces shared by the translation units of libtracer_amd.so (trc_abi.hip, trc_sppm.hip):
-// kernel-side scene staging helpers, the context struct and the error helpers.
+// trc_ctx.hpp -- pieces shared by the translation units of libtracer_amd.so (trc_abi.hip, trc_render_pass.hip, trc_schedule.hip,
+// trc_group.hip, trc_sppm.hip ...): kernel-side scene staging helpers, the context struct, the error helpers and what one unit
+// calls of another.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +29,7 @@ constexpr uint32_t kLaunchIndexMask = (1u << kLaunchCodeShift) - 1u;
 // duration slots per 8x8 block of a list that may be split (KRender::cost_stride): 0..3 the quarters (0 also the whole
 // block), 4..19 the sixteenths, 20..83 the pixels -- slot = code - 1
 constexpr uint32_t kCostSlots = 84u;
-constexpr uint32_t kPlanWords = 12u;          // trc_abi.hip k_plan_split
+constexpr uint32_t kPlanWords = 12u;          // trc_schedule.hip k_plan_split
 
 struct KScene {
     DScene sc;
@@ -208,7 +209,7 @@ struct trc_ctx {
     uint32_t* d_order_keys[2] = {nullptr, nullptr};
     uint32_t* d_order_vals[2] = {nullptr, nullptr};
     uint32_t* d_order_hist = nullptr;
-    // cost-adaptive block size (trc_abi.hip::plan_split): which 8x8 blocks the last launch ran as four 4x4 quarters, the
+    // cost-adaptive block size (trc_schedule.hip: k_plan_split): which 8x8 blocks the last launch ran as four 4x4 quarters, the
     // launch list with the quarters spliced in, and the plan {quarters' parents K, entries}
     uint32_t* d_split = nullptr;
     uint32_t* d_whole = nullptr;        // cost of a block when it last ran whole (while it runs as quarters)
@@ -280,7 +281,7 @@ struct trc_ctx {
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
     struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1, refit_single = 0; } knobs;
-    // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_abi.hip: launch_render):
+    // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;
 
@@ -359,7 +360,7 @@ inline uint32_t trc_scene_min_image(const trc_scene* s) {
         if (s->materials[i].textureInfo.type == TRC_TEX_IMAGE && s->materials[i].textureInfo.textureIndex < m) m = s->materials[i].textureInfo.textureIndex;
     return m;
 }
-void trc_denoise_invalidate(trc_ctx* ctx);   // another scene or environment: the G-buffer is stale and the history dropped
+void trc_denoise_invalidate(trc_ctx* ctx);   // trc_picture_changed: the G-buffer is stale and the history dropped
 // TRC_FLAG_ENV_LIGHT (trc_envlight.hip): build the current map's sampling tables if they are not built (TRC_ERR_OOM: nothing kept), free
 // them, and the kernels' view of them
 trc_status trc_env_light_build(trc_ctx* ctx);
@@ -378,3 +379,30 @@ trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the la
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
 void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays and the refit maps (no-op when absent)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
+
+// ----------------------------------------------------------------------- what is stale now
+// Every entry point that changes what the context's caches were derived from says so through one of these three.
+// trc_forget_costs: the recorded block costs and the launch orders sorted from them are another picture's -- the next launch
+// measures afresh (its cold head).  Called by trc_scene_changed, by the scheduler where a launch's list is not the one the costs
+// were recorded for (trc_ensure_tiles, drop_stale_costs) and by trc_debug_set.  trc_set_camera keeps a rule of its own: it carries
+// the old order over as the next cold pass's prior.
+inline void trc_forget_costs(trc_ctx* ctx) { ctx->cost_valid = false; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr; }
+// trc_picture_changed: what a pixel shows changed -- the denoiser's G-buffer is stale and its history dropped.  Called by
+// trc_scene_changed and by the entry points that change the lighting or the colours alone: trc_set_environment,
+// trc_set_environment_map, trc_upload_textures.
+inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
+// trc_scene_changed (trc_abi.hip): the geometry or its materials changed.  Every kind drops the picture (trc_picture_changed) and the
+// emissive triangles' sampling tables (TRC_FLAG_MESH_LIGHTS: rebuilt when a launch asks).
+//   kSceneReplaced      trc_upload_scene, upload_device_tree (trc_upload_scene_lbvh / _sah / _device), BEFORE they allocate the new
+//                       scene: also forgets the block costs and releases the old scene (trc_release_scene: blob, reference-layout
+//                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
+//   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
+//   kSceneVerticesMoved trc_update_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
+enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved };
+void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
+// Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:
+void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload allocates
+void trc_release_frame(trc_ctx* ctx);    // trc_abi.hip: what depends on the frame size (trc_resize): frame, block list, compose buffers, SPPM, denoiser
+void trc_release_tiles(trc_ctx* ctx);    // trc_schedule.hip: the block list and the arrays sized by it (trc_ensure_tiles)
+void trc_collect_finished_events(trc_ctx* ctx);   // trc_abi.hip: completed event pairs into kernel_ms / schedule_ms without waiting (render_pass)
+void trc_launch_stats_sum(trc_ctx* ctx);          // trc_abi.hip: k_stats_sum of d_stats into d_stats_sum on the context's stream

@@ -1,0 +1,145 @@
+// trc_hooks.hip -- the arithmetic, texture and profile entry points of include/tracer_test_hooks.h with their kernels:
+// compiled with -DTRC_TEST_HOOKS for libtracer_amd_hooks.so (Makefile: HOOK_TU); the product's build holds trc_has_test_hooks alone.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "trc_ctx.hpp"
+
+extern "C" int trc_has_test_hooks(void) {
+#ifdef TRC_TEST_HOOKS
+    return 1;
+#else
+    return 0;
+#endif
+}
+
+#ifdef TRC_TEST_HOOKS      // libtracer_amd_hooks.so only (include/tracer_test_hooks.h)
+// trc_div_by_test: a[i] / b[i] through the guarded shared-divisor path (three numerators a, -a, a * 0.75 on one divisor) and
+// through the plain division
+__global__ void __launch_bounds__(256) k_div_by_test(const float* a, const float* b, uint32_t n, float* fast, float* plain) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float av = a[i], bv = b[i];
+    const GuardedDivBy d = guarded_div_by(bv);
+    const F3 q = guarded_div(f3(av, -av, av * 0.75f), d);
+    fast[3 * i] = q.x; fast[3 * i + 1] = q.y; fast[3 * i + 2] = q.z;
+    plain[3 * i] = av / bv; plain[3 * i + 1] = -av / bv; plain[3 * i + 2] = (av * 0.75f) / bv;
+}
+
+// trc_unary_test: rcp_cr / sqrt_cr / rsqrt_cr (dev_vec.hpp) against the compiler's 1.0f / x, sqrtf(x), 1.0f / sqrtf(x) over a
+// range of BIT PATTERNS; counts the operands whose results differ (NaN == NaN) and keeps the smallest one
+__global__ void __launch_bounds__(256) k_unary_test(uint32_t op, uint32_t first, uint64_t count, unsigned long long* out) {
+    unsigned long long bad = 0, first_bad = ~0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t bits = first + (uint32_t)i;
+        const float x = __uint_as_float(bits);
+        float a, b;
+        if (op == 0u) { a = rcp_cr(x); b = 1.0f / x; }
+        else if (op == 1u) { a = sqrt_cr(x); b = sqrtf(x); }
+#if TRC_WAVE_GUARDS
+        else if (op == 3u) { a = div_const(x, div_by_pi()); b = x / kPi; }
+        else if (op == 4u) { a = div_const(x, div_by_sqr001()); b = x / (0.01f * 0.01f); }
+        else if (op == 5u) { a = div_const(x, div_by_sqr002()); b = x / (0.02f * 0.02f); }
+        else if (op == 6u) { a = div_const(x, div_by_sqr01()); b = x / (0.1f * 0.1f); }
+#endif
+        else { a = rsqrt_cr(x); b = 1.0f / sqrtf(x); }
+        const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
+        if (!same) { bad++; first_bad = min(first_bad, (unsigned long long)bits); }
+    }
+    if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first_bad); }
+}
+
+extern "C" {
+// developer diagnostic: (lanes, wavefronts) that executed each ProfSite of the instrumented kernels
+trc_status trc_debug_profile(trc_ctx* ctx, uint64_t* out, uint32_t n_sites) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    if (!ctx || !out) return TRC_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long h[kStatCount + 3 * kProfCount];
+    trc_launch_stats_sum(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < n_sites && i < (uint32_t)kProfCount; ++i)
+        for (int k = 0; k < 3; ++k) out[3 * i + k] = h[kStatCount + 3 * i + k];
+    return TRC_OK;
+}
+
+// the render kernels' image lookup (dev_integrator.hpp image_sample), one lane per uv pair
+__global__ void __launch_bounds__(256) k_texture_sample_test(const float* texels, const uint4* desc, uint32_t n_tex, uint32_t index,
+                                                             const float* uv, uint32_t n, float* rgb) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    TexTable tt; tt.texels = texels; tt.desc = desc; tt.n = n_tex;
+    F2 p; p.x = uv[2 * i]; p.y = uv[2 * i + 1];
+    const F3 c = image_sample(tt, index, p);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv, size_t n, float* rgb) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    if (!ctx || (n && (!uv || !rgb))) return TRC_ERR_INVALID_ARG;
+    if (index >= ctx->n_tex) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: no such image");
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 3u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: too many pairs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float* d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d, n * 5 * sizeof(float)));
+    float *d_uv = d, *d_rgb = d + 2 * n;
+    trc_status ts = trc_copy_to_device(ctx, d_uv, uv, n * 8, ctx->stream);
+    if (ts == TRC_OK) {
+        hipLaunchKernelGGL(k_texture_sample_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->d_tex_texels, ctx->d_tex_desc, ctx->n_tex, index, d_uv, (uint32_t)n, d_rgb);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_texture_sample_test: ") + hipGetErrorString(e));
+    }
+    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, rgb, d_rgb, n * 12, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return ts;
+}
+
+trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t n, float* fast, float* plain) {
+    if (!ctx || (n && (!a || !b || !fast || !plain))) return TRC_ERR_INVALID_ARG;
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 3u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_div_by_test: too many pairs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float* d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d, n * 8 * sizeof(float)));
+    float *d_a = d, *d_b = d + n, *d_fast = d + 2 * n, *d_plain = d + 5 * n;
+    trc_status ts = trc_copy_to_device(ctx, d_a, a, n * 4, ctx->stream);
+    if (ts == TRC_OK) ts = trc_copy_to_device(ctx, d_b, b, n * 4, ctx->stream);
+    if (ts == TRC_OK) {
+        hipLaunchKernelGGL(k_div_by_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_a, d_b, (uint32_t)n, d_fast, d_plain);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_div_by_test: ") + hipGetErrorString(e));
+    }
+    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, fast, d_fast, n * 12, ctx->stream);
+    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, plain, d_plain, n * 12, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return ts;
+}
+
+trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch) {
+    if (!ctx || !n_mismatch || op > 6u || count > (1ull << 32)) return TRC_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long* d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d, 16));
+    const unsigned long long init[2] = {0ull, ~0ull};
+    unsigned long long h[2] = {0ull, ~0ull};
+    hipError_t e = hipMemcpyAsync(d, init, 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && count) {
+        hipLaunchKernelGGL(k_unary_test, dim3(ctx->cu_count * 16), dim3(256), 0, ctx->stream, op, first_bits, count, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); else (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_unary_test: ") + hipGetErrorString(e));
+    *n_mismatch = h[0];
+    if (first_mismatch) *first_mismatch = (uint32_t)h[1];
+    return TRC_OK;
+}
+
+}  // extern "C"
+#endif  // TRC_TEST_HOOKS

@@ -530,10 +530,7 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     fill_primitives(s, sc, blob.get());
 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_blob) { (void)hipFree(ctx->d_blob); ctx->d_blob = nullptr; }
-    if (ctx->d_bvh_ref) { (void)hipFree(ctx->d_bvh_ref); ctx->d_bvh_ref = nullptr; }
-    ctx->has_scene = false; ctx->n_bvh_ref = 0;
-    trc_denoise_invalidate(ctx);
+    trc_scene_changed(ctx, kSceneReplaced);      // another scene: the old one goes, with everything derived from it
     ctx->blob_bytes = (size_t)total * 4;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bvh_ref, sizeof(trc_BVH) * n_nodes));
@@ -667,7 +664,6 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     ctx->lbvh_build_ms = ms;
     ctx->has_scene = true;
     ctx->scene_min_image = trc_scene_min_image(s);
-    ctx->cost_valid = false; ctx->d_last_order = nullptr;      // another scene: the recorded block costs say nothing about it
     return TRC_OK;
 }
 

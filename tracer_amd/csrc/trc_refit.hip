@@ -275,8 +275,7 @@ trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices,
     hipStream_t st = ctx->stream;
     { const trc_status cs = trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st); if (cs != TRC_OK) return cs; }
     // the copy is queued, so from here on the scene changes: what was derived from the old geometry goes
-    trc_denoise_invalidate(ctx);
-    trc_mesh_light_free(ctx);                    // TRC_FLAG_MESH_LIGHTS: the areas changed, rebuilt when a launch asks
+    trc_scene_changed(ctx, kSceneVerticesMoved);     // (TRC_FLAG_MESH_LIGHTS: the areas changed)
 
     KRefit p{};
     p.nodes = reinterpret_cast<uint4*>(ctx->d_blob + sc.off_nodes); p.n_nodes = sc.n_nodes;

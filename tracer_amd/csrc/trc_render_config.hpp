@@ -1,6 +1,6 @@
 // trc_render_config.hpp -- compile-time shape of the render kernels (launch bounds, persistent-workgroup geometry, stack and
 // record policy per integrator), shared by the translation units that DEFINE the kernels (trc_render_lds.hip, trc_render_mem.hip)
-// and the one that plans and launches them (trc_abi.hip).  Every value is an A/B macro: make variant NAME=x DEFS=-D...
+// and the ones that plan and launch them (trc_render_pass.hip, trc_schedule.hip).  Every value is an A/B macro: make variant NAME=x DEFS=-D...
 #pragma once
 
 #include "trc_ctx.hpp"
@@ -160,7 +160,7 @@ constexpr uint32_t pwg_stack_lds_levels(int integrator) { return integrator == T
 constexpr int pwg_per_cu(int integrator) { return integrator == TRC_INTEGRATOR_PATH ? TRC_PWG_PER_CU_PATH : (integrator == TRC_INTEGRATOR_MIS ? TRC_PWG_PER_CU_MIS : TRC_PWG_PER_CU_VOLUME); }
 
 // wavefronts per SIMD each kernel kind is compiled for: its __launch_bounds__ (trc_render_kernels.hpp) and what the host plans
-// with (trc_abi.hip: the LDS plan, the split plan's wavefront slots) -- one value, read from the kernel table
+// with (trc_render_pass.hip: the LDS plan; trc_schedule.hip: the split plan's wavefront slots) -- one value, read from the kernel table
 constexpr int render_waves(bool lds, bool stats, int integrator) {      // k_render, k_render_tex (statistics: one wavefront)
     return stats ? 1 : integrator == TRC_INTEGRATOR_VOLUME ? TRC_VOLUME_WAVES
                      : integrator == TRC_INTEGRATOR_MIS ? (lds ? TRC_MIS_WAVES_LDS : TRC_MIS_WAVES) : (lds ? TRC_PATH_WAVES : TRC_PATH_WAVES_GLOBAL);
@@ -176,13 +176,18 @@ constexpr int pwg_simd_waves(int integrator) { return pwg_waves(integrator) * pw
 //   trc_render_mem.hip        traceMIS, trees read from memory
 //   trc_render_mem_volume.hip traceVolume, trees read from memory                                             -disable-machine-sink
 // Each exports the kernel table of its families (render_kernels<LDS, INTEGRATOR>), which instantiates exactly the kernels in it;
-// trc_abi.hip launches whatever entry a launch picks.  A null entry is a variant that does not exist.
+// trc_render_pass.hip launches whatever entry a launch picks.  A null entry is a variant that does not exist.
+enum RenderArgs { kArgsPlain, kArgsEnv, kArgsMesh };      // the kernel's parameter block: KRender, KRenderEnv (TRC_FLAG_ENV_LIGHT), KRenderMesh (TRC_FLAG_MESH_LIGHTS)
 struct RenderKernel {
-    void (*fn)(KRender);                // the kernel
+    const void* fn;                     // the kernel (null: no such variant)
     int waves;                          // wavefronts per SIMD of its launch bounds
-    void (*fn_env)(KRenderEnv);         // ... or the kernel, when it takes the environment map's sampling tables too (TRC_FLAG_ENV_LIGHT)
-    void (*fn_mesh)(KRenderMesh);       // ... or the emissive triangles' (TRC_FLAG_MESH_LIGHTS)
+    RenderArgs args;                    // ... and which parameter block launch_render hands it
 };
+// A table entry is made from the kernel itself, so the parameter block is checked by the compiler where the kernel is named.
+// (Not constexpr: a function pointer becomes a data pointer by reinterpret_cast only.  The tables are filled when the library loads.)
+inline RenderKernel render_kernel(void (*fn)(KRender), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsPlain}; }
+inline RenderKernel render_kernel(void (*fn)(KRenderEnv), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsEnv}; }
+inline RenderKernel render_kernel(void (*fn)(KRenderMesh), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsMesh}; }
 // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures, TRC_FLAG_ENV_LIGHT (traceMIS only) without and with image textures,
 // TRC_FLAG_MESH_LIGHTS (traceMIS only) without and with image textures
 enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariantEnv, kVariantEnvTex, kVariantMesh, kVariantMeshTex, kVariants };

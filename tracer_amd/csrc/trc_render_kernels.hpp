@@ -1,6 +1,6 @@
 // trc_render_kernels.hpp -- kernelPathTracing (RT_Metal/Metal/Render.metal:495-558) as HIP kernels: DEFINITIONS.  Included by the
 // five translation units that instantiate them through their kernel tables (render_kernels below; trc_render_config.hpp says which
-// and why); trc_abi.hip only launches them.
+// and why); trc_render_pass.hip only launches them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -332,7 +332,7 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLig
     uint32_t* memo = nullptr;
     if constexpr (MEMO != 0 && MEMO_GLOBAL) memo = kp.memo + (size_t)blockIdx.x * MEMO * kBlock + lane;
     else if constexpr (MEMO != 0) memo = stack + (sc.stack_lds + PARK) * kBlock;
-    if constexpr (PARK != 0) {                  // the park rows follow the stack rows of this one-wavefront workgroup (trc_abi.hip: dense_lds_bytes)
+    if constexpr (PARK != 0) {                  // the park rows follow the stack rows of this one-wavefront workgroup (trc_render_pass.hip: choose_kernel)
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
@@ -480,40 +480,40 @@ __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_stri
 // instantiates it, so this is also the list of what each translation unit compiles: Sobol' for tracePath / traceMIS only,
 // persistent workgroups on trees read from memory only; no statistics twin of the strip / persistent kernels or of the texture ones.
 template <bool LDS, int INTEGRATOR>
-constexpr RenderKernels render_kernels() {
+inline RenderKernels render_kernels() {
     constexpr bool kSobol = INTEGRATOR != TRC_INTEGRATOR_VOLUME;
     RenderKernels t{};
-    t.one[kVariantPlain] = {&k_render<LDS, false, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR)};
-    t.one[kVariantStats] = {&k_render<LDS, true, INTEGRATOR, false>, render_waves(LDS, true, INTEGRATOR)};
-    t.one[kVariantTex] = {&k_render_tex<LDS, INTEGRATOR>, render_waves(LDS, false, INTEGRATOR)};
-    t.strip[kVariantPlain] = {&k_render_strip<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR)};
-    t.strip[kVariantTex] = {&k_render_strip_tex<LDS, INTEGRATOR>, strip_waves(INTEGRATOR)};
+    t.one[kVariantPlain] = render_kernel(&k_render<LDS, false, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR));
+    t.one[kVariantStats] = render_kernel(&k_render<LDS, true, INTEGRATOR, false>, render_waves(LDS, true, INTEGRATOR));
+    t.one[kVariantTex] = render_kernel(&k_render_tex<LDS, INTEGRATOR>, render_waves(LDS, false, INTEGRATOR));
+    t.strip[kVariantPlain] = render_kernel(&k_render_strip<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR));
+    t.strip[kVariantTex] = render_kernel(&k_render_strip_tex<LDS, INTEGRATOR>, strip_waves(INTEGRATOR));
     if constexpr (kSobol) {
-        t.one[kVariantSobol] = {&k_render<LDS, false, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR)};
-        t.strip[kVariantSobol] = {&k_render_strip<LDS, INTEGRATOR, true>, strip_waves(INTEGRATOR)};
+        t.one[kVariantSobol] = render_kernel(&k_render<LDS, false, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR));
+        t.strip[kVariantSobol] = render_kernel(&k_render_strip<LDS, INTEGRATOR, true>, strip_waves(INTEGRATOR));
     }
     if constexpr (!LDS) {
-        t.pwg[kVariantPlain] = {&k_render_pwg<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR)};
-        t.pwg[kVariantTex] = {&k_render_pwg_tex<INTEGRATOR>, pwg_simd_waves(INTEGRATOR)};
-        if constexpr (kSobol) t.pwg[kVariantSobol] = {&k_render_pwg<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR)};
+        t.pwg[kVariantPlain] = render_kernel(&k_render_pwg<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR));
+        t.pwg[kVariantTex] = render_kernel(&k_render_pwg_tex<INTEGRATOR>, pwg_simd_waves(INTEGRATOR));
+        if constexpr (kSobol) t.pwg[kVariantSobol] = render_kernel(&k_render_pwg<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR));
     }
     if constexpr (INTEGRATOR == TRC_INTEGRATOR_MIS) {        // TRC_FLAG_ENV_LIGHT: traceMIS only
-        t.one[kVariantEnv] = {nullptr, render_waves(LDS, false, INTEGRATOR), &k_render_env<LDS, INTEGRATOR, false>};
-        t.one[kVariantEnvTex] = {nullptr, render_waves(LDS, false, INTEGRATOR), &k_render_env<LDS, INTEGRATOR, true>};
-        t.strip[kVariantEnv] = {nullptr, strip_waves(INTEGRATOR), &k_render_strip_env<LDS, INTEGRATOR, false>};
-        t.strip[kVariantEnvTex] = {nullptr, strip_waves(INTEGRATOR), &k_render_strip_env<LDS, INTEGRATOR, true>};
+        t.one[kVariantEnv] = render_kernel(&k_render_env<LDS, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR));
+        t.one[kVariantEnvTex] = render_kernel(&k_render_env<LDS, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR));
+        t.strip[kVariantEnv] = render_kernel(&k_render_strip_env<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR));
+        t.strip[kVariantEnvTex] = render_kernel(&k_render_strip_env<LDS, INTEGRATOR, true>, strip_waves(INTEGRATOR));
         if constexpr (!LDS) {
-            t.pwg[kVariantEnv] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, false>};
-            t.pwg[kVariantEnvTex] = {nullptr, pwg_simd_waves(INTEGRATOR), &k_render_pwg_env<INTEGRATOR, true>};
+            t.pwg[kVariantEnv] = render_kernel(&k_render_pwg_env<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR));
+            t.pwg[kVariantEnvTex] = render_kernel(&k_render_pwg_env<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR));
         }
         // TRC_FLAG_MESH_LIGHTS: traceMIS only
-        t.one[kVariantMesh] = {nullptr, render_waves(LDS, false, INTEGRATOR), nullptr, &k_render_mesh<LDS, INTEGRATOR, false>};
-        t.one[kVariantMeshTex] = {nullptr, render_waves(LDS, false, INTEGRATOR), nullptr, &k_render_mesh<LDS, INTEGRATOR, true>};
-        t.strip[kVariantMesh] = {nullptr, strip_waves(INTEGRATOR), nullptr, &k_render_strip_mesh<LDS, INTEGRATOR, false>};
-        t.strip[kVariantMeshTex] = {nullptr, strip_waves(INTEGRATOR), nullptr, &k_render_strip_mesh<LDS, INTEGRATOR, true>};
+        t.one[kVariantMesh] = render_kernel(&k_render_mesh<LDS, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR));
+        t.one[kVariantMeshTex] = render_kernel(&k_render_mesh<LDS, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR));
+        t.strip[kVariantMesh] = render_kernel(&k_render_strip_mesh<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR));
+        t.strip[kVariantMeshTex] = render_kernel(&k_render_strip_mesh<LDS, INTEGRATOR, true>, strip_waves(INTEGRATOR));
         if constexpr (!LDS) {
-            t.pwg[kVariantMesh] = {nullptr, pwg_simd_waves(INTEGRATOR), nullptr, &k_render_pwg_mesh<INTEGRATOR, false>};
-            t.pwg[kVariantMeshTex] = {nullptr, pwg_simd_waves(INTEGRATOR), nullptr, &k_render_pwg_mesh<INTEGRATOR, true>};
+            t.pwg[kVariantMesh] = render_kernel(&k_render_pwg_mesh<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR));
+            t.pwg[kVariantMeshTex] = render_kernel(&k_render_pwg_mesh<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR));
         }
     }
     return t;

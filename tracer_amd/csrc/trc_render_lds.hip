@@ -2,7 +2,7 @@
 // kernel), instantiated with the guard-free reciprocal / square root of dev_vec.hpp (TRC_FAST_UNARY, bit-identical:
 // tests/test_gpu_unary.py).  traceMIS / traceVolume on such scenes: trc_render_lds_mis.hip -- two translation units since round 5
 // because this one is compiled with -mllvm -amdgpu-use-amdgpu-trackers (Makefile: EXTRA_trc_render_lds; config 2 16.64 -> 16.50 ms,
-// traceMIS on the same scene would lose 1.6 %: profiles/r05/ab_flags*.txt).  Definitions: trc_render_kernels.hpp; launched from trc_abi.hip.
+// traceMIS on the same scene would lose 1.6 %: profiles/r05/ab_flags*.txt).  Definitions: trc_render_kernels.hpp; launched from trc_render_pass.hip.
 #ifndef TRC_TRIANGLE_MATERIALS
 #define TRC_TRIANGLE_MATERIALS 0      // triangles keep material 19; the twins reading per-triangle materials: trc_render_*_tm.hip
 #endif
@@ -20,5 +20,5 @@ __global__ void __launch_bounds__(kBlock, TRC_PATH_WAVES_DENSE) k_render_dense(c
 
 // the kernel table (trc_render_config.hpp); k_render_dense has no texture twin (a textured scene takes k_render_tex instead)
 const RenderKernels render_lds_path = render_kernels<true, TRC_INTEGRATOR_PATH>();
-const RenderKernel render_dense = {&k_render_dense, TRC_PATH_WAVES_DENSE};
+const RenderKernel render_dense = render_kernel(&k_render_dense, TRC_PATH_WAVES_DENSE);
 TRC_RENDER_NS_END

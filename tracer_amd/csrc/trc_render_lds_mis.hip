@@ -1,5 +1,5 @@
 // trc_render_lds_mis.hip -- traceMIS and traceVolume on scenes whose whole tree is staged in LDS (default compiler options; tracePath's
-// kernels of the same scenes are in trc_render_lds.hip).  Definitions: trc_render_kernels.hpp; launched from trc_abi.hip.
+// kernels of the same scenes are in trc_render_lds.hip).  Definitions: trc_render_kernels.hpp; launched from trc_render_pass.hip.
 #ifndef TRC_TRIANGLE_MATERIALS
 #define TRC_TRIANGLE_MATERIALS 0      // triangles keep material 19; the twins reading per-triangle materials: trc_render_*_tm.hip
 #endif

@@ -91,7 +91,7 @@ inline trc_status layout_scene(trc_ctx* ctx, const trc_scene* s, uint32_t n_inte
 }
 
 // Upload-time LDS plan (k_trace, the SPPM passes, the instrumented kernels; production render launches refine it per
-// kernel: trc_abi.hip::plan_launch_lds).  LDS per workgroup = staged prefix + traversal stack; keep 16 one-wavefront
+// kernel: trc_render_pass.hip::plan_launch_lds).  LDS per workgroup = staged prefix + traversal stack; keep 16 one-wavefront
 // workgroups per CU resident (measured on MI355X: occupancy beats top-of-tree staging -- 8/16/24/40/64 KB staged on the
 // 1 M-triangle scene gave 1826/1553/1155/1165/666 Mrays/s), so nodes are staged only into what the stack leaves of 9.5 KB.
 // `prefix_ok`: the first fat nodes are the top of the tree (BFS order); otherwise all or nothing.
