@@ -152,24 +152,22 @@ struct PathCtx {
 };
 // ... of the TEX instantiations (image textures): a struct of its own, so that the others' context keeps its layout
 struct PathCtxTex : PathCtx { TexTable tex; };
-// ... and of the ENV instantiations (TRC_FLAG_ENV_LIGHT): the map's sampling tables (dev_envlight.hpp)
-struct PathCtxEnv : PathCtx { EnvLight envl; };
-struct PathCtxEnvTex : PathCtxTex { EnvLight envl; };
-// ... and of the MESH instantiations (TRC_FLAG_MESH_LIGHTS): the emissive triangles' sampling tables (dev_meshlight.hpp)
-struct PathCtxMesh : PathCtx { MeshLight meshl; };
-struct PathCtxMeshTex : PathCtxTex { MeshLight meshl; };
-template <bool TEX, bool ENV = false, bool MESH = false>
-using PathCtxOf = typename std::conditional<MESH, typename std::conditional<TEX, PathCtxMeshTex, PathCtxMesh>::type,
-                  typename std::conditional<ENV, typename std::conditional<TEX, PathCtxEnvTex, PathCtxEnv>::type,
-                                            typename std::conditional<TEX, PathCtxTex, PathCtx>::type>::type>::type;
+// The light of a traceMIS launch besides the two squares: none, the environment map (TRC_FLAG_ENV_LIGHT, dev_envlight.hpp) or the mesh's
+// emissive triangles (TRC_FLAG_MESH_LIGHTS, dev_meshlight.hpp) -- one choice, never two -- and the sampling tables that go with it
+enum class Light { None, Env, Mesh };
+template <Light LIGHT>
+using LightTables = typename std::conditional<LIGHT == Light::Env, EnvLight, typename std::conditional<LIGHT == Light::Mesh, MeshLight, void>::type>::type;
+TRC_DEV float light_p(const EnvLight& L) { return L.p_env; }        // the probability that the light pick takes this light
+TRC_DEV float light_p(const MeshLight& L) { return L.p_mesh; }
+// ... and the context of a (TEX, LIGHT) instantiation: the light's tables come last, behind the image table of TEX
+template <bool TEX> using PathCtxBase = typename std::conditional<TEX, PathCtxTex, PathCtx>::type;
+template <bool TEX, Light LIGHT = Light::None> struct PathCtxOf : PathCtxBase<TEX> { LightTables<LIGHT> light; };
+template <bool TEX> struct PathCtxOf<TEX, Light::None> : PathCtxBase<TEX> {};
 template <bool TEX> TRC_DEV const TexTable* ctx_tex(const PathCtx& cx) {
     if constexpr (TEX) return &static_cast<const PathCtxTex&>(cx).tex; else return nullptr;
 }
-template <bool TEX, bool ENV> TRC_DEV const EnvLight* ctx_env(const PathCtx& cx) {
-    if constexpr (ENV) return &static_cast<const PathCtxOf<TEX, true>&>(cx).envl; else return nullptr;
-}
-template <bool TEX, bool MESH> TRC_DEV const MeshLight* ctx_mesh(const PathCtx& cx) {
-    if constexpr (MESH) return &static_cast<const PathCtxOf<TEX, false, true>&>(cx).meshl; else return nullptr;
+template <bool TEX, Light LIGHT> TRC_DEV const LightTables<LIGHT>* ctx_light(const PathCtx& cx) {
+    if constexpr (LIGHT != Light::None) return &static_cast<const PathCtxOf<TEX, LIGHT>&>(cx).light; else return nullptr;
 }
 
 // ---------------------------------------------------------------- path state machine
@@ -194,8 +192,8 @@ struct PathState {
     int trk_step;
     uint64_t sobol_index;    // TRC_FLAG_SOBOL: mSobolIndex of this sample and the next dimension (SobolSampler.hh:37-41)
     uint32_t sobol_dim;
-    bool env_mis;            // TRC_FLAG_ENV_LIGHT: the map's light sample shares the escape of the ray in flight (a cosine lobe, env_nee)
-                             // TRC_FLAG_MESH_LIGHTS (never both): ... the mesh's light sample shares the emitter hit of the ray in flight (mesh_nee)
+    bool env_mis;            // Light::Env: the map's light sample shares the escape of the ray in flight (a cosine lobe, light_nee)
+                             // Light::Mesh: ... the mesh's light sample shares the emitter hit of the ray in flight
 };
 
 // ---------------------------------------------------------------- pbrt::SobolSampler (SobolSampler.hh:26-167)
@@ -432,24 +430,30 @@ TRC_DEV float grid_sample(const PathCtx& cx, const HitRec& rec, MediumHit& mi, P
 // Same for traceMIS (Render.metal:298-406) and, with VOLUME, traceVolume (Render.metal:78-275 = traceMIS + the
 // medium block :114-158).  Lights are literally squareList[5] and [6] (:320-324, B-12).
 // The shadow ray (any-hit Scene::hit) is traced here, inside the step.
-// The light sample of a traceMIS vertex with the environment map as a light (TRC_FLAG_ENV_LIGHT; mis_step<.., ENV>): the light pick,
-// then the map's or a square's sample, its shadow ray and its MIS-weighted contribution; leaves the shading frame, -wo and the
-// hit's colour for the BSDF sample.  A square's sample is the reference's (:320-356) with its contribution divided by 1 - p_env.
-// The map's shadow ray is an any-hit walk to infinity from where a BSDF ray of the same direction would start (_origin: only
-// directions above the surface are taken).
-template <bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
-TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
-                     const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
+// The light sample of a traceMIS vertex with a light besides the squares (mis_step<.., LIGHT>; L = its tables, p = light_p(L)): the light
+// pick, then that light's or a square's sample, its shadow ray and its MIS-weighted contribution; leaves the shading frame, -wo and the
+// hit's colour for the BSDF sample.  The pick's one draw takes the light below p, else square 5 below p + (1 - p) / 2 and square 6 above;
+// a square's sample is the reference's (:320-356) with its contribution divided by 1 - p.
+// Light::Env: the map's sample draws six more numbers; its shadow ray is an any-hit walk to infinity from where a BSDF ray of the same
+// direction would start (_origin: only directions above the surface are taken).
+// Light::Mesh: the mesh's sample (dev_meshlight.hpp) draws four more numbers; its shadow ray is the any-hit walk to the sample's distance,
+// as a square's.  Radiance keeps the reference's Le * cos convention.
+template <Light LIGHT, bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
+TRC_DEV void light_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
+                       const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
     const HitRec& rec = ps.rec;
-    const EnvLight& L = *ctx_env<TEX, true>(cx);
+    const LightTables<LIGHT>& L = *ctx_light<TEX, LIGHT>(cx);
     const float pick = pcg_float(rng);
-    // 0: no light sample; 1: a square; 2: the map -- only where the BSDF ray's escape would count (mis_step's depth cutoff), and only
-    // where the BSDF sample is a cosine lobe: a Lambert vertex, or the Lambert lobe a Plastic vertex picks with uu.x < 1/2 (the same uu
-    // picks the same lobe in material_F and material_S_F; that lobe's F and pdf are the value and density it samples with).  The other
-    // lobes (Beckmann, Metal, Glass) report per-lobe pdfs with the reference's lobe-pick conventions, not the density the map's
-    // strategy would have to be weighed against: there a pick of the map takes no sample and the escape keeps weight 1.
+    // 0: no light sample; 1: a square; 2: the light -- drawn only when it is picked, and only where the BSDF sample is a cosine lobe: a
+    // Lambert vertex, or the Lambert lobe a Plastic vertex picks with uu.x < 1/2 (the same uu picks the same lobe in material_F and
+    // material_S_F; that lobe's F and pdf are the value and density it samples with).  The other lobes (Beckmann, Metal, Glass) report
+    // per-lobe pdfs with the reference's lobe-pick conventions, not the density the light's strategy would have to be weighed against:
+    // there a pick of the light takes no sample and the BSDF ray that reaches it keeps weight 1.  The map besides only where the BSDF
+    // ray's escape would count (mis_step's depth cutoff).
     ps.env_mis = mtype == kMatLambert || (mtype == kMatPlastic && uu.x < 0.5f);
-    const int kind = pick < L.p_env ? (ps.depth_left > 1 && ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
+    int kind;
+    if constexpr (LIGHT == Light::Env) kind = pick < light_p(L) ? (ps.depth_left > 1 && ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
+    else kind = pick < light_p(L) ? (ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
     coordinate_system(rec.sn, nx, ny);
     Ray _ray = make_ray(_origin, f3(0.0f, 0.0f, 1.0f));
     float _dis = FLT_MAX;
@@ -457,7 +461,7 @@ TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& c
     float liPDF = 0.0f;
     if (kind == 1) {
         LightSample lsr;
-        square_sample(cx.S, pick < L.p_env + (1.0f - L.p_env) * 0.5f ? 5 : 6, uu, _origin, lsr);
+        square_sample(cx.S, pick < light_p(L) + (1.0f - light_p(L)) * 0.5f ? 5 : 6, uu, _origin, lsr);
         const F3 _dir = lsr.p - _origin;
         const F3 _nor = normalize(_dir);
         _dis = length(_dir);
@@ -466,17 +470,38 @@ TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& c
         light_term = mat_albedo(cx.sh, lsr.material) * cosOnLight;
         liPDF = (_dis * _dis) * lsr.areaPDF / cosOnLight;
     } else if (kind == 2) {
-        const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng), r2 = pcg_next(rng), r3 = pcg_next(rng);
-        const float f0 = pcg_float(rng), f1 = pcg_float(rng);
-        float pdf;
-        const F3 dir = env_light_sample(L, r0, r1, r2, r3, f0, f1, pdf);
         // only where the BSDF strategy has support -- the cosine lobe samples wi.z > 0 and reports pdf 0 unless wo.z > 0 -- does the
-        // map's sample carry weight: below the surface Lambert::F = wi.z / pi is negative, and nothing on the BSDF side covers it
-        const float wi_z = dot(rec.sn, dir), wo_z = -dot(rec.sn, ps.ray.d);
-        liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? L.p_env * pdf : 0.0f;
-        if (liPDF > 0.0f) {
-            _ray = make_ray(_origin, dir);               // where the BSDF ray of this direction starts (wi.z > 0)
-            light_term = env_radiance(cx.env, cx.ambient, _ray.d);
+        // light's sample carry weight: below the surface Lambert::F = wi.z / pi is negative, and nothing on the BSDF side covers it
+        if constexpr (LIGHT == Light::Env) {
+            const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng), r2 = pcg_next(rng), r3 = pcg_next(rng);
+            const float f0 = pcg_float(rng), f1 = pcg_float(rng);
+            float pdf;
+            const F3 dir = env_light_sample(L, r0, r1, r2, r3, f0, f1, pdf);
+            const float wi_z = dot(rec.sn, dir), wo_z = -dot(rec.sn, ps.ray.d);
+            liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? light_p(L) * pdf : 0.0f;
+            if (liPDF > 0.0f) {
+                _ray = make_ray(_origin, dir);               // where the BSDF ray of this direction starts (wi.z > 0)
+                light_term = env_radiance(cx.env, cx.ambient, _ray.d);
+            }
+        } else {
+            const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng);
+            const float f0 = pcg_float(rng), f1 = pcg_float(rng);
+            MeshSample ms;
+            mesh_light_sample(L, cx.S.blob + cx.S.off_tripos, r0, r1, f0, f1, _origin, ms);
+            const F3 _dir = offset_ray(ms.p, ms.n) - _origin;
+            const F3 _nor = normalize(_dir);
+            const float dist = length(_dir);
+            const float cosL = fabsf(dot(ms.n, -_nor));
+            const float wi_z = dot(rec.sn, _nor), wo_z = -dot(rec.sn, ps.ray.d);
+            liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? light_p(L) * ms.pdfA * (dist * dist) / cosL : 0.0f;
+            if (!(liPDF > 0.0f && liPDF <= FLT_MAX)) liPDF = 0.0f;          // (a grazing or coincident sample: cosL or dist 0)
+            if (liPDF > 0.0f) {
+                _dis = dist;
+                _ray = make_ray(_origin, _nor);
+                // the material of triangle ms.tri, as the hit test reads it (dev_intersect.hpp: TRC_TRIANGLE_MATERIALS)
+                const uint32_t material = TRC_TRIANGLE_MATERIALS ? ld1_global(cx.S.blob + cx.S.off_triattr + (size_t)ms.tri * kTriAttrDwords + 15u) : 19u;
+                light_term = mat_albedo(cx.sh, material) * cosL;
+            }
         }
     }
     bool blocked = true;
@@ -498,97 +523,22 @@ TRC_DEV void env_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& c
         float bxPDF = 0;
         bump(n_shaded);
         F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF) * light_term;
-        if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - L.p_env));
+        if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - light_p(L)));
         else ps.color = ps.color + ps.ratio * (weight * env_mis_weight(liPDF, bxPDF)) / liPDF;
     }
 }
 
-// The light sample of a traceMIS vertex with the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; mis_step<.., MESH>), env_nee's
-// twin: the light pick's one draw takes the mesh below p_mesh, else square 5 below p_mesh + (1 - p_mesh) / 2 and square 6 above; a
-// square's sample is the reference's (:320-356) with its contribution divided by 1 - p_mesh.  The mesh's sample (dev_meshlight.hpp) draws
-// four more numbers, only when it is picked and only where the BSDF sample is a cosine lobe (env_nee's rule, for its reason); its shadow
-// ray is the any-hit walk to the sample's distance, as a square's.  Radiance keeps the reference's Le * cos convention.
-template <bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
-TRC_DEV void mesh_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
-                      const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
-    const HitRec& rec = ps.rec;
-    const MeshLight& L = *ctx_mesh<TEX, true>(cx);
-    const float pick = pcg_float(rng);
-    ps.env_mis = mtype == kMatLambert || (mtype == kMatPlastic && uu.x < 0.5f);
-    // 0: no light sample; 1: a square; 2: the mesh
-    const int kind = pick < L.p_mesh ? (ps.env_mis ? 2 : 0) : (L.squares ? 1 : 0);
-    coordinate_system(rec.sn, nx, ny);
-    Ray _ray = make_ray(_origin, f3(0.0f, 0.0f, 1.0f));
-    float _dis = FLT_MAX;
-    F3 light_term = f3(0.0f);
-    float liPDF = 0.0f;
-    if (kind == 1) {
-        LightSample lsr;
-        square_sample(cx.S, pick < L.p_mesh + (1.0f - L.p_mesh) * 0.5f ? 5 : 6, uu, _origin, lsr);
-        const F3 _dir = lsr.p - _origin;
-        const F3 _nor = normalize(_dir);
-        _dis = length(_dir);
-        _ray = make_ray(_origin, _nor);
-        const float cosOnLight = fabsf(dot(lsr.n, -_nor));
-        light_term = mat_albedo(cx.sh, lsr.material) * cosOnLight;
-        liPDF = (_dis * _dis) * lsr.areaPDF / cosOnLight;
-    } else if (kind == 2) {
-        const uint32_t r0 = pcg_next(rng), r1 = pcg_next(rng);
-        const float f0 = pcg_float(rng), f1 = pcg_float(rng);
-        MeshSample ms;
-        mesh_light_sample(L, cx.S.blob + cx.S.off_tripos, r0, r1, f0, f1, _origin, ms);
-        const F3 _dir = offset_ray(ms.p, ms.n) - _origin;
-        const F3 _nor = normalize(_dir);
-        const float dist = length(_dir);
-        const float cosL = fabsf(dot(ms.n, -_nor));
-        // only where the BSDF strategy has support (the cosine lobe samples wi.z > 0 and reports pdf 0 unless wo.z > 0), as env_nee
-        const float wi_z = dot(rec.sn, _nor), wo_z = -dot(rec.sn, ps.ray.d);
-        liPDF = (wi_z > 0.0f && wo_z > 0.0f) ? L.p_mesh * ms.pdfA * (dist * dist) / cosL : 0.0f;
-        if (!(liPDF > 0.0f && liPDF <= FLT_MAX)) liPDF = 0.0f;          // (a grazing or coincident sample: cosL or dist 0)
-        if (liPDF > 0.0f) {
-            _dis = dist;
-            _ray = make_ray(_origin, _nor);
-            // the material of triangle ms.tri, as the hit test reads it (dev_intersect.hpp: TRC_TRIANGLE_MATERIALS)
-            const uint32_t material = TRC_TRIANGLE_MATERIALS ? ld1_global(cx.S.blob + cx.S.off_triattr + (size_t)ms.tri * kTriAttrDwords + 15u) : 19u;
-            light_term = mat_albedo(cx.sh, material) * cosL;
-        }
-    }
-    bool blocked = true;
-    if (kind == 1 || (kind == 2 && liPDF > 0.0f)) {              // (a square's sample walks whatever its pdf, as the reference's does)
-        bump(n_rays);
-        if (STATS) {
-            HitRec shr;
-            hit_init(shr);
-            blocked = scene_hit<ALL_LDS, STATS, true, false, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, shr, _dis, cx.stack, cx.lvstack, cnt);
-        } else {
-            blocked = scene_occluded<ALL_LDS, false, HYB>(cx.S, cx.root_min, cx.root_max, _ray, _dis, cx.stack, cx.S.stack_cap);
-        }
-    }
-    minus_d = -ps.ray.d;
-    base_color = hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx));
-    if (!blocked) {
-        const F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
-        const F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
-        float bxPDF = 0;
-        bump(n_shaded);
-        F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF) * light_term;
-        if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - L.p_mesh));
-        else ps.color = ps.color + ps.ratio * (weight * env_mis_weight(liPDF, bxPDF)) / liPDF;
-    }
-}
-
-// ENV (TRC_FLAG_ENV_LIGHT, traceMIS only): the environment map is a light too (dev_envlight.hpp).  The light pick's one draw takes
-// the map below p_env, else square 5 below p_env + (1 - p_env) / 2 and square 6 above; a square's contribution is divided by
-// 1 - p_env (the reference's expectation, its missing 1/2 included).  The map's sample draws six more numbers, only when it is
-// picked, and only at a vertex whose BSDF ray would be counted if it escaped; an escaping BSDF ray is weighted against it.
+// LIGHT = Light::Env (TRC_FLAG_ENV_LIGHT, traceMIS only): the environment map is a light too (dev_envlight.hpp; light_nee).  A square's
+// contribution is divided by 1 - p_env (the reference's expectation, its missing 1/2 included); the map is sampled only at a vertex whose
+// BSDF ray would be counted if it escaped, and an escaping BSDF ray is weighted against it.
 // With p_env = 0 (a black map) every operation and draw is the flag-off kernel's.
-// MESH (TRC_FLAG_MESH_LIGHTS, traceMIS only, never with ENV): the mesh's emissive triangles are lights too (mesh_nee).  A BSDF-sampled hit
+// LIGHT = Light::Mesh (TRC_FLAG_MESH_LIGHTS, traceMIS only): the mesh's emissive triangles are lights too (light_nee).  A BSDF-sampled hit
 // on a TRIANGLE emitter is then ps.color + ps.ratio * (albedo * cosOnLight) * w, cosOnLight = |dot(geometric normal, -d)| and
 // w = env_mis_weight(scat_bxPDF, p_mesh * pdfA[triangle] * dist^2 / cosOnLight) where the previous vertex took its BSDF sample from a
 // cosine lobe, else 1: the estimator of the integrand the mesh's light sample estimates -- without the reference's second
 // scat_attenuation / scat_bxPDF factor, and without rec.PDF, which only a square writes (tracer_abi.h).  A square emitter hit keeps the
 // reference's formula.  Without a light triangle (p_mesh = 0, no tables) every operation and draw is the flag-off kernel's.
-template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, bool ENV = false, bool MESH = false, class COUNT = uint32_t>
+template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, Light LIGHT = Light::None, class COUNT = uint32_t>
 TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_rays,
                       COUNT& n_shaded, F3& result) {
     HitRec& rec = ps.rec;
@@ -597,8 +547,8 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     if (!ps.primary) {
         if ((!VOLUME || ps.from_bsdf) && hitted && mat_type(cx.sh, rec.material) == kMatDiffuse) {   // MIS-weighted emitter hit, :390-404
             F3 Li = mat_albedo(cx.sh, rec.material);
-            if constexpr (MESH) {
-                const MeshLight& L = *ctx_mesh<TEX, MESH>(cx);
+            if constexpr (LIGHT == Light::Mesh) {
+                const MeshLight& L = *ctx_light<TEX, LIGHT>(cx);
                 if (L.n_lights != 0u && (rec.tag >> kTagIndexBits) == kTagTriangle) {      // a triangle emitter, and a mesh strategy exists
                     const uint32_t t = rec.tag & kTagIndexMask;
                     F3 v0, v1, v2;
@@ -619,16 +569,17 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
             F3 d = rec.p - ps.ray.o;
             float dist2 = dot(d, d);
             float lightPDF = rec.PDF * dist2 / cosOnLight;
-            if (!ENV || ctx_env<TEX, ENV>(cx)->squares)          // (without square lights no light strategy shares the hit: weight 1)
-                weight = weight * power_heuristic(1, ps.scat_bxPDF, 1, lightPDF);
+            bool shared = true;                                  // (without square lights no light strategy shares the hit: weight 1)
+            if constexpr (LIGHT == Light::Env) shared = ctx_light<TEX, LIGHT>(cx)->squares;
+            if (shared) weight = weight * power_heuristic(1, ps.scat_bxPDF, 1, lightPDF);
             result = ps.color + ps.ratio * weight / ps.scat_bxPDF;
             return true;
         }
         if (--ps.depth_left <= 0) { result = ps.color; return true; }   // } while ((--depth) > 0), :406
     }
-    if constexpr (ENV) {
+    if constexpr (LIGHT == Light::Env) {
         if (!hitted) {                                               // a BSDF-sampled ray that escapes, against the map's own strategy
-            const EnvLight& L = *ctx_env<TEX, ENV>(cx);
+            const EnvLight& L = *ctx_light<TEX, LIGHT>(cx);
             F3 le = env_radiance(cx.env, cx.ambient, ps.ray.d);
             if (!ps.primary && ps.env_mis) {
                 const float pe = L.p_env * env_light_pdf(L, ps.ray.d);
@@ -689,10 +640,8 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     const F3 hit_origin = rec.p;
     F3 _origin = offset_ray(rec.p, rec.sn);
     F3 nx, ny, minus_d, base_color;
-    if constexpr (ENV) {
-        env_nee<ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
-    } else if constexpr (MESH) {
-        mesh_nee<ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
+    if constexpr (LIGHT != Light::None) {
+        light_nee<LIGHT, ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
     } else {
     if (pcg_float(rng) < 0.5f) square_sample(cx.S, 5, uu, _origin, lsr);
     else square_sample(cx.S, 6, uu, _origin, lsr);

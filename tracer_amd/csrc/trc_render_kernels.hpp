@@ -33,27 +33,47 @@ template <bool TEX, class CX>
 __device__ __forceinline__ void set_ctx_tex(CX& cx, const KRender& kp) {       // TEX: the image table of the launch (PathCtxTex)
     if constexpr (TEX) { cx.tex.texels = kp.tex_texels; cx.tex.desc = kp.tex_desc; cx.tex.n = kp.n_tex; }
 }
-// ENV (TRC_FLAG_ENV_LIGHT, traceMIS): the environment map is a light too (mis_step<.., ENV>); `envl` = its sampling tables
-template <bool ENV, class CX>
-__device__ __forceinline__ void set_ctx_env(CX& cx, const EnvLight* envl) {
-    if constexpr (ENV) cx.envl = *envl;
+// LIGHT (dev_integrator.hpp: Light; traceMIS): the environment map (TRC_FLAG_ENV_LIGHT) or the mesh's emissive triangles
+// (TRC_FLAG_MESH_LIGHTS) are lights too (mis_step<.., LIGHT>); `tables` = that light's sampling tables, null without one
+template <Light LIGHT, class CX>
+__device__ __forceinline__ void set_ctx_light(CX& cx, const LightTables<LIGHT>* tables) {
+    if constexpr (LIGHT != Light::None) cx.light = *tables;
 }
-// MESH (TRC_FLAG_MESH_LIGHTS, traceMIS): the mesh's emissive triangles are lights too (mis_step<.., MESH>); `meshl` = their sampling tables
-template <bool MESH, class CX>
-__device__ __forceinline__ void set_ctx_mesh(CX& cx, const MeshLight* meshl) {
-    if constexpr (MESH) cx.meshl = *meshl;
+// What a path reads of the launch, the same for every pixel of a kernel.  The call sites add what differs between them: cx.S.ovf, and
+// (SOBOL) the pixel in cx.sobol_xy.
+template <bool SOBOL, bool TEX, Light LIGHT>
+__device__ __forceinline__ void fill_path_ctx(PathCtxOf<TEX, LIGHT>& cx, const KRender& kp, const DScene& sc, const uint32_t* small_base,
+                                              uint32_t* stack, uint32_t* lvstack, const LightTables<LIGHT>* tables) {
+    cx.S = make_scene_ref(sc, small_base);
+    cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
+    cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
+    cx.sh.mats = small_base + sc.off_materials;
+    set_ctx_tex<TEX>(cx, kp);
+    set_ctx_light<LIGHT>(cx, tables);
+    cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
+    cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
+    cx.stack = stack;
+    cx.lvstack = lvstack;
+    cx.max_depth = kp.max_depth;
+    cx.density = kp.density;
+    cx.dinfo = kp.dinfo;
+    cx.occupancy = kp.occupancy;
+    if (SOBOL) {                                       // SobolSampler(rng, frame, thread_pos, vsize), SobolSampler.hh:50-61
+        cx.sobol32 = kp.sobol32; cx.sobol_vdc = kp.sobol_vdc;
+        cx.sobol_m = kp.sobol_m; cx.sobol_res = 1u << kp.sobol_m;
+    }
 }
 // MEMO = 8 | 10 (round 8, tracePath production kernels; trc_render_config.hpp: primary replay): the hit of the pixel's camera ray, kept
 // after the block's first walk in MEMO words of the lane's column `memo` (LDS or global rows).  A later sample whose camera ray has the
 // same origin bits -- the direction follows from (origin, u, v, camera) -- takes its record from there: no walk, and (kp.replay lanes) it is
 // shaded before the wavefront's next walk, so that a lane needs one trip round the loop per BOUNCE ray.  The ray is still counted
 // (trc_stats.rays is the algorithm's Scene::hit count); what was answered from the memo is summed into kStatReplays.
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MESH = false, class COUNT = uint32_t>
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, bool HYB, int PARK = 0, bool TEX = false, Light LIGHT = Light::None, int MEMO = 0, class COUNT = uint32_t>
 __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                              uint32_t* ovf, uint32_t* park, const uint32_t slot, const uint32_t lane,
-                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt, const EnvLight* envl = nullptr,
-                                             uint32_t* memo = nullptr, const MeshLight* meshl = nullptr) {
-    static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && !ENV && !MESH), "primary replay: tracePath production kernels");
+                                             COUNT& n_rays, COUNT& n_shaded, uint32_t& n_paths, TravCounters& cnt,
+                                             const LightTables<LIGHT>* tables = nullptr, uint32_t* memo = nullptr) {
+    static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && LIGHT == Light::None), "primary replay: tracePath production kernels");
     static_assert(MEMO == 0 || MEMO == 10 || !TEX, "an image texture reads rec.uv: 10 memo rows");
     uint32_t replays = 0;                        // camera rays of this lane answered from the memo
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
@@ -76,28 +96,10 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
     const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
 
     if (active) {
-        PathCtxOf<TEX, ENV, MESH> cx;
-        cx.S = make_scene_ref(sc, small_base);
+        PathCtxOf<TEX, LIGHT> cx;
+        fill_path_ctx<SOBOL, TEX, LIGHT>(cx, kp, sc, small_base, stack, lvstack, tables);
         cx.S.ovf = ovf;
-        cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
-        cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
-        cx.sh.mats = small_base + sc.off_materials;
-        set_ctx_tex<TEX>(cx, kp);
-        set_ctx_env<ENV>(cx, envl);
-        set_ctx_mesh<MESH>(cx, meshl);
-        cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
-        cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
-        cx.stack = stack;
-        cx.lvstack = lvstack;
-        cx.max_depth = kp.max_depth;
-        cx.density = kp.density;
-        cx.dinfo = kp.dinfo;
-        cx.occupancy = kp.occupancy;
-        if (SOBOL) {                                   // SobolSampler(rng, frame, thread_pos, vsize), SobolSampler.hh:50-61
-            cx.sobol32 = kp.sobol32; cx.sobol_vdc = kp.sobol_vdc;
-            cx.sobol_m = kp.sobol_m; cx.sobol_res = 1u << kp.sobol_m;
-            cx.sobol_xy[0] = px; cx.sobol_xy[1] = py % kp.view_height;
-        }
+        if (SOBOL) { cx.sobol_xy[0] = px; cx.sobol_xy[1] = py % kp.view_height; }
 
         // the values that are touched only where a sample begins or ends: registers, or (PARK) rows of the lane's LDS column
         F3 cached_r = f3(0);
@@ -268,7 +270,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
                 F3 color;
                 const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                           ? path_step<STATS, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                          : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, ENV, MESH>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                          : mis_step<LDS, STATS, kVolume, SOBOL, HYB, TEX, LIGHT>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
                 if constexpr (MEMO != 0) {
                     if (ends) { memo[kMemoPx * kBlock] = __float_as_uint(color.x); memo[kMemoPy * kBlock] = __float_as_uint(color.y); memo[kMemoPz * kBlock] = __float_as_uint(color.z); }
                 }
@@ -288,7 +290,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
         if constexpr (PARK >= 10) pix = (size_t)park[kParkPy * kBlock] * W + park[kParkPx * kBlock];
         else if constexpr (PARK != 0) {
             // 8 rows: the pixel's coordinates are not carried at all -- the launch entry is read once more (volatile: a second load, not
-            // a value kept alive through the loop) and decoded as at the top
+            // a value kept alive through the loop) and decoded as at the top.  (Written out twice: one decode function for both places,
+            // tried in round 12 in four forms, changed the register allocation of every k_render / k_render_pwg kernel.)
             const uint32_t entry2 = kp.order ? *reinterpret_cast<const volatile uint32_t*>(kp.order + slot) : slot;
             const uint32_t code2 = entry2 >> kLaunchCodeShift;
             const uint32_t tile2 = *reinterpret_cast<const volatile uint32_t*>(kp.tiles + (entry2 & kLaunchIndexMask));
@@ -315,8 +318,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
 
 // the body of k_render (one one-wavefront workgroup = one entry of the launch list)
 // MEMO, MEMO_GLOBAL: the primary-replay rows (render_block) -- behind the stack and park rows of this workgroup's LDS, or rows of its own in kp.memo
-template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, bool ENV = false, int MEMO = 0, bool MEMO_GLOBAL = false, bool MESH = false>
-__device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLight* envl = nullptr, const MeshLight* meshl = nullptr) {
+template <bool LDS, bool STATS, int INTEGRATOR, bool SOBOL, int PARK = 0, bool TEX = false, Light LIGHT = Light::None, int MEMO = 0, bool MEMO_GLOBAL = false>
+__device__ __forceinline__ void render_workgroup(const KRender& kp, const LightTables<LIGHT>* tables = nullptr) {
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
     const uint32_t* small_base = stage_scene(sc);
@@ -336,10 +339,10 @@ __device__ __forceinline__ void render_workgroup(const KRender& kp, const EnvLig
         uint32_t* park = stack + sc.stack_lds * kBlock;
         park[kParkRays * kBlock] = 0u; park[kParkShaded * kBlock] = 0u;
         LdsCount c_rays{park + kParkRays * kBlock}, c_shaded{park + kParkShaded * kBlock};
-        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, ENV, MEMO, MESH>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, envl, memo, meshl);
+        render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, PARK, TEX, LIGHT, MEMO>(kp, sc, small_base, stack, lvstack, ovf, park, blockIdx.x, lane, c_rays, c_shaded, n_paths, cnt, tables, memo);
         n_rays = park[kParkRays * kBlock]; n_shaded = park[kParkShaded * kBlock];
     } else
-    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, MEMO, MESH>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, envl, memo, meshl);
+    render_block<LDS, STATS, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, LIGHT, MEMO>(kp, sc, small_base, stack, lvstack, ovf, nullptr, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, tables, memo);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
@@ -380,12 +383,12 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) 
 // ... with the environment map as a light (TRC_FLAG_ENV_LIGHT), without and with image textures
 template <bool LDS, int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_env(const KRenderEnv kpe) {
-    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, true>(kpe.kp, &kpe.el);
+    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, Light::Env>(kpe.kp, &kpe.el);
 }
 // ... with the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS), without and with image textures
 template <bool LDS, int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_mesh(const KRenderMesh kpm) {
-    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, false, 0, false, true>(kpm.kp, nullptr, &kpm.ml);
+    render_workgroup<LDS, false, INTEGRATOR, false, 0, TEX, Light::Mesh>(kpm.kp, &kpm.ml);
 }
 
 // kernelPathTracing on a tree that is READ FROM MEMORY (mesh scenes), production launches of >= 8 spp: persistent
@@ -401,36 +404,33 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) 
 // TEX (image textures): k_render_pwg_tex<INTEGRATOR>, the same body (trc_render_pwg_body.inc) with hit_color<true>
 template <int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg(const KRender kp) {
-    constexpr bool TEX = false, ENV = false;
-    const EnvLight* const envl = nullptr;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    constexpr bool TEX = false;
+    constexpr Light LIGHT = Light::None;
+    const void* const tables = nullptr;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_tex(const KRender kp) {
-    constexpr bool SOBOL = false, TEX = true, ENV = false;
-    const EnvLight* const envl = nullptr;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    constexpr bool SOBOL = false, TEX = true;
+    constexpr Light LIGHT = Light::None;
+    const void* const tables = nullptr;
 #include "trc_render_pwg_body.inc"
 }
 template <int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_env(const KRenderEnv kpe) {
-    constexpr bool SOBOL = false, ENV = true;
+    constexpr bool SOBOL = false;
+    constexpr Light LIGHT = Light::Env;
     const KRender& kp = kpe.kp;
-    const EnvLight* const envl = &kpe.el;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    const EnvLight* const tables = &kpe.el;
 #include "trc_render_pwg_body.inc"
 }
 
 template <int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INTEGRATOR)) k_render_pwg_mesh(const KRenderMesh kpm) {
-    constexpr bool SOBOL = false, ENV = false, MESH = true;
+    constexpr bool SOBOL = false;
+    constexpr Light LIGHT = Light::Mesh;
     const KRender& kp = kpm.kp;
-    const EnvLight* const envl = nullptr;
-    const MeshLight* const meshl = &kpm.ml;
+    const MeshLight* const tables = &kpm.ml;
 #include "trc_render_pwg_body.inc"
 }
 
@@ -443,36 +443,33 @@ __global__ void __launch_bounds__(64 * pwg_waves(INTEGRATOR), pwg_simd_waves(INT
 // TEX (image textures): k_render_strip_tex<LDS, INTEGRATOR>, the same body (trc_render_strip_body.inc) with hit_color<true>
 template <bool LDS, int INTEGRATOR, bool SOBOL>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip(const KRender kp) {
-    constexpr bool TEX = false, ENV = false;
-    const EnvLight* const envl = nullptr;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    constexpr bool TEX = false;
+    constexpr Light LIGHT = Light::None;
+    const void* const tables = nullptr;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_tex(const KRender kp) {
-    constexpr bool SOBOL = false, TEX = true, ENV = false;
-    const EnvLight* const envl = nullptr;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    constexpr bool SOBOL = false, TEX = true;
+    constexpr Light LIGHT = Light::None;
+    const void* const tables = nullptr;
 #include "trc_render_strip_body.inc"
 }
 template <bool LDS, int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_env(const KRenderEnv kpe) {
-    constexpr bool SOBOL = false, ENV = true;
+    constexpr bool SOBOL = false;
+    constexpr Light LIGHT = Light::Env;
     const KRender& kp = kpe.kp;
-    const EnvLight* const envl = &kpe.el;
-    constexpr bool MESH = false;
-    const MeshLight* const meshl = nullptr;
+    const EnvLight* const tables = &kpe.el;
 #include "trc_render_strip_body.inc"
 }
 
 template <bool LDS, int INTEGRATOR, bool TEX>
 __global__ void __launch_bounds__(kBlock, strip_waves(INTEGRATOR)) k_render_strip_mesh(const KRenderMesh kpm) {
-    constexpr bool SOBOL = false, ENV = false, MESH = true;
+    constexpr bool SOBOL = false;
+    constexpr Light LIGHT = Light::Mesh;
     const KRender& kp = kpm.kp;
-    const EnvLight* const envl = nullptr;
-    const MeshLight* const meshl = &kpm.ml;
+    const MeshLight* const tables = &kpm.ml;
 #include "trc_render_strip_body.inc"
 }
 
@@ -506,7 +503,8 @@ inline RenderKernels render_kernels() {
             t.pwg[kVariantEnv] = render_kernel(&k_render_pwg_env<INTEGRATOR, false>, pwg_simd_waves(INTEGRATOR));
             t.pwg[kVariantEnvTex] = render_kernel(&k_render_pwg_env<INTEGRATOR, true>, pwg_simd_waves(INTEGRATOR));
         }
-        // TRC_FLAG_MESH_LIGHTS: traceMIS only
+        // TRC_FLAG_MESH_LIGHTS: traceMIS only.  (The two blocks stay written out: the kernels are laid out in the code object in the order they
+        // are named here, and a helper that names each once interleaves the Env and Mesh kernels.)
         t.one[kVariantMesh] = render_kernel(&k_render_mesh<LDS, INTEGRATOR, false>, render_waves(LDS, false, INTEGRATOR));
         t.one[kVariantMeshTex] = render_kernel(&k_render_mesh<LDS, INTEGRATOR, true>, render_waves(LDS, false, INTEGRATOR));
         t.strip[kVariantMesh] = render_kernel(&k_render_strip_mesh<LDS, INTEGRATOR, false>, strip_waves(INTEGRATOR));

@@ -15,7 +15,7 @@ TRC_RENDER_NS_BEGIN
 // tracePath on an LDS-resident tree at one more wavefront per SIMD, for launch lists many times the wavefront slots (trc_render_config.hpp)
 __global__ void __launch_bounds__(kBlock, TRC_PATH_WAVES_DENSE) k_render_dense(const KRender kp) {
     // + per-pixel state parked in LDS rows, the camera ray's hit memoised (render_block)
-    render_workgroup<true, false, TRC_INTEGRATOR_PATH, false, TRC_PARK_DENSE, false, false, TRC_REPLAY_DENSE, TRC_REPLAY_DENSE_GLOBAL != 0>(kp);
+    render_workgroup<true, false, TRC_INTEGRATOR_PATH, false, TRC_PARK_DENSE, false, Light::None, TRC_REPLAY_DENSE, TRC_REPLAY_DENSE_GLOBAL != 0>(kp);
 }
 
 // the kernel table (trc_render_config.hpp); k_render_dense has no texture twin (a textured scene takes k_render_tex instead)

@@ -1,7 +1,7 @@
-// trc_render_pwg_body.inc -- the body of k_render_pwg / k_render_pwg_tex, included as the body of each kernel (trc_render_kernels.hpp) rather than
-// called from a helper: the kernel of the parent commit keeps its code and its name, and the image-texture twin shares the source.
-// Expects in scope: kp, INTEGRATOR, SOBOL, TEX, ENV and envl (the environment map's sampling tables of ENV, else null), MESH and meshl
-// (the emissive triangles' sampling tables of MESH, else null).
+// trc_render_pwg_body.inc -- the body of k_render_pwg / _tex / _env / _mesh, included as the body of each kernel (trc_render_kernels.hpp)
+// rather than called from a helper: every kernel keeps its code and its name, and the twins share the source.  (The strip body was tried as
+// a function in round 12 and changed its kernels' code -- trc_render_strip_body.inc; this one stays a file with it.)
+// Expects in scope: kp, INTEGRATOR, SOBOL, TEX, LIGHT and tables (that light's sampling tables, null for Light::None).
     const DScene& sc = kp.ks.sc;
     {
         const uint4* src = reinterpret_cast<const uint4*>(sc.blob);
@@ -18,7 +18,7 @@
     uint32_t* park = stack + sc.stack_lds * kBlock;
     uint32_t* ovf = kHybridStack ? kp.stack_ovf + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * sc.stack_ovf_rows * kBlock + lane : nullptr;
     // primary replay (render_block): MEMO rows per wavefront in global memory, this lane's column
-    constexpr int kMemo = (!SOBOL && !ENV && !MESH) ? (int)pwg_memo_rows(INTEGRATOR) : 0;
+    constexpr int kMemo = (!SOBOL && LIGHT == Light::None) ? (int)pwg_memo_rows(INTEGRATOR) : 0;
     uint32_t* memo = kMemo ? kp.memo + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * kMemo * kBlock + lane : nullptr;
     uint32_t n_paths = 0;
     TravCounters cnt;
@@ -33,7 +33,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX, ENV, kMemo, MESH>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt, envl, memo, meshl);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, (int)kRows, TEX, LIGHT, kMemo>(kp, sc, trc_smem, stack, nullptr, ovf, park, slot, lane, n_rays, n_shaded, n_paths, cnt, tables, memo);
         }
         r_rays = wave_sum(park[kParkRays * kBlock]); r_shaded = wave_sum(park[kParkShaded * kBlock]);
     } else {
@@ -43,7 +43,7 @@
             if (lane == 0) slot = atomicAdd(kp.queue, 1u);
             slot = __builtin_amdgcn_readfirstlane(slot);
             if (slot >= n_entries) break;
-            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, ENV, kMemo, MESH>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt, envl, memo, meshl);
+            render_block<false, false, INTEGRATOR, SOBOL, kHybridStack, 0, TEX, LIGHT, kMemo>(kp, sc, trc_smem, stack, nullptr, ovf, nullptr, slot, lane, n_rays, n_shaded, n_paths, cnt, tables, memo);
         }
         r_rays = wave_sum(n_rays); r_shaded = wave_sum(n_shaded);
     }

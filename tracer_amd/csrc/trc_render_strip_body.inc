@@ -1,7 +1,7 @@
-// trc_render_strip_body.inc -- the body of k_render_strip / k_render_strip_tex, included as the body of each kernel (trc_render_kernels.hpp) rather than
-// called from a helper: the kernel of the parent commit keeps its code and its name, and the image-texture twin shares the source.
-// Expects in scope: kp, LDS, INTEGRATOR, SOBOL, TEX, ENV and envl (the environment map's sampling tables of ENV, else null), MESH and meshl
-// (the emissive triangles' sampling tables of MESH, else null).
+// trc_render_strip_body.inc -- the body of k_render_strip / _tex / _env / _mesh, included as the body of each kernel (trc_render_kernels.hpp)
+// rather than called from a helper: every kernel keeps its code and its name, and the twins share the source.  (Tried in round 12 as a
+// __forceinline__ template taking const KRender&: it changed the code of every k_render_strip* kernel of the translation unit.  It stays a file.)
+// Expects in scope: kp, LDS, INTEGRATOR, SOBOL, TEX, LIGHT and tables (that light's sampling tables, null for Light::None).
     const DScene& sc = kp.ks.sc;
     const uint32_t* small_base = stage_scene(sc);
     uint32_t* stack = lane_stack(sc);
@@ -20,25 +20,11 @@
     TravCounters cnt;
     counters_zero(cnt);
 
-    PathCtxOf<TEX, ENV, MESH> cx;
-    cx.S = make_scene_ref(sc, small_base);
+    PathCtxOf<TEX, LIGHT> cx;
     constexpr bool kHybridStack = !LDS && hybrid_stack(INTEGRATOR);
-    if (kHybridStack) cx.S.ovf = kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane;
-    cx.root_min = f3(kp.ks.root_box[0], kp.ks.root_box[1], kp.ks.root_box[2]);
-    cx.root_max = f3(kp.ks.root_box[3], kp.ks.root_box[4], kp.ks.root_box[5]);
-    cx.sh.mats = small_base + sc.off_materials;
-    set_ctx_tex<TEX>(cx, kp);
-    set_ctx_env<ENV>(cx, envl);
-    set_ctx_mesh<MESH>(cx, meshl);
-    cx.ambient = f3(kp.ambient[0], kp.ambient[1], kp.ambient[2]);
-    cx.env.rgb = kp.env_rgb; cx.env.w = kp.env_w; cx.env.h = kp.env_h;
-    cx.stack = stack;
-    cx.lvstack = stack;
-    cx.max_depth = kp.max_depth;
-    cx.density = kp.density;
-    cx.dinfo = kp.dinfo;
-    cx.occupancy = kp.occupancy;
-    if (SOBOL) { cx.sobol32 = kp.sobol32; cx.sobol_vdc = kp.sobol_vdc; cx.sobol_m = kp.sobol_m; cx.sobol_res = 1u << kp.sobol_m; }
+    uint32_t* const ovf = kHybridStack ? kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane : nullptr;
+    fill_path_ctx<SOBOL, TEX, LIGHT>(cx, kp, sc, small_base, stack, stack, tables);      // (one stack: lvstack = stack; sobol_xy: deal_pixels)
+    cx.S.ovf = ovf;
 
     PathState ps;
     Pcg rng;
@@ -121,7 +107,7 @@
             F3 color;
             const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                       ? path_step<false, SOBOL, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, false, kVolume, SOBOL, kHybridStack, TEX, ENV, MESH>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                      : mis_step<LDS, false, kVolume, SOBOL, kHybridStack, TEX, LIGHT>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
             if (finished) finish_sample(color);
         }
     }
