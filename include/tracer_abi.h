@@ -867,7 +867,9 @@ trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table,
  * otherwise -- the next launch runs as a head + the rest; 1 always forgets, 2 always keeps the filtered costs, 3 always keeps and takes the raw durations: tools/moving_camera.py),
  * "no_primary_replay" (every camera ray is walked: trc_debug_primary_replays), "replay_min_lanes" / "replay_chain" (measurement only: a trip of
  * the render loop shades replayed hits alone where at least n lanes of the wavefront hold one, at most m such trips between two walks; 0 = the
- * defaults, 1 and 1; 65 lanes = never).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
+ * defaults, 1 and 1; 65 lanes = never), "strip_force" (tests only: n > 0 gives every wavefront a strip of exactly n blocks, at any spp and whatever
+ * the size of the frame -- "strip_len" asks for a length and is capped so that the GPU keeps 1.5 workgroups per wavefront slot, which on a
+ * frame of a few blocks always leaves 1).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
 
 /* ------------------------------------------------------------------ */

@@ -69,6 +69,18 @@ trc_status trc_debug_mesh_light_tables(trc_ctx* ctx, uint32_t* alias /* 2 n_ligh
 trc_status trc_mesh_light_test(trc_ctx* ctx, const uint32_t* draws /* 4 n */, const float* pos /* 3 n */, size_t n, uint32_t* tri /* n */,
                                float* out /* 7 n */);
 
+/* test hook of the kernel choice (trc_render_pass.hip: choose_kernel): which render kernel the last launch of this context took.
+ * shape: 0 = one pixel block per one-wavefront workgroup (k_render), 1 = a strip of blocks per wavefront (k_render_strip), 2 =
+ * persistent workgroups (k_render_pwg), 3 = k_render_dense.  variant: 0 plain, 1 statistics, 2 Sobol', 3 image textures, 4
+ * TRC_FLAG_ENV_LIGHT, 5 ... with image textures, 6 TRC_FLAG_MESH_LIGHTS, 7 ... with image textures.  lds_resident: the whole tree was
+ * staged in LDS (else read from memory).  triangle_materials: the kernels that read each triangle's material ran
+ * (trc_upload_triangle_materials).  strip: blocks per wavefront (1 unless shape is 1).  launches: kernel choices made since trc_create
+ * (a trc_render call may be several launches; a kept launch of few samples is flushed first).  All zero before the first launch. */
+typedef struct trc_kernel_choice {
+    uint32_t shape, variant, lds_resident, triangle_materials, strip, launches;
+} trc_kernel_choice;
+trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,19 @@
 #include "trc_detmath.h"
 #include "trc_sobol.h"
 
+// The one CPU statement of the light tables and samplers (tests/envlight_ref/envlight_ref.cpp, tests/meshlight_ref/meshlight_ref.cpp,
+// compiled into this library: oracle/Makefile); traceMISLight below draws through them, one item per call.
+extern "C" {
+void envlight_ref_tables(const float* rgb, uint32_t W, uint32_t H, float* weight, uint32_t* rows, uint32_t* marg, double* total);
+void envlight_ref_sample(uint32_t W, uint32_t H, const float* weight, const uint32_t* rows, const uint32_t* marg, double total,
+                         const uint32_t* draws, size_t n, float* dir_pdf);
+void envlight_ref_pdf(uint32_t W, uint32_t H, const float* weight, double total, const float* dirs, size_t m, float* pdf);
+void meshlight_ref_tables(const float* tri_v, uint32_t n_tri, const uint32_t* tri_mat, const int32_t* mat_type, const float* mat_albedo, uint32_t n_mat,
+                          uint32_t* alias, uint32_t* tri, float* pdfA, double* total, uint32_t* n_lights);
+void meshlight_ref_sample(const float* tri_v, const uint32_t* alias, const uint32_t* tri, const float* pdfA, uint32_t n_lights,
+                          const uint32_t* draws, const float* pos, size_t n, uint32_t* tri_out, float* out);
+}
+
 namespace {
 
 // ---------------------------------------------------------------- elementary functions
@@ -53,6 +66,16 @@ inline float m_atan2(float y, float x) { return dm_atan2f(y, x); }
 
 const float PI_F = 3.14159265358979323846f;   // M_PI_F
 const float PI_2_F = 1.57079632679489661923f; // M_PI_2_F
+
+// ---------------------------------------------------------------- the project's own additions (NOT the reference's; oracle/README.md)
+// State of the four features defined in include/tracer_abi.h: per-triangle materials (trc_upload_triangle_materials), image textures
+// (trc_upload_textures), and -- further down, traceMISLight -- TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS.  All borrowed, all null by default:
+// with nothing set every function below is the reference's restatement.
+const uint32_t* g_tri_material = nullptr;      // orc_set_triangle_materials
+uint32_t g_n_tri_material = 0;
+const trc_image* g_images = nullptr;           // orc_set_textures
+uint32_t g_n_images = 0;
+int g_mesh_light_pick = 1;                     // orc_set_mesh_light_pick (knob mesh_light_pick)
 
 // ---------------------------------------------------------------- vectors
 struct V2 { float x, y; float& operator[](int i) { return i == 0 ? x : y; } float operator[](int i) const { return i == 0 ? x : y; } };
@@ -296,6 +319,7 @@ struct Counters {
     uint64_t rays = 0, shaded = 0, n_descend = 0, n_return = 0;
     uint64_t n_leaf[4] = {0, 0, 0, 0};
     uint64_t n_hit_triangle = 0, n_hit_cube = 0;
+    uint64_t branch[ORC_BRANCH_COUNT] = {};     // visits of traceMISLight's branches (oracle.h: orc_branch)
 };
 
 // ---------------------------------------------------------------- AABB.hh (device branch)
@@ -547,6 +571,8 @@ struct Scene {
                 uint32_t r = pIndex * 3;
                 ok = triangle_hit_test(prims.triList[prims.idxList[r]], prims.triList[prims.idxList[r + 1]],
                                        prims.triList[prims.idxList[r + 2]], ray, range_t, rec, cnt);
+                // trc_upload_triangle_materials (tracer_abi.h): triangle t names material[t] instead of the reference's 19
+                if (ok && g_tri_material && pIndex < g_n_tri_material) rec.material = g_tri_material[pIndex];
                 break;
             }
             default: break;
@@ -1012,6 +1038,25 @@ inline GlassMaterial createGlass() { return GlassMaterial(FresnelDielectric{1.5f
 // ---------------------------------------------------------------- Texture.hh:17-43, Material.hh:44-146
 // Noise / Image need Metal's sampler and noise(); no material on the path uses them:
 // Image with a null texture returns albedo (Texture.hh:29-31); Noise is resolved to albedo too.
+// trc_upload_textures (tracer_abi.h; the lookup as tests/test_gpu_textures.py states it): sample.rgb of an RGB float image, rows
+// bottom-up, bilinear, clamp to edge, one binary32 operation at a time.  A non-finite uv component is looked up as 0, a finite one is
+// clamped to [-1, 2].
+inline V3 image_value(const trc_image& im, V2 uv) {
+    const float u = (std::isnan(uv.x) || std::isinf(uv.x)) ? 0.0f : fminf(fmaxf(uv.x, -1.0f), 2.0f);
+    const float v = (std::isnan(uv.y) || std::isinf(uv.y)) ? 0.0f : fminf(fmaxf(uv.y, -1.0f), 2.0f);
+    const uint32_t w = im.width, h = im.height;
+    const float x = u * (float)w - 0.5f;
+    const float y = v * (float)h - 0.5f;
+    const float fx0 = floorf(x), fy0 = floorf(y);
+    const float fx = x - fx0, fy = y - fy0;
+    auto clampi = [](float f, uint32_t n) { return f < 0.0f ? 0u : (f > (float)(n - 1) ? n - 1 : (uint32_t)f); };
+    const uint32_t x0 = clampi(fx0, w), x1 = clampi(fx0 + 1.0f, w);
+    const uint32_t y0 = clampi(fy0, h), y1 = clampi(fy0 + 1.0f, h);
+    auto texel = [&](uint32_t xx, uint32_t yy) { const float* t = im.rgb + 3 * ((size_t)yy * w + xx); return v3(t[0], t[1], t[2]); };
+    const V3 top = (1.0f - fx) * texel(x0, y0) + fx * texel(x1, y0);
+    const V3 bot = (1.0f - fx) * texel(x0, y1) + fx * texel(x1, y1);
+    return (1.0f - fy) * top + fy * bot;
+}
 inline V3 texture_value(const trc_TextureInfo& ti, V2 uv) {
     const V3 albedo = v3(ti.albedo);
     switch (ti.type) {
@@ -1020,7 +1065,9 @@ inline V3 texture_value(const trc_TextureInfo& ti, V2 uv) {
             float sines = m_sin(8 * PI_F * uv.x) * m_cos(PI_F / 2 + 4 * PI_F * uv.y);
             return albedo * (0.5f * (sines < 0 ? 0.0f : 1.0f) + 0.5f);   // step(0, sines)
         }
-        case TRC_TEX_IMAGE: return albedo;
+        // an ACTIVE image (textureIndex below the number uploaded) is its sample, not scaled by albedo (Texture.hh:33-34); an index
+        // not below it, or nothing uploaded, is the reference's nullptr branch
+        case TRC_TEX_IMAGE: return (g_images && ti.textureIndex < g_n_images) ? image_value(g_images[ti.textureIndex], uv) : albedo;
         case TRC_TEX_NOISE: return albedo;
         default: return v3(1.0f);
     }
@@ -1083,10 +1130,28 @@ inline Ray castRay(const trc_Camera* camera, float s, float t, RandomSampler* xs
 }
 
 // ---------------------------------------------------------------- integrators
+// The light of a traceMIS launch besides the two squares (TRC_FLAG_ENV_LIGHT or TRC_FLAG_MESH_LIGHTS, tracer_abi.h): its tables, built per
+// orc_render call by the restatements named at the top of this file, and p = the probability that the light pick takes it.
+struct LightSetup {
+    enum Kind { kEnv, kMesh } kind = kEnv;
+    float p = 0.0f;                     // p_env / p_mesh: 0 without light, 1/2 with squareList[5] / [6], else 1
+    bool squares = false;               // n_square >= 7
+    // the map's cells
+    uint32_t W = 0, H = 0;
+    std::vector<float> weight;
+    std::vector<uint32_t> rows, marg;
+    double total = 0.0;
+    // the mesh's light triangles
+    std::vector<float> tri_v;           // 9 floats per triangle: v0, v1, v2 as the scene holds them
+    std::vector<uint32_t> alias, tri;
+    std::vector<float> pdfA;
+    uint32_t n_lights = 0;
+};
 struct Env {
     const trc_Material* materials; V3 ambient;
     const trc_GridDensityInfo* densityInfo = nullptr; const float* densityArray = nullptr;
     const float* envmap = nullptr; uint32_t env_w = 0, env_h = 0;      // equirectangular RGB float image (texHDR)
+    const LightSetup* light = nullptr;                                 // TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS (traceMISLight)
 };
 // Render.hh:42-48 + `texHDR.sample(textureSampler, uv)` (Render.metal:100-105,301-304,435-438, Photon.metal:29-33):
 // linear filter, clamp-to-edge (Common.hh:11).  Metal's filtering weights are implementation-defined; this is the
@@ -1231,6 +1296,206 @@ V3 traceMIS(int depth, Ray& ray, XSampler& xsampler, const Env& env, Scene& scen
             float dist2 = dot(d, d);
             float lightPDF = hitRecord.PDF * dist2 / cosOnLight;
             weight = weight * PowerHeuristic(1, scat_bxPDF, 1, lightPDF);
+            color = color + ratio * weight / scat_bxPDF;
+            break;
+        }
+    } while ((--depth) > 0);
+    return color;
+}
+
+// ---------------------------------------------------------------- traceMIS with a light besides the squares
+// NOT the reference's: the project's own TRC_FLAG_ENV_LIGHT and TRC_FLAG_MESH_LIGHTS, written from their definitions in
+// include/tracer_abi.h and DESIGN.md 4.9 / 4.10, one operation at a time.  traceMIS above stays the code that runs without a flag.
+// power heuristic f^2 / (f^2 + g^2) in the form the definitions use for the new strategies: 1 when g is not > 0, 0 when f is not > 0
+inline float light_mis_weight(float f, float g) {
+    if (!(g > 0.0f)) return 1.0f;
+    if (!(f > 0.0f)) return 0.0f;
+    const float r = g / f;
+    return 1.0f / (1.0f + r * r);
+}
+inline void visit(Counters* cnt, int b) { if (cnt) cnt->branch[b]++; }
+
+V3 traceMISLight(int depth, Ray& ray, RandomSampler& xsampler, const Env& env, Scene& scene, Counters* cnt) {
+    const LightSetup& L = *env.light;
+    const bool is_env = L.kind == LightSetup::kEnv;
+    const float p = L.p;
+    HitRecord hitRecord;
+    V3 scat_attenuation = v3(0); float scat_bxPDF = 1.0f;
+    V3 ratio = v3(1.0f);
+    V3 color = v3(0.0f);
+    bool cosine_lobe = false;       // the previous vertex took its BSDF sample from a cosine lobe: the light's strategy shares the ray in flight
+    bool primary = true;
+    const trc_scene& prims = scene.prims;
+    bool hitted = scene.hit(ray, hitRecord, FLT_MAX);
+    do {
+        if (!hitted) {
+            V3 le = env_radiance(env, ray.direction);
+            if (is_env) {               // an escaping ray: a BSDF-sampled one from a cosine lobe is weighted against the map's strategy
+                if (primary) visit(cnt, ORC_BR_ESCAPE_CAMERA);
+                else if (!cosine_lobe) visit(cnt, ORC_BR_ESCAPE_OTHER_LOBE);
+                else {
+                    const float d[3] = {ray.direction.x, ray.direction.y, ray.direction.z};
+                    float pdf = 0.0f;
+                    envlight_ref_pdf(L.W, L.H, L.weight.data(), L.total, d, 1, &pdf);
+                    const float pe = p * pdf;
+                    if (pe > 0.0f) { le = le * light_mis_weight(scat_bxPDF, pe); visit(cnt, ORC_BR_ESCAPE_WEIGHTED); }
+                    else visit(cnt, ORC_BR_ESCAPE_ZERO_PDF);
+                }
+            }
+            color = color + ratio * le;
+            break;
+        }
+        const trc_Material& mat = env.materials[hitRecord.material];
+        if (mat.type == TRC_MAT_DIFFUSE) {      // (a camera ray: a bounce ray's emitter hit ends the path at the bottom of the loop)
+            V3 le = v3(mat.textureInfo.albedo);
+            float w = dot(-ray.direction, -hitRecord.gn);
+            return ratio * le * fabsf(w);
+        }
+        primary = false;
+        V2 uu = xsampler.sample2D();
+        const V3 hit_origin = hitRecord.p;
+        V3 _origin = offset_ray(hitRecord.p, hitRecord.sn);
+        // the light pick: one draw; below p the light, else square 5 below p + (1 - p) / 2 and square 6 above
+        const float pick = xsampler.random();
+        cosine_lobe = mat.type == TRC_MAT_LAMBERT || (mat.type == TRC_MAT_PLASTIC && uu.x < 0.5f);
+        if (mat.type == TRC_MAT_PLASTIC) visit(cnt, uu.x < 0.5f ? ORC_BR_PLASTIC_LAMBERT_LOBE : ORC_BR_PLASTIC_BECKMANN_LOBE);
+        int kind = 0;                           // 0: no light sample, 1: a square's, 2: the light's
+        if (pick < p) {
+            visit(cnt, p == 1.0f ? ORC_BR_PICK_LIGHT_P1 : ORC_BR_PICK_LIGHT);
+            if (!cosine_lobe) visit(cnt, mat.type == TRC_MAT_PLASTIC ? ORC_BR_NO_SAMPLE_BECKMANN : mat.type == TRC_MAT_METAL ? ORC_BR_NO_SAMPLE_METAL : ORC_BR_NO_SAMPLE_GLASS);
+            else if (is_env && !(depth > 1)) visit(cnt, ORC_BR_ENV_DEPTH_CUTOFF);      // the BSDF ray of this vertex would not count if it escaped
+            else kind = 2;
+        } else if (L.squares) {
+            kind = 1;
+        } else visit(cnt, ORC_BR_NO_SQUARES_NO_SAMPLE);
+        V3 nx, ny;
+        CoordinateSystem(hitRecord.sn, nx, ny);
+        Ray _ray(_origin, v3(0.0f, 0.0f, 1.0f));
+        float _dis = FLT_MAX;
+        V3 light_term = v3(0.0f);
+        float liPDF = 0.0f;
+        if (kind == 1) {
+            LightSampleRecord lsr;
+            const bool five = pick < p + (1.0f - p) * 0.5f;
+            visit(cnt, five ? ORC_BR_PICK_SQUARE5 : ORC_BR_PICK_SQUARE6);
+            square_sample(prims.squareList[five ? 5 : 6], uu, _origin, lsr);
+            V3 _dir = lsr.p - _origin;
+            V3 _nor = normalize(_dir);
+            _dis = length(_dir);
+            _ray = Ray(_origin, _nor);
+            float cosOnLight = fabsf(dot(lsr.n, -_nor));
+            light_term = v3(env.materials[lsr.material].textureInfo.albedo) * cosOnLight;
+            liPDF = (_dis * _dis) * lsr.areaPDF / cosOnLight;
+        } else if (kind == 2 && is_env) {       // the map's sample: six more draws
+            uint32_t draws[6];
+            for (int k = 0; k < 4; ++k) draws[k] = pcg32_random_r(xsampler.rng);
+            for (int k = 4; k < 6; ++k) { const float f = xsampler.random(); memcpy(&draws[k], &f, 4); }
+            float dir_pdf[4];
+            envlight_ref_sample(L.W, L.H, L.weight.data(), L.rows.data(), L.marg.data(), L.total, draws, 1, dir_pdf);
+            const V3 dir = v3(dir_pdf[0], dir_pdf[1], dir_pdf[2]);
+            const float wi_z = dot(hitRecord.sn, dir), wo_z = -dot(hitRecord.sn, ray.direction);
+            const bool support = wi_z > 0.0f && wo_z > 0.0f;
+            visit(cnt, support ? ORC_BR_SUPPORT : ORC_BR_NO_SUPPORT);
+            liPDF = support ? p * dir_pdf[3] : 0.0f;
+            if (liPDF > 0.0f) {
+                _ray = Ray(_origin, dir);       // from where a BSDF ray of this direction starts, to infinity
+                light_term = env_radiance(env, _ray.direction);
+            }
+        } else if (kind == 2) {                 // the mesh's sample: four more draws
+            uint32_t draws[4];
+            for (int k = 0; k < 2; ++k) draws[k] = pcg32_random_r(xsampler.rng);
+            for (int k = 2; k < 4; ++k) { const float f = xsampler.random(); memcpy(&draws[k], &f, 4); }
+            const float pos[3] = {_origin.x, _origin.y, _origin.z};
+            uint32_t t = 0;
+            float out[7];
+            meshlight_ref_sample(L.tri_v.data(), L.alias.data(), L.tri.data(), L.pdfA.data(), L.n_lights, draws, pos, 1, &t, out);
+            const V3 sp = v3(out[0], out[1], out[2]), sn = v3(out[3], out[4], out[5]);
+            const float pdfA = out[6];
+            V3 _dir = offset_ray(sp, sn) - _origin;
+            V3 _nor = normalize(_dir);
+            const float dist = length(_dir);
+            const float cosL = fabsf(dot(sn, -_nor));
+            const float wi_z = dot(hitRecord.sn, _nor), wo_z = -dot(hitRecord.sn, ray.direction);
+            const bool support = wi_z > 0.0f && wo_z > 0.0f;
+            visit(cnt, support ? ORC_BR_SUPPORT : ORC_BR_NO_SUPPORT);
+            liPDF = support ? p * pdfA * (dist * dist) / cosL : 0.0f;
+            if (!(liPDF > 0.0f && liPDF <= FLT_MAX)) {          // a grazing or coincident sample: cosL or dist 0
+                if (support) visit(cnt, ORC_BR_LIPDF_GUARD);
+                liPDF = 0.0f;
+            }
+            if (liPDF > 0.0f) {
+                _dis = dist;
+                _ray = Ray(_origin, _nor);
+                const uint32_t material = (g_tri_material && t < g_n_tri_material) ? g_tri_material[t] : 19u;
+                light_term = v3(env.materials[material].textureInfo.albedo) * cosL;
+            }
+        }
+        bool blocked = true;
+        if (kind == 1 || (kind == 2 && liPDF > 0.0f)) {         // a square's sample walks whatever its pdf; a light sample of pdf 0 walks nothing
+            HitRecord shr;
+            blocked = scene.hit(_ray, shr, _dis, true);
+        } else if (kind == 2) visit(cnt, ORC_BR_ZERO_PDF_NO_SHADOW_RAY);
+        V3 minus_d = -ray.direction;
+        if (!blocked) {
+            V3 wo = v3(dot(nx, minus_d), dot(ny, minus_d), dot(hitRecord.sn, minus_d));
+            V3 wi = v3(dot(nx, _ray.direction), dot(ny, _ray.direction), dot(hitRecord.sn, _ray.direction));
+            float bxPDF = 0;
+            if (cnt) cnt->shaded++;
+            V3 weight = Material_F(mat, wo, wi, hitRecord.uv, bxPDF, uu) * light_term;
+            if (kind == 1) color = color + ratio * (weight * PowerHeuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - p));
+            else color = color + ratio * (weight * light_mis_weight(liPDF, bxPDF)) / liPDF;
+        }
+        // BXDF sampling, as traceMIS
+        V3 wi = v3(0);
+        float bxPDF = 0;
+        V3 wo = v3(dot(nx, minus_d), dot(ny, minus_d), dot(hitRecord.sn, minus_d));
+        if (cnt) cnt->shaded++;
+        scat_attenuation = Material_S_F(mat, wo, wi, hitRecord.uv, uu, bxPDF);
+        scat_bxPDF = bxPDF;
+        if (bxPDF <= 0) break;
+        if (wi.z < 0) {
+            V3 wiw = (nx * wi.x + ny * wi.y) + hitRecord.sn * wi.z;
+            ray.update(offset_ray(hit_origin, -hitRecord.sn), wiw);
+        } else {
+            V3 wiw = (nx * wi.x + ny * wi.y) + hitRecord.sn * wi.z;
+            ray.update(_origin, wiw);
+        }
+        ratio = ratio * (scat_attenuation / scat_bxPDF);
+        {
+            float rr = RGBToY(ratio);
+            if (xsampler.random() > rr) break;
+            ratio = ratio * (1.0f / rr);
+        }
+        hitted = scene.hit(ray, hitRecord, FLT_MAX);
+        if (hitted && env.materials[hitRecord.material].type == TRC_MAT_DIFFUSE) {
+            V3 Li = v3(env.materials[hitRecord.material].textureInfo.albedo);
+            if (!is_env && L.n_lights != 0 && hitRecord.pType == TRC_PRIM_TRIANGLE) {
+                // a triangle emitter while the scene has a light triangle: the integrand the mesh's light sample estimates, on the
+                // GEOMETRIC normal, without the reference's second scat_attenuation / scat_bxPDF and without hitRecord.PDF
+                const uint32_t t = hitRecord.pIndex;
+                const float* tv = L.tri_v.data() + 9 * (size_t)t;
+                const V3 v0 = v3a(tv), v1 = v3a(tv + 3), v2 = v3a(tv + 6);
+                const V3 n = normalize(cross(v1 - v0, v2 - v0));
+                const float cosL = fabsf(dot(n, -ray.direction));
+                V3 d = hitRecord.p - ray.origin;
+                float w = 1.0f;
+                bool weighted = false;
+                if (cosine_lobe) {
+                    const float lightPDF = p * L.pdfA[t] * dot(d, d) / cosL;
+                    if (lightPDF > 0.0f && lightPDF <= FLT_MAX) { w = light_mis_weight(scat_bxPDF, lightPDF); weighted = true; }
+                }
+                visit(cnt, weighted ? ORC_BR_TRI_EMITTER_WEIGHTED : ORC_BR_TRI_EMITTER_W1);
+                color = color + ratio * (Li * cosL) * w;
+                break;
+            }
+            float cosOnLight = dot(-ray.direction, hitRecord.sn);
+            V3 weight = scat_attenuation * Li * cosOnLight;
+            V3 d = hitRecord.p - ray.origin;
+            float dist2 = dot(d, d);
+            float lightPDF = hitRecord.PDF * dist2 / cosOnLight;
+            const bool shared = is_env ? L.squares : true;      // without square lights no light strategy shares the hit: weight 1
+            visit(cnt, shared ? ORC_BR_EMITTER_SHARED : ORC_BR_EMITTER_NOT_SHARED);
+            if (shared) weight = weight * PowerHeuristic(1, scat_bxPDF, 1, lightPDF);
             color = color + ratio * weight / scat_bxPDF;
             break;
         }
@@ -1451,6 +1716,40 @@ V3 traceVolume(int depth, Ray& ray, RandomSampler& xsampler, const Env& env, Sce
 // density grid of the GridDensity medium for orc_render (the oracle keeps one, like PackageEnv ids 3/4)
 static const float* g_envmap = nullptr;
 static uint32_t g_env_w = 0, g_env_h = 0;
+static uint64_t g_branch[ORC_BRANCH_COUNT] = {};      // orc_debug_branch_counts
+
+// the tables of the light a flagged orc_render samples (tracer_abi.h: TRC_FLAG_ENV_LIGHT, TRC_FLAG_MESH_LIGHTS)
+void light_setup(LightSetup& L, const trc_scene& sc, uint32_t flags) {
+    L.squares = sc.n_square >= 7;
+    if (flags & TRC_FLAG_ENV_LIGHT) {
+        L.kind = LightSetup::kEnv;
+        L.W = g_env_w; L.H = g_env_h;
+        const size_t n = (size_t)L.W * L.H;
+        L.weight.resize(n); L.rows.resize(2 * n); L.marg.resize(2 * (size_t)L.H);
+        envlight_ref_tables(g_envmap, L.W, L.H, L.weight.data(), L.rows.data(), L.marg.data(), &L.total);
+        L.p = !(L.total > 0.0) ? 0.0f : (L.squares ? 0.5f : 1.0f);
+    } else {
+        L.kind = LightSetup::kMesh;
+        const uint32_t n_tri = sc.n_index / 3;
+        L.tri_v.resize(9 * (size_t)n_tri);
+        std::vector<uint32_t> tri_mat(n_tri);
+        for (uint32_t t = 0; t < n_tri; ++t) {
+            for (int k = 0; k < 3; ++k) memcpy(&L.tri_v[9 * (size_t)t + 3 * k], sc.triList[sc.idxList[3 * t + k]].v, 12);
+            tri_mat[t] = (g_tri_material && t < g_n_tri_material) ? g_tri_material[t] : 19u;
+        }
+        std::vector<int32_t> mat_type(sc.n_material);
+        std::vector<float> mat_albedo(3 * (size_t)sc.n_material);
+        for (uint32_t m = 0; m < sc.n_material; ++m) {
+            mat_type[m] = sc.materials[m].type;
+            mat_albedo[3 * m] = sc.materials[m].textureInfo.albedo.x; mat_albedo[3 * m + 1] = sc.materials[m].textureInfo.albedo.y;
+            mat_albedo[3 * m + 2] = sc.materials[m].textureInfo.albedo.z;
+        }
+        L.alias.resize(2 * (size_t)n_tri + 2); L.tri.resize((size_t)n_tri + 1); L.pdfA.resize((size_t)n_tri + 1);
+        meshlight_ref_tables(L.tri_v.data(), n_tri, tri_mat.data(), mat_type.data(), mat_albedo.data(), sc.n_material, L.alias.data(), L.tri.data(),
+                             L.pdfA.data(), &L.total, &L.n_lights);
+        L.p = (L.n_lights == 0 || g_mesh_light_pick == 0) ? 0.0f : (L.squares ? 0.5f : 1.0f);
+    }
+}
 static const trc_GridDensityInfo* g_density_info = nullptr;
 static const float* g_density_array = nullptr;
 static trc_GridDensityInfo g_density_info_copy;
@@ -1479,6 +1778,8 @@ void render_pixel(const trc_scene& prims, const trc_Camera* camera, const Env& e
             SobolSampler ss(rng, frame, x, y % vh, W, vh);
             color = (prm.integrator == TRC_INTEGRATOR_MIS) ? traceMIS((int)prm.max_depth, ray, ss, env, scene, cnt)
                                                            : tracePath((int)prm.max_depth, ray, ss, env, scene, cnt);
+        } else if (env.light && prm.integrator == TRC_INTEGRATOR_MIS) {      // TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS (orc_render)
+            color = traceMISLight((int)prm.max_depth, ray, rs, env, scene, cnt);
         } else
         color = (prm.integrator == TRC_INTEGRATOR_VOLUME) ? traceVolume((int)prm.max_depth, ray, rs, env, scene, cnt)
                    : (prm.integrator == TRC_INTEGRATOR_MIS)  ? traceMIS((int)prm.max_depth, ray, rs, env, scene, cnt)
@@ -1941,6 +2242,26 @@ void orc_set_environment_map(uint32_t w, uint32_t h, const float* rgb) {
     if (rgb && w && h) { g_envmap = rgb; g_env_w = w; g_env_h = h; } else { g_envmap = nullptr; g_env_w = g_env_h = 0; }
 }
 
+void orc_set_triangle_materials(const uint32_t* material, uint32_t n) {
+    if (material && n) { g_tri_material = material; g_n_tri_material = n; } else { g_tri_material = nullptr; g_n_tri_material = 0; }
+}
+void orc_set_textures(const trc_image* images, uint32_t n) {
+    if (images && n) { g_images = images; g_n_images = n; } else { g_images = nullptr; g_n_images = 0; }
+}
+void orc_set_mesh_light_pick(int value) { g_mesh_light_pick = value; }
+void orc_debug_branch_counts(uint64_t* out, int reset) {
+    if (out) memcpy(out, g_branch, sizeof g_branch);
+    if (reset) memset(g_branch, 0, sizeof g_branch);
+}
+const char* orc_debug_branch_name(uint32_t b) {
+    static const char* const names[ORC_BRANCH_COUNT] = {
+        "pick_light", "pick_light_p1", "pick_square5", "pick_square6", "no_squares_no_sample", "support", "no_support", "lipdf_guard",
+        "zero_pdf_no_shadow_ray", "no_sample_beckmann", "no_sample_metal", "no_sample_glass", "env_depth_cutoff", "escape_weighted",
+        "escape_zero_pdf", "escape_other_lobe", "escape_camera", "tri_emitter_weighted", "tri_emitter_w1", "emitter_shared",
+        "emitter_not_shared", "plastic_lambert_lobe", "plastic_beckmann_lobe"};
+    return b < ORC_BRANCH_COUNT ? names[b] : "";
+}
+
 void orc_set_density(const trc_GridDensityInfo* info, const float* density) {
     if (info && density) { g_density_info_copy = *info; g_density_info = &g_density_info_copy; g_density_array = density; }
     else { g_density_info = nullptr; g_density_array = nullptr; }
@@ -1951,6 +2272,13 @@ void orc_render(const trc_scene* scene, const trc_Camera* camera, const float en
     Env env{scene->materials, v3(env_rgb[0], env_rgb[1], env_rgb[2])};
     env.densityInfo = g_density_info; env.densityArray = g_density_array;
     env.envmap = g_envmap; env.env_w = g_env_w; env.env_h = g_env_h;
+    LightSetup light;
+    const bool env_light = (params->flags & TRC_FLAG_ENV_LIGHT) != 0 && g_envmap;
+    const bool mesh_lights = (params->flags & TRC_FLAG_MESH_LIGHTS) != 0 && !env_light;
+    if ((env_light || mesh_lights) && params->integrator == TRC_INTEGRATOR_MIS && !(params->flags & TRC_FLAG_SOBOL)) {
+        light_setup(light, *scene, env_light ? (uint32_t)TRC_FLAG_ENV_LIGHT : (uint32_t)TRC_FLAG_MESH_LIGHTS);
+        env.light = &light;
+    }
     const uint32_t nranks = params->tile_nranks ? params->tile_nranks : 1;
     unsigned T = n_threads > 0 ? (unsigned)n_threads : std::max(1u, std::thread::hardware_concurrency());
     T = std::min<unsigned>(T, H ? H : 1);
@@ -1973,6 +2301,8 @@ void orc_render(const trc_scene* scene, const trc_Camera* camera, const float en
         for (unsigned t = 0; t < T; ++t) pool.emplace_back(work, t);
         for (auto& th : pool) th.join();
     }
+    for (unsigned t = 0; t < T; ++t)
+        for (int b = 0; b < ORC_BRANCH_COUNT; ++b) g_branch[b] += counters[t].branch[b];
     if (stats) {
         for (unsigned t = 0; t < T; ++t) {
             const Counters& c = counters[t];

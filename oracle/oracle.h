@@ -52,6 +52,48 @@ void orc_set_density(const trc_GridDensityInfo* info, const float* density);
  * its bilinear lookup instead of the constant env_rgb; `rgb` (3*w*h floats, row 0 at v = 0) is borrowed; NULL clears */
 void orc_set_environment_map(uint32_t w, uint32_t h, const float* rgb);
 
+/* ---- the project's own features (include/tracer_abi.h), NOT the reference's: see oracle/README.md ----
+ * Per-triangle materials (trc_upload_triangle_materials): a triangle hit names material[t] instead of 19, for every caller of
+ * Scene::hit (the three integrators, orc_trace_rays, the SPPM pass).  `material` (n entries) is borrowed; NULL clears it. */
+void orc_set_triangle_materials(const uint32_t* material, uint32_t n);
+/* Image textures (trc_upload_textures): n images, rows bottom-up; the array and the texels are borrowed; NULL / 0 clears them.  An
+ * Image material whose textureIndex is below n takes the bilinear sample, any other its albedo. */
+void orc_set_textures(const trc_image* images, uint32_t n);
+/* knob mesh_light_pick of TRC_FLAG_MESH_LIGHTS: 0 forces p_mesh = 0 and keeps the triangle-emitter formula (the BSDF-only estimator) */
+void orc_set_mesh_light_pick(int value);
+/* TRC_FLAG_ENV_LIGHT (with orc_set_environment_map) and TRC_FLAG_MESH_LIGHTS in trc_params.flags of orc_render, TRC_INTEGRATOR_MIS
+ * without TRC_FLAG_SOBOL, run traceMISLight; its tables and samplers are tests/envlight_ref and tests/meshlight_ref, linked in.
+ * Visits of its branches since the last reset, summed over the orc_render calls (a debugging aid of the tests: which arithmetic a
+ * scene reaches).  Not thread-safe against a running orc_render. */
+enum orc_branch {
+    ORC_BR_PICK_LIGHT = 0,           /* the pick took the light, p = 1/2 */
+    ORC_BR_PICK_LIGHT_P1,            /* ... p = 1 (a scene without squareList[5] / [6]) */
+    ORC_BR_PICK_SQUARE5,             /* the pick took square 5: contribution / (1 - p) */
+    ORC_BR_PICK_SQUARE6,
+    ORC_BR_NO_SQUARES_NO_SAMPLE,     /* the pick left the light, and there is no square */
+    ORC_BR_SUPPORT,                  /* the light's sample has wi.z > 0 and wo.z > 0 */
+    ORC_BR_NO_SUPPORT,
+    ORC_BR_LIPDF_GUARD,              /* the mesh's sample with support whose liPDF is 0, infinite or NaN */
+    ORC_BR_ZERO_PDF_NO_SHADOW_RAY,   /* a light sample of pdf 0 walks no shadow ray */
+    ORC_BR_NO_SAMPLE_BECKMANN,       /* the pick took the light at a vertex whose lobe is not a cosine lobe: no sample */
+    ORC_BR_NO_SAMPLE_METAL,
+    ORC_BR_NO_SAMPLE_GLASS,
+    ORC_BR_ENV_DEPTH_CUTOFF,         /* the map picked at the last vertex (depth 1): no sample */
+    ORC_BR_ESCAPE_WEIGHTED,          /* an escaping BSDF ray from a cosine lobe, weighted against p_env pdf(d) > 0 */
+    ORC_BR_ESCAPE_ZERO_PDF,          /* ... where that density is 0: weight 1 */
+    ORC_BR_ESCAPE_OTHER_LOBE,        /* an escaping BSDF ray from another lobe: weight 1 */
+    ORC_BR_ESCAPE_CAMERA,            /* an escaping camera ray */
+    ORC_BR_TRI_EMITTER_WEIGHTED,     /* BSDF-sampled hit on a triangle emitter, weighted against p_mesh pdfA dist^2 / cos */
+    ORC_BR_TRI_EMITTER_W1,           /* ... with weight 1 (another lobe, p_mesh = 0) */
+    ORC_BR_EMITTER_SHARED,           /* the reference's emitter-hit formula with its power heuristic */
+    ORC_BR_EMITTER_NOT_SHARED,       /* ... without it (TRC_FLAG_ENV_LIGHT, no squares) */
+    ORC_BR_PLASTIC_LAMBERT_LOBE,     /* a Plastic vertex whose sample2D picks the Lambert lobe */
+    ORC_BR_PLASTIC_BECKMANN_LOBE,
+    ORC_BRANCH_COUNT
+};
+void        orc_debug_branch_counts(uint64_t* out /* ORC_BRANCH_COUNT */, int reset);
+const char* orc_debug_branch_name(uint32_t branch);
+
 /* material entry points (Material.hh:77-146) in the local shading frame */
 void  orc_material_S_F(const trc_Material* m, const float wo[3], const float uv[2], const float uu[2],
                        float wi_out[3], float f_out[3], float* pdf_out);

@@ -93,6 +93,16 @@ def lib(libm=False):
         L.orc_set_environment_map.restype = None
         L.orc_set_density.argtypes = [C.POINTER(abi.GridDensityInfo), C.c_void_p]
         L.orc_set_density.restype = None
+        L.orc_set_triangle_materials.argtypes = [C.c_void_p, C.c_uint32]
+        L.orc_set_triangle_materials.restype = None
+        L.orc_set_textures.argtypes = [C.c_void_p, C.c_uint32]
+        L.orc_set_textures.restype = None
+        L.orc_set_mesh_light_pick.argtypes = [C.c_int]
+        L.orc_set_mesh_light_pick.restype = None
+        L.orc_debug_branch_counts.argtypes = [C.c_void_p, C.c_int]
+        L.orc_debug_branch_counts.restype = None
+        L.orc_debug_branch_name.argtypes = [C.c_uint32]
+        L.orc_debug_branch_name.restype = C.c_char_p
         L.orc_lbvh_build.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(abi.BVH), C.POINTER(C.c_uint32)]
         L.orc_lbvh_build.restype = None
         L.orc_sah_build.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(abi.BVH)]
@@ -123,31 +133,87 @@ def make_rays(origins, directions, tmax=None):
     return rays
 
 
-def trace_rays(scene_view, rays, any_hit=False, brute=False, libm=False):
+def trace_rays(scene_view, rays, any_hit=False, brute=False, libm=False, triangle_materials=None):
     hits = np.zeros(len(rays), dtype=HIT_DTYPE)
     L = lib(libm)
-    if brute:
-        L.orc_trace_rays_brute(C.byref(scene_view), rays.ctypes.data, len(rays), hits.ctypes.data)
-    else:
-        L.orc_trace_rays(C.byref(scene_view), rays.ctypes.data, len(rays), hits.ctypes.data, 1 if any_hit else 0)
+    with _features(L, triangle_materials):
+        if brute:
+            L.orc_trace_rays_brute(C.byref(scene_view), rays.ctypes.data, len(rays), hits.ctypes.data)
+        else:
+            L.orc_trace_rays(C.byref(scene_view), rays.ctypes.data, len(rays), hits.ctypes.data, 1 if any_hit else 0)
     return hits
 
 
 def render(scene_view, camera, width, height, rng, accum=None, spp=1, max_depth=8, integrator=0, frame0=0,
-           env=(0.0, 0.0, 0.0), tile_rank=0, tile_nranks=1, n_threads=0, libm=False, view_height=0, sobol=False):
-    """kernelPathTracing on the CPU.  rng: (H,W,4) uint32, updated in place.  Returns (accum, stats)."""
+           env=(0.0, 0.0, 0.0), tile_rank=0, tile_nranks=1, n_threads=0, libm=False, view_height=0, sobol=False,
+           env_light=False, mesh_lights=False, mesh_light_pick=1, triangle_materials=None, textures=None):
+    """kernelPathTracing on the CPU.  rng: (H,W,4) uint32, updated in place.  Returns (accum, stats).
+    The project's own features (include/tracer_abi.h; not the reference's), for this call only: env_light = TRC_FLAG_ENV_LIGHT over
+    the map of set_environment_map, mesh_lights = TRC_FLAG_MESH_LIGHTS (mesh_light_pick: the knob of that name), both traceMIS
+    without Sobol'; triangle_materials = the array of trc_upload_triangle_materials; textures = the images of trc_upload_textures,
+    (h, w, 3) float32 each, rows bottom-up."""
     assert rng.dtype == np.uint32 and rng.shape == (height, width, 4) and rng.flags.c_contiguous
     if accum is None:
         accum = np.zeros((height, width, 4), dtype=np.float32)
     assert accum.dtype == np.float32 and accum.shape == (height, width, 4) and accum.flags.c_contiguous
+    assert not (env_light and mesh_lights), "one light besides the squares, never two"
+    if env_light or mesh_lights:
+        assert integrator == abi.INTEGRATOR_MIS and not sobol, "the light flags are traceMIS's, without Sobol'"
+    assert not env_light or _ENVMAP_KEEPALIVE, "TRC_FLAG_ENV_LIGHT needs a map (set_environment_map)"
+    flags = abi.FLAG_COLLECT_STATS | (abi.FLAG_SOBOL if sobol else 0)
+    flags |= (abi.FLAG_ENV_LIGHT if env_light else 0) | (abi.FLAG_MESH_LIGHTS if mesh_lights else 0)
     prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0,
-                     tile_rank=tile_rank, tile_nranks=tile_nranks,
-                     flags=abi.FLAG_COLLECT_STATS | (abi.FLAG_SOBOL if sobol else 0), view_height=view_height)
+                     tile_rank=tile_rank, tile_nranks=tile_nranks, flags=flags, view_height=view_height)
     stats = abi.Stats()
     env_c = (C.c_float * 3)(*env)
-    lib(libm).orc_render(C.byref(scene_view), C.byref(camera), env_c, width, height, rng.ctypes.data,
-                         accum.ctypes.data, C.byref(prm), C.byref(stats), n_threads)
+    L = lib(libm)
+    with _features(L, triangle_materials, textures, mesh_light_pick):
+        L.orc_render(C.byref(scene_view), C.byref(camera), env_c, width, height, rng.ctypes.data,
+                     accum.ctypes.data, C.byref(prm), C.byref(stats), n_threads)
     return accum, stats
+
+
+class _features:
+    """per-triangle materials, image textures and the mesh_light_pick knob set in the oracle for the calls inside the block"""
+
+    def __init__(self, L, triangle_materials=None, textures=None, mesh_light_pick=1):
+        self.L, self.pick = L, mesh_light_pick
+        self.tm = None if triangle_materials is None else np.ascontiguousarray(triangle_materials, dtype=np.uint32)
+        self.imgs = None
+        if textures:
+            self.texels = [np.ascontiguousarray(t, dtype=np.float32) for t in textures]
+            assert all(t.ndim == 3 and t.shape[2] == 3 and t.size for t in self.texels)
+            self.imgs = (abi.Image * len(self.texels))()
+            for d, t in zip(self.imgs, self.texels):
+                d.width, d.height, d.rgb = t.shape[1], t.shape[0], t.ctypes.data_as(C.POINTER(C.c_float))
+
+    def __enter__(self):
+        if self.tm is not None:
+            self.L.orc_set_triangle_materials(self.tm.ctypes.data, len(self.tm))
+        if self.imgs is not None:
+            self.L.orc_set_textures(C.cast(self.imgs, C.c_void_p), len(self.imgs))
+        self.L.orc_set_mesh_light_pick(int(self.pick))
+
+    def __exit__(self, *exc):
+        self.L.orc_set_triangle_materials(None, 0)
+        self.L.orc_set_textures(None, 0)
+        self.L.orc_set_mesh_light_pick(1)
+
+
+BRANCHES = None
+
+
+def branch_counts(reset=False, libm=False):
+    """visits of traceMISLight's branches (oracle.h: orc_branch) since the last reset -> {name: count}"""
+    global BRANCHES
+    L = lib(libm)
+    if BRANCHES is None:
+        BRANCHES = []
+        while L.orc_debug_branch_name(len(BRANCHES)):
+            BRANCHES.append(L.orc_debug_branch_name(len(BRANCHES)).decode())
+    out = np.zeros(len(BRANCHES), dtype=np.uint64)
+    L.orc_debug_branch_counts(out.ctypes.data, 1 if reset else 0)
+    return dict(zip(BRANCHES, (int(c) for c in out)))
 
 
 def shard_seed(seed, sample_group):
@@ -252,11 +318,12 @@ class Sppm:
         self.W, self.H = width, height
         self._h = lib().orc_sppm_create(width, height, photon_seed)
 
-    def frames(self, scene_view, camera, rng, accum, n_frames=1, env=(0.0, 0.0, 0.0)):
+    def frames(self, scene_view, camera, rng, accum, n_frames=1, env=(0.0, 0.0, 0.0), triangle_materials=None, textures=None):
         assert rng.dtype == np.uint32 and rng.shape == (self.H, self.W, 4) and rng.flags.c_contiguous
         assert accum.dtype == np.float32 and accum.shape == (self.H, self.W, 4) and accum.flags.c_contiguous
-        lib().orc_sppm_frames(self._h, C.byref(scene_view), C.byref(camera), (C.c_float * 3)(*env), rng.ctypes.data,
-                              accum.ctypes.data, n_frames)
+        with _features(lib(), triangle_materials, textures):
+            lib().orc_sppm_frames(self._h, C.byref(scene_view), C.byref(camera), (C.c_float * 3)(*env), rng.ctypes.data,
+                                  accum.ctypes.data, n_frames)
 
     def download(self):
         n = abi.PHOTON_HASHN

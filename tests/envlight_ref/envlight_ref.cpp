@@ -1,7 +1,7 @@
 // envlight_ref.cpp -- CPU restatement of the environment map as a light (TRC_FLAG_ENV_LIGHT, include/tracer_abi.h): the cell
 // weights, Vose's alias tables in their stated order, the sampler and the pdf of tracer_amd/csrc/dev_envlight.hpp and
 // trc_envlight.hip, written again from the statement with trc_detmath.h's elementary functions (the same bits as the kernels').
-// Built by envlight_loader.py with -ffp-contract=off.
+// Built into the oracle library (oracle/Makefile, -ffp-contract=off), where the oracle's traceMISLight and envlight_loader.py find it.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>

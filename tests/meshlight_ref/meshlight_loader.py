@@ -1,5 +1,5 @@
-"""Builds tests/meshlight_ref/meshlight_ref.cpp (the CPU restatement of TRC_FLAG_MESH_LIGHTS' light set, tables and sampler) into a
-directory of the caller's and wraps it."""
+"""Wraps tests/meshlight_ref/meshlight_ref.cpp (the CPU restatement of TRC_FLAG_MESH_LIGHTS' light set, tables and sampler), which the
+oracle library links in (oracle/Makefile)."""
 import ctypes as C
 import os
 import subprocess
@@ -42,10 +42,15 @@ class Ref:
         return tri, out
 
 
-def build(out_dir):
-    so = os.path.join(str(out_dir), "libmeshlight_ref.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I", os.path.join(ROOT, "include"),
-                           "-o", so, os.path.join(ROOT, "tests", "meshlight_ref", "meshlight_ref.cpp")])
+def build():
+    """the restatement as the oracle library holds it (oracle/Makefile links tests/meshlight_ref/meshlight_ref.cpp into liboracle.so: one CPU
+    statement, one build of it).  make runs every time -- it does nothing when the library is newer than its sources -- so an edit of the
+    restatement is never answered from a stale library; TRC_ORACLE_DIR names a build of somebody else's making (the sanitized one)."""
+    if os.environ.get("TRC_ORACLE_DIR"):
+        so = os.path.join(os.environ["TRC_ORACLE_DIR"], "liboracle.so")
+    else:
+        so = os.path.join(ROOT, "oracle", "liboracle.so")
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"], stdout=subprocess.DEVNULL)
     L = C.CDLL(so)
     vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
     L.meshlight_ref_tables.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(u32)]

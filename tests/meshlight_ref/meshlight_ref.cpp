@@ -1,6 +1,6 @@
 // meshlight_ref.cpp -- CPU restatement of the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS, include/tracer_abi.h): the
 // light set, the weights, Vose's alias table in its stated order, pdfA and the sampler of tracer_amd/csrc/dev_meshlight.hpp and
-// trc_meshlight.hip, written again from the statement (the same bits as the kernels').  Built by meshlight_loader.py with
+// trc_meshlight.hip, written again from the statement (the same bits as the kernels').  Built into the oracle library (oracle/Makefile), where the oracle's traceMISLight and meshlight_loader.py find it, with
 // -ffp-contract=off.
 #include <cfloat>
 #include <cmath>

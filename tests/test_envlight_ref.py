@@ -13,8 +13,8 @@ import envlight_loader as el  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return el.build(tmp_path_factory.mktemp("envlight_ref"))
+def ref():
+    return el.build()
 
 
 def alias_probabilities(tab):

@@ -19,8 +19,8 @@ F = np.float32
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return el.build(tmp_path_factory.mktemp("envlight_ref"))
+def ref():
+    return el.build()
 
 
 @pytest.fixture(scope="module")
@@ -135,7 +135,8 @@ def test_refused_combinations(gpu):
 
 @pytest.mark.parametrize("residence", ["lds", "mem"])
 def test_black_map_equals_flag_off(gpu, residence):
-    """p_env = 0: every draw and operation of the flag-off kernel (one-wavefront, strips, and on the mesh scene persistent workgroups)"""
+    """p_env = 0: every draw and operation of the flag-off kernel (one-wavefront workgroups and on the mesh scene persistent
+    workgroups; a 96 x 64 frame is too small for a strip launch at any spp: tests/test_gpu_light_oracle.py forces those)"""
     mesh = host.Mesh.ball(24, 24, 1.0) if residence == "mem" else None
     sc = host.HostScene(abi.SCENE_CORNELL_MESH if residence == "mem" else abi.SCENE_CORNELL_SPHERES, mesh)
     black = np.zeros((16, 32, 3), F)

@@ -24,8 +24,8 @@ EMITTER, LAMBERT = 3, 4            # Cornell's material table: the lamp (Diffuse
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return ml.build(tmp_path_factory.mktemp("meshlight_ref"))
+def ref():
+    return ml.build()
 
 
 @pytest.fixture(scope="module")
@@ -190,7 +190,8 @@ def test_refused_combinations(mgpu):
 # ------------------------------------------------------------------------------------------- 3. no light triangle: the flag-off frame
 @pytest.mark.parametrize("name", ["ball", "bigball"])
 def test_no_light_triangle_equals_flag_off(mgpu, name):
-    """p_mesh = 0: every draw and operation of the flag-off kernel (one-wavefront, strips, and on 'bigball' persistent workgroups), with the
+    """p_mesh = 0: every draw and operation of the flag-off kernel (one-wavefront workgroups and on 'bigball' persistent workgroups; a
+    96 x 64 frame is too small for a strip launch at any spp: tests/test_gpu_light_oracle.py forces those), with the
     triangles at material 19 and with an array that names no emitter; then knob mesh_light_pick = 0 where the only emitters are squares"""
     sc = cornell_mesh(name)
     n = sc.view.n_index // 3

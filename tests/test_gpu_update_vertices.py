@@ -164,9 +164,9 @@ def test_triangle_materials_survive(gpu):
     gpu.upload_triangle_materials(None)
 
 
-def test_mesh_light_tables_follow_the_vertices(tmp_path):
+def test_mesh_light_tables_follow_the_vertices():
     import meshlight_loader as ml
-    ref = ml.build(tmp_path)
+    ref = ml.build()
     sc = scene("lds")
     n = sc.view.n_index // 3
     tri_mat = np.full(n, 4, np.uint32); tri_mat[n // 2:n // 2 + 6] = 3   # Cornell's table: 3 = the lamp's emitter, 4 = the red Lambert

@@ -16,8 +16,8 @@ MAT_DIFFUSE, MAT_LAMBERT = 0, 1
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    return ml.build(tmp_path_factory.mktemp("meshlight_ref"))
+def ref():
+    return ml.build()
 
 
 def random_mesh(rng, n, n_mat=6):

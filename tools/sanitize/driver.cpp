@@ -76,6 +76,38 @@ static void build_and_render(bool second_thread) {
                                                           (unsigned long long)st.rays, (unsigned long long)st1.rays, diff, acc.size());
             EXPECT(diff == 0);
         }
+        // the oracle's statement of the project's own features (oracle.h): random per-triangle materials with emitters among them, an
+        // image on every non-emitter material, then traceMIS with the environment map and with the mesh's triangles as lights, 8 workers
+        {
+            const uint32_t n_tri = sc.n_index / 3;
+            std::vector<uint32_t> tri_mat(n_tri);
+            for (uint32_t t = 0; t < n_tri; ++t) tri_mat[t] = (t * 2654435761u >> 8) % sc.n_material;
+            std::vector<trc_Material> mats(sc.materials, sc.materials + sc.n_material);
+            std::vector<float> texels(3 * 5 * 3), map(3 * 16 * 8, 0.0f);
+            for (size_t k = 0; k < texels.size(); ++k) texels[k] = (float)(k % 7) / 7.0f;
+            for (size_t k = 0; k < map.size(); ++k) map[k] = k % 5 == 0 ? 0.0f : (float)(k % 11);
+            const trc_image img = {5, 3, texels.data()};
+            for (auto& m : mats) if (m.type != TRC_MAT_DIFFUSE) { m.textureInfo.type = TRC_TEX_IMAGE; m.textureInfo.textureIndex = 0; }
+            trc_scene tex = sc;
+            tex.materials = mats.data();
+            orc_set_triangle_materials(tri_mat.data(), n_tri);
+            orc_set_textures(&img, 1);
+            orc_set_environment_map(16, 8, map.data());
+            for (uint32_t flag : {(uint32_t)TRC_FLAG_ENV_LIGHT, (uint32_t)TRC_FLAG_MESH_LIGHTS}) {
+                std::vector<uint32_t> rng((size_t)W * H * 4);
+                std::vector<float> acc((size_t)W * H * 4, 0.0f);
+                trc_host_fill_rng(11, W, H, rng.data());
+                trc_params prm; std::memset(&prm, 0, sizeof prm);
+                prm.spp = 4; prm.max_depth = 8; prm.integrator = TRC_INTEGRATOR_MIS; prm.tile_nranks = 1; prm.flags = flag;
+                trc_stats st; std::memset(&st, 0, sizeof st);
+                orc_render(&tex, &cam, env, W, H, rng.data(), acc.data(), &prm, &st, 8);
+                EXPECT(st.paths == (uint64_t)W * H * 4 && st.rays > st.paths);
+            }
+            uint64_t visits[ORC_BRANCH_COUNT];
+            orc_debug_branch_counts(visits, 1);
+            EXPECT(visits[ORC_BR_PICK_LIGHT] > 0 && visits[ORC_BR_SUPPORT] > 0);
+            orc_set_triangle_materials(nullptr, 0); orc_set_textures(nullptr, 0); orc_set_environment_map(0, 0, nullptr);
+        }
         // LBVH oracle on the leaves
         const uint32_t n_leaves = (sc.n_bvh + 1) / 2;
         std::vector<trc_BVH> out(2 * (size_t)n_leaves - 1);

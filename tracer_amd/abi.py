@@ -216,6 +216,16 @@ DENOISE_ALBEDO_EPS = 0.001
 DENOISE_MAX_ITERATIONS = 5
 
 
+class KernelChoice(C.Structure):
+    """trc_kernel_choice (tracer_test_hooks.h)"""
+    _fields_ = [("shape", C.c_uint32), ("variant", C.c_uint32), ("lds_resident", C.c_uint32), ("triangle_materials", C.c_uint32),
+                ("strip", C.c_uint32), ("launches", C.c_uint32)]
+
+
+KERNEL_SHAPES = ("one", "strip", "pwg", "dense")                                                  # trc_kernel_choice.shape
+KERNEL_VARIANTS = ("plain", "stats", "sobol", "tex", "env", "env_tex", "mesh", "mesh_tex")         # ... .variant (RenderVariant)
+
+
 class LaunchShape(C.Structure):
     """trc_launch_shape"""
     _fields_ = [("entries", C.c_uint32), ("wave_slots", C.c_uint32), ("longest_entry_ms", C.c_double),
@@ -254,7 +264,7 @@ DEVICE_SYMBOLS = [
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
-                "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test"]
+                "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test", "trc_debug_last_kernel"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",

@@ -938,7 +938,7 @@ trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value) {
               : k == "no_plan_reuse" ? &ctx->knobs.no_plan_reuse : k == "no_coalesce" ? &ctx->knobs.no_coalesce : k == "no_dense" ? &ctx->knobs.no_dense : k == "head_stages" ? &ctx->knobs.head_stages : k == "descend_min" ? &ctx->knobs.descend_min
               : k == "camera_policy" ? &ctx->knobs.camera_policy : k == "no_primary_replay" ? &ctx->knobs.no_primary_replay
               : k == "replay_min_lanes" ? &ctx->knobs.replay_min_lanes : k == "replay_chain" ? &ctx->knobs.replay_chain
-              : k == "mesh_light_pick" ? &ctx->knobs.mesh_light_pick : nullptr;
+              : k == "mesh_light_pick" ? &ctx->knobs.mesh_light_pick : k == "strip_force" ? &ctx->knobs.strip_force : nullptr;
     if (!slot) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_debug_set: unknown knob " + k);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // a launch in flight keeps the plan it was made with

@@ -227,6 +227,10 @@ struct trc_ctx {
     bool cost_quarters = false;         // d_block_cost / d_split describe a launch made with cost_stride 4
     bool cost_valid = false; uint32_t cost_strip = 1;
     uint32_t last_cost_div = 0, last_wave_slots = 0;     // of the last render launch (trc_debug_launch_shape)
+    // what choose_kernel (trc_render_pass.hip) decided for the last render launch (trc_debug_last_kernel, tracer_test_hooks.h): the
+    // launch shape (0 one block per one-wavefront workgroup, 1 strips, 2 persistent workgroups, 3 k_render_dense), the RenderVariant,
+    // whether the whole tree was staged in LDS, whether the per-triangle-material twins ran, and the strip length; launches counted
+    struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0; } last_kernel;
     trc_params deferred{}; bool has_deferred = false; uint64_t deferred_calls = 0;   // a launch of few samples kept for coalescing (trc_render)
     int cost_head_age = 0;                    // 1: the costs are a cold head's (trc_render), 2: the launch after it ran on them
     bool cost_fresh_next = false;             // the next ordered launch takes the last launch's raw durations as its costs (trc_set_camera, policy 2)
@@ -280,7 +284,7 @@ struct trc_ctx {
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
-    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1, refit_single = 0; } knobs;
+    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1, refit_single = 0, strip_force = 0; } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;

@@ -98,6 +98,16 @@ trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv
     return ts;
 }
 
+// the kernel choice of the last render launch (trc_render_pass.hip: choose_kernel)
+trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out) {
+    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    if (!ctx || !out) return TRC_ERR_INVALID_ARG;
+    const trc_ctx::LastKernel& k = ctx->last_kernel;
+    out->shape = k.shape; out->variant = k.variant; out->lds_resident = k.lds_resident; out->triangle_materials = k.tri_materials;
+    out->strip = k.strip; out->launches = k.count;
+    return TRC_OK;
+}
+
 trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t n, float* fast, float* plain) {
     if (!ctx || (n && (!a || !b || !fast || !plain))) return TRC_ERR_INVALID_ARG;
     if (n == 0) return TRC_OK;

@@ -274,6 +274,9 @@ static trc_status launch_geometry(trc_ctx* ctx, const trc_params* p, RenderLaunc
         const uint32_t slots = (uint32_t)ctx->cu_count * 16u;
         const uint32_t room = ctx->n_tiles / (slots + slots / 2u);          // keep >= 1.5 workgroups per slot
         kp.strip = std::max(1u, std::min(want, room));
+        // test knob: exactly this many blocks per wavefront whatever the room (a frame of a few blocks runs the strip kernels: the
+        // cap above is a matter of speed, the kernels bound every strip by the block list themselves)
+        if (ctx->knobs.strip_force > 0) kp.strip = std::min((uint32_t)ctx->knobs.strip_force, std::max(1u, ctx->n_tiles));
     }
     r.quarters_ok = kp.strip == 1 && blk_shift == 3;
     kp.cost_stride = r.quarters_ok ? kCostSlots : 1u;
@@ -336,6 +339,12 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
                                         : ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
     if (!r.kern.fn) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
+    ctx->last_kernel.shape = r.dense ? 3u : r.pwg ? 2u : kp.strip > 1 ? 1u : 0u;                 // trc_debug_last_kernel
+    ctx->last_kernel.variant = r.dense ? (uint32_t)kVariantPlain : (uint32_t)variant;
+    ctx->last_kernel.lds_resident = ctx->lds_scene ? 1u : 0u;
+    ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
+    ctx->last_kernel.strip = kp.strip;
+    ctx->last_kernel.count++;
     if (mem_plan && !r.pwg) plan_launch_lds(ctx, kp.ks.sc, (uint32_t)r.kern.waves, hybrid_stack(integrator));
     r.lds = r.pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)r.pwg_waves * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
                   : dyn_lds_bytes(kp.ks.sc, r.stats) + (r.dense ? (size_t)park_rows * kBlock * 4 : 0u);

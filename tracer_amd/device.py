@@ -132,6 +132,7 @@ def _load(path, hooks=False):
         L.trc_env_light_test.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp]
         L.trc_debug_mesh_light_tables.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(u32)]
         L.trc_mesh_light_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+        L.trc_debug_last_kernel.argtypes = [vp, C.POINTER(abi.KernelChoice)]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -533,6 +534,15 @@ class Tracer:
     def debug_set(self, knob, value):
         """A/B and test knobs of this context (trc_debug_set): scheduling only, never a pixel."""
         self._check(self._L.trc_debug_set(self._h, knob.encode(), int(value)), "trc_debug_set")
+
+    def last_kernel(self):
+        """hooks build only: which render kernel the last launch took (trc_debug_last_kernel) -> dict of shape ("one", "strip", "pwg",
+        "dense"), variant ("plain", "stats", "sobol", "tex", "env", "env_tex", "mesh", "mesh_tex"), lds_resident, triangle_materials
+        (bools), strip (blocks per wavefront) and launches (kernel choices since the context was made)."""
+        k = abi.KernelChoice()
+        self._check(self._L.trc_debug_last_kernel(self._h, C.byref(k)), "trc_debug_last_kernel")
+        return dict(shape=abi.KERNEL_SHAPES[k.shape], variant=abi.KERNEL_VARIANTS[k.variant], lds_resident=bool(k.lds_resident),
+                    triangle_materials=bool(k.triangle_materials), strip=int(k.strip), launches=int(k.launches))
 
     def div_by_test(self, a, b):
         """(fast, plain): 3 quotients per operand pair through the guarded shared-divisor division and through `/`."""
