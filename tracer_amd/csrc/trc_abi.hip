@@ -108,17 +108,14 @@ trc_status trc_repack_triangles(trc_ctx* ctx, const trc_scene* s, const DScene& 
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_verts, (size_t)s->n_vertex * sizeof(trc_TriangleVertex)));
     if (hipMalloc((void**)&ctx->d_idx, (size_t)s->n_index * 4) != hipSuccess) { trc_refit_free(ctx); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc triangle indices"); }
     ctx->n_vertex = s->n_vertex;
-    trc_status st = TRC_OK;
-    do {
-        if (trc_copy_to_device(ctx, ctx->d_verts, s->triList, (size_t)s->n_vertex * sizeof(trc_TriangleVertex), ctx->stream) != TRC_OK ||
-            trc_copy_to_device(ctx, ctx->d_idx, s->idxList, (size_t)s->n_index * 4, ctx->stream) != TRC_OK) { st = trc_fail(ctx, TRC_ERR_HIP, "H2D triangles"); break; }
-        hipLaunchKernelGGL(k_repack_triangles, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri,
-                           reinterpret_cast<float4*>(d_blob + sc.off_tripos), reinterpret_cast<float4*>(d_blob + sc.off_triattr));
-        if (d_tri_leaves) hipLaunchKernelGGL(k_triangle_leaves, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri, d_tri_leaves);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, "k_repack_triangles"); break; }
-    } while (0);
-    if (st != TRC_OK) trc_refit_free(ctx);
-    return st;
+    auto failed = [&](const char* what) { trc_refit_free(ctx); return trc_fail(ctx, TRC_ERR_HIP, what); };      // the kept arrays belong to the context: freed first
+    if (trc_copy_to_device(ctx, ctx->d_verts, s->triList, (size_t)s->n_vertex * sizeof(trc_TriangleVertex), ctx->stream) != TRC_OK ||
+        trc_copy_to_device(ctx, ctx->d_idx, s->idxList, (size_t)s->n_index * 4, ctx->stream) != TRC_OK) return failed("H2D triangles");
+    hipLaunchKernelGGL(k_repack_triangles, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri,
+                       reinterpret_cast<float4*>(d_blob + sc.off_tripos), reinterpret_cast<float4*>(d_blob + sc.off_triattr));
+    if (d_tri_leaves) hipLaunchKernelGGL(k_triangle_leaves, dim3((n_tri + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_verts, ctx->d_idx, n_tri, d_tri_leaves);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return failed("k_repack_triangles");
+    return TRC_OK;
 }
 
 // the counters' rows (stat_row) summed into one row
@@ -129,7 +126,12 @@ __global__ void __launch_bounds__(64) k_stats_sum(const unsigned long long* rows
     for (uint32_t r = 0; r < kStatRows; ++r) v += rows[(size_t)r * kStatRowStride + c];
     sum[c] = v;
 }
-void trc_launch_stats_sum(trc_ctx* ctx) { hipLaunchKernelGGL(k_stats_sum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_stats, ctx->d_stats_sum); }
+trc_status trc_read_stats_sum(trc_ctx* ctx, unsigned long long* h, size_t count) {
+    hipLaunchKernelGGL(k_stats_sum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_stats, ctx->d_stats_sum);
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, count * sizeof *h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TRC_OK;
+}
 
 // ---- output stage (fragmentShader, Render.metal:29-75): exposure sums, then ACES to 8 bit
 __global__ void __launch_bounds__(256) k_tonemap_sum(const float4* accum, uint32_t n, unsigned long long* sums /* [3] */) {
@@ -220,54 +222,46 @@ __global__ void __launch_bounds__(kBlock) k_trace(const KTrace kp) {
 // stream is in order, so the first unfinished pair ends the scan).  Called from trc_render, so a host that never
 // synchronises through trc_synchronize / trc_get_stats (one launch + one download per frame, the reference's own
 // pattern) keeps a bounded list.
-void trc_collect_finished_events(trc_ctx* ctx) {
+using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+static void collect_finished(trc_ctx* ctx, EventPairs& list, double& ms_sum) {
     size_t done = 0;
-    for (; done < ctx->pending.size(); ++done) {
-        const hipError_t q = hipEventQuery(ctx->pending[done].second);
+    for (; done < list.size(); ++done) {
+        const hipError_t q = hipEventQuery(list[done].second);
         if (q == hipErrorNotReady) { (void)hipGetLastError(); break; }      // "not ready" is reported through the sticky error too
         if (q != hipSuccess) break;                                        // a real error stays for the caller's next check
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ctx->pending[done].first, ctx->pending[done].second) == hipSuccess) ctx->kernel_ms += ms;
-        ctx->event_pool.push_back(ctx->pending[done].first);
-        ctx->event_pool.push_back(ctx->pending[done].second);
+        if (hipEventElapsedTime(&ms, list[done].first, list[done].second) == hipSuccess) ms_sum += ms;
+        ctx->event_pool.push_back(list[done].first);
+        ctx->event_pool.push_back(list[done].second);
     }
-    ctx->pending.erase(ctx->pending.begin(), ctx->pending.begin() + (ptrdiff_t)done);
-    for (done = 0; done < ctx->pending_sched.size(); ++done) {                 // the launch-list kernels' pairs: schedule_ms
-        const hipError_t q = hipEventQuery(ctx->pending_sched[done].second);
-        if (q == hipErrorNotReady) { (void)hipGetLastError(); break; }
-        if (q != hipSuccess) break;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ctx->pending_sched[done].first, ctx->pending_sched[done].second) == hipSuccess) ctx->schedule_ms += ms;
-        ctx->event_pool.push_back(ctx->pending_sched[done].first);
-        ctx->event_pool.push_back(ctx->pending_sched[done].second);
-    }
-    ctx->pending_sched.erase(ctx->pending_sched.begin(), ctx->pending_sched.begin() + (ptrdiff_t)done);
+    list.erase(list.begin(), list.begin() + (ptrdiff_t)done);
+}
+void trc_collect_finished_events(trc_ctx* ctx) {
+    collect_finished(ctx, ctx->pending, ctx->kernel_ms);
+    collect_finished(ctx, ctx->pending_sched, ctx->schedule_ms);      // the launch-list kernels' pairs
 }
 
 namespace {
 
-// drains finished per-launch event pairs into kernel_ms (call after a stream sync)
+// drains every per-launch event pair into kernel_ms / schedule_ms (call after a stream sync)
 void collect_events(trc_ctx* ctx) {
-    for (auto& pr : ctx->pending) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ctx->kernel_ms += ms;
-        ctx->event_pool.push_back(pr.first);
-        ctx->event_pool.push_back(pr.second);
-    }
-    ctx->pending.clear();
-    for (auto& pr : ctx->pending_sched) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ctx->schedule_ms += ms;
-        ctx->event_pool.push_back(pr.first);
-        ctx->event_pool.push_back(pr.second);
-    }
-    ctx->pending_sched.clear();
+    auto drain = [&](EventPairs& list, double& ms_sum) {
+        for (auto& pr : list) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ms_sum += ms;
+            ctx->event_pool.push_back(pr.first);
+            ctx->event_pool.push_back(pr.second);
+        }
+        list.clear();
+    };
+    drain(ctx->pending, ctx->kernel_ms);
+    drain(ctx->pending_sched, ctx->schedule_ms);
 }
 
 // Repack the reference arrays into the device layout (dev_scene.hpp) and validate the tree.
 trc_status build_blob(trc_ctx* ctx, const trc_scene* s, std::vector<uint32_t>& blob, uint64_t& blob_total, KScene& ks) {
     if (!s || !s->bvhList || s->n_bvh < 3 || (s->n_bvh & 1u) == 0) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "scene: need >= 2 leaves (n_bvh odd, >= 3)");
-    { trc_status st = validate_primitives(ctx, s); if (st != TRC_OK) return st; }
+    TRC_TRY(validate_primitives(ctx, s));
     const trc_BVH* nodes = s->bvhList;
     const uint32_t n = s->n_bvh;
     if (nodes[0].pType != TRC_PRIM_BVH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "bvh: root is not an interior node");
@@ -292,8 +286,7 @@ trc_status build_blob(trc_ctx* ctx, const trc_scene* s, std::vector<uint32_t>& b
                 order.push_back(c);
             } else {
                 max_leaf_depth = std::max(max_leaf_depth, depth_of[c]);
-                trc_status st = validate_leaf(ctx, s, nodes[c]);
-                if (st != TRC_OK) return st;
+                TRC_TRY(validate_leaf(ctx, s, nodes[c]));
             }
         }
     }
@@ -303,7 +296,7 @@ trc_status build_blob(trc_ctx* ctx, const trc_scene* s, std::vector<uint32_t>& b
     const uint32_t n_interior = (uint32_t)order.size();
     DScene sc{};
     uint64_t total = 0;
-    { trc_status st = layout_scene(ctx, s, n_interior, sc, total); if (st != TRC_OK) return st; }
+    TRC_TRY(layout_scene(ctx, s, n_interior, sc, total));
     plan_lds(sc, max_leaf_depth, true);
     blob.assign((size_t)sc.off_tripos, 0u);      // analytic primitives, materials, fat nodes; triangle records are made on the device
     blob_total = total;
@@ -350,7 +343,7 @@ static trc_status xfer_ready(trc_ctx* ctx) {
 }
 trc_status trc_copy_to_host(trc_ctx* ctx, void* host, const void* dev, size_t bytes, hipStream_t st) {
     if (bytes == 0) return TRC_OK;
-    { const trc_status rs = xfer_ready(ctx); if (rs != TRC_OK) return rs; }
+    TRC_TRY(xfer_ready(ctx));
     size_t prev_off = 0, prev_n = 0;
     int slot = 0;
     for (size_t off = 0; off < bytes; off += kXferChunk, slot ^= 1) {
@@ -369,7 +362,7 @@ trc_status trc_copy_to_host(trc_ctx* ctx, void* host, const void* dev, size_t by
 }
 trc_status trc_copy_to_device(trc_ctx* ctx, void* dev, const void* host, size_t bytes, hipStream_t st) {
     if (bytes == 0) return TRC_OK;
-    { const trc_status rs = xfer_ready(ctx); if (rs != TRC_OK) return rs; }
+    TRC_TRY(xfer_ready(ctx));
     int slot = 0;
     bool used[2] = {false, false};
     for (size_t off = 0; off < bytes; off += kXferChunk, slot ^= 1) {
@@ -428,6 +421,36 @@ static void release_textures(trc_ctx* ctx) {
     ctx->d_tex_texels = nullptr; ctx->d_tex_desc = nullptr; ctx->n_tex = 0;
 }
 
+// The knobs (trc_ctx::Knobs) by name, each once: what trc_debug_set calls it, its member, and the environment variable trc_create reads
+// its default from (null: none) -- a flag (1 when the variable is present) or a number (max(0, atoi)).  The list in tracer_abi.h
+// (trc_debug_set) describes them to a caller.
+struct KnobEntry { const char* name; int trc_ctx::Knobs::*slot; const char* env; bool env_flag; };
+static const KnobEntry kKnobs[] = {
+    {"no_lds_fit", &trc_ctx::Knobs::no_lds_fit, "TRC_NO_LDS_FIT", true},
+    {"stack_lds_levels", &trc_ctx::Knobs::stack_lds_levels, "TRC_STACK_LDS_LEVELS", false},
+    {"strip_len", &trc_ctx::Knobs::strip_len, "TRC_STRIP_LEN", false},
+    {"no_pwg", &trc_ctx::Knobs::no_pwg, "TRC_NO_PWG", true},
+    {"sppm_serial_camera", &trc_ctx::Knobs::sppm_serial_camera, "TRC_SPPM_SERIAL_CAMERA", true},
+    {"sppm_timing", &trc_ctx::Knobs::sppm_timing, nullptr, false},
+    {"force_blk_shift", &trc_ctx::Knobs::force_blk_shift, nullptr, false},
+    {"no_split", &trc_ctx::Knobs::no_split, nullptr, false},
+    {"no_cost_filter", &trc_ctx::Knobs::no_cost_filter, "TRC_NO_COST_FILTER", true},
+    {"no_cold_probe", &trc_ctx::Knobs::no_cold_probe, "TRC_NO_COLD_PROBE", true},
+    {"probe_spp", &trc_ctx::Knobs::probe_spp, "TRC_PROBE_SPP", false},
+    {"no_plan_reuse", &trc_ctx::Knobs::no_plan_reuse, "TRC_NO_PLAN_REUSE", true},
+    {"no_coalesce", &trc_ctx::Knobs::no_coalesce, "TRC_NO_COALESCE", true},
+    {"no_dense", &trc_ctx::Knobs::no_dense, "TRC_NO_DENSE", true},
+    {"head_stages", &trc_ctx::Knobs::head_stages, "TRC_HEAD_STAGES", false},
+    {"descend_min", &trc_ctx::Knobs::descend_min, nullptr, false},
+    {"camera_policy", &trc_ctx::Knobs::camera_policy, nullptr, false},
+    {"no_primary_replay", &trc_ctx::Knobs::no_primary_replay, nullptr, false},
+    {"replay_min_lanes", &trc_ctx::Knobs::replay_min_lanes, nullptr, false},
+    {"replay_chain", &trc_ctx::Knobs::replay_chain, nullptr, false},
+    {"mesh_light_pick", &trc_ctx::Knobs::mesh_light_pick, nullptr, false},
+    {"refit_single", &trc_ctx::Knobs::refit_single, nullptr, false},
+    {"strip_force", &trc_ctx::Knobs::strip_force, nullptr, false},
+};
+
 // ======================================================================= C ABI
 extern "C" {
 
@@ -471,24 +494,8 @@ trc_status trc_create(int device, trc_ctx** out) {
     ctx->device = device;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) ctx->cu_count = cus; }
     if (ctx->cu_count <= 0) ctx->cu_count = 256;
-    {
-        auto env_int = [](const char* name, bool flag) {
-            const char* v = std::getenv(name);
-            return !v ? 0 : flag ? 1 : std::max(0, std::atoi(v));
-        };
-        ctx->knobs.no_lds_fit = env_int("TRC_NO_LDS_FIT", true);
-        ctx->knobs.stack_lds_levels = env_int("TRC_STACK_LDS_LEVELS", false);
-        ctx->knobs.strip_len = env_int("TRC_STRIP_LEN", false);
-        ctx->knobs.no_pwg = env_int("TRC_NO_PWG", true);
-        ctx->knobs.sppm_serial_camera = env_int("TRC_SPPM_SERIAL_CAMERA", true);
-        ctx->knobs.no_cost_filter = env_int("TRC_NO_COST_FILTER", true);
-        ctx->knobs.no_cold_probe = env_int("TRC_NO_COLD_PROBE", true);
-        ctx->knobs.probe_spp = env_int("TRC_PROBE_SPP", false);
-        ctx->knobs.no_plan_reuse = env_int("TRC_NO_PLAN_REUSE", true);
-        ctx->knobs.no_coalesce = env_int("TRC_NO_COALESCE", true);
-        ctx->knobs.no_dense = env_int("TRC_NO_DENSE", true);
-        ctx->knobs.head_stages = env_int("TRC_HEAD_STAGES", false);
-    }
+    for (const KnobEntry& k : kKnobs)
+        if (const char* v = k.env ? std::getenv(k.env) : nullptr) ctx->knobs.*k.slot = k.env_flag ? 1 : std::max(0, std::atoi(v));
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void**)&ctx->d_stats, sizeof(unsigned long long) * kStatRows * kStatRowStride) != hipSuccess ||
         hipMalloc((void**)&ctx->d_stats_sum, sizeof(unsigned long long) * kStatRowStride) != hipSuccess ||
@@ -527,20 +534,19 @@ void trc_destroy(trc_ctx* ctx) {
 }
 
 trc_status trc_upload_scene(trc_ctx* ctx, const trc_scene* scene) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> blob;
     uint64_t blob_total = 0;
     KScene ks{};
-    trc_status st = build_blob(ctx, scene, blob, blob_total, ks);
-    if (st != TRC_OK) return st;
+    TRC_TRY(build_blob(ctx, scene, blob, blob_total, ks));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     trc_scene_changed(ctx, kSceneReplaced);      // another scene: the old one goes, with everything derived from it
     ctx->blob_bytes = (size_t)blob_total * 4;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_blob, blob.data(), blob.size() * 4, ctx->stream); if (cs != TRC_OK) return cs; }
-    { trc_status rs = trc_repack_triangles(ctx, scene, ks.sc, ctx->d_blob, nullptr); if (rs != TRC_OK) return rs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_blob, blob.data(), blob.size() * 4, ctx->stream));
+    TRC_TRY(trc_repack_triangles(ctx, scene, ks.sc, ctx->d_blob, nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ks.sc.blob = ctx->d_blob;
     ctx->ks = ks;
@@ -552,7 +558,7 @@ trc_status trc_upload_scene(trc_ctx* ctx, const trc_scene* scene) {
 }
 
 trc_status trc_upload_density(trc_ctx* ctx, const trc_GridDensityInfo* info, const float* density) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -562,7 +568,7 @@ trc_status trc_upload_density(trc_ctx* ctx, const trc_GridDensityInfo* info, con
     const uint64_t count = (uint64_t)info->nx * info->ny * info->nz;
     if (count > (1ull << 31)) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_upload_density: more than 2^31 cells");
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_density, count * sizeof(float)));
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_density, density, count * sizeof(float), ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_density, density, count * sizeof(float), ctx->stream));
     // occupancy of 4x4x4 bricks: brick b covers lookups whose base cell i = floor(p*n - 0.5) has (i + 1) >> 2 == b, i.e.
     // the cells 4b-1 .. 4b+3 and their +1 neighbours; nonzero = any of them holds a value other than +0
     const int nx = (int)info->nx, ny = (int)info->ny, nz = (int)info->nz;
@@ -580,14 +586,14 @@ trc_status trc_upload_density(trc_ctx* ctx, const trc_GridDensityInfo* info, con
                         for (int bx = x >> 2; bx <= (x + 1) >> 2; ++bx) occ[((size_t)bz * nby + by) * nbx + bx] = 1;
             }
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_occupancy, occ.size()));
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_occupancy, occ.data(), occ.size(), ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_occupancy, occ.data(), occ.size(), ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->dinfo = *info;
     return TRC_OK;
 }
 
 trc_status trc_set_camera(trc_ctx* ctx, const trc_Camera* c) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !c) return TRC_ERR_INVALID_ARG;
     const DCamera before = ctx->cam;
     DCamera& d = ctx->cam;
@@ -631,7 +637,7 @@ trc_status trc_set_camera(trc_ctx* ctx, const trc_Camera* c) {
 }
 
 trc_status trc_set_environment(trc_ctx* ctx, const float rgb[3]) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !rgb) return TRC_ERR_INVALID_ARG;
     ctx->ambient[0] = rgb[0]; ctx->ambient[1] = rgb[1]; ctx->ambient[2] = rgb[2];
     trc_picture_changed(ctx);
@@ -639,7 +645,7 @@ trc_status trc_set_environment(trc_ctx* ctx, const float rgb[3]) {
 }
 
 trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const float* rgb) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -649,7 +655,7 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
     if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 28)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_set_environment_map: bad size");
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_envmap, bytes));
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_envmap, rgb, bytes, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_envmap, rgb, bytes, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->env_w = w; ctx->env_h = h;
     return TRC_OK;
@@ -658,7 +664,7 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
 // image textures: all images in one pool of RGB float texels (3 per texel, each image's rows bottom-up, the layout the caller
 // gives), and a descriptor {first texel, w, h, 0} per image; hit_color<true> (dev_integrator.hpp) reads both
 trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (n && !images) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_textures: images == NULL");
     uint64_t total = 0;
@@ -700,7 +706,7 @@ trc_status trc_upload_textures(trc_ctx* ctx, const trc_image* images, uint32_t n
 
 // per-triangle materials: dword 15 of the triangle attribute records (dev_scene.hpp), which every scene upload sets to 19
 trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material, uint32_t n_triangles) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_upload_triangle_materials: no scene");
     const DScene& sc = ctx->ks.sc;
@@ -713,16 +719,14 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (sc.n_triangles) {
-        uint32_t* d_mat = nullptr;
-        if (material) HIP_TRY(ctx, hipMalloc((void**)&d_mat, (size_t)sc.n_triangles * 4));
-        trc_status st = material ? trc_copy_to_device(ctx, d_mat, material, (size_t)sc.n_triangles * 4, ctx->stream) : TRC_OK;
-        if (st == TRC_OK) {
-            hipLaunchKernelGGL(k_triangle_materials, dim3((sc.n_triangles + 255) / 256), dim3(256), 0, ctx->stream, d_mat, sc.n_triangles,
-                               ctx->d_blob + sc.off_triattr);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) st = trc_fail(ctx, TRC_ERR_HIP, "k_triangle_materials");
+        DevBuf mat;                 // stays null for "19 for all"
+        if (material) {
+            TRC_TRY(mat.alloc(ctx, (size_t)sc.n_triangles * 4, "triangle materials"));
+            TRC_TRY(trc_copy_to_device(ctx, mat.p, material, (size_t)sc.n_triangles * 4, ctx->stream));
         }
-        (void)hipFree(d_mat);
-        if (st != TRC_OK) return st;
+        hipLaunchKernelGGL(k_triangle_materials, dim3((sc.n_triangles + 255) / 256), dim3(256), 0, ctx->stream, mat.as<uint32_t>(), sc.n_triangles,
+                           ctx->d_blob + sc.off_triattr);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "k_triangle_materials");
     }
     ctx->tri_materials = material != nullptr && sc.n_triangles != 0;
     // what the frame shows changed, and with it the set of emissive triangles; the recorded block costs are another picture's
@@ -732,7 +736,7 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
 }
 
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || width == 0 || height == 0 || width > 65535u * 8u || height > 65535u * 8u) return TRC_ERR_INVALID_ARG;
     // pixel indices are 32-bit in the seed / tonemap / strip / SPPM kernels
     if ((uint64_t)width * height >= (1ull << 32)) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_resize: 2^32 pixels or more");
@@ -750,7 +754,7 @@ trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height) {
 }
 
 trc_status trc_seed(trc_ctx* ctx, uint64_t seed) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_rng) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_seed before trc_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -762,13 +766,13 @@ trc_status trc_seed(trc_ctx* ctx, uint64_t seed) {
 }
 
 static trc_status copy_frame(trc_ctx* ctx, void* dev, void* host, bool to_device) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !host) return TRC_ERR_INVALID_ARG;
     if (!dev) return trc_fail(ctx, TRC_ERR_NO_FRAME, "frame buffers not allocated (trc_resize)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->width * ctx->height * 16;
     trc_sppm_order_after_camera(ctx);
-    { const trc_status cs = to_device ? trc_copy_to_device(ctx, dev, host, bytes, ctx->stream) : trc_copy_to_host(ctx, host, dev, bytes, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(to_device ? trc_copy_to_device(ctx, dev, host, bytes, ctx->stream) : trc_copy_to_host(ctx, host, dev, bytes, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     collect_events(ctx);
     return TRC_OK;
@@ -779,7 +783,7 @@ trc_status trc_upload_accum(trc_ctx* ctx, const float* rgba) { return copy_frame
 trc_status trc_download_accum(trc_ctx* ctx, float* rgba) { return copy_frame(ctx, ctx ? ctx->d_accum : nullptr, rgba, false); }
 
 trc_status trc_clear_accum(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_clear_accum before trc_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -788,7 +792,7 @@ trc_status trc_clear_accum(trc_ctx* ctx) {
 }
 
 trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !rgba8) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_tonemap before trc_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -798,38 +802,33 @@ trc_status trc_tonemap(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
 
 trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, float* exposure_out) {
     const uint32_t n = ctx->width * ctx->height;
-    unsigned long long* d_sums = nullptr;
-    uchar4* d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_sums, 3 * sizeof(unsigned long long)));
-    if (hipMalloc((void**)&d_out, (size_t)n * 4) != hipSuccess) { (void)hipFree(d_sums); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc tonemap"); }
-    trc_status st = TRC_OK;
-    do {
-        unsigned long long sums[3];
-        if (hipMemsetAsync(d_sums, 0, sizeof sums, ctx->stream) != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, "tonemap memset"); break; }
-        hipLaunchKernelGGL(k_tonemap_sum, dim3(std::min<uint32_t>((n + 255) / 256, 2048u)), dim3(256), 0, ctx->stream,
-                           reinterpret_cast<const float4*>(plane), n, d_sums);
-        if (hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, "tonemap sums"); break; }
-        // same binary32 / binary64 steps as oracle/oracle.cpp orc_tonemap (exp through trc_detmath.h)
-        float mean[3];
-        for (int c = 0; c < 3; ++c) mean[c] = (float)((double)sums[c] / 65536.0 / (double)n);
-        const float luma = (mean[0] * 0.2126f + mean[1] * 0.7152f) + mean[2] * 0.0722f;
-        float mapped = 1 - dm_expf(-1.0f * luma);
-        mapped = std::fmin(std::fmax(mapped, 0.0f), 0.9999f);
-        const float expose = 1.0f - mapped;
-        if (exposure_out) *exposure_out = expose;
-        hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(plane),
-                           ctx->width, ctx->height, expose, d_out);
-        if (hipGetLastError() != hipSuccess || trc_copy_to_host(ctx, rgba8, d_out, (size_t)n * 4, ctx->stream) != TRC_OK ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, "tonemap kernel"); break; }
-    } while (0);
-    (void)hipFree(d_sums); (void)hipFree(d_out);
-    return st;
+    DevBuf d_sums, d_out;
+    TRC_TRY(d_sums.alloc(ctx, 3 * sizeof(unsigned long long), "tonemap"));
+    TRC_TRY(d_out.alloc(ctx, (size_t)n * 4, "tonemap"));
+    unsigned long long sums[3];
+    if (hipMemsetAsync(d_sums.p, 0, sizeof sums, ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap memset");
+    hipLaunchKernelGGL(k_tonemap_sum, dim3(std::min<uint32_t>((n + 255) / 256, 2048u)), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<const float4*>(plane), n, d_sums.as<unsigned long long>());
+    if (hipMemcpyAsync(sums, d_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap sums");
+    // same binary32 / binary64 steps as oracle/oracle.cpp orc_tonemap (exp through trc_detmath.h)
+    float mean[3];
+    for (int c = 0; c < 3; ++c) mean[c] = (float)((double)sums[c] / 65536.0 / (double)n);
+    const float luma = (mean[0] * 0.2126f + mean[1] * 0.7152f) + mean[2] * 0.0722f;
+    float mapped = 1 - dm_expf(-1.0f * luma);
+    mapped = std::fmin(std::fmax(mapped, 0.0f), 0.9999f);
+    const float expose = 1.0f - mapped;
+    if (exposure_out) *exposure_out = expose;
+    hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(plane),
+                       ctx->width, ctx->height, expose, d_out.as<uchar4>());
+    if (hipGetLastError() != hipSuccess || trc_copy_to_host(ctx, rgba8, d_out.p, (size_t)n * 4, ctx->stream) != TRC_OK ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap kernel");
+    return TRC_OK;
 }
 
 extern "C" {
 trc_status trc_synchronize(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -839,51 +838,45 @@ trc_status trc_synchronize(trc_ctx* ctx) {
 }
 
 trc_status trc_trace_rays(trc_ctx* ctx, const trc_ray* rays, size_t n, trc_hit* out, int any_hit) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || (n && (!rays || !out))) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_trace_rays before trc_upload_scene");
     if (n == 0) return TRC_OK;
     if (n > 0x7FFFFFFFu) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "too many rays in one call");
     if (any_hit & ~(TRC_TRACE_ANY_HIT | TRC_TRACE_PRODUCTION)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_trace_rays: unknown mode bits");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    trc_ray* d_rays = nullptr; trc_hit* d_hits = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_rays, n * sizeof(trc_ray)));
-    if (hipMalloc((void**)&d_hits, n * sizeof(trc_hit)) != hipSuccess) { (void)hipFree(d_rays); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc hits"); }
-    trc_status st = TRC_OK;
-    do {
-        if (trc_copy_to_device(ctx, d_rays, rays, n * sizeof(trc_ray), ctx->stream) != TRC_OK) { st = trc_fail(ctx, TRC_ERR_HIP, "H2D rays"); break; }
-        KTrace kp{};
-        kp.ks = ctx->ks; kp.rays = d_rays; kp.hits = d_hits; kp.n = (uint32_t)n;
-        const size_t lds = trc_dyn_lds_bytes(ctx, true);
-        dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-        const bool any = (any_hit & TRC_TRACE_ANY_HIT) != 0, prod = (any_hit & TRC_TRACE_PRODUCTION) != 0;
+    DevBuf d_rays, d_hits;
+    TRC_TRY(d_rays.alloc(ctx, n * sizeof(trc_ray), "rays"));
+    TRC_TRY(d_hits.alloc(ctx, n * sizeof(trc_hit), "hits"));
+    if (trc_copy_to_device(ctx, d_rays.p, rays, n * sizeof(trc_ray), ctx->stream) != TRC_OK) return trc_fail(ctx, TRC_ERR_HIP, "H2D rays");
+    KTrace kp{};
+    kp.ks = ctx->ks; kp.rays = d_rays.as<trc_ray>(); kp.hits = d_hits.as<trc_hit>(); kp.n = (uint32_t)n;
+    const size_t lds = trc_dyn_lds_bytes(ctx, true);
+    dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    const bool any = (any_hit & TRC_TRACE_ANY_HIT) != 0, prod = (any_hit & TRC_TRACE_PRODUCTION) != 0;
 #define TRC_LAUNCH_TRACE(L, A, S) hipLaunchKernelGGL((k_trace<L, A, S>), grid, block, lds, ctx->stream, kp)
-        if (ctx->lds_scene) {
-            if (prod) { if (any) TRC_LAUNCH_TRACE(true, true, false); else TRC_LAUNCH_TRACE(true, false, false); }
-            else      { if (any) TRC_LAUNCH_TRACE(true, true, true);  else TRC_LAUNCH_TRACE(true, false, true); }
-        } else {
-            if (prod) { if (any) TRC_LAUNCH_TRACE(false, true, false); else TRC_LAUNCH_TRACE(false, false, false); }
-            else      { if (any) TRC_LAUNCH_TRACE(false, true, true);  else TRC_LAUNCH_TRACE(false, false, true); }
-        }
+    if (ctx->lds_scene) {
+        if (prod) { if (any) TRC_LAUNCH_TRACE(true, true, false); else TRC_LAUNCH_TRACE(true, false, false); }
+        else      { if (any) TRC_LAUNCH_TRACE(true, true, true);  else TRC_LAUNCH_TRACE(true, false, true); }
+    } else {
+        if (prod) { if (any) TRC_LAUNCH_TRACE(false, true, false); else TRC_LAUNCH_TRACE(false, false, false); }
+        else      { if (any) TRC_LAUNCH_TRACE(false, true, true);  else TRC_LAUNCH_TRACE(false, false, true); }
+    }
 #undef TRC_LAUNCH_TRACE
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, std::string("k_trace launch: ") + hipGetErrorString(e)); break; }
-        if (trc_copy_to_host(ctx, out, d_hits, n * sizeof(trc_hit), ctx->stream) != TRC_OK) { st = trc_fail(ctx, TRC_ERR_HIP, "D2H hits"); break; }
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { st = trc_fail(ctx, TRC_ERR_HIP, std::string("k_trace: ") + hipGetErrorString(e)); break; }
-    } while (0);
-    (void)hipFree(d_rays); (void)hipFree(d_hits);
-    return st;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("k_trace launch: ") + hipGetErrorString(e));
+    if (trc_copy_to_host(ctx, out, d_hits.p, n * sizeof(trc_hit), ctx->stream) != TRC_OK) return trc_fail(ctx, TRC_ERR_HIP, "D2H hits");
+    e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("k_trace: ") + hipGetErrorString(e));
+    return TRC_OK;
 }
 
 trc_status trc_get_stats(trc_ctx* ctx, trc_stats* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     unsigned long long h[kStatCount];
-    trc_launch_stats_sum(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TRC_TRY(trc_read_stats_sum(ctx, h, kStatCount));
     collect_events(ctx);
     std::memset(out, 0, sizeof *out);
     out->paths = h[kStatPaths]; out->rays = h[kStatRays]; out->shaded = h[kStatShaded];
@@ -898,7 +891,7 @@ trc_status trc_get_stats(trc_ctx* ctx, trc_stats* out) {
 }
 
 trc_status trc_reset_stats(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -927,22 +920,13 @@ trc_status trc_device_pci_bus_id(trc_ctx* ctx, char* out, size_t out_len) {
 }
 
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !knob) return TRC_ERR_INVALID_ARG;
-    const std::string k(knob);
-    int* slot = k == "refit_single" ? &ctx->knobs.refit_single : k == "no_lds_fit" ? &ctx->knobs.no_lds_fit : k == "stack_lds_levels" ? &ctx->knobs.stack_lds_levels
-              : k == "strip_len" ? &ctx->knobs.strip_len : k == "no_pwg" ? &ctx->knobs.no_pwg
-              : k == "sppm_serial_camera" ? &ctx->knobs.sppm_serial_camera : k == "sppm_timing" ? &ctx->knobs.sppm_timing
-              : k == "force_blk_shift" ? &ctx->knobs.force_blk_shift : k == "no_split" ? &ctx->knobs.no_split : k == "no_cost_filter" ? &ctx->knobs.no_cost_filter
-              : k == "no_cold_probe" ? &ctx->knobs.no_cold_probe : k == "probe_spp" ? &ctx->knobs.probe_spp
-              : k == "no_plan_reuse" ? &ctx->knobs.no_plan_reuse : k == "no_coalesce" ? &ctx->knobs.no_coalesce : k == "no_dense" ? &ctx->knobs.no_dense : k == "head_stages" ? &ctx->knobs.head_stages : k == "descend_min" ? &ctx->knobs.descend_min
-              : k == "camera_policy" ? &ctx->knobs.camera_policy : k == "no_primary_replay" ? &ctx->knobs.no_primary_replay
-              : k == "replay_min_lanes" ? &ctx->knobs.replay_min_lanes : k == "replay_chain" ? &ctx->knobs.replay_chain
-              : k == "mesh_light_pick" ? &ctx->knobs.mesh_light_pick : k == "strip_force" ? &ctx->knobs.strip_force : nullptr;
-    if (!slot) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_debug_set: unknown knob " + k);
+    const KnobEntry* entry = std::find_if(std::begin(kKnobs), std::end(kKnobs), [&](const KnobEntry& k) { return std::strcmp(k.name, knob) == 0; });
+    if (entry == std::end(kKnobs)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_debug_set: unknown knob ") + knob);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // a launch in flight keeps the plan it was made with
-    *slot = value < 0 ? 0 : value;
+    ctx->knobs.*entry->slot = value < 0 ? 0 : value;
     trc_forget_costs(ctx);                                 // block costs recorded under another launch geometry say nothing
     ctx->plan_streak = 0;
     return TRC_OK;

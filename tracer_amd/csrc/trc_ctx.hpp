@@ -191,11 +191,10 @@ struct trc_ctx {
     bool tri_materials = false;         // trc_upload_triangle_materials holds an array: launch the render kernels' trimat twins
     // TRC_FLAG_ENV_LIGHT: the map's sampling tables (trc_envlight.hip), built at the first flagged render after trc_set_environment_map
     uint8_t* d_envl = nullptr; double envl_total = 0.0; float envl_build_ms = 0.0f;
-    bool cost_env = false;              // the flag of the launches whose block costs are recorded (drop_stale_costs)
+    Light cost_light = Light::None;     // the light variant of the launches whose block costs are recorded (drop_stale_costs)
     // TRC_FLAG_MESH_LIGHTS: the emissive triangles' sampling tables (trc_meshlight.hip), built at the first flagged render after a scene
     // or triangle-material upload.  mesh_built with d_meshl null: a scene without a light triangle (or without a triangle)
     uint8_t* d_meshl = nullptr; bool mesh_built = false; uint32_t mesh_n_lights = 0; double mesh_total = 0.0;
-    bool cost_mesh = false;             // ... and its flag of the launches whose block costs are recorded
 
     // frame
     uint32_t width = 0, height = 0;
@@ -284,7 +283,32 @@ struct trc_ctx {
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
     // TRC_STRIP_LEN, TRC_NO_PWG, TRC_SPPM_SERIAL_CAMERA), changed through trc_debug_set
-    struct Knobs { int no_lds_fit = 0, stack_lds_levels = 0, strip_len = 0, no_pwg = 0, sppm_serial_camera = 0, sppm_timing = 0, force_blk_shift = 0, no_split = 0, no_cost_filter = 0, no_cold_probe = 0, probe_spp = 0, no_plan_reuse = 0, no_coalesce = 0, no_dense = 0, head_stages = 0, descend_min = 0, camera_policy = 0, no_primary_replay = 0, replay_min_lanes = 0, replay_chain = 0, mesh_light_pick = 1, refit_single = 0, strip_force = 0; } knobs;
+    // (trc_abi.hip: kKnobs names each once, for both)
+    struct Knobs {
+        int no_lds_fit = 0;             // the whole traversal stack in LDS, no node prefix fitted to the launch (plan_launch_lds)
+        int stack_lds_levels = 0;       // entries of a lane's stack kept in LDS (0: the kernel family's default)
+        int strip_len = 0;              // blocks per wavefront of a strip launch, any spp, capped by the room (launch_geometry)
+        int no_pwg = 0;                 // no persistent workgroups on trees read from memory
+        int sppm_serial_camera = 0;     // SPPM: the camera pass on the context's stream, not beside the photon pass
+        int sppm_timing = 0;            // SPPM: event pairs around a frame's photon, hash / table and refine passes, added to kernel_ms
+        int force_blk_shift = 0;        // k + 1: 2^k x 2^k pixel blocks whatever the flags say
+        int no_split = 0;               // every block whole: no cost-adaptive block size
+        int no_cost_filter = 0;         // order and plan by the last launch's raw durations
+        int no_cold_probe = 0;          // a first launch runs as one pass, no cold head
+        int probe_spp = 0;              // samples of the cold head (at least kColdHeadSpp)
+        int no_plan_reuse = 0;          // a settled list is planned again at every launch
+        int no_coalesce = 0;            // launches of few samples go at once
+        int no_dense = 0;               // never k_render_dense
+        int head_stages = 0;            // passes of a staged cold head (0: 3)
+        int descend_min = 0;            // DScene::descend_min of the launches (0: the upload's)
+        int camera_policy = 0;          // trc_set_camera: 0 keep the costs under a small move, 1 always forget, 2 / 3 always keep (filtered / raw)
+        int no_primary_replay = 0;      // every camera ray walks
+        int replay_min_lanes = 0;       // lanes that must hold a replayed hit for a replay trip (0: TRC_REPLAY_MIN_LANES)
+        int replay_chain = 0;           // replay trips in a row (0: TRC_REPLAY_CHAIN)
+        int mesh_light_pick = 1;        // TRC_FLAG_MESH_LIGHTS: 0 never picks the mesh's light sample (the BSDF-only estimator)
+        int refit_single = 0;           // trc_update_vertices: refit in a single launch (trc_refit.hip)
+        int strip_force = 0;            // tests: exactly this many blocks per wavefront (launch_geometry)
+    } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;
@@ -304,6 +328,45 @@ inline trc_status trc_fail(trc_ctx* ctx, trc_status s, const std::string& msg) {
             return trc_fail(ctx, e_ == hipErrorOutOfMemory ? TRC_ERR_OOM : TRC_ERR_HIP,     \
                             std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
+
+// ... and the same for the library's own status: evaluates `expr` once and returns it from the enclosing function unless it is TRC_OK
+#define TRC_TRY(expr)                                                                      \
+    do {                                                                                   \
+        const trc_status s_ = (expr);                                                      \
+        if (s_ != TRC_OK) return s_;                                                       \
+    } while (0)
+
+// A device allocation that lives no longer than the function that makes it: freed on every path out.  release() hands the
+// pointer to a longer-lived owner.  A failed hipMalloc leaves no sticky error behind for a later, unrelated call to report.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    trc_status alloc(trc_ctx* ctx, size_t bytes, const char* what) {
+        if (hipMalloc(&p, bytes) == hipSuccess) return TRC_OK;
+        p = nullptr;
+        (void)hipGetLastError();
+        return trc_fail(ctx, TRC_ERR_OOM, std::string("hipMalloc ") + what);
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    void* release() { void* q = p; p = nullptr; return q; }
+};
+
+// A buffer of the context that must hold at least `need` bytes (`have`: what it holds): a launch in flight may still use the old
+// one, so the stream is synchronised before it goes.  `msg`: the error text of a failed allocation (TRC_ERR_OOM, nothing kept)
+template <class T>
+inline trc_status trc_grow_buffer(trc_ctx* ctx, T*& buf, size_t& have, size_t need, const char* msg) {
+    if (need <= have) return TRC_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(buf); buf = nullptr;
+    have = 0;
+    if (hipMalloc((void**)&buf, need) != hipSuccess) return trc_fail(ctx, TRC_ERR_OOM, msg);
+    have = need;
+    return TRC_OK;
+}
 
 // RCCL entry points, resolved at run time (dlopen) so the library loads where RCCL is absent
 struct IdBlob { char internal[TRC_UNIQUE_ID_BYTES]; };   // ncclUniqueId, passed by value
@@ -353,7 +416,10 @@ void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint
 uint32_t trc_sort_hist_words(uint32_t n);
 // trc_tonemap's output stage on any W*H RGBA32F plane of the context (the accumulator, the denoised frame); synchronous
 trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, float* exposure_out);
-trc_status trc_flush(trc_ctx* ctx);       // launches what trc_render kept back (every other entry point calls it first)
+// launches what trc_render kept back, and settles what trc_update_vertices left for later.  Every other entry point opens with
+// TRC_TRY(trc_flush(ctx)), before it looks at its arguments: a kept launch of few samples goes first (trc_render), and its status is the
+// entry point's.  trc_flush(nullptr) is TRC_OK: the null-context check that follows answers
+trc_status trc_flush(trc_ctx* ctx);
 hipEvent_t trc_get_event(trc_ctx* ctx);   // from the context's pool (null on failure); pairs go to ctx->pending
 void trc_sppm_release(trc_ctx* ctx);   // frees ctx->sppm (no-op when absent)
 void trc_denoise_release(trc_ctx* ctx);      // frees ctx->denoise: its G-buffers, planes and history (no-op when absent)
@@ -409,4 +475,5 @@ void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload all
 void trc_release_frame(trc_ctx* ctx);    // trc_abi.hip: what depends on the frame size (trc_resize): frame, block list, compose buffers, SPPM, denoiser
 void trc_release_tiles(trc_ctx* ctx);    // trc_schedule.hip: the block list and the arrays sized by it (trc_ensure_tiles)
 void trc_collect_finished_events(trc_ctx* ctx);   // trc_abi.hip: completed event pairs into kernel_ms / schedule_ms without waiting (render_pass)
-void trc_launch_stats_sum(trc_ctx* ctx);          // trc_abi.hip: k_stats_sum of d_stats into d_stats_sum on the context's stream
+// trc_abi.hip: the first `count` words of the counters' rows summed into one (k_stats_sum of d_stats into d_stats_sum), on the host; synchronises the stream
+trc_status trc_read_stats_sum(trc_ctx* ctx, unsigned long long* h, size_t count);

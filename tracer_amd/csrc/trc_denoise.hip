@@ -397,7 +397,7 @@ void trc_denoise_default_params(trc_denoise_params* out) {
 }
 
 trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !prm) return TRC_ERR_INVALID_ARG;
     if (ctx->grouped()) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_denoise: composed multi-rank frames are not denoised");
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_denoise before trc_resize");
@@ -486,7 +486,7 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
 
 static trc_status denoise_download(trc_ctx* ctx, void* host, const void* dev, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { const trc_status cs = trc_copy_to_host(ctx, host, dev, bytes, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_host(ctx, host, dev, bytes, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TRC_OK;
 }
@@ -497,30 +497,30 @@ static trc_status denoise_ready(trc_ctx* ctx, const char* what) {
 }
 
 trc_status trc_download_denoised(trc_ctx* ctx, float* rgba) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !rgba) return TRC_ERR_INVALID_ARG;
-    { const trc_status r = denoise_ready(ctx, "trc_download_denoised"); if (r != TRC_OK) return r; }
+    TRC_TRY(denoise_ready(ctx, "trc_download_denoised"));
     return denoise_download(ctx, rgba, ctx->denoise->out, (size_t)ctx->width * ctx->height * sizeof(float4));
 }
 
 trc_status trc_tonemap_denoised(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !rgba8) return TRC_ERR_INVALID_ARG;
-    { const trc_status r = denoise_ready(ctx, "trc_tonemap_denoised"); if (r != TRC_OK) return r; }
+    TRC_TRY(denoise_ready(ctx, "trc_tonemap_denoised"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return trc_tonemap_plane(ctx, reinterpret_cast<const float*>(ctx->denoise->out), rgba8, exposure_out);
 }
 
 trc_status trc_download_gbuffer(trc_ctx* ctx, trc_gbuffer_texel* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
-    { const trc_status r = denoise_ready(ctx, "trc_download_gbuffer"); if (r != TRC_OK) return r; }
+    TRC_TRY(denoise_ready(ctx, "trc_download_gbuffer"));
     static_assert(sizeof(trc_gbuffer_texel) == 2 * sizeof(float4), "one texel = the two float4 of the G-buffer planes");
     return denoise_download(ctx, out, ctx->denoise->gb[ctx->denoise->gb_cur], (size_t)ctx->width * ctx->height * sizeof(trc_gbuffer_texel));
 }
 
 trc_status trc_denoise_reset(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (ctx->denoise) ctx->denoise->have_hist = false;
     return TRC_OK;
@@ -528,15 +528,15 @@ trc_status trc_denoise_reset(trc_ctx* ctx) {
 
 #ifdef TRC_TEST_HOOKS
 trc_status trc_debug_denoise_state(trc_ctx* ctx, float* integrated, float* history, float* moments) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
-    { const trc_status r = denoise_ready(ctx, "trc_debug_denoise_state"); if (r != TRC_OK) return r; }
+    TRC_TRY(denoise_ready(ctx, "trc_debug_denoise_state"));
     const DenoiseState* s = ctx->denoise;
     const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
     const void* src[3] = {s->integ, s->hist_col[s->hist_cur], s->hist_mom[s->hist_cur]};
     void* dst[3] = {integrated, history, moments};
     for (int k = 0; k < 3; ++k)
-        if (dst[k]) { const trc_status r = denoise_download(ctx, dst[k], src[k], bytes); if (r != TRC_OK) return r; }
+        if (dst[k]) TRC_TRY(denoise_download(ctx, dst[k], src[k], bytes));
     return TRC_OK;
 }
 #endif

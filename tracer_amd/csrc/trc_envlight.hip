@@ -70,15 +70,11 @@ trc_status trc_env_light_build(trc_ctx* ctx) {
     const size_t n = (size_t)W * H;
     const EnvLayout L = env_layout(W, H);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* t = nullptr;
-    uint8_t* scratch = nullptr;                     // q (float64) and the worklist per cell, the rows' sums, then the same for the marginal
-    const size_t scratch_bytes = n * 12 + (size_t)H * 20;
-    if (hipMalloc((void**)&t, L.bytes) != hipSuccess) { (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc environment-light tables"); }
-    if (hipMalloc((void**)&scratch, scratch_bytes) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(t);
-        return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc environment-light table scratch");
-    }
-    double* q = reinterpret_cast<double*>(scratch);
+    DevBuf tables, scratch;                         // scratch: q (float64) and the worklist per cell, the rows' sums, then the same for the marginal
+    TRC_TRY(tables.alloc(ctx, L.bytes, "environment-light tables"));
+    TRC_TRY(scratch.alloc(ctx, n * 12 + (size_t)H * 20, "environment-light table scratch"));
+    uint8_t* const t = tables.as<uint8_t>();
+    double* q = scratch.as<double>();
     double* rowsum = q + n;
     double* qm = rowsum + H;
     uint32_t* list = reinterpret_cast<uint32_t*>(qm + H);
@@ -102,9 +98,8 @@ trc_status trc_env_light_build(trc_ctx* ctx) {
     if (e == hipSuccess && e0 && e1) (void)hipEventElapsedTime(&ms, e0, e1);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(scratch);
-    if (e != hipSuccess) { (void)hipFree(t); return trc_fail(ctx, TRC_ERR_HIP, std::string("environment-light tables: ") + hipGetErrorString(e)); }
-    ctx->d_envl = t;
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("environment-light tables: ") + hipGetErrorString(e));
+    ctx->d_envl = static_cast<uint8_t*>(tables.release());
     ctx->envl_total = h_total;
     ctx->envl_build_ms = ms;
     return TRC_OK;
@@ -149,9 +144,9 @@ __global__ void __launch_bounds__(256) k_env_light_test(const EnvLight el, const
 
 extern "C" {
 trc_status trc_debug_env_tables(trc_ctx* ctx, float* weight, uint32_t* rows, uint32_t* marg, double* total, float* build_ms) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
-    { const trc_status st = trc_env_light_build(ctx); if (st != TRC_OK) return st; }
+    TRC_TRY(trc_env_light_build(ctx));
     const EnvLayout L = env_layout(ctx->env_w, ctx->env_h);
     const size_t n = (size_t)ctx->env_w * ctx->env_h;
     trc_status st = TRC_OK;
@@ -165,34 +160,28 @@ trc_status trc_debug_env_tables(trc_ctx* ctx, float* weight, uint32_t* rows, uin
 }
 
 trc_status trc_env_light_test(trc_ctx* ctx, const uint32_t* draws, size_t n, float* dir_pdf, const float* dirs, size_t m, float* pdf) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || (n && (!draws || !dir_pdf)) || (m && (!dirs || !pdf))) return TRC_ERR_INVALID_ARG;
     if (n > 0x7FFFFFFFu / 6u || m > 0x7FFFFFFFu / 6u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_env_light_test: too many items in one call");
-    { const trc_status st = trc_env_light_build(ctx); if (st != TRC_OK) return st; }
+    TRC_TRY(trc_env_light_build(ctx));
     if (n == 0 && m == 0) return TRC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* d = nullptr;
-    const size_t bytes = n * (24 + 16) + m * (12 + 4);
-    HIP_TRY(ctx, hipMalloc((void**)&d, bytes));
-    uint32_t* d_draws = reinterpret_cast<uint32_t*>(d);
-    float* d_out = reinterpret_cast<float*>(d + n * 24);
+    DevBuf d;           // (freeing it waits for whatever a failed step left in flight)
+    TRC_TRY(d.alloc(ctx, n * (24 + 16) + m * (12 + 4), "environment-light test"));
+    uint32_t* d_draws = d.as<uint32_t>();
+    float* d_out = reinterpret_cast<float*>(d.as<uint8_t>() + n * 24);
     float* d_dirs = d_out + 4 * n;
     float* d_pdf = d_dirs + 3 * m;
-    trc_status ts = TRC_OK;
-    if (n) ts = trc_copy_to_device(ctx, d_draws, draws, n * 24, ctx->stream);
-    if (ts == TRC_OK && m) ts = trc_copy_to_device(ctx, d_dirs, dirs, m * 12, ctx->stream);
-    if (ts == TRC_OK) {
-        const size_t items = n > m ? n : m;
-        hipLaunchKernelGGL(k_env_light_test, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, trc_env_light_view(ctx),
-                           d_draws, (uint32_t)n, d_out, d_dirs, (uint32_t)m, d_pdf);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_env_light_test: ") + hipGetErrorString(e));
-    }
-    if (ts == TRC_OK && n) ts = trc_copy_to_host(ctx, dir_pdf, d_out, n * 16, ctx->stream);
-    if (ts == TRC_OK && m) ts = trc_copy_to_host(ctx, pdf, d_pdf, m * 4, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return ts;
+    if (n) TRC_TRY(trc_copy_to_device(ctx, d_draws, draws, n * 24, ctx->stream));
+    if (m) TRC_TRY(trc_copy_to_device(ctx, d_dirs, dirs, m * 12, ctx->stream));
+    const size_t items = n > m ? n : m;
+    hipLaunchKernelGGL(k_env_light_test, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, trc_env_light_view(ctx),
+                       d_draws, (uint32_t)n, d_out, d_dirs, (uint32_t)m, d_pdf);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_env_light_test: ") + hipGetErrorString(e));
+    if (n) TRC_TRY(trc_copy_to_host(ctx, dir_pdf, d_out, n * 16, ctx->stream));
+    if (m) TRC_TRY(trc_copy_to_host(ctx, pdf, d_pdf, m * 4, ctx->stream));
+    return TRC_OK;
 }
 }  // extern "C"
 #endif  // TRC_TEST_HOOKS

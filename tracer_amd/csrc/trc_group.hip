@@ -137,7 +137,7 @@ trc_status trc_group_unique_id(uint8_t id[TRC_UNIQUE_ID_BYTES]) {
 }
 
 trc_status trc_group_init(trc_ctx* ctx, const uint8_t id[TRC_UNIQUE_ID_BYTES], int nranks, int rank) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) return TRC_ERR_INVALID_ARG;
     std::string err;
     if (!trc_load_rccl(err)) return trc_fail(ctx, TRC_ERR_RCCL, err);
@@ -156,7 +156,7 @@ trc_status trc_group_init(trc_ctx* ctx, const uint8_t id[TRC_UNIQUE_ID_BYTES], i
 }
 
 trc_status trc_group_reduce_accum(trc_ctx* ctx, int root) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->grouped()) return trc_fail(ctx, TRC_ERR_RCCL, "trc_group_reduce_accum before trc_group_init / trc_group_set_collectives");
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "no frame");
@@ -224,8 +224,7 @@ trc_status compose_samples(trc_ctx* ctx, const float* src, int root, uint32_t gr
             const int rc = c.alltoall(c.user, ctx->d_shard_in, slice_bytes, (void*)st);
             if (rc != 0) return trc_fail(ctx, TRC_ERR_RCCL, std::string(what) + ": the caller's alltoall returned " + std::to_string(rc));
         } else {
-            trc_status cs = staged(ctx, ctx->d_shard_in, total_bytes, true, st, what, [&](void* h) { return c.alltoall(c.user, h, slice_bytes, nullptr); });
-            if (cs != TRC_OK) return cs;
+            TRC_TRY(staged(ctx, ctx->d_shard_in, total_bytes, true, st, what, [&](void* h) { return c.alltoall(c.user, h, slice_bytes, nullptr); }));
         }
     } else {
         if (!ctx->comm) return trc_fail(ctx, TRC_ERR_RCCL, std::string(what) + " before trc_group_init / trc_group_set_collectives");
@@ -286,24 +285,24 @@ trc_status check_compose(trc_ctx* ctx, int root, uint32_t groups, const char* wh
 uint64_t trc_shard_seed(uint64_t seed, uint32_t sample_group) { return seed + (uint64_t)sample_group * 0x9E3779B97F4A7C15ull; }
 
 trc_status trc_group_compose_samples(trc_ctx* ctx, int root, uint32_t sample_groups) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || root < 0) return TRC_ERR_INVALID_ARG;
     if (sample_groups == 0) sample_groups = (uint32_t)ctx->nranks;
-    { trc_status cs = check_compose(ctx, root, sample_groups, "trc_group_compose_samples"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(check_compose(ctx, root, sample_groups, "trc_group_compose_samples"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->comm_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->comm_stream));    // an earlier pipelined compose still owns the slice buffers
-    { trc_status cs = compose_samples(ctx, ctx->d_accum, root, sample_groups, ctx->stream, "compose of the sample shards"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(compose_samples(ctx, ctx->d_accum, root, sample_groups, ctx->stream, "compose of the sample shards"));
     ctx->d_composed = ctx->rank == root ? ctx->d_shard_out : nullptr;      // the composed frame exists on the root only
     return TRC_OK;
 }
 
 trc_status trc_group_allreduce_mean_accum(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
-    { trc_status cs = check_compose(ctx, -1, (uint32_t)ctx->nranks, "trc_group_allreduce_mean_accum"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(check_compose(ctx, -1, (uint32_t)ctx->nranks, "trc_group_allreduce_mean_accum"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->comm_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->comm_stream));
-    { trc_status cs = compose_samples(ctx, ctx->d_accum, -1, (uint32_t)ctx->nranks, ctx->stream, "compose of the sample shards"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(compose_samples(ctx, ctx->d_accum, -1, (uint32_t)ctx->nranks, ctx->stream, "compose of the sample shards"));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_accum, ctx->d_shard_out, (size_t)ctx->width * ctx->height * 16, hipMemcpyDeviceToDevice, ctx->stream));
     return TRC_OK;
 }
@@ -331,7 +330,7 @@ trc_status compose_async(trc_ctx* ctx, Collective&& collective) {
     // compose the current accumulator once everything queued so far on the render stream has finished
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rendered, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_rendered, 0));
-    { trc_status cs = collective(); if (cs != TRC_OK) return cs; }
+    TRC_TRY(collective());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_busy, ctx->comm_stream));
     ctx->busy = true;
     // swap accumulators (and their events); the render stream may touch the new current one only after ITS last compose
@@ -345,7 +344,7 @@ trc_status compose_async(trc_ctx* ctx, Collective&& collective) {
 }  // extern "C++"
 
 trc_status trc_group_reduce_accum_async(trc_ctx* ctx, int root) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->grouped()) return trc_fail(ctx, TRC_ERR_RCCL, "trc_group_reduce_accum_async before trc_group_init / trc_group_set_collectives");
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "no frame");
@@ -359,10 +358,10 @@ trc_status trc_group_reduce_accum_async(trc_ctx* ctx, int root) {
 }
 
 trc_status trc_group_compose_samples_async(trc_ctx* ctx, int root, uint32_t sample_groups) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || root < 0) return TRC_ERR_INVALID_ARG;
     if (sample_groups == 0) sample_groups = (uint32_t)ctx->nranks;
-    { trc_status cs = check_compose(ctx, root, sample_groups, "trc_group_compose_samples_async"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(check_compose(ctx, root, sample_groups, "trc_group_compose_samples_async"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // Unlike the tile reduce (which composes IN the accumulator and therefore switches to the other one), the sample compose only
     // reads: it works on a SNAPSHOT of the accumulator (a 33 MB device copy: ~20 us) taken in render-stream order, so the rank
@@ -380,7 +379,7 @@ trc_status trc_group_compose_samples_async(trc_ctx* ctx, int root, uint32_t samp
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_shard_src, ctx->d_accum, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_rendered, ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_rendered, 0));
-    { trc_status cs = compose_samples(ctx, ctx->d_shard_src, root, sample_groups, ctx->comm_stream, "compose of the sample shards"); if (cs != TRC_OK) return cs; }
+    TRC_TRY(compose_samples(ctx, ctx->d_shard_src, root, sample_groups, ctx->comm_stream, "compose of the sample shards"));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_snapshot_free, ctx->comm_stream));
     ctx->snapshot_busy = true;
     ctx->d_composed = ctx->rank == root ? ctx->d_shard_out : nullptr;      // the composed frame exists on the root only
@@ -388,18 +387,18 @@ trc_status trc_group_compose_samples_async(trc_ctx* ctx, int root, uint32_t samp
 }
 
 trc_status trc_download_composed(trc_ctx* ctx, float* rgba) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !rgba) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_composed) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_download_composed before trc_group_reduce_accum_async / trc_group_compose_samples");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->comm_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->comm_stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    { const trc_status cs = trc_copy_to_host(ctx, rgba, ctx->d_composed, (size_t)ctx->width * ctx->height * 16, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_host(ctx, rgba, ctx->d_composed, (size_t)ctx->width * ctx->height * 16, ctx->stream));
     return TRC_OK;
 }
 
 trc_status trc_group_finalize(trc_ctx* ctx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (ctx->grouped()) {
         (void)hipSetDevice(ctx->device);
@@ -414,12 +413,12 @@ trc_status trc_group_finalize(trc_ctx* ctx) {
 }
 
 trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table, int nranks, int rank) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!table) return trc_group_finalize(ctx);
     if (nranks < 1 || rank < 0 || rank >= nranks) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_group_set_collectives: rank / nranks");
     if (!table->reduce || !table->allreduce || !table->allgather) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_group_set_collectives: the table needs reduce, allreduce and allgather (alltoall / gather: only for sample shards)");
-    { trc_status fs = trc_group_finalize(ctx); if (fs != TRC_OK) return fs; }
+    TRC_TRY(trc_group_finalize(ctx));
     ctx->coll = *table;
     ctx->coll_active = true;
     ctx->nranks = nranks; ctx->rank = rank;

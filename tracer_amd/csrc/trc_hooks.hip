@@ -53,13 +53,11 @@ __global__ void __launch_bounds__(256) k_unary_test(uint32_t op, uint32_t first,
 extern "C" {
 // developer diagnostic: (lanes, wavefronts) that executed each ProfSite of the instrumented kernels
 trc_status trc_debug_profile(trc_ctx* ctx, uint64_t* out, uint32_t n_sites) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     unsigned long long h[kStatCount + 3 * kProfCount];
-    trc_launch_stats_sum(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TRC_TRY(trc_read_stats_sum(ctx, h, kStatCount + 3 * kProfCount));
     for (uint32_t i = 0; i < n_sites && i < (uint32_t)kProfCount; ++i)
         for (int k = 0; k < 3; ++k) out[3 * i + k] = h[kStatCount + 3 * i + k];
     return TRC_OK;
@@ -76,31 +74,26 @@ __global__ void __launch_bounds__(256) k_texture_sample_test(const float* texels
     rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 trc_status trc_texture_sample_test(trc_ctx* ctx, uint32_t index, const float* uv, size_t n, float* rgb) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || (n && (!uv || !rgb))) return TRC_ERR_INVALID_ARG;
     if (index >= ctx->n_tex) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: no such image");
     if (n == 0) return TRC_OK;
     if (n > 0x7FFFFFFFu / 3u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_texture_sample_test: too many pairs in one call");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, n * 5 * sizeof(float)));
-    float *d_uv = d, *d_rgb = d + 2 * n;
-    trc_status ts = trc_copy_to_device(ctx, d_uv, uv, n * 8, ctx->stream);
-    if (ts == TRC_OK) {
-        hipLaunchKernelGGL(k_texture_sample_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->d_tex_texels, ctx->d_tex_desc, ctx->n_tex, index, d_uv, (uint32_t)n, d_rgb);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_texture_sample_test: ") + hipGetErrorString(e));
-    }
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, rgb, d_rgb, n * 12, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return ts;
+    DevBuf d;           // (freeing it waits for whatever a failed step left in flight)
+    TRC_TRY(d.alloc(ctx, n * 5 * sizeof(float), "texture sample test"));
+    float *d_uv = d.as<float>(), *d_rgb = d_uv + 2 * n;
+    TRC_TRY(trc_copy_to_device(ctx, d_uv, uv, n * 8, ctx->stream));
+    hipLaunchKernelGGL(k_texture_sample_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->d_tex_texels, ctx->d_tex_desc, ctx->n_tex, index, d_uv, (uint32_t)n, d_rgb);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_texture_sample_test: ") + hipGetErrorString(e));
+    return trc_copy_to_host(ctx, rgb, d_rgb, n * 12, ctx->stream);
 }
 
 // the kernel choice of the last render launch (trc_render_pass.hip: choose_kernel)
 trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
     const trc_ctx::LastKernel& k = ctx->last_kernel;
     out->shape = k.shape; out->variant = k.variant; out->lds_resident = k.lds_resident; out->triangle_materials = k.tri_materials;
@@ -113,28 +106,24 @@ trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t 
     if (n == 0) return TRC_OK;
     if (n > 0x7FFFFFFFu / 3u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_div_by_test: too many pairs in one call");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, n * 8 * sizeof(float)));
-    float *d_a = d, *d_b = d + n, *d_fast = d + 2 * n, *d_plain = d + 5 * n;
-    trc_status ts = trc_copy_to_device(ctx, d_a, a, n * 4, ctx->stream);
-    if (ts == TRC_OK) ts = trc_copy_to_device(ctx, d_b, b, n * 4, ctx->stream);
-    if (ts == TRC_OK) {
-        hipLaunchKernelGGL(k_div_by_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_a, d_b, (uint32_t)n, d_fast, d_plain);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_div_by_test: ") + hipGetErrorString(e));
-    }
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, fast, d_fast, n * 12, ctx->stream);
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, plain, d_plain, n * 12, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return ts;
+    DevBuf d;
+    TRC_TRY(d.alloc(ctx, n * 8 * sizeof(float), "div_by test"));
+    float *d_a = d.as<float>(), *d_b = d_a + n, *d_fast = d_a + 2 * n, *d_plain = d_a + 5 * n;
+    TRC_TRY(trc_copy_to_device(ctx, d_a, a, n * 4, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_b, b, n * 4, ctx->stream));
+    hipLaunchKernelGGL(k_div_by_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_a, d_b, (uint32_t)n, d_fast, d_plain);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_div_by_test: ") + hipGetErrorString(e));
+    TRC_TRY(trc_copy_to_host(ctx, fast, d_fast, n * 12, ctx->stream));
+    return trc_copy_to_host(ctx, plain, d_plain, n * 12, ctx->stream);
 }
 
 trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch) {
     if (!ctx || !n_mismatch || op > 6u || count > (1ull << 32)) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned long long* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, 16));
+    DevBuf buf;
+    TRC_TRY(buf.alloc(ctx, 16, "unary test"));
+    unsigned long long* const d = buf.as<unsigned long long>();
     const unsigned long long init[2] = {0ull, ~0ull};
     unsigned long long h[2] = {0ull, ~0ull};
     hipError_t e = hipMemcpyAsync(d, init, 16, hipMemcpyHostToDevice, ctx->stream);
@@ -144,7 +133,6 @@ trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); else (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_unary_test: ") + hipGetErrorString(e));
     *n_mismatch = h[0];
     if (first_mismatch) *first_mismatch = (uint32_t)h[1];

@@ -24,10 +24,9 @@ __host__ __device__ __forceinline__ void for_each_part(const uint32_t* qsplit, u
 struct RenderLaunch {
     KRender kp{};                       // the kernel's parameters
     bool stats = false, sobol = false;  // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL
-    bool env = false;                   // TRC_FLAG_ENV_LIGHT ...
-    EnvLight el{};                      // ... and the map's sampling tables (the k_render*_env kernels' second half of KRenderEnv)
-    bool mesh = false;                  // TRC_FLAG_MESH_LIGHTS ...
-    MeshLight ml{};                     // ... and the emissive triangles' sampling tables (the k_render*_mesh kernels' second half of KRenderMesh)
+    Light light = Light::None;          // TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS: the light the kernels sample besides the squares ...
+    EnvLight el{};                      // ... Light::Env: the map's sampling tables (the k_render*_env kernels' second half of KRenderEnv)
+    MeshLight ml{};                     // ... Light::Mesh: the emissive triangles' (the k_render*_mesh kernels' second half of KRenderMesh)
     bool fits = false;                  // launch_geometry: the frame's edges allow 4x4 blocks ...
     uint64_t blocks8 = 0;               // ... 8x8 blocks in this rank's share
     bool quarters_ok = false;           // ... the list's blocks are 8x8: costs live in kCostSlots slots per block

@@ -508,7 +508,7 @@ uint32_t trc_sort_hist_words(uint32_t n) { return 256u * ((n + kSortTile - 1) / 
 // reference's own binned-SAH build, trc_sah_build.hpp) share everything around the topology: leaf intake, boxes bottom-up,
 // fat nodes by depth, the tree in the reference's array layout.
 static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah, bool triangle_leaves) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!s) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "device tree: no scene");
     // triangle_leaves: bvhList holds the analytic primitives' leaves only; one leaf per triangle follows them, written on the device
@@ -516,12 +516,12 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     if ((!s->bvhList && !triangle_leaves) || n_all < 2) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "lbvh: need >= 2 leaf records");
     if (n_all > (1u << 28)) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "lbvh: more than 2^28 leaves");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { trc_status st = validate_primitives(ctx, s); if (st != TRC_OK) return st; }
+    TRC_TRY(validate_primitives(ctx, s));
     const uint32_t n = (uint32_t)n_all, n_interior = n - 1, n_nodes = 2 * n - 1;
 
     DScene sc{};
     uint64_t total = 0;
-    { trc_status st = layout_scene(ctx, s, n_interior, sc, total); if (st != TRC_OK) return st; }
+    TRC_TRY(layout_scene(ctx, s, n_interior, sc, total));
     // host side of the blob: analytic primitives + materials (the prefix).  The fat nodes are written by k_lbvh_emit, the
     // triangle records by k_repack_triangles from the caller's vertex / index arrays: neither is staged on the host
     std::unique_ptr<uint32_t[]> blob(new (std::nothrow) uint32_t[(size_t)sc.off_nodes]);
@@ -535,11 +535,11 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bvh_ref, sizeof(trc_BVH) * n_nodes));
     hipStream_t st = ctx->stream;
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_blob, blob.get(), (size_t)sc.off_nodes * 4, st); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_blob, blob.get(), (size_t)sc.off_nodes * 4, st));
     // the caller's leaf records go straight to slots 1..n of the reference-layout array (BVH.hh:246-269), the triangles' behind them
-    { trc_status rs = trc_repack_triangles(ctx, s, sc, ctx->d_blob, triangle_leaves ? ctx->d_bvh_ref + 1 + n_given : nullptr); if (rs != TRC_OK) return rs; }
+    TRC_TRY(trc_repack_triangles(ctx, s, sc, ctx->d_blob, triangle_leaves ? ctx->d_bvh_ref + 1 + n_given : nullptr));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_bvh_ref, 0, sizeof(trc_BVH), st));
-    if (n_given) { const trc_status cs = trc_copy_to_device(ctx, ctx->d_bvh_ref + 1, s->bvhList, sizeof(trc_BVH) * n_given, st); if (cs != TRC_OK) return cs; }
+    if (n_given) TRC_TRY(trc_copy_to_device(ctx, ctx->d_bvh_ref + 1, s->bvhList, sizeof(trc_BVH) * n_given, st));
 
     Buffers buf;
     DLeaf* d_leaves; uint32_t *d_keys[2], *d_vals[2], *d_hist, *d_bounds, *d_height, *d_arrived;
@@ -587,8 +587,7 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
         }
         hipLaunchKernelGGL(k_lbvh_hierarchy, g_int, b256, 0, st, d_keys[cur], d_vals[cur], n, tp);
     } else {
-        const trc_status bs = sah_build_topology(ctx, buf, d_leaves, n, d_bounds + 6, tp, d_vals[0], &first_chunk);
-        if (bs != TRC_OK) return bs;
+        TRC_TRY(sah_build_topology(ctx, buf, d_leaves, n, d_bounds + 6, tp, d_vals[0], &first_chunk));
         first_chunk = std::min(std::max(first_chunk, 1u), TRC_MAX_BVH_DEPTH + 1u);      // the builder knows the tree's height: that many refit passes
     }
     // refit passes: a tree of height h needs h passes; check the root every few passes beyond the usual depth
@@ -613,15 +612,14 @@ static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah,
         if (!root_done) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
         return TRC_OK;
     };
-    { trc_status rs = refit(); if (rs != TRC_OK) return rs; }
+    TRC_TRY(refit());
     for (int sweep = 0; sweep < (sah ? 0 : kRotationSweeps); ++sweep) {
         // d_arrived[i] = pass in which i was fitted = its height; the root's is the height of the tree.  Nodes of
         // height 1 have two leaf children and nothing to rotate.
         const uint32_t h = root_done;
         for (uint32_t pass = 2; pass <= h; ++pass)
             hipLaunchKernelGGL(k_lbvh_rotate_pass, g_int, b256, 0, st, d_leaves, d_vals[cur], n, tp, d_boxes, d_arrived, pass);
-        trc_status rs = refit();
-        if (rs != TRC_OK) return rs;
+        TRC_TRY(refit());
     }
     // fat-node numbering: interior nodes sorted by depth (one stable 8-bit radix pass; the root is the only node of depth 0)
     uint32_t* d_rank = nullptr;                         // reuses the arrival array (the heights in d_height are read back below)
@@ -677,14 +675,14 @@ trc_status trc_upload_scene_device(trc_ctx* ctx, const trc_scene* s, uint32_t fl
 }
 
 trc_status trc_download_bvh(trc_ctx* ctx, trc_BVH* out, uint32_t capacity, uint32_t* n_nodes) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_bvh_ref || ctx->n_bvh_ref == 0) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_download_bvh: no device-built tree (trc_upload_scene_lbvh)");
     if (n_nodes) *n_nodes = ctx->n_bvh_ref;
     if (!out) return TRC_OK;
     if (capacity < ctx->n_bvh_ref) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_bvh: capacity too small");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { const trc_status cs = trc_copy_to_host(ctx, out, ctx->d_bvh_ref, sizeof(trc_BVH) * ctx->n_bvh_ref, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_host(ctx, out, ctx->d_bvh_ref, sizeof(trc_BVH) * ctx->n_bvh_ref, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TRC_OK;
 }

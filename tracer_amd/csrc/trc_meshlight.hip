@@ -97,14 +97,11 @@ trc_status trc_mesh_light_build(trc_ctx* ctx) {
     if (n == 0) { ctx->mesh_built = true; ctx->mesh_n_lights = 0; ctx->mesh_total = 0.0; return TRC_OK; }
     const MeshLayout L = mesh_layout(n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* t = nullptr;
-    uint8_t* scratch = nullptr;                     // per triangle: w, wl, q (float64) and the worklist
-    if (hipMalloc((void**)&t, L.bytes) != hipSuccess) { (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc mesh-light tables"); }
-    if (hipMalloc((void**)&scratch, (size_t)n * 28) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(t);
-        return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc mesh-light table scratch");
-    }
-    double* w = reinterpret_cast<double*>(scratch);
+    DevBuf tables, scratch;                         // scratch, per triangle: w, wl, q (float64) and the worklist
+    TRC_TRY(tables.alloc(ctx, L.bytes, "mesh-light tables"));
+    TRC_TRY(scratch.alloc(ctx, (size_t)n * 28, "mesh-light table scratch"));
+    uint8_t* const t = tables.as<uint8_t>();
+    double* w = scratch.as<double>();
     double* wl = w + n;
     double* q = wl + n;
     uint32_t* list = reinterpret_cast<uint32_t*>(q + n);
@@ -120,9 +117,8 @@ trc_status trc_mesh_light_build(trc_ctx* ctx) {
     struct { double total; uint32_t count, pad; } head = {0.0, 0u, 0u};
     if (e == hipSuccess) e = hipMemcpyAsync(&head, t, sizeof head, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(scratch);
-    if (e != hipSuccess) { (void)hipFree(t); return trc_fail(ctx, TRC_ERR_HIP, std::string("mesh-light tables: ") + hipGetErrorString(e)); }
-    ctx->d_meshl = t;
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("mesh-light tables: ") + hipGetErrorString(e));
+    ctx->d_meshl = static_cast<uint8_t*>(tables.release());
     ctx->mesh_n_lights = head.count;
     ctx->mesh_total = head.total;
     ctx->mesh_built = true;
@@ -169,10 +165,10 @@ __global__ void __launch_bounds__(256) k_mesh_light_test(const MeshLight ml, con
 
 extern "C" {
 trc_status trc_debug_mesh_light_tables(trc_ctx* ctx, uint32_t* alias, uint32_t* tri, float* pdfA, double* total, uint32_t* n_lights) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_debug_mesh_light_tables: no scene");
-    { const trc_status st = trc_mesh_light_build(ctx); if (st != TRC_OK) return st; }
+    TRC_TRY(trc_mesh_light_build(ctx));
     const uint32_t n_tri = ctx->ks.sc.n_triangles, n = ctx->mesh_n_lights;
     const MeshLayout L = mesh_layout(n_tri);
     trc_status st = TRC_OK;
@@ -188,34 +184,30 @@ trc_status trc_debug_mesh_light_tables(trc_ctx* ctx, uint32_t* alias, uint32_t* 
 }
 
 trc_status trc_mesh_light_test(trc_ctx* ctx, const uint32_t* draws, const float* pos, size_t n, uint32_t* tri, float* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || (n && (!draws || !pos || !tri || !out))) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_mesh_light_test: no scene");
     if (n > 0x7FFFFFFFu / 7u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_mesh_light_test: too many items in one call");
-    { const trc_status st = trc_mesh_light_build(ctx); if (st != TRC_OK) return st; }
+    TRC_TRY(trc_mesh_light_build(ctx));
     if (ctx->mesh_n_lights == 0) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_mesh_light_test: the scene has no light triangle");
     if (n == 0) return TRC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d, n * (16 + 12 + 4 + 28)));
+    DevBuf buf;         // (freeing it waits for whatever a failed step left in flight)
+    TRC_TRY(buf.alloc(ctx, n * (16 + 12 + 4 + 28), "mesh-light test"));
+    uint8_t* const d = buf.as<uint8_t>();
     uint32_t* d_draws = reinterpret_cast<uint32_t*>(d);
     float* d_pos = reinterpret_cast<float*>(d + n * 16);
     uint32_t* d_tri = reinterpret_cast<uint32_t*>(d + n * 28);
     float* d_out = reinterpret_cast<float*>(d + n * 32);
-    trc_status ts = trc_copy_to_device(ctx, d_draws, draws, n * 16, ctx->stream);
-    if (ts == TRC_OK) ts = trc_copy_to_device(ctx, d_pos, pos, n * 12, ctx->stream);
-    if (ts == TRC_OK) {
-        MeshLight ml = trc_mesh_light_view(ctx);
-        hipLaunchKernelGGL(k_mesh_light_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ml, ctx->d_blob + ctx->ks.sc.off_tripos,
-                           d_draws, d_pos, (uint32_t)n, d_tri, d_out);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_mesh_light_test: ") + hipGetErrorString(e));
-    }
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, tri, d_tri, n * 4, ctx->stream);
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, out, d_out, n * 28, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return ts;
+    TRC_TRY(trc_copy_to_device(ctx, d_draws, draws, n * 16, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_pos, pos, n * 12, ctx->stream));
+    MeshLight ml = trc_mesh_light_view(ctx);
+    hipLaunchKernelGGL(k_mesh_light_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ml, ctx->d_blob + ctx->ks.sc.off_tripos,
+                       d_draws, d_pos, (uint32_t)n, d_tri, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_mesh_light_test: ") + hipGetErrorString(e));
+    TRC_TRY(trc_copy_to_host(ctx, tri, d_tri, n * 4, ctx->stream));
+    return trc_copy_to_host(ctx, out, d_out, n * 28, ctx->stream);
 }
 }  // extern "C"
 #endif  // TRC_TEST_HOOKS

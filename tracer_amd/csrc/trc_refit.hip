@@ -177,51 +177,57 @@ __global__ void __launch_bounds__(256) k_refit_climb(KRefit p, const uint32_t* _
     }
 }
 
-// maps of the uploaded scene (trc_ctx: d_refit_*, refit_levels), behind whatever the stream still holds; the only part of an update
-// that waits for the device, once per scene
-trc_status refit_prepare(trc_ctx* ctx) {
-    if (!ctx->refit_levels.empty()) return TRC_OK;
+// the maps themselves (refit_prepare frees what a failure leaves half made)
+trc_status refit_make_maps(trc_ctx* ctx) {
     const DScene& sc = ctx->ks.sc;
     const uint32_t n = sc.n_nodes;
     const uint4* nodes = reinterpret_cast<const uint4*>(ctx->d_blob + sc.off_nodes);
     const dim3 grid((n + 255) / 256), b256(256);
     hipStream_t st = ctx->stream;
-    uint32_t* d_level = nullptr;
+    DevBuf level_buf;
     uint32_t level[kRefitMaxLevels + 1];
-    trc_status rs = TRC_OK;
-    auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rs == TRC_OK) rs = trc_fail(ctx, e == hipErrorOutOfMemory ? TRC_ERR_OOM : TRC_ERR_HIP, std::string("trc_update_vertices: ") + what + ": " + hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    do {
-        if (!hip_ok(hipMalloc((void**)&ctx->d_refit_parent, (size_t)n * 4), "parent map")) break;
-        if (!hip_ok(hipMalloc((void**)&ctx->d_refit_arrive, (size_t)n * 4), "arrival counters")) break;
-        if (!hip_ok(hipMalloc((void**)&ctx->d_refit_root, 8 * sizeof(float)), "root box")) break;
-        if (!hip_ok(hipMalloc((void**)&d_level, sizeof level), "level table")) break;
-        if (ctx->d_bvh_ref && !hip_ok(hipMalloc((void**)&ctx->d_refit_refnode, (size_t)n * 4), "record map")) break;
-        if (!hip_ok(hipMemsetAsync(ctx->d_refit_parent, 0, (size_t)n * 4, st), "memset")) break;
-        if (!hip_ok(hipMemsetAsync(ctx->d_refit_arrive, 0, (size_t)n * 4, st), "memset")) break;
-        if (!hip_ok(hipMemsetAsync(d_level, 0, sizeof level, st), "memset")) break;
-        hipLaunchKernelGGL(k_refit_parents, grid, b256, 0, st, nodes, n, ctx->d_refit_parent);
-        hipLaunchKernelGGL(k_refit_levels, grid, b256, 0, st, ctx->d_refit_parent, n, d_level);
-        if (!hip_ok(hipGetLastError(), "map kernels")) break;
-        if (!hip_ok(hipMemcpyAsync(ctx->h_readback, d_level, sizeof level, hipMemcpyDeviceToHost, st), "level table")) break;
-        if (!hip_ok(hipStreamSynchronize(st), "level table")) break;
-        std::memcpy(level, ctx->h_readback, sizeof level);
-        if (level[kRefitBad]) { rs = trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_update_vertices: the fat nodes are not numbered by depth"); break; }
-        std::vector<uint32_t> levels{0u};
-        for (uint32_t d = 1; d < kRefitMaxLevels && level[d] != 0u; ++d) levels.push_back(level[d]);
-        levels.push_back(n);
-        if (ctx->d_bvh_ref) {
-            for (size_t d = 0; d + 1 < levels.size(); ++d)
-                hipLaunchKernelGGL(k_refit_refnodes, dim3((levels[d + 1] - levels[d] + 255) / 256), b256, 0, st, nodes, ctx->d_bvh_ref, levels[d], levels[d + 1],
-                                   n, ctx->d_refit_refnode);
-            if (!hip_ok(hipGetLastError(), "record map")) break;
-            if (!hip_ok(hipStreamSynchronize(st), "record map")) break;
-        }
-        ctx->refit_levels = std::move(levels);
-    } while (0);
-    (void)hipFree(d_level);
+#define REFIT_TRY(expr, what)                                                                                                  \
+    do {                                                                                                                       \
+        const hipError_t e_ = (expr);                                                                                          \
+        if (e_ != hipSuccess)                                                                                                  \
+            return trc_fail(ctx, e_ == hipErrorOutOfMemory ? TRC_ERR_OOM : TRC_ERR_HIP, std::string("trc_update_vertices: ") + what + ": " + hipGetErrorString(e_)); \
+    } while (0)
+    REFIT_TRY(hipMalloc((void**)&ctx->d_refit_parent, (size_t)n * 4), "parent map");
+    REFIT_TRY(hipMalloc((void**)&ctx->d_refit_arrive, (size_t)n * 4), "arrival counters");
+    REFIT_TRY(hipMalloc((void**)&ctx->d_refit_root, 8 * sizeof(float)), "root box");
+    TRC_TRY(level_buf.alloc(ctx, sizeof level, "level table"));
+    uint32_t* const d_level = level_buf.as<uint32_t>();
+    if (ctx->d_bvh_ref) REFIT_TRY(hipMalloc((void**)&ctx->d_refit_refnode, (size_t)n * 4), "record map");
+    REFIT_TRY(hipMemsetAsync(ctx->d_refit_parent, 0, (size_t)n * 4, st), "memset");
+    REFIT_TRY(hipMemsetAsync(ctx->d_refit_arrive, 0, (size_t)n * 4, st), "memset");
+    REFIT_TRY(hipMemsetAsync(d_level, 0, sizeof level, st), "memset");
+    hipLaunchKernelGGL(k_refit_parents, grid, b256, 0, st, nodes, n, ctx->d_refit_parent);
+    hipLaunchKernelGGL(k_refit_levels, grid, b256, 0, st, ctx->d_refit_parent, n, d_level);
+    REFIT_TRY(hipGetLastError(), "map kernels");
+    REFIT_TRY(hipMemcpyAsync(ctx->h_readback, d_level, sizeof level, hipMemcpyDeviceToHost, st), "level table");
+    REFIT_TRY(hipStreamSynchronize(st), "level table");
+    std::memcpy(level, ctx->h_readback, sizeof level);
+    if (level[kRefitBad]) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_update_vertices: the fat nodes are not numbered by depth");
+    std::vector<uint32_t> levels{0u};
+    for (uint32_t d = 1; d < kRefitMaxLevels && level[d] != 0u; ++d) levels.push_back(level[d]);
+    levels.push_back(n);
+    if (ctx->d_bvh_ref) {
+        for (size_t d = 0; d + 1 < levels.size(); ++d)
+            hipLaunchKernelGGL(k_refit_refnodes, dim3((levels[d + 1] - levels[d] + 255) / 256), b256, 0, st, nodes, ctx->d_bvh_ref, levels[d], levels[d + 1],
+                               n, ctx->d_refit_refnode);
+        REFIT_TRY(hipGetLastError(), "record map");
+        REFIT_TRY(hipStreamSynchronize(st), "record map");
+    }
+#undef REFIT_TRY
+    ctx->refit_levels = std::move(levels);
+    return TRC_OK;
+}
+
+// maps of the uploaded scene (trc_ctx: d_refit_*, refit_levels), behind whatever the stream still holds; the only part of an update
+// that waits for the device, once per scene
+trc_status refit_prepare(trc_ctx* ctx) {
+    if (!ctx->refit_levels.empty()) return TRC_OK;
+    const trc_status rs = refit_make_maps(ctx);
     if (rs != TRC_OK) {
         (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
         ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
@@ -254,7 +260,7 @@ void trc_refit_free(trc_ctx* ctx) {
 extern "C" {
 
 trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices, uint32_t first, uint32_t count) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_update_vertices: no scene");
     if (count == 0) return TRC_OK;
@@ -266,14 +272,14 @@ trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices,
         for (int k = 0; k < 3; ++k)
             if (!(std::fabs(vertices[i].v[k]) <= 1e37f)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_update_vertices: position not finite or beyond 1e37");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { const trc_status hs = trc_readback_alloc(ctx); if (hs != TRC_OK) return hs; }
-    { const trc_status ps = refit_prepare(ctx); if (ps != TRC_OK) return ps; }
+    TRC_TRY(trc_readback_alloc(ctx));
+    TRC_TRY(refit_prepare(ctx));
     for (hipEvent_t& e : ctx->refit_ev)
         if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return trc_fail(ctx, TRC_ERR_HIP, "trc_update_vertices: hipEventCreate"); }
     hipEvent_t e0 = ctx->refit_ev[0], e1 = ctx->refit_ev[1];
 
     hipStream_t st = ctx->stream;
-    { const trc_status cs = trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st));
     // the copy is queued, so from here on the scene changes: what was derived from the old geometry goes
     trc_scene_changed(ctx, kSceneVerticesMoved);     // (TRC_FLAG_MESH_LIGHTS: the areas changed)
 
@@ -308,7 +314,7 @@ trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices,
 
 trc_status trc_debug_refit_ms(trc_ctx* ctx, float* ms) {
     if (!ctx || !ms) return TRC_ERR_INVALID_ARG;
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }
+    TRC_TRY(trc_flush(ctx));
     *ms = ctx->refit_ms;
     return TRC_OK;
 }

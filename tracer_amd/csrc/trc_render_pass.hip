@@ -71,7 +71,7 @@ trc_status ensure_sobol_tables(trc_ctx* ctx, uint32_t m) {
         std::vector<uint32_t> m32(TRC_SOBOL_DIMS * TRC_SOBOL_MATRIX_SIZE);
         trc_sobol_matrices32(m32.data());
         if (!ctx->d_sobol32) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_sobol32, m32.size() * sizeof(uint32_t)));
-        { const trc_status cs = trc_copy_to_device(ctx, ctx->d_sobol32, m32.data(), m32.size() * sizeof(uint32_t), ctx->stream); if (cs != TRC_OK) return cs; }
+        TRC_TRY(trc_copy_to_device(ctx, ctx->d_sobol32, m32.data(), m32.size() * sizeof(uint32_t), ctx->stream));
         HIP_TRY(ctx, hipMalloc((void**)&ctx->d_sobol_vdc, 2 * TRC_SOBOL_MATRIX_SIZE * sizeof(uint64_t)));
         ctx->sobol_m = ~0u;
     }
@@ -98,19 +98,21 @@ const RenderKernels& render_family(bool lds_scene, uint32_t integrator, bool tri
 
 // One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
 // device (the attribute is set on the current device's copy of the function): remembered in the context, which is bound to one device.
-hipError_t launch_render(trc_ctx* ctx, const RenderKernel& kern, const KRender& kp, const EnvLight& el, const MeshLight& ml, uint32_t grid, uint32_t block, size_t lds) {
-    const void* const fn = kern.fn;
-    if (lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
+hipError_t launch_render(trc_ctx* ctx, const RenderLaunch& r) {
+    const void* const fn = r.kern.fn;
+    if (r.lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
         if (e != hipSuccess) return e;
         ctx->lds_granted.push_back(fn);
     }
-    KRenderEnv kpe;                                     // the k_render*_env kernels' parameters: the launch's and the map's tables
-    if (kern.args == kArgsEnv) { kpe.kp = kp; kpe.el = el; }
-    KRenderMesh kpm;                                    // ... the k_render*_mesh kernels': the launch's and the emissive triangles' tables
-    if (kern.args == kArgsMesh) { kpm.kp = kp; kpm.ml = ml; }
-    void* args[] = {kern.args == kArgsMesh ? static_cast<void*>(&kpm) : kern.args == kArgsEnv ? static_cast<void*>(&kpe) : const_cast<KRender*>(&kp)};
-    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(block), args, lds, ctx->stream);
+    // the parameter block the kernel's RenderArgs asks for: the launch's parameters alone, or with its light's tables behind them
+    KRenderEnv kpe;
+    KRenderMesh kpm;
+    void* params = const_cast<KRender*>(&r.kp);
+    if (r.kern.args == kArgsEnv) { kpe.kp = r.kp; kpe.el = r.el; params = &kpe; }
+    if (r.kern.args == kArgsMesh) { kpm.kp = r.kp; kpm.ml = r.ml; params = &kpm; }
+    void* args[] = {params};
+    const hipError_t e = hipLaunchKernel(fn, dim3(r.grid), dim3(r.block), args, r.lds, ctx->stream);
     const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
     return e != hipSuccess ? e : last;
 }
@@ -185,7 +187,7 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
 constexpr uint32_t kCoalesceBelow = 8, kCoalesceUpTo = 16;
 trc_status trc_flush(trc_ctx* ctx) {
     if (!ctx) return TRC_OK;
-    { const trc_status rs = trc_refit_settle(ctx); if (rs != TRC_OK) return rs; }      // trc_update_vertices returns before its root box has
+    TRC_TRY(trc_refit_settle(ctx));      // trc_update_vertices returns before its root box has arrived
     if (!ctx->has_deferred) return TRC_OK;
     ctx->has_deferred = false;
     const trc_params q = ctx->deferred;
@@ -202,7 +204,7 @@ trc_status trc_flush(trc_ctx* ctx) {
 }
 extern "C" {
 trc_status trc_render(trc_ctx* ctx, const trc_params* p) {
-    { const trc_status st = render_check(ctx, p); if (st != TRC_OK) return st; }
+    TRC_TRY(render_check(ctx, p));
     const bool candidate = p->spp > 0 && p->spp < kCoalesceBelow && !(p->flags & TRC_FLAG_COLLECT_STATS) && !ctx->knobs.no_coalesce;
     if (ctx->has_deferred) {
         trc_params& d = ctx->deferred;
@@ -213,8 +215,7 @@ trc_status trc_render(trc_ctx* ctx, const trc_params* p) {
             ctx->deferred_calls++;
             return d.spp >= kCoalesceUpTo ? trc_flush(ctx) : TRC_OK;
         }
-        const trc_status st = trc_flush(ctx);
-        if (st != TRC_OK) return st;
+        TRC_TRY(trc_flush(ctx));
     }
     if (candidate) { ctx->deferred = *p; ctx->deferred_calls = 1; ctx->has_deferred = true; return TRC_OK; }
     return render_pass(ctx, p, false);
@@ -257,7 +258,7 @@ static trc_status launch_geometry(trc_ctx* ctx, const trc_params* p, RenderLaunc
     r.fits = ctx->width <= 65535u * 4u && ctx->height <= 65535u * 4u;
     if ((p->flags & TRC_FLAG_SMALL_BLOCKS) && r.fits) blk_shift = 2;
     if (ctx->knobs.force_blk_shift > 0) blk_shift = std::min(3u, (uint32_t)ctx->knobs.force_blk_shift - 1u);   // measurement knob: 2^k x 2^k pixel blocks
-    { trc_status ts = trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift); if (ts != TRC_OK) return ts; }
+    TRC_TRY(trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift));
     KRender& kp = r.kp;
     kp.tiles = ctx->d_tiles;
     kp.blk_shift = blk_shift;
@@ -302,8 +303,7 @@ static trc_status render_cold_head(trc_ctx* ctx, const trc_params* p, uint32_t h
     for (uint32_t k = 0; k < max_stages && p->spp - done >= (k == 0 ? 2u : 4u) * stage; ++k, stage *= 2u) {
         trc_params h = *p;
         h.spp = stage; h.frame0 = p->frame0 + done;
-        trc_status st = render_pass(ctx, &h, true);
-        if (st != TRC_OK) return st;
+        TRC_TRY(render_pass(ctx, &h, true));
         ctx->launches--;                   // one trc_render call = one launch in trc_stats
         if (k == 0) ctx->cost_head_age = 1;
         done += stage;
@@ -334,9 +334,9 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
         r.pwg = plan_pwg_lds(ctx, kp.ks.sc, r.pwg_waves, (uint32_t)pwg_per_cu(integrator), hybrid_stack(integrator), pwg_stack_lds_levels(integrator), park_rows);
         if (!r.pwg) park_rows = 0u;
     }
-    const RenderVariant variant = r.mesh ? (ctx->tex_active() ? kVariantMeshTex : kVariantMesh)
-                                : r.env ? (ctx->tex_active() ? kVariantEnvTex : kVariantEnv)
-                                        : ctx->tex_active() ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
+    const bool tex = ctx->tex_active();
+    const RenderVariant variant = r.light == Light::Mesh ? (tex ? kVariantMeshTex : kVariantMesh) : r.light == Light::Env ? (tex ? kVariantEnvTex : kVariantEnv)
+                                : tex ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
     if (!r.kern.fn) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
     ctx->last_kernel.shape = r.dense ? 3u : r.pwg ? 2u : kp.strip > 1 ? 1u : 0u;                 // trc_debug_last_kernel
@@ -356,8 +356,7 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
 static trc_status launch_buffers(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
     KRender& kp = r.kp;
     if (r.sobol) {
-        trc_status ts = ensure_sobol_tables(ctx, kp.sobol_m);
-        if (ts != TRC_OK) return ts;
+        TRC_TRY(ensure_sobol_tables(ctx, kp.sobol_m));
         kp.sobol32 = ctx->d_sobol32;
         kp.sobol_vdc = ctx->d_sobol_vdc;
     }
@@ -368,26 +367,14 @@ static trc_status launch_buffers(trc_ctx* ctx, const trc_params* p, RenderLaunch
     if (!r.stats && !ctx->lds_scene) {
         const size_t rows = kp.ks.sc.stack_ovf_rows;
         const size_t need = rows * kBlock * sizeof(uint32_t) * (r.pwg ? (size_t)r.grid * r.pwg_waves : (size_t)r.grid_cap);   // rows per wavefront
-        if (need > ctx->stack_ovf_bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_stack_ovf) { (void)hipFree(ctx->d_stack_ovf); ctx->d_stack_ovf = nullptr; }
-            ctx->stack_ovf_bytes = 0;
-            if (hipMalloc((void**)&ctx->d_stack_ovf, need) != hipSuccess) return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc traversal-stack overflow rows");
-            ctx->stack_ovf_bytes = need;
-        }
+        TRC_TRY(trc_grow_buffer(ctx, ctx->d_stack_ovf, ctx->stack_ovf_bytes, need, "hipMalloc traversal-stack overflow rows"));
         kp.stack_ovf = ctx->d_stack_ovf;
     }
     // the primary-replay memo rows of the kernels that keep them in global memory (trc_render_config.hpp), per wavefront as above
-    const size_t memo_rows = r.stats || r.sobol || r.env || r.mesh ? 0u : r.pwg ? pwg_memo_rows((int)p->integrator) : (r.dense && TRC_REPLAY_DENSE_GLOBAL) ? (size_t)TRC_REPLAY_DENSE : 0u;
+    const size_t memo_rows = r.stats || r.sobol || r.light != Light::None ? 0u : r.pwg ? pwg_memo_rows((int)p->integrator) : (r.dense && TRC_REPLAY_DENSE_GLOBAL) ? (size_t)TRC_REPLAY_DENSE : 0u;
     if (memo_rows) {
         const size_t need = memo_rows * kBlock * sizeof(uint32_t) * (r.pwg ? (size_t)r.grid * r.pwg_waves : (size_t)r.grid_cap);
-        if (need > ctx->memo_bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_memo) { (void)hipFree(ctx->d_memo); ctx->d_memo = nullptr; }
-            ctx->memo_bytes = 0;
-            if (hipMalloc((void**)&ctx->d_memo, need) != hipSuccess) return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc primary-replay memo rows");
-            ctx->memo_bytes = need;
-        }
+        TRC_TRY(trc_grow_buffer(ctx, ctx->d_memo, ctx->memo_bytes, need, "hipMalloc primary-replay memo rows"));
         kp.memo = ctx->d_memo;
     }
     kp.replay = ctx->knobs.no_primary_replay ? 0u : (uint32_t)(ctx->knobs.replay_min_lanes > 0 ? ctx->knobs.replay_min_lanes : TRC_REPLAY_MIN_LANES);
@@ -407,7 +394,7 @@ static trc_status timed_launch(trc_ctx* ctx, const RenderLaunch& r) {
     auto give_back = [&]() { if (e0) ctx->event_pool.push_back(e0); if (e1) ctx->event_pool.push_back(e1); };
     if (!e0 || !e1) { give_back(); return trc_fail(ctx, TRC_ERR_HIP, "hipEventCreate failed"); }
     hipError_t le = hipEventRecord(e0, ctx->stream);
-    if (le == hipSuccess) le = launch_render(ctx, r.kern, r.kp, r.el, r.ml, r.grid, r.block, r.lds);
+    if (le == hipSuccess) le = launch_render(ctx, r);
     if (le == hipSuccess) le = hipEventRecord(e1, ctx->stream);
     if (le != hipSuccess) { give_back(); return trc_fail(ctx, TRC_ERR_HIP, std::string("k_render launch: ") + hipGetErrorString(le)); }
     ctx->pending.emplace_back(e0, e1);
@@ -417,46 +404,43 @@ static trc_status timed_launch(trc_ctx* ctx, const RenderLaunch& r) {
 
 static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     RenderLaunch r;
-    { const trc_status st = render_check(ctx, p, &r.kp.sobol_m); if (st != TRC_OK) return st; }
+    TRC_TRY(render_check(ctx, p, &r.kp.sobol_m));
     if (p->spp == 0) return TRC_OK;
-    { const trc_status st = trc_refit_settle(ctx); if (st != TRC_OK) return st; }      // ks.root_box of a trc_update_vertices just before
+    TRC_TRY(trc_refit_settle(ctx));      // ks.root_box of a trc_update_vertices just before
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     trc_collect_finished_events(ctx);        // before any launch of this call: it may consume a "not ready" sticky error
     r.stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
     r.sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
-    r.env = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
-    if (r.env) r.el = trc_env_light_view(ctx);
-    r.mesh = (p->flags & TRC_FLAG_MESH_LIGHTS) != 0;
-    if (r.mesh) r.ml = trc_mesh_light_view(ctx);
-    { const trc_status st = launch_geometry(ctx, p, r); if (st != TRC_OK) return st; }
+    r.light = (p->flags & TRC_FLAG_MESH_LIGHTS) ? Light::Mesh : (p->flags & TRC_FLAG_ENV_LIGHT) ? Light::Env : Light::None;      // (render_check: never both)
+    if (r.light == Light::Env) r.el = trc_env_light_view(ctx);
+    if (r.light == Light::Mesh) r.ml = trc_mesh_light_view(ctx);
+    TRC_TRY(launch_geometry(ctx, p, r));
     if (ctx->n_tiles == 0) return TRC_OK;
     if (trc_dyn_lds_bytes(ctx, r.stats) > 160 * 1024) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "traversal stack exceeds the 160 KB LDS of a CU");
     launch_params(ctx, p, r.kp);
     drop_stale_costs(ctx, p, r);
     if (const uint32_t head = cold_head_spp(ctx, p, r, inner)) return render_cold_head(ctx, p, head);
-    { const trc_status st = choose_kernel(ctx, p, r); if (st != TRC_OK) return st; }
-    { const trc_status st = schedule_blocks(ctx, p, r); if (st != TRC_OK) return st; }
-    { const trc_status st = launch_buffers(ctx, p, r); if (st != TRC_OK) return st; }
+    TRC_TRY(choose_kernel(ctx, p, r));
+    TRC_TRY(schedule_blocks(ctx, p, r));
+    TRC_TRY(launch_buffers(ctx, p, r));
     return timed_launch(ctx, r);
 }
 
 extern "C" {
 // developer diagnostic: camera rays answered from the primary-replay memo since the last trc_reset_stats (tracer_abi.h)
 trc_status trc_debug_primary_replays(trc_ctx* ctx, uint64_t* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     unsigned long long h[kStatCount];
-    trc_launch_stats_sum(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TRC_TRY(trc_read_stats_sum(ctx, h, kStatCount));
     *out = h[kStatReplays];
     return TRC_OK;
 }
 
 // developer diagnostic: the chain bound and the work bound of the last launch (tracer_abi.h)
 trc_status trc_debug_launch_shape(trc_ctx* ctx, trc_launch_shape* out) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx || !out) return TRC_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -469,10 +453,10 @@ trc_status trc_debug_launch_shape(trc_ctx* ctx, trc_launch_shape* out) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t stride = ctx->cost_quarters ? kCostSlots : 1u;
     std::vector<uint32_t> c((size_t)n * stride), sp(n, 0u), qs((size_t)n * 4u, 0u);
-    { const trc_status cs = trc_copy_to_host(ctx, c.data(), ctx->d_block_cost, c.size() * 4, ctx->stream); if (cs != TRC_OK) return cs; }
+    TRC_TRY(trc_copy_to_host(ctx, c.data(), ctx->d_block_cost, c.size() * 4, ctx->stream));
     if (stride != 1u && ctx->split_live) {
-        { const trc_status cs = trc_copy_to_host(ctx, sp.data(), ctx->d_split, (size_t)n * 4, ctx->stream); if (cs != TRC_OK) return cs; }
-        { const trc_status cs = trc_copy_to_host(ctx, qs.data(), ctx->d_qsplit, (size_t)n * 16, ctx->stream); if (cs != TRC_OK) return cs; }
+        TRC_TRY(trc_copy_to_host(ctx, sp.data(), ctx->d_split, (size_t)n * 4, ctx->stream));
+        TRC_TRY(trc_copy_to_host(ctx, qs.data(), ctx->d_qsplit, (size_t)n * 16, ctx->stream));
     }
     uint64_t sum = 0, longest = 0;
     uint32_t entries = 0;

@@ -597,7 +597,7 @@ static trc_status sah_build_topology(trc_ctx* ctx, Buffers& buf, const DLeaf* d_
     int cur = 0;
     bool broken = false;
     static_assert(sizeof(uint32_t) * (2u + 2u * (TRC_MAX_BVH_DEPTH + 3u) + 1u) <= kReadbackBytes, "h_readback holds the counter block and the intake flags");
-    { const trc_status hs = trc_readback_alloc(ctx); if (hs != TRC_OK) return hs; }
+    TRC_TRY(trc_readback_alloc(ctx));
     uint32_t* hc = ctx->h_readback;      // pinned: the copy is queued behind k_sah_split and the host goes on launching
     hc[0] = 0;
     for (uint32_t level = 0; n_rows > 0; ++level, cur ^= 1) {

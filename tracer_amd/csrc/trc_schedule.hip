@@ -389,7 +389,7 @@ trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32
             HIP_TRY(ctx, hipMalloc((void**)&ctx->d_order_vals[k], tiles.size() * 4));
         }
         HIP_TRY(ctx, hipMalloc((void**)&ctx->d_order_hist, (trc_sort_hist_words(ctx->n_tiles) + 256) * 4));
-        { const trc_status cs = trc_copy_to_device(ctx, ctx->d_tiles, tiles.data(), tiles.size() * 4, ctx->stream); if (cs != TRC_OK) return cs; }
+        TRC_TRY(trc_copy_to_device(ctx, ctx->d_tiles, tiles.data(), tiles.size() * 4, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->tiles_nranks = nranks; ctx->tiles_rank = rank; ctx->tiles_view_height = view_height; ctx->tiles_blk_shift = blk_shift;
@@ -402,8 +402,8 @@ void drop_stale_costs(trc_ctx* ctx, const trc_params* p, const RenderLaunch& r) 
     if (ctx->cost_strip != r.kp.strip || ctx->cost_quarters != r.quarters_ok) {
         trc_forget_costs(ctx); ctx->cost_strip = r.kp.strip; ctx->cost_quarters = r.quarters_ok;
     }
-    if (ctx->cost_integrator != p->integrator || ctx->cost_env != r.env || ctx->cost_mesh != r.mesh) {
-        trc_forget_costs(ctx); ctx->cost_integrator = p->integrator; ctx->cost_env = r.env; ctx->cost_mesh = r.mesh;
+    if (ctx->cost_integrator != p->integrator || ctx->cost_light != r.light) {
+        trc_forget_costs(ctx); ctx->cost_integrator = p->integrator; ctx->cost_light = r.light;
     }
 }
 
@@ -511,7 +511,7 @@ extern "C" {
 // developer diagnostic: the pixel blocks of the last trc_render (x | y << 16 in units of the block edge) and the duration
 // each one's wavefront measured per sample (shader clocks / (4 spp), the adaptive order's sort key)
 trc_status trc_debug_block_costs(trc_ctx* ctx, uint32_t* tiles, uint32_t* costs, uint32_t capacity, uint32_t* n_blocks, uint32_t* blk_shift) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n_blocks) *n_blocks = ctx->n_tiles;
@@ -519,14 +519,14 @@ trc_status trc_debug_block_costs(trc_ctx* ctx, uint32_t* tiles, uint32_t* costs,
     const uint32_t n = std::min(capacity, ctx->n_tiles);
     if (n == 0 || !ctx->d_tiles) return TRC_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (tiles) { const trc_status cs = trc_copy_to_host(ctx, tiles, ctx->d_tiles, (size_t)n * 4, ctx->stream); if (cs != TRC_OK) return cs; }
+    if (tiles) TRC_TRY(trc_copy_to_host(ctx, tiles, ctx->d_tiles, (size_t)n * 4, ctx->stream));
     if (costs) {
         const uint32_t stride = ctx->cost_quarters ? kCostSlots : 1u;
         std::vector<uint32_t> c((size_t)n * stride), sp(n, 0u), qs((size_t)n * 4u, 0u);
-        { const trc_status cs = trc_copy_to_host(ctx, c.data(), ctx->d_block_cost, c.size() * 4, ctx->stream); if (cs != TRC_OK) return cs; }
+        TRC_TRY(trc_copy_to_host(ctx, c.data(), ctx->d_block_cost, c.size() * 4, ctx->stream));
         if (stride != 1u) {
-            { const trc_status cs = trc_copy_to_host(ctx, sp.data(), ctx->d_split, (size_t)n * 4, ctx->stream); if (cs != TRC_OK) return cs; }
-            { const trc_status cs = trc_copy_to_host(ctx, qs.data(), ctx->d_qsplit, (size_t)n * 16, ctx->stream); if (cs != TRC_OK) return cs; }
+            TRC_TRY(trc_copy_to_host(ctx, sp.data(), ctx->d_split, (size_t)n * 4, ctx->stream));
+            TRC_TRY(trc_copy_to_host(ctx, qs.data(), ctx->d_qsplit, (size_t)n * 16, ctx->stream));
         }
         for (uint32_t i = 0; i < n; ++i) {        // a block that ran in parts: its slowest part, bit 31 set (bit 30: some of them 2x2)
             const uint32_t* q = &c[(size_t)i * stride];

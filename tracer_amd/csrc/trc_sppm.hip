@@ -637,7 +637,7 @@ __global__ void __launch_bounds__(256) k_sppm_seed(uint32_t* rng, uint32_t n, ui
 extern "C" {
 
 trc_status trc_sppm_init(trc_ctx* ctx, uint64_t photon_seed) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_sppm_init before trc_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -687,7 +687,7 @@ trc_status trc_sppm_init(trc_ctx* ctx, uint64_t photon_seed) {
 }
 
 trc_status trc_sppm_frames(trc_ctx* ctx, uint32_t n_frames) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     SppmState* s = ctx->sppm;
     if (!s) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_sppm_frames before trc_sppm_init");
@@ -709,7 +709,7 @@ trc_status trc_sppm_frames(trc_ctx* ctx, uint32_t n_frames) {
     if (nranks > kPhotonSlack / kBlock) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "the grouped SPPM pass splits its photons over at most 64 ranks");
     const uint32_t chunk = (nph / kBlock + nranks - 1) / nranks * kBlock;
     const uint32_t first = std::min(nph, rank * chunk), mine = std::min(chunk, nph - first);
-    { trc_status ts = trc_ensure_tiles(ctx, nranks, rank); if (ts != TRC_OK) return ts; }
+    TRC_TRY(trc_ensure_tiles(ctx, nranks, rank));
     // A rank that owns no tile of a small frame still bounces ITS photon range and takes part in every collective (it returned early
     // here up to round 5 and left the others waiting in the all-reduce: tests/campaigns/fuzz_ranks.sh); only its camera and refine launches are empty.
     if (ctx->n_tiles == 0 && !grouped) return TRC_OK;
@@ -835,50 +835,41 @@ trc_status trc_sppm_hash_cells(trc_ctx* ctx, const float* cells, size_t n, float
     if (n == 0) return TRC_OK;
     if (n > 0x7FFFFFFFu / 3u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_sppm_hash_cells: too many cells in one call");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_in, n * 12));
-    if (hipMalloc((void**)&d_out, n * 4) != hipSuccess) { (void)hipFree(d_in); return trc_fail(ctx, TRC_ERR_OOM, "hipMalloc"); }
-    trc_status ts = trc_copy_to_device(ctx, d_in, cells, n * 12, ctx->stream);
-    if (ts == TRC_OK) {
-        hipLaunchKernelGGL(k_sppm_hash_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_in, (uint32_t)n, hash_scale, d_out);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) ts = trc_fail(ctx, TRC_ERR_HIP, std::string("trc_sppm_hash_cells: ") + hipGetErrorString(e));
-    }
-    if (ts == TRC_OK) ts = trc_copy_to_host(ctx, out, d_out, n * 4, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    return ts;
+    DevBuf d_in, d_out;         // (freeing them waits for whatever a failed step left in flight)
+    TRC_TRY(d_in.alloc(ctx, n * 12, "hash cells"));
+    TRC_TRY(d_out.alloc(ctx, n * 4, "hash values"));
+    TRC_TRY(trc_copy_to_device(ctx, d_in.p, cells, n * 12, ctx->stream));
+    hipLaunchKernelGGL(k_sppm_hash_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_in.as<float>(), (uint32_t)n, hash_scale, d_out.as<float>());
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_sppm_hash_cells: ") + hipGetErrorString(e));
+    return trc_copy_to_host(ctx, out, d_out.p, n * 4, ctx->stream);
 }
 #endif  // TRC_TEST_HOOKS
 
 trc_status trc_sppm_download(trc_ctx* ctx, trc_CameraRecord* cam, trc_PhotonRecord* pho, float* mark, float* count, trc_Complex* cx) {
-    { const trc_status fs_ = trc_flush(ctx); if (fs_ != TRC_OK) return fs_; }      // a kept launch of few samples goes first (trc_render)
+    TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
     SppmState* s = ctx->sppm;
     if (!s) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_sppm_download before trc_sppm_init");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t np = (size_t)s->W * s->H, nph = (size_t)kHashN * kHashN;
-    trc_CameraRecord* d_packed = nullptr;
     if (cam) {
-        HIP_TRY(ctx, hipMalloc((void**)&d_packed, np * sizeof(trc_CameraRecord)));
-        hipLaunchKernelGGL(k_sppm_pack_records, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, s->vp[s->cur], d_packed, (uint32_t)np);
-        const trc_status cs = trc_copy_to_host(ctx, cam, d_packed, np * sizeof(trc_CameraRecord), ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_packed);
-        if (cs != TRC_OK) return cs;
+        DevBuf packed;
+        TRC_TRY(packed.alloc(ctx, np * sizeof(trc_CameraRecord), "packed camera records"));
+        hipLaunchKernelGGL(k_sppm_pack_records, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, s->vp[s->cur], packed.as<trc_CameraRecord>(), (uint32_t)np);
+        TRC_TRY(trc_copy_to_host(ctx, cam, packed.p, np * sizeof(trc_CameraRecord), ctx->stream));
     }
     if (pho) {
         if (s->pho_partial && ctx->grouped()) {           // the per-frame gather moves 40 bytes per photon: the whole records, now (collective)
             const size_t chunk = (nph / kBlock + (size_t)ctx->nranks - 1) / (size_t)ctx->nranks * kBlock;      // trc_sppm_frames' split
-            trc_status cs = trc_coll_allgather(ctx, s->d_pho, chunk * sizeof(trc_PhotonRecord), ctx->stream, "allgather of the photon records (download)");
-            if (cs != TRC_OK) return cs;
+            TRC_TRY(trc_coll_allgather(ctx, s->d_pho, chunk * sizeof(trc_PhotonRecord), ctx->stream, "allgather of the photon records (download)"));
             s->pho_partial = false;
         }
-        { const trc_status cs = trc_copy_to_host(ctx, pho, s->d_pho, nph * sizeof(trc_PhotonRecord), ctx->stream); if (cs != TRC_OK) return cs; }
+        TRC_TRY(trc_copy_to_host(ctx, pho, s->d_pho, nph * sizeof(trc_PhotonRecord), ctx->stream));
     }
     std::vector<uint32_t> hm, hc;
-    if (mark) { hm.resize(nph); const trc_status cs = trc_copy_to_host(ctx, hm.data(), s->d_mark, nph * 4, ctx->stream); if (cs != TRC_OK) return cs; }
-    if (count) { hc.resize(nph); const trc_status cs = trc_copy_to_host(ctx, hc.data(), s->d_count, nph * 4, ctx->stream); if (cs != TRC_OK) return cs; }
+    if (mark) { hm.resize(nph); TRC_TRY(trc_copy_to_host(ctx, hm.data(), s->d_mark, nph * 4, ctx->stream)); }
+    if (count) { hc.resize(nph); TRC_TRY(trc_copy_to_host(ctx, hc.data(), s->d_count, nph * 4, ctx->stream)); }
     DComplex h;
     HIP_TRY(ctx, hipMemcpyAsync(&h, s->d_cx, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
