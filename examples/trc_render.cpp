@@ -7,6 +7,8 @@
 //              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
 //              [--spin N]  after the frame, N more frames of the mesh turned about its own vertical axis (360 / N degrees per frame) through
 //                          trc_update_vertices: no second upload, the tree is refitted in place; frame k goes to <out>.k.png
+//              [--pose N]  the same turn, sent as ONE matrix per frame (trc_pose_vertices: the device keeps the rest vertices and poses
+//                          them itself, 144 bytes cross the bus instead of the vertex array); frame k goes to <out>.k.png
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -37,7 +39,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    uint32_t spin = 0;
+    uint32_t spin = 0, pose = 0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -57,6 +59,11 @@ int main(int argc, char** argv) {
             const int n = std::atoi(argv[++i]);
             if (n <= 0 || n > 100000) { std::fprintf(stderr, "--spin wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
             spin = (uint32_t)n;
+        }
+        else if (a == "--pose" && i + 1 < argc) {                               // moving geometry: one matrix per frame, trc_pose_vertices
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > 100000) { std::fprintf(stderr, "--pose wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
+            pose = (uint32_t)n;
         }
         else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
@@ -234,6 +241,38 @@ int main(int argc, char** argv) {
         }
     } else if (spin) {
         std::fprintf(stderr, "--spin turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+    }
+    if (pose && scene.n_vertex) {
+        // the same turn about the vertical axis through the centre of the mesh's box, as T(c) * R_y(a) * T(-c): the device poses its
+        // own rest copy of the vertices, so the host sends one trc_pose per frame and computes no vertex
+        float lo[3] = {scene.triList[0].v[0], scene.triList[0].v[1], scene.triList[0].v[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+        for (uint32_t i = 0; i < scene.n_vertex; ++i)
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], scene.triList[i].v[k]); hi[k] = std::max(hi[k], scene.triList[i].v[k]); }
+        const float cx = 0.5f * (lo[0] + hi[0]), cz = 0.5f * (lo[2] + hi[2]);
+        const uint32_t first_frame = spin;             // after --spin's frames, when both are given
+        for (uint32_t f = 1; f <= pose; ++f) {
+            const double a = 6.283185307179586 * f / pose;
+            const float ca = (float)std::cos(a), sa = (float)std::sin(a);
+            trc_pose p;
+            std::memset(&p, 0, sizeof p);
+            p.first = 0; p.count = scene.n_vertex;
+            p.model_matrix.columns[0] = {ca, 0.0f, -sa, 0.0f};
+            p.model_matrix.columns[1] = {0.0f, 1.0f, 0.0f, 0.0f};
+            p.model_matrix.columns[2] = {sa, 0.0f, ca, 0.0f};
+            p.model_matrix.columns[3] = {cx - ca * cx - sa * cz, 0.0f, cz + sa * cx - ca * cz, 1.0f};
+            p.normal_matrix = p.model_matrix;          // a rotation is its own inverse transpose; the translation column is not read
+            const auto u0 = std::chrono::steady_clock::now();
+            CHECK(trc_pose_vertices(ctx, &p, 1));
+            const double pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(trc_clear_accum(ctx));
+            CHECK(trc_render(ctx, &prm));
+            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
+            if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+            std::printf("pose %u / %u: trc_pose_vertices %.2f ms -> %s\n", f, pose, pose_ms, name.c_str());
+        }
+    } else if (pose) {
+        std::fprintf(stderr, "--pose turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
     }
     trc_destroy(ctx);
     trc_host_scene_destroy(hs);

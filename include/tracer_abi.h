@@ -52,7 +52,9 @@ extern "C" {
  *    algorithm, the camera rays answered from the memo included (nothing existing changed)
  * 12: TRC_FLAG_MESH_LIGHTS: the emissive triangles of a mesh as sampled lights of traceMIS, knob mesh_light_pick (nothing existing
  *    changed)
- * 13: moving geometry: trc_update_vertices, trc_debug_refit_ms, knob refit_single (nothing existing changed) */
+ * 13: moving geometry: trc_update_vertices, trc_debug_refit_ms, knob refit_single (nothing existing changed)
+ *     added under 13, the number stays: trc_pose, trc_pose_vertices, trc_download_vertices, trc_debug_pose_overflows (posing vertex
+ *     ranges by matrices on the device; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -576,6 +578,52 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
 trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices, uint32_t first, uint32_t count);
 /* device time in ms of the kernels of the last trc_update_vertices (record rewrite + refit, without the transfer) */
 trc_status trc_debug_refit_ms(trc_ctx* ctx, float* ms);
+/* Posed geometry: the rigid (or affine) animation of whole objects, where the host has nothing to say per frame but one matrix per
+ * object.  Each trc_pose names vertices [first, first + count) of the scene's triList and the two matrices to put them under; the
+ * device computes the posed vertices from a REST copy it keeps, and the record rewrite and refit of trc_update_vertices run behind.
+ *  - Rest vertices: the values the caller last gave -- by trc_upload_scene*, then by any trc_update_vertices for its range.  A pose
+ *    is always applied to the rest vertices, never to the previous pose: frame k is M_k * rest, and nothing drifts.  Vertices in no
+ *    range of a call keep their current values, which may be an earlier call's pose.
+ *  - Position, binary32, no contraction, c0..c3 the columns of model_matrix, in this order (simd's matrix times vector, which the
+ *    reference's placement of a primitive uses):  x' = ((c0.x*x + c1.x*y) + c2.x*z) + c3.x, and y', z' alike with .y and .z.  The
+ *    fourth row (the .w lanes) is not read.
+ *  - Normal, N = normal_matrix:  n' = (N.c0*nx + N.c1*ny) + N.c2*nz per component, no translation and NOT normalised (the reference
+ *    shades in the frame of the normal as stored).  The caller passes the inverse transpose of the model matrix; for a rigid pose
+ *    that is the rotation itself.  Column 3 and the .w lanes are not read.  uv is copied.
+ *  - An identity pose reproduces the rest values as values; a -0 may come back as +0 (-0 + 0*y is +0).
+ *  - After the call everything observable is what trc_update_vertices would have left had the host computed those vertices and
+ *    passed them: triangle records, leaf and interior boxes (the right child's bound on a tie), the root box, the records of
+ *    trc_download_bvh, frames, RNG texture and ray counts, the G-buffer, the tables of TRC_FLAG_MESH_LIGHTS.  The one exception: the
+ *    rest copy stays what it was.  It works on the tree of every upload path and with both values of knob refit_single.  The same
+ *    things survive (triangle materials, textures, environment, camera, density, accumulator, RNG texture) and the same are dropped
+ *    (G-buffer, denoiser history, mesh-light tables); the launch planner's block costs are kept.  Launches kept back for coalescing
+ *    run first.  Not collective.  The 144 * n_poses bytes are copied out of the caller's array before the call returns; the kernels
+ *    run behind it on the context's stream.
+ *  - TRC_ERR_NO_SCENE before any upload.  TRC_ERR_INVALID_ARG: poses == NULL with n_poses > 0, a range with count == 0 or with
+ *    first + count > the scene's n_vertex, two ranges that overlap, a non-finite value among the 21 matrix entries that are read, or
+ *    n_poses > 0 on a scene without triangles.  TRC_ERR_OOM if the rest copy cannot be allocated.  On any error nothing has changed.
+ *    n_poses == 0 is TRC_OK and changes nothing.  The ranges may come in any order.
+ *  - Overflow: the host cannot check posed positions without computing them.  Keeping every posed position finite and within 1e37
+ *    in magnitude (trc_update_vertices' bound) is the CALLER's contract.  The kernel counts the positions that break it, and
+ *    trc_debug_pose_overflows reports the count of the last trc_pose_vertices (it waits for that call's kernels).  A frame rendered
+ *    after a non-zero count is not defined; no index is ever derived from a position, so nothing is read or written out of bounds,
+ *    and a later pose within the bound (or any trc_update_vertices / upload) makes the scene well defined again.
+ * The rest copy is 32 B per vertex more device memory, allocated by the first trc_pose_vertices of a scene (a copy of the vertices
+ * as they are then) and freed with the scene; a host that never poses pays nothing.  While it exists trc_update_vertices writes
+ * its range into it as well. */
+typedef struct trc_pose {
+    uint32_t     first, count;     /* vertices [first, first + count) of the scene's triList */
+    uint32_t     _pad[2];
+    trc_float4x4 model_matrix;     /* positions */
+    trc_float4x4 normal_matrix;    /* normals: the caller's inverse transpose (the rotation itself for a rigid pose) */
+} trc_pose;
+trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_poses);
+/* the CURRENT vertices [first, first + count) as they are on the device (position, normal, uv): what the last upload, update or pose
+ * left.  TRC_ERR_NO_SCENE before any upload; TRC_ERR_INVALID_ARG: first + count > the scene's n_vertex, out == NULL with count > 0, or
+ * a scene without triangles.  count == 0 on a scene with triangles is TRC_OK.  Synchronous, like every download. */
+trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count);
+/* the number of posed positions of the last trc_pose_vertices that came out non-finite or beyond 1e37 in magnitude (0 before any) */
+trc_status trc_debug_pose_overflows(trc_ctx* ctx, uint32_t* n);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -1082,6 +1130,7 @@ TRC_SA(sizeof(trc_Square) == 272 && offsetof(trc_Square, axis_j) == 1 && offseto
 TRC_SA(sizeof(trc_Cube) == 240 && offsetof(trc_Cube, normal_matrix) == 64 && offsetof(trc_Cube, inverse_matrix) == 128 &&
        offsetof(trc_Cube, box) == 192 && offsetof(trc_Cube, material) == 224, "Cube");
 TRC_SA(sizeof(trc_TriangleVertex) == 32, "TriangleVertex");
+TRC_SA(sizeof(trc_pose) == 144 && offsetof(trc_pose, model_matrix) == 16 && offsetof(trc_pose, normal_matrix) == 80, "pose");
 TRC_SA(sizeof(trc_TextureInfo) == 32 && offsetof(trc_TextureInfo, albedo) == 16, "TextureInfo");
 TRC_SA(sizeof(trc_Material) == 64 && offsetof(trc_Material, medium) == 4 && offsetof(trc_Material, specular) == 8 &&
        offsetof(trc_Material, eta) == 12 && offsetof(trc_Material, roughness) == 16 &&

@@ -8,6 +8,8 @@
 //   3. every file reader on well-formed files it writes itself (pbrt scene with plymesh / disk / cylinder / texture, PLY in
 //      three encodings, OBJ, pbrt density, Radiance .hdr), then on `--fuzz N` mutations of each: a reader must return a
 //      status, never crash, over-read or leak
+//   4. the range check of trc_pose_vertices (tracer_amd/csrc/pose_ranges.hpp, host code of the HIP library that includes nothing of
+//      HIP) on hostile tables: first + count wrapping past 2^32, equal ranges, a table of one, non-finite matrix entries
 // "build host code under -fsanitize=thread,address".
 #include <cmath>
 #include <cstdio>
@@ -20,6 +22,7 @@
 
 #include "tracer_abi.h"
 #include "../../oracle/oracle.h"
+#include "../../tracer_amd/csrc/pose_ranges.hpp"
 
 static int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "EXPECT failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); ++g_fail; } } while (0)
@@ -142,6 +145,42 @@ static void sppm_pass() {
     trc_host_scene_destroy(hs);
 }
 
+// ---------------------------------------------------------------- trc_pose_vertices' table check
+static trc_pose make_pose(uint32_t first, uint32_t count) {
+    trc_pose p; std::memset(&p, 0, sizeof p);
+    p.first = first; p.count = count;
+    for (int c = 0; c < 4; ++c) { float* m = &p.model_matrix.columns[c].x; float* n = &p.normal_matrix.columns[c].x; m[c] = n[c] = 1.0f; }
+    return p;
+}
+static void pose_tables() {
+    const uint32_t n_vertex = 1000;
+    std::vector<uint32_t> order;
+    auto ok = [&](const std::vector<trc_pose>& t) { return trc_pose_table_check(t.data(), (uint32_t)t.size(), n_vertex, order) == nullptr; };
+    EXPECT(trc_pose_table_check(nullptr, 0, n_vertex, order) == nullptr && order.empty());
+    EXPECT(trc_pose_table_check(nullptr, 3, n_vertex, order) != nullptr);
+    EXPECT(ok({make_pose(0, 1000)}) && order.size() == 1);                                     // n_poses of 1, the whole array
+    EXPECT(ok({make_pose(999, 1)}) && !ok({make_pose(1000, 1)}) && !ok({make_pose(999, 2)}));
+    EXPECT(!ok({make_pose(0, 0)}) && !ok({make_pose(5, 3), make_pose(9, 0)}));
+    EXPECT(!ok({make_pose(0xFFFFFFFFu, 2)}) && !ok({make_pose(2, 0xFFFFFFFFu)}) && !ok({make_pose(0xFFFFFF00u, 0x200u)}));   // first + count wraps
+    EXPECT(!ok({make_pose(10, 5), make_pose(10, 5)}));                                         // equal ranges
+    EXPECT(!ok({make_pose(10, 5), make_pose(14, 1)}) && !ok({make_pose(14, 3), make_pose(0, 15)}) && !ok({make_pose(0, 1000), make_pose(500, 1)}));
+    EXPECT(ok({make_pose(500, 500), make_pose(10, 5), make_pose(0, 10), make_pose(15, 485)}));  // unsorted, back to back, up to the end
+    EXPECT(order.size() == 4 && order[0] == 2 && order[1] == 1 && order[2] == 3 && order[3] == 0);
+    trc_pose bad = make_pose(0, 10);
+    bad.model_matrix.columns[3].y = NAN;
+    EXPECT(!ok({bad}));
+    bad = make_pose(0, 10); bad.normal_matrix.columns[2].z = INFINITY;
+    EXPECT(!ok({bad}));
+    bad = make_pose(0, 10); bad.model_matrix.columns[1].w = NAN; bad.normal_matrix.columns[3].x = INFINITY;      // lanes that are not read
+    EXPECT(ok({bad}));
+    // a large table of unit ranges in reverse order, and the same with one duplicate in the middle
+    std::vector<trc_pose> many;
+    for (uint32_t i = 0; i < n_vertex; ++i) many.push_back(make_pose(n_vertex - 1 - i, 1));
+    EXPECT(ok(many) && order.front() == n_vertex - 1 && order.back() == 0);
+    many[n_vertex / 2].first = 3;
+    EXPECT(!ok(many));
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -207,6 +246,7 @@ int main(int argc, char** argv) {
     build_and_render(false);
     other.join();
     sppm_pass();
+    pose_tables();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

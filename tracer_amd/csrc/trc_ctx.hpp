@@ -170,11 +170,19 @@ struct trc_ctx {
     uint32_t* d_refit_parent = nullptr;     // [n_nodes] fat node that holds this fat node's box (root: itself)
     uint32_t* d_refit_refnode = nullptr;    // [n_nodes] device-built trees: this fat node's record in d_bvh_ref
     uint32_t* d_refit_arrive = nullptr;     // [n_nodes] arrival counters of the single-launch climb (zero between updates)
-    float* d_refit_root = nullptr;          // [8] the refitted root box
+    float* d_refit_root = nullptr;          // [12] the refitted root box in words 0..5 (the root's store zeroes 6 and 7); word 8: pose overflows
     std::vector<uint32_t> refit_levels;     // first fat node of every depth, and n_nodes behind them (the fat nodes are numbered by depth)
     float refit_ms = 0.0f;                  // device time of the last update's kernels (trc_debug_refit_ms)
     hipEvent_t refit_ev[3] = {nullptr, nullptr, nullptr};      // around the update's kernels; behind the root box's copy to h_readback
     bool refit_pending = false;             // ks.root_box and refit_ms still wait for refit_ev[2] (trc_refit_settle)
+    // trc_pose_vertices (trc_refit.hip): the rest copy of d_verts, made by the first pose of a scene, and the pose table of the last
+    // call; freed with the scene (trc_refit_free).  The kernel adds its overflows to word kPoseCountWord of d_refit_root, which is
+    // never put back to zero: the count of a call is the difference to what the call before left
+    trc_TriangleVertex* d_rest = nullptr;
+    trc_pose* d_pose_table = nullptr; size_t pose_table_bytes = 0;
+    uint32_t pose_count_seen = 0;           // the counter word as last read back
+    uint32_t pose_overflows = 0;            // of the last trc_pose_vertices (trc_debug_pose_overflows)
+    bool refit_posed = false;               // the pending read-back carries the counter word as well
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -445,7 +453,7 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
     if (!ctx->h_readback) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_readback, kReadbackBytes, hipHostMallocDefault));
     return TRC_OK;
 }
-trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices left for later (ks.root_box)
+trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices left for later (ks.root_box, the pose's overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
 void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays and the refit maps (no-op when absent)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
@@ -467,7 +475,7 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //                       scene: also forgets the block costs and releases the old scene (trc_release_scene: blob, reference-layout
 //                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
-//   kSceneVerticesMoved trc_update_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
+//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
 enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:

@@ -15,18 +15,26 @@
 // A union keeps the RIGHT child's bound when the two compare equal (-0 against +0): minss / maxss of box_union(left, right), what
 // the host builder and the device SAH build leave in a record.  The maps (parent of every fat node, its record in d_bvh_ref, the
 // first node of every depth) are made by the first update of a scene and freed with its blob.
+//
+// trc_pose_vertices computes the new vertices on the device instead of receiving them, and then runs the same tail (refit_run):
+//   k_pose_vertices     ONE launch for all ranges of a call: thread g of the concatenated ranges finds its range in the sorted pose
+//                       table by bisection (the table's _pad[0] is the range's first g), reads the vertex from the rest copy d_rest
+//                       and writes it, posed, to d_verts; two 16 B accesses per vertex each way
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "dev_trileaf.hpp"
+#include "pose_ranges.hpp"
 #include "trc_ctx.hpp"
 
 namespace {
 
 constexpr uint32_t kRefitMaxLevels = TRC_MAX_BVH_DEPTH + 1;     // interior nodes have depth 0 .. TRC_MAX_BVH_DEPTH - 1
 constexpr uint32_t kRefitBad = kRefitMaxLevels;                 // word of the level table: the numbering is not by depth
+constexpr uint32_t kRefitRootWords = 12;                        // d_refit_root: the box in 0..5, 6 and 7 zeroed by the root's store, ...
+constexpr uint32_t kPoseCountWord = 8;                          // ... and the running count of pose overflows (trc_ctx.hpp)
 
 __device__ __forceinline__ float keep_right_min(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float keep_right_max(float a, float b) { return a > b ? a : b; }
@@ -177,6 +185,34 @@ __global__ void __launch_bounds__(256) k_refit_climb(KRefit p, const uint32_t* _
     }
 }
 
+// ---- the pose: verts[v] = M * rest[v] for every vertex of every range, in the operation order of include/tracer_abi.h.
+// table: the call's poses sorted by first, _pad[0] = the number of vertices in the ranges before (host, trc_pose_vertices); total: in all
+__global__ void __launch_bounds__(256) k_pose_vertices(const float4* __restrict__ rest, float4* __restrict__ verts, uint32_t n_vertex,
+                                                       const trc_pose* __restrict__ table, uint32_t n_poses, uint32_t total, uint32_t* __restrict__ overflows) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= total) return;
+    uint32_t lo = 0, hi = n_poses;                                  // the last range that starts at or before g
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (table[mid]._pad[0] <= g) lo = mid; else hi = mid;
+    }
+    const uint32_t v = table[lo].first + (g - table[lo]._pad[0]);
+    if (v >= n_vertex) return;                                      // (the host refused such a table)
+    const float4* m = reinterpret_cast<const float4*>(&table[lo].model_matrix);      // 4 columns, then the normal matrix's
+    const float4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3], n0 = m[4], n1 = m[5], n2 = m[6];
+    const float4 a = rest[2 * (size_t)v], b = rest[2 * (size_t)v + 1];              // x y z nx | ny nz u v
+    const float x = ((c0.x * a.x + c1.x * a.y) + c2.x * a.z) + c3.x;
+    const float y = ((c0.y * a.x + c1.y * a.y) + c2.y * a.z) + c3.y;
+    const float z = ((c0.z * a.x + c1.z * a.y) + c2.z * a.z) + c3.z;
+    const float nx = (n0.x * a.w + n1.x * b.x) + n2.x * b.y;
+    const float ny = (n0.y * a.w + n1.y * b.x) + n2.y * b.y;
+    const float nz = (n0.z * a.w + n1.z * b.x) + n2.z * b.y;
+    verts[2 * (size_t)v] = make_float4(x, y, z, nx);
+    verts[2 * (size_t)v + 1] = make_float4(ny, nz, b.z, b.w);
+    if (!(fabsf(x) <= 1e37f) || !(fabsf(y) <= 1e37f) || !(fabsf(z) <= 1e37f))      // the caller's contract, broken: counted, never an index
+        __hip_atomic_fetch_add(overflows, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // the maps themselves (refit_prepare frees what a failure leaves half made)
 trc_status refit_make_maps(trc_ctx* ctx) {
     const DScene& sc = ctx->ks.sc;
@@ -194,13 +230,15 @@ trc_status refit_make_maps(trc_ctx* ctx) {
     } while (0)
     REFIT_TRY(hipMalloc((void**)&ctx->d_refit_parent, (size_t)n * 4), "parent map");
     REFIT_TRY(hipMalloc((void**)&ctx->d_refit_arrive, (size_t)n * 4), "arrival counters");
-    REFIT_TRY(hipMalloc((void**)&ctx->d_refit_root, 8 * sizeof(float)), "root box");
+    REFIT_TRY(hipMalloc((void**)&ctx->d_refit_root, kRefitRootWords * sizeof(float)), "root box");
+    ctx->pose_count_seen = 0;
     TRC_TRY(level_buf.alloc(ctx, sizeof level, "level table"));
     uint32_t* const d_level = level_buf.as<uint32_t>();
     if (ctx->d_bvh_ref) REFIT_TRY(hipMalloc((void**)&ctx->d_refit_refnode, (size_t)n * 4), "record map");
     REFIT_TRY(hipMemsetAsync(ctx->d_refit_parent, 0, (size_t)n * 4, st), "memset");
     REFIT_TRY(hipMemsetAsync(ctx->d_refit_arrive, 0, (size_t)n * 4, st), "memset");
     REFIT_TRY(hipMemsetAsync(d_level, 0, sizeof level, st), "memset");
+    REFIT_TRY(hipMemsetAsync(ctx->d_refit_root, 0, kRefitRootWords * sizeof(float), st), "memset");
     hipLaunchKernelGGL(k_refit_parents, grid, b256, 0, st, nodes, n, ctx->d_refit_parent);
     hipLaunchKernelGGL(k_refit_levels, grid, b256, 0, st, ctx->d_refit_parent, n, d_level);
     REFIT_TRY(hipGetLastError(), "map kernels");
@@ -235,6 +273,59 @@ trc_status refit_prepare(trc_ctx* ctx) {
     return rs;
 }
 
+// What both entry points do before anything changes: the pinned read-back buffer, the maps, the events.  `who` names the caller
+trc_status refit_begin(trc_ctx* ctx, const char* who) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TRC_TRY(trc_readback_alloc(ctx));
+    TRC_TRY(refit_prepare(ctx));
+    for (hipEvent_t& e : ctx->refit_ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return trc_fail(ctx, TRC_ERR_HIP, std::string(who) + ": hipEventCreate"); }
+    return TRC_OK;
+}
+
+// ... and behind their vertices, on the context's stream: [the pose kernel,] the records of the triangles that name a vertex of
+// [first, first + count), every box of the tree, the root box on its way back.  pose_total != 0: trc_pose_vertices, whose sorted
+// table of n_poses ranges (pose_total vertices in all) is in d_pose_table; [first, first + count) is then the hull of its ranges --
+// a triangle of the hull that no range touched gets the bits it had, and keeps its material
+trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_poses = 0, uint32_t pose_total = 0) {
+    const DScene& sc = ctx->ks.sc;
+    hipEvent_t e0 = ctx->refit_ev[0], e1 = ctx->refit_ev[1];
+    hipStream_t st = ctx->stream;
+    KRefit p{};
+    p.nodes = reinterpret_cast<uint4*>(ctx->d_blob + sc.off_nodes); p.n_nodes = sc.n_nodes;
+    p.verts = ctx->d_verts; p.idx = ctx->d_idx; p.n_tri = sc.n_triangles;
+    p.ref = ctx->d_bvh_ref; p.refnode = ctx->d_refit_refnode; p.n_ref = ctx->d_bvh_ref ? ctx->n_bvh_ref : 0u;
+    p.root = ctx->d_refit_root;
+    const dim3 b256(256);
+    HIP_TRY(ctx, hipEventRecord(e0, st));
+    if (pose_total)
+        hipLaunchKernelGGL(k_pose_vertices, dim3((pose_total + 255) / 256), b256, 0, st, reinterpret_cast<const float4*>(ctx->d_rest),
+                           reinterpret_cast<float4*>(ctx->d_verts), ctx->n_vertex, ctx->d_pose_table, n_poses, pose_total,
+                           reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord);
+    hipLaunchKernelGGL(k_refit_triangles, dim3((sc.n_triangles + 255) / 256), b256, 0, st, ctx->d_verts, ctx->d_idx, sc.n_triangles, first, count,
+                       reinterpret_cast<float4*>(ctx->d_blob + sc.off_tripos), reinterpret_cast<float4*>(ctx->d_blob + sc.off_triattr));
+    if (ctx->knobs.refit_single) {
+        hipLaunchKernelGGL(k_refit_climb, dim3((sc.n_nodes + 255) / 256), b256, 0, st, p, ctx->d_refit_parent, ctx->d_refit_arrive);
+    } else {
+        const std::vector<uint32_t>& lv = ctx->refit_levels;
+        for (size_t d = lv.size() - 1; d-- > 0;)
+            hipLaunchKernelGGL(k_refit_level, dim3((lv[d + 1] - lv[d] + 255) / 256), b256, 0, st, p, lv[d], lv[d + 1]);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(e1, st));
+    // the root box is a kernel PARAMETER of every launch (KScene): it is copied back behind the refit and read by the next entry
+    // point that is entered (trc_refit_settle, at the top of trc_flush and render_pass), so this call does not wait for the device.
+    // A pose's overflow count travels with it
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_readback, ctx->d_refit_root, (pose_total ? kPoseCountWord + 1 : 6) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->refit_ev[2], st));
+    ctx->refit_pending = true;
+    ctx->refit_posed = pose_total != 0;
+    // the picture changed a little, as under a camera that moves a little (trc_set_camera): the recorded block costs stay, and the
+    // next ordered launch is one pass on the last launch's raw durations
+    if (ctx->cost_valid) { ctx->plan_streak = 0; ctx->cost_fresh_next = true; }
+    return TRC_OK;
+}
+
 }  // namespace
 
 // the root box of the last update into ks (a kernel PARAMETER of every launch) and the device time of its kernels; waits for them
@@ -243,14 +334,22 @@ trc_status trc_refit_settle_pending(trc_ctx* ctx) {
     HIP_TRY(ctx, hipEventSynchronize(ctx->refit_ev[2]));      // on an error the box stays pending: no launch runs on the old one
     std::memcpy(ctx->ks.root_box, ctx->h_readback, 6 * sizeof(float));
     ctx->refit_pending = false;
+    if (ctx->refit_posed) {
+        ctx->pose_overflows = ctx->h_readback[kPoseCountWord] - ctx->pose_count_seen;      // (modulo 2^32, as the counter itself)
+        ctx->pose_count_seen = ctx->h_readback[kPoseCountWord];
+        ctx->refit_posed = false;
+    }
     (void)hipEventElapsedTime(&ctx->refit_ms, ctx->refit_ev[0], ctx->refit_ev[1]);
     return TRC_OK;
 }
 
 void trc_refit_free(trc_ctx* ctx) {
     for (hipEvent_t& e : ctx->refit_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    ctx->refit_pending = false;
+    ctx->refit_pending = ctx->refit_posed = false;
     (void)hipFree(ctx->d_verts); (void)hipFree(ctx->d_idx);
+    (void)hipFree(ctx->d_rest); (void)hipFree(ctx->d_pose_table);
+    ctx->d_rest = nullptr; ctx->d_pose_table = nullptr; ctx->pose_table_bytes = 0;
+    ctx->pose_count_seen = ctx->pose_overflows = 0;
     (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
     ctx->d_verts = nullptr; ctx->d_idx = nullptr; ctx->n_vertex = 0;
     ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
@@ -271,44 +370,67 @@ trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices,
     for (uint32_t i = 0; i < count; ++i)
         for (int k = 0; k < 3; ++k)
             if (!(std::fabs(vertices[i].v[k]) <= 1e37f)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_update_vertices: position not finite or beyond 1e37");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TRC_TRY(trc_readback_alloc(ctx));
-    TRC_TRY(refit_prepare(ctx));
-    for (hipEvent_t& e : ctx->refit_ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return trc_fail(ctx, TRC_ERR_HIP, "trc_update_vertices: hipEventCreate"); }
-    hipEvent_t e0 = ctx->refit_ev[0], e1 = ctx->refit_ev[1];
+    TRC_TRY(refit_begin(ctx, "trc_update_vertices"));
 
     hipStream_t st = ctx->stream;
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st));
-    // the copy is queued, so from here on the scene changes: what was derived from the old geometry goes
+    // the copy is queued, so from here on the scene changed: what was derived from the old geometry goes
     trc_scene_changed(ctx, kSceneVerticesMoved);     // (TRC_FLAG_MESH_LIGHTS: the areas changed)
+    // a scene that has been posed keeps rest vertices: these are the caller's last values for the range
+    if (ctx->d_rest) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rest + first, ctx->d_verts + first, (size_t)count * sizeof(trc_TriangleVertex), hipMemcpyDeviceToDevice, st));
+    return refit_run(ctx, first, count);
+}
 
-    KRefit p{};
-    p.nodes = reinterpret_cast<uint4*>(ctx->d_blob + sc.off_nodes); p.n_nodes = sc.n_nodes;
-    p.verts = ctx->d_verts; p.idx = ctx->d_idx; p.n_tri = sc.n_triangles;
-    p.ref = ctx->d_bvh_ref; p.refnode = ctx->d_refit_refnode; p.n_ref = ctx->d_bvh_ref ? ctx->n_bvh_ref : 0u;
-    p.root = ctx->d_refit_root;
-    const dim3 b256(256);
-    HIP_TRY(ctx, hipEventRecord(e0, st));
-    hipLaunchKernelGGL(k_refit_triangles, dim3((sc.n_triangles + 255) / 256), b256, 0, st, ctx->d_verts, ctx->d_idx, sc.n_triangles, first, count,
-                       reinterpret_cast<float4*>(ctx->d_blob + sc.off_tripos), reinterpret_cast<float4*>(ctx->d_blob + sc.off_triattr));
-    if (ctx->knobs.refit_single) {
-        hipLaunchKernelGGL(k_refit_climb, dim3((sc.n_nodes + 255) / 256), b256, 0, st, p, ctx->d_refit_parent, ctx->d_refit_arrive);
-    } else {
-        const std::vector<uint32_t>& lv = ctx->refit_levels;
-        for (size_t d = lv.size() - 1; d-- > 0;)
-            hipLaunchKernelGGL(k_refit_level, dim3((lv[d + 1] - lv[d] + 255) / 256), b256, 0, st, p, lv[d], lv[d + 1]);
+trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_poses) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_pose_vertices: no scene");
+    if (n_poses == 0) return TRC_OK;
+    if (ctx->ks.sc.n_triangles == 0 || !ctx->d_verts) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_pose_vertices: the scene has no triangles");
+    std::vector<uint32_t> order;
+    if (const char* why = trc_pose_table_check(poses, n_poses, ctx->n_vertex, order)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_pose_vertices: ") + why);
+    // the kernel's table: sorted by first, every range with the number of vertices before it (no two overlap: the sum is <= n_vertex)
+    std::vector<trc_pose> table(n_poses);
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < n_poses; ++i) {
+        table[i] = poses[order[i]];
+        table[i]._pad[0] = total; table[i]._pad[1] = 0;
+        total += table[i].count;
     }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(e1, st));
-    // the root box is a kernel PARAMETER of every launch (KScene): it is copied back behind the refit and read by the next entry
-    // point that is entered (trc_refit_settle, at the top of trc_flush and render_pass), so this call does not wait for the device
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_readback, ctx->d_refit_root, 6 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->refit_ev[2], st));
-    ctx->refit_pending = true;
-    // the picture changed a little, as under a camera that moves a little (trc_set_camera): the recorded block costs stay, and the
-    // next ordered launch is one pass on the last launch's raw durations
-    if (ctx->cost_valid) { ctx->plan_streak = 0; ctx->cost_fresh_next = true; }
+    const uint32_t hull_first = table.front().first, hull_count = table.back().first - hull_first + table.back().count;
+    TRC_TRY(refit_begin(ctx, "trc_pose_vertices"));
+    TRC_TRY(trc_grow_buffer(ctx, ctx->d_pose_table, ctx->pose_table_bytes, table.size() * sizeof(trc_pose), "trc_pose_vertices: hipMalloc pose table"));
+    hipStream_t st = ctx->stream;
+    if (!ctx->d_rest) {      // the first pose of this scene: no pose has written d_verts yet, so they are the caller's values
+        const size_t bytes = (size_t)ctx->n_vertex * sizeof(trc_TriangleVertex);
+        DevBuf rest;
+        TRC_TRY(rest.alloc(ctx, bytes, "rest vertices (trc_pose_vertices)"));
+        HIP_TRY(ctx, hipMemcpyAsync(rest.p, ctx->d_verts, bytes, hipMemcpyDeviceToDevice, st));
+        ctx->d_rest = static_cast<trc_TriangleVertex*>(rest.release());
+    }
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_pose_table, table.data(), table.size() * sizeof(trc_pose), st));
+    trc_scene_changed(ctx, kSceneVerticesMoved);
+    return refit_run(ctx, hull_first, hull_count, n_poses, total);
+}
+
+trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_download_vertices: no scene");
+    if (ctx->ks.sc.n_triangles == 0 || !ctx->d_verts) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_vertices: the scene has no triangles");
+    if (first > ctx->n_vertex || count > ctx->n_vertex - first) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_vertices: first + count > n_vertex");
+    if (count == 0) return TRC_OK;
+    if (!out) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_vertices: out == NULL with count > 0");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TRC_TRY(trc_copy_to_host(ctx, out, ctx->d_verts + first, (size_t)count * sizeof(trc_TriangleVertex), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TRC_OK;
+}
+
+trc_status trc_debug_pose_overflows(trc_ctx* ctx, uint32_t* n) {
+    if (!ctx || !n) return TRC_ERR_INVALID_ARG;
+    TRC_TRY(trc_flush(ctx));
+    *n = ctx->pose_overflows;
     return TRC_OK;
 }
 

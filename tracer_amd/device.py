@@ -121,6 +121,9 @@ def _load(path, hooks=False):
     L.trc_upload_triangle_materials.argtypes = [vp, vp, u32]
     L.trc_update_vertices.argtypes = [vp, vp, u32, u32]
     L.trc_debug_refit_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.trc_pose_vertices.argtypes = [vp, C.POINTER(abi.Pose), u32]
+    L.trc_download_vertices.argtypes = [vp, vp, u32, u32]
+    L.trc_debug_pose_overflows.argtypes = [vp, C.POINTER(u32)]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -148,6 +151,19 @@ def _load(path, hooks=False):
     return L
 
 
+def make_poses(poses):
+    """ctypes array of abi.Pose from a sequence of (first, count, model, normal); the matrices are (4, 4), model[r][c] row r column c"""
+    arr = (abi.Pose * len(poses))()
+    for k, (first, count, model, normal) in enumerate(poses):
+        arr[k].first, arr[k].count = int(first), int(count)
+        for name, m in (("model_matrix", model), ("normal_matrix", normal)):
+            m = np.asarray(m, dtype=np.float32).reshape(4, 4)
+            cols = getattr(arr[k], name).columns
+            for c in range(4):
+                cols[c].x, cols[c].y, cols[c].z, cols[c].w = (float(m[r, c]) for r in range(4))
+    return arr
+
+
 def group_unique_id():
     buf = (C.c_uint8 * abi.TRC_UNIQUE_ID_BYTES)()
     st = lib().trc_group_unique_id(buf)
@@ -168,6 +184,7 @@ class Tracer:
             self._h = None
             raise TracerError(f"trc_create(device={device})", st, self._L.trc_status_string(st).decode())
         self.width = self.height = 0
+        self._n_vertex = 0               # of the scene uploaded through this object (download_vertices' default count)
 
     def _check(self, st, what):
         if st != abi.OK:
@@ -189,6 +206,7 @@ class Tracer:
     # --- scene / camera / frame -------------------------------------------------
     def upload_scene(self, scene_view):
         self._check(self._L.trc_upload_scene(self._h, C.byref(scene_view)), "trc_upload_scene")
+        self._n_vertex = scene_view.n_vertex
 
     def set_environment_map(self, rgb):
         """(h, w, 3) float32 equirectangular environment; None returns to the constant one."""
@@ -231,8 +249,32 @@ class Tracer:
         buf = v if v.size else np.zeros((1, 8), np.float32)      # an empty array is count == 0, never NULL with a count
         self._check(self._L.trc_update_vertices(self._h, buf.ctypes.data, first, v.shape[0]), "trc_update_vertices")
 
+    def pose_vertices(self, poses):
+        """trc_pose_vertices: `poses` is a ctypes array of abi.Pose, or a sequence of (first, count, model, normal) with the matrices
+        as (4, 4) arrays in the usual row-major mathematical layout (model[r][c]; stored column-major, as simd does).  Every range is
+        posed from the scene's REST vertices on the device, and the tree is refitted in place.  The accumulator is not cleared."""
+        if not (isinstance(poses, C.Array) and poses._type_ is abi.Pose):
+            poses = make_poses(poses)
+        self._check(self._L.trc_pose_vertices(self._h, poses if len(poses) else None, len(poses)), "trc_pose_vertices")
+
+    def download_vertices(self, first=0, count=None):
+        """trc_download_vertices: the current vertices [first, first + count) on the device as (count, 8) float32 rows (position,
+        normal, uv); count None: up to the end of the scene's vertex list."""
+        if count is None:
+            count = max(self._n_vertex - first, 0)
+        out = np.empty((max(count, 0), 8), dtype=np.float32)
+        buf = out if out.size else np.zeros((1, 8), np.float32)
+        self._check(self._L.trc_download_vertices(self._h, buf.ctypes.data, first, count), "trc_download_vertices")
+        return out
+
+    def pose_overflows(self):
+        """posed positions of the last pose_vertices that came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
+        n = C.c_uint32(0)
+        self._check(self._L.trc_debug_pose_overflows(self._h, C.byref(n)), "trc_debug_pose_overflows")
+        return n.value
+
     def refit_ms(self):
-        """device time in ms of the kernels of the last update_vertices (trc_debug_refit_ms)"""
+        """device time in ms of the kernels of the last update_vertices or pose_vertices (trc_debug_refit_ms)"""
         ms = C.c_float(0)
         self._check(self._L.trc_debug_refit_ms(self._h, C.byref(ms)), "trc_debug_refit_ms")
         return ms.value
@@ -310,14 +352,17 @@ class Tracer:
     def upload_scene_lbvh(self, leaves_view):
         """Scene whose bvhList holds only leaf records (HostScene.leaves_view()); the tree is built on the GPU."""
         self._check(self._L.trc_upload_scene_lbvh(self._h, C.byref(leaves_view)), "trc_upload_scene_lbvh")
+        self._n_vertex = leaves_view.n_vertex
 
     def upload_scene_sah(self, leaves_view):
         """Same input as upload_scene_lbvh; the reference's binned-SAH tree (BVH::buildTree), built on the GPU."""
         self._check(self._L.trc_upload_scene_sah(self._h, C.byref(leaves_view)), "trc_upload_scene_sah")
+        self._n_vertex = leaves_view.n_vertex
 
     def upload_scene_device(self, view, flags):
         """trc_upload_scene_device: abi.TREE_SAH | abi.TREE_TRIANGLE_LEAVES (bvhList = the analytic primitives' leaves only)."""
         self._check(self._L.trc_upload_scene_device(self._h, C.byref(view), flags), "trc_upload_scene_device")
+        self._n_vertex = view.n_vertex
 
     def download_bvh(self):
         """The device-built tree in the reference's array layout: ctypes array of abi.BVH (2n-1 records)."""
