@@ -173,6 +173,36 @@ def test_rejected_inputs(gpu):
     assert not first_difference(raw(gpu.download_bvh()), sc.bvh_array())
 
 
+@pytest.mark.parametrize("builder", ["upload_scene_lbvh", "upload_scene_sah"])
+def test_upload_rejected_on_the_device_leaves_no_scene_and_a_usable_context(gpu, builder):
+    """An interior record among the leaves is found by the device, when the old scene has gone: the upload fails with
+    TRC_ERR_BVH_INVALID, the context holds no scene, and the next valid upload builds the oracle's tree again"""
+    from tracer_amd.device import TracerError
+    sc = host.HostScene(abi.SCENE_CORNELL_SPHERES)
+    n = 300
+    boxes = [((-1.0 - k,) * 3, (1.0 + k,) * 3) for k in range(n)]
+    good, bad = leaf_records(boxes, sc.view.n_sphere), leaf_records(boxes, sc.view.n_sphere)
+    bad[150].pType = abi.PRIM_BVH
+    view = lambda leaves: (lambda v: (setattr(v, "bvhList", C.cast(leaves, C.POINTER(abi.BVH))), setattr(v, "n_bvh", n), v)[2])(abi.Scene.from_buffer_copy(sc.leaves_view()))
+    want = pyoracle.lbvh_build(good, n)[0] if builder == "upload_scene_lbvh" else pyoracle.sah_build(good, n)
+    rays = random_rays(2000, 31)
+    ref = pyoracle.trace_rays(sc.view_with_bvh(want), rays)
+    upload = getattr(gpu, builder)
+    upload(view(good))
+    with pytest.raises(TracerError) as err:
+        upload(view(bad))
+    assert err.value.status == abi.ERR_BVH_INVALID
+    with pytest.raises(TracerError):
+        gpu.trace_rays(rays)
+    with pytest.raises(TracerError):
+        gpu.download_bvh()
+    upload(view(good))
+    assert not first_difference(raw(gpu.download_bvh()), raw(want))
+    got = gpu.trace_rays(rays)
+    for f in ref.dtype.names:
+        assert (got[f].view(np.uint32) == ref[f].view(np.uint32)).all(), f
+
+
 def test_render_through_device_sah_tree(gpu):
     sc = host.HostScene(abi.SCENE_CORNELL_MESH, host.Mesh.ball(40, 40, 1.0))
     W, H = 96, 64

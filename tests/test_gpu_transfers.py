@@ -1,5 +1,7 @@
 """Every transfer between device memory and caller memory goes through the context's pinned staging buffer in 4 MB chunks, two in flight
-(trc_copy_to_host / trc_copy_to_device, trc_ctx.hpp; DESIGN.md section 6 says why).  Round trips at the chunk boundaries."""
+(trc_copy_to_host / trc_copy_to_device, trc_ctx.hpp; DESIGN.md section 6 says why).  The library's own small read-backs take the same buffer,
+h_xfer (trc_read_to_host); h_readback serves the two asynchronous read-backs (refit_run, sah_build_topology) and h_stage host-staged
+collectives: tests/test_transfer_sites.py holds every copy in the sources to these three.  Round trips at the chunk boundaries."""
 import numpy as np
 import pytest
 

@@ -49,7 +49,8 @@ def fused(m, v):
 
 
 def test_the_test_matrices_tell_the_definition_from_its_near_misses():
-    v = rr.vertices_of(small_ball().view)
+    sc = small_ball()                      # kept alive: its view points into memory the scene owns
+    v = rr.vertices_of(sc.view)
     centre = pr.box_centre(v)
     for angle, scale, shift in ((ANGLE_A, SCALE_A, SHIFT_A), (ANGLE_B, SCALE_B, SHIFT_B)):
         model, normal = pr.turn(centre, angle, scale, shift)
@@ -64,7 +65,8 @@ def test_the_test_matrices_tell_the_definition_from_its_near_misses():
 
 
 def test_identity_reproduces_the_rest_values():
-    v = rr.vertices_of(small_ball().view)
+    sc = small_ball()                      # kept alive: its view points into memory the scene owns
+    v = rr.vertices_of(sc.view)
     v[0, 0] = F(-0.0)
     got = pr.pose(v, v * F(2), [(0, len(v), pr.identity(), pr.identity())])
     assert (got == v).all()                                           # as values ...
@@ -72,7 +74,8 @@ def test_identity_reproduces_the_rest_values():
 
 
 def test_pose_is_from_rest_and_leaves_the_rest_alone():
-    v = rr.vertices_of(small_ball().view)
+    sc = small_ball()                      # kept alive: its view points into memory the scene owns
+    v = rr.vertices_of(sc.view)
     n = len(v)
     model, normal = pr.turn(pr.box_centre(v), ANGLE_A, SCALE_A, SHIFT_A)
     current = v + F(1)

@@ -128,9 +128,7 @@ __global__ void __launch_bounds__(64) k_stats_sum(const unsigned long long* rows
 }
 trc_status trc_read_stats_sum(trc_ctx* ctx, unsigned long long* h, size_t count) {
     hipLaunchKernelGGL(k_stats_sum, dim3(1), dim3(64), 0, ctx->stream, ctx->d_stats, ctx->d_stats_sum);
-    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->d_stats_sum, count * sizeof *h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TRC_OK;
+    return trc_read_to_host(ctx, ctx->stream, "stats sum", {{h, ctx->d_stats_sum, count * sizeof *h}});
 }
 
 // ---- output stage (fragmentShader, Render.metal:29-75): exposure sums, then ACES to 8 bit
@@ -377,6 +375,22 @@ trc_status trc_copy_to_device(trc_ctx* ctx, void* dev, const void* host, size_t 
     return TRC_OK;
 }
 
+trc_status trc_read_to_host(trc_ctx* ctx, hipStream_t st, const char* what, std::initializer_list<trc_read_item> items) {
+    TRC_TRY(xfer_ready(ctx));
+    hipError_t e = hipGetLastError();
+    size_t off = 0;
+    for (const trc_read_item& it : items) {
+        if (e == hipSuccess) e = off + it.bytes <= kXferChunk ? hipMemcpyAsync(ctx->h_xfer + off, it.dev, it.bytes, hipMemcpyDeviceToHost, st) : hipErrorInvalidValue;
+        off += (it.bytes + 15u) & ~(size_t)15u;
+    }
+    const hipError_t sync = hipStreamSynchronize(st);      // also after a failure: nothing of this call is in flight on return
+    if (e == hipSuccess) e = sync;
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    off = 0;
+    for (const trc_read_item& it : items) { std::memcpy(it.host, ctx->h_xfer + off, it.bytes); off += (it.bytes + 15u) & ~(size_t)15u; }
+    return TRC_OK;
+}
+
 // ----------------------------------------------------------------------- what is stale now, and who frees what (trc_ctx.hpp)
 void trc_release_scene(trc_ctx* ctx) {
     (void)hipFree(ctx->d_blob); ctx->d_blob = nullptr;
@@ -384,6 +398,14 @@ void trc_release_scene(trc_ctx* ctx) {
     ctx->has_scene = false;
     trc_mesh_light_free(ctx);
     trc_refit_free(ctx);
+}
+
+void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s) {
+    ks.sc.blob = ctx->d_blob;
+    ctx->ks = ks;
+    ctx->lds_scene = ks.sc.n_lds_nodes == ks.sc.n_nodes;      // whole tree staged in LDS
+    ctx->lds_prefix_ok = ctx->has_scene = true;
+    ctx->scene_min_image = trc_scene_min_image(s);
 }
 
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind) {
@@ -546,14 +568,8 @@ trc_status trc_upload_scene(trc_ctx* ctx, const trc_scene* scene) {
     ctx->blob_bytes = (size_t)blob_total * 4;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_blob, blob.data(), blob.size() * 4, ctx->stream));
-    TRC_TRY(trc_repack_triangles(ctx, scene, ks.sc, ctx->d_blob, nullptr));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ks.sc.blob = ctx->d_blob;
-    ctx->ks = ks;
-    ctx->lds_scene = ks.sc.n_lds_nodes == ks.sc.n_nodes;      // whole tree staged in LDS
-    ctx->lds_prefix_ok = true;
-    ctx->has_scene = true;
-    ctx->scene_min_image = trc_scene_min_image(scene);
+    TRC_TRY(trc_repack_triangles(ctx, scene, ks.sc, ctx->d_blob, nullptr));      // synchronous, as the copy before it
+    trc_adopt_scene(ctx, ks, scene);
     return TRC_OK;
 }
 
@@ -587,7 +603,6 @@ trc_status trc_upload_density(trc_ctx* ctx, const trc_GridDensityInfo* info, con
             }
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_occupancy, occ.size()));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_occupancy, occ.data(), occ.size(), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->dinfo = *info;
     return TRC_OK;
 }
@@ -656,7 +671,6 @@ trc_status trc_set_environment_map(trc_ctx* ctx, uint32_t w, uint32_t h, const f
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_envmap, bytes));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_envmap, rgb, bytes, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->env_w = w; ctx->env_h = h;
     return TRC_OK;
 }
@@ -773,7 +787,6 @@ static trc_status copy_frame(trc_ctx* ctx, void* dev, void* host, bool to_device
     const size_t bytes = (size_t)ctx->width * ctx->height * 16;
     trc_sppm_order_after_camera(ctx);
     TRC_TRY(to_device ? trc_copy_to_device(ctx, dev, host, bytes, ctx->stream) : trc_copy_to_host(ctx, host, dev, bytes, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     collect_events(ctx);
     return TRC_OK;
 }
@@ -809,8 +822,7 @@ trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, f
     if (hipMemsetAsync(d_sums.p, 0, sizeof sums, ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap memset");
     hipLaunchKernelGGL(k_tonemap_sum, dim3(std::min<uint32_t>((n + 255) / 256, 2048u)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<const float4*>(plane), n, d_sums.as<unsigned long long>());
-    if (hipMemcpyAsync(sums, d_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap sums");
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "tonemap sums", {{sums, d_sums.p, sizeof sums}}));
     // same binary32 / binary64 steps as oracle/oracle.cpp orc_tonemap (exp through trc_detmath.h)
     float mean[3];
     for (int c = 0; c < 3; ++c) mean[c] = (float)((double)sums[c] / 65536.0 / (double)n);
@@ -821,8 +833,7 @@ trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, f
     if (exposure_out) *exposure_out = expose;
     hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(plane),
                        ctx->width, ctx->height, expose, d_out.as<uchar4>());
-    if (hipGetLastError() != hipSuccess || trc_copy_to_host(ctx, rgba8, d_out.p, (size_t)n * 4, ctx->stream) != TRC_OK ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, "tonemap kernel");
+    if (hipGetLastError() != hipSuccess || trc_copy_to_host(ctx, rgba8, d_out.p, (size_t)n * 4, ctx->stream) != TRC_OK) return trc_fail(ctx, TRC_ERR_HIP, "tonemap kernel");
     return TRC_OK;
 }
 

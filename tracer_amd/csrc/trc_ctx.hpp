@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -281,12 +282,12 @@ struct trc_ctx {
     bool coll_active = false;
     void* h_stage = nullptr;            // pinned staging buffer of host-staged collectives
     size_t h_stage_bytes = 0;
-    // 1 KB of pinned host memory (trc_readback_alloc) for small read-backs: the per-level counter block of trc_upload_scene_sah, and of
-    // trc_update_vertices the level table (first update of a scene) and the refitted root box.  The root box's copy is still in flight
-    // when trc_update_vertices returns; that is safe only because every entry point calls trc_flush first, which settles it
-    // (trc_refit_settle) before anything else writes or reads the buffer
+    // 1 KB of pinned host memory (trc_readback_alloc) for the two read-backs that are ASYNCHRONOUS on purpose: the per-level counter block of
+    // trc_upload_scene_sah (sah_build_topology) and the refitted root box of trc_update_vertices (refit_run).  The root box's copy is still
+    // in flight when trc_update_vertices returns; that is safe only because every entry point calls trc_flush first, which settles it
+    // (trc_refit_settle) before anything else writes or reads the buffer -- and why every synchronous read-back goes through h_xfer instead
     uint32_t* h_readback = nullptr;
-    char* h_xfer = nullptr;             // 2 x kXferChunk bytes of pinned host memory: every transfer to / from caller memory goes through it (trc_copy_*)
+    char* h_xfer = nullptr;             // 2 x kXferChunk bytes of pinned host memory, synchronous users only: trc_copy_*, trc_read_to_host
     hipEvent_t ev_xfer[2] = {nullptr, nullptr};
 
     // A/B and test knobs, per context: defaults from the environment at trc_create (TRC_NO_LDS_FIT, TRC_STACK_LDS_LEVELS,
@@ -363,6 +364,17 @@ struct DevBuf {
     void* release() { void* q = p; p = nullptr; return q; }
 };
 
+// The many temporary device arrays of one function (the tree builds), each a DevBuf: freed on every path out, failing as DevBuf::alloc does
+struct DevBufs {
+    std::vector<DevBuf> bufs;
+    template <class T> trc_status alloc(trc_ctx* ctx, T** out, size_t count, const char* what) {      // `count` elements, at least one
+        bufs.emplace_back();
+        TRC_TRY(bufs.back().alloc(ctx, (count ? count : 1) * sizeof(T), what));
+        *out = bufs.back().as<T>();
+        return TRC_OK;
+    }
+};
+
 // A buffer of the context that must hold at least `need` bytes (`have`: what it holds): a launch in flight may still use the old
 // one, so the stream is synchronised before it goes.  `msg`: the error text of a failed allocation (TRC_ERR_OOM, nothing kept)
 template <class T>
@@ -411,15 +423,19 @@ trc_status trc_coll_allgather(trc_ctx* ctx, void* buf, size_t bytes_per_rank, hi
 // downloaded again, had the data (round 6: tests/campaigns/sppm_stress.py reproduced round 5's "unwritten photon records" 380 times in
 // 9 000 scenes, every one of them a transfer, none a kernel).  So the bytes go through the context's own pinned
 // buffer, two chunks of kXferChunk in flight, and are copied to / from the caller's memory by the CPU.  Synchronous: on return the
-// transfer is complete (`st` is synchronised up to it).
+// transfer is complete (`st` is synchronised up to it): no caller synchronises again.
 constexpr size_t kXferChunk = 4u << 20;
 trc_status trc_copy_to_host(trc_ctx* ctx, void* host, const void* dev, size_t bytes, hipStream_t st);
 trc_status trc_copy_to_device(trc_ctx* ctx, void* dev, const void* host, size_t bytes, hipStream_t st);
+// ... and the library's own small read-backs (flags, counters, a root box): a few device ranges into host variables through the same buffer with
+// ONE synchronisation of `st`, kXferChunk bytes in all.  Reports a launch that failed before it too: TRC_ERR_HIP, "<what>: <hipGetErrorString>"
+struct trc_read_item { void* host; const void* dev; size_t bytes; };
+trc_status trc_read_to_host(trc_ctx* ctx, hipStream_t st, const char* what, std::initializer_list<trc_read_item> items);
 
 // tiles owned by `rank` of `nranks` (XCD-aware order) uploaded into ctx->d_tiles; shared by render and SPPM
 trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_t view_height = 0, uint32_t blk_shift = 3);
 size_t trc_dyn_lds_bytes(const trc_ctx* ctx, bool stats);
-// trc_lbvh.hip: stable 24-bit radix sort of (key, value) pairs
+// trc_lbvh.hip: stable radix sort of (key, value) pairs on the 24 low key bits, three of the tree builds' 8-bit passes; *result: the buffer that holds it
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result);
 uint32_t trc_sort_hist_words(uint32_t n);
 // trc_tonemap's output stage on any W*H RGBA32F plane of the context (the accumulator, the denoised frame); synchronous
@@ -429,6 +445,15 @@ trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, f
 // entry point's.  trc_flush(nullptr) is TRC_OK: the null-context check that follows answers
 trc_status trc_flush(trc_ctx* ctx);
 hipEvent_t trc_get_event(trc_ctx* ctx);   // from the context's pool (null on failure); pairs go to ctx->pending
+// A timed section of a stream between two events of the context's pool, which get them back on every path out.  stop() closes it; ms() is its
+// device time once the stream has been synchronised.  No event to be had: nothing fails, the section took 0 ms (lbvh_build_ms, envl_build_ms: diagnostics)
+struct TimedSection {
+    trc_ctx* ctx; hipStream_t st; hipEvent_t e0, e1;
+    TimedSection(trc_ctx* c, hipStream_t s) : ctx(c), st(s), e0(trc_get_event(c)), e1(trc_get_event(c)) { if (e0 && e1) (void)hipEventRecord(e0, st); }
+    ~TimedSection() { if (e0) ctx->event_pool.push_back(e0); if (e1) ctx->event_pool.push_back(e1); }
+    void stop() { if (e0 && e1) (void)hipEventRecord(e1, st); }
+    float ms() const { float v = 0.0f; return e0 && e1 && hipEventElapsedTime(&v, e0, e1) == hipSuccess ? v : 0.0f; }
+};
 void trc_sppm_release(trc_ctx* ctx);   // frees ctx->sppm (no-op when absent)
 void trc_denoise_release(trc_ctx* ctx);      // frees ctx->denoise: its G-buffers, planes and history (no-op when absent)
 // smallest textureIndex of the scene's Image materials (~0u: none); recorded by every scene upload (trc_ctx::scene_min_image)
@@ -474,12 +499,14 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //   kSceneReplaced      trc_upload_scene, upload_device_tree (trc_upload_scene_lbvh / _sah / _device), BEFORE they allocate the new
 //                       scene: also forgets the block costs and releases the old scene (trc_release_scene: blob, reference-layout
 //                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
+//                       A device tree upload that fails after that releases what it allocated of the NEW scene too, before it returns
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
 //   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
 enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:
 void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload allocates
+void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s);      // trc_abi.hip: the last step of every scene upload -- `ks` becomes the context's scene
 void trc_release_frame(trc_ctx* ctx);    // trc_abi.hip: what depends on the frame size (trc_resize): frame, block list, compose buffers, SPPM, denoiser
 void trc_release_tiles(trc_ctx* ctx);    // trc_schedule.hip: the block list and the arrays sized by it (trc_ensure_tiles)
 void trc_collect_finished_events(trc_ctx* ctx);   // trc_abi.hip: completed event pairs into kernel_ms / schedule_ms without waiting (render_pass)

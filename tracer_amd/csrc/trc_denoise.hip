@@ -487,7 +487,6 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
 static trc_status denoise_download(trc_ctx* ctx, void* host, const void* dev, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     TRC_TRY(trc_copy_to_host(ctx, host, dev, bytes, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TRC_OK;
 }
 

@@ -83,25 +83,16 @@ trc_status trc_env_light_build(trc_ctx* ctx) {
     uint2* rows = reinterpret_cast<uint2*>(t + L.rows);
     uint2* marg = reinterpret_cast<uint2*>(t + L.marg);
     double* total = reinterpret_cast<double*>(t + L.total);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    if (e0) (void)hipEventRecord(e0, ctx->stream);
+    TimedSection timed(ctx, ctx->stream);
     hipLaunchKernelGGL(k_env_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_envmap, W, H, weight);
     hipLaunchKernelGGL(k_env_rows, dim3((H + 63) / 64), dim3(64), 0, ctx->stream, weight, W, H, q, list, rows, rowsum);
     hipLaunchKernelGGL(k_env_marginal, dim3(1), dim3(64), 0, ctx->stream, rowsum, H, qm, listm, marg, total);
-    if (e1) (void)hipEventRecord(e1, ctx->stream);
-    hipError_t e = hipGetLastError();
+    timed.stop();
     double h_total = 0.0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, sizeof h_total, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0.0f;
-    if (e == hipSuccess && e0 && e1) (void)hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("environment-light tables: ") + hipGetErrorString(e));
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "environment-light tables", {{&h_total, total, sizeof h_total}}));
     ctx->d_envl = static_cast<uint8_t*>(tables.release());
     ctx->envl_total = h_total;
-    ctx->envl_build_ms = ms;
+    ctx->envl_build_ms = timed.ms();
     return TRC_OK;
 }
 
@@ -153,7 +144,6 @@ trc_status trc_debug_env_tables(trc_ctx* ctx, float* weight, uint32_t* rows, uin
     if (weight && st == TRC_OK) st = trc_copy_to_host(ctx, weight, ctx->d_envl + L.weight, n * 4, ctx->stream);
     if (rows && st == TRC_OK) st = trc_copy_to_host(ctx, rows, ctx->d_envl + L.rows, n * 8, ctx->stream);
     if (marg && st == TRC_OK) st = trc_copy_to_host(ctx, marg, ctx->d_envl + L.marg, (size_t)ctx->env_h * 8, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
     if (total) *total = ctx->envl_total;
     if (build_ms) *build_ms = ctx->envl_build_ms;
     return st;

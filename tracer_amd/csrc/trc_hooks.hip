@@ -124,16 +124,10 @@ trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64
     DevBuf buf;
     TRC_TRY(buf.alloc(ctx, 16, "unary test"));
     unsigned long long* const d = buf.as<unsigned long long>();
-    const unsigned long long init[2] = {0ull, ~0ull};
     unsigned long long h[2] = {0ull, ~0ull};
-    hipError_t e = hipMemcpyAsync(d, init, 16, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && count) {
-        hipLaunchKernelGGL(k_unary_test, dim3(ctx->cu_count * 16), dim3(256), 0, ctx->stream, op, first_bits, count, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); else (void)hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_unary_test: ") + hipGetErrorString(e));
+    TRC_TRY(trc_copy_to_device(ctx, d, h, 16, ctx->stream));
+    if (count) hipLaunchKernelGGL(k_unary_test, dim3(ctx->cu_count * 16), dim3(256), 0, ctx->stream, op, first_bits, count, d);
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "trc_unary_test", {{h, d, 16}}));
     *n_mismatch = h[0];
     if (first_mismatch) *first_mismatch = (uint32_t)h[1];
     return TRC_OK;

@@ -13,6 +13,11 @@
 //   k_lbvh_emit       fat nodes into the scene blob (dev_scene.hpp) + the tree in the reference's own array
 //                     layout [root, leaf 0..n-1, interior 1..n-2] (BVH.hh:246-269) for trc_download_bvh
 //
+// The host side, upload_device_tree, is these steps over one TreeBuild:
+//   intake (arguments, blob layout, host-made prefix: the context is untouched) -> replace_scene (the old scene goes; blob, triangle and
+//   leaf records, the build's temporaries: from here a failure releases the new scene too) -> leaf_records -> lbvh_topology | sah_build_topology ->
+//   fit_boxes (refit passes; the intake flags are looked at here) -> rotate_sweep + fit_boxes, twice (Morton trees only) -> renumber_and_emit -> adopt
+//
 // All of it is integer / min-max work on a few bytes per leaf: HBM-bound streaming passes, no MFMA.  The CPU
 // statement of the same build is oracle/oracle_lbvh.cpp; tests compare all 2n-1 records bit for bit.
 #include <hip/hip_runtime.h>
@@ -22,8 +27,6 @@
 #include <cstring>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 #include "trc_ctx.hpp"
 #include "trc_scene_prep.hpp"
@@ -473,196 +476,182 @@ __global__ void __launch_bounds__(256) k_lbvh_emit(const DLeaf* leaves, const ui
     if (ch[1] & kChildLeaf) ref[slot[1]].parent = self;      // interior children write their own record
 }
 
-struct Buffers {
-    std::vector<void*> ptrs;
-    ~Buffers() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** out, size_t count) {
-        hipError_t e = hipMalloc((void**)out, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*out);
-        return e;
-    }
+// ---- host side.  One 8-bit digit of the sort: n pairs from (keys_in, vals_in) into (keys_out, vals_out); hist: trc_sort_hist_words(n) words
+void radix_pass(hipStream_t st, const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t* hist,
+                uint32_t* digit_base, uint32_t n, uint32_t shift) {
+    const uint32_t n_blocks = (n + kSortTile - 1) / kSortTile;
+    hipLaunchKernelGGL(k_radix_hist, dim3(n_blocks), dim3(kSortBlock), 0, st, keys_in, n, shift, hist, n_blocks);
+    hipLaunchKernelGGL(k_radix_row_scan, dim3(256), dim3(256), 0, st, hist, n_blocks, digit_base);
+    hipLaunchKernelGGL(k_radix_digit_base, dim3(1), dim3(256), 0, st, digit_base);
+    hipLaunchKernelGGL(k_radix_scatter, dim3(n_blocks), dim3(kSortBlock), 0, st, keys_in, vals_in, keys_out, vals_out, n, shift, hist, digit_base, n_blocks);
+}
+// ... and the sort on the `bits` low key bits, from buffer 0 of the two ping-pong arrays; returns the buffer that holds the result
+int radix_sort(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, uint32_t bits) {
+    int cur = 0;
+    for (uint32_t shift = 0; shift < bits; shift += 8, cur ^= 1)
+        radix_pass(st, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], hist, digit_base, n, shift);
+    return cur;
+}
+
+// What the steps of a device tree build share.  The device arrays are temporaries (tmp); blob and reference-layout tree are the context's
+struct TreeBuild {
+    trc_ctx* ctx; hipStream_t st; const trc_scene* s;
+    bool sah, triangle_leaves;      // sah: the reference's binned-SAH topology, else Morton order + rotations.  triangle_leaves: bvhList holds
+                                    // the analytic primitives' leaves only; one leaf per triangle follows them, written on the device
+    uint32_t n = 0, n_interior = 0; DScene sc{}; uint64_t blob_words = 0;
+    std::unique_ptr<uint32_t[]> prefix; DevBufs tmp;      // prefix: host side of the blob, analytic primitives + materials
+    DLeaf* leaves = nullptr; float* boxes = nullptr; DTopo tp{};
+    uint32_t *keys[2] = {}, *vals[2] = {}, *hist = nullptr, *digit_base = nullptr;      // sort ping-pong; vals[cur][position] = leaf index
+    uint32_t* bounds = nullptr;               // 6 ordered centroid bounds + word 6 = the leaf-intake flags
+    uint32_t *height = nullptr, *arrived = nullptr;      // per interior node: subtree height; pass of fitting (later: its depth rank)
+    int cur = 0; uint32_t first_chunk = 40, tree_height = 0;      // sorted buffer; refit passes before the first look at the root; pass that fitted it
+    dim3 g_leaf() const { return dim3((n + 255) / 256); }
+    dim3 g_int() const { return dim3((n_interior + 255) / 256); }
 };
 
 #include "trc_sah_build.hpp"
 
-}  // namespace
-
-// stable LSD sort of (key, value) pairs on the 24 low key bits, 3 passes of the radix kernels above; the result is in
-// buffer *result (0 or 1) of the two ping-pong arrays.  hist: 256 * ceil(n / 4096) words, digit_base: 256 words.
-void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result) {
-    const uint32_t n_sort_blocks = (n + kSortTile - 1) / kSortTile;
-    int cur = 0;
-    for (uint32_t shift = 0; shift < 24; shift += 8) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(n_sort_blocks), dim3(kSortBlock), 0, st, keys[cur], n, shift, hist, n_sort_blocks);
-        hipLaunchKernelGGL(k_radix_row_scan, dim3(256), dim3(256), 0, st, hist, n_sort_blocks, digit_base);
-        hipLaunchKernelGGL(k_radix_digit_base, dim3(1), dim3(256), 0, st, digit_base);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(n_sort_blocks), dim3(kSortBlock), 0, st, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n,
-                           shift, hist, digit_base, n_sort_blocks);
-        cur ^= 1;
-    }
-    *result = cur;
-}
-uint32_t trc_sort_hist_words(uint32_t n) { return 256u * ((n + kSortTile - 1) / kSortTile); }
-
-// trc_upload_scene_lbvh (sah = false: Morton order, radix tree, rotations) and trc_upload_scene_sah (sah = true: the
-// reference's own binned-SAH build, trc_sah_build.hpp) share everything around the topology: leaf intake, boxes bottom-up,
-// fat nodes by depth, the tree in the reference's array layout.
-static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah, bool triangle_leaves) {
-    TRC_TRY(trc_flush(ctx));
-    if (!ctx) return TRC_ERR_INVALID_ARG;
+// The fat nodes are written by k_lbvh_emit, the triangle records by k_repack_triangles from the caller's arrays: neither is staged on the host
+trc_status intake(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx; const trc_scene* const s = b.s;
     if (!s) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "device tree: no scene");
-    // triangle_leaves: bvhList holds the analytic primitives' leaves only; one leaf per triangle follows them, written on the device
-    const uint64_t n_given = s->bvhList ? s->n_bvh : 0u, n_all = n_given + (triangle_leaves ? s->n_index / 3 : 0u);
-    if ((!s->bvhList && !triangle_leaves) || n_all < 2) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "lbvh: need >= 2 leaf records");
+    const uint64_t n_given = s->bvhList ? s->n_bvh : 0u, n_all = n_given + (b.triangle_leaves ? s->n_index / 3 : 0u);
+    if ((!s->bvhList && !b.triangle_leaves) || n_all < 2) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "lbvh: need >= 2 leaf records");
     if (n_all > (1u << 28)) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "lbvh: more than 2^28 leaves");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     TRC_TRY(validate_primitives(ctx, s));
-    const uint32_t n = (uint32_t)n_all, n_interior = n - 1, n_nodes = 2 * n - 1;
+    b.n = (uint32_t)n_all; b.n_interior = b.n - 1;
+    TRC_TRY(layout_scene(ctx, s, b.n_interior, b.sc, b.blob_words));
+    b.prefix.reset(new (std::nothrow) uint32_t[(size_t)b.sc.off_nodes]());      // zeroed
+    if (!b.prefix) return trc_fail(ctx, TRC_ERR_OOM, "lbvh: host staging buffer");
+    fill_primitives(s, b.sc, b.prefix.get());
+    return TRC_OK;
+}
 
-    DScene sc{};
-    uint64_t total = 0;
-    TRC_TRY(layout_scene(ctx, s, n_interior, sc, total));
-    // host side of the blob: analytic primitives + materials (the prefix).  The fat nodes are written by k_lbvh_emit, the
-    // triangle records by k_repack_triangles from the caller's vertex / index arrays: neither is staged on the host
-    std::unique_ptr<uint32_t[]> blob(new (std::nothrow) uint32_t[(size_t)sc.off_nodes]);
-    if (!blob) return trc_fail(ctx, TRC_ERR_OOM, "lbvh: host staging buffer");
-    std::memset(blob.get(), 0, (size_t)sc.off_nodes * 4);
-    fill_primitives(s, sc, blob.get());
-
+// the caller's leaf records go straight to slots 1..n of the reference-layout array (BVH.hh:246-269), the triangles' behind them
+trc_status replace_scene(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx;
+    const uint64_t n_given = b.s->bvhList ? b.s->n_bvh : 0u;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     trc_scene_changed(ctx, kSceneReplaced);      // another scene: the old one goes, with everything derived from it
-    ctx->blob_bytes = (size_t)total * 4;
+    ctx->blob_bytes = (size_t)b.blob_words * 4;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_blob, ctx->blob_bytes));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bvh_ref, sizeof(trc_BVH) * n_nodes));
-    hipStream_t st = ctx->stream;
-    TRC_TRY(trc_copy_to_device(ctx, ctx->d_blob, blob.get(), (size_t)sc.off_nodes * 4, st));
-    // the caller's leaf records go straight to slots 1..n of the reference-layout array (BVH.hh:246-269), the triangles' behind them
-    TRC_TRY(trc_repack_triangles(ctx, s, sc, ctx->d_blob, triangle_leaves ? ctx->d_bvh_ref + 1 + n_given : nullptr));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_bvh_ref, 0, sizeof(trc_BVH), st));
-    if (n_given) TRC_TRY(trc_copy_to_device(ctx, ctx->d_bvh_ref + 1, s->bvhList, sizeof(trc_BVH) * n_given, st));
-
-    Buffers buf;
-    DLeaf* d_leaves; uint32_t *d_keys[2], *d_vals[2], *d_hist, *d_bounds, *d_height, *d_arrived;
-    float* d_boxes;
-    DTopo tp{};
-    const uint32_t n_sort_blocks = (n + kSortTile - 1) / kSortTile;
-    HIP_TRY(ctx, buf.alloc(&d_leaves, n));
-    for (int k = 0; k < 2; ++k) { HIP_TRY(ctx, buf.alloc(&d_keys[k], n)); HIP_TRY(ctx, buf.alloc(&d_vals[k], n)); }
-    HIP_TRY(ctx, buf.alloc(&d_hist, (size_t)256 * n_sort_blocks));
-    uint32_t* d_digit_base;
-    HIP_TRY(ctx, buf.alloc(&d_digit_base, 256));
-    HIP_TRY(ctx, buf.alloc(&d_bounds, 8));       // 6 ordered bounds + [6] = bad-leaf flags
-    HIP_TRY(ctx, buf.alloc(&d_height, n_interior));
-    HIP_TRY(ctx, buf.alloc(&d_arrived, n_interior));
-    HIP_TRY(ctx, buf.alloc(&d_boxes, (size_t)n_interior * 6));
-    HIP_TRY(ctx, buf.alloc(&tp.child_l, n_interior)); HIP_TRY(ctx, buf.alloc(&tp.child_r, n_interior));
-    HIP_TRY(ctx, buf.alloc(&tp.parent_interior, n_interior)); HIP_TRY(ctx, buf.alloc(&tp.parent_leaf, n));
-    HIP_TRY(ctx, buf.alloc(&tp.axis, n_interior));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_bvh_ref, sizeof(trc_BVH) * (2 * (size_t)b.n - 1)));
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_blob, b.prefix.get(), (size_t)b.sc.off_nodes * 4, b.st));
+    TRC_TRY(trc_repack_triangles(ctx, b.s, b.sc, ctx->d_blob, b.triangle_leaves ? ctx->d_bvh_ref + 1 + n_given : nullptr));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_bvh_ref, 0, sizeof(trc_BVH), b.st));
+    if (n_given) TRC_TRY(trc_copy_to_device(ctx, ctx->d_bvh_ref + 1, b.s->bvhList, sizeof(trc_BVH) * n_given, b.st));
+    const uint32_t n = b.n, ni = b.n_interior;       // ... and the build's temporary arrays
+    const char* const what = "tree build: work arrays";
+    TRC_TRY(b.tmp.alloc(ctx, &b.leaves, n, what)); TRC_TRY(b.tmp.alloc(ctx, &b.boxes, (size_t)ni * 6, what));
+    const struct { uint32_t** p; size_t count; } words[] = {
+        {&b.keys[0], n}, {&b.vals[0], n}, {&b.keys[1], n}, {&b.vals[1], n}, {&b.hist, trc_sort_hist_words(n)}, {&b.digit_base, 256}, {&b.bounds, 8},
+        {&b.height, ni}, {&b.arrived, ni}, {&b.tp.child_l, ni}, {&b.tp.child_r, ni}, {&b.tp.parent_interior, ni}, {&b.tp.parent_leaf, n}, {&b.tp.axis, ni}};
+    for (const auto& w : words) TRC_TRY(b.tmp.alloc(ctx, w.p, w.count, what));
     const uint32_t bounds_init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    HIP_TRY(ctx, hipMemcpyAsync(d_bounds, bounds_init, sizeof bounds_init, hipMemcpyHostToDevice, st));
+    return trc_copy_to_device(ctx, b.bounds, bounds_init, sizeof bounds_init, b.st);
+}
 
-    struct Events {                 // destroyed on every exit path
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_TRY(ctx, hipEventCreate(&ev.a)); HIP_TRY(ctx, hipEventCreate(&ev.b));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
-    HIP_TRY(ctx, hipEventRecord(e0, st));
-    const dim3 g_leaf((n + 255) / 256), g_int((n_interior + 255) / 256), b256(256);
+// the uploaded leaf records (slots 1..n of the reference-layout array) -> compact leaves; what is wrong with them -> the intake flags
+void leaf_records(TreeBuild& b) {
     LeafLimits lim;
-    lim.n[0] = s->n_sphere; lim.n[1] = s->n_square; lim.n[2] = s->n_cube; lim.n[3] = s->n_index / 3;
-    hipLaunchKernelGGL(k_lbvh_prepare, g_leaf, b256, 0, st, ctx->d_bvh_ref + 1, n, lim, d_leaves, d_bounds + 6);
-    int cur = 0;
-    uint32_t first_chunk = 40;                  // refit passes before the root is looked at for the first time
-    if (!sah) {
-        hipLaunchKernelGGL(k_lbvh_bounds, dim3(std::min<uint32_t>((n + 255) / 256, 1024u)), b256, 0, st, d_leaves, n, d_bounds);
-        hipLaunchKernelGGL(k_lbvh_keys, g_leaf, b256, 0, st, d_leaves, n, d_bounds, d_keys[0], d_vals[0]);
-        for (uint32_t shift = 0; shift < 32; shift += 8) {
-            hipLaunchKernelGGL(k_radix_hist, dim3(n_sort_blocks), dim3(kSortBlock), 0, st, d_keys[cur], n, shift, d_hist, n_sort_blocks);
-            hipLaunchKernelGGL(k_radix_row_scan, dim3(256), b256, 0, st, d_hist, n_sort_blocks, d_digit_base);
-            hipLaunchKernelGGL(k_radix_digit_base, dim3(1), b256, 0, st, d_digit_base);
-            hipLaunchKernelGGL(k_radix_scatter, dim3(n_sort_blocks), dim3(kSortBlock), 0, st, d_keys[cur], d_vals[cur], d_keys[cur ^ 1],
-                               d_vals[cur ^ 1], n, shift, d_hist, d_digit_base, n_sort_blocks);
-            cur ^= 1;
-        }
-        hipLaunchKernelGGL(k_lbvh_hierarchy, g_int, b256, 0, st, d_keys[cur], d_vals[cur], n, tp);
-    } else {
-        TRC_TRY(sah_build_topology(ctx, buf, d_leaves, n, d_bounds + 6, tp, d_vals[0], &first_chunk));
-        first_chunk = std::min(std::max(first_chunk, 1u), TRC_MAX_BVH_DEPTH + 1u);      // the builder knows the tree's height: that many refit passes
-    }
-    // refit passes: a tree of height h needs h passes; check the root every few passes beyond the usual depth
-    uint32_t root_done = 0, bad_leaves = 0;
+    lim.n[0] = b.s->n_sphere; lim.n[1] = b.s->n_square; lim.n[2] = b.s->n_cube; lim.n[3] = b.s->n_index / 3;
+    hipLaunchKernelGGL(k_lbvh_prepare, b.g_leaf(), dim3(256), 0, b.st, b.ctx->d_bvh_ref + 1, b.n, lim, b.leaves, b.bounds + 6);
+}
+
+// Morton order and T. Karras' radix tree over it: the sibling of sah_build_topology
+void lbvh_topology(TreeBuild& b) {
+    hipLaunchKernelGGL(k_lbvh_bounds, dim3(std::min<uint32_t>((b.n + 255) / 256, 1024u)), dim3(256), 0, b.st, b.leaves, b.n, b.bounds);
+    hipLaunchKernelGGL(k_lbvh_keys, b.g_leaf(), dim3(256), 0, b.st, b.leaves, b.n, b.bounds, b.keys[0], b.vals[0]);
+    b.cur = radix_sort(b.st, b.keys, b.vals, b.hist, b.digit_base, b.n, 32);
+    hipLaunchKernelGGL(k_lbvh_hierarchy, b.g_int(), dim3(256), 0, b.st, b.keys[b.cur], b.vals[b.cur], b.n, b.tp);
+}
+
+// boxes and heights bottom-up, a tree of height h in h passes; the root is looked at after first_chunk passes, then every 8, the intake flags with it
+trc_status fit_boxes(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx;
+    uint32_t pass = 0, bad_leaves = 0;
     const uint32_t pass_limit = TRC_MAX_BVH_DEPTH + 1;
-    auto refit = [&]() -> trc_status {
-        uint32_t pass = 0;
-        root_done = 0;
-        HIP_TRY(ctx, hipMemsetAsync(d_arrived, 0, sizeof(uint32_t) * n_interior, st));
-        for (uint32_t chunk = first_chunk; pass < pass_limit && !root_done; chunk = 8) {
-            for (uint32_t k = 0; k < chunk && pass < pass_limit; ++k)
-                if (sah) hipLaunchKernelGGL(k_lbvh_refit_pass<true>, g_int, b256, 0, st, d_leaves, d_vals[cur], n, tp, d_boxes, d_height, d_arrived, ++pass);
-                else hipLaunchKernelGGL(k_lbvh_refit_pass<false>, g_int, b256, 0, st, d_leaves, d_vals[cur], n, tp, d_boxes, d_height, d_arrived, ++pass);
-            HIP_TRY(ctx, hipMemcpyAsync(&root_done, d_arrived, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(&bad_leaves, d_bounds + 6, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (bad_leaves & 1u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: input must be leaf records only");
-            if (bad_leaves & 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "bvh: leaf with bad primitive type/index");
-            if (bad_leaves & 4u) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "bvh: primitive index exceeds 29 bits");
-            if (bad_leaves & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
-        }
-        if (!root_done) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
-        return TRC_OK;
-    };
-    TRC_TRY(refit());
-    for (int sweep = 0; sweep < (sah ? 0 : kRotationSweeps); ++sweep) {
-        // d_arrived[i] = pass in which i was fitted = its height; the root's is the height of the tree.  Nodes of
-        // height 1 have two leaf children and nothing to rotate.
-        const uint32_t h = root_done;
-        for (uint32_t pass = 2; pass <= h; ++pass)
-            hipLaunchKernelGGL(k_lbvh_rotate_pass, g_int, b256, 0, st, d_leaves, d_vals[cur], n, tp, d_boxes, d_arrived, pass);
-        TRC_TRY(refit());
+    const auto pass_kernel = b.sah ? k_lbvh_refit_pass<true> : k_lbvh_refit_pass<false>;
+    b.tree_height = 0;
+    HIP_TRY(ctx, hipMemsetAsync(b.arrived, 0, sizeof(uint32_t) * b.n_interior, b.st));
+    for (uint32_t chunk = b.first_chunk; pass < pass_limit && !b.tree_height; chunk = 8) {
+        for (uint32_t k = 0; k < chunk && pass < pass_limit; ++k)
+            hipLaunchKernelGGL(pass_kernel, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, b.height, b.arrived, ++pass);
+        TRC_TRY(trc_read_to_host(ctx, b.st, "tree build: refit", {{&b.tree_height, b.arrived, 4}, {&bad_leaves, b.bounds + 6, 4}}));
+        if (bad_leaves & 1u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: input must be leaf records only");      // k_lbvh_prepare, k_sah_init
+        if (bad_leaves & 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "bvh: leaf with bad primitive type/index");
+        if (bad_leaves & 4u) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "bvh: primitive index exceeds 29 bits");
+        if (bad_leaves & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
     }
-    // fat-node numbering: interior nodes sorted by depth (one stable 8-bit radix pass; the root is the only node of depth 0)
-    uint32_t* d_rank = nullptr;                         // reuses the arrival array (the heights in d_height are read back below)
-    {
-        uint32_t* dk[2] = {d_keys[cur ^ 1], nullptr};
-        uint32_t* dv[2] = {d_vals[cur ^ 1], nullptr};
-        HIP_TRY(ctx, buf.alloc(&dk[1], n_interior)); HIP_TRY(ctx, buf.alloc(&dv[1], n_interior));
-        d_rank = d_arrived;
-        hipLaunchKernelGGL(k_lbvh_depth, g_int, b256, 0, st, n_interior, tp.parent_interior, dk[0], dv[0]);
-        const uint32_t nsb = (n_interior + kSortTile - 1) / kSortTile;
-        hipLaunchKernelGGL(k_radix_hist, dim3(nsb), dim3(kSortBlock), 0, st, dk[0], n_interior, 0u, d_hist, nsb);
-        hipLaunchKernelGGL(k_radix_row_scan, dim3(256), b256, 0, st, d_hist, nsb, d_digit_base);
-        hipLaunchKernelGGL(k_radix_digit_base, dim3(1), b256, 0, st, d_digit_base);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(nsb), dim3(kSortBlock), 0, st, dk[0], dv[0], dk[1], dv[1], n_interior, 0u, d_hist, d_digit_base, nsb);
-        hipLaunchKernelGGL(k_lbvh_rank, g_int, b256, 0, st, n_interior, dv[1], d_rank);
-    }
-    hipLaunchKernelGGL(k_lbvh_emit, g_int, b256, 0, st, d_leaves, d_vals[cur], n, tp, d_boxes, d_rank, ctx->d_blob + sc.off_nodes, ctx->d_bvh_ref);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(e1, st));
-
-    uint32_t height = 0;
-    float root_box[6];
-    HIP_TRY(ctx, hipMemcpyAsync(&height, d_height, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(root_box, d_boxes, sizeof root_box, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (height > TRC_MAX_BVH_DEPTH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
-
-    plan_lds(sc, height, true);       // the fat nodes are numbered by depth: any prefix may be staged
-    sc.blob = ctx->d_blob;
-    KScene ks{};
-    ks.sc = sc;
-    for (int a = 0; a < 6; ++a) ks.root_box[a] = root_box[a];
-    ctx->ks = ks;
-    ctx->lds_scene = sc.n_lds_nodes == sc.n_nodes;
-    ctx->lds_prefix_ok = true;
-    ctx->n_bvh_ref = n_nodes;
-    ctx->lbvh_height = height;
-    ctx->lbvh_build_ms = ms;
-    ctx->has_scene = true;
-    ctx->scene_min_image = trc_scene_min_image(s);
+    if (!b.tree_height) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
     return TRC_OK;
+}
+
+// one sweep of rotations.  arrived[i] = pass in which i was fitted = its height; nodes of height 1 have two leaf children: nothing to rotate
+void rotate_sweep(TreeBuild& b) {
+    for (uint32_t pass = 2; pass <= b.tree_height; ++pass)
+        hipLaunchKernelGGL(k_lbvh_rotate_pass, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, b.arrived, pass);
+}
+
+// fat-node numbering: the interior nodes sorted by depth (one radix pass; the root alone has depth 0), then the fat nodes and the reference-layout tree
+trc_status renumber_and_emit(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx;
+    uint32_t *depth = b.keys[b.cur ^ 1], *node = b.vals[b.cur ^ 1], *sorted_depth = nullptr, *sorted_node = nullptr;
+    for (uint32_t** p : {&sorted_depth, &sorted_node}) TRC_TRY(b.tmp.alloc(ctx, p, b.n_interior, "tree build: depth sort"));
+    uint32_t* const rank = b.arrived;              // reuses the arrival array (the heights in b.height are read back by adopt)
+    hipLaunchKernelGGL(k_lbvh_depth, b.g_int(), dim3(256), 0, b.st, b.n_interior, b.tp.parent_interior, depth, node);
+    radix_pass(b.st, depth, node, sorted_depth, sorted_node, b.hist, b.digit_base, b.n_interior, 0u);
+    hipLaunchKernelGGL(k_lbvh_rank, b.g_int(), dim3(256), 0, b.st, b.n_interior, sorted_node, rank);
+    hipLaunchKernelGGL(k_lbvh_emit, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, rank, ctx->d_blob + b.sc.off_nodes, ctx->d_bvh_ref);
+    HIP_TRY(ctx, hipGetLastError());
+    return TRC_OK;
+}
+
+// the tree's height and root box come back, and the scene becomes the context's
+trc_status adopt(TreeBuild& b, const TimedSection& timed) {
+    trc_ctx* const ctx = b.ctx;
+    uint32_t height = 0; KScene ks{};
+    TRC_TRY(trc_read_to_host(ctx, b.st, "tree build: root", {{&height, b.height, 4}, {ks.root_box, b.boxes, sizeof ks.root_box}}));
+    if (height > TRC_MAX_BVH_DEPTH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
+    plan_lds(b.sc, height, true);       // the fat nodes are numbered by depth: any prefix may be staged
+    ks.sc = b.sc;
+    ctx->n_bvh_ref = 2 * b.n - 1;
+    ctx->lbvh_height = height;
+    ctx->lbvh_build_ms = timed.ms();
+    trc_adopt_scene(ctx, ks, b.s);
+    return TRC_OK;
+}
+
+// everything after the old scene has gone; a failure here leaves upload_device_tree a half-built scene to release
+trc_status build_tree(TreeBuild& b) {
+    TRC_TRY(replace_scene(b));
+    TimedSection timed(b.ctx, b.st);
+    leaf_records(b);
+    if (b.sah) TRC_TRY(sah_build_topology(b)); else lbvh_topology(b);
+    TRC_TRY(fit_boxes(b));
+    for (int sweep = 0; !b.sah && sweep < kRotationSweeps; ++sweep) { rotate_sweep(b); TRC_TRY(fit_boxes(b)); }
+    TRC_TRY(renumber_and_emit(b));
+    timed.stop();
+    return adopt(b, timed);
+}
+
+}  // namespace
+
+void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result) {
+    *result = radix_sort(st, keys, vals, hist, digit_base, n, 24);
+}
+uint32_t trc_sort_hist_words(uint32_t n) { return 256u * ((n + kSortTile - 1) / kSortTile); }
+
+// the steps are the list at the top of this file; what the device finds wrong with the leaf records (fit_boxes) is found when the old scene has gone
+static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah, bool triangle_leaves) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    TreeBuild b{ctx, ctx->stream, s, sah, triangle_leaves};
+    TRC_TRY(intake(b));
+    const trc_status status = build_tree(b);
+    if (status != TRC_OK) trc_release_scene(ctx);
+    return status;
 }
 
 extern "C" {
@@ -682,9 +671,7 @@ trc_status trc_download_bvh(trc_ctx* ctx, trc_BVH* out, uint32_t capacity, uint3
     if (!out) return TRC_OK;
     if (capacity < ctx->n_bvh_ref) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_bvh: capacity too small");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TRC_TRY(trc_copy_to_host(ctx, out, ctx->d_bvh_ref, sizeof(trc_BVH) * ctx->n_bvh_ref, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TRC_OK;
+    return trc_copy_to_host(ctx, out, ctx->d_bvh_ref, sizeof(trc_BVH) * ctx->n_bvh_ref, ctx->stream);      // synchronous
 }
 
 trc_status trc_lbvh_info(trc_ctx* ctx, uint32_t* n_nodes, uint32_t* height, float* device_build_ms) {

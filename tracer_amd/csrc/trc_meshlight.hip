@@ -113,11 +113,8 @@ trc_status trc_mesh_light_build(trc_ctx* ctx) {
     hipLaunchKernelGGL(k_mesh_compact, dim3(1), dim3(1024), 0, ctx->stream, w, n, reinterpret_cast<uint32_t*>(t + L.tri), wl, count);
     hipLaunchKernelGGL(k_mesh_alias, dim3(1), dim3(64), 0, ctx->stream, wl, count, q, list, reinterpret_cast<uint2*>(t + L.alias), total);
     hipLaunchKernelGGL(k_mesh_pdf, dim3(grid), dim3(256), 0, ctx->stream, ms, w, total, reinterpret_cast<float*>(t + L.pdfA));
-    hipError_t e = hipGetLastError();
     struct { double total; uint32_t count, pad; } head = {0.0, 0u, 0u};
-    if (e == hipSuccess) e = hipMemcpyAsync(&head, t, sizeof head, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("mesh-light tables: ") + hipGetErrorString(e));
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "mesh-light tables", {{&head, t, sizeof head}}));
     ctx->d_meshl = static_cast<uint8_t*>(tables.release());
     ctx->mesh_n_lights = head.count;
     ctx->mesh_total = head.total;
@@ -176,7 +173,6 @@ trc_status trc_debug_mesh_light_tables(trc_ctx* ctx, uint32_t* alias, uint32_t* 
         if (alias && n && st == TRC_OK) st = trc_copy_to_host(ctx, alias, ctx->d_meshl + L.alias, (size_t)n * 8, ctx->stream);
         if (tri && n && st == TRC_OK) st = trc_copy_to_host(ctx, tri, ctx->d_meshl + L.tri, (size_t)n * 4, ctx->stream);
         if (pdfA && n_tri && st == TRC_OK) st = trc_copy_to_host(ctx, pdfA, ctx->d_meshl + L.pdfA, (size_t)n_tri * 4, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
     }
     if (total) *total = ctx->mesh_total;
     if (n_lights) *n_lights = n;

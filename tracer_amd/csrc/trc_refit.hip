@@ -242,9 +242,7 @@ trc_status refit_make_maps(trc_ctx* ctx) {
     hipLaunchKernelGGL(k_refit_parents, grid, b256, 0, st, nodes, n, ctx->d_refit_parent);
     hipLaunchKernelGGL(k_refit_levels, grid, b256, 0, st, ctx->d_refit_parent, n, d_level);
     REFIT_TRY(hipGetLastError(), "map kernels");
-    REFIT_TRY(hipMemcpyAsync(ctx->h_readback, d_level, sizeof level, hipMemcpyDeviceToHost, st), "level table");
-    REFIT_TRY(hipStreamSynchronize(st), "level table");
-    std::memcpy(level, ctx->h_readback, sizeof level);
+    TRC_TRY(trc_read_to_host(ctx, st, "trc_update_vertices: level table", {{level, d_level, sizeof level}}));
     if (level[kRefitBad]) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_update_vertices: the fat nodes are not numbered by depth");
     std::vector<uint32_t> levels{0u};
     for (uint32_t d = 1; d < kRefitMaxLevels && level[d] != 0u; ++d) levels.push_back(level[d]);
@@ -423,7 +421,6 @@ trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t
     if (!out) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_vertices: out == NULL with count > 0");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     TRC_TRY(trc_copy_to_host(ctx, out, ctx->d_verts + first, (size_t)count * sizeof(trc_TriangleVertex), ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TRC_OK;
 }
 

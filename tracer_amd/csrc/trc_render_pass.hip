@@ -80,7 +80,7 @@ trc_status ensure_sobol_tables(trc_ctx* ctx, uint32_t m) {
         if (m != 0 && trc_sobol_interval_tables(m, tb, tb + TRC_SOBOL_MATRIX_SIZE) != 0)
             return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "Sobol interval tables");
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));            // a launch in flight may still read the old tables
-        HIP_TRY(ctx, hipMemcpy(ctx->d_sobol_vdc, tb, sizeof(tb), hipMemcpyHostToDevice));
+        TRC_TRY(trc_copy_to_device(ctx, ctx->d_sobol_vdc, tb, sizeof(tb), ctx->stream));
         ctx->sobol_m = m;
     }
     return TRC_OK;

@@ -565,71 +565,73 @@ __global__ void __launch_bounds__(64) k_sah_finish(const DLeaf* elems, const SFi
     if (lane < S) vals[F + lane] = s_leaf[s_ord[lane]];
 }
 
-// Topology (tp) and leaf order (vals[position] = leaf index) of the SAH tree over leaves[0, n).  bad = the leaf-intake flag word.
-static trc_status sah_build_topology(trc_ctx* ctx, Buffers& buf, const DLeaf* d_leaves, uint32_t n, uint32_t* d_bad, DTopo tp, uint32_t* d_vals, uint32_t* out_height) {
-    hipStream_t st = ctx->stream;
+// Topology (t.tp) and leaf order (t.vals[0][position] = leaf index) of the SAH tree over t.leaves; the builder knows the tree's height,
+// which is the number of refit passes before fit_boxes first looks at the root (t.first_chunk).  The sibling of lbvh_topology.
+static trc_status sah_build_topology(TreeBuild& t) {
+    trc_ctx* const ctx = t.ctx;
+    hipStream_t st = t.st;
+    const uint32_t n = t.n;
     const uint32_t max_rows = n / kFinishSpan + 2u, max_tasks = n / kChunk + max_rows + 2u;
     const uint32_t n_counters = 2u + 2u * (TRC_MAX_BVH_DEPTH + 3u);
     SahBufs b{};
     b.n = n;
-    HIP_TRY(ctx, buf.alloc(&b.elems, n)); HIP_TRY(ctx, buf.alloc(&b.tmp, n)); HIP_TRY(ctx, buf.alloc(&b.mv, n));
-    for (int k = 0; k < 2; ++k) { HIP_TRY(ctx, buf.alloc(&b.nodes[k], max_rows)); HIP_TRY(ctx, buf.alloc(&b.task_node[k], max_tasks)); }
-    HIP_TRY(ctx, buf.alloc(&b.task_hist, (size_t)max_tasks * kSahBuckets));
-    HIP_TRY(ctx, buf.alloc(&b.finish, n / 2u + 2u));
-    HIP_TRY(ctx, buf.alloc(&b.counters, n_counters));
+    const char* const what = "sah build: work arrays";
+    TRC_TRY(t.tmp.alloc(ctx, &b.elems, n, what)); TRC_TRY(t.tmp.alloc(ctx, &b.tmp, n, what)); TRC_TRY(t.tmp.alloc(ctx, &b.mv, n, what));
+    for (int k = 0; k < 2; ++k) { TRC_TRY(t.tmp.alloc(ctx, &b.nodes[k], max_rows, what)); TRC_TRY(t.tmp.alloc(ctx, &b.task_node[k], max_tasks, what)); }
+    TRC_TRY(t.tmp.alloc(ctx, &b.task_hist, (size_t)max_tasks * kSahBuckets, what));
+    TRC_TRY(t.tmp.alloc(ctx, &b.finish, n / 2u + 2u, what));
+    TRC_TRY(t.tmp.alloc(ctx, &b.counters, n_counters, what));
     HIP_TRY(ctx, hipMemsetAsync(b.counters, 0, sizeof(uint32_t) * n_counters, st));
-    HIP_TRY(ctx, hipMemsetAsync(tp.parent_interior, 0, sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(t.tp.parent_interior, 0, sizeof(uint32_t), st));
     const dim3 g_leaf((n + 255) / 256), b256(256);
     uint32_t n_rows = 0, n_tasks = 0;
     if (n <= kFinishSpan) {
         const SFinish f{0u, n, 0u, 0u};                 // the root, depth 0
         const uint32_t one = 1u;
-        HIP_TRY(ctx, hipMemcpyAsync(b.finish, &f, sizeof f, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(b.counters, &one, sizeof one, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));          // f and one are on this frame
-        hipLaunchKernelGGL(k_sah_init, g_leaf, b256, 0, st, d_leaves, n, b.elems, d_bad, (SNode*)nullptr);
+        TRC_TRY(trc_copy_to_device(ctx, b.finish, &f, sizeof f, st));
+        TRC_TRY(trc_copy_to_device(ctx, b.counters, &one, sizeof one, st));
+        hipLaunchKernelGGL(k_sah_init, g_leaf, b256, 0, st, t.leaves, n, b.elems, t.bounds + 6, (SNode*)nullptr);
     } else {
         n_rows = 1; n_tasks = (n + kChunk - 1) / kChunk;
         hipLaunchKernelGGL(k_sah_root_row, dim3(1), dim3(128), 0, st, b.nodes[0], n);
         HIP_TRY(ctx, hipMemsetAsync(b.task_node[0], 0, sizeof(uint32_t) * n_tasks, st));
-        hipLaunchKernelGGL(k_sah_init, g_leaf, b256, 0, st, d_leaves, n, b.elems, d_bad, b.nodes[0]);
+        hipLaunchKernelGGL(k_sah_init, g_leaf, b256, 0, st, t.leaves, n, b.elems, t.bounds + 6, b.nodes[0]);
     }
     int cur = 0;
     bool broken = false;
     static_assert(sizeof(uint32_t) * (2u + 2u * (TRC_MAX_BVH_DEPTH + 3u) + 1u) <= kReadbackBytes, "h_readback holds the counter block and the intake flags");
     TRC_TRY(trc_readback_alloc(ctx));
-    uint32_t* hc = ctx->h_readback;      // pinned: the copy is queued behind k_sah_split and the host goes on launching
-    hc[0] = 0;
+    uint32_t* const h_readback = ctx->h_readback;      // pinned: the copy is queued behind k_sah_split and the host goes on launching
+    h_readback[0] = 0;
     for (uint32_t level = 0; n_rows > 0; ++level, cur ^= 1) {
         if (level > TRC_MAX_BVH_DEPTH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: tree deeper than TRC_MAX_BVH_DEPTH");
         uint32_t* next_counts = b.counters + 2u + 2u * (level + 1u);
         hipLaunchKernelGGL(k_sah_bins, dim3(n_tasks), b256, 0, st, b.elems, b.nodes[cur], b.task_node[cur], b.task_hist);
-        hipLaunchKernelGGL(k_sah_split, dim3((n_rows + 63u) / 64u), dim3(64), 0, st, b.nodes[cur], n_rows, b.nodes[cur ^ 1], next_counts, b.finish, b.counters, tp, n, level);
+        hipLaunchKernelGGL(k_sah_split, dim3((n_rows + 63u) / 64u), dim3(64), 0, st, b.nodes[cur], n_rows, b.nodes[cur ^ 1], next_counts, b.finish, b.counters, t.tp, n, level);
         // one read-back per level: the whole counter block (next level's rows / tasks, error bits)
-        HIP_TRY(ctx, hipMemcpyAsync(hc, b.counters, sizeof(uint32_t) * n_counters, hipMemcpyDeviceToHost, st));
-        hc[n_counters] = 0;
-        if (level == 0) HIP_TRY(ctx, hipMemcpyAsync(hc + n_counters, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));      // intake flags are final by now
+        HIP_TRY(ctx, hipMemcpyAsync(h_readback, b.counters, sizeof(uint32_t) * n_counters, hipMemcpyDeviceToHost, st));
+        h_readback[n_counters] = 0;
+        if (level == 0) HIP_TRY(ctx, hipMemcpyAsync(h_readback + n_counters, t.bounds + 6, sizeof(uint32_t), hipMemcpyDeviceToHost, st));      // intake flags are final by now
         hipLaunchKernelGGL(k_sah_scatter, dim3(n_tasks), b256, 0, st, b.elems, b.tmp, b.mv, b.nodes[cur], b.nodes[cur ^ 1], b.task_node[cur], b.task_hist, b.task_node[cur ^ 1]);
         hipLaunchKernelGGL(k_sah_apply, dim3(n_tasks), b256, 0, st, b.elems, b.tmp, b.mv, b.nodes[cur], b.nodes[cur ^ 1], b.task_node[cur]);
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        const uint32_t bad = hc[n_counters];
+        const uint32_t bad = h_readback[n_counters];
         if (bad & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
         if (bad) { n_rows = 0; broken = true; break; }     // the other intake errors are reported by the caller's refit
-        if (hc[1] & 16u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: one-sided partition on a positive extent");
-        const uint32_t next[2] = {hc[2u + 2u * (level + 1u)], hc[3u + 2u * (level + 1u)]};
+        if (h_readback[1] & 16u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: one-sided partition on a positive extent");
+        const uint32_t next[2] = {h_readback[2u + 2u * (level + 1u)], h_readback[3u + 2u * (level + 1u)]};
         n_rows = next[0]; n_tasks = next[1];
         if (n_rows > max_rows || n_tasks > max_tasks) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: level table overflow");
     }
-    hipLaunchKernelGGL(k_sah_vals, g_leaf, b256, 0, st, b.elems, n, d_vals);
+    hipLaunchKernelGGL(k_sah_vals, g_leaf, b256, 0, st, b.elems, n, t.vals[0]);
     if (broken) return TRC_OK;
-    const uint32_t n_finish = n <= kFinishSpan ? 1u : hc[0];       // every level's read-back came after its k_sah_split
+    const uint32_t n_finish = n <= kFinishSpan ? 1u : h_readback[0];       // every level's read-back came after its k_sah_split
     if (n_finish > n / 2u + 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: finish list overflow");
-    if (n_finish) hipLaunchKernelGGL(k_sah_finish, dim3(n_finish), dim3(64), 0, st, b.elems, b.finish, d_vals, b.counters, tp, n);
-    uint32_t* flags = hc;
-    HIP_TRY(ctx, hipMemcpyAsync(flags, b.counters, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (n_finish) hipLaunchKernelGGL(k_sah_finish, dim3(n_finish), dim3(64), 0, st, b.elems, b.finish, t.vals[0], b.counters, t.tp, n);
+    HIP_TRY(ctx, hipMemcpyAsync(h_readback, b.counters, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    *out_height = flags[2];
-    if (flags[1] & 16u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: one-sided partition on a positive extent");
+    t.first_chunk = std::min(std::max(h_readback[2], 1u), TRC_MAX_BVH_DEPTH + 1u);
+    if (h_readback[1] & 16u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: one-sided partition on a positive extent");
     HIP_TRY(ctx, hipGetLastError());
     return TRC_OK;
 }

@@ -678,8 +678,7 @@ trc_status trc_sppm_init(trc_ctx* ctx, uint64_t photon_seed) {
     DComplex h;
     std::memset(&h, 0, sizeof h);
     for (int k = 0; k < 3; ++k) { h.key_min[k] = 0xFF7FFFFFu; h.key_max[k] = 0x00800000u; }      // f2key(FLT_MAX), f2key(-FLT_MAX): k_sppm_camera
-    HIP_TRY(ctx, hipMemcpyAsync(s->d_cx, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // `h` is a stack temporary
+    TRC_TRY(trc_copy_to_device(ctx, s->d_cx, &h, sizeof h, ctx->stream));
     hipLaunchKernelGGL(k_sppm_seed, dim3((unsigned)((nph + 255) / 256)), dim3(256), 0, ctx->stream, s->d_photon_rng,
                        (uint32_t)nph, photon_seed);
     HIP_TRY(ctx, hipGetLastError());
@@ -871,8 +870,7 @@ trc_status trc_sppm_download(trc_ctx* ctx, trc_CameraRecord* cam, trc_PhotonReco
     if (mark) { hm.resize(nph); TRC_TRY(trc_copy_to_host(ctx, hm.data(), s->d_mark, nph * 4, ctx->stream)); }
     if (count) { hc.resize(nph); TRC_TRY(trc_copy_to_host(ctx, hc.data(), s->d_count, nph * 4, ctx->stream)); }
     DComplex h;
-    HIP_TRY(ctx, hipMemcpyAsync(&h, s->d_cx, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "SPPM parameters", {{&h, s->d_cx, sizeof h}}));
     if (mark) for (size_t c = 0; c < nph; ++c) {
         if (hm[c] == 0) { mark[4 * c] = mark[4 * c + 1] = mark[4 * c + 2] = mark[4 * c + 3] = -1.0f; }
         else {
