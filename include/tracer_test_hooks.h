@@ -81,6 +81,21 @@ typedef struct trc_kernel_choice {
 } trc_kernel_choice;
 trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out);
 
+
+/* test hook of the LDS plans (trc_render_pass.hip: resident_workgroups): how the kernel of the last render launch sits on a CU.
+ * cu_count: CUs of the device; block: threads per workgroup; waves: wavefronts per SIMD of the kernel's launch bounds; lds_bytes: dynamic
+ * LDS per workgroup; planned_per_cu: workgroups per CU the launch's plan is for (4 x waves, or the persistent workgroups' count);
+ * planned_with: the runtime's answer the planner used; per_cu: hipOccupancyMaxActiveBlocksPerMultiprocessor for (kernel, block,
+ * lds_bytes), asked again by this call.  The runtime's query counts bytes; beside it, plain arithmetic: lds_static_bytes: the kernel's own
+ * LDS; per_cu_block1280: workgroups of lds_bytes + lds_static_bytes that 160 KB hold if LDS is granted in blocks of 1280 bytes.
+ * dense_memo_rows: primary-replay rows in that LDS when k_render_dense ran (else 0).  All zero before the first launch. */
+typedef struct trc_residency {
+    uint32_t cu_count, block, waves, planned_per_cu, planned_with, per_cu;
+    uint64_t lds_bytes;
+    uint32_t lds_static_bytes, per_cu_block1280, dense_memo_rows, reserved;
+} trc_residency;
+trc_status trc_debug_last_residency(trc_ctx* ctx, trc_residency* out);
+
 #ifdef __cplusplus
 }
 #endif

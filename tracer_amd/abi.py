@@ -227,6 +227,13 @@ class KernelChoice(C.Structure):
                 ("strip", C.c_uint32), ("launches", C.c_uint32)]
 
 
+class Residency(C.Structure):
+    """trc_residency (tracer_test_hooks.h)"""
+    _fields_ = [("cu_count", C.c_uint32), ("block", C.c_uint32), ("waves", C.c_uint32), ("planned_per_cu", C.c_uint32),
+                ("planned_with", C.c_uint32), ("per_cu", C.c_uint32), ("lds_bytes", C.c_uint64),
+                ("lds_static_bytes", C.c_uint32), ("per_cu_block1280", C.c_uint32), ("dense_memo_rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 KERNEL_SHAPES = ("one", "strip", "pwg", "dense")                                                  # trc_kernel_choice.shape
 KERNEL_VARIANTS = ("plain", "stats", "sobol", "tex", "env", "env_tex", "mesh", "mesh_tex")         # ... .variant (RenderVariant)
 
@@ -270,7 +277,8 @@ DEVICE_SYMBOLS = [
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
-                "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test", "trc_debug_last_kernel"]
+                "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test", "trc_debug_last_kernel",
+                "trc_debug_last_residency"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",

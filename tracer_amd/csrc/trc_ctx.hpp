@@ -239,6 +239,9 @@ struct trc_ctx {
     // launch shape (0 one block per one-wavefront workgroup, 1 strips, 2 persistent workgroups, 3 k_render_dense), the RenderVariant,
     // whether the whole tree was staged in LDS, whether the per-triangle-material twins ran, and the strip length; launches counted
     struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0; } last_kernel;
+    // ... and how that launch sits on a CU (trc_debug_last_residency): the kernel, its workgroup size and dynamic LDS, the workgroups per
+    // CU its plan is for (4 x the waves of its launch bounds; the persistent workgroups' per-CU count) and the runtime's answer
+    struct LastFit { const void* fn = nullptr; uint32_t block = 0, waves = 0, planned_per_cu = 0, per_cu = 0; size_t lds = 0; } last_fit;
     trc_params deferred{}; bool has_deferred = false; uint64_t deferred_calls = 0;   // a launch of few samples kept for coalescing (trc_render)
     int cost_head_age = 0;                    // 1: the costs are a cold head's (trc_render), 2: the launch after it ran on them
     bool cost_fresh_next = false;             // the next ordered launch takes the last launch's raw durations as its costs (trc_set_camera, policy 2)
@@ -321,6 +324,10 @@ struct trc_ctx {
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
     std::vector<const void*> lds_granted;
+    // workgroups of a render kernel that one CU holds at once, as the runtime answers for (kernel, workgroup size, dynamic LDS) on this
+    // context's device (trc_render_pass.hip: resident_workgroups); asked once per combination
+    struct Residency { const void* fn; uint32_t block; size_t lds; uint32_t per_cu; };
+    std::vector<Residency> residency;
 
     bool grouped() const { return comm != nullptr || coll_active; }
 };

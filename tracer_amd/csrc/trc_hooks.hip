@@ -5,6 +5,7 @@
 #include <string>
 
 #include "trc_ctx.hpp"
+#include "trc_render_config.hpp"
 
 extern "C" int trc_has_test_hooks(void) {
 #ifdef TRC_TEST_HOOKS
@@ -98,6 +99,26 @@ trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out) {
     const trc_ctx::LastKernel& k = ctx->last_kernel;
     out->shape = k.shape; out->variant = k.variant; out->lds_resident = k.lds_resident; out->triangle_materials = k.tri_materials;
     out->strip = k.strip; out->launches = k.count;
+    return TRC_OK;
+}
+// how the kernel of the last render launch sits on a CU (trc_render_pass.hip: resident_workgroups): the runtime's answer, asked again here,
+// beside the plain arithmetic of trc_lds_fit.hpp for an allocation block of 1280 bytes (320 dwords) -- the runtime's query counts bytes
+trc_status trc_debug_last_residency(trc_ctx* ctx, trc_residency* out) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx || !out) return TRC_ERR_INVALID_ARG;
+    const trc_ctx::LastFit& f = ctx->last_fit;
+    *out = trc_residency{};
+    if (!f.fn) return TRC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int now = 0;
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&now, f.fn, (int)f.block, f.lds));      // not the planner's copy
+    hipFuncAttributes attr{};
+    HIP_TRY(ctx, hipFuncGetAttributes(&attr, f.fn));
+    out->cu_count = (uint32_t)ctx->cu_count; out->block = f.block; out->waves = f.waves; out->planned_per_cu = f.planned_per_cu;
+    out->planned_with = f.per_cu; out->per_cu = now > 0 ? (uint32_t)now : 0u; out->lds_bytes = (uint64_t)f.lds;
+    out->lds_static_bytes = (uint32_t)attr.sharedSizeBytes;
+    out->per_cu_block1280 = trc_lds_workgroups((uint32_t)(f.lds + attr.sharedSizeBytes), 1280u, 160u * 1024u);
+    out->dense_memo_rows = ctx->last_kernel.shape == 3u ? (uint32_t)TRC_REPLAY_DENSE : 0u;
     return TRC_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "trc_ctx.hpp"
+#include "trc_lds_fit.hpp"
 
 // "test now, build the record for the winner afterwards" (dev_intersect.hpp: trav_test_leaf<DEFER>), per tree residence
 // two-level traversal stack (first entries in LDS, deeper ones in global rows: dev_intersect.hpp stack_put) per integrator, on
@@ -38,6 +39,10 @@ constexpr bool hybrid_stack(int integrator) {
 // ... and at 6 when the launch list is many times the wavefront slots (a whole 1080p frame: 19.85 -> 19.63 ms; its 25-52 spilled
 // dwords lengthen a lone block's chain, so shares of a frame -- which end on their slowest block -- keep the 5-wave kernel:
 // an eighth of config 2 5.6 against 5.9 ms).  k_render_dense: tracePath, LDS-resident tree, production, no Sobol'.
+// Measured again with the primary replay in place (profiles/r17/ab_lds_fit.txt; 80 registers + 112 B of scratch per lane, 1.6 % of the
+// kernel's instructions scratch accesses, against 96 + 36 B and 0.5 % at 5): 5 waves 15.20 ms where 6 with 8 memo rows run 15.73 -- but 6
+// with SEVEN rows 15.10, at 0.92 of its wavefront slots busy under the counters where 8 rows had 0.82 (profiles/r17/occupancy.txt): the
+// sixth wave was short of LDS more than of registers (TRC_REPLAY_DENSE below).  6 stays.
 #ifndef TRC_PATH_WAVES_DENSE
 #define TRC_PATH_WAVES_DENSE 6
 #endif
@@ -117,8 +122,14 @@ static_assert((TRC_PARK_PATH == 0 || TRC_PARK_PATH == 8 || TRC_PARK_PATH == 10) 
 // A lane keeps what the integrator reads of that hit -- p, gn, tag, material | the side sn took, with 10 rows uv -- in MEMO words of a
 // column of its own (row r at memo[r * kBlock]) after the first walk of a block, and a later sample whose origin has the eye's bits takes
 // the record from there instead of walking.  Per kernel family, 0 = compiled out:
-//   k_render_dense       8 rows of LDS behind the stack rows (what six waves per SIMD leave).  uv has no row: a hit whose colour reads
-//                        rec.uv (a checker texture on a cube or a triangle) is not kept, and that pixel walks every sample
+//   k_render_dense       7 rows of LDS behind the stack rows: tag, material, side and the replay count of a column that lost its record
+//                        share ONE word (trc_lds_fit.hpp).  The headline scene's workgroup is then 3008 B of scene + 6 stack rows + 7 memo
+//                        rows = 6336 B, and 24 of them -- six waves per SIMD -- fit a CU's 160 KB whether LDS is granted in 512-byte or
+//                        in 1280-byte blocks; with 8 rows (6592 B) the runtime still answers 24, but the counters show 0.82 of 6144
+//                        wavefront slots busy (= 0.93 of the 5376 that 21 per CU make) against 0.92 with 7, and the launch 4 % slower:
+//                        15.73 -> 15.10 ms (profiles/r17/occupancy.txt, ab_lds_fit.txt; 5 waves with 8 / 10 / 7 rows: 15.20 / 15.23 / 15.23).  uv has no row: a hit whose
+//                        colour reads rec.uv (a checker texture on a cube or a triangle) is not kept, and that pixel walks every sample;
+//                        nor is a hit whose material or primitive index does not fit the word's 8 / 20 bits
 //   k_render_pwg<path>   10 rows per wavefront in global memory, sized per launch like the overflow rows of the stack (coalesced 256 B)
 // TRC_REPLAY_DENSE_GLOBAL 1 puts the dense kernel's rows in global memory too (the storage A/B).  Scheduling (knobs replay_min_lanes /
 // replay_chain): where at least TRC_REPLAY_MIN_LANES lanes of a wavefront hold a replayed hit, a trip of the loop shades those lanes alone, at
@@ -127,10 +138,11 @@ static_assert((TRC_PARK_PATH == 0 || TRC_PARK_PATH == 8 || TRC_PARK_PATH == 10) 
 // 15.7 / 15.7 / 16.2 / 17.4; plain 17.6; 1 lane, trips unbounded 21.0 (pixels that replay 63 times in a row starve the walkers).
 // traceMIS / traceVolume, Sobol', k_render, the strip and the instrumented kernels always walk.
 enum : uint32_t { kMemoPx = 0, kMemoPy, kMemoPz, kMemoNx, kMemoNy, kMemoNz, kMemoTag, kMemoMat, kMemoU, kMemoV };
+constexpr uint32_t kMemoWord = kMemoTag;           // 7 rows: tag, material, side and replay count packed into this one (trc_lds_fit.hpp)
 constexpr uint32_t kMemoNone = 0xFFFFFFFFu;        // the material word of a column that holds no record (its tag word: replays so far)
 constexpr uint32_t kMemoSameSide = 0x80000000u;    // material word: sn == gn (else sn == -gn: check_face)
 #ifndef TRC_REPLAY_DENSE
-#define TRC_REPLAY_DENSE 8
+#define TRC_REPLAY_DENSE 7
 #endif
 #ifndef TRC_REPLAY_DENSE_GLOBAL
 #define TRC_REPLAY_DENSE_GLOBAL 0
@@ -144,7 +156,7 @@ constexpr uint32_t kMemoSameSide = 0x80000000u;    // material word: sn == gn (e
 #ifndef TRC_REPLAY_CHAIN
 #define TRC_REPLAY_CHAIN 1
 #endif
-static_assert((TRC_REPLAY_DENSE == 0 || TRC_REPLAY_DENSE == 8 || TRC_REPLAY_DENSE == 10) && (TRC_REPLAY_PWG_PATH == 0 || TRC_REPLAY_PWG_PATH == 10), "memo rows: 0, 8 or 10 (10 wherever image textures may be live)");
+static_assert((TRC_REPLAY_DENSE == 0 || TRC_REPLAY_DENSE == 7 || TRC_REPLAY_DENSE == 8 || TRC_REPLAY_DENSE == 10) && (TRC_REPLAY_PWG_PATH == 0 || TRC_REPLAY_PWG_PATH == 10), "memo rows: 0, 7 (dense), 8 or 10 (10 wherever image textures may be live)");
 constexpr uint32_t dense_lds_rows() { return (uint32_t)TRC_PARK_DENSE + (TRC_REPLAY_DENSE_GLOBAL ? 0u : (uint32_t)TRC_REPLAY_DENSE); }      // LDS rows of k_render_dense behind its stack
 constexpr uint32_t pwg_memo_rows(int integrator) { return integrator == TRC_INTEGRATOR_PATH ? (uint32_t)TRC_REPLAY_PWG_PATH : 0u; }
 #ifndef TRC_PWG_STACK_LDS_PATH

@@ -63,7 +63,7 @@ __device__ __forceinline__ void fill_path_ctx(PathCtxOf<TEX, LIGHT>& cx, const K
         cx.sobol_m = kp.sobol_m; cx.sobol_res = 1u << kp.sobol_m;
     }
 }
-// MEMO = 8 | 10 (round 8, tracePath production kernels; trc_render_config.hpp: primary replay): the hit of the pixel's camera ray, kept
+// MEMO = 7 | 8 | 10 (round 8, tracePath production kernels; trc_render_config.hpp: primary replay): the hit of the pixel's camera ray, kept
 // after the block's first walk in MEMO words of the lane's column `memo` (LDS or global rows).  A later sample whose camera ray has the
 // same origin bits -- the direction follows from (origin, u, v, camera) -- takes its record from there: no walk, and (kp.replay lanes) it is
 // shaded before the wavefront's next walk, so that a lane needs one trip round the loop per BOUNCE ray.  The ray is still counted
@@ -75,6 +75,7 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
                                              const LightTables<LIGHT>* tables = nullptr, uint32_t* memo = nullptr) {
     static_assert(MEMO == 0 || (INTEGRATOR == TRC_INTEGRATOR_PATH && !STATS && !SOBOL && LIGHT == Light::None), "primary replay: tracePath production kernels");
     static_assert(MEMO == 0 || MEMO == 10 || !TEX, "an image texture reads rec.uv: 10 memo rows");
+    constexpr bool kPacked = MEMO == 7;          // material, side, tag and replay count in ONE word (trc_lds_fit.hpp), row kMemoWord
     uint32_t replays = 0;                        // camera rays of this lane answered from the memo
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
     const uint32_t entry = kp.order ? kp.order[slot] : slot;     // adaptive launch order / cost-adaptive block size (trc_render)
@@ -146,23 +147,25 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
             path_begin(ps, cast_ray(kp.cam, u, v, rng), kp.max_depth);
             if constexpr (MEMO != 0) {
                 if (replay_on && s != 0u) {
-                    const uint32_t mat = memo[kMemoMat * kBlock];
-                    if (mat != kMemoNone) {
+                    const uint32_t mat = memo[(kPacked ? kMemoWord : kMemoMat) * kBlock];
+                    if (kPacked ? !trc_memo_is_none(mat) : mat != kMemoNone) {
                         if (at_eye(ps.ray.o)) {                 // the memoised ray: its record, as Scene::hit left it for the integrator
-                            const uint32_t tag = memo[kMemoTag * kBlock];
+                            const uint32_t tag = kPacked ? (trc_memo_is_ends(mat) ? kTagNone : (trc_memo_tag_type(mat) << kTagIndexBits) | trc_memo_tag_index(mat))
+                                                         : memo[kMemoTag * kBlock];
                             if (tag == kTagNone) terminal = true;
                             else {
                                 ps.rec.p = f3(memo_f(kMemoPx), memo_f(kMemoPy), memo_f(kMemoPz));
                                 ps.rec.gn = f3(memo_f(kMemoNx), memo_f(kMemoNy), memo_f(kMemoNz));
-                                ps.rec.sn = (mat & kMemoSameSide) ? ps.rec.gn : -ps.rec.gn;
-                                ps.rec.material = mat & ~kMemoSameSide;
+                                ps.rec.sn = (kPacked ? trc_memo_same_side(mat) : (mat & kMemoSameSide) != 0u) ? ps.rec.gn : -ps.rec.gn;
+                                ps.rec.material = kPacked ? trc_memo_material(mat) : mat & ~kMemoSameSide;
                                 ps.rec.tag = tag;
                                 if constexpr (MEMO >= 10) { ps.rec.uv.x = memo_f(kMemoU); ps.rec.uv.y = memo_f(kMemoV); }
                                 have = true;
                             }
                             bump(n_rays);                       // still one Scene::hit of the algorithm
                         } else {                                // another ray (a lens): the pixel walks from here on; s - 1 samples replayed
-                            memo[kMemoMat * kBlock] = kMemoNone; memo[kMemoTag * kBlock] = s - 1u;
+                            if constexpr (kPacked) memo[kMemoWord * kBlock] = trc_memo_pack_none(s - 1u);
+                            else { memo[kMemoMat * kBlock] = kMemoNone; memo[kMemoTag * kBlock] = s - 1u; }
                         }
                     }
                 }
@@ -227,7 +230,9 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
                 else {
                     // 8 rows have no room for uv, which only a checker texture on a cube or a triangle reads (hit_color): such a hit is not kept
                     const bool uv_read = MEMO < 10 && (ps.rec.tag >> kTagIndexBits) >= 2u && mat_tex(cx.sh, ps.rec.material) == kTexChecker;
-                    if (!uv_read && ps.rec.material < kMemoSameSide - 1u) {
+                    const bool fits = kPacked ? trc_memo_packable(ps.rec.material, ps.rec.tag >> kTagIndexBits, ps.rec.tag & kTagIndexMask)
+                                              : ps.rec.material < kMemoSameSide - 1u;
+                    if (!uv_read && fits) {
                         const bool same = __float_as_uint(ps.rec.sn.x) == __float_as_uint(ps.rec.gn.x);      // sn is gn or -gn (check_face)
                         mat = ps.rec.material | (same ? kMemoSameSide : 0u); tag = ps.rec.tag;
                         memo[kMemoPx * kBlock] = __float_as_uint(ps.rec.p.x); memo[kMemoPy * kBlock] = __float_as_uint(ps.rec.p.y);
@@ -238,7 +243,10 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
                     }
                 }
             }
-            memo[kMemoMat * kBlock] = mat; memo[kMemoTag * kBlock] = tag;
+            if constexpr (kPacked) {
+                memo[kMemoWord * kBlock] = mat == kMemoNone ? trc_memo_pack_none(0u) : tag == kTagNone ? trc_memo_pack_ends()
+                                         : trc_memo_pack_hit(mat & ~kMemoSameSide, (mat & kMemoSameSide) != 0u, tag >> kTagIndexBits, tag & kTagIndexMask);
+            } else { memo[kMemoMat * kBlock] = mat; memo[kMemoTag * kBlock] = tag; }
             return ends;
         };
         // flat loop: one Scene::hit per iteration; a finished path immediately regenerates the next sample
@@ -278,7 +286,8 @@ __device__ __forceinline__ void render_block(const KRender& kp, const DScene& sc
             }
         }
         if constexpr (MEMO != 0) {      // a column that still holds its record answered every sample but the first; one that lost it says how many
-            if (replay_on) replays = memo[kMemoMat * kBlock] != kMemoNone ? kp.spp - 1u : memo[kMemoTag * kBlock];
+            if constexpr (kPacked) { if (replay_on) { const uint32_t w = memo[kMemoWord * kBlock]; replays = trc_memo_is_none(w) ? trc_memo_count(w) : kp.spp - 1u; } }
+            else if (replay_on) replays = memo[kMemoMat * kBlock] != kMemoNone ? kp.spp - 1u : memo[kMemoTag * kBlock];
         }
         if constexpr (PARK) {       // the loop is left by the last finish_sample only (trc_render launches spp >= 1): what that one would
             n_paths += kp.spp;      // have put into the texel, and one finished sample per call of it

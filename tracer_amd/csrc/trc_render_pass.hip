@@ -30,24 +30,79 @@ static void set_hybrid_stack(DScene& sc, uint32_t levels) {
     sc.stack_lds = std::min(sc.stack_depth, std::max(1u, levels));
     sc.stack_ovf_rows = sc.stack_depth - sc.stack_lds;
 }
-static void plan_launch_lds(const trc_ctx* ctx, DScene& sc, uint32_t waves_per_simd, bool hybrid) {
+// More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per device (the attribute is set
+// on the current device's copy of the function): remembered in the context, which is bound to one device.
+static hipError_t grant_lds(trc_ctx* ctx, const void* fn, size_t lds) {
+    if (lds <= 64 * 1024 || std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) != ctx->lds_granted.end()) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+    if (e == hipSuccess) ctx->lds_granted.push_back(fn);
+    return e;
+}
+
+// Workgroups of `block` threads and `lds` bytes of dynamic LDS of kernel `fn` that one CU holds at once: the runtime's answer, which
+// knows the kernel's registers and the unit LDS is granted in on this device (a hand formula knew neither: it assumed 512 bytes, and
+// the launch plans counted wavefront slots the CU never filled).  Asked once per (kernel, block, lds) and context.
+static trc_status resident_workgroups(trc_ctx* ctx, const void* fn, uint32_t block, size_t lds, uint32_t* per_cu) {
+    for (const trc_ctx::Residency& e : ctx->residency)
+        if (e.fn == fn && e.block == block && e.lds == lds) { *per_cu = e.per_cu; return TRC_OK; }
+    HIP_TRY(ctx, grant_lds(ctx, fn, lds));
+    if (ctx->residency.size() >= 64u) ctx->residency.clear();      // (a context that has seen many scenes: start over, the answers come back)
+    int n = 0;
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, (int)block, lds));
+    *per_cu = (uint32_t)std::max(n, 0);
+    ctx->residency.push_back({fn, block, lds, *per_cu});
+    return TRC_OK;
+}
+// ... and of the same kernel with no dynamic LDS at all: what its registers allow, the most any LDS plan can reach
+static trc_status resident_by_registers(trc_ctx* ctx, const void* fn, uint32_t block, uint32_t* per_cu) { return resident_workgroups(ctx, fn, block, 0, per_cu); }
+
+// LDS is planned in steps of 512 bytes; where the runtime then admits fewer workgroups than the plan is for, the plan is made again
+// for a share one step smaller, until they fit
+constexpr uint32_t kLdsStepDwords = 128;
+
+static trc_status plan_launch_lds(trc_ctx* ctx, DScene& sc, const RenderKernel& kern, bool hybrid) {
     const uint32_t levels = ctx->knobs.stack_lds_levels > 0 ? (uint32_t)ctx->knobs.stack_lds_levels : kStackLdsLevels;
     if (hybrid) set_hybrid_stack(sc, ctx->knobs.no_lds_fit ? std::max(levels, sc.stack_depth) : levels);      // (knob: the whole stack in LDS)
-    if (ctx->knobs.no_lds_fit) return;                                                 // A/B knobs (trc_debug_set)
-    if (!ctx->lds_prefix_ok) return;                                                   // all or nothing was decided at upload
-    const uint32_t per_wg = ((160u * 1024u / 4u) / (4u * waves_per_simd)) & ~127u;     // dwords; LDS is granted in 512-byte units
-    const uint32_t stack = sc.stack_lds * kBlock;
-    uint32_t room = std::max(per_wg > stack ? per_wg - stack : 0u, sc.off_nodes + kNodeDwords);
-    room = std::min(room, kLdsSceneBytes / 4);
-    sc.n_lds_nodes = std::min(sc.n_nodes, (room - sc.off_nodes) / kNodeDwords);
-    sc.lds_dwords = sc.off_nodes + sc.n_lds_nodes * kNodeDwords;
+    if (ctx->knobs.no_lds_fit) return TRC_OK;                                          // A/B knobs (trc_debug_set)
+    if (!ctx->lds_prefix_ok) return TRC_OK;                                            // all or nothing was decided at upload
+    const uint32_t planned = 4u * (uint32_t)kern.waves;                                // workgroups per CU the kernel is compiled for
+    uint32_t want = 0;
+    TRC_TRY(resident_by_registers(ctx, kern.fn, kBlock, &want));
+    want = std::min(want, planned);
+    const uint32_t share = ((160u * 1024u / 4u) / planned) & ~(kLdsStepDwords - 1u);   // dwords
+    const uint32_t least = sc.off_nodes + kNodeDwords;
+    // the node prefix for a share of `per_wg` dwords beside the stack rows
+    auto plan_prefix = [&](uint32_t per_wg) {
+        const uint32_t stack = sc.stack_lds * kBlock;
+        uint32_t room = std::max(per_wg > stack ? per_wg - stack : 0u, least);
+        room = std::min(room, kLdsSceneBytes / 4);
+        sc.n_lds_nodes = std::min(sc.n_nodes, (room - sc.off_nodes) / kNodeDwords);
+        sc.lds_dwords = sc.off_nodes + sc.n_lds_nodes * kNodeDwords;
+        return room > least;                                                           // there is prefix left to give back
+    };
+    plan_prefix(share);
+    const DScene first = sc;
+    // checked against the runtime: give back node prefix, 512 bytes at a time; then (a stack of two levels, no knob) one stack entry
+    // in LDS and the prefix again -- down to the six entries the persistent workgroups stop at too
+    for (uint32_t lv = sc.stack_lds;; --lv) {
+        if (lv != first.stack_lds) set_hybrid_stack(sc, lv);
+        for (uint32_t per_wg = share;; per_wg -= kLdsStepDwords) {
+            const bool more = plan_prefix(per_wg);
+            uint32_t fit = 0;
+            TRC_TRY(resident_workgroups(ctx, kern.fn, kBlock, dyn_lds_bytes(sc, false), &fit));
+            if (fit >= want) return TRC_OK;
+            if (!more || per_wg < kLdsStepDwords) break;
+        }
+        if (!hybrid || lv <= 6u || ctx->knobs.stack_lds_levels > 0) break;
+    }
+    sc = first;                              // nothing the plan can give back lets `want` in: the first plan, as it always ran
+    return TRC_OK;
 }
 
 // LDS plan of a persistent-workgroup launch (k_render_pwg): `waves` wavefronts share one staged prefix; the workgroup's
 // share of the CU's 160 KB minus the wavefronts' stacks is all node prefix.  False when even one node does not fit.
-static bool plan_pwg_lds(const trc_ctx* ctx, DScene& sc, uint32_t waves, uint32_t per_cu, bool hybrid, uint32_t default_levels, uint32_t park_rows) {
+static bool plan_pwg_share(const trc_ctx* ctx, DScene& sc, uint32_t waves, uint32_t per_wg, bool hybrid, uint32_t default_levels, uint32_t park_rows) {
     uint32_t levels = ctx->knobs.stack_lds_levels > 0 ? (uint32_t)ctx->knobs.stack_lds_levels : default_levels;      // trc_render_config.hpp
-    const uint32_t per_wg = ((160u * 1024u / 4u) / per_cu) & ~127u;
     for (;; --levels) {
         DScene t = sc;
         if (hybrid) set_hybrid_stack(t, levels);
@@ -61,6 +116,14 @@ static bool plan_pwg_lds(const trc_ctx* ctx, DScene& sc, uint32_t waves, uint32_
         // a scene with many analytic primitives / materials: fewer stack entries in LDS before giving the persistent workgroups up
         if (!hybrid || levels <= 6u || ctx->knobs.stack_lds_levels > 0) return false;
     }
+}
+static size_t pwg_lds_bytes(const DScene& sc, uint32_t waves, uint32_t park_rows) {
+    return ((size_t)sc.lds_dwords + (size_t)waves * (sc.stack_lds + park_rows) * kBlock) * 4;
+}
+// ... for `per_cu` workgroups per CU.  (Not checked against the runtime as plan_launch_lds is: with that check the full bench ran
+// traceVolume 1.4 % slower, outside its spread: profiles/r17/other_configs.txt.)
+static bool plan_pwg_lds(const trc_ctx* ctx, DScene& sc, uint32_t waves, uint32_t per_cu, bool hybrid, uint32_t default_levels, uint32_t park_rows) {
+    return plan_pwg_share(ctx, sc, waves, ((160u * 1024u / 4u) / per_cu) & ~(kLdsStepDwords - 1u), hybrid, default_levels, park_rows);
 }
 
 namespace {
@@ -96,15 +159,10 @@ const RenderKernels& render_family(bool lds_scene, uint32_t integrator, bool tri
     return *(tri_materials ? (lds_scene ? lds_tm : mem_tm) : (lds_scene ? lds : mem))[integrator];
 }
 
-// One render launch.  More than 64 KB of dynamic LDS (the persistent workgroups) has to be asked for once per kernel AND per
-// device (the attribute is set on the current device's copy of the function): remembered in the context, which is bound to one device.
+// One render launch (more than 64 KB of dynamic LDS: grant_lds).
 hipError_t launch_render(trc_ctx* ctx, const RenderLaunch& r) {
     const void* const fn = r.kern.fn;
-    if (r.lds > 64 * 1024 && std::find(ctx->lds_granted.begin(), ctx->lds_granted.end(), fn) == ctx->lds_granted.end()) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) return e;
-        ctx->lds_granted.push_back(fn);
-    }
+    if (const hipError_t e = grant_lds(ctx, fn, r.lds); e != hipSuccess) return e;
     // the parameter block the kernel's RenderArgs asks for: the launch's parameters alone, or with its light's tables behind them
     KRenderEnv kpe;
     KRenderMesh kpm;
@@ -319,13 +377,18 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
     const int integrator = (int)p->integrator;
     const RenderKernels& family = render_family(ctx->lds_scene, p->integrator, ctx->tri_materials);
     const RenderKernel& render_dense = ctx->tri_materials ? trimat::render_dense : ::render_dense;
-    // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD
+    const bool tex = ctx->tex_active();
+    const RenderVariant variant = r.light == Light::Mesh ? (tex ? kVariantMeshTex : kVariantMesh) : r.light == Light::Env ? (tex ? kVariantEnvTex : kVariantEnv)
+                                : tex ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
+    // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD -- where the
+    // CU holds (the runtime's answer) the workgroups the kernel is compiled for, with their memo rows
     r.dense = ctx->lds_scene && integrator == TRC_INTEGRATOR_PATH && !r.stats && !r.sobol && !ctx->tex_active() && kp.strip == 1 && !ctx->knobs.no_dense &&
-              ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * render_dense.waves &&
-              ((dyn_lds_bytes(kp.ks.sc, false) + (size_t)dense_lds_rows() * kBlock * 4u + 511u) & ~(size_t)511u) * 4u * render_dense.waves <= 160u * 1024u;
-    // wavefront slots of the kernel this launch runs (the split plan's model).  Strip and persistent-workgroup launches count
-    // the one-wavefront kernel's waves, as they always have (a strip launch plans nothing; the persistent ones' default is the same).
-    r.wave_slots = (uint32_t)ctx->cu_count * 4u * (uint32_t)(r.dense ? render_dense : family.one[kVariantPlain]).waves;
+              ctx->n_tiles >= (uint32_t)TRC_DENSE_MIN_BLOCKS_PER_SLOT * (uint32_t)ctx->cu_count * 4u * render_dense.waves;
+    uint32_t dense_per_cu = 0;
+    if (r.dense) {
+        TRC_TRY(resident_workgroups(ctx, render_dense.fn, kBlock, dyn_lds_bytes(kp.ks.sc, false) + (size_t)dense_lds_rows() * kBlock * 4u, &dense_per_cu));
+        r.dense = dense_per_cu >= 4u * (uint32_t)render_dense.waves;
+    }
     uint32_t park_rows = r.dense ? dense_lds_rows() : 0u;      // LDS rows of parked per-pixel state and of the primary-replay memo (render_block)
     const bool mem_plan = !r.stats && !ctx->lds_scene;                   // trees read from memory: the LDS is planned per launch
     if (mem_plan && !ctx->knobs.no_pwg && kp.strip == 1 && ctx->lds_prefix_ok) {       // no_pwg: A/B knob
@@ -334,9 +397,6 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
         r.pwg = plan_pwg_lds(ctx, kp.ks.sc, r.pwg_waves, (uint32_t)pwg_per_cu(integrator), hybrid_stack(integrator), pwg_stack_lds_levels(integrator), park_rows);
         if (!r.pwg) park_rows = 0u;
     }
-    const bool tex = ctx->tex_active();
-    const RenderVariant variant = r.light == Light::Mesh ? (tex ? kVariantMeshTex : kVariantMesh) : r.light == Light::Env ? (tex ? kVariantEnvTex : kVariantEnv)
-                                : tex ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     r.kern = r.dense ? render_dense : (r.pwg ? family.pwg : kp.strip > 1 ? family.strip : family.one)[variant];
     if (!r.kern.fn) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "no render kernel for this integrator, flags and launch shape");
     ctx->last_kernel.shape = r.dense ? 3u : r.pwg ? 2u : kp.strip > 1 ? 1u : 0u;                 // trc_debug_last_kernel
@@ -345,9 +405,18 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
     ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
     ctx->last_kernel.strip = kp.strip;
     ctx->last_kernel.count++;
-    if (mem_plan && !r.pwg) plan_launch_lds(ctx, kp.ks.sc, (uint32_t)r.kern.waves, hybrid_stack(integrator));
-    r.lds = r.pwg ? ((size_t)kp.ks.sc.lds_dwords + (size_t)r.pwg_waves * (kp.ks.sc.stack_lds + park_rows) * kBlock) * 4
+    if (mem_plan && !r.pwg) TRC_TRY(plan_launch_lds(ctx, kp.ks.sc, r.kern, hybrid_stack(integrator)));
+    r.lds = r.pwg ? pwg_lds_bytes(kp.ks.sc, r.pwg_waves, park_rows)
                   : dyn_lds_bytes(kp.ks.sc, r.stats) + (r.dense ? (size_t)park_rows * kBlock * 4 : 0u);
+    // wavefront slots of the kernel this launch runs (the split plan's model, trc_debug_launch_shape): k_render_dense's are the workgroups
+    // the runtime says a CU holds of it; the other kernels count the waves they are compiled for, strip and persistent-workgroup
+    // launches the one-wavefront kernel's, as they always have (a strip launch plans nothing; the persistent ones' default is the same).
+    const uint32_t per_cu = r.dense ? dense_per_cu : 4u * (uint32_t)family.one[kVariantPlain].waves;
+    r.wave_slots = (uint32_t)ctx->cu_count * per_cu;
+    trc_ctx::LastFit& fit = ctx->last_fit;
+    fit.fn = r.kern.fn; fit.block = r.pwg ? 64u * r.pwg_waves : kBlock; fit.waves = (uint32_t)r.kern.waves; fit.lds = r.lds;
+    fit.planned_per_cu = r.pwg ? (uint32_t)pwg_per_cu(integrator) : 4u * fit.waves;
+    TRC_TRY(resident_workgroups(ctx, fit.fn, fit.block, fit.lds, &fit.per_cu));
     return TRC_OK;
 }
 

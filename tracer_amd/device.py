@@ -136,6 +136,7 @@ def _load(path, hooks=False):
         L.trc_debug_mesh_light_tables.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(u32)]
         L.trc_mesh_light_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
         L.trc_debug_last_kernel.argtypes = [vp, C.POINTER(abi.KernelChoice)]
+        L.trc_debug_last_residency.argtypes = [vp, C.POINTER(abi.Residency)]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -588,6 +589,14 @@ class Tracer:
         self._check(self._L.trc_debug_last_kernel(self._h, C.byref(k)), "trc_debug_last_kernel")
         return dict(shape=abi.KERNEL_SHAPES[k.shape], variant=abi.KERNEL_VARIANTS[k.variant], lds_resident=bool(k.lds_resident),
                     triangle_materials=bool(k.triangle_materials), strip=int(k.strip), launches=int(k.launches))
+
+    def last_residency(self):
+        """hooks build only: how the kernel of the last launch sits on a CU (trc_debug_last_residency) -> dict of cu_count, block (threads
+        per workgroup), waves (per SIMD, the kernel's launch bounds), planned_per_cu (workgroups per CU the plan is for), planned_with
+        (the runtime's answer the planner used), per_cu (the runtime's answer now) and lds_bytes (dynamic LDS per workgroup)."""
+        r = abi.Residency()
+        self._check(self._L.trc_debug_last_residency(self._h, C.byref(r)), "trc_debug_last_residency")
+        return {name: int(getattr(r, name)) for name, _ in abi.Residency._fields_}
 
     def div_by_test(self, a, b):
         """(fast, plain): 3 quotients per operand pair through the guarded shared-divisor division and through `/`."""
