@@ -9,6 +9,8 @@
 //                          trc_update_vertices: no second upload, the tree is refitted in place; frame k goes to <out>.k.png
 //              [--pose N]  the same turn, sent as ONE matrix per frame (trc_pose_vertices: the device keeps the rest vertices and poses
 //                          them itself, 144 bytes cross the bus instead of the vertex array); frame k goes to <out>.k.png
+//              [--bend N]  N frames of a two-bone bend: the foot of the mesh stands, its top makes --pose's turn, and every vertex blends
+//                          the two by its height (trc_skin_bind once, trc_skin_vertices per frame); frame k goes to <out>.k.png
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -39,7 +41,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    uint32_t spin = 0, pose = 0;
+    uint32_t spin = 0, pose = 0, bend = 0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -64,6 +66,11 @@ int main(int argc, char** argv) {
             const int n = std::atoi(argv[++i]);
             if (n <= 0 || n > 100000) { std::fprintf(stderr, "--pose wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
             pose = (uint32_t)n;
+        }
+        else if (a == "--bend" && i + 1 < argc) {                               // bending geometry: a two-bone palette per frame, trc_skin_vertices
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > 100000) { std::fprintf(stderr, "--bend wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
+            bend = (uint32_t)n;
         }
         else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
@@ -273,6 +280,49 @@ int main(int argc, char** argv) {
         }
     } else if (pose) {
         std::fprintf(stderr, "--pose turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+    }
+    if (bend && scene.n_vertex) {
+        // two bones: bone 0 stays, bone 1 makes --pose's turn, and a vertex follows bone 1 by its height in the mesh's box -- the foot
+        // stands, the top turns, what lies between is twisted.  The influences go up once; a frame sends 256 bytes of palette
+        float lo[3] = {scene.triList[0].v[0], scene.triList[0].v[1], scene.triList[0].v[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+        for (uint32_t i = 0; i < scene.n_vertex; ++i)
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], scene.triList[i].v[k]); hi[k] = std::max(hi[k], scene.triList[i].v[k]); }
+        const float cx = 0.5f * (lo[0] + hi[0]), cz = 0.5f * (lo[2] + hi[2]), height = hi[1] - lo[1];
+        std::vector<trc_skin_influence> influences(scene.n_vertex);
+        for (uint32_t i = 0; i < scene.n_vertex; ++i) {
+            const float up = height > 0.0f ? (scene.triList[i].v[1] - lo[1]) / height : 0.0f;
+            influences[i] = {{0u, 1u, 0u, 0u}, {1.0f - up, up, 0.0f, 0.0f}};
+        }
+        CHECK(trc_skin_bind(ctx, influences.data(), 0, scene.n_vertex));
+        const uint32_t first_frame = spin + pose;      // after --spin's and --pose's frames, when they are given too
+        for (uint32_t f = 1; f <= bend; ++f) {
+            const double a = 6.283185307179586 * f / bend;
+            const float ca = (float)std::cos(a), sa = (float)std::sin(a);
+            trc_skin_bone bones[2];
+            std::memset(bones, 0, sizeof bones);
+            for (int c = 0; c < 4; ++c) (&bones[0].model_matrix.columns[c].x)[c] = 1.0f;
+            bones[0].normal_matrix = bones[0].model_matrix;
+            bones[1].model_matrix.columns[0] = {ca, 0.0f, -sa, 0.0f};
+            bones[1].model_matrix.columns[1] = {0.0f, 1.0f, 0.0f, 0.0f};
+            bones[1].model_matrix.columns[2] = {sa, 0.0f, ca, 0.0f};
+            bones[1].model_matrix.columns[3] = {cx - ca * cx - sa * cz, 0.0f, cz + sa * cx - ca * cz, 1.0f};
+            bones[1].normal_matrix = bones[1].model_matrix;      // a rotation is its own inverse transpose; the translation column is not read
+            const auto u0 = std::chrono::steady_clock::now();
+            CHECK(trc_skin_vertices(ctx, bones, 2));
+            const double skin_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(trc_clear_accum(ctx));
+            CHECK(trc_render(ctx, &prm));
+            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
+            if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+            std::printf("bend %u / %u: trc_skin_vertices %.2f ms -> %s\n", f, bend, skin_ms, name.c_str());
+        }
+    } else if (bend) {
+        std::fprintf(stderr, "--bend bends the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+        trc_destroy(ctx);
+        trc_host_scene_destroy(hs);
+        trc_host_mesh_destroy(mesh);
+        return 1;
     }
     trc_destroy(ctx);
     trc_host_scene_destroy(hs);

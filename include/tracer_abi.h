@@ -54,7 +54,9 @@ extern "C" {
  *    changed)
  * 13: moving geometry: trc_update_vertices, trc_debug_refit_ms, knob refit_single (nothing existing changed)
  *     added under 13, the number stays: trc_pose, trc_pose_vertices, trc_download_vertices, trc_debug_pose_overflows (posing vertex
- *     ranges by matrices on the device; additions only, nothing existing changed) */
+ *     ranges by matrices on the device; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_skin_influence, trc_skin_bone, TRC_SKIN_MAX_BONES, trc_skin_bind, trc_skin_vertices, knob
+ *     skin_no_lds (linear blend skinning on the device; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -622,8 +624,53 @@ trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_pos
  * left.  TRC_ERR_NO_SCENE before any upload; TRC_ERR_INVALID_ARG: first + count > the scene's n_vertex, out == NULL with count > 0, or
  * a scene without triangles.  count == 0 on a scene with triangles is TRC_OK.  Synchronous, like every download. */
 trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count);
-/* the number of posed positions of the last trc_pose_vertices that came out non-finite or beyond 1e37 in magnitude (0 before any) */
+/* the number of posed positions of the last trc_pose_vertices, or of skinned positions of the last trc_skin_vertices -- whichever of the
+ * two calls came last -- that came out non-finite or beyond 1e37 in magnitude (0 before any) */
 trc_status trc_debug_pose_overflows(trc_ctx* ctx, uint32_t* n);
+/* Skinned geometry: linear blend skinning for whatever bends -- characters, cloth proxies.  trc_skin_bind gives a range of vertices
+ * four (bone, weight) influences each, once; trc_skin_vertices takes the frame's bone palette, the device blends the bones' matrices
+ * per vertex, puts the REST vertex under the blend, and the record rewrite and refit of trc_update_vertices run behind.
+ *  - trc_skin_bind: vertex first + i of the scene's triList gets influences[i].  A scene has ONE binding, which is one range: a
+ *    second call replaces it, count == 0 removes it (influences may then be NULL).  Weights need not sum to 1 and may be zero or
+ *    negative: the definition below is what runs.  The table is copied to the device before the call returns: 32 B per bound vertex
+ *    of device memory, freed with the scene (every trc_upload_scene*, trc_destroy).  A bind alone moves no vertex and drops nothing.
+ *    TRC_ERR_NO_SCENE before any upload.  TRC_ERR_INVALID_ARG: influences == NULL with count > 0, first + count > the scene's
+ *    n_vertex, a weight that is not finite, a bone index >= TRC_SKIN_MAX_BONES (whatever its weight), or count > 0 on a scene without
+ *    triangles.  TRC_ERR_OOM if the table cannot be allocated.  On any error the previous binding stays and nothing has changed.
+ *    The binding survives trc_update_vertices, trc_pose_vertices and trc_upload_triangle_materials.
+ *  - trc_skin_vertices: bones[b] is bone b's model_matrix and normal_matrix (the caller's inverse transpose).  Every bound vertex is
+ *    computed from its REST vertex -- the rest copy of trc_pose_vertices: the caller's last values by upload or trc_update_vertices,
+ *    allocated by whichever of the two calls comes first (32 B per vertex), never written by a pose or a skin -- so frame k never
+ *    builds on frame k - 1.  Vertices outside the binding keep their current values; a pose may name bound vertices, the next skin
+ *    overwrites them from rest.
+ *  - Definition, binary32, one rounding per operation, no contraction; (b_k, w_k), k = 0..3, the vertex's influences, M = bones[.].
+ *    For each of the 12 entries e that a pose reads of a model matrix (.x .y .z of columns 0..3):
+ *        B.e = ((w0*M[b0].e + w1*M[b1].e) + w2*M[b2].e) + w3*M[b3].e
+ *    and the same blend of the 9 entries read of the normal matrices (.x .y .z of columns 0..2) gives BN.  Then exactly
+ *    trc_pose_vertices' expressions with B for model_matrix and BN for normal_matrix: x' = ((B.c0.x*x + B.c1.x*y) + B.c2.x*z) + B.c3.x,
+ *    n' = (BN.c0*nx + BN.c1*ny) + BN.c2*nz, not normalised, uv copied.  The .w lanes and column 3 of the normal matrix are not read.
+ *    So a vertex with one weight 1.0f and three weights 0.0f (any valid bone indices) gets, as values, what trc_pose_vertices gives it
+ *    with that bone's two matrices; a -0 may come back as +0.
+ *  - After the call everything observable is what trc_update_vertices would have left had the host computed those vertices and passed
+ *    them, as for a pose: the same things survive, the same are dropped, the block costs are kept, launches kept back for coalescing
+ *    run first, not collective.  The 128 * n_bones bytes are copied out of the caller's array before the call returns; the kernels
+ *    run behind it on the context's stream.  The refit runs over the binding's range.
+ *  - TRC_ERR_NO_SCENE before any upload.  n_bones == 0 is TRC_OK and changes nothing.  Otherwise TRC_ERR_INVALID_ARG: no binding,
+ *    bones == NULL, n_bones > TRC_SKIN_MAX_BONES, n_bones <= the largest bone index of the binding, or a non-finite value among the
+ *    21 entries read of any of the n_bones bones.  TRC_ERR_OOM if the rest copy or the palette buffer cannot be allocated.  On any
+ *    error nothing has changed.  No index on the device comes from anything the host has not checked.
+ *  - Overflow: as for a pose, keeping skinned positions finite and within 1e37 is the CALLER's contract; the kernel counts the ones
+ *    that break it and trc_debug_pose_overflows reports the count.
+ *  - Knob skin_no_lds (trc_debug_set): palettes of up to 256 bones are staged in LDS once per workgroup; 1 = always gather the bones
+ *    from memory, as larger palettes do.  The same arithmetic on the same operands: never a bit of difference.
+ * Out of scope: more than four influences per vertex; dual-quaternion blending; more than one binding per scene (several characters
+ * share one palette through offset bone indices); fusing a pose and a skin of the same frame into one refit chain (they are two calls
+ * and two chains). */
+typedef struct trc_skin_influence { uint32_t bone[4]; float weight[4]; } trc_skin_influence;   /* 32 B */
+typedef struct trc_skin_bone { trc_float4x4 model_matrix, normal_matrix; } trc_skin_bone;      /* 128 B */
+#define TRC_SKIN_MAX_BONES 65536u
+trc_status trc_skin_bind(trc_ctx* ctx, const trc_skin_influence* influences, uint32_t first, uint32_t count);
+trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t n_bones);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -917,7 +964,7 @@ trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table,
  * the render loop shades replayed hits alone where at least n lanes of the wavefront hold one, at most m such trips between two walks; 0 = the
  * defaults, 1 and 1; 65 lanes = never), "strip_force" (tests only: n > 0 gives every wavefront a strip of exactly n blocks, at any spp and whatever
  * the size of the frame -- "strip_len" asks for a length and is capped so that the GPU keeps 1.5 workgroups per wavefront slot, which on a
- * frame of a few blocks always leaves 1).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
+ * frame of a few blocks always leaves 1), "refit_single" (trc_update_vertices), "skin_no_lds" (trc_skin_vertices).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
 
 /* ------------------------------------------------------------------ */
@@ -1131,6 +1178,8 @@ TRC_SA(sizeof(trc_Cube) == 240 && offsetof(trc_Cube, normal_matrix) == 64 && off
        offsetof(trc_Cube, box) == 192 && offsetof(trc_Cube, material) == 224, "Cube");
 TRC_SA(sizeof(trc_TriangleVertex) == 32, "TriangleVertex");
 TRC_SA(sizeof(trc_pose) == 144 && offsetof(trc_pose, model_matrix) == 16 && offsetof(trc_pose, normal_matrix) == 80, "pose");
+TRC_SA(sizeof(trc_skin_influence) == 32 && offsetof(trc_skin_influence, weight) == 16, "skin_influence");
+TRC_SA(sizeof(trc_skin_bone) == 128 && offsetof(trc_skin_bone, normal_matrix) == 64, "skin_bone");
 TRC_SA(sizeof(trc_TextureInfo) == 32 && offsetof(trc_TextureInfo, albedo) == 16, "TextureInfo");
 TRC_SA(sizeof(trc_Material) == 64 && offsetof(trc_Material, medium) == 4 && offsetof(trc_Material, specular) == 8 &&
        offsetof(trc_Material, eta) == 12 && offsetof(trc_Material, roughness) == 16 &&

@@ -10,6 +10,9 @@
 //      status, never crash, over-read or leak
 //   4. the range check of trc_pose_vertices (tracer_amd/csrc/pose_ranges.hpp, host code of the HIP library that includes nothing of
 //      HIP) on hostile tables: first + count wrapping past 2^32, equal ranges, a table of one, non-finite matrix entries
+//   5. the checks of trc_skin_bind and trc_skin_vertices (tracer_amd/csrc/skin_check.hpp, HIP-free like pose_ranges.hpp) on hostile
+//      influence tables and palettes: NULL with a count, a range that wraps, non-finite weights, a bone index at the bound, a palette
+//      one bone too small, NaN in entries that are read and in entries that are not
 // "build host code under -fsanitize=thread,address".
 #include <cmath>
 #include <cstdio>
@@ -23,6 +26,7 @@
 #include "tracer_abi.h"
 #include "../../oracle/oracle.h"
 #include "../../tracer_amd/csrc/pose_ranges.hpp"
+#include "../../tracer_amd/csrc/skin_check.hpp"
 
 static int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "EXPECT failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); ++g_fail; } } while (0)
@@ -181,6 +185,49 @@ static void pose_tables() {
     EXPECT(!ok(many));
 }
 
+// ---------------------------------------------------------------- trc_skin_bind's and trc_skin_vertices' checks
+static trc_skin_bone make_bone() {
+    trc_skin_bone b; std::memset(&b, 0, sizeof b);
+    for (int c = 0; c < 4; ++c) { (&b.model_matrix.columns[c].x)[c] = 1.0f; (&b.normal_matrix.columns[c].x)[c] = 1.0f; }
+    return b;
+}
+static void skin_tables() {
+    const uint32_t n_vertex = 1000;
+    uint32_t max_bone = 77;
+    std::vector<trc_skin_influence> t(10);
+    for (uint32_t i = 0; i < t.size(); ++i) t[i] = {{i, 2u * i, 0u, 3u}, {0.5f, 0.25f, 0.0f, -0.125f}};
+    auto ok = [&](uint32_t first, uint32_t count) { return trc_skin_influence_check(t.data(), first, count, n_vertex, &max_bone) == nullptr; };
+    EXPECT(trc_skin_influence_check(nullptr, 5, 0, n_vertex, &max_bone) == nullptr && max_bone == 0);      // count == 0: NULL is fine
+    max_bone = 77;
+    EXPECT(trc_skin_influence_check(nullptr, 0, 3, n_vertex, &max_bone) != nullptr && max_bone == 77);     // NULL with a count; nothing written
+    EXPECT(ok(0, 10) && max_bone == 18);
+    EXPECT(ok(990, 10) && !ok(991, 10) && !ok(1000, 1) && !ok(1001, 0xFFFFFFFFu));
+    EXPECT(!ok(0xFFFFFFFFu, 2) && !ok(2, 0xFFFFFFFFu) && !ok(0xFFFFFF00u, 0x200u));                        // first + count wraps
+    for (const float bad : {NAN, INFINITY, -INFINITY}) {
+        t[7].weight[3] = bad;
+        EXPECT(!ok(0, 10) && ok(0, 7));
+        t[7].weight[3] = -0.125f;
+    }
+    t[9].bone[2] = TRC_SKIN_MAX_BONES;                                                                     // refused whatever its weight (0)
+    EXPECT(!ok(0, 10) && ok(0, 9));
+    t[9].bone[2] = TRC_SKIN_MAX_BONES - 1;
+    max_bone = 77;
+    EXPECT(ok(0, 10) && max_bone == TRC_SKIN_MAX_BONES - 1);
+    // palettes
+    std::vector<trc_skin_bone> pal(19, make_bone());
+    auto pal_ok = [&](uint32_t n_bones, uint32_t largest) { return trc_skin_palette_check(pal.data(), n_bones, largest) == nullptr; };
+    EXPECT(trc_skin_palette_check(nullptr, 19, 18) != nullptr);
+    EXPECT(pal_ok(19, 18) && !pal_ok(18, 18) && pal_ok(1, 0) && !pal_ok(19, 19));                          // n_bones one too small
+    EXPECT(trc_skin_palette_check(pal.data(), TRC_SKIN_MAX_BONES + 1, 18) != nullptr);                     // refused before a bone is read
+    EXPECT(trc_skin_palette_check(pal.data(), 0xFFFFFFFFu, 18) != nullptr);
+    pal[18].model_matrix.columns[3].y = NAN;
+    EXPECT(!pal_ok(19, 18) && !pal_ok(19, 3));                                                             // a bone that no vertex names counts
+    pal[18] = make_bone(); pal[0].normal_matrix.columns[2].z = INFINITY;
+    EXPECT(!pal_ok(19, 18));
+    pal[0] = make_bone(); pal[5].model_matrix.columns[1].w = NAN; pal[5].normal_matrix.columns[3].x = INFINITY; pal[5].normal_matrix.columns[0].w = NAN;
+    EXPECT(pal_ok(19, 18));                                                                                // lanes that are not read
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -247,6 +294,7 @@ int main(int argc, char** argv) {
     other.join();
     sppm_pass();
     pose_tables();
+    skin_tables();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

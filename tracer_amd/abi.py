@@ -104,6 +104,18 @@ class Pose(C.Structure):         # trc_pose: one vertex range and its two matric
                 ("model_matrix", float4x4), ("normal_matrix", float4x4)]
 
 
+class SkinInfluence(C.Structure):   # trc_skin_influence: the four (bone, weight) pairs of one bound vertex (trc_skin_bind)
+    _fields_ = [("bone", C.c_uint32 * 4), ("weight", C.c_float * 4)]
+
+
+class SkinBone(C.Structure):        # trc_skin_bone: one bone of a palette (trc_skin_vertices)
+    _fields_ = [("model_matrix", float4x4), ("normal_matrix", float4x4)]
+
+
+TRC_SKIN_MAX_BONES = 65536
+SKIN_LDS_BONES = 256                # csrc/skin_check.hpp kSkinLdsBones: palettes up to this size are staged in LDS (tests/test_skin_cpu.py)
+
+
 class TextureInfo(C.Structure):
     _fields_ = [("type", C.c_int32), ("textureIndex", C.c_uint32), ("_pad", C.c_uint32 * 2), ("albedo", float3)]
 
@@ -257,7 +269,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32,
+                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -273,7 +285,7 @@ DEVICE_SYMBOLS = [
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape", "trc_debug_primary_replays",
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
-    "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows",
+    "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",

@@ -470,6 +470,7 @@ static const KnobEntry kKnobs[] = {
     {"replay_chain", &trc_ctx::Knobs::replay_chain, nullptr, false},
     {"mesh_light_pick", &trc_ctx::Knobs::mesh_light_pick, nullptr, false},
     {"refit_single", &trc_ctx::Knobs::refit_single, nullptr, false},
+    {"skin_no_lds", &trc_ctx::Knobs::skin_no_lds, nullptr, false},
     {"strip_force", &trc_ctx::Knobs::strip_force, nullptr, false},
 };
 

@@ -184,6 +184,12 @@ struct trc_ctx {
     uint32_t pose_count_seen = 0;           // the counter word as last read back
     uint32_t pose_overflows = 0;            // of the last trc_pose_vertices (trc_debug_pose_overflows)
     bool refit_posed = false;               // the pending read-back carries the counter word as well
+    // trc_skin_bind / trc_skin_vertices (trc_refit.hip): the binding's influence table (vertex skin_first + i has d_skin_influences[i];
+    // null: no binding), the largest bone index it names, and the palette of the last skin; freed with the scene (trc_refit_free).
+    // A skin reads d_rest and counts its overflows as a pose does
+    trc_skin_influence* d_skin_influences = nullptr;
+    uint32_t skin_first = 0, skin_count = 0, skin_max_bone = 0;
+    trc_skin_bone* d_skin_palette = nullptr; size_t skin_palette_bytes = 0;
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -319,6 +325,7 @@ struct trc_ctx {
         int replay_chain = 0;           // replay trips in a row (0: TRC_REPLAY_CHAIN)
         int mesh_light_pick = 1;        // TRC_FLAG_MESH_LIGHTS: 0 never picks the mesh's light sample (the BSDF-only estimator)
         int refit_single = 0;           // trc_update_vertices: refit in a single launch (trc_refit.hip)
+        int skin_no_lds = 0;            // trc_skin_vertices: the bones gathered from memory whatever the palette's size (trc_refit.hip)
         int strip_force = 0;            // tests: exactly this many blocks per wavefront (launch_geometry)
     } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
@@ -485,7 +492,7 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
     if (!ctx->h_readback) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_readback, kReadbackBytes, hipHostMallocDefault));
     return TRC_OK;
 }
-trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices left for later (ks.root_box, the pose's overflow count)
+trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices left for later (ks.root_box, the overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
 void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays and the refit maps (no-op when absent)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
@@ -508,7 +515,7 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
 //                       A device tree upload that fails after that releases what it allocated of the NEW scene too, before it returns
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
-//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
+//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
 enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:

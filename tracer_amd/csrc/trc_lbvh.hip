@@ -579,10 +579,7 @@ trc_status fit_boxes(TreeBuild& b) {
         for (uint32_t k = 0; k < chunk && pass < pass_limit; ++k)
             hipLaunchKernelGGL(pass_kernel, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, b.height, b.arrived, ++pass);
         TRC_TRY(trc_read_to_host(ctx, b.st, "tree build: refit", {{&b.tree_height, b.arrived, 4}, {&bad_leaves, b.bounds + 6, 4}}));
-        if (bad_leaves & 1u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: input must be leaf records only");      // k_lbvh_prepare, k_sah_init
-        if (bad_leaves & 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "bvh: leaf with bad primitive type/index");
-        if (bad_leaves & 4u) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "bvh: primitive index exceeds 29 bits");
-        if (bad_leaves & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
+        TRC_TRY(intake_status(ctx, bad_leaves));      // k_lbvh_prepare, k_sah_init
     }
     if (!b.tree_height) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
     return TRC_OK;

@@ -20,6 +20,12 @@
 //   k_pose_vertices     ONE launch for all ranges of a call: thread g of the concatenated ranges finds its range in the sorted pose
 //                       table by bisection (the table's _pad[0] is the range's first g), reads the vertex from the rest copy d_rest
 //                       and writes it, posed, to d_verts; two 16 B accesses per vertex each way
+//
+// trc_skin_vertices does the same for vertices that bend: trc_skin_bind has left four (bone, weight) influences per bound vertex on
+// the device, the call brings the frame's bone palette, and in front of the same tail runs one of
+//   k_skin_vertices_lds the palette's read columns staged in LDS once per workgroup, which then takes 256 bound vertices at a time
+//   k_skin_vertices     the columns gathered from memory: palettes beyond kSkinLdsBones (skin_check.hpp), and knob skin_no_lds
+// Both blend the four bones' matrices entry by entry and put the REST vertex under the blend with k_pose_vertices' expressions.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +33,7 @@
 
 #include "dev_trileaf.hpp"
 #include "pose_ranges.hpp"
+#include "skin_check.hpp"
 #include "trc_ctx.hpp"
 
 namespace {
@@ -213,6 +220,86 @@ __global__ void __launch_bounds__(256) k_pose_vertices(const float4* __restrict_
         __hip_atomic_fetch_add(overflows, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the skin: verts[first + i] = blend(influences[i], palette) * rest[first + i] for every bound vertex, in the operation order of
+// include/tracer_abi.h: the four bones' columns blended entry by entry, then k_pose_vertices' expressions with the blend.  Every
+// statement is one operation (the exact build compiles without contraction).  col(b, c): column c of bone b, 0..3 of its model matrix
+// and 4..6 of its normal matrix.  The two kernels differ in where col reads from and in nothing else
+__device__ __forceinline__ float skin_blend(const float4& w, float a0, float a1, float a2, float a3) {
+    const float p0 = w.x * a0;
+    const float p1 = w.y * a1;
+    const float p2 = w.z * a2;
+    const float p3 = w.w * a3;
+    const float s01 = p0 + p1;
+    const float s012 = s01 + p2;
+    return s012 + p3;
+}
+template <class Col>
+__device__ __forceinline__ void skin_vertex(const float4* __restrict__ rest, float4* __restrict__ verts, uint32_t v, const uint4& bone, const float4& w,
+                                            const Col& col, uint32_t* __restrict__ overflows) {
+    float4 m[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) {
+        const float4 m0 = col(bone.x, c), m1 = col(bone.y, c), m2 = col(bone.z, c), m3 = col(bone.w, c);
+        m[c].x = skin_blend(w, m0.x, m1.x, m2.x, m3.x);
+        m[c].y = skin_blend(w, m0.y, m1.y, m2.y, m3.y);
+        m[c].z = skin_blend(w, m0.z, m1.z, m2.z, m3.z);
+        m[c].w = 0.0f;
+    }
+    const float4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3], n0 = m[4], n1 = m[5], n2 = m[6];
+    const float4 a = rest[2 * (size_t)v], b = rest[2 * (size_t)v + 1];              // x y z nx | ny nz u v
+    const float x = ((c0.x * a.x + c1.x * a.y) + c2.x * a.z) + c3.x;
+    const float y = ((c0.y * a.x + c1.y * a.y) + c2.y * a.z) + c3.y;
+    const float z = ((c0.z * a.x + c1.z * a.y) + c2.z * a.z) + c3.z;
+    const float nx = (n0.x * a.w + n1.x * b.x) + n2.x * b.y;
+    const float ny = (n0.y * a.w + n1.y * b.x) + n2.y * b.y;
+    const float nz = (n0.z * a.w + n1.z * b.x) + n2.z * b.y;
+    verts[2 * (size_t)v] = make_float4(x, y, z, nx);
+    verts[2 * (size_t)v + 1] = make_float4(ny, nz, b.z, b.w);
+    if (!(fabsf(x) <= 1e37f) || !(fabsf(y) <= 1e37f) || !(fabsf(z) <= 1e37f))      // the caller's contract, broken: counted, never an index
+        __hip_atomic_fetch_add(overflows, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+struct KSkin {
+    const float4* rest; float4* verts; uint32_t n_vertex;
+    const uint4* influences; uint32_t first, count;     // influences: 2 x 16 B per bound vertex, the bones and then the weights
+    const float4* palette; uint32_t n_bones;            // 8 columns per bone (trc_skin_bone)
+    uint32_t* overflows;
+};
+// bound vertex i of the binding (the host refused a table or a palette that these tests would catch)
+template <class Col>
+__device__ __forceinline__ void skin_bound_vertex(const KSkin& p, uint32_t i, uint32_t n_bones, const Col& col) {
+    const uint32_t v = p.first + i;
+    if (v >= p.n_vertex) return;
+    const uint4 bone = p.influences[2 * (size_t)i];
+    const uint4 wb = p.influences[2 * (size_t)i + 1];
+    if (bone.x >= n_bones || bone.y >= n_bones || bone.z >= n_bones || bone.w >= n_bones) return;
+    const float4 w = make_float4(__uint_as_float(wb.x), __uint_as_float(wb.y), __uint_as_float(wb.z), __uint_as_float(wb.w));
+    skin_vertex(p.rest, p.verts, v, bone, w, col, p.overflows);
+}
+// gathered: one thread per bound vertex, the columns straight from the palette in memory (a palette is small: L2-resident)
+__global__ void __launch_bounds__(256) k_skin_vertices(KSkin p) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.count) return;
+    const float4* palette = p.palette;
+    skin_bound_vertex(p, i, p.n_bones, [palette](uint32_t b, int c) { return palette[8 * (size_t)b + c]; });
+}
+// staged: the read columns of every bone (112 of its 128 bytes) once per WORKGROUP into LDS, then the workgroup's threads take batches
+// of 256 bound vertices until none is left, so a palette is loaded gridDim.x times and not count / 256 times.  n_bones <= kSkinLdsBones
+__global__ void __launch_bounds__(256) k_skin_vertices_lds(KSkin p) {
+    __shared__ float4 cols[7 * kSkinLdsBones];
+    const uint32_t n_bones = p.n_bones < kSkinLdsBones ? p.n_bones : kSkinLdsBones;
+    for (uint32_t k = threadIdx.x; k < 7u * n_bones; k += 256u) {
+        const uint32_t b = k / 7u;
+        cols[k] = p.palette[8 * (size_t)b + (k - 7u * b)];
+    }
+    __syncthreads();
+    const float4* staged = cols;
+    for (size_t base = (size_t)blockIdx.x * 256u; base < p.count; base += (size_t)gridDim.x * 256u) {      // (64 bits: base + the stride may pass 2^32)
+        const size_t i = base + threadIdx.x;
+        if (i < p.count) skin_bound_vertex(p, (uint32_t)i, n_bones, [staged](uint32_t b, int c) { return staged[7u * b + c]; });
+    }
+}
+constexpr uint32_t kSkinWorkgroupsPerCu = 2;     // of the staged kernel: 512 threads of a CU's 2048, each workgroup ~4 batches on 0.5 M vertices
+
 // the maps themselves (refit_prepare frees what a failure leaves half made)
 trc_status refit_make_maps(trc_ctx* ctx) {
     const DScene& sc = ctx->ks.sc;
@@ -281,11 +368,23 @@ trc_status refit_begin(trc_ctx* ctx, const char* who) {
     return TRC_OK;
 }
 
+// The rest copy, made by the first pose or skin of a scene: neither has written d_verts yet, so they are the caller's values
+trc_status rest_ensure(trc_ctx* ctx, const char* what) {
+    if (ctx->d_rest) return TRC_OK;
+    const size_t bytes = (size_t)ctx->n_vertex * sizeof(trc_TriangleVertex);
+    DevBuf rest;
+    TRC_TRY(rest.alloc(ctx, bytes, what));
+    HIP_TRY(ctx, hipMemcpyAsync(rest.p, ctx->d_verts, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->d_rest = static_cast<trc_TriangleVertex*>(rest.release());
+    return TRC_OK;
+}
+
 // ... and behind their vertices, on the context's stream: [the pose kernel,] the records of the triangles that name a vertex of
 // [first, first + count), every box of the tree, the root box on its way back.  pose_total != 0: trc_pose_vertices, whose sorted
 // table of n_poses ranges (pose_total vertices in all) is in d_pose_table; [first, first + count) is then the hull of its ranges --
-// a triangle of the hull that no range touched gets the bits it had, and keeps its material
-trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_poses = 0, uint32_t pose_total = 0) {
+// a triangle of the hull that no range touched gets the bits it had, and keeps its material.  skin_bones != 0: trc_skin_vertices, whose
+// palette of skin_bones bones is in d_skin_palette; [first, first + count) is then the binding's range
+trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_poses = 0, uint32_t pose_total = 0, uint32_t skin_bones = 0) {
     const DScene& sc = ctx->ks.sc;
     hipEvent_t e0 = ctx->refit_ev[0], e1 = ctx->refit_ev[1];
     hipStream_t st = ctx->stream;
@@ -300,6 +399,19 @@ trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_po
         hipLaunchKernelGGL(k_pose_vertices, dim3((pose_total + 255) / 256), b256, 0, st, reinterpret_cast<const float4*>(ctx->d_rest),
                            reinterpret_cast<float4*>(ctx->d_verts), ctx->n_vertex, ctx->d_pose_table, n_poses, pose_total,
                            reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord);
+    if (skin_bones) {
+        KSkin k{};
+        k.rest = reinterpret_cast<const float4*>(ctx->d_rest); k.verts = reinterpret_cast<float4*>(ctx->d_verts); k.n_vertex = ctx->n_vertex;
+        k.influences = reinterpret_cast<const uint4*>(ctx->d_skin_influences); k.first = first; k.count = count;
+        k.palette = reinterpret_cast<const float4*>(ctx->d_skin_palette); k.n_bones = skin_bones;
+        k.overflows = reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord;
+        const uint32_t batches = (uint32_t)(((size_t)count + 255) / 256);
+        if (skin_bones <= kSkinLdsBones && !ctx->knobs.skin_no_lds)
+            hipLaunchKernelGGL(k_skin_vertices_lds, dim3(std::min(batches, kSkinWorkgroupsPerCu * (uint32_t)ctx->cu_count)), b256, 0, st, k);
+        else
+            hipLaunchKernelGGL(k_skin_vertices, dim3(batches), b256, 0, st, k);
+    }
+    const bool counted = pose_total != 0 || skin_bones != 0;
     hipLaunchKernelGGL(k_refit_triangles, dim3((sc.n_triangles + 255) / 256), b256, 0, st, ctx->d_verts, ctx->d_idx, sc.n_triangles, first, count,
                        reinterpret_cast<float4*>(ctx->d_blob + sc.off_tripos), reinterpret_cast<float4*>(ctx->d_blob + sc.off_triattr));
     if (ctx->knobs.refit_single) {
@@ -313,11 +425,11 @@ trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_po
     HIP_TRY(ctx, hipEventRecord(e1, st));
     // the root box is a kernel PARAMETER of every launch (KScene): it is copied back behind the refit and read by the next entry
     // point that is entered (trc_refit_settle, at the top of trc_flush and render_pass), so this call does not wait for the device.
-    // A pose's overflow count travels with it
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_readback, ctx->d_refit_root, (pose_total ? kPoseCountWord + 1 : 6) * sizeof(float), hipMemcpyDeviceToHost, st));
+    // A pose's or a skin's overflow count travels with it
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_readback, ctx->d_refit_root, (counted ? kPoseCountWord + 1 : 6) * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipEventRecord(ctx->refit_ev[2], st));
     ctx->refit_pending = true;
-    ctx->refit_posed = pose_total != 0;
+    ctx->refit_posed = counted;
     // the picture changed a little, as under a camera that moves a little (trc_set_camera): the recorded block costs stay, and the
     // next ordered launch is one pass on the last launch's raw durations
     if (ctx->cost_valid) { ctx->plan_streak = 0; ctx->cost_fresh_next = true; }
@@ -348,6 +460,9 @@ void trc_refit_free(trc_ctx* ctx) {
     (void)hipFree(ctx->d_rest); (void)hipFree(ctx->d_pose_table);
     ctx->d_rest = nullptr; ctx->d_pose_table = nullptr; ctx->pose_table_bytes = 0;
     ctx->pose_count_seen = ctx->pose_overflows = 0;
+    (void)hipFree(ctx->d_skin_influences); (void)hipFree(ctx->d_skin_palette);
+    ctx->d_skin_influences = nullptr; ctx->d_skin_palette = nullptr; ctx->skin_palette_bytes = 0;
+    ctx->skin_first = ctx->skin_count = ctx->skin_max_bone = 0;
     (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
     ctx->d_verts = nullptr; ctx->d_idx = nullptr; ctx->n_vertex = 0;
     ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
@@ -399,16 +514,47 @@ trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_pos
     TRC_TRY(refit_begin(ctx, "trc_pose_vertices"));
     TRC_TRY(trc_grow_buffer(ctx, ctx->d_pose_table, ctx->pose_table_bytes, table.size() * sizeof(trc_pose), "trc_pose_vertices: hipMalloc pose table"));
     hipStream_t st = ctx->stream;
-    if (!ctx->d_rest) {      // the first pose of this scene: no pose has written d_verts yet, so they are the caller's values
-        const size_t bytes = (size_t)ctx->n_vertex * sizeof(trc_TriangleVertex);
-        DevBuf rest;
-        TRC_TRY(rest.alloc(ctx, bytes, "rest vertices (trc_pose_vertices)"));
-        HIP_TRY(ctx, hipMemcpyAsync(rest.p, ctx->d_verts, bytes, hipMemcpyDeviceToDevice, st));
-        ctx->d_rest = static_cast<trc_TriangleVertex*>(rest.release());
-    }
+    TRC_TRY(rest_ensure(ctx, "rest vertices (trc_pose_vertices)"));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_pose_table, table.data(), table.size() * sizeof(trc_pose), st));
     trc_scene_changed(ctx, kSceneVerticesMoved);
     return refit_run(ctx, hull_first, hull_count, n_poses, total);
+}
+
+trc_status trc_skin_bind(trc_ctx* ctx, const trc_skin_influence* influences, uint32_t first, uint32_t count) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_skin_bind: no scene");
+    if (count != 0 && (ctx->ks.sc.n_triangles == 0 || !ctx->d_verts)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_skin_bind: the scene has no triangles");
+    uint32_t max_bone = 0;
+    if (const char* why = trc_skin_influence_check(influences, first, count, ctx->n_vertex, &max_bone)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_skin_bind: ") + why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf table;
+    if (count != 0) {
+        TRC_TRY(table.alloc(ctx, (size_t)count * sizeof(trc_skin_influence), "influence table (trc_skin_bind)"));
+        TRC_TRY(trc_copy_to_device(ctx, table.p, influences, (size_t)count * sizeof(trc_skin_influence), st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));      // a skin still in flight reads the table that goes
+    (void)hipFree(ctx->d_skin_influences);
+    ctx->d_skin_influences = static_cast<trc_skin_influence*>(table.release());
+    ctx->skin_first = count ? first : 0u; ctx->skin_count = count; ctx->skin_max_bone = max_bone;
+    return TRC_OK;
+}
+
+trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t n_bones) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_skin_vertices: no scene");
+    if (n_bones == 0) return TRC_OK;
+    if (!ctx->d_skin_influences || !ctx->d_verts) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_skin_vertices: no binding (trc_skin_bind)");
+    if (const char* why = trc_skin_palette_check(bones, n_bones, ctx->skin_max_bone)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_skin_vertices: ") + why);
+    TRC_TRY(refit_begin(ctx, "trc_skin_vertices"));
+    const size_t bytes = (size_t)n_bones * sizeof(trc_skin_bone);
+    TRC_TRY(trc_grow_buffer(ctx, ctx->d_skin_palette, ctx->skin_palette_bytes, bytes, "trc_skin_vertices: hipMalloc bone palette"));
+    TRC_TRY(rest_ensure(ctx, "rest vertices (trc_skin_vertices)"));
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_skin_palette, bones, bytes, ctx->stream));
+    trc_scene_changed(ctx, kSceneVerticesMoved);
+    return refit_run(ctx, ctx->skin_first, ctx->skin_count, 0, 0, n_bones);
 }
 
 trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count) {

@@ -565,6 +565,15 @@ __global__ void __launch_bounds__(64) k_sah_finish(const DLeaf* elems, const SFi
     if (lane < S) vals[F + lane] = s_leaf[s_ord[lane]];
 }
 
+// what the intake flags (k_lbvh_prepare, k_sah_init) say is wrong with the leaf records; TRC_OK for none
+static trc_status intake_status(trc_ctx* ctx, uint32_t bad_leaves) {
+    if (bad_leaves & 1u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: input must be leaf records only");
+    if (bad_leaves & 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "bvh: leaf with bad primitive type/index");
+    if (bad_leaves & 4u) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "bvh: primitive index exceeds 29 bits");
+    if (bad_leaves & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
+    return TRC_OK;
+}
+
 // Topology (t.tp) and leaf order (t.vals[0][position] = leaf index) of the SAH tree over t.leaves; the builder knows the tree's height,
 // which is the number of refit passes before fit_boxes first looks at the root (t.first_chunk).  The sibling of lbvh_topology.
 static trc_status sah_build_topology(TreeBuild& t) {
@@ -598,7 +607,6 @@ static trc_status sah_build_topology(TreeBuild& t) {
         hipLaunchKernelGGL(k_sah_init, g_leaf, b256, 0, st, t.leaves, n, b.elems, t.bounds + 6, b.nodes[0]);
     }
     int cur = 0;
-    bool broken = false;
     static_assert(sizeof(uint32_t) * (2u + 2u * (TRC_MAX_BVH_DEPTH + 3u) + 1u) <= kReadbackBytes, "h_readback holds the counter block and the intake flags");
     TRC_TRY(trc_readback_alloc(ctx));
     uint32_t* const h_readback = ctx->h_readback;      // pinned: the copy is queued behind k_sah_split and the host goes on launching
@@ -617,14 +625,15 @@ static trc_status sah_build_topology(TreeBuild& t) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
         const uint32_t bad = h_readback[n_counters];
         if (bad & 8u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: leaf box not finite or beyond 1e37");
-        if (bad) { n_rows = 0; broken = true; break; }     // the other intake errors are reported by the caller's refit
+        // the other intake errors end the build here as well: the levels below this one are not built, and a refit pass over them
+        // (fit_boxes) would follow child links that nothing has written
+        if (bad) return intake_status(ctx, bad);
         if (h_readback[1] & 16u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: one-sided partition on a positive extent");
         const uint32_t next[2] = {h_readback[2u + 2u * (level + 1u)], h_readback[3u + 2u * (level + 1u)]};
         n_rows = next[0]; n_tasks = next[1];
         if (n_rows > max_rows || n_tasks > max_tasks) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: level table overflow");
     }
     hipLaunchKernelGGL(k_sah_vals, g_leaf, b256, 0, st, b.elems, n, t.vals[0]);
-    if (broken) return TRC_OK;
     const uint32_t n_finish = n <= kFinishSpan ? 1u : h_readback[0];       // every level's read-back came after its k_sah_split
     if (n_finish > n / 2u + 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: finish list overflow");
     if (n_finish) hipLaunchKernelGGL(k_sah_finish, dim3(n_finish), dim3(64), 0, st, b.elems, b.finish, t.vals[0], b.counters, t.tp, n);

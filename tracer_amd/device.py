@@ -124,6 +124,8 @@ def _load(path, hooks=False):
     L.trc_pose_vertices.argtypes = [vp, C.POINTER(abi.Pose), u32]
     L.trc_download_vertices.argtypes = [vp, vp, u32, u32]
     L.trc_debug_pose_overflows.argtypes = [vp, C.POINTER(u32)]
+    L.trc_skin_bind.argtypes = [vp, vp, u32, u32]
+    L.trc_skin_vertices.argtypes = [vp, C.POINTER(abi.SkinBone), u32]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -163,6 +165,13 @@ def make_poses(poses):
             for c in range(4):
                 cols[c].x, cols[c].y, cols[c].z, cols[c].w = (float(m[r, c]) for r in range(4))
     return arr
+
+
+def make_bones(palette):
+    """ctypes array of abi.SkinBone from a sequence of (model, normal); the matrices are (4, 4), m[r][c] row r column c, as make_poses takes"""
+    m = np.asarray(palette, dtype=np.float32).reshape(-1, 2, 4, 4)
+    cols = np.ascontiguousarray(m.transpose(0, 1, 3, 2))      # stored column-major: [bone, matrix, column, row]
+    return (abi.SkinBone * len(cols)).from_buffer_copy(cols.tobytes())
 
 
 def group_unique_id():
@@ -268,14 +277,35 @@ class Tracer:
         self._check(self._L.trc_download_vertices(self._h, buf.ctypes.data, first, count), "trc_download_vertices")
         return out
 
+    def skin_bind(self, bones, weights, first=0):
+        """trc_skin_bind: vertex first + i gets the four influences (bones[i, k], weights[i, k]); `bones` is (n, 4) integers, `weights`
+        (n, 4) float32.  One binding per scene: a second call replaces it, an empty array removes it.  Moves no vertex."""
+        b = np.asarray(bones, dtype=np.int64).reshape(-1, 4)
+        w = np.asarray(weights, dtype=np.float32).reshape(-1, 4)
+        if len(b) != len(w):
+            raise ValueError(f"skin_bind: {len(b)} rows of bones, {len(w)} rows of weights")
+        table = np.empty((len(b), 8), dtype=np.uint32)            # abi.SkinInfluence rows
+        table[:, :4] = np.where((b < 0) | (b > 0xFFFFFFFF), 0xFFFFFFFF, b)      # what no uint32 holds is refused by the library
+        table[:, 4:] = w.view(np.uint32)
+        self._check(self._L.trc_skin_bind(self._h, table.ctypes.data if len(table) else None, first, len(table)), "trc_skin_bind")
+
+    def skin_vertices(self, palette):
+        """trc_skin_vertices: `palette` is a ctypes array of abi.SkinBone, or a sequence of (model, normal) with the matrices as (4, 4)
+        arrays in the layout make_poses takes.  Every bound vertex (skin_bind) is computed from the scene's REST vertices on the
+        device under the blend of its four bones, and the tree is refitted in place.  The accumulator is not cleared."""
+        if not (isinstance(palette, C.Array) and palette._type_ is abi.SkinBone):
+            palette = make_bones(palette)
+        self._check(self._L.trc_skin_vertices(self._h, palette if len(palette) else None, len(palette)), "trc_skin_vertices")
+
     def pose_overflows(self):
-        """posed positions of the last pose_vertices that came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
+        """posed positions of the last pose_vertices, or skinned positions of the last skin_vertices (whichever call came last), that
+        came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
         n = C.c_uint32(0)
         self._check(self._L.trc_debug_pose_overflows(self._h, C.byref(n)), "trc_debug_pose_overflows")
         return n.value
 
     def refit_ms(self):
-        """device time in ms of the kernels of the last update_vertices or pose_vertices (trc_debug_refit_ms)"""
+        """device time in ms of the kernels of the last update_vertices, pose_vertices or skin_vertices (trc_debug_refit_ms)"""
         ms = C.c_float(0)
         self._check(self._L.trc_debug_refit_ms(self._h, C.byref(ms)), "trc_debug_refit_ms")
         return ms.value
