@@ -11,6 +11,9 @@
 //                          them itself, 144 bytes cross the bus instead of the vertex array); frame k goes to <out>.k.png
 //              [--bend N]  N frames of a two-bone bend: the foot of the mesh stands, its top makes --pose's turn, and every vertex blends
 //                          the two by its height (trc_skin_bind once, trc_skin_vertices per frame); frame k goes to <out>.k.png
+//              [--rebuild-ratio R]  beside --spin / --pose / --bend: after every animation call the tree's cost is read (trc_tree_cost), and
+//                          when (interior + leaf) / root exceeds R times what it was right after the last build, the tree is built anew on the
+//                          device (trc_rebuild_tree, TRC_TREE_SAH); the number of rebuilds is printed at the end
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -42,6 +45,7 @@ int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0;
+    double rebuild_ratio = 0.0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -71,6 +75,10 @@ int main(int argc, char** argv) {
             const int n = std::atoi(argv[++i]);
             if (n <= 0 || n > 100000) { std::fprintf(stderr, "--bend wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
             bend = (uint32_t)n;
+        }
+        else if (a == "--rebuild-ratio" && i + 1 < argc) {                      // a fresh tree when the refitted one has worn: trc_tree_cost, trc_rebuild_tree
+            rebuild_ratio = std::atof(argv[++i]);
+            if (!(rebuild_ratio >= 1.0)) { std::fprintf(stderr, "--rebuild-ratio wants a factor of at least 1, not %s\n", argv[i]); return 2; }
         }
         else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
@@ -220,6 +228,33 @@ int main(int argc, char** argv) {
     std::printf("%s %ux%u %u spp %s: %llu rays, kernel %.2f ms (wall %.2f ms), %.1f Mrays/s, exposure %.4f -> %s\n",
                 scene_name.c_str(), W, H, spp, integ_name.c_str(), (unsigned long long)st.rays, st.kernel_ms, wall_ms,
                 st.rays / st.kernel_ms / 1e3, exposure, out.c_str());
+    // --rebuild-ratio: the cost right after the last build is the yardstick; called after every animation call
+    uint32_t rebuilds = 0, cost_reads = 0;
+    double built_cost = 0.0;
+    auto tree_ratio = [&](double* ratio) {
+        trc_tree_cost_t c;
+        const trc_status cs = trc_tree_cost(ctx, &c);
+        if (cs == TRC_OK) *ratio = c.root_half_area > 0.0 ? (c.interior_half_area + c.leaf_half_area) / c.root_half_area : 0.0;
+        return cs;
+    };
+    auto rebuild_if_worn = [&]() {
+        if (rebuild_ratio == 0.0) return TRC_OK;
+        double now = 0.0;
+        trc_status rs = tree_ratio(&now);
+        if (rs != TRC_OK) return rs;
+        ++cost_reads;
+        if (now <= rebuild_ratio * built_cost) return TRC_OK;
+        const auto r0 = std::chrono::steady_clock::now();
+        if ((rs = trc_rebuild_tree(ctx, TRC_TREE_SAH)) != TRC_OK) return rs;
+        const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
+        const double worn = now;
+        if ((rs = tree_ratio(&now)) != TRC_OK) return rs;
+        std::printf("tree cost %.3f > %.2f x %.3f: trc_rebuild_tree %.2f ms -> cost %.3f\n", worn, rebuild_ratio, built_cost, rebuild_ms, now);
+        built_cost = now;
+        ++rebuilds;
+        return TRC_OK;
+    };
+    if (rebuild_ratio != 0.0) CHECK(tree_ratio(&built_cost));
     if (spin && scene.n_vertex) {
         // the mesh's world-space vertices, turned about the vertical axis through the centre of their box; normals alike
         const std::vector<trc_TriangleVertex> rest(scene.triList, scene.triList + scene.n_vertex);
@@ -239,6 +274,7 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_update_vertices(ctx, turned.data(), 0, scene.n_vertex));
             const double update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
@@ -271,6 +307,7 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_pose_vertices(ctx, &p, 1));
             const double pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
@@ -310,6 +347,7 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_skin_vertices(ctx, bones, 2));
             const double skin_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
@@ -324,6 +362,7 @@ int main(int argc, char** argv) {
         trc_host_mesh_destroy(mesh);
         return 1;
     }
+    if (rebuild_ratio != 0.0) std::printf("rebuild-ratio %.2f: %u rebuilds after %u animation calls\n", rebuild_ratio, rebuilds, cost_reads);
     trc_destroy(ctx);
     trc_host_scene_destroy(hs);
     trc_host_mesh_destroy(mesh);

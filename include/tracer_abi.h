@@ -56,7 +56,9 @@ extern "C" {
  *     added under 13, the number stays: trc_pose, trc_pose_vertices, trc_download_vertices, trc_debug_pose_overflows (posing vertex
  *     ranges by matrices on the device; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_skin_influence, trc_skin_bone, TRC_SKIN_MAX_BONES, trc_skin_bind, trc_skin_vertices, knob
- *     skin_no_lds (linear blend skinning on the device; additions only, nothing existing changed) */
+ *     skin_no_lds (linear blend skinning on the device; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_rebuild_tree, trc_tree_cost_t, trc_tree_cost (a fresh tree for a moved mesh from what the
+ *     device holds, and a surface-area measure that tells a host when to ask for one; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -572,7 +574,7 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
  *    and the next entry point that is entered waits for them.  The first update of a scene also waits once for its maps.)
  *  - In a group every rank calls it for itself; it is not collective.
  *  - It repairs nothing: after a large deformation the tree is valid but slow to walk, and a host that wants a fresh one calls
- *    trc_upload_scene_device.  Only the triangles that name a changed vertex get their records rewritten; every box of the tree is
+ *    trc_rebuild_tree (trc_tree_cost tells it when).  Only the triangles that name a changed vertex get their records rewritten; every box of the tree is
  *    recomputed.
  * The scene's vertex and index arrays stay on the device for this call (32 B per vertex + 12 B per triangle beside the blob),
  * freed by the next trc_upload_scene* and by trc_destroy.
@@ -671,6 +673,57 @@ typedef struct trc_skin_bone { trc_float4x4 model_matrix, normal_matrix; } trc_s
 #define TRC_SKIN_MAX_BONES 65536u
 trc_status trc_skin_bind(trc_ctx* ctx, const trc_skin_influence* influences, uint32_t first, uint32_t count);
 trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t n_bones);
+/* A fresh tree for a moved mesh.  A refit keeps the topology of the tree it found: after objects have travelled past each other the boxes
+ * near the top overlap and every ray walks more of them.  trc_rebuild_tree builds the tree anew from what the DEVICE holds -- no vertex,
+ * index or record crosses the bus, nothing but the tree changes -- and trc_tree_cost (below) tells a host when to ask for it.
+ *  - The tree afterwards is the tree trc_upload_scene_sah builds from the scene's current LEAF RECORDS when flags == TRC_TREE_SAH, and
+ *    the tree trc_upload_scene_lbvh builds from them when flags == 0: record for record in trc_download_bvh, fat node for fat node on
+ *    the device, with the LDS plan of that upload.  The vertices, the triangle records and the primitives are those it found: no vertex
+ *    moves.
+ *  - Leaf records of a device-built tree (trc_upload_scene_lbvh / _sah / _device): slots 1..n of trc_download_bvh, in the order of the
+ *    upload, with the boxes the last upload or refit left them.  So after any update, pose or skin a TRC_TREE_SAH rebuild of a
+ *    TRC_TREE_TRIANGLE_LEAVES scene equals a fresh context's trc_upload_scene_device(TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES) of the same
+ *    analytic leaves and the vertices of trc_download_vertices.
+ *  - Leaf records of a caller's tree (trc_upload_scene): the caller's bvhList is gone, so the leaf list has a canonical order -- by pType
+ *    ascending, then by pIndex (the order of first[pType] + pIndex, first[] the prefix sums of the scene's sphere, square, cube and
+ *    triangle counts).  A leaf's box is the one its child slot holds on the device (the caller's, or the last refit's), padding lanes
+ *    0; parent, left, right and axis are 0.  A primitive that the caller's tree leaves out (the Cornell scenes list spheres that no
+ *    leaf names) has no leaf afterwards either.  A tree that names one primitive in two leaves has no such list:
+ *    TRC_ERR_UNSUPPORTED, nothing changes.  Afterwards the scene is a device-built one: trc_download_bvh and trc_lbvh_info work on it.
+ *  - What survives: the kept vertex and index arrays, the rest copy of trc_pose_vertices / trc_skin_vertices and the skin binding; the
+ *    triangle records with their per-triangle materials; textures, the environment, the camera, the density grid, the accumulator and the
+ *    RNG texture (the caller clears).  The launch planner's block costs are KEPT as after trc_update_vertices: scheduling only.
+ *  - What is dropped: the G-buffer and the denoiser history (a tie in t may now resolve to another primitive); the tables of
+ *    TRC_FLAG_MESH_LIGHTS (rebuilt at the next flagged render); the maps of the refit, which the next trc_update_vertices,
+ *    trc_pose_vertices or trc_skin_vertices makes again for the new topology, as the first update of a scene does.  trc_sppm_frames sees
+ *    the new tree at its next call.
+ *  - The leaf count does not change, so neither does the layout of the device's scene: the node region and the tree records are
+ *    rewritten in place, only temporaries are allocated, and nothing larger than the build's small read-backs is transferred.
+ *  - Atomic on error.  TRC_ERR_INVALID_ARG: a flag other than TRC_TREE_SAH (TRC_TREE_TRIANGLE_LEAVES included: the leaves are the
+ *    device's).  TRC_ERR_NO_SCENE before any upload.  TRC_ERR_UNSUPPORTED: see above.  TRC_ERR_BVH_INVALID: a tree deeper than
+ *    TRC_MAX_BVH_DEPTH, or a leaf box the SAH build does not take.  TRC_ERR_OOM: the temporaries.  All of them are found before the
+ *    first byte of the old tree is overwritten: a render after a refused call gives the frame it would have given before it.
+ *  - Launches kept back for coalescing run first.  Not collective.  The call waits where an upload waits -- the read-backs of the build
+ *    -- and returns with the tree in place.  trc_lbvh_info reports the rebuild's height and device time. */
+trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags);       /* flags: 0 (LBVH + rotations) or TRC_TREE_SAH */
+/* A surface-area measure of the tree as it stands, on any upload path (it reads the device's nodes): one kernel pass over 64 bytes per
+ * interior node on the context's stream; synchronous like a download.  Launches kept back for coalescing run first.
+ *  - For a box, d = max - min per axis in binary32, and a d that is not > 0 counts as 0; its half area is
+ *    h = ((double)dx * dy + (double)dy * dz) + (double)dz * dx.  A product of two binary32 values is exact in binary64, so contraction
+ *    cannot change a bit of h.
+ *  - root_half_area is h of the root's box.  A tree of n leaves has n - 1 interior nodes with two child slots each: interior_half_area is
+ *    the sum of h over the n - 2 slots that hold an interior child, leaf_half_area over the n slots that hold a leaf; n_interior and
+ *    n_leaves count those slots (exact).  The sums are binary64 additions in the order the reduction takes: any order of n non-negative
+ *    terms is within (n - 1) * 2^-53 relative of the exact sum.  Defined for boxes within the 1e37 bound of the device builds.
+ *  - The expected cost of a ray through the tree, up to the host's own constants: (Ct * interior_half_area + Ci * leaf_half_area) /
+ *    root_half_area with Ct the price of a box step and Ci that of a leaf test.  A refit changes it, a rebuild resets it: a host compares
+ *    the value with the one right after its last build (examples/trc_render --rebuild-ratio).
+ *  - TRC_ERR_NO_SCENE before any upload; TRC_ERR_INVALID_ARG: out == NULL. */
+typedef struct trc_tree_cost_t {
+    double   root_half_area, interior_half_area, leaf_half_area;
+    uint32_t n_interior, n_leaves;
+} trc_tree_cost_t;
+trc_status trc_tree_cost(trc_ctx* ctx, trc_tree_cost_t* out);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -1180,6 +1233,7 @@ TRC_SA(sizeof(trc_TriangleVertex) == 32, "TriangleVertex");
 TRC_SA(sizeof(trc_pose) == 144 && offsetof(trc_pose, model_matrix) == 16 && offsetof(trc_pose, normal_matrix) == 80, "pose");
 TRC_SA(sizeof(trc_skin_influence) == 32 && offsetof(trc_skin_influence, weight) == 16, "skin_influence");
 TRC_SA(sizeof(trc_skin_bone) == 128 && offsetof(trc_skin_bone, normal_matrix) == 64, "skin_bone");
+TRC_SA(sizeof(trc_tree_cost_t) == 32 && offsetof(trc_tree_cost_t, n_interior) == 24, "tree_cost");
 TRC_SA(sizeof(trc_TextureInfo) == 32 && offsetof(trc_TextureInfo, albedo) == 16, "TextureInfo");
 TRC_SA(sizeof(trc_Material) == 64 && offsetof(trc_Material, medium) == 4 && offsetof(trc_Material, specular) == 8 &&
        offsetof(trc_Material, eta) == 12 && offsetof(trc_Material, roughness) == 16 &&

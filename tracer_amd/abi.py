@@ -233,6 +233,12 @@ DENOISE_ALBEDO_EPS = 0.001
 DENOISE_MAX_ITERATIONS = 5
 
 
+class TreeCost(C.Structure):
+    """trc_tree_cost_t: half areas of the root, of the child slots that hold an interior node and of those that hold a leaf"""
+    _fields_ = [("root_half_area", C.c_double), ("interior_half_area", C.c_double), ("leaf_half_area", C.c_double),
+                ("n_interior", C.c_uint32), ("n_leaves", C.c_uint32)]
+
+
 class KernelChoice(C.Structure):
     """trc_kernel_choice (tracer_test_hooks.h)"""
     _fields_ = [("shape", C.c_uint32), ("variant", C.c_uint32), ("lds_resident", C.c_uint32), ("triangle_materials", C.c_uint32),
@@ -269,7 +275,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32,
+                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32, TreeCost: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -286,6 +292,7 @@ DEVICE_SYMBOLS = [
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
+    "trc_rebuild_tree", "trc_tree_cost",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",

@@ -410,7 +410,8 @@ void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s) {
 
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind) {
     trc_picture_changed(ctx);
-    if (kind != kSceneVerticesMoved) trc_forget_costs(ctx);
+    if (kind != kSceneVerticesMoved && kind != kSceneTreeRebuilt) trc_forget_costs(ctx);
+    if (kind == kSceneTreeRebuilt) trc_refit_free_maps(ctx);
     if (kind != kSceneReplaced) { trc_mesh_light_free(ctx); return; }
     ctx->tri_materials = false;
     trc_release_scene(ctx);

@@ -162,7 +162,7 @@ struct trc_ctx {
     uint32_t* d_memo = nullptr;         // primary-replay memo rows of the render launches that keep them in global memory
     size_t memo_bytes = 0;
     uint32_t* d_queue = nullptr;        // block queue head of the persistent-workgroup launches
-    trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh, reference array layout (trc_download_bvh)
+    trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh / _sah / _device or trc_rebuild_tree, reference array layout (trc_download_bvh)
     uint32_t n_bvh_ref = 0, lbvh_height = 0;
     float lbvh_build_ms = 0.0f;
     // trc_update_vertices (trc_refit.hip): the scene's vertex and index arrays, kept beside the blob by every upload
@@ -378,12 +378,24 @@ struct DevBuf {
     void* release() { void* q = p; p = nullptr; return q; }
 };
 
-// The many temporary device arrays of one function (the tree builds), each a DevBuf: freed on every path out, failing as DevBuf::alloc does
+// The many temporary device arrays of one function (the tree builds), each a DevBuf: freed on every path out, failing as DevBuf::alloc does.
+// reserve() first makes ONE allocation that the arrays are then carved from, 256 bytes apart at least; an array that no longer fits, or
+// every array when the reservation itself found no room, gets a buffer of its own as before.  Why: hipFree waits for the device and
+// unmaps, 0.18 ms apiece on an MI355X -- the thirty-odd arrays of a tree build over 1 M leaves took 5.5 ms to free, a single one of their
+// total size (203 MB) 0.23 ms (profiles/r19/rebuild_tree.txt)
 struct DevBufs {
     std::vector<DevBuf> bufs;
-    template <class T> trc_status alloc(trc_ctx* ctx, T** out, size_t count, const char* what) {      // `count` elements, at least one
+    char* arena = nullptr; size_t arena_bytes = 0, arena_used = 0;
+    void reserve(size_t bytes) {
         bufs.emplace_back();
-        TRC_TRY(bufs.back().alloc(ctx, (count ? count : 1) * sizeof(T), what));
+        if (hipMalloc(&bufs.back().p, bytes) != hipSuccess) { bufs.back().p = nullptr; (void)hipGetLastError(); return; }
+        arena = bufs.back().as<char>(); arena_bytes = bytes; arena_used = 0;
+    }
+    template <class T> trc_status alloc(trc_ctx* ctx, T** out, size_t count, const char* what) {      // `count` elements, at least one
+        const size_t bytes = (count ? count : 1) * sizeof(T), padded = (bytes + 255u) & ~(size_t)255u;
+        if (padded <= arena_bytes - arena_used) { *out = reinterpret_cast<T*>(arena + arena_used); arena_used += padded; return TRC_OK; }
+        bufs.emplace_back();
+        TRC_TRY(bufs.back().alloc(ctx, bytes, what));
         *out = bufs.back().as<T>();
         return TRC_OK;
     }
@@ -494,7 +506,8 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
 }
 trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices left for later (ks.root_box, the overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
-void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays and the refit maps (no-op when absent)
+void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, binding and the refit maps (no-op when absent)
+void trc_refit_free_maps(trc_ctx* ctx);            // trc_refit.hip: the refit maps alone (parent, level table, record map): the tree's topology changed (trc_rebuild_tree)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
 
 // ----------------------------------------------------------------------- what is stale now
@@ -516,7 +529,10 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //                       A device tree upload that fails after that releases what it allocated of the NEW scene too, before it returns
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
 //   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
-enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved };
+//   kSceneTreeRebuilt   trc_rebuild_tree, once the new tree is on its way into the blob: no vertex moved, but a tie in t may now resolve to
+//                       another primitive.  The block costs stay; the refit maps go (trc_refit_free_maps: the next update, pose or skin makes
+//                       them for the new topology); vertex and index arrays, rest copy, binding and triangle materials stay
+enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneTreeRebuilt };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:
 void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload allocates

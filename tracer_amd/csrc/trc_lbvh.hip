@@ -18,6 +18,11 @@
 //   leaf records, the build's temporaries: from here a failure releases the new scene too) -> leaf_records -> lbvh_topology | sah_build_topology ->
 //   fit_boxes (refit passes; the intake flags are looked at here) -> rotate_sweep + fit_boxes, twice (Morton trees only) -> renumber_and_emit -> adopt
 //
+// trc_rebuild_tree runs the same steps from what the device already holds (rebuild_tree below): the leaf records are slots 1..n of the
+// reference-layout tree as the last upload or refit left them -- for a caller's tree (trc_upload_scene), which has none, k_canonical_leaves
+// writes them from the fat nodes' leaf slots -- and k_lbvh_emit overwrites the node region of the blob and the records in place.
+// trc_tree_cost (k_tree_cost, k_tree_cost_sum) is a surface-area measure of the fat nodes as they stand.
+//
 // All of it is integer / min-max work on a few bytes per leaf: HBM-bound streaming passes, no MFMA.  The CPU
 // statement of the same build is oracle/oracle_lbvh.cpp; tests compare all 2n-1 records bit for bit.
 #include <hip/hip_runtime.h>
@@ -56,7 +61,9 @@ __device__ __forceinline__ void leaf_centroid(const DLeaf& l, float c[3]) {
 // leaf records as uploaded (reference layout, ref_leaves = slot 1 of the output array) -> compact DLeaf; checks
 // what trc_upload_scene checks on the host (primitive type / index range) and clears the link fields
 struct LeafLimits { uint32_t n[4]; };      // spheres, squares, cubes, triangles
-__global__ void __launch_bounds__(256) k_lbvh_prepare(trc_BVH* ref_leaves, uint32_t n, LeafLimits lim, DLeaf* out, uint32_t* bad) {
+// clear_links == 0 (trc_rebuild_tree): the records are those of the tree in use, which a refused rebuild leaves as it found them; the
+// leaves' child links are 0 since their upload and k_lbvh_emit writes every leaf's parent
+__global__ void __launch_bounds__(256) k_lbvh_prepare(trc_BVH* ref_leaves, uint32_t n, LeafLimits lim, DLeaf* out, uint32_t* bad, uint32_t clear_links) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     trc_BVH& r = ref_leaves[i];
@@ -70,7 +77,7 @@ __global__ void __launch_bounds__(256) k_lbvh_prepare(trc_BVH* ref_leaves, uint3
     d.mx[0] = r.bBOX.maxi.x; d.mx[1] = r.bBOX.maxi.y; d.mx[2] = r.bBOX.maxi.z;
     d.tag = ((uint32_t)t << kTagIndexBits) | (pi & kTagIndexMask); d._pad = 0;
     out[i] = d;
-    r.parent = 0; r.left = 0; r.right = 0;
+    if (clear_links) { r.parent = 0; r.left = 0; r.right = 0; }
 }
 
 // bounds[0..2] = min, bounds[3..5] = max of the centroids, as ordered uints (init: 0xFFFFFFFF / 0).
@@ -476,6 +483,107 @@ __global__ void __launch_bounds__(256) k_lbvh_emit(const DLeaf* leaves, const ui
     if (ch[1] & kChildLeaf) ref[slot[1]].parent = self;      // interior children write their own record
 }
 
+// ---- trc_rebuild_tree on a caller's tree (trc_upload_scene): no reference-layout array exists, so the leaf records are written from the
+// fat nodes in the canonical order of include/tracer_abi.h -- by pType, then by pIndex.  k_canonical_keys gives child slot s of fat node k
+// (value 2k + s) the key first[pType] + pIndex (first[]: prefix sums of the scene's primitive counts) when it holds a leaf and ~0 when it
+// holds an interior node; the tree builds' radix sort puts the n leaves in front, in canonical order; k_canonical_leaves writes the leaf at
+// sorted position p into record 1 + p (the box from the slot's six floats, padding lanes 0, parent and links 0).  Bad bit 1: a tag that
+// names no primitive of the scene, or fewer than n leaves; bit 2: two leaves name the same primitive
+struct LeafFirst { uint32_t first[4], n[4]; };
+constexpr uint32_t kNoLeafKey = 0xFFFFFFFFu;
+__global__ void __launch_bounds__(256) k_canonical_keys(const uint4* __restrict__ nodes, uint32_t n_nodes, LeafFirst lf, uint32_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ vals, uint32_t* __restrict__ bad) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n_nodes) return;
+    const uint4 q3 = nodes[4 * (size_t)k + 3];
+    const uint32_t tag[2] = {q3.z, q3.w};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const uint32_t type = tag[s] >> kTagIndexBits, index = tag[s] & kTagIndexMask;
+        uint32_t key = kNoLeafKey;
+        if (type != kTagInterior) {
+            if (type <= (uint32_t)TRC_PRIM_TRIANGLE && index < lf.n[type]) key = lf.first[type] + index; else atomicOr(bad, 1u);
+        }
+        keys[2u * k + s] = key; vals[2u * k + s] = 2u * k + s;
+    }
+}
+__global__ void __launch_bounds__(256) k_canonical_leaves(const uint4* __restrict__ nodes, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                          LeafFirst lf, uint32_t n_leaves, trc_BVH* __restrict__ ref, uint32_t* __restrict__ bad) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n_leaves) return;
+    const uint32_t key = keys[p], slot = vals[p];
+    if (key == kNoLeafKey) { atomicOr(bad, 1u); return; }
+    if (p > 0 && keys[p - 1] == key) atomicOr(bad, 2u);
+    const uint32_t type = key >= lf.first[3] ? 3u : key >= lf.first[2] ? 2u : key >= lf.first[1] ? 1u : 0u;
+    const uint4* nd = nodes + 4 * (size_t)(slot >> 1);
+    const uint4 q0 = nd[0], q1 = nd[1], q2 = nd[2];
+    const bool right = (slot & 1u) != 0u;
+    uint4* r = reinterpret_cast<uint4*>(&ref[1u + p]);          // a 64-byte record: links + axis | pType, pIndex, padding | mini | maxi
+    r[0] = make_uint4(0u, 0u, 0u, 0u);
+    r[1] = make_uint4(type, key - lf.first[type], 0u, 0u);
+    r[2] = right ? make_uint4(q1.z, q1.w, q2.x, 0u) : make_uint4(q0.x, q0.y, q0.z, 0u);
+    r[3] = right ? make_uint4(q2.y, q2.z, q2.w, 0u) : make_uint4(q0.w, q1.x, q1.y, 0u);
+}
+
+// ---- trc_tree_cost: half areas of the child slots of every fat node, summed in binary64.  One thread per fat node (grid-stride), the
+// node read as k_refit_level reads it (4 x 16 bytes); a wavefront shuffle reduction, the four wavefronts through LDS, ONE partial per
+// workgroup; k_tree_cost_sum adds the partials in one workgroup.  No float64 atomics: they execute at the memory side one after the other
+// on one address, and the two-launch form gives the same bits for the same grid.  64 B per node, nothing to reuse: bandwidth-trivial.
+// d = max - min in binary32, a d that is not > 0 counts as 0; the three products of two binary32 values each are exact in binary64
+// (24 + 24 significand bits), so neither contraction nor the fast-math build changes a bit of a slot's value
+struct CostPartial { double interior, leaf; uint32_t n_interior, n_leaves; };
+__device__ __forceinline__ double half_area(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) {
+    float dx = mxx - mnx, dy = mxy - mny, dz = mxz - mnz;
+    if (!(dx > 0.0f)) dx = 0.0f;
+    if (!(dy > 0.0f)) dy = 0.0f;
+    if (!(dz > 0.0f)) dz = 0.0f;
+    return ((double)dx * (double)dy + (double)dy * (double)dz) + (double)dz * (double)dx;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ void cost_block_reduce(double si, double sl, uint32_t ci, uint32_t cl, CostPartial* out) {
+    __shared__ double part_d[4][2];
+    __shared__ uint32_t part_u[4][2];
+    si = wave_sum_f64(si); sl = wave_sum_f64(sl); ci = wave_sum(ci); cl = wave_sum(cl);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) { part_d[wave][0] = si; part_d[wave][1] = sl; part_u[wave][0] = ci; part_u[wave][1] = cl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        CostPartial p;
+        p.interior = ((part_d[0][0] + part_d[1][0]) + part_d[2][0]) + part_d[3][0];
+        p.leaf = ((part_d[0][1] + part_d[1][1]) + part_d[2][1]) + part_d[3][1];
+        p.n_interior = part_u[0][0] + part_u[1][0] + part_u[2][0] + part_u[3][0];
+        p.n_leaves = part_u[0][1] + part_u[1][1] + part_u[2][1] + part_u[3][1];
+        *out = p;
+    }
+}
+__global__ void __launch_bounds__(256) k_tree_cost(const uint4* __restrict__ nodes, uint32_t n_nodes, CostPartial* __restrict__ partial) {
+    double si = 0.0, sl = 0.0;
+    uint32_t ci = 0, cl = 0;
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_nodes; k += gridDim.x * 256u) {
+        const uint4* nd = nodes + 4 * (size_t)k;
+        const uint4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
+        const double h[2] = {half_area(__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z), __uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q1.y)),
+                             half_area(__uint_as_float(q1.z), __uint_as_float(q1.w), __uint_as_float(q2.x), __uint_as_float(q2.y), __uint_as_float(q2.z), __uint_as_float(q2.w))};
+        const uint32_t tag[2] = {q3.z, q3.w};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if ((tag[s] >> kTagIndexBits) == kTagInterior) { si += h[s]; ++ci; } else { sl += h[s]; ++cl; }
+        }
+    }
+    cost_block_reduce(si, sl, ci, cl, &partial[blockIdx.x]);
+}
+__global__ void __launch_bounds__(256) k_tree_cost_sum(const CostPartial* __restrict__ partial, uint32_t n_partial, CostPartial* __restrict__ out) {
+    double si = 0.0, sl = 0.0;
+    uint32_t ci = 0, cl = 0;
+    for (uint32_t i = threadIdx.x; i < n_partial; i += 256u) { const CostPartial p = partial[i]; si += p.interior; sl += p.leaf; ci += p.n_interior; cl += p.n_leaves; }
+    cost_block_reduce(si, sl, ci, cl, out);
+}
+constexpr uint32_t kCostMaxWorkgroups = 2048;      // 8 per CU of 256: every partial is one 24-byte store, the second kernel reads 48 KB at most
+
 // ---- host side.  One 8-bit digit of the sort: n pairs from (keys_in, vals_in) into (keys_out, vals_out); hist: trc_sort_hist_words(n) words
 void radix_pass(hipStream_t st, const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out, uint32_t* hist,
                 uint32_t* digit_base, uint32_t n, uint32_t shift) {
@@ -495,7 +603,7 @@ int radix_sort(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* h
 
 // What the steps of a device tree build share.  The device arrays are temporaries (tmp); blob and reference-layout tree are the context's
 struct TreeBuild {
-    trc_ctx* ctx; hipStream_t st; const trc_scene* s;
+    trc_ctx* ctx; hipStream_t st; const trc_scene* s;      // s == nullptr: trc_rebuild_tree -- n, n_interior and sc come from the context's scene (ctx->ks.sc)
     bool sah, triangle_leaves;      // sah: the reference's binned-SAH topology, else Morton order + rotations.  triangle_leaves: bvhList holds
                                     // the analytic primitives' leaves only; one leaf per triangle follows them, written on the device
     uint32_t n = 0, n_interior = 0; DScene sc{}; uint64_t blob_words = 0;
@@ -505,6 +613,7 @@ struct TreeBuild {
     uint32_t* bounds = nullptr;               // 6 ordered centroid bounds + word 6 = the leaf-intake flags
     uint32_t *height = nullptr, *arrived = nullptr;      // per interior node: subtree height; pass of fitting (later: its depth rank)
     int cur = 0; uint32_t first_chunk = 40, tree_height = 0;      // sorted buffer; refit passes before the first look at the root; pass that fitted it
+    trc_BVH* ref = nullptr;                   // the reference-layout array the steps read the leaf records from and emit into (ctx->d_bvh_ref unless a rebuild makes a new one)
     dim3 g_leaf() const { return dim3((n + 255) / 256); }
     dim3 g_int() const { return dim3((n_interior + 255) / 256); }
 };
@@ -528,6 +637,26 @@ trc_status intake(TreeBuild& b) {
     return TRC_OK;
 }
 
+// Room for the build's temporaries in one allocation (DevBufs::reserve): per leaf 32 + 24 B of leaves and boxes, 11 words of sort and
+// topology arrays and 2 of the depth sort (109 B with the histograms), for the SAH build 68 B of records in tree order, side array and
+// moves and ~20 B of level tables and finish list (198 B in all); `extra`: what a rebuild of a caller's tree sorts before that.  An
+// estimate: what it leaves out gets a buffer of its own
+void reserve_temporaries(TreeBuild& b, size_t extra = 0) { b.tmp.reserve((size_t)b.n * (b.sah ? 198u : 109u) + extra + (64u << 10)); }
+
+// the build's temporary arrays, and the centroid bounds / intake flags at their identities
+trc_status work_arrays(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx;
+    const uint32_t n = b.n, ni = b.n_interior;
+    const char* const what = "tree build: work arrays";
+    TRC_TRY(b.tmp.alloc(ctx, &b.leaves, n, what)); TRC_TRY(b.tmp.alloc(ctx, &b.boxes, (size_t)ni * 6, what));
+    const struct { uint32_t** p; size_t count; } words[] = {
+        {&b.keys[0], n}, {&b.vals[0], n}, {&b.keys[1], n}, {&b.vals[1], n}, {&b.hist, trc_sort_hist_words(n)}, {&b.digit_base, 256}, {&b.bounds, 8},
+        {&b.height, ni}, {&b.arrived, ni}, {&b.tp.child_l, ni}, {&b.tp.child_r, ni}, {&b.tp.parent_interior, ni}, {&b.tp.parent_leaf, n}, {&b.tp.axis, ni}};
+    for (const auto& w : words) TRC_TRY(b.tmp.alloc(ctx, w.p, w.count, what));
+    const uint32_t bounds_init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+    return trc_copy_to_device(ctx, b.bounds, bounds_init, sizeof bounds_init, b.st);
+}
+
 // the caller's leaf records go straight to slots 1..n of the reference-layout array (BVH.hh:246-269), the triangles' behind them
 trc_status replace_scene(TreeBuild& b) {
     trc_ctx* const ctx = b.ctx;
@@ -541,22 +670,17 @@ trc_status replace_scene(TreeBuild& b) {
     TRC_TRY(trc_repack_triangles(ctx, b.s, b.sc, ctx->d_blob, b.triangle_leaves ? ctx->d_bvh_ref + 1 + n_given : nullptr));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_bvh_ref, 0, sizeof(trc_BVH), b.st));
     if (n_given) TRC_TRY(trc_copy_to_device(ctx, ctx->d_bvh_ref + 1, b.s->bvhList, sizeof(trc_BVH) * n_given, b.st));
-    const uint32_t n = b.n, ni = b.n_interior;       // ... and the build's temporary arrays
-    const char* const what = "tree build: work arrays";
-    TRC_TRY(b.tmp.alloc(ctx, &b.leaves, n, what)); TRC_TRY(b.tmp.alloc(ctx, &b.boxes, (size_t)ni * 6, what));
-    const struct { uint32_t** p; size_t count; } words[] = {
-        {&b.keys[0], n}, {&b.vals[0], n}, {&b.keys[1], n}, {&b.vals[1], n}, {&b.hist, trc_sort_hist_words(n)}, {&b.digit_base, 256}, {&b.bounds, 8},
-        {&b.height, ni}, {&b.arrived, ni}, {&b.tp.child_l, ni}, {&b.tp.child_r, ni}, {&b.tp.parent_interior, ni}, {&b.tp.parent_leaf, n}, {&b.tp.axis, ni}};
-    for (const auto& w : words) TRC_TRY(b.tmp.alloc(ctx, w.p, w.count, what));
-    const uint32_t bounds_init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    return trc_copy_to_device(ctx, b.bounds, bounds_init, sizeof bounds_init, b.st);
+    b.ref = ctx->d_bvh_ref;
+    reserve_temporaries(b);
+    return work_arrays(b);
 }
+
 
 // the uploaded leaf records (slots 1..n of the reference-layout array) -> compact leaves; what is wrong with them -> the intake flags
 void leaf_records(TreeBuild& b) {
     LeafLimits lim;
-    lim.n[0] = b.s->n_sphere; lim.n[1] = b.s->n_square; lim.n[2] = b.s->n_cube; lim.n[3] = b.s->n_index / 3;
-    hipLaunchKernelGGL(k_lbvh_prepare, b.g_leaf(), dim3(256), 0, b.st, b.ctx->d_bvh_ref + 1, b.n, lim, b.leaves, b.bounds + 6);
+    lim.n[0] = b.sc.n_spheres; lim.n[1] = b.sc.n_squares; lim.n[2] = b.sc.n_cubes; lim.n[3] = b.sc.n_triangles;
+    hipLaunchKernelGGL(k_lbvh_prepare, b.g_leaf(), dim3(256), 0, b.st, b.ref + 1, b.n, lim, b.leaves, b.bounds + 6, b.s ? 1u : 0u);
 }
 
 // Morton order and T. Karras' radix tree over it: the sibling of sah_build_topology
@@ -600,7 +724,7 @@ trc_status renumber_and_emit(TreeBuild& b) {
     hipLaunchKernelGGL(k_lbvh_depth, b.g_int(), dim3(256), 0, b.st, b.n_interior, b.tp.parent_interior, depth, node);
     radix_pass(b.st, depth, node, sorted_depth, sorted_node, b.hist, b.digit_base, b.n_interior, 0u);
     hipLaunchKernelGGL(k_lbvh_rank, b.g_int(), dim3(256), 0, b.st, b.n_interior, sorted_node, rank);
-    hipLaunchKernelGGL(k_lbvh_emit, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, rank, ctx->d_blob + b.sc.off_nodes, ctx->d_bvh_ref);
+    hipLaunchKernelGGL(k_lbvh_emit, b.g_int(), dim3(256), 0, b.st, b.leaves, b.vals[b.cur], b.n, b.tp, b.boxes, rank, ctx->d_blob + b.sc.off_nodes, b.ref);
     HIP_TRY(ctx, hipGetLastError());
     return TRC_OK;
 }
@@ -633,6 +757,70 @@ trc_status build_tree(TreeBuild& b) {
     return adopt(b, timed);
 }
 
+// trc_rebuild_tree on a caller's tree: a new reference-layout array with the leaf records in canonical order (k_canonical_leaves); the
+// context keeps its own (none) until the rebuild has emitted into this one.  The tree builds' sort arrays are not yet in use
+trc_status canonical_leaf_records(TreeBuild& b, DevBuf& new_ref) {
+    trc_ctx* const ctx = b.ctx;
+    const DScene& sc = b.sc;
+    LeafFirst lf;
+    const uint32_t counts[4] = {sc.n_spheres, sc.n_squares, sc.n_cubes, sc.n_triangles};
+    uint32_t total = 0;
+    for (int t = 0; t < 4; ++t) { lf.first[t] = total; lf.n[t] = counts[t]; total += counts[t]; }      // (each below 2^29: no wrap)
+    TRC_TRY(new_ref.alloc(ctx, sizeof(trc_BVH) * (2 * (size_t)b.n - 1), "trc_rebuild_tree: tree records"));
+    const uint32_t n_slots = 2u * b.n_interior;
+    const char* const what = "trc_rebuild_tree: leaf intake";
+    uint32_t *keys[2] = {}, *vals[2] = {}, *hist = nullptr, *digit_base = nullptr, *bad = nullptr, flags = 0;
+    for (uint32_t** p : {&keys[0], &keys[1], &vals[0], &vals[1]}) TRC_TRY(b.tmp.alloc(ctx, p, n_slots, what));
+    TRC_TRY(b.tmp.alloc(ctx, &hist, trc_sort_hist_words(n_slots), what)); TRC_TRY(b.tmp.alloc(ctx, &digit_base, 256, what)); TRC_TRY(b.tmp.alloc(ctx, &bad, 1, what));
+    HIP_TRY(ctx, hipMemsetAsync(bad, 0, sizeof(uint32_t), b.st));
+    HIP_TRY(ctx, hipMemsetAsync(new_ref.p, 0, sizeof(trc_BVH), b.st));
+    const uint4* const nodes = reinterpret_cast<const uint4*>(ctx->d_blob + sc.off_nodes);
+    hipLaunchKernelGGL(k_canonical_keys, b.g_int(), dim3(256), 0, b.st, nodes, sc.n_nodes, lf, keys[0], vals[0], bad);
+    const int cur = radix_sort(b.st, keys, vals, hist, digit_base, n_slots, 32);
+    hipLaunchKernelGGL(k_canonical_leaves, b.g_leaf(), dim3(256), 0, b.st, nodes, keys[cur], vals[cur], lf, b.n, new_ref.as<trc_BVH>(), bad);
+    TRC_TRY(trc_read_to_host(ctx, b.st, "trc_rebuild_tree: leaf intake", {{&flags, bad, 4}}));
+    if (flags) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_rebuild_tree: two leaves of the tree name the same primitive");
+    b.ref = new_ref.as<trc_BVH>();
+    return TRC_OK;
+}
+
+// The second way into the steps: everything from what the device holds.  Whatever can refuse comes before renumber_and_emit, which is the first
+// to write into the tree in use; from there on only a HIP error can end the call
+trc_status rebuild_tree(TreeBuild& b) {
+    trc_ctx* const ctx = b.ctx;
+    b.sc = ctx->ks.sc; b.n_interior = b.sc.n_nodes; b.n = b.n_interior + 1;
+    DevBuf new_ref;
+    b.ref = ctx->d_bvh_ref;
+    reserve_temporaries(b, b.ref ? 0u : (size_t)b.n * 33u);      // a caller's tree: two key / value pairs over its 2 (n - 1) child slots
+    TimedSection timed(ctx, b.st);
+    if (!b.ref) TRC_TRY(canonical_leaf_records(b, new_ref));
+    TRC_TRY(work_arrays(b));
+    leaf_records(b);
+    if (b.sah) TRC_TRY(sah_build_topology(b)); else lbvh_topology(b);
+    TRC_TRY(fit_boxes(b));
+    for (int sweep = 0; !b.sah && sweep < kRotationSweeps; ++sweep) { rotate_sweep(b); TRC_TRY(fit_boxes(b)); }
+    uint32_t height = 0; float root_box[6];
+    TRC_TRY(trc_read_to_host(ctx, b.st, "tree rebuild: root", {{&height, b.height, 4}, {root_box, b.boxes, sizeof root_box}}));
+    if (height > TRC_MAX_BVH_DEPTH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: tree deeper than TRC_MAX_BVH_DEPTH");
+    trc_sppm_order_after_camera(ctx);             // a camera pass running ahead on its own stream still walks the old nodes
+    TRC_TRY(renumber_and_emit(b));
+    timed.stop();
+    // the new tree is on its way: the layout stays (same leaf count), the LDS plan follows the new height, the root box is the new root's
+    plan_lds(b.sc, height, true);
+    ctx->ks.sc = b.sc;
+    std::memcpy(ctx->ks.root_box, root_box, sizeof root_box);
+    ctx->lds_scene = b.sc.n_lds_nodes == b.sc.n_nodes;
+    ctx->lds_prefix_ok = true;
+    if (new_ref.p) ctx->d_bvh_ref = static_cast<trc_BVH*>(new_ref.release());
+    ctx->n_bvh_ref = 2 * b.n - 1;
+    ctx->lbvh_height = height;
+    trc_scene_changed(ctx, kSceneTreeRebuilt);
+    if (ctx->cost_valid) { ctx->plan_streak = 0; ctx->cost_fresh_next = true; }      // as after trc_update_vertices: one pass on the last launch's raw durations
+    HIP_TRY(ctx, hipStreamSynchronize(b.st));       // the temporaries go when this returns; the build's device time is known
+    ctx->lbvh_build_ms = timed.ms();
+    return TRC_OK;
+}
+
 }  // namespace
 
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result) {
@@ -658,6 +846,40 @@ trc_status trc_upload_scene_sah(trc_ctx* ctx, const trc_scene* s) { return uploa
 trc_status trc_upload_scene_device(trc_ctx* ctx, const trc_scene* s, uint32_t flags) {
     if (flags & ~(uint32_t)(TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES)) return ctx ? trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_scene_device: unknown flag") : TRC_ERR_INVALID_ARG;
     return upload_device_tree(ctx, s, (flags & TRC_TREE_SAH) != 0, (flags & TRC_TREE_TRIANGLE_LEAVES) != 0);
+}
+
+trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)TRC_TREE_SAH) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_rebuild_tree: flags other than TRC_TREE_SAH");
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_rebuild_tree: no scene");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TreeBuild b{ctx, ctx->stream, nullptr, (flags & TRC_TREE_SAH) != 0, false};
+    return rebuild_tree(b);
+}
+
+trc_status trc_tree_cost(trc_ctx* ctx, trc_tree_cost_t* out) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!out) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_tree_cost: out == NULL");
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_tree_cost: no scene");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const DScene& sc = ctx->ks.sc;
+    const uint32_t n_wg = std::min<uint32_t>((sc.n_nodes + 255) / 256, kCostMaxWorkgroups);
+    DevBuf partial;
+    TRC_TRY(partial.alloc(ctx, sizeof(CostPartial) * ((size_t)n_wg + 1), "trc_tree_cost: partial sums"));
+    CostPartial* const d_partial = partial.as<CostPartial>();
+    hipLaunchKernelGGL(k_tree_cost, dim3(n_wg), dim3(256), 0, ctx->stream, reinterpret_cast<const uint4*>(ctx->d_blob + sc.off_nodes), sc.n_nodes, d_partial);
+    hipLaunchKernelGGL(k_tree_cost_sum, dim3(1), dim3(256), 0, ctx->stream, d_partial, n_wg, d_partial + n_wg);
+    CostPartial sum{};
+    TRC_TRY(trc_read_to_host(ctx, ctx->stream, "trc_tree_cost", {{&sum, d_partial + n_wg, sizeof sum}}));
+    const float* r = ctx->ks.root_box;
+    float d[3];
+    for (int a = 0; a < 3; ++a) { d[a] = r[3 + a] - r[a]; if (!(d[a] > 0.0f)) d[a] = 0.0f; }
+    out->root_half_area = ((double)d[0] * (double)d[1] + (double)d[1] * (double)d[2]) + (double)d[2] * (double)d[0];
+    out->interior_half_area = sum.interior; out->leaf_half_area = sum.leaf;
+    out->n_interior = sum.n_interior; out->n_leaves = sum.n_leaves;
+    return TRC_OK;
 }
 
 trc_status trc_download_bvh(trc_ctx* ctx, trc_BVH* out, uint32_t capacity, uint32_t* n_nodes) {

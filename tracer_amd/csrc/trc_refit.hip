@@ -351,10 +351,7 @@ trc_status refit_make_maps(trc_ctx* ctx) {
 trc_status refit_prepare(trc_ctx* ctx) {
     if (!ctx->refit_levels.empty()) return TRC_OK;
     const trc_status rs = refit_make_maps(ctx);
-    if (rs != TRC_OK) {
-        (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
-        ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
-    }
+    if (rs != TRC_OK) trc_refit_free_maps(ctx);
     return rs;
 }
 
@@ -453,9 +450,19 @@ trc_status trc_refit_settle_pending(trc_ctx* ctx) {
     return TRC_OK;
 }
 
+// the maps follow the tree's topology and numbering: made by refit_prepare, freed with the scene and by trc_rebuild_tree.  The overflow
+// counter lives in d_refit_root and starts again at zero with it; a pending read-back has been settled by the caller's trc_flush
+void trc_refit_free_maps(trc_ctx* ctx) {
+    (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
+    ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
+    ctx->pose_count_seen = 0;
+    ctx->refit_levels.clear();
+}
+
 void trc_refit_free(trc_ctx* ctx) {
     for (hipEvent_t& e : ctx->refit_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     ctx->refit_pending = ctx->refit_posed = false;
+    trc_refit_free_maps(ctx);
     (void)hipFree(ctx->d_verts); (void)hipFree(ctx->d_idx);
     (void)hipFree(ctx->d_rest); (void)hipFree(ctx->d_pose_table);
     ctx->d_rest = nullptr; ctx->d_pose_table = nullptr; ctx->pose_table_bytes = 0;
@@ -463,10 +470,7 @@ void trc_refit_free(trc_ctx* ctx) {
     (void)hipFree(ctx->d_skin_influences); (void)hipFree(ctx->d_skin_palette);
     ctx->d_skin_influences = nullptr; ctx->d_skin_palette = nullptr; ctx->skin_palette_bytes = 0;
     ctx->skin_first = ctx->skin_count = ctx->skin_max_bone = 0;
-    (void)hipFree(ctx->d_refit_parent); (void)hipFree(ctx->d_refit_arrive); (void)hipFree(ctx->d_refit_root); (void)hipFree(ctx->d_refit_refnode);
     ctx->d_verts = nullptr; ctx->d_idx = nullptr; ctx->n_vertex = 0;
-    ctx->d_refit_parent = ctx->d_refit_arrive = ctx->d_refit_refnode = nullptr; ctx->d_refit_root = nullptr;
-    ctx->refit_levels.clear();
 }
 
 extern "C" {

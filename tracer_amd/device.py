@@ -126,6 +126,8 @@ def _load(path, hooks=False):
     L.trc_debug_pose_overflows.argtypes = [vp, C.POINTER(u32)]
     L.trc_skin_bind.argtypes = [vp, vp, u32, u32]
     L.trc_skin_vertices.argtypes = [vp, C.POINTER(abi.SkinBone), u32]
+    L.trc_rebuild_tree.argtypes = [vp, u32]
+    L.trc_tree_cost.argtypes = [vp, C.POINTER(abi.TreeCost)]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -401,6 +403,18 @@ class Tracer:
         self._check(self._L.trc_download_bvh(self._h, None, 0, C.byref(n)), "trc_download_bvh")
         out = (abi.BVH * n.value)()
         self._check(self._L.trc_download_bvh(self._h, out, n.value, C.byref(n)), "trc_download_bvh")
+        return out
+
+    def rebuild_tree(self, flags=0):
+        """trc_rebuild_tree: a fresh tree over the scene's current leaf records, built on the device from what it holds -- abi.TREE_SAH
+        for the reference's binned-SAH tree, 0 for the LBVH with rotations.  Vertices, materials, rest copy and binding stay."""
+        self._check(self._L.trc_rebuild_tree(self._h, flags), "trc_rebuild_tree")
+
+    def tree_cost(self):
+        """trc_tree_cost -> abi.TreeCost: half areas of the root box, of the interior child slots and of the leaf child slots of the
+        tree as it stands, with the two slot counts; (interior + leaf) / root grows as a refitted tree degrades."""
+        out = abi.TreeCost()
+        self._check(self._L.trc_tree_cost(self._h, C.byref(out)), "trc_tree_cost")
         return out
 
     def lbvh_info(self):
