@@ -11,7 +11,10 @@
 //                          them itself, 144 bytes cross the bus instead of the vertex array); frame k goes to <out>.k.png
 //              [--bend N]  N frames of a two-bone bend: the foot of the mesh stands, its top makes --pose's turn, and every vertex blends
 //                          the two by its height (trc_skin_bind once, trc_skin_vertices per frame); frame k goes to <out>.k.png
-//              [--rebuild-ratio R]  beside --spin / --pose / --bend: after every animation call the tree's cost is read (trc_tree_cost), and
+//              [--morph N] N frames of two blend shapes with swinging weights: one swells the mesh, one presses it towards its foot
+//                          (trc_morph_bind once, trc_morph_vertices per frame); with --bend each of these frames is the morph AND --bend's
+//                          two bones on top of it in one call; frame k goes to <out>.k.png
+//              [--rebuild-ratio R]  beside --spin / --pose / --bend / --morph: after every animation call the tree's cost is read (trc_tree_cost), and
 //                          when (interior + leaf) / root exceeds R times what it was right after the last build, the tree is built anew on the
 //                          device (trc_rebuild_tree, TRC_TREE_SAH); the number of rebuilds is printed at the end
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
@@ -44,7 +47,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    uint32_t spin = 0, pose = 0, bend = 0;
+    uint32_t spin = 0, pose = 0, bend = 0, morph = 0;
     double rebuild_ratio = 0.0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
     for (int i = 1; i < argc; ++i) {
@@ -76,7 +79,12 @@ int main(int argc, char** argv) {
             if (n <= 0 || n > 100000) { std::fprintf(stderr, "--bend wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
             bend = (uint32_t)n;
         }
-        else if (a == "--rebuild-ratio" && i + 1 < argc) {                      // a fresh tree when the refitted one has worn: trc_tree_cost, trc_rebuild_tree
+        else if (a == "--morph" && i + 1 < argc) {                              // blend shapes: two weights per frame, trc_morph_vertices
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > 100000) { std::fprintf(stderr, "--morph wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
+            morph = (uint32_t)n;
+        }
+        else if (a == "--rebuild-ratio" && i + 1 < argc) {                   // a fresh tree when the refitted one has worn: trc_tree_cost, trc_rebuild_tree
             rebuild_ratio = std::atof(argv[++i]);
             if (!(rebuild_ratio >= 1.0)) { std::fprintf(stderr, "--rebuild-ratio wants a factor of at least 1, not %s\n", argv[i]); return 2; }
         }
@@ -357,6 +365,54 @@ int main(int argc, char** argv) {
         }
     } else if (bend) {
         std::fprintf(stderr, "--bend bends the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+        trc_destroy(ctx);
+        trc_host_scene_destroy(hs);
+        trc_host_mesh_destroy(mesh);
+        return 1;
+    }
+    if (morph && scene.n_vertex) {
+        // two targets over the whole mesh, target-major: target 0 swells the mesh away from the vertical axis through the centre of its
+        // box, target 1 presses it towards its foot; the normals keep their rest values (deltas of 0).  The table goes up once; a frame
+        // sends two weights.  After --bend the skin binding is still there: every frame then goes through the fused call, the morph and
+        // --bend's two bones on top of it
+        float lo[3] = {scene.triList[0].v[0], scene.triList[0].v[1], scene.triList[0].v[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+        for (uint32_t i = 0; i < scene.n_vertex; ++i)
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], scene.triList[i].v[k]); hi[k] = std::max(hi[k], scene.triList[i].v[k]); }
+        const float cx = 0.5f * (lo[0] + hi[0]), cz = 0.5f * (lo[2] + hi[2]);
+        std::vector<trc_morph_delta> deltas(2 * (size_t)scene.n_vertex);
+        for (uint32_t i = 0; i < scene.n_vertex; ++i) {
+            const float* q = scene.triList[i].v;
+            deltas[i] = {{0.5f * (q[0] - cx), 0.0f, 0.5f * (q[2] - cz)}, {0.0f, 0.0f, 0.0f}};
+            deltas[(size_t)scene.n_vertex + i] = {{0.0f, -0.5f * (q[1] - lo[1]), 0.0f}, {0.0f, 0.0f, 0.0f}};
+        }
+        CHECK(trc_morph_bind(ctx, deltas.data(), 2, 0, scene.n_vertex));
+        const uint32_t first_frame = spin + pose + bend;      // after the other animations' frames, when they are given too
+        for (uint32_t f = 1; f <= morph; ++f) {
+            const double a = 6.283185307179586 * f / morph;
+            const float weights[2] = {(float)std::sin(a), (float)(0.5 - 0.5 * std::cos(a))};      // swinging: -1..1 and 0..1
+            const float ca = (float)std::cos(a), sa = (float)std::sin(a);
+            trc_skin_bone bones[2];
+            std::memset(bones, 0, sizeof bones);
+            for (int c = 0; c < 4; ++c) (&bones[0].model_matrix.columns[c].x)[c] = 1.0f;
+            bones[0].normal_matrix = bones[0].model_matrix;
+            bones[1].model_matrix.columns[0] = {ca, 0.0f, -sa, 0.0f};
+            bones[1].model_matrix.columns[1] = {0.0f, 1.0f, 0.0f, 0.0f};
+            bones[1].model_matrix.columns[2] = {sa, 0.0f, ca, 0.0f};
+            bones[1].model_matrix.columns[3] = {cx - ca * cx - sa * cz, 0.0f, cz + sa * cx - ca * cz, 1.0f};
+            bones[1].normal_matrix = bones[1].model_matrix;
+            const auto u0 = std::chrono::steady_clock::now();
+            CHECK(trc_morph_vertices(ctx, weights, 2, bones, bend ? 2u : 0u));
+            const double morph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(rebuild_if_worn());
+            CHECK(trc_clear_accum(ctx));
+            CHECK(trc_render(ctx, &prm));
+            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
+            if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+            std::printf("morph %u / %u: trc_morph_vertices%s %.2f ms -> %s\n", f, morph, bend ? " under two bones" : "", morph_ms, name.c_str());
+        }
+    } else if (morph) {
+        std::fprintf(stderr, "--morph morphs the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
         trc_destroy(ctx);
         trc_host_scene_destroy(hs);
         trc_host_mesh_destroy(mesh);

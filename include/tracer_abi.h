@@ -58,7 +58,9 @@ extern "C" {
  *     added under 13, the number stays: trc_skin_influence, trc_skin_bone, TRC_SKIN_MAX_BONES, trc_skin_bind, trc_skin_vertices, knob
  *     skin_no_lds (linear blend skinning on the device; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_rebuild_tree, trc_tree_cost_t, trc_tree_cost (a fresh tree for a moved mesh from what the
- *     device holds, and a surface-area measure that tells a host when to ask for one; additions only, nothing existing changed) */
+ *     device holds, and a surface-area measure that tells a host when to ask for one; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_morph_delta, TRC_MORPH_MAX_TARGETS, trc_morph_bind, trc_morph_vertices (blend shapes on the
+ *     device, alone or under the skin of trc_skin_bind in one call; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -626,8 +628,9 @@ trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_pos
  * left.  TRC_ERR_NO_SCENE before any upload; TRC_ERR_INVALID_ARG: first + count > the scene's n_vertex, out == NULL with count > 0, or
  * a scene without triangles.  count == 0 on a scene with triangles is TRC_OK.  Synchronous, like every download. */
 trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count);
-/* the number of posed positions of the last trc_pose_vertices, or of skinned positions of the last trc_skin_vertices -- whichever of the
- * two calls came last -- that came out non-finite or beyond 1e37 in magnitude (0 before any) */
+/* the number of posed positions of the last trc_pose_vertices, of skinned positions of the last trc_skin_vertices, or of final positions
+ * of the last trc_morph_vertices -- whichever of the three calls came last -- that came out non-finite or beyond 1e37 in magnitude (0
+ * before any) */
 trc_status trc_debug_pose_overflows(trc_ctx* ctx, uint32_t* n);
 /* Skinned geometry: linear blend skinning for whatever bends -- characters, cloth proxies.  trc_skin_bind gives a range of vertices
  * four (bone, weight) influences each, once; trc_skin_vertices takes the frame's bone palette, the device blends the bones' matrices
@@ -673,6 +676,48 @@ typedef struct trc_skin_bone { trc_float4x4 model_matrix, normal_matrix; } trc_s
 #define TRC_SKIN_MAX_BONES 65536u
 trc_status trc_skin_bind(trc_ctx* ctx, const trc_skin_influence* influences, uint32_t first, uint32_t count);
 trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t n_bones);
+/* Morphed geometry: blend shapes (morph targets) for faces, muscle correctives, cloth wrinkles -- v = rest + sum of w_k * delta_k -- alone
+ * or with the skin of trc_skin_bind on top, which is the order of a character pipeline (glTF's: morph first, then the bones).
+ * trc_morph_bind gives a range of vertices n_targets deltas each, once; trc_morph_vertices takes the frame's weights, the device adds the
+ * weighted deltas to the REST vertex, and the record rewrite and refit of trc_update_vertices run behind.
+ *  - trc_morph_bind: deltas[k * count + i] is target k's delta (dv to the position, dn to the normal) for vertex first + i of the
+ *    scene's triList: target-major, so that a wavefront reads consecutive bytes.  A scene has ONE morph binding, which is one range: a
+ *    second call replaces it, count == 0 or n_targets == 0 removes it (deltas may then be NULL and the other arguments are not looked
+ *    at).  The table is copied to the device before the call returns: 24 B per bound vertex PER TARGET of device memory, freed with the
+ *    scene (every trc_upload_scene*, trc_destroy).  A bind alone moves no vertex and drops nothing.  TRC_ERR_NO_SCENE before any
+ *    upload.  TRC_ERR_INVALID_ARG: deltas == NULL with a non-empty table, first + count > the scene's n_vertex, n_targets >
+ *    TRC_MORPH_MAX_TARGETS, a delta component that is not finite, or a non-empty table on a scene without triangles.  TRC_ERR_OOM if the
+ *    table cannot be allocated.  On any error the previous binding stays and nothing has changed.  The binding survives
+ *    trc_update_vertices, trc_pose_vertices, trc_skin_bind, trc_skin_vertices, trc_upload_triangle_materials and trc_rebuild_tree.
+ *  - trc_morph_vertices, definition: binary32, one rounding per operation, no contraction.  The ACTIVE LIST is the targets k,
+ *    ascending, whose weights[k] is not zero (neither +0 nor -0 counts).  For bound vertex i the accumulator starts as the six rest
+ *    values (x y z nx ny nz) of the rest copy (trc_skin_vertices says what that is); then for every active k in order and every
+ *    component c:  p = w_k * d[k][i].c;  acc.c = acc.c + p.  uv is copied, normals are NOT normalised.  With no active target the
+ *    vertex is the rest vertex bit for bit, a -0 included: zero weights are skipped, not multiplied -- which is also what makes a
+ *    rig of hundreds of mostly idle targets cheap.
+ *  - n_bones == 0 (bones is not looked at): morph only.  Vertices outside the binding keep their current values.
+ *  - n_bones > 0: the skin of trc_skin_bind runs on top, in the same kernel and the same single refit chain.  A vertex in both
+ *    bindings gets trc_skin_vertices' expressions applied to its MORPHED six values in place of its rest values; a vertex in the skin
+ *    binding only is skinned from rest; a vertex in the morph binding only is morphed.  The refit runs over the hull of the two
+ *    ranges; a vertex of the hull that is in neither binding is not written.  This call is the only way to skin(rest + morph): a
+ *    later plain trc_skin_vertices skins from rest again, as it always did.
+ *  - After the call everything observable is what trc_update_vertices would have left had the host computed those vertices and passed
+ *    them, as for a pose or a skin: the rest copy stays, the same things survive, the same are dropped, the block costs are kept,
+ *    launches kept back for coalescing run first, not collective.  The 4 * n_weights bytes, and the 128 * n_bones bytes of a palette,
+ *    are copied out of the caller's arrays before the call returns; the kernels run behind it on the context's stream.
+ *  - TRC_ERR_NO_SCENE before any upload.  TRC_ERR_INVALID_ARG: no morph binding, weights == NULL, n_weights != the binding's n_targets,
+ *    a weight that is not finite, and with n_bones > 0 everything trc_skin_vertices refuses, a missing skin binding included.
+ *    TRC_ERR_OOM if the rest copy or the small buffers cannot be allocated.  On any error nothing has changed.  No index on the device
+ *    comes from anything the host has not checked.
+ *  - Overflow: as for a pose, keeping the final positions finite and within 1e37 is the CALLER's contract; the kernel counts the ones
+ *    that break it and trc_debug_pose_overflows reports the count.
+ * Out of scope: sparse targets (a target that names few vertices still stores a delta for every bound vertex); more than one morph
+ * binding per scene; a morph under a trc_pose_vertices in one chain (they are two calls and two chains); re-derived (renormalised)
+ * normals. */
+typedef struct trc_morph_delta { float dv[3]; float dn[3]; } trc_morph_delta;   /* 24 B, packed */
+#define TRC_MORPH_MAX_TARGETS 1024u
+trc_status trc_morph_bind(trc_ctx* ctx, const trc_morph_delta* deltas, uint32_t n_targets, uint32_t first, uint32_t count);
+trc_status trc_morph_vertices(trc_ctx* ctx, const float* weights, uint32_t n_weights, const trc_skin_bone* bones, uint32_t n_bones);
 /* A fresh tree for a moved mesh.  A refit keeps the topology of the tree it found: after objects have travelled past each other the boxes
  * near the top overlap and every ray walks more of them.  trc_rebuild_tree builds the tree anew from what the DEVICE holds -- no vertex,
  * index or record crosses the bus, nothing but the tree changes -- and trc_tree_cost (below) tells a host when to ask for it.
@@ -690,7 +735,7 @@ trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t 
  *    0; parent, left, right and axis are 0.  A primitive that the caller's tree leaves out (the Cornell scenes list spheres that no
  *    leaf names) has no leaf afterwards either.  A tree that names one primitive in two leaves has no such list:
  *    TRC_ERR_UNSUPPORTED, nothing changes.  Afterwards the scene is a device-built one: trc_download_bvh and trc_lbvh_info work on it.
- *  - What survives: the kept vertex and index arrays, the rest copy of trc_pose_vertices / trc_skin_vertices and the skin binding; the
+ *  - What survives: the kept vertex and index arrays, the rest copy of trc_pose_vertices / trc_skin_vertices and the skin and morph bindings; the
  *    triangle records with their per-triangle materials; textures, the environment, the camera, the density grid, the accumulator and the
  *    RNG texture (the caller clears).  The launch planner's block costs are KEPT as after trc_update_vertices: scheduling only.
  *  - What is dropped: the G-buffer and the denoiser history (a tie in t may now resolve to another primitive); the tables of
@@ -1233,6 +1278,7 @@ TRC_SA(sizeof(trc_TriangleVertex) == 32, "TriangleVertex");
 TRC_SA(sizeof(trc_pose) == 144 && offsetof(trc_pose, model_matrix) == 16 && offsetof(trc_pose, normal_matrix) == 80, "pose");
 TRC_SA(sizeof(trc_skin_influence) == 32 && offsetof(trc_skin_influence, weight) == 16, "skin_influence");
 TRC_SA(sizeof(trc_skin_bone) == 128 && offsetof(trc_skin_bone, normal_matrix) == 64, "skin_bone");
+TRC_SA(sizeof(trc_morph_delta) == 24 && offsetof(trc_morph_delta, dn) == 12, "morph_delta");
 TRC_SA(sizeof(trc_tree_cost_t) == 32 && offsetof(trc_tree_cost_t, n_interior) == 24, "tree_cost");
 TRC_SA(sizeof(trc_TextureInfo) == 32 && offsetof(trc_TextureInfo, albedo) == 16, "TextureInfo");
 TRC_SA(sizeof(trc_Material) == 64 && offsetof(trc_Material, medium) == 4 && offsetof(trc_Material, specular) == 8 &&

@@ -13,6 +13,9 @@
 //   5. the checks of trc_skin_bind and trc_skin_vertices (tracer_amd/csrc/skin_check.hpp, HIP-free like pose_ranges.hpp) on hostile
 //      influence tables and palettes: NULL with a count, a range that wraps, non-finite weights, a bone index at the bound, a palette
 //      one bone too small, NaN in entries that are read and in entries that are not
+//   6. the checks of trc_morph_bind and trc_morph_vertices (tracer_amd/csrc/morph_check.hpp, HIP-free as well) on hostile delta tables
+//      and weights: NULL with a non-empty table, a range that wraps, non-finite deltas at the table's end, n_targets beyond the cap, a
+//      weight count off by one, non-finite weights, all-zero weights, and the compaction of the weights into the active list
 // "build host code under -fsanitize=thread,address".
 #include <cmath>
 #include <cstdio>
@@ -27,6 +30,7 @@
 #include "../../oracle/oracle.h"
 #include "../../tracer_amd/csrc/pose_ranges.hpp"
 #include "../../tracer_amd/csrc/skin_check.hpp"
+#include "../../tracer_amd/csrc/morph_check.hpp"
 
 static int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "EXPECT failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); ++g_fail; } } while (0)
@@ -228,6 +232,51 @@ static void skin_tables() {
     EXPECT(pal_ok(19, 18));                                                                                // lanes that are not read
 }
 
+// ---------------------------------------------------------------- trc_morph_bind's and trc_morph_vertices' checks
+static void morph_tables() {
+    const uint32_t n_vertex = 1000;
+    std::vector<trc_morph_delta> t(3 * 10);                                                                // three targets over ten vertices
+    for (uint32_t r = 0; r < t.size(); ++r) t[r] = {{0.5f * r, -1.0f, 0.0f}, {0.0f, 0.25f, -0.125f * r}};
+    auto ok = [&](uint32_t n_targets, uint32_t first, uint32_t count) { return trc_morph_table_check(t.data(), n_targets, first, count, n_vertex) == nullptr; };
+    EXPECT(trc_morph_table_check(nullptr, 3, 5, 0, n_vertex) == nullptr && trc_morph_table_check(nullptr, 0, 5, 7, n_vertex) == nullptr);      // empty: NULL is fine
+    EXPECT(trc_morph_table_check(nullptr, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, n_vertex) == nullptr);              // ... and nothing else is looked at
+    EXPECT(trc_morph_table_check(nullptr, 3, 0, 10, n_vertex) != nullptr);                                 // NULL with a non-empty table
+    EXPECT(ok(3, 0, 10) && ok(3, 990, 10) && !ok(3, 991, 10) && !ok(1, 1000, 1) && !ok(1, 1001, 0xFFFFFFFFu));
+    EXPECT(!ok(1, 0xFFFFFFFFu, 2) && !ok(1, 2, 0xFFFFFFFFu) && !ok(1, 0xFFFFFF00u, 0x200u));                // first + count wraps
+    EXPECT(!ok(TRC_MORPH_MAX_TARGETS + 1, 0, 10) && !ok(0xFFFFFFFFu, 0, 10));                              // beyond the cap: refused before a delta is read
+    for (const float bad : {NAN, INFINITY, -INFINITY}) {
+        t[2 * 10 + 7].dv[1] = bad;                                                                         // target 2, vertex 7
+        EXPECT(!ok(3, 0, 10) && ok(2, 0, 10) && ok(1, 0, 30 - 3));                                         // (one target over the first 27 records)
+        t[2 * 10 + 7].dv[1] = -1.0f;
+        t[29].dn[2] = bad;                                                                                 // the last component of the table
+        EXPECT(!ok(3, 0, 10) && ok(3, 0, 9) && ok(1, 0, 29));
+        t[29].dn[2] = 0.0f;
+    }
+    {   // the cap itself is legal: 1024 targets over one vertex
+        std::vector<trc_morph_delta> wide(TRC_MORPH_MAX_TARGETS);
+        std::memset(wide.data(), 0, wide.size() * sizeof(trc_morph_delta));
+        EXPECT(trc_morph_table_check(wide.data(), TRC_MORPH_MAX_TARGETS, 999, 1, n_vertex) == nullptr);
+    }
+    // weights, and their compaction into the active list
+    std::vector<trc_morph_active> active(5, trc_morph_active{7u, 1.0f});
+    const float w[6] = {0.5f, 0.0f, -0.25f, -0.0f, 1e-45f, 0.0f};
+    EXPECT(trc_morph_weights_check(nullptr, 6, 6, active) != nullptr && active.empty());
+    EXPECT(trc_morph_weights_check(w, 5, 6, active) != nullptr && trc_morph_weights_check(w, 6, 5, active) != nullptr && active.empty());      // off by one, either way
+    EXPECT(trc_morph_weights_check(w, 6, 6, active) == nullptr && active.size() == 3);
+    EXPECT(active.size() == 3 && active[0].target == 0 && active[0].weight == 0.5f && active[1].target == 2 && active[1].weight == -0.25f &&
+           active[2].target == 4 && active[2].weight == 1e-45f);                                           // a denormal is not zero; +0 and -0 are
+    const float zeros[4] = {0.0f, -0.0f, 0.0f, -0.0f};
+    EXPECT(trc_morph_weights_check(zeros, 4, 4, active) == nullptr && active.empty());                     // all zero: accepted, nothing active
+    for (const float bad : {NAN, INFINITY, -INFINITY}) {
+        float v[6]; std::memcpy(v, w, sizeof v); v[5] = bad;
+        EXPECT(trc_morph_weights_check(v, 6, 6, active) != nullptr && active.empty());
+        EXPECT(trc_morph_weights_check(v, 5, 5, active) == nullptr && active.size() == 3);                 // ... which lies past the weights that are read
+    }
+    std::vector<float> all(TRC_MORPH_MAX_TARGETS, 0.125f);
+    EXPECT(trc_morph_weights_check(all.data(), TRC_MORPH_MAX_TARGETS, TRC_MORPH_MAX_TARGETS, active) == nullptr && active.size() == TRC_MORPH_MAX_TARGETS &&
+           active.back().target == TRC_MORPH_MAX_TARGETS - 1);
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -295,6 +344,7 @@ int main(int argc, char** argv) {
     sppm_pass();
     pose_tables();
     skin_tables();
+    morph_tables();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

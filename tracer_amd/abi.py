@@ -116,6 +116,13 @@ TRC_SKIN_MAX_BONES = 65536
 SKIN_LDS_BONES = 256                # csrc/skin_check.hpp kSkinLdsBones: palettes up to this size are staged in LDS (tests/test_skin_cpu.py)
 
 
+class MorphDelta(C.Structure):      # trc_morph_delta: one target's delta for one bound vertex (trc_morph_bind), 24 B packed
+    _fields_ = [("dv", C.c_float * 3), ("dn", C.c_float * 3)]
+
+
+TRC_MORPH_MAX_TARGETS = 1024
+
+
 class TextureInfo(C.Structure):
     _fields_ = [("type", C.c_int32), ("textureIndex", C.c_uint32), ("_pad", C.c_uint32 * 2), ("albedo", float3)]
 
@@ -275,7 +282,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32, TreeCost: 32,
+                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32, TreeCost: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -292,6 +299,7 @@ DEVICE_SYMBOLS = [
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
+    "trc_morph_bind", "trc_morph_vertices",
     "trc_rebuild_tree", "trc_tree_cost",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)

@@ -190,6 +190,12 @@ struct trc_ctx {
     trc_skin_influence* d_skin_influences = nullptr;
     uint32_t skin_first = 0, skin_count = 0, skin_max_bone = 0;
     trc_skin_bone* d_skin_palette = nullptr; size_t skin_palette_bytes = 0;
+    // trc_morph_bind / trc_morph_vertices (trc_refit.hip): the binding's delta table, target-major (target k, vertex morph_first + i:
+    // d_morph_deltas[k * morph_count + i]; null: no binding), and the active list of the last morph (morph_check.hpp: 8 B per target
+    // with a non-zero weight); freed with the scene (trc_refit_free), kept by a rebuild.  A morph reads d_rest and counts as a pose does
+    trc_morph_delta* d_morph_deltas = nullptr;
+    uint32_t morph_first = 0, morph_count = 0, morph_targets = 0;
+    void* d_morph_active = nullptr; size_t morph_active_bytes = 0;
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -504,9 +510,9 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
     if (!ctx->h_readback) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_readback, kReadbackBytes, hipHostMallocDefault));
     return TRC_OK;
 }
-trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices left for later (ks.root_box, the overflow count)
+trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices / trc_morph_vertices left for later (ks.root_box, the overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
-void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, binding and the refit maps (no-op when absent)
+void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, skin and morph bindings and the refit maps (no-op when absent)
 void trc_refit_free_maps(trc_ctx* ctx);            // trc_refit.hip: the refit maps alone (parent, level table, record map): the tree's topology changed (trc_rebuild_tree)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
 
@@ -528,10 +534,10 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
 //                       A device tree upload that fails after that releases what it allocated of the NEW scene too, before it returns
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
-//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
+//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
 //   kSceneTreeRebuilt   trc_rebuild_tree, once the new tree is on its way into the blob: no vertex moved, but a tie in t may now resolve to
 //                       another primitive.  The block costs stay; the refit maps go (trc_refit_free_maps: the next update, pose or skin makes
-//                       them for the new topology); vertex and index arrays, rest copy, binding and triangle materials stay
+//                       them for the new topology); vertex and index arrays, rest copy, bindings and triangle materials stay
 enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneTreeRebuilt };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:

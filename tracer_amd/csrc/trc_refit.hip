@@ -26,12 +26,20 @@
 //   k_skin_vertices_lds the palette's read columns staged in LDS once per workgroup, which then takes 256 bound vertices at a time
 //   k_skin_vertices     the columns gathered from memory: palettes beyond kSkinLdsBones (skin_check.hpp), and knob skin_no_lds
 // Both blend the four bones' matrices entry by entry and put the REST vertex under the blend with k_pose_vertices' expressions.
+//
+// trc_morph_vertices adds weighted deltas to the rest vertex: trc_morph_bind has left n_targets deltas per bound vertex on the device,
+// target-major, the call brings the frame's weights, compacted by the host into the active list (morph_check.hpp), and in front of the
+// same tail runs one of
+//   k_morph_vertices       one thread per bound vertex: rest + the active targets' weighted deltas, in the list's order
+//   k_morph_skin_vertices  with a palette: one thread per vertex of the hull of the morph and the skin binding; the morph where the
+//                          vertex is morph-bound, then the skin's arithmetic on those values where it is skin-bound (columns gathered)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "dev_trileaf.hpp"
+#include "morph_check.hpp"
 #include "pose_ranges.hpp"
 #include "skin_check.hpp"
 #include "trc_ctx.hpp"
@@ -234,8 +242,8 @@ __device__ __forceinline__ float skin_blend(const float4& w, float a0, float a1,
     return s012 + p3;
 }
 template <class Col>
-__device__ __forceinline__ void skin_vertex(const float4* __restrict__ rest, float4* __restrict__ verts, uint32_t v, const uint4& bone, const float4& w,
-                                            const Col& col, uint32_t* __restrict__ overflows) {
+__device__ __forceinline__ void skin_vertex(const float4& __restrict__ a, const float4& __restrict__ b, float4* __restrict__ verts, uint32_t v, const uint4& bone, const float4& w,
+                                            const Col& col, uint32_t* __restrict__ overflows) {      // a, b: x y z nx | ny nz u v, the values to skin
     float4 m[7];
 #pragma unroll
     for (int c = 0; c < 7; ++c) {
@@ -246,7 +254,6 @@ __device__ __forceinline__ void skin_vertex(const float4* __restrict__ rest, flo
         m[c].w = 0.0f;
     }
     const float4 c0 = m[0], c1 = m[1], c2 = m[2], c3 = m[3], n0 = m[4], n1 = m[5], n2 = m[6];
-    const float4 a = rest[2 * (size_t)v], b = rest[2 * (size_t)v + 1];              // x y z nx | ny nz u v
     const float x = ((c0.x * a.x + c1.x * a.y) + c2.x * a.z) + c3.x;
     const float y = ((c0.y * a.x + c1.y * a.y) + c2.y * a.z) + c3.y;
     const float z = ((c0.z * a.x + c1.z * a.y) + c2.z * a.z) + c3.z;
@@ -273,7 +280,7 @@ __device__ __forceinline__ void skin_bound_vertex(const KSkin& p, uint32_t i, ui
     const uint4 wb = p.influences[2 * (size_t)i + 1];
     if (bone.x >= n_bones || bone.y >= n_bones || bone.z >= n_bones || bone.w >= n_bones) return;
     const float4 w = make_float4(__uint_as_float(wb.x), __uint_as_float(wb.y), __uint_as_float(wb.z), __uint_as_float(wb.w));
-    skin_vertex(p.rest, p.verts, v, bone, w, col, p.overflows);
+    skin_vertex(p.rest[2 * (size_t)v], p.rest[2 * (size_t)v + 1], p.verts, v, bone, w, col, p.overflows);
 }
 // gathered: one thread per bound vertex, the columns straight from the palette in memory (a palette is small: L2-resident)
 __global__ void __launch_bounds__(256) k_skin_vertices(KSkin p) {
@@ -299,6 +306,104 @@ __global__ void __launch_bounds__(256) k_skin_vertices_lds(KSkin p) {
     }
 }
 constexpr uint32_t kSkinWorkgroupsPerCu = 2;     // of the staged kernel: 512 threads of a CU's 2048, each workgroup ~4 batches on 0.5 M vertices
+
+// ---- the morph: verts[first + i] = rest[first + i] + the weighted deltas of the active targets, in the operation order of
+// include/tracer_abi.h: for every entry (k, w) of the active list in order and every component c, p = w * d[k][i].c; acc.c = acc.c + p.
+// Every statement is one operation (the exact build compiles without contraction).  The list index is the same in every lane, so an
+// entry is one scalar 8-byte load; a delta is three 8-byte loads (a record is 24 bytes from a hipMalloc base: 8-byte aligned)
+struct KMorph {
+    const float4* rest; float4* verts; uint32_t n_vertex;
+    const float2* deltas; uint32_t n_targets, first, count;      // deltas: 3 x 8 B per bound vertex and target, target-major
+    const uint2* active; uint32_t n_active;                      // trc_morph_active: the target, the weight's bits
+    uint32_t* overflows;
+};
+__device__ __forceinline__ void morph_add(float (&acc)[6], float w, const float2& d0, const float2& d1, const float2& d2) {
+    const float p0 = w * d0.x;
+    const float p1 = w * d0.y;
+    const float p2 = w * d1.x;
+    const float p3 = w * d1.y;
+    const float p4 = w * d2.x;
+    const float p5 = w * d2.y;
+    acc[0] = acc[0] + p0;
+    acc[1] = acc[1] + p1;
+    acc[2] = acc[2] + p2;
+    acc[3] = acc[3] + p3;
+    acc[4] = acc[4] + p4;
+    acc[5] = acc[5] + p5;
+}
+// a, b: bound vertex i's rest values in, its morphed values out.  The six sums are serial chains by definition; the loop takes four
+// entries at a time and loads their twelve 8-byte words before the first add, so that the memory latency of four targets overlaps --
+// the order of the operations is the list's all the same.  false: an entry names a target the table does not hold (the host made
+// the list from the binding's own n_targets: never)
+__device__ __forceinline__ bool morph_bound_vertex(const KMorph& p, uint32_t i, float4& a, float4& b) {
+    float acc[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+    const float2* __restrict__ deltas = p.deltas;
+    const uint2* __restrict__ active = p.active;
+    uint32_t j = 0;
+    for (; j + 4u <= p.n_active; j += 4u) {
+        const uint2 e0 = active[j], e1 = active[j + 1], e2 = active[j + 2], e3 = active[j + 3];
+        if (e0.x >= p.n_targets || e1.x >= p.n_targets || e2.x >= p.n_targets || e3.x >= p.n_targets) return false;
+        const float2* q0 = deltas + 3 * ((size_t)e0.x * p.count + i);      // (64 bits: n_targets * count passes 2^32)
+        const float2* q1 = deltas + 3 * ((size_t)e1.x * p.count + i);
+        const float2* q2 = deltas + 3 * ((size_t)e2.x * p.count + i);
+        const float2* q3 = deltas + 3 * ((size_t)e3.x * p.count + i);
+        const float2 d00 = q0[0], d01 = q0[1], d02 = q0[2];
+        const float2 d10 = q1[0], d11 = q1[1], d12 = q1[2];
+        const float2 d20 = q2[0], d21 = q2[1], d22 = q2[2];
+        const float2 d30 = q3[0], d31 = q3[1], d32 = q3[2];
+        morph_add(acc, __uint_as_float(e0.y), d00, d01, d02);
+        morph_add(acc, __uint_as_float(e1.y), d10, d11, d12);
+        morph_add(acc, __uint_as_float(e2.y), d20, d21, d22);
+        morph_add(acc, __uint_as_float(e3.y), d30, d31, d32);
+    }
+    for (; j < p.n_active; ++j) {
+        const uint2 e = active[j];
+        if (e.x >= p.n_targets) return false;
+        const float2* q = deltas + 3 * ((size_t)e.x * p.count + i);
+        const float2 d0 = q[0], d1 = q[1], d2 = q[2];
+        morph_add(acc, __uint_as_float(e.y), d0, d1, d2);
+    }
+    a = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    b = make_float4(acc[4], acc[5], b.z, b.w);
+    return true;
+}
+__device__ __forceinline__ void morph_store(float4* __restrict__ verts, uint32_t v, const float4& a, const float4& b, uint32_t* __restrict__ overflows) {
+    verts[2 * (size_t)v] = a;
+    verts[2 * (size_t)v + 1] = b;
+    if (!(fabsf(a.x) <= 1e37f) || !(fabsf(a.y) <= 1e37f) || !(fabsf(a.z) <= 1e37f))      // the caller's contract, broken: counted, never an index
+        __hip_atomic_fetch_add(overflows, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// morph only: one thread per bound vertex
+__global__ void __launch_bounds__(256) k_morph_vertices(KMorph p) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.count) return;
+    const uint32_t v = p.first + i;
+    if (v >= p.n_vertex) return;                                    // (the host refused such a table)
+    float4 a = p.rest[2 * (size_t)v], b = p.rest[2 * (size_t)v + 1];              // x y z nx | ny nz u v
+    if (!morph_bound_vertex(p, i, a, b)) return;
+    morph_store(p.verts, v, a, b, p.overflows);
+}
+// the morph and the skin on top: one thread per vertex of [hull_first, hull_first + hull_count), the hull of the two bindings' ranges.
+// A vertex of the morph binding is morphed, a vertex of the skin binding then skinned from what it has by then -- the morphed values
+// or the rest values; a vertex in neither is not written.  s.first / s.count: the skin binding's own range
+__global__ void __launch_bounds__(256) k_morph_skin_vertices(KMorph p, KSkin s, uint32_t hull_first, uint32_t hull_count) {
+    const uint32_t h = blockIdx.x * 256u + threadIdx.x;
+    if (h >= hull_count) return;
+    const uint32_t v = hull_first + h;
+    if (v >= p.n_vertex) return;
+    const uint32_t im = v - p.first, is = v - s.first;             // (below `first`: wraps to a value >= count)
+    const bool morphed = im < p.count, skinned = is < s.count;
+    if (!morphed && !skinned) return;
+    float4 a = p.rest[2 * (size_t)v], b = p.rest[2 * (size_t)v + 1];
+    if (morphed && !morph_bound_vertex(p, im, a, b)) return;
+    if (!skinned) { morph_store(p.verts, v, a, b, p.overflows); return; }
+    const uint4 bone = s.influences[2 * (size_t)is];
+    const uint4 wb = s.influences[2 * (size_t)is + 1];
+    if (bone.x >= s.n_bones || bone.y >= s.n_bones || bone.z >= s.n_bones || bone.w >= s.n_bones) return;
+    const float4 w = make_float4(__uint_as_float(wb.x), __uint_as_float(wb.y), __uint_as_float(wb.z), __uint_as_float(wb.w));
+    const float4* palette = s.palette;
+    skin_vertex(a, b, s.verts, v, bone, w, [palette](uint32_t bn, int c) { return palette[8 * (size_t)bn + c]; }, s.overflows);
+}
 
 // the maps themselves (refit_prepare frees what a failure leaves half made)
 trc_status refit_make_maps(trc_ctx* ctx) {
@@ -376,12 +481,22 @@ trc_status rest_ensure(trc_ctx* ctx, const char* what) {
     return TRC_OK;
 }
 
-// ... and behind their vertices, on the context's stream: [the pose kernel,] the records of the triangles that name a vertex of
-// [first, first + count), every box of the tree, the root box on its way back.  pose_total != 0: trc_pose_vertices, whose sorted
-// table of n_poses ranges (pose_total vertices in all) is in d_pose_table; [first, first + count) is then the hull of its ranges --
-// a triangle of the hull that no range touched gets the bits it had, and keeps its material.  skin_bones != 0: trc_skin_vertices, whose
-// palette of skin_bones bones is in d_skin_palette; [first, first + count) is then the binding's range
-trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_poses = 0, uint32_t pose_total = 0, uint32_t skin_bones = 0) {
+// ... and behind their vertices, on the context's stream: [the kernel in front,] the records of the triangles that name a vertex of
+// [first, first + count), every box of the tree, the root box on its way back.  Where the range is a hull, a triangle of the hull that
+// no vertex of the call touched gets the bits it had, and keeps its material.  RefitFront names the kernel in front:
+//   kFrontNone   trc_update_vertices: the vertices came by copy
+//   kFrontPose   trc_pose_vertices, whose sorted table of n_poses ranges (pose_total vertices in all) is in d_pose_table; [first,
+//                first + count) is the hull of its ranges
+//   kFrontSkin   trc_skin_vertices, whose palette of n_bones bones is in d_skin_palette; [first, first + count) is the binding's range
+//   kFrontMorph  trc_morph_vertices, whose active list of n_active entries is in d_morph_active; [first, first + count) is the morph
+//                binding's range, or with n_bones != 0 (the palette in d_skin_palette) the hull of the morph and the skin binding
+struct RefitFront {
+    enum Kind { kFrontNone, kFrontPose, kFrontSkin, kFrontMorph } kind = kFrontNone;
+    uint32_t n_poses = 0, pose_total = 0;
+    uint32_t n_bones = 0;
+    uint32_t n_active = 0;
+};
+trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, const RefitFront& front = RefitFront{}) {
     const DScene& sc = ctx->ks.sc;
     hipEvent_t e0 = ctx->refit_ev[0], e1 = ctx->refit_ev[1];
     hipStream_t st = ctx->stream;
@@ -392,23 +507,37 @@ trc_status refit_run(trc_ctx* ctx, uint32_t first, uint32_t count, uint32_t n_po
     p.root = ctx->d_refit_root;
     const dim3 b256(256);
     HIP_TRY(ctx, hipEventRecord(e0, st));
-    if (pose_total)
-        hipLaunchKernelGGL(k_pose_vertices, dim3((pose_total + 255) / 256), b256, 0, st, reinterpret_cast<const float4*>(ctx->d_rest),
-                           reinterpret_cast<float4*>(ctx->d_verts), ctx->n_vertex, ctx->d_pose_table, n_poses, pose_total,
-                           reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord);
-    if (skin_bones) {
-        KSkin k{};
+    const uint32_t batches = (uint32_t)(((size_t)count + 255) / 256);
+    KSkin k{};
+    if (front.n_bones) {      // a skin, or the skin on top of a morph: the skin binding's own range
         k.rest = reinterpret_cast<const float4*>(ctx->d_rest); k.verts = reinterpret_cast<float4*>(ctx->d_verts); k.n_vertex = ctx->n_vertex;
-        k.influences = reinterpret_cast<const uint4*>(ctx->d_skin_influences); k.first = first; k.count = count;
-        k.palette = reinterpret_cast<const float4*>(ctx->d_skin_palette); k.n_bones = skin_bones;
+        k.influences = reinterpret_cast<const uint4*>(ctx->d_skin_influences); k.first = ctx->skin_first; k.count = ctx->skin_count;
+        k.palette = reinterpret_cast<const float4*>(ctx->d_skin_palette); k.n_bones = front.n_bones;
         k.overflows = reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord;
-        const uint32_t batches = (uint32_t)(((size_t)count + 255) / 256);
-        if (skin_bones <= kSkinLdsBones && !ctx->knobs.skin_no_lds)
+    }
+    if (front.kind == RefitFront::kFrontPose)
+        hipLaunchKernelGGL(k_pose_vertices, dim3((front.pose_total + 255) / 256), b256, 0, st, reinterpret_cast<const float4*>(ctx->d_rest),
+                           reinterpret_cast<float4*>(ctx->d_verts), ctx->n_vertex, ctx->d_pose_table, front.n_poses, front.pose_total,
+                           reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord);
+    if (front.kind == RefitFront::kFrontSkin) {
+        if (front.n_bones <= kSkinLdsBones && !ctx->knobs.skin_no_lds)
             hipLaunchKernelGGL(k_skin_vertices_lds, dim3(std::min(batches, kSkinWorkgroupsPerCu * (uint32_t)ctx->cu_count)), b256, 0, st, k);
         else
             hipLaunchKernelGGL(k_skin_vertices, dim3(batches), b256, 0, st, k);
     }
-    const bool counted = pose_total != 0 || skin_bones != 0;
+    if (front.kind == RefitFront::kFrontMorph) {
+        KMorph m{};
+        m.rest = reinterpret_cast<const float4*>(ctx->d_rest); m.verts = reinterpret_cast<float4*>(ctx->d_verts); m.n_vertex = ctx->n_vertex;
+        m.deltas = reinterpret_cast<const float2*>(ctx->d_morph_deltas); m.n_targets = ctx->morph_targets;
+        m.first = ctx->morph_first; m.count = ctx->morph_count;
+        m.active = static_cast<const uint2*>(ctx->d_morph_active); m.n_active = front.n_active;
+        m.overflows = reinterpret_cast<uint32_t*>(ctx->d_refit_root) + kPoseCountWord;
+        if (front.n_bones)
+            hipLaunchKernelGGL(k_morph_skin_vertices, dim3(batches), b256, 0, st, m, k, first, count);
+        else
+            hipLaunchKernelGGL(k_morph_vertices, dim3(batches), b256, 0, st, m);
+    }
+    const bool counted = front.kind != RefitFront::kFrontNone;
     hipLaunchKernelGGL(k_refit_triangles, dim3((sc.n_triangles + 255) / 256), b256, 0, st, ctx->d_verts, ctx->d_idx, sc.n_triangles, first, count,
                        reinterpret_cast<float4*>(ctx->d_blob + sc.off_tripos), reinterpret_cast<float4*>(ctx->d_blob + sc.off_triattr));
     if (ctx->knobs.refit_single) {
@@ -470,6 +599,9 @@ void trc_refit_free(trc_ctx* ctx) {
     (void)hipFree(ctx->d_skin_influences); (void)hipFree(ctx->d_skin_palette);
     ctx->d_skin_influences = nullptr; ctx->d_skin_palette = nullptr; ctx->skin_palette_bytes = 0;
     ctx->skin_first = ctx->skin_count = ctx->skin_max_bone = 0;
+    (void)hipFree(ctx->d_morph_deltas); (void)hipFree(ctx->d_morph_active);
+    ctx->d_morph_deltas = nullptr; ctx->d_morph_active = nullptr; ctx->morph_active_bytes = 0;
+    ctx->morph_first = ctx->morph_count = ctx->morph_targets = 0;
     ctx->d_verts = nullptr; ctx->d_idx = nullptr; ctx->n_vertex = 0;
 }
 
@@ -521,7 +653,9 @@ trc_status trc_pose_vertices(trc_ctx* ctx, const trc_pose* poses, uint32_t n_pos
     TRC_TRY(rest_ensure(ctx, "rest vertices (trc_pose_vertices)"));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_pose_table, table.data(), table.size() * sizeof(trc_pose), st));
     trc_scene_changed(ctx, kSceneVerticesMoved);
-    return refit_run(ctx, hull_first, hull_count, n_poses, total);
+    RefitFront front;
+    front.kind = RefitFront::kFrontPose; front.n_poses = n_poses; front.pose_total = total;
+    return refit_run(ctx, hull_first, hull_count, front);
 }
 
 trc_status trc_skin_bind(trc_ctx* ctx, const trc_skin_influence* influences, uint32_t first, uint32_t count) {
@@ -558,7 +692,60 @@ trc_status trc_skin_vertices(trc_ctx* ctx, const trc_skin_bone* bones, uint32_t 
     TRC_TRY(rest_ensure(ctx, "rest vertices (trc_skin_vertices)"));
     TRC_TRY(trc_copy_to_device(ctx, ctx->d_skin_palette, bones, bytes, ctx->stream));
     trc_scene_changed(ctx, kSceneVerticesMoved);
-    return refit_run(ctx, ctx->skin_first, ctx->skin_count, 0, 0, n_bones);
+    RefitFront front;
+    front.kind = RefitFront::kFrontSkin; front.n_bones = n_bones;
+    return refit_run(ctx, ctx->skin_first, ctx->skin_count, front);
+}
+
+trc_status trc_morph_bind(trc_ctx* ctx, const trc_morph_delta* deltas, uint32_t n_targets, uint32_t first, uint32_t count) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_morph_bind: no scene");
+    const bool empty = trc_morph_table_empty(n_targets, count);
+    if (!empty && (ctx->ks.sc.n_triangles == 0 || !ctx->d_verts)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_morph_bind: the scene has no triangles");
+    if (const char* why = trc_morph_table_check(deltas, n_targets, first, count, ctx->n_vertex)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_morph_bind: ") + why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevBuf table;
+    if (!empty) {
+        const size_t bytes = (size_t)n_targets * count * sizeof(trc_morph_delta);      // (size_t: the product passes 2^32)
+        TRC_TRY(table.alloc(ctx, bytes, "delta table (trc_morph_bind)"));
+        TRC_TRY(trc_copy_to_device(ctx, table.p, deltas, bytes, st));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));      // a morph still in flight reads the table that goes
+    (void)hipFree(ctx->d_morph_deltas);
+    ctx->d_morph_deltas = static_cast<trc_morph_delta*>(table.release());
+    ctx->morph_first = empty ? 0u : first; ctx->morph_count = empty ? 0u : count; ctx->morph_targets = empty ? 0u : n_targets;
+    return TRC_OK;
+}
+
+trc_status trc_morph_vertices(trc_ctx* ctx, const float* weights, uint32_t n_weights, const trc_skin_bone* bones, uint32_t n_bones) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_morph_vertices: no scene");
+    if (!ctx->d_morph_deltas || !ctx->d_verts) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_morph_vertices: no binding (trc_morph_bind)");
+    std::vector<trc_morph_active> active;
+    if (const char* why = trc_morph_weights_check(weights, n_weights, ctx->morph_targets, active)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_morph_vertices: ") + why);
+    uint32_t first = ctx->morph_first, count = ctx->morph_count;
+    if (n_bones != 0) {
+        if (!ctx->d_skin_influences) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_morph_vertices: n_bones > 0 without a skin binding (trc_skin_bind)");
+        if (const char* why = trc_skin_palette_check(bones, n_bones, ctx->skin_max_bone)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string("trc_morph_vertices: ") + why);
+        // the hull of the two ranges; both end within n_vertex, so neither sum wraps
+        const uint32_t end = std::max(first + count, ctx->skin_first + ctx->skin_count);
+        first = std::min(first, ctx->skin_first);
+        count = end - first;
+    }
+    TRC_TRY(refit_begin(ctx, "trc_morph_vertices"));
+    const size_t list_bytes = active.size() * sizeof(trc_morph_active), palette_bytes = (size_t)n_bones * sizeof(trc_skin_bone);
+    TRC_TRY(trc_grow_buffer(ctx, ctx->d_morph_active, ctx->morph_active_bytes, list_bytes, "trc_morph_vertices: hipMalloc active list"));
+    if (n_bones != 0) TRC_TRY(trc_grow_buffer(ctx, ctx->d_skin_palette, ctx->skin_palette_bytes, palette_bytes, "trc_morph_vertices: hipMalloc bone palette"));
+    TRC_TRY(rest_ensure(ctx, "rest vertices (trc_morph_vertices)"));
+    if (list_bytes != 0) TRC_TRY(trc_copy_to_device(ctx, ctx->d_morph_active, active.data(), list_bytes, ctx->stream));
+    if (n_bones != 0) TRC_TRY(trc_copy_to_device(ctx, ctx->d_skin_palette, bones, palette_bytes, ctx->stream));
+    trc_scene_changed(ctx, kSceneVerticesMoved);
+    RefitFront front;
+    front.kind = RefitFront::kFrontMorph; front.n_active = (uint32_t)active.size(); front.n_bones = n_bones;
+    return refit_run(ctx, first, count, front);
 }
 
 trc_status trc_download_vertices(trc_ctx* ctx, trc_TriangleVertex* out, uint32_t first, uint32_t count) {

@@ -126,6 +126,8 @@ def _load(path, hooks=False):
     L.trc_debug_pose_overflows.argtypes = [vp, C.POINTER(u32)]
     L.trc_skin_bind.argtypes = [vp, vp, u32, u32]
     L.trc_skin_vertices.argtypes = [vp, C.POINTER(abi.SkinBone), u32]
+    L.trc_morph_bind.argtypes = [vp, vp, u32, u32, u32]
+    L.trc_morph_vertices.argtypes = [vp, vp, u32, C.POINTER(abi.SkinBone), u32]
     L.trc_rebuild_tree.argtypes = [vp, u32]
     L.trc_tree_cost.argtypes = [vp, C.POINTER(abi.TreeCost)]
     if hooks:
@@ -299,15 +301,37 @@ class Tracer:
             palette = make_bones(palette)
         self._check(self._L.trc_skin_vertices(self._h, palette if len(palette) else None, len(palette)), "trc_skin_vertices")
 
+    def morph_bind(self, deltas, first=0):
+        """trc_morph_bind: `deltas` is (n_targets, count, 6) float32 -- deltas[k, i] is target k's (dx, dy, dz, dnx, dny, dnz) for
+        vertex first + i.  One morph binding per scene: a second call replaces it, an empty array removes it.  Moves no vertex."""
+        d = np.ascontiguousarray(deltas, dtype=np.float32)
+        if d.ndim != 3 or d.shape[2] != 6:
+            raise ValueError(f"morph_bind: deltas of shape {d.shape}, not (n_targets, count, 6)")
+        self._check(self._L.trc_morph_bind(self._h, d.ctypes.data if d.size else None, d.shape[0], first, d.shape[1]), "trc_morph_bind")
+
+    def morph_vertices(self, weights, bones=None):
+        """trc_morph_vertices: every vertex of the morph binding becomes its REST vertex plus the weighted deltas of the targets whose
+        weight is not zero, in ascending order of the target.  `bones` (what skin_vertices takes) puts the skin of skin_bind on top of
+        the morphed values in the same call.  The tree is refitted in place; the accumulator is not cleared."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        buf = w if w.size else np.zeros(1, np.float32)            # an empty array is n_weights == 0, never NULL
+        if bones is None or len(bones) == 0:
+            bones, n_bones = None, 0
+        else:
+            if not (isinstance(bones, C.Array) and bones._type_ is abi.SkinBone):
+                bones = make_bones(bones)
+            n_bones = len(bones)
+        self._check(self._L.trc_morph_vertices(self._h, buf.ctypes.data, w.size, bones, n_bones), "trc_morph_vertices")
+
     def pose_overflows(self):
-        """posed positions of the last pose_vertices, or skinned positions of the last skin_vertices (whichever call came last), that
-        came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
+        """posed positions of the last pose_vertices, skinned positions of the last skin_vertices or final positions of the last
+        morph_vertices (whichever call came last) that came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
         n = C.c_uint32(0)
         self._check(self._L.trc_debug_pose_overflows(self._h, C.byref(n)), "trc_debug_pose_overflows")
         return n.value
 
     def refit_ms(self):
-        """device time in ms of the kernels of the last update_vertices, pose_vertices or skin_vertices (trc_debug_refit_ms)"""
+        """device time in ms of the kernels of the last update_vertices, pose_vertices, skin_vertices or morph_vertices (trc_debug_refit_ms)"""
         ms = C.c_float(0)
         self._check(self._L.trc_debug_refit_ms(self._h, C.byref(ms)), "trc_debug_refit_ms")
         return ms.value
