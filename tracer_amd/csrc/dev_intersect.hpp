@@ -106,24 +106,40 @@ TRC_DEV void load_node(const SceneRef& S, uint32_t idx, float4& q0, float4& q1, 
 }
 
 // ---------------------------------------------------------------- boxes
-TRC_DEV bool box_hit(F3 mn, F3 mx, const Ray& r, float rx, float ry) {      // AABB.hh:73-90
+// TRC_WALK_TRIM: the two short forms of the walk's always-executed code, the box tests here and the record of an accepted square
+// (square_hit_test).  Same bits as the long forms on every input; they pay where instructions are what is short -- the LDS-resident
+// kernels (config 2: 15.09 -> 14.85 ms per launch, profiles/r21/) -- and cost traceVolume on a tree read from memory 1.8 % through the
+// register allocation of k_render_pwg<2> (either form alone does: profiles/r21/other_configs.txt), with nothing gained on configs 3 / 4:
+// the translation units of the trees read from memory (trc_render_mem*.hip) set it to 0 and keep the reference's forms.
+#ifndef TRC_WALK_TRIM
+#define TRC_WALK_TRIM 1
+#endif
+// range_t.x of every Scene::hit walk (Render.hh:139).  The short box tests are written for a POSITIVE lower bound:
+//   tmin = fmaxf(tmin, kRangeTMin) is >= kRangeTMin > 0 and never NaN (fmaxf returns its non-NaN operand), so
+//   tmax < 0 implies tmax < tmin: the reference's `|| tmax < 0` (AABB.hh:86,106) cannot change the answer, and with
+//   a NaN tmax both forms say "hit"; and `tmin < 0 ? tmax : tmin` (AABB.hh:110) is always tmin.
+// The compiler cannot see the first (it emits v_max_f32 0, tmin in front of the compare, once per box); the lower
+// bound is therefore this constant and no parameter: a caller with range_t.x <= 0 needs the long form.
+constexpr float kRangeTMin = FLT_MIN;
+static_assert(!TRC_WALK_TRIM || kRangeTMin > 0, "box_hit / box_hit_t drop `|| tmax < 0` and `tmin < 0 ? tmax : tmin`: valid for a positive lower bound only");
+TRC_DEV bool box_hit(F3 mn, F3 mx, const Ray& r, float ry) {      // AABB.hh:73-90
     F3 ts = (mn - r.o) * r.inv;
     F3 te = (mx - r.o) * r.inv;
     float tmin = fmax3(fminf(ts.x, te.x), fminf(ts.y, te.y), fminf(ts.z, te.z));
     float tmax = fmin3(fmaxf(ts.x, te.x), fmaxf(ts.y, te.y), fmaxf(ts.z, te.z));
-    tmin = fmaxf(tmin, rx);
+    tmin = fmaxf(tmin, kRangeTMin);
     tmax = fminf(tmax, ry);
-    return !(tmax < tmin || tmax < 0);
+    return !(tmax < tmin || (!TRC_WALK_TRIM && tmax < 0));
 }
-TRC_DEV bool box_hit_t(F3 mn, F3 mx, const Ray& r, float rx, float ry, float& t) {   // AABB.hh:92-112
+TRC_DEV bool box_hit_t(F3 mn, F3 mx, const Ray& r, float ry, float& t) {   // AABB.hh:92-112
     F3 ts = (mn - r.o) * r.inv;
     F3 te = (mx - r.o) * r.inv;
     float tmin = fmax3(fminf(ts.x, te.x), fminf(ts.y, te.y), fminf(ts.z, te.z));
     float tmax = fmin3(fmaxf(ts.x, te.x), fmaxf(ts.y, te.y), fmaxf(ts.z, te.z));
-    tmin = fmaxf(tmin, rx);
+    tmin = fmaxf(tmin, kRangeTMin);
     tmax = fminf(tmax, ry);
-    if (tmax < tmin || tmax < 0) return false;
-    t = (tmin < 0) ? tmax : tmin;
+    if (tmax < tmin || (!TRC_WALK_TRIM && tmax < 0)) return false;
+    t = (!TRC_WALK_TRIM && tmin < 0) ? tmax : tmin;
     return true;
 }
 
@@ -235,7 +251,7 @@ TRC_DEV bool sphere_hit_test(const SceneRef& S, uint32_t index, const Ray& ray, 
 }
 
 // uv of a point on square `index` (Square.hh: the two quotients of the accepted test).  The render kernels take it from here at
-// shading time, and only when a texture consumes it: rec.p holds a and b exactly (set_comp below), so the value is the one the
+// shading time, and only when a texture consumes it: rec.p holds a and b exactly (below), so the value is the one the
 // test would have stored -- and the two divisions leave the traversal loop.
 TRC_DEV F2 square_uv(const SceneRef& S, uint32_t index, F3 p) {
     const uint32_t* sq = S.small_base + S.off_squares + index * kSquareDwords;
@@ -267,6 +283,24 @@ TRC_DEV bool square_hit_test(const SceneRef& S, uint32_t index, const Ray& ray, 
         rec.uv.y = (b - rg.z) / (rg.w - rg.z);
     }
     rec.t = t;
+#if TRC_WALK_TRIM
+    // The record as selects: set_comp() with a per-lane axis compiles to nested divergent branches, and the bounce rays of a
+    // wavefront meet walls of all three orientations, so a wavefront ran every one of them (k_render_dense: 89 instructions with
+    // 14 exec-mask saves and 8 branches, where these are 22 in a straight line: profiles/r21/walk_trim_isa.txt).  Square.hh:98-108
+    // builds a one-hot gn, check_face() tests dot(ray.d, gn) <= 0, then gn = sn.  Every ray that reaches a leaf is finite
+    // (trav_begin), so the two other products of that dot are +-0 and the dot is ray.d[axis_k] -- not 0 here, or t would have
+    // been infinite or NaN.  The kept face is (+1 at axis_k, +0, +0), the flipped one its negation: -1 and two NEGATIVE zeros,
+    // which the replay memo's same-side test and later products can see.
+    const bool front = comp(ray.d, axis_k) <= 0;
+    const float one = front ? 1.0f : -1.0f, zero = front ? 0.0f : -0.0f;
+    rec.sn = f3(axis_k == 0 ? one : zero, axis_k == 1 ? one : zero, axis_k >= 2 ? one : zero);
+    rec.gn = rec.sn;
+    // p: value_k, a and b at their axes, a permutation of 0, 1, 2 in every scene a builder makes (otherwise the last writer of
+    // k, i, j still wins, and a component that nobody names holds value_k where set_comp() left it alone)
+    rec.p = f3(axis_j == 0 ? b : (axis_i == 0 ? a : value_k),
+               axis_j == 1 ? b : (axis_i == 1 ? a : value_k),
+               axis_j >= 2 ? b : (axis_i >= 2 ? a : value_k));
+#else
     F3 gn = f3(0);
     set_comp(gn, axis_k, 1.0f);
     rec.gn = gn;
@@ -275,6 +309,7 @@ TRC_DEV bool square_hit_test(const SceneRef& S, uint32_t index, const Ray& ray, 
     set_comp(rec.p, axis_k, value_k);
     set_comp(rec.p, axis_i, a);
     set_comp(rec.p, axis_j, b);
+#endif
     ry = t;
     rec.PDF = kx.y;
     rec.material = __float_as_uint(kx.w);
@@ -499,7 +534,7 @@ TRC_DEV bool trav_begin(const F3 root_min, const F3 root_max, const Ray& ray, co
     // without it NaN-ignoring min/max make such a ray "hit" every box of the tree
     const float finite_probe = fabsf(ray.o.x) + fabsf(ray.o.y) + fabsf(ray.o.z) + fabsf(ray.d.x) + fabsf(ray.d.y) + fabsf(ray.d.z);
     if (!(finite_probe < __builtin_inff())) return false;
-    if (!box_hit(root_min, root_max, ray, FLT_MIN, test_t)) return false;
+    if (!box_hit(root_min, root_max, ray, test_t)) return false;
     tv.tag = kTagInterior << kTagIndexBits;   // root
     return true;
 }
@@ -520,7 +555,7 @@ TRC_DEV bool trav_begin(const F3 root_min, const F3 root_max, const Ray& ray, co
 // after the walk leaves such a winner's record alone.
 template <bool STATS, bool EAGER_UV, bool VOL, int DEFER = 0>
 TRC_DEV bool trav_test_leaf(const SceneRef& S, const Ray& ray, HitRec& rec, Trav& tv, uint32_t tag, TravCounters& cnt) {
-    const float rx = FLT_MIN;
+    const float rx = kRangeTMin;
     const uint32_t type = tag >> kTagIndexBits, index = tag & kTagIndexMask;
     bool ok;
     HitRec scratch;                          // DEFER: what the tests write here is read by nobody (dead code), except ...
@@ -560,8 +595,8 @@ TRC_DEV void trav_build_record(const SceneRef& S, const Ray& ray, HitRec& rec, c
     TravCounters nocount;
     float ry = tv.win_ry;
     if (type == 3u) triangle_record(S, index, ray, rec);
-    else if (type == 1u) { square_hit_test<EAGER_UV>(S, index, ray, FLT_MIN, ry, rec); if (!EAGER_UV) { rec.uv.x = 0; rec.uv.y = 0; } }
-    else if (type == 0u) { sphere_hit_test<EAGER_UV>(S, index, ray, FLT_MIN, ry, rec); if (!EAGER_UV) { rec.uv.x = 0; rec.uv.y = 0; } }
+    else if (type == 1u) { square_hit_test<EAGER_UV>(S, index, ray, kRangeTMin, ry, rec); if (!EAGER_UV) { rec.uv.x = 0; rec.uv.y = 0; } }
+    else if (type == 0u) { sphere_hit_test<EAGER_UV>(S, index, ray, kRangeTMin, ry, rec); if (!EAGER_UV) { rec.uv.x = 0; rec.uv.y = 0; } }
     else if (DEFER != 2) cube_hit_test<false, VOL>(S, index, ray, ry, rec, nocount);
     rec.tag = tv.win_tag;
 }
@@ -590,7 +625,6 @@ TRC_DEV void trav_build_record(const SceneRef& S, const Ray& ray, HitRec& rec, c
 template <bool ALL_LDS, bool STATS, bool ANY, bool EAGER_UV, bool VOL = false, bool HYB = false, int DEFER = 0>
 TRC_DEV void trav_iter(const SceneRef& S, const Ray& ray, HitRec& rec, const float test_t, Trav& tv,
                        uint32_t* stack, uint32_t* lvstack, TravCounters& cnt) {
-    const float rx = FLT_MIN;
 #ifndef TRC_DESCEND_MIN_LDS
 #define TRC_DESCEND_MIN_LDS 1
 #endif
@@ -609,8 +643,8 @@ TRC_DEV void trav_iter(const SceneRef& S, const Ray& ray, HitRec& rec, const flo
         if (STATS) cnt.n_descend++;
         ProfScope<STATS> scope(cnt, kProfDescend);
         float t_left = tv.ry, t_right = tv.ry;
-        const bool left_test = box_hit_t(f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), ray, rx, tv.ry, t_left);
-        const bool right_test = box_hit_t(f3(q1.z, q1.w, q2.x), f3(q2.y, q2.z, q2.w), ray, rx, tv.ry, t_right);
+        const bool left_test = box_hit_t(f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), ray, tv.ry, t_left);
+        const bool right_test = box_hit_t(f3(q1.z, q1.w, q2.x), f3(q2.y, q2.z, q2.w), ray, tv.ry, t_right);
         if (left_test || right_test) {
             const uint32_t tagL = __float_as_uint(q3.z), tagR = __float_as_uint(q3.w);
             const bool left_first = t_left < t_right;            // Render.hh:174 (literal, also when only one hit)
@@ -668,7 +702,6 @@ TRC_DEV uint32_t scene_occluded_free(const SceneRef& S, const F3 root_min, const
     Trav tb;
     TravCounters nocount;
     if (!trav_begin<false>(root_min, root_max, ray, test_t, tb, nocount)) return kOccludedNo;
-    const float rx = FLT_MIN;
     constexpr uint32_t kRoot = kTagInterior << kTagIndexBits;
     uint32_t cur0 = kRoot, sp = 0;
     bool found = false, ask_reference = false;
@@ -707,8 +740,8 @@ TRC_DEV uint32_t scene_occluded_free(const SceneRef& S, const F3 root_min, const
             // exactly t == range_t.y loses to its sibling, whose box did NOT pass, and is never visited.  Kept literally.
             auto expand = [&](const float4& q0, const float4& q1, const float4& q2, const float4& q3) {
                 float t_left = test_t, t_right = test_t;
-                const bool l = box_hit_t(f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), ray, rx, test_t, t_left);
-                const bool r = box_hit_t(f3(q1.z, q1.w, q2.x), f3(q2.y, q2.z, q2.w), ray, rx, test_t, t_right);
+                const bool l = box_hit_t(f3(q0.x, q0.y, q0.z), f3(q0.w, q1.x, q1.y), ray, test_t, t_left);
+                const bool r = box_hit_t(f3(q1.z, q1.w, q2.x), f3(q2.y, q2.z, q2.w), ray, test_t, t_right);
                 const uint32_t tagL = __float_as_uint(q3.z), tagR = __float_as_uint(q3.w);
                 if (l && r) { give(tagL); give(tagR); }
                 else if (l || r) give(t_left < t_right ? tagL : tagR);

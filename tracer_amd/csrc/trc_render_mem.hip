@@ -9,6 +9,9 @@
 #ifndef TRC_FAST_UNARY
 #define TRC_FAST_UNARY 1
 #endif
+#ifndef TRC_WALK_TRIM
+#define TRC_WALK_TRIM 0      // dev_intersect.hpp: the short forms cost traceVolume 1.8 % on a tree read from memory and gain nothing here
+#endif
 #include "trc_render_kernels.hpp"
 
 TRC_RENDER_NS_BEGIN
