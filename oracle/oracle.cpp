@@ -1,7 +1,8 @@
 // oracle.cpp -- CPU oracle: scalar restatement of RT_Metal's path-tracing hot path.
 //
-// TEST INFRASTRUCTURE ONLY (see oracle.h).  PARITY PIN STATUS: unpinned beyond PCG32 and the
-// Sobol' tables (tests/test_sobol.py) -- the reference has no tests/goldens for this path and cannot be built here.
+// TEST INFRASTRUCTURE ONLY (see oracle.h).  PARITY PIN STATUS: everything from Math.hh down to Scene::hit and Material::F / PDF / S_F is held
+// bit for bit to the reference's own headers compiled on the host (_ref/libmetal_ref.so, tests/test_reference_pin.py); PCG32 and the Sobol'
+// tables to the reference's files; tracePath / traceMIS / traceVolume, kernelPathTracing, the SPPM pass and the media are not pinned yet.
 //
 // Conventions that resolve what Metal leaves unspecified (the HIP path uses the same ones):
 //   * all arithmetic is IEEE-754 binary32, no FMA contraction (-ffp-contract=off);
@@ -9,7 +10,9 @@
 //   * dot(a,b) = a.x*b.x + a.y*b.y + a.z*b.z (left to right); length = sqrt(dot);
 //     normalize(v) = v * (1 / length(v)); distance(a,b) = length(a-b);
 //   * M * (v,0) = (c0*v.x + c1*v.y) + c2*v.z;  M * (p,1) = that + c3;
-//   * min/max ignore NaN (fminf/fmaxf), Appendix B-10 of SURVEY.md;
+//   * min/max ignore NaN (fminf/fmaxf), Appendix B-10 of SURVEY.md; max3(a,b,c) = max(max(a,b),c), min3 likewise, and
+//     clamp(x,lo,hi) = min(max(x,lo),hi) (Metal fixes neither the nesting nor what a NaN or a signed-zero tie gives; written
+//     down because oracle/metal_shim/metal_stdlib, the stand-in the reference's headers compile against, has to choose the same);
 //   * sin/cos/exp/log/pow/asin/acos/atan2 come from include/trc_detmath.h
 //     (or glibc with -DORACLE_USE_LIBM, used to bound the statistical effect);
 //   * constructor/function arguments are evaluated left to right (clang behaviour);
@@ -40,6 +43,13 @@ void meshlight_ref_tables(const float* tri_v, uint32_t n_tri, const uint32_t* tr
 void meshlight_ref_sample(const float* tri_v, const uint32_t* alias, const uint32_t* tri, const float* pdfA, uint32_t n_lights,
                           const uint32_t* draws, const float* pos, size_t n, uint32_t* tri_out, float* out);
 }
+
+// Teeth of tests/test_reference_pin.py, a developer step (oracle/README.md): -DORC_PIN_TEETH=n builds the oracle with ONE token of one
+// function changed, to count how many of the pin's inputs notice.  0, the default and the only committed build, changes nothing.
+#ifndef ORC_PIN_TEETH
+#define ORC_PIN_TEETH 0
+#endif
+#define PIN_TOOTH(n, as_written, one_token_off) ((ORC_PIN_TEETH == (n)) ? (one_token_off) : (as_written))
 
 namespace {
 
@@ -286,6 +296,24 @@ inline float Erf(float x) {
     return sign * y;
 }
 
+// Math.hh:15-49 (pbrt's; only Ray.hh's OffsetRayOrigin, which nothing calls, uses them)
+inline uint32_t FloatToBits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+inline float BitsToFloat(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+inline float NextFloatUp(float v) {
+    if (std::isinf(v) && v > 0.f) return v;
+    if (v == -0.f) v = 0.f;
+    uint32_t ui = FloatToBits(v);
+    if (v >= 0) ++ui; else --ui;
+    return BitsToFloat(ui);
+}
+inline float NextFloatDown(float v) {
+    if (std::isinf(v) && v < 0.f) return v;
+    if (v == 0.f) v = -0.f;
+    uint32_t ui = FloatToBits(v);
+    if (v > 0) --ui; else ++ui;
+    return BitsToFloat(ui);
+}
+
 // ---------------------------------------------------------------- Ray / HitRecord
 // Ray.hh:10-33
 struct Ray {
@@ -420,7 +448,7 @@ inline bool sphere_hit_test(const trc_Sphere& s, const Ray& ray, V2& range_t, Hi
     float t_min = range_t.x, t_max = range_t.y;
     float root = sqrtf(discriminant);
     float temp = (-half_b - root) / a;
-    if (temp < t_max && temp > t_min) {
+    if (PIN_TOOTH(1, temp < t_max, temp <= t_max) && temp > t_min) {
         rec.t = temp;
         rec.p = ray.pointAt(rec.t);
         rec.gn = (rec.p - center) / s.radius;
@@ -455,7 +483,7 @@ inline float square_areaPDF(const trc_Square& q) { return 1 / square_area(q); }
 inline bool square_hit_test(const trc_Square& q, const Ray& ray, V2& range_t, HitRecord& rec) {
     float t = (q.value_k - ray.origin[q.axis_k]) / ray.direction[q.axis_k];
     if (std::isinf(t) || std::isnan(t)) return false;
-    if (t < range_t.x || t > range_t.y) return false;
+    if (t < range_t.x || PIN_TOOTH(2, t > range_t.y, t >= range_t.y)) return false;
     float a = ray.origin[q.axis_i] + t * ray.direction[q.axis_i];
     if (a < q.range_i.x || a > q.range_i.y) return false;
     float b = ray.origin[q.axis_j] + t * ray.direction[q.axis_j];
@@ -506,7 +534,7 @@ inline bool cube_hit_test(const trc_Cube& cube, const Ray& ray, V2& range_t, Hit
     _record._r = _ray;                               // Cube.hh:30-31
     _record._t = _record.t;
     _record.t = length(ray.origin - _record.p);     // distance(ray.origin, p)
-    if (_record.t >= range_t.y) return false;
+    if (PIN_TOOTH(3, _record.t >= range_t.y, _record.t > range_t.y)) return false;
     range_t.y = _record.t;
     _record.material = cube.material;
     _record.modelMatrix = &cube.model_matrix;        // Cube.hh:39
@@ -529,7 +557,7 @@ inline bool triangle_hit_test(const trc_TriangleVertex& A, const trc_TriangleVer
     float invDet = 1 / det;
     V3 tvec = ori - v0;
     float u = dot(tvec, pvec) * invDet;
-    if (u < 0 || u > 1) return false;
+    if (u < 0 || PIN_TOOTH(4, u > 1, u >= 1)) return false;
     V3 qvec = cross(tvec, v0v1);
     float v = dot(dir, qvec) * invDet;
     if (v < 0 || (u + v) > 1) return false;
@@ -687,6 +715,26 @@ inline V3 CosineSampleHemisphere(const V2& u) {
 inline float PowerHeuristic(int nf, float fPdf, int ng, float gPdf) {
     float f = nf * fPdf, g = ng * gPdf;
     return (f * f) / (f * f + g * g);
+}
+// Sampling.hh:120-123
+inline V2 UniformSampleTriangle(const V2& u) {
+    float su0 = sqrtf(u[0]);
+    return V2{1 - su0, u[1] * su0};
+}
+// Triangle.hh:87-128 (nothing on the reference's path calls them; its mesh is no light)
+inline float triangle_area(const trc_TriangleVertex& A, const trc_TriangleVertex& B, const trc_TriangleVertex& C) {
+    const V3 p0 = v3a(A.v), p1 = v3a(B.v), p2 = v3a(C.v);
+    return 0.5f * length(cross(p1 - p0, p2 - p0));
+}
+inline void triangle_sample(const trc_TriangleVertex& A, const trc_TriangleVertex& B, const trc_TriangleVertex& C, const V2& uu,
+                            LightSampleRecord& lsr) {
+    V2 b = UniformSampleTriangle(uu);
+    const V3 p0 = v3a(A.v), p1 = v3a(B.v), p2 = v3a(C.v);
+    V3 p = b[0] * p0 + b[1] * p1 + (1 - b[0] - b[1]) * p2;
+    V3 n = normalize(cross(p1 - p0, p2 - p0));
+    lsr.p = p;
+    lsr.n = n;
+    lsr.areaPDF = 1 / triangle_area(A, B, C);
 }
 // Sampling.hh:148-203
 inline float CosTheta(const V3& w) { return w.z; }
@@ -1004,7 +1052,7 @@ struct PlasticMaterial {
     }
     V3 S_F(const V3& wo, V3& wi, const V2& uu, float& pdf) const {
         V2 _uu_ = uu;
-        if (_uu_[0] < 0.5f) { _uu_[0] *= 2; return kd * matte.S_F(wo, wi, _uu_, pdf); }
+        if (PIN_TOOTH(5, _uu_[0] < 0.5f, _uu_[0] <= 0.5f)) { _uu_[0] *= 2; return kd * matte.S_F(wo, wi, _uu_, pdf); }
         _uu_[0] -= 0.5f; _uu_[0] *= 2.0f;
         return ks * micro.S_F(wo, wi, _uu_, pdf);
     }
@@ -2456,5 +2504,193 @@ void orc_sppm_download(const orc_sppm* s, trc_CameraRecord* cam, trc_PhotonRecor
     }
 }
 float orc_photon_hash(const float idx[3], float hash_scale) { return ph_hash(v3a(idx), hash_scale, (float)kHashN); }
+
+// ---------------------------------------------------------------- pin_api.h, family orc_*: thin batch wrappers over the functions above
+}  // extern "C"
+namespace {
+inline void put3(float* o, V3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+inline V2 v2a(const float* p) { return V2{p[0], p[1]}; }
+inline Ray raw_ray(const pin_ray& in) {     // direction as given: Ray::Ray would normalise it
+    Ray r;
+    r.origin = v3a(in.origin);
+    r.direction = v3a(in.direction);
+    return r;
+}
+inline void put_rec(pin_rec& o, bool accepted, float range_y, const HitRecord& r) {
+    o.accepted = accepted ? 1 : 0;
+    o.range_y = range_y;
+    o.t = r.t;
+    put3(o.p, r.p); put3(o.gn, r.gn); put3(o.sn, r.sn);
+    o.uv[0] = r.uv.x; o.uv[1] = r.uv.y;
+    o.material = r.material;
+    o.PDF = r.PDF;
+    o.f = r.f ? 1 : 0;
+}
+template <typename F>
+inline void hit_batch(const pin_ray* rays, size_t n, pin_rec* out, F&& test) {
+    for (size_t i = 0; i < n; ++i) {
+        Ray ray = raw_ray(rays[i]);
+        V2 range_t = v2a(rays[i].range);
+        HitRecord rec;
+        bool ok = test(i, ray, range_t, rec);
+        put_rec(out[i], ok, range_t.y, rec);
+    }
+}
+}  // namespace
+extern "C" {
+
+float orc_literal_probe(float u, float v) { float w = 1.0f - u - v; return w; }
+
+void orc_sphere_hit(const trc_Sphere* prim, size_t n_prim, const pin_ray* rays, size_t n, pin_rec* out) {
+    hit_batch(rays, n, out, [&](size_t i, const Ray& ray, V2& range_t, HitRecord& rec) { return sphere_hit_test(prim[i % n_prim], ray, range_t, rec); });
+}
+void orc_square_hit(const trc_Square* prim, size_t n_prim, const pin_ray* rays, size_t n, pin_rec* out) {
+    hit_batch(rays, n, out, [&](size_t i, const Ray& ray, V2& range_t, HitRecord& rec) { return square_hit_test(prim[i % n_prim], ray, range_t, rec); });
+}
+void orc_cube_hit(const trc_Cube* prim, size_t n_prim, const pin_ray* rays, size_t n, pin_rec* out) {
+    hit_batch(rays, n, out, [&](size_t i, const Ray& ray, V2& range_t, HitRecord& rec) { return cube_hit_test(prim[i % n_prim], ray, range_t, rec, nullptr); });
+}
+void orc_triangle_hit(const trc_TriangleVertex* tri, size_t n_prim, const pin_ray* rays, size_t n, pin_rec* out) {
+    hit_batch(rays, n, out, [&](size_t i, const Ray& ray, V2& range_t, HitRecord& rec) {
+        const trc_TriangleVertex* t = tri + 3 * (i % n_prim);
+        return triangle_hit_test(t[0], t[1], t[2], ray, range_t, rec, nullptr);
+    });
+}
+void orc_aabb_hit(const trc_AABB* box, size_t n_prim, const pin_ray* rays, size_t n, int32_t* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = aabb_hit(box[i % n_prim], raw_ray(rays[i]), v2a(rays[i].range)) ? 1 : 0;
+}
+void orc_aabb_hit_t_n(const trc_AABB* box, size_t n_prim, const pin_ray* rays, size_t n, int32_t* out, float* t_out) {
+    for (size_t i = 0; i < n; ++i) {
+        float t = rays[i].range[1];
+        out[i] = aabb_hit_t(box[i % n_prim], raw_ray(rays[i]), v2a(rays[i].range), t) ? 1 : 0;
+        t_out[i] = t;
+    }
+}
+void orc_aabb_hit_record(const trc_AABB* box, size_t n_prim, const pin_ray* rays, size_t n, pin_rec* out) {
+    hit_batch(rays, n, out, [&](size_t i, const Ray& ray, V2& range_t, HitRecord& rec) { return aabb_hit_record(box[i % n_prim], ray, range_t, rec); });
+}
+void orc_scene_hit(const trc_scene* scene, const trc_ray* rays, size_t n, int any_hit, pin_rec* out) {
+    Scene sc{*scene, nullptr};
+    for (size_t i = 0; i < n; ++i) {
+        Ray ray(v3a(rays[i].origin), v3a(rays[i].direction));
+        HitRecord rec;
+        bool ok = sc.hit(ray, rec, rays[i].tmax, any_hit != 0);
+        put_rec(out[i], ok, 0.0f, rec);
+    }
+}
+void orc_square_sample(const trc_Square* prim, size_t n_prim, const float* u2, const float* pos3, size_t n, float* out8) {
+    for (size_t i = 0; i < n; ++i) {
+        LightSampleRecord lsr;
+        square_sample(prim[i % n_prim], v2a(u2 + 2 * i), v3a(pos3 + 3 * i), lsr);
+        put3(out8 + 8 * i, lsr.p); put3(out8 + 8 * i + 3, lsr.n);
+        out8[8 * i + 6] = lsr.areaPDF;
+        memcpy(out8 + 8 * i + 7, &lsr.material, 4);
+    }
+}
+void orc_triangle_sample(const trc_TriangleVertex* tri, size_t n_prim, const float* u2, size_t n, float* out7) {
+    for (size_t i = 0; i < n; ++i) {
+        const trc_TriangleVertex* t = tri + 3 * (i % n_prim);
+        LightSampleRecord lsr;
+        triangle_sample(t[0], t[1], t[2], v2a(u2 + 2 * i), lsr);
+        put3(out7 + 7 * i, lsr.p); put3(out7 + 7 * i + 3, lsr.n);
+        out7[7 * i + 6] = lsr.areaPDF;
+    }
+}
+void orc_triangle_area(const trc_TriangleVertex* tri, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = triangle_area(tri[3 * i], tri[3 * i + 1], tri[3 * i + 2]);
+}
+void orc_offset_ray_n(const float* p3, const float* n3, size_t n, float* out3) {
+    for (size_t i = 0; i < n; ++i) put3(out3 + 3 * i, offset_ray(v3a(p3 + 3 * i), v3a(n3 + 3 * i)));
+}
+void orc_next_float_up(const float* x, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = NextFloatUp(x[i]); }
+void orc_next_float_down(const float* x, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = NextFloatDown(x[i]); }
+void orc_erf_n(const float* x, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = Erf(x[i]); }
+void orc_erfinv_n(const float* x, size_t n, float* out) { for (size_t i = 0; i < n; ++i) out[i] = ErfInv(x[i]); }
+float orc_gamma(int n) { return gamma_n(n); }
+void orc_cosine_sample_hemisphere_n(const float* u2, size_t n, float* out3) {
+    for (size_t i = 0; i < n; ++i) put3(out3 + 3 * i, CosineSampleHemisphere(v2a(u2 + 2 * i)));
+}
+void orc_concentric_sample_disk(const float* u2, size_t n, float* out2) {
+    for (size_t i = 0; i < n; ++i) { V2 d = ConcentricSampleDisk(v2a(u2 + 2 * i)); out2[2 * i] = d.x; out2[2 * i + 1] = d.y; }
+}
+void orc_uniform_sample_triangle(const float* u2, size_t n, float* out2) {
+    for (size_t i = 0; i < n; ++i) { V2 d = UniformSampleTriangle(v2a(u2 + 2 * i)); out2[2 * i] = d.x; out2[2 * i + 1] = d.y; }
+}
+void orc_power_heuristic_n(int nf, const float* fPdf, int ng, const float* gPdf, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = PowerHeuristic(nf, fPdf[i], ng, gPdf[i]);
+}
+void orc_coordinate_system(const float* a3, size_t n, float* out6) {
+    for (size_t i = 0; i < n; ++i) {
+        V3 b = v3(0), c = v3(0);
+        CoordinateSystem(v3a(a3 + 3 * i), b, c);
+        put3(out6 + 6 * i, b); put3(out6 + 6 * i + 3, c);
+    }
+}
+void orc_spherical_direction(const float* scp, const float* xyz9, size_t n, float* out3) {
+    for (size_t i = 0; i < n; ++i)
+        put3(out3 + 3 * i, SphericalDirection(scp[3 * i], scp[3 * i + 1], scp[3 * i + 2], v3a(xyz9 + 9 * i), v3a(xyz9 + 9 * i + 3), v3a(xyz9 + 9 * i + 6)));
+}
+void orc_phase_hg_n(const float* cosTheta, const float* g, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = PhaseHG(cosTheta[i], g[i]);
+}
+void orc_hg_sample_n(const float* g, const float* wo3, const float* uu2, size_t n, float* out4) {
+    for (size_t i = 0; i < n; ++i) {
+        V3 wi = v3(0);
+        out4[4 * i + 3] = HG_Sample_p(g[i], v3a(wo3 + 3 * i), wi, v2a(uu2 + 2 * i));
+        put3(out4 + 4 * i, wi);
+    }
+}
+void orc_fr_dielectric_n(const float* cosi, const float* eta, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = FrDielectric(cosi[i], eta[i]);
+}
+void orc_fr_conductor_n(const float* cosi, const float* eta3, const float* k3, size_t n, float* out3) {
+    for (size_t i = 0; i < n; ++i) put3(out3 + 3 * i, FrConductor(cosi[i], v3a(eta3 + 3 * i), v3a(k3 + 3 * i)));
+}
+void orc_reflect(const float* wo3, const float* n3, size_t n, float* out3) {
+    for (size_t i = 0; i < n; ++i) put3(out3 + 3 * i, Reflect(v3a(wo3 + 3 * i), v3a(n3 + 3 * i)));
+}
+void orc_refract(const float* wo3, const float* n3, const float* eta, size_t n, float* out4) {
+    for (size_t i = 0; i < n; ++i) {
+        V3 wi = v3(0);
+        out4[4 * i] = Refract(v3a(wo3 + 3 * i), v3a(n3 + 3 * i), eta[i], wi) ? 1.0f : 0.0f;
+        put3(out4 + 4 * i + 1, wi);
+    }
+}
+void orc_material_f_n(const trc_Material* m, const float* wo3, const float* wi3, const float* uv2, const float* uu2, size_t n, float* out4) {
+    for (size_t i = 0; i < n; ++i) {
+        float pdf = 0;
+        put3(out4 + 4 * i, Material_F(*m, v3a(wo3 + 3 * i), v3a(wi3 + 3 * i), v2a(uv2 + 2 * i), pdf, v2a(uu2 + 2 * i)));
+        out4[4 * i + 3] = pdf;
+    }
+}
+void orc_material_pdf_n(const trc_Material* m, const float* wo3, const float* wi3, const float* uu2, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = Material_PDF(*m, v3a(wo3 + 3 * i), v3a(wi3 + 3 * i), v2a(uu2 + 2 * i));
+}
+void orc_material_s_f_n(const trc_Material* m, const float* wo3, const float* uv2, const float* uu2, size_t n, float* out7) {
+    for (size_t i = 0; i < n; ++i) {
+        V3 wi = v3(0); float pdf = 0;
+        V3 f = Material_S_F(*m, v3a(wo3 + 3 * i), wi, v2a(uv2 + 2 * i), v2a(uu2 + 2 * i), pdf);
+        put3(out7 + 7 * i, wi); put3(out7 + 7 * i + 3, f);
+        out7[7 * i + 6] = pdf;
+    }
+}
+void orc_microfacet(int dist, float ax, float ay, const float* wo3, const float* wh3, const float* uu2, size_t n, float* out8) {
+    const Beckmann bk(ax, ay);
+    const TrowbridgeReitz tr(ax, ay);
+    for (size_t i = 0; i < n; ++i) {
+        const V3 wo = v3a(wo3 + 3 * i), wh = v3a(wh3 + 3 * i);
+        const V2 uu = v2a(uu2 + 2 * i);
+        float* o = out8 + 8 * i;
+        if (dist == 0) {
+            o[0] = bk.D(wh); o[1] = bk.G(wo, wh); o[2] = bk.G1(wo); o[3] = bk.PDF(wo, wh);
+            put3(o + 4, bk.sample_wh(wo, uu));
+            o[7] = 0.0f;      // Beckmann::Lambda is private in the reference: not compared
+        } else {
+            o[0] = tr.D(wh); o[1] = tr.G(wo, wh); o[2] = tr.G1(wo); o[3] = tr.PDF(wo, wh);
+            put3(o + 4, tr.sample_wh(wo, uu));
+            o[7] = tr.Lambda(wo);
+        }
+    }
+}
 
 }  // extern "C"

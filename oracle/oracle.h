@@ -6,19 +6,22 @@
  * tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it;
  * the product path (tracer_amd/) never includes, links or calls anything here.
  *
- * PARITY PIN STATUS: the reference ships no tests, golden vectors or fixtures
- * for this path and its Metal/Obj-C++/Swift sources cannot be built or run on
- * Linux.  The only executable pin is PCG32: the reference's own
- * vendored RT_Metal/Tracer/pcg_basic.c compiles here (oracle/_ref) and its
- * outputs are committed as tests/golden/pcg32_kat.json.  Everything else is
- * pinned by analytic known-answer tests and brute-force cross-checks
- * (tests/test_oracle_*.py).  Parity against the reference's actual Metal
- * output is therefore UNPINNED ("parity unpinned" beyond PCG32).
+ * PARITY PIN STATUS (oracle/README.md has the whole of it): the reference ships
+ * no tests or fixtures for this path and its kernels cannot run on Linux, but
+ * its shader headers compile on the host against oracle/metal_shim (oracle/_ref/
+ * libmetal_ref.so).  The primitive tests, the AABB tests, Scene::hit, the light
+ * samplers, Math.hh, Sampling.hh, the Fresnel terms and the lobes below are held
+ * to that library bit for bit (pin_api.h, tests/test_reference_pin.py; recorded
+ * in tests/golden/reference_pin.npz for machines without the reference), PCG32
+ * to the reference's pcg_basic.c.  The integrators, kernelPathTracing, the SPPM
+ * pass and the media are still pinned by analytic known-answer tests and
+ * brute-force cross-checks only (tests/test_oracle_*.py).
  */
 #ifndef ORACLE_H
 #define ORACLE_H
 
 #include "tracer_abi.h"
+#include "pin_api.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -148,6 +151,9 @@ void orc_tonemap(const float* accum_rgba, uint32_t W, uint32_t H, uint8_t* rgba8
 float orc_hg_sample(float g, const float wo[3], const float uu[2], float wi_out[3]);
 float orc_phase_hg(float cosTheta, float g);
 float orc_grid_density(const trc_GridDensityInfo* info, const float* density, const float p[3]);
+
+/* the unit entry points that _ref/libmetal_ref.so has too, as ref_* over the reference's own headers (pin_api.h) */
+PIN_API(orc)
 
 /* deterministic math under test (identity wrappers over trc_detmath.h / libm) */
 float orc_math(int fn, float a, float b);   /* 0 sin 1 cos 2 exp 3 log 4 pow 5 asin 6 acos 7 atan2 */

@@ -339,3 +339,146 @@ class Sppm:
         if getattr(self, "_h", None):
             lib().orc_sppm_destroy(self._h)
             self._h = None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pin_api.h: the unit entry points that exist twice, orc_* here and ref_* in _ref/libmetal_ref.so (the reference's own
+# shader headers compiled on the host).  Pin binds one family; tests/reference_pin_cases.py drives both the same way.
+PIN_RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("direction", np.float32, 3), ("range", np.float32, 2)])
+PIN_REC_DTYPE = np.dtype([("accepted", np.int32), ("range_y", np.float32), ("t", np.float32), ("p", np.float32, 3),
+                          ("gn", np.float32, 3), ("sn", np.float32, 3), ("uv", np.float32, 2), ("material", np.uint32),
+                          ("PDF", np.float32), ("f", np.int32)])
+assert PIN_RAY_DTYPE.itemsize == 32 and PIN_REC_DTYPE.itemsize == 68
+METAL_REF = os.path.join(_HERE, "_ref", "libmetal_ref.so")
+
+
+def pin_rays(origin, direction, lo, hi):
+    r = np.zeros(len(origin), dtype=PIN_RAY_DTYPE)
+    r["origin"], r["direction"] = origin, direction
+    r["range"][:, 0], r["range"][:, 1] = lo, hi
+    return r
+
+
+class Pin:
+    """One family of pin_api.h: Pin() is orc_* of liboracle.so, Pin(ref=True) is ref_* of _ref/libmetal_ref.so."""
+
+    def __init__(self, ref=False):
+        self.prefix = "ref" if ref else "orc"
+        if ref:
+            if not os.path.exists(METAL_REF):
+                raise RuntimeError(f"{METAL_REF} is missing: `make -C oracle` builds it where the reference is present")
+            self.L = C.CDLL(METAL_REF)
+        else:
+            self.L = lib()
+        v, z, i, f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+        sig = {"literal_probe": ([f, f], f), "gamma": ([i], f),
+               "sphere_hit": [v, z, v, z, v], "square_hit": [v, z, v, z, v], "cube_hit": [v, z, v, z, v], "triangle_hit": [v, z, v, z, v],
+               "aabb_hit": [v, z, v, z, v], "aabb_hit_t_n": [v, z, v, z, v, v], "aabb_hit_record": [v, z, v, z, v],
+               "scene_hit": [C.POINTER(abi.Scene), v, z, i, v],
+               "square_sample": [v, z, v, v, z, v], "triangle_sample": [v, z, v, z, v], "triangle_area": [v, z, v],
+               "offset_ray_n": [v, v, z, v], "next_float_up": [v, z, v], "next_float_down": [v, z, v], "erf_n": [v, z, v], "erfinv_n": [v, z, v],
+               "cosine_sample_hemisphere_n": [v, z, v], "concentric_sample_disk": [v, z, v], "uniform_sample_triangle": [v, z, v],
+               "power_heuristic_n": [i, v, i, v, z, v], "coordinate_system": [v, z, v], "spherical_direction": [v, v, z, v],
+               "phase_hg_n": [v, v, z, v], "hg_sample_n": [v, v, v, z, v],
+               "fr_dielectric_n": [v, v, z, v], "fr_conductor_n": [v, v, v, z, v], "reflect": [v, v, z, v], "refract": [v, v, v, z, v],
+               "material_f_n": [C.POINTER(abi.Material), v, v, v, v, z, v], "material_pdf_n": [C.POINTER(abi.Material), v, v, v, z, v],
+               "material_s_f_n": [C.POINTER(abi.Material), v, v, v, z, v], "microfacet": [i, f, f, v, v, v, z, v]}
+        self._fn = {}
+        for name, s in sig.items():
+            fn = getattr(self.L, f"{self.prefix}_{name}")
+            fn.argtypes, fn.restype = (s[0], s[1]) if isinstance(s, tuple) else (s, None)
+            self._fn[name] = fn
+
+    @staticmethod
+    def _f(a, width=None):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert width is None or (a.ndim == 2 and a.shape[1] == width) or (width == 1 and a.ndim == 1), (a.shape, width)
+        return a
+
+    def literal_probe(self, u, v):
+        return np.float32(self._fn["literal_probe"](float(u), float(v)))
+
+    def gamma(self, n):
+        return np.float32(self._fn["gamma"](int(n)))
+
+    def _prims(self, prims, T):
+        """prims: a ctypes array of T (or of TriangleVertex, 3 per triangle)"""
+        assert isinstance(prims, C.Array) and prims._type_ is T
+        return C.addressof(prims), len(prims)
+
+    def hit(self, kind, prims, rays):
+        """kind: sphere / square / cube / triangle / aabb_record -> PIN_REC_DTYPE array"""
+        T = {"sphere": abi.Sphere, "square": abi.Square, "cube": abi.Cube, "triangle": abi.TriangleVertex, "aabb_record": abi.AABB}[kind]
+        addr, n_prim = self._prims(prims, T)
+        n_prim = n_prim // 3 if kind == "triangle" else n_prim
+        assert rays.dtype == PIN_RAY_DTYPE and rays.flags.c_contiguous and n_prim > 0
+        out = np.zeros(len(rays), dtype=PIN_REC_DTYPE)
+        self._fn["aabb_hit_record" if kind == "aabb_record" else kind + "_hit"](addr, n_prim, rays.ctypes.data, len(rays), out.ctypes.data)
+        return out
+
+    def aabb_hit(self, boxes, rays):
+        addr, n_prim = self._prims(boxes, abi.AABB)
+        out = np.zeros(len(rays), dtype=np.int32)
+        self._fn["aabb_hit"](addr, n_prim, rays.ctypes.data, len(rays), out.ctypes.data)
+        return out
+
+    def aabb_hit_t(self, boxes, rays):
+        addr, n_prim = self._prims(boxes, abi.AABB)
+        out, t = np.zeros(len(rays), dtype=np.int32), np.zeros(len(rays), dtype=np.float32)
+        self._fn["aabb_hit_t_n"](addr, n_prim, rays.ctypes.data, len(rays), out.ctypes.data, t.ctypes.data)
+        return out, t
+
+    def scene_hit(self, scene_view, rays, any_hit=False):
+        assert rays.dtype == RAY_DTYPE and rays.flags.c_contiguous
+        out = np.zeros(len(rays), dtype=PIN_REC_DTYPE)
+        self._fn["scene_hit"](C.byref(scene_view), rays.ctypes.data, len(rays), 1 if any_hit else 0, out.ctypes.data)
+        return out
+
+    def square_sample(self, squares, u, pos):
+        addr, n_prim = self._prims(squares, abi.Square)
+        u, pos = self._f(u, 2), self._f(pos, 3)
+        out = np.zeros((len(u), 8), dtype=np.float32)
+        self._fn["square_sample"](addr, n_prim, u.ctypes.data, pos.ctypes.data, len(u), out.ctypes.data)
+        return out
+
+    def triangle_sample(self, verts, u):
+        addr, nv = self._prims(verts, abi.TriangleVertex)
+        u = self._f(u, 2)
+        out = np.zeros((len(u), 7), dtype=np.float32)
+        self._fn["triangle_sample"](addr, nv // 3, u.ctypes.data, len(u), out.ctypes.data)
+        return out
+
+    def triangle_area(self, verts):
+        addr, nv = self._prims(verts, abi.TriangleVertex)
+        out = np.zeros(nv // 3, dtype=np.float32)
+        self._fn["triangle_area"](addr, nv // 3, out.ctypes.data)
+        return out
+
+    def map(self, name, out_width, *inputs):
+        """the plain array functions: inputs are (n,) or (n, w) float32 arrays in the order of the C signature -> (n, out_width)"""
+        arrs = [self._f(a) for a in inputs]
+        n = len(arrs[0])
+        assert all(len(a) == n for a in arrs)
+        out = np.zeros((n, out_width), dtype=np.float32)
+        self._fn[name](*[a.ctypes.data for a in arrs], n, out.ctypes.data)
+        return out
+
+    def power_heuristic(self, nf, f_pdf, ng, g_pdf):
+        f_pdf, g_pdf = self._f(f_pdf), self._f(g_pdf)
+        out = np.zeros((len(f_pdf), 1), dtype=np.float32)
+        self._fn["power_heuristic_n"](nf, f_pdf.ctypes.data, ng, g_pdf.ctypes.data, len(f_pdf), out.ctypes.data)
+        return out
+
+    def material(self, which, m, *inputs):
+        """which: f (wo wi uv uu -> f[3] pdf), pdf (wo wi uu -> pdf), s_f (wo uv uu -> wi[3] f[3] pdf)"""
+        arrs = [self._f(a) for a in inputs]
+        n = len(arrs[0])
+        out = np.zeros((n, {"f": 4, "pdf": 1, "s_f": 7}[which]), dtype=np.float32)
+        self._fn[f"material_{which}_n"](C.byref(m), *[a.ctypes.data for a in arrs], n, out.ctypes.data)
+        return out
+
+    def microfacet(self, dist, ax, ay, wo, wh, uu):
+        wo, wh, uu = self._f(wo, 3), self._f(wh, 3), self._f(uu, 2)
+        out = np.zeros((len(wo), 8), dtype=np.float32)
+        self._fn["microfacet"](dist, ax, ay, wo.ctypes.data, wh.ctypes.data, uu.ctypes.data, len(wo), out.ctypes.data)
+        return out
