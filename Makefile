@@ -106,7 +106,7 @@ examples/trc_render: examples/trc_render.cpp include/tracer_abi.h $(LIBDIR)/libt
 # preloads the runtime).  GPU code is not covered: GPU AddressSanitizer is not available on this pool.
 ORACLE_SRC := oracle/oracle.cpp oracle/oracle_lbvh.cpp oracle/oracle_sah.cpp tests/envlight_ref/envlight_ref.cpp tests/meshlight_ref/meshlight_ref.cpp
 SAN_SRC := tools/sanitize/driver.cpp $(HOST_SRC) $(ORACLE_SRC)
-SAN_HDR := $(HOST_HDR) oracle/oracle.h tracer_amd/csrc/pose_ranges.hpp tracer_amd/csrc/skin_check.hpp tracer_amd/csrc/morph_check.hpp
+SAN_HDR := $(HOST_HDR) oracle/oracle.h tracer_amd/csrc/pose_ranges.hpp tracer_amd/csrc/skin_check.hpp tracer_amd/csrc/morph_check.hpp tracer_amd/csrc/normals_check.hpp
 build/asan/driver: $(SAN_SRC) $(SAN_HDR)
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=undefined,float-cast-overflow -ffp-contract=off -Iinclude -o $@ $(SAN_SRC) -lpthread

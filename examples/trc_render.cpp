@@ -17,6 +17,9 @@
 //              [--rebuild-ratio R]  beside --spin / --pose / --bend / --morph: after every animation call the tree's cost is read (trc_tree_cost), and
 //                          when (interior + leaf) / root exceeds R times what it was right after the last build, the tree is built anew on the
 //                          device (trc_rebuild_tree, TRC_TREE_SAH); the number of rebuilds is printed at the end
+//              [--normals]  beside --spin / --pose / --bend / --morph: after every animation call the smooth normals of the whole mesh are
+//                          derived anew on the device from the vertices as they now stand (trc_recompute_normals); its device time is printed
+//                          beside the animation call's, and the first call, which builds the adjacency, is timed between two trc_synchronize
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -49,7 +52,7 @@ int main(int argc, char** argv) {
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0;
     double rebuild_ratio = 0.0;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false;
+    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -88,7 +91,8 @@ int main(int argc, char** argv) {
             rebuild_ratio = std::atof(argv[++i]);
             if (!(rebuild_ratio >= 1.0)) { std::fprintf(stderr, "--rebuild-ratio wants a factor of at least 1, not %s\n", argv[i]); return 2; }
         }
-        else if (a == "--mesh-lights") mesh_lights = true;                      // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
+        else if (a == "--normals") normals = true;                              // smooth normals re-derived on the device after every animation call
+        else if (a == "--mesh-lights") mesh_lights = true;                     // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
         else if (a == "--triangle-materials") tri_materials = true;            // --pbrt: per-mesh materials instead of material 19
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -263,6 +267,31 @@ int main(int argc, char** argv) {
         return TRC_OK;
     };
     if (rebuild_ratio != 0.0) CHECK(tree_ratio(&built_cost));
+    // --normals: called after every animation call, over the whole mesh.  The first call of a scene builds the vertex -> corner adjacency
+    // and waits for it: that call is timed on the host with a trc_synchronize on each side, and what it took beyond its own kernels'
+    // device time (trc_debug_refit_ms) is the build.  normals_note: what the animation's own line of output ends with
+    uint32_t normal_calls = 0;
+    std::string normals_note;
+    auto recompute_normals = [&]() {
+        if (!normals) return TRC_OK;
+        trc_status rs;
+        float device_ms = 0.0f;
+        char text[160];
+        if (normal_calls++ == 0) {
+            if ((rs = trc_synchronize(ctx)) != TRC_OK) return rs;
+            const auto n0 = std::chrono::steady_clock::now();
+            if ((rs = trc_recompute_normals(ctx, 0, scene.n_vertex)) != TRC_OK || (rs = trc_synchronize(ctx)) != TRC_OK) return rs;
+            const double first_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - n0).count();
+            if ((rs = trc_debug_refit_ms(ctx, &device_ms)) != TRC_OK) return rs;
+            std::printf("trc_recompute_normals, first call: %.2f ms between two trc_synchronize, %.3f ms of it its kernels, the rest the adjacency build "
+                        "(%.1f KB kept on the device)\n", first_ms, device_ms, (4.0 * (scene.n_vertex + 1.0) + 4.0 * scene.n_index) / 1024.0);
+        } else {
+            if ((rs = trc_recompute_normals(ctx, 0, scene.n_vertex)) != TRC_OK || (rs = trc_debug_refit_ms(ctx, &device_ms)) != TRC_OK) return rs;
+        }
+        std::snprintf(text, sizeof text, ", trc_recompute_normals %.3f ms device", device_ms);
+        normals_note = text;
+        return TRC_OK;
+    };
     if (spin && scene.n_vertex) {
         // the mesh's world-space vertices, turned about the vertical axis through the centre of their box; normals alike
         const std::vector<trc_TriangleVertex> rest(scene.triList, scene.triList + scene.n_vertex);
@@ -282,13 +311,14 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_update_vertices(ctx, turned.data(), 0, scene.n_vertex));
             const double update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
             const std::string name = out + "." + std::to_string(f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("spin %u / %u: trc_update_vertices %.2f ms -> %s\n", f, spin, update_ms, name.c_str());
+            std::printf("spin %u / %u: trc_update_vertices %.2f ms%s -> %s\n", f, spin, update_ms, normals_note.c_str(), name.c_str());
         }
     } else if (spin) {
         std::fprintf(stderr, "--spin turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -315,13 +345,14 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_pose_vertices(ctx, &p, 1));
             const double pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("pose %u / %u: trc_pose_vertices %.2f ms -> %s\n", f, pose, pose_ms, name.c_str());
+            std::printf("pose %u / %u: trc_pose_vertices %.2f ms%s -> %s\n", f, pose, pose_ms, normals_note.c_str(), name.c_str());
         }
     } else if (pose) {
         std::fprintf(stderr, "--pose turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -355,13 +386,14 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_skin_vertices(ctx, bones, 2));
             const double skin_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("bend %u / %u: trc_skin_vertices %.2f ms -> %s\n", f, bend, skin_ms, name.c_str());
+            std::printf("bend %u / %u: trc_skin_vertices %.2f ms%s -> %s\n", f, bend, skin_ms, normals_note.c_str(), name.c_str());
         }
     } else if (bend) {
         std::fprintf(stderr, "--bend bends the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -403,13 +435,14 @@ int main(int argc, char** argv) {
             const auto u0 = std::chrono::steady_clock::now();
             CHECK(trc_morph_vertices(ctx, weights, 2, bones, bend ? 2u : 0u));
             const double morph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
             CHECK(trc_clear_accum(ctx));
             CHECK(trc_render(ctx, &prm));
             CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("morph %u / %u: trc_morph_vertices%s %.2f ms -> %s\n", f, morph, bend ? " under two bones" : "", morph_ms, name.c_str());
+            std::printf("morph %u / %u: trc_morph_vertices%s %.2f ms%s -> %s\n", f, morph, bend ? " under two bones" : "", morph_ms, normals_note.c_str(), name.c_str());
         }
     } else if (morph) {
         std::fprintf(stderr, "--morph morphs the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");

@@ -60,7 +60,9 @@ extern "C" {
  *     added under 13, the number stays: trc_rebuild_tree, trc_tree_cost_t, trc_tree_cost (a fresh tree for a moved mesh from what the
  *     device holds, and a surface-area measure that tells a host when to ask for one; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_morph_delta, TRC_MORPH_MAX_TARGETS, trc_morph_bind, trc_morph_vertices (blend shapes on the
- *     device, alone or under the skin of trc_skin_bind in one call; additions only, nothing existing changed) */
+ *     device, alone or under the skin of trc_skin_bind in one call; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_recompute_normals (smooth vertex normals re-derived on the device from the mesh as it now
+ *     stands; an addition only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -582,7 +584,9 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
  * freed by the next trc_upload_scene* and by trc_destroy.
  * Knob refit_single (trc_debug_set): 0 = one launch per depth of the tree (the default), 1 = one launch with a counter per node. */
 trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices, uint32_t first, uint32_t count);
-/* device time in ms of the kernels of the last trc_update_vertices (record rewrite + refit, without the transfer) */
+/* device time in ms of the kernels of the last trc_update_vertices (record rewrite + refit, without the transfer).  It reports the
+ * device time of the last call of the family -- trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices,
+ * trc_recompute_normals (gather + record rewrite; the one-off adjacency build is not in it) -- whichever came last. */
 trc_status trc_debug_refit_ms(trc_ctx* ctx, float* ms);
 /* Posed geometry: the rigid (or affine) animation of whole objects, where the host has nothing to say per frame but one matrix per
  * object.  Each trc_pose names vertices [first, first + count) of the scene's triList and the two matrices to put them under; the
@@ -718,6 +722,45 @@ typedef struct trc_morph_delta { float dv[3]; float dn[3]; } trc_morph_delta;   
 #define TRC_MORPH_MAX_TARGETS 1024u
 trc_status trc_morph_bind(trc_ctx* ctx, const trc_morph_delta* deltas, uint32_t n_targets, uint32_t first, uint32_t count);
 trc_status trc_morph_vertices(trc_ctx* ctx, const float* weights, uint32_t n_weights, const trc_skin_bone* bones, uint32_t n_bones);
+/* Re-derived normals: a pose puts the stored normal under the caller's inverse transpose, a skin under a blend of inverse transposes
+ * (which is not the inverse transpose of the blend), a morph adds linear deltas, and none of them normalises -- so a bent or morphed
+ * mesh is shaded with normals that are neither unit length nor perpendicular to the surface it now has.  trc_recompute_normals
+ * replaces the normals of vertices [first, first + count) of the scene's CURRENT vertices by area-weighted smooth normals of the mesh
+ * as it now stands, on the device: no vertex crosses the bus.  A host calls it after each update, pose, skin or morph it wants shaded
+ * that way.
+ *  - Definition: binary32, one rounding per operation, no contraction.
+ *    Face term of triangle t with current positions p0, p1, p2 in index-list order: e1 = p1 - p0, e2 = p2 - p0,
+ *        c.x = e1.y*e2.z - e1.z*e2.y,  c.y = e1.z*e2.x - e1.x*e2.z,  c.z = e1.x*e2.y - e1.y*e2.x
+ *    (the e1, e2 and c of TRC_FLAG_MESH_LIGHTS' triangle area; its length is twice the area, which is the weight).
+ *    Vertex sum: the CORNER LIST of vertex v is every k with idxList[k] == v, ascending in k.  s starts as (+0, +0, +0); for every
+ *    corner in that order s = s + c(k / 3), component by component.  A triangle that names v twice contributes twice.
+ *    Side: n_cur is the normal the vertex holds when the call starts, d = (s.x*n_cur.x + s.y*n_cur.y) + s.z*n_cur.z.  If d < 0 then
+ *    s = -s; any other d, zero and NaN included, leaves s alone.  (The winding of a mesh need not agree with its stored normals:
+ *    trc_host_scene_create mirrors z when it places a mesh, which turns every winding round and leaves the ball of
+ *    trc_host_mesh_make_ball wound against its normals at every vertex.  Every pose, skin and morph leaves an interpolated normal
+ *    behind, which is the hemisphere guide this rule needs.)
+ *    Normalise: q = (s.x*s.x + s.y*s.y) + s.z*s.z, l = sqrt(q) correctly rounded.  If l is finite and > 0 then
+ *    n = (s.x / l, s.y / l, s.z / l) with IEEE division.  Otherwise the vertex keeps the bits of the normal it had: a vertex with no
+ *    corner, one with zero-area triangles only, overflow or underflow of q.
+ *  - Vertices outside the range keep their normals, even where a triangle is shared (their positions are read).  Positions, uv, every
+ *    box of the tree, the root box, the rest copy and all bindings are untouched.  trc_download_vertices returns the new normals, and
+ *    the attribute records of every triangle that names a vertex of the range hold them; the triangle's material is kept.
+ *  - After the call everything observable is what trc_update_vertices would have left had the host computed those vertices and passed
+ *    them, with one exception: the rest copy is NOT written.  The next pose, skin or morph derives its normals from rest again, as
+ *    always; a host calls this after each of them.  What survives: triangle materials, textures, environment, camera, density,
+ *    accumulator, RNG texture, the skin and morph bindings, the refit maps.  What is dropped: the G-buffer, the denoiser history and
+ *    the tables of TRC_FLAG_MESH_LIGHTS (they do not depend on normals; one rule for every call that changes vertices).  The launch
+ *    planner's block costs are kept.  Launches kept back for coalescing run first.  Not collective.
+ *  - The first call of a scene builds the vertex -> corner adjacency on the device from the index list it keeps (no index crosses the
+ *    bus) and waits for that once: 4 * (n_vertex + 1) + 4 * n_index bytes of device memory, freed with the scene (every
+ *    trc_upload_scene*, trc_destroy), kept across trc_rebuild_tree, the four animation calls and trc_upload_triangle_materials.  Every
+ *    later call is asynchronous on the context's stream, like trc_render.
+ *  - TRC_ERR_NO_SCENE before any upload.  count == 0 is TRC_OK and changes and drops nothing.  TRC_ERR_INVALID_ARG: first + count > the
+ *    scene's n_vertex, or count > 0 on a scene without triangles.  TRC_ERR_OOM if the adjacency cannot be allocated.  On any error
+ *    nothing has changed and nothing is dropped.  No index on the device comes from anything the host has not checked.
+ * Out of scope: welding of duplicated seam vertices (two vertices at one position are two vertices); smoothing groups and crease angles;
+ * angle weighting; writing the rest copy; fusing into the morph or skin kernel's chain (it is a second, short chain). */
+trc_status trc_recompute_normals(trc_ctx* ctx, uint32_t first, uint32_t count);
 /* A fresh tree for a moved mesh.  A refit keeps the topology of the tree it found: after objects have travelled past each other the boxes
  * near the top overlap and every ray walks more of them.  trc_rebuild_tree builds the tree anew from what the DEVICE holds -- no vertex,
  * index or record crosses the bus, nothing but the tree changes -- and trc_tree_cost (below) tells a host when to ask for it.

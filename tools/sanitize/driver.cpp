@@ -16,6 +16,8 @@
 //   6. the checks of trc_morph_bind and trc_morph_vertices (tracer_amd/csrc/morph_check.hpp, HIP-free as well) on hostile delta tables
 //      and weights: NULL with a non-empty table, a range that wraps, non-finite deltas at the table's end, n_targets beyond the cap, a
 //      weight count off by one, non-finite weights, all-zero weights, and the compaction of the weights into the active list
+//   7. the range check of trc_recompute_normals (tracer_amd/csrc/normals_check.hpp, HIP-free too): the off-by-one, a range that wraps,
+//      the empty range, and the key bits of the adjacency build's sort at the powers of two
 // "build host code under -fsanitize=thread,address".
 #include <cmath>
 #include <cstdio>
@@ -31,6 +33,7 @@
 #include "../../tracer_amd/csrc/pose_ranges.hpp"
 #include "../../tracer_amd/csrc/skin_check.hpp"
 #include "../../tracer_amd/csrc/morph_check.hpp"
+#include "../../tracer_amd/csrc/normals_check.hpp"
 
 static int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "EXPECT failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); ++g_fail; } } while (0)
@@ -277,6 +280,17 @@ static void morph_tables() {
            active.back().target == TRC_MORPH_MAX_TARGETS - 1);
 }
 
+// ---------------------------------------------------------------- trc_recompute_normals' checks
+static void normals_ranges() {
+    EXPECT(trc_normals_range_check(0, 10, 10) == nullptr && trc_normals_range_check(3, 7, 10) == nullptr && trc_normals_range_check(9, 1, 10) == nullptr);
+    EXPECT(trc_normals_range_check(0, 11, 10) != nullptr && trc_normals_range_check(3, 8, 10) != nullptr && trc_normals_range_check(10, 1, 10) != nullptr);      // off by one
+    EXPECT(trc_normals_range_check(0xFFFFFFFFu, 1, 10) != nullptr && trc_normals_range_check(2, 0xFFFFFFFFu, 10) != nullptr);                                   // first + count wraps
+    EXPECT(trc_normals_range_check(0xFFFFFFFFu, 2, 0xFFFFFFFFu) != nullptr && trc_normals_range_check(0xFFFFFFFEu, 1, 0xFFFFFFFFu) == nullptr);
+    EXPECT(trc_normals_range_check(0, 0, 10) == nullptr && trc_normals_range_check(10, 0, 10) == nullptr && trc_normals_range_check(0xFFFFFFFFu, 0, 10) == nullptr);  // empty
+    EXPECT(trc_normals_key_bits(0) == 1 && trc_normals_key_bits(1) == 1 && trc_normals_key_bits(2) == 1 && trc_normals_key_bits(3) == 2);
+    EXPECT(trc_normals_key_bits(256) == 8 && trc_normals_key_bits(257) == 9 && trc_normals_key_bits(2601) == 12 && trc_normals_key_bits(0xFFFFFFFFu) == 32);
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -345,6 +359,7 @@ int main(int argc, char** argv) {
     pose_tables();
     skin_tables();
     morph_tables();
+    normals_ranges();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

@@ -299,7 +299,7 @@ DEVICE_SYMBOLS = [
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
-    "trc_morph_bind", "trc_morph_vertices",
+    "trc_morph_bind", "trc_morph_vertices", "trc_recompute_normals",
     "trc_rebuild_tree", "trc_tree_cost",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)

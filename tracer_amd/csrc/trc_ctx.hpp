@@ -196,6 +196,13 @@ struct trc_ctx {
     trc_morph_delta* d_morph_deltas = nullptr;
     uint32_t morph_first = 0, morph_count = 0, morph_targets = 0;
     void* d_morph_active = nullptr; size_t morph_active_bytes = 0;
+    // trc_recompute_normals (trc_refit.hip): the vertex -> corner adjacency of the index list, made by the first call of a scene --
+    // d_adj_corners[d_adj_offsets[v] .. d_adj_offsets[v + 1]) are the k with d_idx[k] == v, ascending; freed with the scene
+    // (trc_refit_free), kept by a rebuild: the index list never changes.  The call's kernels run between two events of its own
+    uint32_t* d_adj_offsets = nullptr;      // [n_vertex + 1]
+    uint32_t* d_adj_corners = nullptr;      // [n_index]
+    hipEvent_t normals_ev[2] = {nullptr, nullptr};
+    bool normals_timed = false;             // refit_ms is still to be read from normals_ev (trc_debug_refit_ms): this call was the family's last
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -469,6 +476,8 @@ trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32
 size_t trc_dyn_lds_bytes(const trc_ctx* ctx, bool stats);
 // trc_lbvh.hip: stable radix sort of (key, value) pairs on the 24 low key bits, three of the tree builds' 8-bit passes; *result: the buffer that holds it
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result);
+// ... and on the `bits` low key bits (rounded up to whole passes), for keys known to be small: trc_recompute_normals' vertex indices
+void trc_sort_pairs(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, uint32_t bits, int* result);
 uint32_t trc_sort_hist_words(uint32_t n);
 // trc_tonemap's output stage on any W*H RGBA32F plane of the context (the accumulator, the denoised frame); synchronous
 trc_status trc_tonemap_plane(trc_ctx* ctx, const float* plane, uint8_t* rgba8, float* exposure_out);
@@ -512,7 +521,7 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
 }
 trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices / trc_morph_vertices left for later (ks.root_box, the overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
-void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, skin and morph bindings and the refit maps (no-op when absent)
+void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, skin and morph bindings, the normals' adjacency and the refit maps (no-op when absent)
 void trc_refit_free_maps(trc_ctx* ctx);            // trc_refit.hip: the refit maps alone (parent, level table, record map): the tree's topology changed (trc_rebuild_tree)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
 

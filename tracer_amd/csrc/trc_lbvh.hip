@@ -826,6 +826,9 @@ trc_status rebuild_tree(TreeBuild& b) {
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result) {
     *result = radix_sort(st, keys, vals, hist, digit_base, n, 24);
 }
+void trc_sort_pairs(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, uint32_t bits, int* result) {
+    *result = radix_sort(st, keys, vals, hist, digit_base, n, bits);
+}
 uint32_t trc_sort_hist_words(uint32_t n) { return 256u * ((n + kSortTile - 1) / kSortTile); }
 
 // the steps are the list at the top of this file; what the device finds wrong with the leaf records (fit_boxes) is found when the old scene has gone

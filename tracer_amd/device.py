@@ -128,6 +128,7 @@ def _load(path, hooks=False):
     L.trc_skin_vertices.argtypes = [vp, C.POINTER(abi.SkinBone), u32]
     L.trc_morph_bind.argtypes = [vp, vp, u32, u32, u32]
     L.trc_morph_vertices.argtypes = [vp, vp, u32, C.POINTER(abi.SkinBone), u32]
+    L.trc_recompute_normals.argtypes = [vp, u32, u32]
     L.trc_rebuild_tree.argtypes = [vp, u32]
     L.trc_tree_cost.argtypes = [vp, C.POINTER(abi.TreeCost)]
     if hooks:
@@ -323,6 +324,14 @@ class Tracer:
             n_bones = len(bones)
         self._check(self._L.trc_morph_vertices(self._h, buf.ctypes.data, w.size, bones, n_bones), "trc_morph_vertices")
 
+    def recompute_normals(self, first=0, count=None):
+        """trc_recompute_normals: the normals of the current vertices [first, first + count) become area-weighted smooth normals of the
+        mesh as it now stands, computed on the device; count None: up to the end of the scene's vertex list.  No position moves and the
+        rest copy is not written: call it after each update, pose, skin or morph.  The accumulator is not cleared."""
+        if count is None:
+            count = max(self._n_vertex - first, 0)
+        self._check(self._L.trc_recompute_normals(self._h, first, count), "trc_recompute_normals")
+
     def pose_overflows(self):
         """posed positions of the last pose_vertices, skinned positions of the last skin_vertices or final positions of the last
         morph_vertices (whichever call came last) that came out non-finite or beyond 1e37 (trc_debug_pose_overflows)"""
@@ -331,7 +340,8 @@ class Tracer:
         return n.value
 
     def refit_ms(self):
-        """device time in ms of the kernels of the last update_vertices, pose_vertices, skin_vertices or morph_vertices (trc_debug_refit_ms)"""
+        """device time in ms of the kernels of the last update_vertices, pose_vertices, skin_vertices, morph_vertices or recompute_normals
+        (trc_debug_refit_ms)"""
         ms = C.c_float(0)
         self._check(self._L.trc_debug_refit_ms(self._h, C.byref(ms)), "trc_debug_refit_ms")
         return ms.value
