@@ -1,6 +1,8 @@
 """The cases of tests/test_gpu_light_oracle.py: scenes, maps, the launch each case asks for, and the oracle's frame of each (cached: a
 frame does not depend on the launch shape, so the shapes of one scene share it).  tests/test_oracle_lights.py runs the same cases
-through the oracle alone and checks that they reach every branch of the oracle's traceMISLight.  No GPU is touched here."""
+through the oracle alone and checks that they reach every branch of the oracle's traceMISLight.  Below them: the enumeration and the
+cases of the kernel census (tests/test_gpu_kernel_census.py), and the scenes, cameras and primary-hit prediction of the replay matrix
+(tests/test_gpu_primary_replay.py; tests/test_replay_scenes.py checks both on the CPU).  No GPU is touched here."""
 import os
 import re
 import sys
@@ -28,8 +30,8 @@ _SCENES, _ORACLE = {}, {}
 class SceneSet:
     """a scene, its camera for the W x H frame, the per-triangle materials (or None) and the images (or [])"""
 
-    def __init__(self, scene, cam, tri=None, images=()):
-        self.scene, self.view, self.cam, self.tri, self.images = scene, scene.view, cam, tri, list(images)
+    def __init__(self, scene, cam, tri=None, images=(), view=None):
+        self.scene, self.view, self.cam, self.tri, self.images = scene, view if view is not None else scene.view, cam, tri, list(images)
 
 
 def _random_images(view, rng, sizes=((13, 7), (64, 64), (1, 9), (32, 5))):
@@ -46,14 +48,19 @@ def _random_images(view, rng, sizes=((13, 7), (64, 64), (1, 9), (32, 5))):
     return imgs
 
 
-def cornell(residence, tex=False, random_materials=True, lamp19=False):
+def cornell(residence, tex=False, random_materials=True, lamp19=False, checker=False, tri_materials=None):
     """Cornell + the 48-triangle ball (the whole tree in LDS) or the 1104-triangle one (read from memory); every triangle a random
     material of the whole table, in which entry 8 is made a Plastic and entry 9 a second, dimmer emitter.  random_materials=False: no
     array, every triangle is material 19 (the kernels that do not read a triangle's material run); lamp19 then makes entry 19 an emitter,
-    so that the mesh is a light without an array"""
-    key = ("cornell", residence, tex, random_materials, lamp19)
+    so that the mesh is a light without an array; checker makes every cube's material a checker texture (its colour reads rec.uv:
+    tests/test_gpu_lds_fit.py), over the image if there is one -- the cubes' materials are 0, 19 and 2, so without an array the mesh's
+    triangles are checkered with them.  "tiny": the 12-triangle ball (6 of them with area), the largest whose workgroup k_render_dense
+    still holds 24 of per CU (its LDS is the 6592 bytes of trc_render_config.hpp; the 48-triangle ball's 9408 bytes are refused the dense
+    kernel), with tri_materials = the array of its materials: replay_camera sees its triangles 1 and 6"""
+    key = ("cornell", residence, tex, random_materials, lamp19, checker, tri_materials)
     if key not in _SCENES:
-        mesh = host.Mesh.ball(4, 6, 0.1) if residence == "lds" else host.Mesh.ball(24, 24, 1.0)
+        mesh = {"lds": (4, 6, 0.1), "mem": (24, 24, 1.0), "tiny": (2, 3, 0.1)}[residence]
+        mesh = host.Mesh.ball(*mesh)
         sc = host.HostScene(abi.SCENE_CORNELL_MESH, mesh)
         v = sc.view
         v.materials[PLASTIC_SLOT].type = abi.MAT_PLASTIC
@@ -65,7 +72,14 @@ def cornell(residence, tex=False, random_materials=True, lamp19=False):
             v.materials[19].textureInfo.albedo.x, v.materials[19].textureInfo.albedo.y, v.materials[19].textureInfo.albedo.z = 3.0, 2.5, 2.0
         rng = np.random.default_rng(100 + (residence == "mem"))
         tri = rng.integers(0, v.n_material, v.n_index // 3).astype(np.uint32) if random_materials else None
+        if tri_materials is not None:
+            tri = np.array(tri_materials, np.uint32)
+            assert random_materials and len(tri) == v.n_index // 3
         imgs = _random_images(v, np.random.default_rng(7)) if tex else []
+        if checker:
+            assert v.n_cube > 0
+            for i in range(v.n_cube):
+                v.materials[v.cubeList[i].material].textureInfo.type = abi.TEX_CHECKER
         _SCENES[key] = SceneSet(sc, host.prepare_camera(W, H), tri, imgs)
     return _SCENES[key]
 
@@ -135,17 +149,27 @@ def env_map(name):
 
 
 class Case:
-    def __init__(self, id, scene, light=None, shape="one", env=None, spp=None, max_depth=8, integrator=MIS, pick=1, frame0=0, second=0):
+    """sobol = TRC_FLAG_SOBOL, stats = TRC_FLAG_COLLECT_STATS, env_rgb = the constant environment (trc_set_environment), cam = a
+    function of (width, height) that gives the camera instead of the scene's own (replay_camera)"""
+
+    def __init__(self, id, scene, light=None, shape="one", env=None, spp=None, max_depth=8, integrator=MIS, pick=1, frame0=0, second=0,
+                 sobol=False, stats=False, env_rgb=(0.0, 0.0, 0.0), cam=None):
         self.id, self.scene_fn, self.light, self.shape, self.env = id, scene, light, shape, env
         self.spp = spp if spp is not None else (2 if shape == "strip" else 16)
         self.max_depth, self.integrator, self.pick, self.frame0, self.second = max_depth, integrator, pick, frame0, second
+        self.sobol, self.stats, self.env_rgb, self.cam_fn = sobol, stats, tuple(env_rgb), cam
 
     @property
     def scene(self):
         return self.scene_fn()
 
+    @property
+    def camera(self):
+        return self.cam_fn(W, H) if self.cam_fn else self.scene.cam
+
     def oracle_key(self):
-        return (self.scene_fn.__name__, getattr(self.scene_fn, "args", ()), self.light, self.env, self.spp, self.max_depth, self.integrator, self.pick, self.frame0, self.second)
+        return (self.scene_fn.__name__, getattr(self.scene_fn, "args", ()), self.light, self.env, self.spp, self.max_depth, self.integrator, self.pick, self.frame0, self.second,
+                self.sobol, self.env_rgb, getattr(self.cam_fn, "__name__", None))
 
     def __repr__(self):
         return self.id
@@ -210,17 +234,122 @@ def oracle_frame(case):
     """(accum, rng, stats) of the case in the oracle; a second launch (case.second samples) continues the first's frame count"""
     key = case.oracle_key()
     if key not in _ORACLE:
-        s = case.scene
+        s, cam = case.scene, case.camera
         po.set_environment_map(env_map(case.env) if case.env else None)
         try:
             rng = host.fill_rng(SEED, W, H)
             kw = dict(max_depth=case.max_depth, integrator=case.integrator, env_light=case.light == "env", mesh_lights=case.light == "mesh",
-                      mesh_light_pick=case.pick, triangle_materials=s.tri, textures=s.images)
-            acc, st = po.render(s.view, s.cam, W, H, rng, spp=case.spp, frame0=case.frame0, **kw)
+                      mesh_light_pick=case.pick, triangle_materials=s.tri, textures=s.images, sobol=case.sobol, env=case.env_rgb)
+            acc, st = po.render(s.view, cam, W, H, rng, spp=case.spp, frame0=case.frame0, **kw)
             if case.second:
-                acc, st2 = po.render(s.view, s.cam, W, H, rng, accum=acc, spp=case.second, frame0=case.frame0 + case.spp, **kw)
-                st.rays += st2.rays; st.paths += st2.paths; st.shaded += st2.shaded
+                acc, st2 = po.render(s.view, cam, W, H, rng, accum=acc, spp=case.second, frame0=case.frame0 + case.spp, **kw)
+                for f, _ in abi.Stats._fields_:
+                    if isinstance(getattr(st, f), int):
+                        setattr(st, f, getattr(st, f) + getattr(st2, f))
         finally:
             po.set_environment_map(None)
         _ORACLE[key] = (acc, rng, st)
     return _ORACLE[key]
+
+
+# ---------------------------------------------------------------------- the census of the kernel tables (tests/test_gpu_kernel_census.py)
+ENV_RGB = (0.3, 0.4, 0.6)                                   # a constant environment that is not black: an escaping ray carries it
+FAMILIES = ("plain", "trimat")                              # the tables and their per-triangle-material twins (namespace trimat)
+INTEGRATOR_NAMES = {PATH: "path", MIS: "mis", VOLUME: "volume"}
+LIGHT_VARIANTS = ("env", "env_tex", "mesh", "mesh_tex")
+_KNOWN_VARIANTS, _KNOWN_SHAPES = ("plain", "stats", "sobol", "tex") + LIGHT_VARIANTS, ("one", "strip", "pwg", "dense")
+
+
+def _in_table(integrator, variant, residence, shape):
+    """render_kernels<LDS, INTEGRATOR>() (trc_render_kernels.hpp), restated: is this entry non-null?  A variant or a shape this
+    function has not heard of is taken to be everywhere, so that it shows as unreached until the census learns its rule."""
+    if variant not in _KNOWN_VARIANTS or shape not in _KNOWN_SHAPES:
+        return True
+    if shape == "dense":                                    # k_render_dense: one kernel beside the tables, tracePath on a tree in LDS
+        return integrator == PATH and variant == "plain" and residence == "lds"
+    if shape == "pwg" and residence == "lds":               # persistent workgroups: trees read from memory only
+        return False
+    if variant in LIGHT_VARIANTS:
+        return integrator == MIS
+    if variant == "sobol":
+        return integrator != VOLUME
+    if variant == "stats":                                  # no statistics twin of the strip / persistent kernels
+        return shape == "one"
+    return True
+
+
+def table_entries():
+    """every entry of the kernel tables as (family, integrator, variant, residence, shape), from what the library names"""
+    return [(f, i, v, r, sh) for f in FAMILIES for i in (PATH, MIS, VOLUME) for v in abi.KERNEL_VARIANTS for r in ("lds", "mem")
+            for sh in abi.KERNEL_SHAPES if _in_table(i, v, r, sh)]
+
+
+def census_cases():
+    """one case for every entry that tests/test_gpu_light_oracle.py does not assert (the light variants of both families, the Tex
+    entries of the plain one) and that is no dense launch (a frame of its own size: test_gpu_kernel_census.py renders those)"""
+    out = []
+    for (family, integ, variant, residence, shape) in table_entries():
+        if variant in LIGHT_VARIANTS or (family == "plain" and variant == "tex") or shape == "dense":
+            continue
+        c = Case(f"{family}-{INTEGRATOR_NAMES[integ]}-{variant}-{residence}-{shape}", _bind(cornell, residence, variant == "tex", family == "trimat"),
+                 shape=shape, spp=2 if shape == "strip" else 8, integrator=integ, sobol=variant == "sobol", stats=variant == "stats", env_rgb=ENV_RGB)
+        c.entry = (family, integ, variant, residence, shape)
+        out.append(c)
+    return out
+
+
+# ---------------------------------------------------------------------- the replay matrix (tests/test_gpu_primary_replay.py)
+REPLAY_EYES = [((500.0, 40.0, -450.0), (200.0, 450.0, 250.0)),      # the matrix's camera
+               ((455.0, 70.0, -500.0), (215.0, 430.0, 260.0)),      # the same, moved a little (a second launch from another eye)
+               ((-450.0, 200.0, -350.0), (278.0, 278.0, 278.0))]    # from the far left: triangles of the small ball whose sn is -gn
+
+
+def replay_camera(w, h, which=0):
+    """pulled back from Cornell's open side and off its axis, aperture 0: part of the frame escapes, the lamp is seen from below, the
+    ball and the cubes are in view (tests/test_replay_scenes.py holds it to that).  No component of lookFrom is zero."""
+    look_from, look_at = REPLAY_EYES[which]
+    return host.make_camera(look_from, look_at, (0.0, 1.0, 0.0), 0.0, w / h, float(np.deg2rad(50.0)), 10.0)
+
+
+REPLAY_SCENES = {"trimat": ("mem", False, True, False, False), "tex": ("mem", True, False, False, True), "trimat+tex": ("mem", True, True, False, True),
+                 # triangle 1 the dim emitter and 6 the Plastic (kept in the packed word); 1 kept and 6 of a cube's material (checkered: it reads uv);
+                 # triangle 3, which the camera on the far left sees from its far side, a Lambert / the Plastic: the lobe knows sn from -sn
+                 "dense-trimat": ("tiny", False, True, False, False, (11, 9, 15, 4, 0, 13, 8, 7, 3, 12, 17, 5)),
+                 "dense-trimat-checker": ("tiny", False, True, False, True, (11, 12, 15, 8, 0, 13, 2, 7, 3, 9, 17, 5))}
+
+
+def replay_scene(name):
+    """the 1104-triangle ball (persistent workgroups) with random per-triangle materials / random images and checker cubes, every triangle
+    material 19 / both; the 12-triangle ball (the dense kernel) with a material per triangle, plain and with checker cubes"""
+    return cornell(*REPLAY_SCENES[name])
+
+
+def primary_hits(s, cam, w, h, view_height=0):
+    """what the camera ray of every pixel of the w x h frame meets, from the oracle's trace_rays (aperture 0: castRay's own arithmetic,
+    v of a stacked view as kernelPathTracing takes it) -> (h, w) arrays: hit, emitter (the ray ends on a Diffuse material), triangle,
+    material, and uv_read -- a hit that is no emitter, on a cube or a triangle whose material is a checker texture: its colour reads
+    rec.uv, which a memo of fewer than 10 rows does not keep (render_block: memo_store); back -- a hit whose sn is not its gn (the
+    memo keeps gn and one bit for the side)"""
+    vh = view_height if 0 < view_height < h else h
+    ys, xs = np.mgrid[0:h, 0:w]
+    u = (xs.astype(F) / F(w)).ravel()
+    v = ((ys % vh).astype(F) / F(vh)).ravel()
+    f = lambda a: np.array([a.x, a.y, a.z], dtype=F)
+    sample = f(cam.cornerLowLeft)[None] + f(cam.horizontal)[None] * u[:, None] + f(cam.vertical)[None] * v[:, None]
+    o = np.repeat(f(cam.lookFrom)[None], len(u), 0)
+    hits = po.trace_rays(s.view, po.make_rays(o, (sample - o).astype(F)), triangle_materials=s.tri)
+    mat_type = np.array([s.view.materials[i].type for i in range(s.view.n_material)])
+    tex_type = np.array([s.view.materials[i].textureInfo.type for i in range(s.view.n_material)])
+    hit = hits["hit"] != 0
+    material = np.where(hit, hits["material"], 0)
+    emitter = hit & (mat_type[material] == abi.MAT_DIFFUSE)
+    uv_read = hit & ~emitter & np.isin(hits["pType"], (abi.PRIM_CUBE, abi.PRIM_TRIANGLE)) & (tex_type[material] == abi.TEX_CHECKER)
+    back = hit & (hits["sn"].view(np.uint32) != hits["gn"].view(np.uint32)).any(axis=1)
+    sh = lambda a: a.reshape(h, w)
+    return dict(hit=sh(hit), emitter=sh(emitter), triangle=sh(hit & (hits["pType"] == abi.PRIM_TRIANGLE)), material=sh(material), uv_read=sh(uv_read),
+                back=sh(back))
+
+
+def kept_pixels(hits, memo_rows):
+    """the pixels whose primary hit the memo keeps: all of them with 10 rows, all but the uv readers with 7 or 8"""
+    return np.ones_like(hits["hit"]) if memo_rows >= 10 else ~hits["uv_read"]

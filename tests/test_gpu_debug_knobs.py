@@ -1,6 +1,9 @@
 """trc_debug_set and the knobs' defaults (tracer_abi.h): every knob name is accepted, an unknown one is refused and leaves the context
 as it was, negative values clamp to 0, and trc_create reads the defaults from the environment.  Knobs are scheduling only, so every
-frame compared here is compared bit for bit.  The module renders on hooks Tracers of its own (trc_debug_last_kernel)."""
+frame compared here is compared bit for bit.  The frames of this module run kernels that keep no primary-replay memo: replay_min_lanes
+and replay_chain are only named here, and are run with values, on the kernels that have a memo, by the replay matrix of
+tests/test_gpu_primary_replay.py (test_replay_schedule_knobs_change_nothing).  The module renders on hooks Tracers of its own
+(trc_debug_last_kernel)."""
 import os
 
 import numpy as np

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import light_oracle_cases as lc
 from oracle import pyoracle as po
 from tracer_amd import abi, host
 
@@ -65,7 +66,10 @@ def plain(gpu_hooks):
 def checker(gpu_hooks):
     scene = host.HostScene(abi.SCENE_CORNELL_SPHERES)
     view, mats = _checker_cube_view(scene)
-    return _on_and_off(gpu_hooks, view)
+    res = _on_and_off(gpu_hooks, view)
+    # what every pixel's camera ray meets, from the oracle: the replay count is predicted from it (tests/test_gpu_primary_replay.py)
+    res["hits"] = lc.primary_hits(lc.SceneSet(scene, None, view=view), host.prepare_camera(W, H), W, H)
+    return res
 
 
 def test_wave_slots_are_what_the_runtime_says_the_cu_holds(plain):
@@ -98,8 +102,9 @@ def test_replay_on_and_off_give_the_same_bits(request, which):
             assert replays == expected
         elif res["fit"]["dense_memo_rows"] >= 10:
             assert replays == expected                # uv has rows: the cubes' pixels replay too
-        else:
-            assert 0 < replays < expected             # a checker cube is in view, and its pixels walk every sample
+        else:                                         # checker cubes are in view, and exactly their pixels walk every sample
+            assert replays == (SPP - 1) * int(lc.kept_pixels(res["hits"], res["fit"]["dense_memo_rows"]).sum())
+            assert 0 < replays < expected
 
 
 @pytest.fixture(scope="module")

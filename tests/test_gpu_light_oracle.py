@@ -12,6 +12,7 @@ from conftest import camera_rays
 from oracle import pyoracle as po
 from tracer_amd import abi, host
 from tracer_amd.device import Tracer, TracerError
+from test_gpu_primary_replay import STAT_FIELDS
 
 pytestmark = pytest.mark.gpu
 W, H = lc.W, lc.H
@@ -27,11 +28,11 @@ def lgpu():
     t.close()
 
 
-def _upload(t, s, env=None):
+def _upload(t, s, env=None, env_rgb=(0.0, 0.0, 0.0), cam=None):
     t.upload_scene(s.view)
     t.upload_triangle_materials(s.tri)
     t.upload_textures(s.images)
-    t.set_camera(s.cam); t.set_environment((0.0, 0.0, 0.0)); t.resize(W, H)
+    t.set_camera(cam if cam is not None else s.cam); t.set_environment(env_rgb); t.resize(W, H)
     t.set_environment_map(lc.env_map(env) if env else None)
     t.seed(lc.SEED); t.clear_accum(); t.reset_stats()
 
@@ -50,18 +51,19 @@ def _render_case(t, case):
 
 
 def _launch_case(t, case, s):
-    _upload(t, s, case.env)
+    _upload(t, s, case.env, case.env_rgb, case.camera)
     t.debug_set("strip_force", 2 if case.shape == "strip" else 0)
     t.debug_set("no_pwg", 1 if case.shape == "one" else 0)
     t.debug_set("mesh_light_pick", case.pick)
-    kw = dict(max_depth=case.max_depth, integrator=case.integrator, env_light=case.light == "env", mesh_lights=case.light == "mesh")
+    kw = dict(max_depth=case.max_depth, integrator=case.integrator, env_light=case.light == "env", mesh_lights=case.light == "mesh",
+              sobol=case.sobol, collect_stats=case.stats)
     t.render(spp=case.spp, frame0=case.frame0, **kw)
     if case.second:
         t.render(spp=case.second, frame0=case.frame0 + case.spp, **kw)
     out = t.download_accum(), t.download_rng(), t.stats(), t.last_kernel()
     # (not in a `finally`: after a TracerError, a device fault included, nothing more is asked of this context)
     t.debug_set("strip_force", 0); t.debug_set("no_pwg", 0); t.debug_set("mesh_light_pick", 1)
-    t.set_environment_map(None); t.upload_textures([])
+    t.set_environment_map(None); t.upload_textures([]); t.set_environment((0.0, 0.0, 0.0))
     return out
 
 
@@ -74,7 +76,8 @@ def _check(case, got):
     acc, rng, st, k = got
     ref_acc, ref_rng, ref_st = lc.oracle_frame(case)
     s = case.scene
-    variant = (case.light + ("_tex" if s.images else "")) if case.light else ("tex" if s.images else "plain")
+    # (choose_kernel: a light, then images, then Sobol', then the counters)
+    variant = (case.light + ("_tex" if s.images else "")) if case.light else ("tex" if s.images else "sobol" if case.sobol else "stats" if case.stats else "plain")
     print(f"{case.id}: kernel {_entry(case, k)}, strip {k['strip']}; "
           f"rays {st.rays} shaded {st.shaded}; accum mismatches {int((acc.view(np.uint32) != ref_acc.view(np.uint32)).any(axis=-1).sum())}, "
           f"rng mismatches {int((rng != ref_rng).any(axis=-1).sum())}")
@@ -85,6 +88,9 @@ def _check(case, got):
     assert len(bad) == 0, f"{len(bad)} pixels differ, first (y, x) {bad[0]}: gpu {acc[tuple(bad[0])]} oracle {ref_acc[tuple(bad[0])]}"
     assert np.array_equal(rng, ref_rng)
     assert (st.rays, st.paths, st.shaded) == (ref_st.rays, ref_st.paths, ref_st.shaded)
+    if case.stats:                               # TRC_FLAG_COLLECT_STATS: the traversal counters are the oracle's too
+        for f in STAT_FIELDS:
+            assert getattr(st, f) == getattr(ref_st, f), f
 
 
 MATRIX, BEYOND = lc.matrix(), lc.beyond()
