@@ -34,6 +34,14 @@ trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t 
  * RN(1 / c) and one residual correction, against the compiler's x / c */
 trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch);
 
+/* test hook of the lobe code: Material::S_F as the render kernels evaluate it (tracer_amd/csrc/dev_bsdf.hpp: material_S_F), one lane per
+ * input in the order given, so that the caller decides which materials meet in one wavefront of 64.  For n inputs (material type by
+ * ordinal, colour, wo in the shading frame, the two random numbers) out receives 7 floats each: wi, the attenuation and the pdf; wi
+ * starts as 0 and the pdf as pdf_init, which an early-out leaves in place.  stream 0: the Metal lobe as a branch of its own; stream 1:
+ * through the Beckmann lobes' stream (TRC_MICROFACET_STREAM).  Both exist here whichever the render kernels were compiled with. */
+trc_status trc_material_s_f_test(trc_ctx* ctx, uint32_t stream, const uint32_t* type /* n */, const float* color /* 3 n */,
+                                 const float* wo /* 3 n */, const float* uu /* 2 n */, size_t n, float pdf_init, float* out /* 7 n */);
+
 /* test hook of the SVGF stage (tracer_abi.h, trc_denoise): the state the last trc_denoise left, W*H float4 each (any pointer may
  * be NULL): integrated = the temporal pass's (colour, variance), history = the colour history the next frame reprojects
  * (a-trous iteration 0's (colour, variance), or the integrated colour at 0 iterations), moments = (mu1, mu2, history length, 0).

@@ -584,6 +584,242 @@ TRC_DEV F3 beckmann_finish(const Beckmann& d, bool refl, float R, F3 wo, F3 wh, 
     return out;
 }
 
+// ---------------------------------------------------------------- one stream for the four microfacet lobes
+// TRC_MICROFACET_STREAM (read by material_S_F): the Metal lobe (Trowbridge-Reitz (0.01, 0.02), conductor Fresnel) runs through the
+// instruction stream of the three Beckmann lobes instead of a branch of its own beside them -- a wavefront that holds Metal lanes
+// and Plastic / Glass lanes then issues the skeleton the two families share (stretch, phi_of, rotate, unstretch, reflect, the
+// normalisations, the final quotients) once.  The family is a per-lane value like the roughness pair; what differs between the
+// families (sample11's bodies, the tails of Lambda and D, the Fresnel term, two literals) stays each family's own expression.
+// Every lane evaluates the reference's expressions for its material on the same operands in the same order
+// (trc_material_s_f_test holds the two forms against each other bit for bit).  A translation unit sets it before including this header.
+#ifndef TRC_MICROFACET_STREAM
+#define TRC_MICROFACET_STREAM 0
+#endif
+
+struct Microfacet {
+    bool tr;                         // Trowbridge-Reitz (Metal), else Beckmann (Plastic's specular lobe, Glass's two lobes)
+    float alpha_x, alpha_y;
+    DivConst by_ax2, by_ay2;         // alpha^2 and its reciprocal (D divides by them)
+    TRC_DEV static Microfacet make_lobe(bool metal, bool plastic) {
+        Microfacet d; d.tr = metal;
+        d.alpha_x = fmaxf(0.001f, 0.01f); d.alpha_y = fmaxf(0.001f, metal ? 0.02f : plastic ? 0.1f : 0.01f);
+        d.by_ax2 = div_by_sqr001();
+        const DivConst rough = div_by_sqr01(), mid = div_by_sqr002(), smooth = div_by_sqr001();
+        d.by_ay2.c = metal ? mid.c : plastic ? rough.c : smooth.c; d.by_ay2.y = metal ? mid.y : plastic ? rough.y : smooth.y;
+        return d;
+    }
+    TRC_DEV float ax() const { return alpha_x; }
+    TRC_DEV float ay() const { return alpha_y; }
+
+    // Beckmann::lambda / TrowbridgeReitzD::lambda.  Shared: sin_theta, phi_of, ONE quotient (sin / cos for Beckmann's tan_theta,
+    // sin^2 / cos^2 for Trowbridge-Reitz's tan2_theta, each with its own zero tests) and ONE square root (of each family's operand)
+    TRC_DEV float lambda(F3 w) const {
+        const float st = sin_theta(w);
+        const Phi ph = phi_of(w, st);
+        const float zz = w.z * w.z;
+        const float temp = 1 - zz;
+        const float num = tr ? temp : st, den = tr ? zz : w.z;
+        const float t = (temp <= 0.0f || den == 0.0f) ? 0.0f : num / den;       // tan2_theta(w) | tan_theta_st(w, st)
+        const float x = tr ? 1 + (sqr(ph.c * ax()) + sqr(ph.s * ay())) * t
+                           : (ph.c * ph.c) * ax() * ax() + (ph.s * ph.s) * ay() * ay();
+        const float r = sqrt_cr(x);
+        if (is_inf(t)) return 0.;                     // is_inf(tan2Theta) | is_inf(fabsf(tanTheta))
+        if (tr) return 0.5f * (r - 1);
+        float a = rcp1(r * fabsf(t));
+        if (a >= 1.6f) return 0;
+        return (1 - 1.259f * a + 0.396f * a * a) / (3.535f * a + 2.181f * a * a);
+    }
+    TRC_DEV float D(F3 wh) const {
+        float tan2Theta = tan2_theta(wh);
+        if (is_inf(tan2Theta)) return 0.;
+        const float cos4Theta = cos2_theta(wh) * cos2_theta(wh);
+        if (tr && cos4Theta < 1e-16f) return 0;
+        const Phi ph = phi_of(wh);
+        float qc, qs;                                     // cos2_phi / (ax * ax), sin2_phi / (ay * ay)
+        div_const2(ph.c * ph.c, by_ax2, ph.s * ph.s, by_ay2, qc, qs);
+        if (tr) {
+            float e = (qc + qs) * tan2Theta;
+            return rcp1(kPi * ax() * ay() * sqr(1 + e) * cos4Theta);
+        }
+        return dm_expf(-tan2Theta * (qc + qs)) /
+               (kPi * ax() * ay() * cos4Theta);
+    }
+
+    TRC_DEV void sample11(float cosTheta, float sinTheta, float U1, float U2, float& slope_x, float& slope_y) const {
+        if (cosTheta > .9999f) {
+            float r2;                                     // each family's own radius, one root
+            if (tr) r2 = U1 / (1 - U1);
+            else r2 = -dm_logf(1.0f - U1);
+            float r = sqrt_cr(r2);
+            const float phi = tr ? 6.28318530718f * U2 : 2 * kPi * U2;      // each family's own literal
+            float s, c;
+            dm_sincosf(phi, &s, &c);
+            slope_x = r * c;
+            slope_y = r * s;
+            return;
+        }
+        const float tanTheta = sinTheta / cosTheta;
+        const float cotTheta = rcp1(tanTheta);
+        if (tr) {                                         // TrowbridgeReitzD::sample11: the closed form
+            const float a = cotTheta;
+            float G1 = 2 * rcp1(1 + sqrt_cr(1.f + rcp1(a * a)));
+            float A = 2 * U1 / G1 - 1;
+            float tmp = rcp1(A * A - 1.f);
+            if (tmp > 1e10f) tmp = 1e10f;
+            float B = tanTheta;
+            float D = sqrt_cr(fmaxf(B * B * tmp * tmp - (A * A - B * B) * tmp, 0.0f));
+            float slope_x_1 = B * tmp - D;
+            float slope_x_2 = B * tmp + D;
+            slope_x = (A < 0 || slope_x_2 > a) ? slope_x_1 : slope_x_2;
+            float S;
+            if (U2 > 0.5f) { S = 1.f; U2 = 2.f * (U2 - .5f); }
+            else { S = -1.f; U2 = 2.f * (.5f - U2); }
+            float z = (U2 * (U2 * (U2 * 0.27385f - 0.73369f) + 0.46341f)) /
+                      (U2 * (U2 * (U2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
+            slope_y = S * z * sqrt_cr(1.f + slope_x * slope_x);
+            return;
+        }
+        const float tanThetaI = tanTheta, cotThetaI = cotTheta, cosThetaI = cosTheta;      // Beckmann::sample11: the Newton iteration
+        float a = -1, c = erf_approx(cotThetaI);
+        float sample_x = fmaxf(U1, 1e-6f);
+        float thetaI = dm_acosf(cosThetaI);
+        float fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
+        const float base = 1 - sample_x;
+        const float pw = dm_expf_fin(fit * dm_logf_pos(base == 0.0f ? 1.0f : base));
+        float b = c - (1 + c) * (base == 0.0f ? 0.0f : pw);
+        const float SQRT_PI_INV = 1.f / sqrtf(kPi);
+        float normalization = rcp1(1 + c + SQRT_PI_INV * tanThetaI * dm_expf(-cotThetaI * cotThetaI));
+        int it = 0;
+        while (++it < 10) {
+            if (!(b >= a && b <= c)) b = 0.5f * (a + c);
+            float invErf = erf_inv(b);
+            float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * dm_expf_fin(-invErf * invErf)) - sample_x;
+            float derivative = normalization * (1 - invErf * tanThetaI);
+            if (fabsf(value) < 1e-5f) break;
+            if (value > 0) c = b; else a = b;
+            b -= value / derivative;
+        }
+        slope_x = erf_inv(b);
+        slope_y = erf_inv(2.0f * fmaxf(U2, 1e-6f) - 1.0f);
+    }
+    TRC_DEV F3 sample_wh(F3 wo, F2 u) const {
+        const bool flip = wo.z < 0;
+        const F3 wi = flip ? -wo : wo;
+        F3 wiStretched = normalize(f3(ax() * wi.x, ay() * wi.y, wi.z));
+        float slope_x, slope_y;
+        const float st = sin_theta(wiStretched);
+        sample11(cos_theta(wiStretched), st, u.x, u.y, slope_x, slope_y);
+        const Phi ph = phi_of(wiStretched, st);
+        float tmp = ph.c * slope_x - ph.s * slope_y;
+        slope_y = ph.s * slope_x + ph.c * slope_y;
+        slope_x = tmp;
+        slope_x = ax() * slope_x;
+        slope_y = ay() * slope_y;
+        F3 wh = normalize(f3(-slope_x, -slope_y, 1.f));
+        return flip ? -wh : wh;
+    }
+};
+
+// beckmann_finish with the family per lane: Metal takes the reflection side of phase (A) -- MicroRefl::S_F's early-outs are the
+// ones written there, in its order --, its own Lambda / D tails and the conductor Fresnel term in phase (B), and in phase (C) the
+// shared reflection combination with its own statement of the pdf: D G1 |dot(wo, wh) / cos| where Beckmann's is
+// D G1 |dot(wo, wh)| / |cos| (another order of operations, not the same bits) -- one quotient serves both.
+TRC_DEV F3 microfacet_finish(const Microfacet& d, bool refl, float R, F3 wo, F3 wh, F3& wi_out, float& pdf_out) {
+    const float etaA = 1.0f, etaB = 1.5f;
+    bool live;                    // got past the early-outs of S_F: pdf_out will be written
+    bool pdf_live = false;        // ... with a non-trivial value
+    bool f_live = false;          // F reaches its D * G * Fresnel expression
+    F3 wi = wi_out, whA = wh, whB = wh;
+    float eta = 0, fres_cos = 0, fres_eta = 1.5f;
+    // ---- (A)
+    if (refl) {
+        live = !(dot(wo, wh) <= 0);
+        if (live) {
+            wi = reflect(wo, wh);
+            if (d.tr) wi_out = wi;            // MicroRefl::S_F assigns its wi before the second early-out, beckmann_finish after it
+            live = !(wo.z * wi.z <= 0);
+        }
+        if (live) {
+            pdf_live = true;
+            const float cosThetaO = abs_cos_theta(wo), cosThetaI = abs_cos_theta(wi);
+            F3 sum = wi + wo;
+            f_live = !(cosThetaI == 0 || cosThetaO == 0) && !(sum.x == 0 && sum.y == 0 && sum.z == 0);
+            if (f_live) {
+                whB = normalize(sum);
+                const float d001 = whB.x * 0.0f + whB.y * 0.0f + whB.z * 1.0f;      // Faceforward(wh, (0,0,1))
+                const F3 whf = (d001 < 0.f) ? -whB : whB;
+                fres_cos = dot(wi, whf);
+                fres_eta = 1.5f;
+            }
+        }
+    } else {
+        live = !(dot(wo, wh) < 0);
+        if (live) live = refract(wo, wh, cos_theta(wo) > 0 ? (etaA / etaB) : (etaB / etaA), wi);
+        if (live) {
+            eta = cos_theta(wo) > 0 ? (etaB / etaA) : (etaA / etaB);
+            const bool same_side = wo.z * wi.z > 0;
+            whA = normalize(wo + wi * eta);
+            const bool backfacing = dot(wo, whA) * dot(wi, whA) > 0;               // same truth value for -whA
+            pdf_live = !same_side && !backfacing;
+            whB = whA;
+            if (whB.z < 0) whB = -whB;
+            f_live = pdf_live && !(cos_theta(wi) == 0 || cos_theta(wo) == 0);
+            fres_cos = dot(wo, whB);
+            fres_eta = etaA;
+        }
+    }
+    // ---- (B)
+    float D_A = 0, D_B = 0, lam_o = 0, lam_i = 0;
+    F3 fres = f3(0);
+    if (pdf_live) {
+        lam_o = d.lambda(wo);
+        D_A = d.D(whA);
+        D_B = D_A;
+        if (refl && f_live) D_B = d.D(whB);
+        if (f_live) {
+            lam_i = d.lambda(wi);
+            if (d.tr) fres = FrCond::eval(fres_cos);
+            else fres = f3(fr_dielectric(fres_cos, fres_eta));
+        }
+    }
+    // ---- (C)
+    F3 out = f3(0);
+    if (live) {
+        wi_out = wi;
+        const float G1 = rcp1(1 + lam_o);
+        const float G = rcp1(1 + lam_o + lam_i);
+        if (refl) {
+            const float dwh = dot(wo, wh);
+            const float num = d.tr ? dwh : D_A * G1 * fabsf(dwh), den = d.tr ? cos_theta(wo) : abs_cos_theta(wo);
+            const float q = num / den;
+            const float dist_pdf = d.tr ? D_A * G1 * fabsf(q) : q;
+            pdf_out = dist_pdf / (4 * dot(wo, wh));
+            if (f_live) {
+                const float cosThetaO = abs_cos_theta(wo), cosThetaI = abs_cos_theta(wi);
+                out = f3(R) * D_B * G * fres / (4 * cosThetaI * cosThetaO);
+            }
+        } else {
+            float p = 0;
+            if (pdf_live) {
+                const float sqrtDenom = dot(wo, whA) + eta * dot(wi, whA);
+                const float dwh_dwi = fabsf((eta * eta * dot(wi, whA)) / (sqrtDenom * sqrtDenom));
+                const float dist_pdf = D_A * G1 * fabsf(dot(wo, whA)) / abs_cos_theta(wo);
+                p = dist_pdf * dwh_dwi;
+            }
+            pdf_out = p;
+            if (f_live) {
+                const float cosThetaO = cos_theta(wo), cosThetaI = cos_theta(wi);
+                const float sqrtDenom = dot(wo, whB) + eta * dot(wi, whB);
+                const float factor = 1;
+                out = (f3(1.0f) - fres) * f3(0.98f) *
+                      fabsf(D_B * G * eta * eta * fabsf(dot(wi, whB)) * fabsf(dot(wo, whB)) * factor * factor /
+                            (cosThetaI * cosThetaO * sqrtDenom * sqrtDenom));
+            }
+        }
+    }
+    return out;
+}
+
 // composites (MicrofacetBXDF.h:436-586)
 typedef MicroRefl<TrowbridgeReitzD<Alpha_01_02>, FrCond> MetalLobe;       // alpha (0.01, 0.02), R = 1
 // Plastic specular: Beckmann (0.01, 0.1), R = 1; Glass: Beckmann (0.01, 0.01), reflection R = kr = 0.98
@@ -609,10 +845,37 @@ TRC_DEV F3 texture_value(int tex_type, F3 albedo, F2 uv) {           // Texture.
 // Organised by LOBE rather than by material so that lanes of different materials share instructions: the
 // cosine lobe serves Lambert and Plastic's diffuse half, the Beckmann sampling serves Plastic's specular half
 // and both Glass lobes.  Every lane evaluates exactly the reference's expressions for its own material.
-template <bool STATS>
+// STREAM: the four microfacet lobes as one stream (TRC_MICROFACET_STREAM above).  The instrumented kernels (STATS) keep the
+// branches apart, so that the per-site profile of trc_debug_profile stays what it says.
+template <bool STATS, bool STREAM = (TRC_MICROFACET_STREAM != 0)>
 TRC_DEV F3 material_S_F(int type, F3 color, F3 wo, F3& wi, F2 uu, float& pdf, TravCounters& cnt) {
     const bool plastic = type == kMatPlastic, glass = type == kMatGlass;
     F3 out = f3(0);
+    if constexpr (STREAM && !STATS) {
+        const bool metal = type == kMatMetal;
+        if (type == kMatLambert || (plastic && uu.x < 0.5f)) {
+            F2 u2 = uu;
+            if (plastic) u2.x *= 2;
+            const float v = Lambert::S_F(wo, wi, u2, pdf);
+            out = plastic ? color * (f3(0.35f, 0.12f, 0.48f) * v) : color * f3(v);
+        } else if (metal || plastic || glass) {
+            const float ratio = 0.25f;
+            const bool refl = metal || plastic || uu.x < ratio;
+            F2 u2 = uu;
+            if (metal) { }                                           // MetalMaterial::S_F hands uu on as it is
+            else if (plastic) { u2.x -= 0.5f; u2.x *= 2.0f; }
+            else if (refl) u2.x = uu.x / ratio;
+            else u2.x = (uu.x - ratio) / (1.0f - ratio);
+            const Microfacet d = Microfacet::make_lobe(metal, plastic);
+            F3 lobe = f3(0);
+            if (wo.z != 0) {
+                const F3 wh = d.sample_wh(wo, u2);
+                lobe = microfacet_finish(d, refl, (metal || plastic) ? 1.0f : 0.98f, wo, wh, wi, pdf);
+            }
+            out = plastic ? color * (f3(0.2f) * lobe) : color * lobe;
+        }
+        return out;
+    }
     if (type == kMatMetal) {
         ProfScope<STATS> scope(cnt, kProfMetal);
         out = color * MetalLobe::S_F(1.0f, wo, wi, uu, pdf);

@@ -51,6 +51,23 @@ __global__ void __launch_bounds__(256) k_unary_test(uint32_t op, uint32_t first,
     if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first_bad); }
 }
 
+// trc_material_s_f_test: material_S_F (dev_bsdf.hpp) in either form, one lane per input, so that the order of the inputs decides
+// which materials share a wavefront.  Both forms are instantiated here whatever TRC_MICROFACET_STREAM says.
+template <bool STREAM>
+__global__ void __launch_bounds__(256) k_material_s_f_test(const uint32_t* type, const float* color, const float* wo, const float* uu,
+                                                           uint32_t n, float pdf_init, float* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    F2 u; u.x = uu[2 * i]; u.y = uu[2 * i + 1];
+    F3 wi = f3(0);
+    float pdf = pdf_init;
+    TravCounters none;
+    const F3 f = material_S_F<false, STREAM>((int)type[i], f3(color[3 * i], color[3 * i + 1], color[3 * i + 2]),
+                                             f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), wi, u, pdf, none);
+    float* o = out + 7 * (size_t)i;
+    o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = f.x; o[4] = f.y; o[5] = f.z; o[6] = pdf;
+}
+
 extern "C" {
 // developer diagnostic: (lanes, wavefronts) that executed each ProfSite of the instrumented kernels
 trc_status trc_debug_profile(trc_ctx* ctx, uint64_t* out, uint32_t n_sites) {
@@ -137,6 +154,28 @@ trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t 
     if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_div_by_test: ") + hipGetErrorString(e));
     TRC_TRY(trc_copy_to_host(ctx, fast, d_fast, n * 12, ctx->stream));
     return trc_copy_to_host(ctx, plain, d_plain, n * 12, ctx->stream);
+}
+
+trc_status trc_material_s_f_test(trc_ctx* ctx, uint32_t stream, const uint32_t* type, const float* color, const float* wo, const float* uu,
+                                 size_t n, float pdf_init, float* out) {
+    if (!ctx || stream > 1u || (n && (!type || !color || !wo || !uu || !out))) return TRC_ERR_INVALID_ARG;
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 7u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_material_s_f_test: too many inputs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf d;
+    TRC_TRY(d.alloc(ctx, n * 16 * sizeof(float), "material S_F test"));
+    float *d_color = d.as<float>(), *d_wo = d_color + 3 * n, *d_uu = d_color + 6 * n, *d_out = d_color + 8 * n;
+    uint32_t* d_type = reinterpret_cast<uint32_t*>(d_color + 15 * n);
+    TRC_TRY(trc_copy_to_device(ctx, d_color, color, n * 12, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_wo, wo, n * 12, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_uu, uu, n * 8, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_type, type, n * 4, ctx->stream));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (stream) hipLaunchKernelGGL(k_material_s_f_test<true>, grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
+    else hipLaunchKernelGGL(k_material_s_f_test<false>, grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_material_s_f_test: ") + hipGetErrorString(e));
+    return trc_copy_to_host(ctx, out, d_out, n * 28, ctx->stream);
 }
 
 trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch) {

@@ -9,6 +9,9 @@
 #ifndef TRC_FAST_UNARY
 #define TRC_FAST_UNARY 1
 #endif
+#ifndef TRC_MICROFACET_STREAM
+#define TRC_MICROFACET_STREAM 1      // dev_bsdf.hpp: the Metal lobe through the Beckmann lobes' stream (profiles/r22)
+#endif
 #include "trc_render_kernels.hpp"
 
 TRC_RENDER_NS_BEGIN

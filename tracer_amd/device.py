@@ -144,6 +144,7 @@ def _load(path, hooks=False):
         L.trc_mesh_light_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
         L.trc_debug_last_kernel.argtypes = [vp, C.POINTER(abi.KernelChoice)]
         L.trc_debug_last_residency.argtypes = [vp, C.POINTER(abi.Residency)]
+        L.trc_material_s_f_test.argtypes = [vp, u32, vp, vp, vp, vp, C.c_size_t, C.c_float, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -675,6 +676,18 @@ class Tracer:
         r = abi.Residency()
         self._check(self._L.trc_debug_last_residency(self._h, C.byref(r)), "trc_debug_last_residency")
         return {name: int(getattr(r, name)) for name, _ in abi.Residency._fields_}
+
+    def material_s_f_test(self, types, color, wo, uu, stream, pdf_init=0.0):
+        """(n, 7) float32: wi, attenuation, pdf of the kernels' material_S_F, one lane per input in this order; stream: the Metal lobe
+        through the Beckmann lobes' stream (TRC_MICROFACET_STREAM) or as a branch of its own.  An early-out leaves pdf_init in place."""
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+        color, wo, uu = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, wo, uu))
+        n = len(types)
+        assert types.ndim == 1 and color.shape == (n, 3) and wo.shape == (n, 3) and uu.shape == (n, 2)
+        out = np.empty((n, 7), np.float32)
+        self._check(self._L.trc_material_s_f_test(self._h, 1 if stream else 0, types.ctypes.data, color.ctypes.data, wo.ctypes.data,
+                                                  uu.ctypes.data, n, float(pdf_init), out.ctypes.data), "trc_material_s_f_test")
+        return out
 
     def div_by_test(self, a, b):
         """(fast, plain): 3 quotients per operand pair through the guarded shared-divisor division and through `/`."""
