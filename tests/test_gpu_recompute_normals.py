@@ -11,10 +11,13 @@ import pytest
 
 import morph_ref as mr
 import normals_ref as nr
+import pose_ref as pr
 import refit_ref as rr
 import skin_ref as sr
 from test_gpu_morph_vertices import layouts
 from test_gpu_pose_vertices import bits, oracle_moved
+from test_gpu_pose_vertices import table as pose_table
+from test_gpu_skin_vertices import small_case
 from test_gpu_update_vertices import DEVICE_TREE, MIS, PATH, frame, oracle_frame, same, scene
 from test_morph_cpu import deltas_of
 from test_normals_cpu import MESHES, indices_of, mesh_scene, ranges, rest_of, twisted
@@ -274,6 +277,44 @@ def test_refit_ms_reports_the_family_s_last_call(gpu):
     assert 0.0 < a < 1000.0 and gpu.refit_ms() == a
     gpu.update_vertices(twisted("mem"))
     assert gpu.refit_ms() > a                                           # the same record rewrite and a launch per depth of the tree behind it
+
+
+def test_refit_ms_is_every_call_s_own_whatever_came_before(gpu):
+    """update, normals, pose, normals, skin, normals on one context: every call of the family is timed, the time is read once and then
+    kept (a second read and a read behind a render return it again), and no call's bookkeeping disturbs another's vertices."""
+    idx, poses = indices_of("mem"), pose_table("mem", "ragged")
+    first, b, w, palette = small_case("mem")
+    upload(gpu, "mem")
+    state = {"now": rest_of("mem"), "rest": None}                       # the vertices as they stand; the rest copy (made by the first pose)
+
+    def update():
+        gpu.update_vertices(twisted("mem"))
+        return twisted("mem")
+
+    def normals():
+        gpu.recompute_normals()
+        return nr.recompute(state["now"], idx)
+
+    def pose():
+        state["rest"] = state["now"]
+        gpu.pose_vertices(poses)
+        return pr.pose(state["rest"], state["now"], poses)
+
+    def skin():
+        gpu.skin_bind(b, w, first=first)
+        gpu.skin_vertices(palette)
+        return sr.skin(state["rest"], state["now"], first, b, w, palette)
+
+    for step, call in enumerate((update, normals, pose, normals, skin, normals)):
+        state["now"] = call()
+        ms = gpu.refit_ms()
+        assert 0.0 < ms < 1000.0, (step, ms)
+        assert gpu.refit_ms() == ms, step
+        frame(gpu, 1, PATH)
+        assert gpu.refit_ms() == ms, step
+        assert not differences(gpu.download_vertices(), state["now"]), step
+        if call is not normals:
+            assert gpu.pose_overflows() == 0, step
 
 
 # --------------------------------------------------------------------------------------------------- refusals

@@ -1,4 +1,4 @@
-// morph_check.hpp -- what trc_morph_bind and trc_morph_vertices (trc_refit.hip) refuse before they touch the device: the delta table of
+// morph_check.hpp -- what trc_morph_bind and trc_morph_vertices (trc_deform.hip) refuse before they touch the device: the delta table of
 // a binding and the weights of a frame, and the compaction of the weights into the ACTIVE LIST the kernels walk.  Nothing of HIP is
 // included, so the sanitizer driver (tools/sanitize/driver.cpp) calls the same code with hostile input.  Every target index the kernel
 // uses comes from the active list, which names only k < n_weights == the binding's n_targets <= TRC_MORPH_MAX_TARGETS.

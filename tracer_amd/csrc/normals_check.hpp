@@ -1,4 +1,4 @@
-// normals_check.hpp -- what trc_recompute_normals (trc_refit.hip) decides on the host before it touches the device: whether the vertex
+// normals_check.hpp -- what trc_recompute_normals (trc_normals.hip) decides on the host before it touches the device: whether the vertex
 // range is acceptable, and how many low key bits the sort of the adjacency build has to look at.  Nothing of HIP is included, so a
 // stand-alone CPU program (tests/test_normals_cpu.py's probe) calls the same code.
 #pragma once

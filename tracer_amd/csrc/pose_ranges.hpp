@@ -1,4 +1,4 @@
-// pose_ranges.hpp -- what trc_pose_vertices (trc_refit.hip) refuses before it touches the device: the range table and the matrix
+// pose_ranges.hpp -- what trc_pose_vertices (trc_deform.hip) refuses before it touches the device: the range table and the matrix
 // entries the kernel reads.  Nothing of HIP is included, so the sanitizer driver (tools/sanitize/driver.cpp) calls the same code
 // with hostile tables.
 #pragma once

@@ -1,4 +1,4 @@
-// skin_check.hpp -- what trc_skin_bind and trc_skin_vertices (trc_refit.hip) refuse before they touch the device: the influence table
+// skin_check.hpp -- what trc_skin_bind and trc_skin_vertices (trc_deform.hip) refuse before they touch the device: the influence table
 // of a binding and the bone palette of a frame.  Nothing of HIP is included, so the sanitizer driver (tools/sanitize/driver.cpp) calls
 // the same code with hostile input.  Every bone index the kernel uses has passed both checks: an index of the table is below
 // TRC_SKIN_MAX_BONES and at most *max_bone, and a palette is accepted only when it holds more bones than that.

@@ -144,6 +144,37 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 struct SppmState;   // trc_sppm.hip
 struct DenoiseState;   // trc_denoise.hip
 
+// What the calls that move a scene's vertices keep between them (trc_refit.hip, trc_deform.hip, trc_normals.hip; trc_refit.hpp is what
+// the three share).  Made on demand by the first call that needs it, freed with the scene (trc_refit_free); a rebuild drops `maps` alone
+struct RefitState {
+    struct Maps {                           // follow the tree's topology and numbering (trc_refit_free_maps)
+        uint32_t* d_parent = nullptr;       // [n_nodes] fat node that holds this fat node's box (root: itself)
+        uint32_t* d_refnode = nullptr;      // [n_nodes] device-built trees: this fat node's record in d_bvh_ref
+        uint32_t* d_arrive = nullptr;       // [n_nodes] arrival counters of the single-launch climb (zero between updates)
+        float* d_root = nullptr;            // [12] the refitted root box in words 0..5 (the root's store zeroes 6 and 7); word kPoseCountWord:
+                                            // the overflows of every pose, skin and morph so far, never put back to zero
+        std::vector<uint32_t> levels;       // first fat node of every depth, and n_nodes behind them (the fat nodes are numbered by depth)
+        uint32_t count_seen = 0;            // the counter word as last read back: a call's count is the difference to it
+    } maps;
+    // ev[0], ev[1]: around the kernels of the family's last call, whichever it was; ev[2]: behind the root box's copy to h_readback.
+    // ONE pair serves every call because every entry point opens with trc_flush: the flush settles a pending refit, and with it reads
+    // that refit's time (trc_refit_read_time), before the pair is recorded again.  A trc_recompute_normals leaves nothing pending, so
+    // its time is read when it is asked for, or never
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ms = 0.0f; bool timed = false;    // device time of those kernels (trc_debug_refit_ms); timed: still to be read from ev[0], ev[1]
+    bool pending = false, posed = false;    // ks.root_box still waits for ev[2] (trc_refit_settle); the counter word travels with it
+    uint32_t overflows = 0;                 // of the last pose, skin or morph (trc_debug_pose_overflows)
+    trc_TriangleVertex* d_rest = nullptr;   // the rest copy of d_verts, made by the first pose, skin or morph of a scene
+    trc_pose* d_pose_table = nullptr; size_t pose_table_bytes = 0;      // of the last trc_pose_vertices
+    // trc_skin_bind: vertex first + i has d_influences[i] (null: no binding); trc_morph_bind: target k, vertex first + i has d_deltas[k * count + i]
+    struct Skin { trc_skin_influence* d_influences = nullptr; uint32_t first = 0, count = 0, max_bone = 0; } skin;
+    struct Morph { trc_morph_delta* d_deltas = nullptr; uint32_t first = 0, count = 0, n_targets = 0; } morph;
+    trc_skin_bone* d_palette = nullptr; size_t palette_bytes = 0;       // of the last skin, alone or on top of a morph
+    void* d_morph_active = nullptr; size_t morph_active_bytes = 0;      // the active list of the last morph (morph_check.hpp)
+    // trc_recompute_normals: d_adj_corners[d_adj_offsets[v] .. d_adj_offsets[v + 1]) are the k with d_idx[k] == v, ascending
+    uint32_t* d_adj_offsets = nullptr; uint32_t* d_adj_corners = nullptr;      // [n_vertex + 1], [n_index]
+};
+
 struct trc_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -165,44 +196,10 @@ struct trc_ctx {
     trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh / _sah / _device or trc_rebuild_tree, reference array layout (trc_download_bvh)
     uint32_t n_bvh_ref = 0, lbvh_height = 0;
     float lbvh_build_ms = 0.0f;
-    // trc_update_vertices (trc_refit.hip): the scene's vertex and index arrays, kept beside the blob by every upload
-    // (trc_repack_triangles), and the refit maps, made at the first update of a scene; all freed with the blob (trc_refit_free)
+    // the scene's vertex and index arrays, kept beside the blob by every upload (trc_repack_triangles), and what the calls that move
+    // them keep (RefitState); all freed with the blob (trc_refit_free)
     trc_TriangleVertex* d_verts = nullptr; uint32_t* d_idx = nullptr; uint32_t n_vertex = 0;
-    uint32_t* d_refit_parent = nullptr;     // [n_nodes] fat node that holds this fat node's box (root: itself)
-    uint32_t* d_refit_refnode = nullptr;    // [n_nodes] device-built trees: this fat node's record in d_bvh_ref
-    uint32_t* d_refit_arrive = nullptr;     // [n_nodes] arrival counters of the single-launch climb (zero between updates)
-    float* d_refit_root = nullptr;          // [12] the refitted root box in words 0..5 (the root's store zeroes 6 and 7); word 8: pose overflows
-    std::vector<uint32_t> refit_levels;     // first fat node of every depth, and n_nodes behind them (the fat nodes are numbered by depth)
-    float refit_ms = 0.0f;                  // device time of the last update's kernels (trc_debug_refit_ms)
-    hipEvent_t refit_ev[3] = {nullptr, nullptr, nullptr};      // around the update's kernels; behind the root box's copy to h_readback
-    bool refit_pending = false;             // ks.root_box and refit_ms still wait for refit_ev[2] (trc_refit_settle)
-    // trc_pose_vertices (trc_refit.hip): the rest copy of d_verts, made by the first pose of a scene, and the pose table of the last
-    // call; freed with the scene (trc_refit_free).  The kernel adds its overflows to word kPoseCountWord of d_refit_root, which is
-    // never put back to zero: the count of a call is the difference to what the call before left
-    trc_TriangleVertex* d_rest = nullptr;
-    trc_pose* d_pose_table = nullptr; size_t pose_table_bytes = 0;
-    uint32_t pose_count_seen = 0;           // the counter word as last read back
-    uint32_t pose_overflows = 0;            // of the last trc_pose_vertices (trc_debug_pose_overflows)
-    bool refit_posed = false;               // the pending read-back carries the counter word as well
-    // trc_skin_bind / trc_skin_vertices (trc_refit.hip): the binding's influence table (vertex skin_first + i has d_skin_influences[i];
-    // null: no binding), the largest bone index it names, and the palette of the last skin; freed with the scene (trc_refit_free).
-    // A skin reads d_rest and counts its overflows as a pose does
-    trc_skin_influence* d_skin_influences = nullptr;
-    uint32_t skin_first = 0, skin_count = 0, skin_max_bone = 0;
-    trc_skin_bone* d_skin_palette = nullptr; size_t skin_palette_bytes = 0;
-    // trc_morph_bind / trc_morph_vertices (trc_refit.hip): the binding's delta table, target-major (target k, vertex morph_first + i:
-    // d_morph_deltas[k * morph_count + i]; null: no binding), and the active list of the last morph (morph_check.hpp: 8 B per target
-    // with a non-zero weight); freed with the scene (trc_refit_free), kept by a rebuild.  A morph reads d_rest and counts as a pose does
-    trc_morph_delta* d_morph_deltas = nullptr;
-    uint32_t morph_first = 0, morph_count = 0, morph_targets = 0;
-    void* d_morph_active = nullptr; size_t morph_active_bytes = 0;
-    // trc_recompute_normals (trc_refit.hip): the vertex -> corner adjacency of the index list, made by the first call of a scene --
-    // d_adj_corners[d_adj_offsets[v] .. d_adj_offsets[v + 1]) are the k with d_idx[k] == v, ascending; freed with the scene
-    // (trc_refit_free), kept by a rebuild: the index list never changes.  The call's kernels run between two events of its own
-    uint32_t* d_adj_offsets = nullptr;      // [n_vertex + 1]
-    uint32_t* d_adj_corners = nullptr;      // [n_index]
-    hipEvent_t normals_ev[2] = {nullptr, nullptr};
-    bool normals_timed = false;             // refit_ms is still to be read from normals_ev (trc_debug_refit_ms): this call was the family's last
+    RefitState refit;
     float* d_density = nullptr;      // GridDensity medium (trc_upload_density)
     uint8_t* d_occupancy = nullptr;
     trc_GridDensityInfo dinfo{};
@@ -305,7 +302,7 @@ struct trc_ctx {
     void* h_stage = nullptr;            // pinned staging buffer of host-staged collectives
     size_t h_stage_bytes = 0;
     // 1 KB of pinned host memory (trc_readback_alloc) for the two read-backs that are ASYNCHRONOUS on purpose: the per-level counter block of
-    // trc_upload_scene_sah (sah_build_topology) and the refitted root box of trc_update_vertices (refit_run).  The root box's copy is still
+    // trc_upload_scene_sah (sah_build_topology) and the refitted root box of trc_update_vertices (trc_refit_tail).  The root box's copy is still
     // in flight when trc_update_vertices returns; that is safe only because every entry point calls trc_flush first, which settles it
     // (trc_refit_settle) before anything else writes or reads the buffer -- and why every synchronous read-back goes through h_xfer instead
     uint32_t* h_readback = nullptr;
@@ -338,7 +335,7 @@ struct trc_ctx {
         int replay_chain = 0;           // replay trips in a row (0: TRC_REPLAY_CHAIN)
         int mesh_light_pick = 1;        // TRC_FLAG_MESH_LIGHTS: 0 never picks the mesh's light sample (the BSDF-only estimator)
         int refit_single = 0;           // trc_update_vertices: refit in a single launch (trc_refit.hip)
-        int skin_no_lds = 0;            // trc_skin_vertices: the bones gathered from memory whatever the palette's size (trc_refit.hip)
+        int skin_no_lds = 0;            // trc_skin_vertices: the bones gathered from memory whatever the palette's size (trc_deform.hip)
         int strip_force = 0;            // tests: exactly this many blocks per wavefront (launch_geometry)
     } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
@@ -520,7 +517,7 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
     return TRC_OK;
 }
 trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices / trc_morph_vertices left for later (ks.root_box, the overflow count)
-inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit_pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
+inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit.pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
 void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, skin and morph bindings, the normals' adjacency and the refit maps (no-op when absent)
 void trc_refit_free_maps(trc_ctx* ctx);            // trc_refit.hip: the refit maps alone (parent, level table, record map): the tree's topology changed (trc_rebuild_tree)
 void trc_sppm_order_after_camera(trc_ctx* ctx);   // context stream waits for a camera pass running ahead (no-op when none)
