@@ -20,6 +20,10 @@
 //              [--normals]  beside --spin / --pose / --bend / --morph: after every animation call the smooth normals of the whole mesh are
 //                          derived anew on the device from the vertices as they now stand (trc_recompute_normals); its device time is printed
 //                          beside the animation call's, and the first call, which builds the adjacency, is timed between two trc_synchronize
+//              [--denoise]  beside --spin / --pose / --bend / --morph: the SVGF history follows the moving mesh (trc_denoise_track_motion), every
+//                          frame is denoised (trc_denoise) and the DENOISED frame is what <out> and <out>.k.png hold; per frame the mean
+//                          history length over the hit pixels is printed (1 = no history; it grows by one per frame where the filter
+//                          found the surface again).  Use it with a low --spp: that is what the history is for
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -52,7 +56,7 @@ int main(int argc, char** argv) {
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0;
     double rebuild_ratio = 0.0;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false;
+    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -92,6 +96,7 @@ int main(int argc, char** argv) {
             if (!(rebuild_ratio >= 1.0)) { std::fprintf(stderr, "--rebuild-ratio wants a factor of at least 1, not %s\n", argv[i]); return 2; }
         }
         else if (a == "--normals") normals = true;                              // smooth normals re-derived on the device after every animation call
+        else if (a == "--denoise") denoise = true;                              // SVGF on every frame, the history kept across the animation calls
         else if (a == "--mesh-lights") mesh_lights = true;                     // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
         else if (a == "--triangle-materials") tri_materials = true;            // --pbrt: per-mesh materials instead of material 19
@@ -235,11 +240,44 @@ int main(int argc, char** argv) {
 
     std::vector<uint8_t> rgba8((size_t)W * H * 4);
     float exposure = 0;
-    CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+    // --denoise: the frame's output stage.  Tracking is switched on before the first trc_denoise, so that the history this frame leaves
+    // is the one the first animation frame finds; history_note: what that frame's line of output ends with
+    std::vector<float> history;
+    std::vector<trc_gbuffer_texel> gbuffer;
+    std::string history_note;
+    trc_denoise_params dn;
+    trc_denoise_default_params(&dn);
+    dn.flags = TRC_DENOISE_DEMODULATE;
+    auto denoised_output = [&]() {
+        trc_status rs;
+        if ((rs = trc_denoise(ctx, &dn)) != TRC_OK || (rs = trc_tonemap_denoised(ctx, rgba8.data(), &exposure)) != TRC_OK) return rs;
+        history.resize((size_t)W * H); gbuffer.resize((size_t)W * H);
+        if ((rs = trc_download_history_length(ctx, history.data())) != TRC_OK || (rs = trc_download_gbuffer(ctx, gbuffer.data())) != TRC_OK) return rs;
+        double sum = 0.0; size_t hit = 0;
+        for (size_t i = 0; i < history.size(); ++i)
+            if (gbuffer[i].id != TRC_GBUFFER_MISS) { sum += history[i]; ++hit; }
+        char text[96];
+        std::snprintf(text, sizeof text, ", denoised, mean history length %.2f over %zu hit pixels", hit ? sum / hit : 0.0, hit);
+        history_note = text;
+        return TRC_OK;
+    };
+    // what every animation frame does once its vertices are in place
+    auto animation_frame = [&]() {
+        trc_status rs;
+        if ((rs = trc_clear_accum(ctx)) != TRC_OK || (rs = trc_render(ctx, &prm)) != TRC_OK) return rs;
+        return denoise ? denoised_output() : trc_tonemap(ctx, rgba8.data(), &exposure);
+    };
+    if (denoise) {
+        CHECK(trc_denoise_track_motion(ctx, 1));
+        CHECK(denoised_output());
+    } else {
+        CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+    }
     if (trc_host_write_png(out.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
     std::printf("%s %ux%u %u spp %s: %llu rays, kernel %.2f ms (wall %.2f ms), %.1f Mrays/s, exposure %.4f -> %s\n",
                 scene_name.c_str(), W, H, spp, integ_name.c_str(), (unsigned long long)st.rays, st.kernel_ms, wall_ms,
                 st.rays / st.kernel_ms / 1e3, exposure, out.c_str());
+    if (denoise) std::printf("frame 0%s\n", history_note.c_str());
     // --rebuild-ratio: the cost right after the last build is the yardstick; called after every animation call
     uint32_t rebuilds = 0, cost_reads = 0;
     double built_cost = 0.0;
@@ -313,12 +351,10 @@ int main(int argc, char** argv) {
             const double update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
             CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
-            CHECK(trc_clear_accum(ctx));
-            CHECK(trc_render(ctx, &prm));
-            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            CHECK(animation_frame());
             const std::string name = out + "." + std::to_string(f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("spin %u / %u: trc_update_vertices %.2f ms%s -> %s\n", f, spin, update_ms, normals_note.c_str(), name.c_str());
+            std::printf("spin %u / %u: trc_update_vertices %.2f ms%s%s -> %s\n", f, spin, update_ms, normals_note.c_str(), history_note.c_str(), name.c_str());
         }
     } else if (spin) {
         std::fprintf(stderr, "--spin turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -347,12 +383,10 @@ int main(int argc, char** argv) {
             const double pose_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
             CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
-            CHECK(trc_clear_accum(ctx));
-            CHECK(trc_render(ctx, &prm));
-            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            CHECK(animation_frame());
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("pose %u / %u: trc_pose_vertices %.2f ms%s -> %s\n", f, pose, pose_ms, normals_note.c_str(), name.c_str());
+            std::printf("pose %u / %u: trc_pose_vertices %.2f ms%s%s -> %s\n", f, pose, pose_ms, normals_note.c_str(), history_note.c_str(), name.c_str());
         }
     } else if (pose) {
         std::fprintf(stderr, "--pose turns the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -388,12 +422,10 @@ int main(int argc, char** argv) {
             const double skin_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
             CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
-            CHECK(trc_clear_accum(ctx));
-            CHECK(trc_render(ctx, &prm));
-            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            CHECK(animation_frame());
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("bend %u / %u: trc_skin_vertices %.2f ms%s -> %s\n", f, bend, skin_ms, normals_note.c_str(), name.c_str());
+            std::printf("bend %u / %u: trc_skin_vertices %.2f ms%s%s -> %s\n", f, bend, skin_ms, normals_note.c_str(), history_note.c_str(), name.c_str());
         }
     } else if (bend) {
         std::fprintf(stderr, "--bend bends the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
@@ -437,12 +469,10 @@ int main(int argc, char** argv) {
             const double morph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
             CHECK(recompute_normals());
             CHECK(rebuild_if_worn());
-            CHECK(trc_clear_accum(ctx));
-            CHECK(trc_render(ctx, &prm));
-            CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));
+            CHECK(animation_frame());
             const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
             if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
-            std::printf("morph %u / %u: trc_morph_vertices%s %.2f ms%s -> %s\n", f, morph, bend ? " under two bones" : "", morph_ms, normals_note.c_str(), name.c_str());
+            std::printf("morph %u / %u: trc_morph_vertices%s %.2f ms%s%s -> %s\n", f, morph, bend ? " under two bones" : "", morph_ms, normals_note.c_str(), history_note.c_str(), name.c_str());
         }
     } else if (morph) {
         std::fprintf(stderr, "--morph morphs the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");

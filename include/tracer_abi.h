@@ -62,7 +62,9 @@ extern "C" {
  *     added under 13, the number stays: trc_morph_delta, TRC_MORPH_MAX_TARGETS, trc_morph_bind, trc_morph_vertices (blend shapes on the
  *     device, alone or under the skin of trc_skin_bind in one call; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_recompute_normals (smooth vertex normals re-derived on the device from the mesh as it now
- *     stands; an addition only, nothing existing changed) */
+ *     stands; an addition only, nothing existing changed)
+ *     added under 13, the number stays: trc_motion_texel, trc_denoise_track_motion, trc_download_motion, trc_download_history_length (the SVGF history follows
+ *     surfaces that the calls above move; opt-in, off by default; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -946,6 +948,60 @@ trc_status trc_download_denoised(trc_ctx* ctx, float* rgba /* 4*W*H */);        
 trc_status trc_tonemap_denoised(trc_ctx* ctx, uint8_t* rgba8, float* exposure_out);  /* trc_tonemap's output stage on it */
 trc_status trc_download_gbuffer(trc_ctx* ctx, trc_gbuffer_texel* out /* W*H */);
 trc_status trc_denoise_reset(trc_ctx* ctx);
+/* Motion tracking: the history follows surfaces that move (opt-in; with it off every call is what it was).
+ *
+ * The calls that move a scene in place -- trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices (they move
+ * vertices), trc_recompute_normals and trc_rebuild_tree (they move none) -- drop the history like every other change of the picture:
+ * the frame after one has n = 1 everywhere.  With tracking on these six mark the G-buffer stale and KEEP the history, and the temporal
+ * pass finds a moved surface point where it was.  Every other call that drops the history (step 5's list, trc_upload_triangle_materials,
+ * trc_denoise_reset) drops it as before.
+ *
+ * State.  trc_denoise_track_motion(ctx, on) is a switch of the context like the textures: off at trc_create, kept across
+ * trc_upload_scene* and trc_resize (the two buffers below are not: they go with the scene and the frame).  A call that changes the
+ * switch, either way, drops the history; switching off frees both buffers; a call that leaves it as it is does nothing.
+ * While on, the context holds 16 bytes per vertex (the snapshot) and 16 bytes per pixel (the motion plane) more, and nothing else.
+ * Both are allocated by trc_denoise (the snapshot when the scene has vertices): TRC_ERR_OOM surfaces there, the moving calls gain
+ * no failure mode.
+ *
+ * Snapshot.  While tracking is on, the FIRST of the four vertex-moving calls after a trc_denoise copies the position of every vertex of
+ * the scene, as it stands before that call changes anything, into the snapshot (x, y, z as one 16-byte record per vertex).  Further
+ * moving calls before the next trc_denoise take no new one.  The snapshot is in force for that next trc_denoise and no longer: it
+ * holds every vertex where the previous trc_denoise saw it.  (Before the first trc_denoise with tracking on there is no buffer and no
+ * history: nothing is copied.)
+ *
+ * Motion texel of pixel (x, y), written when trc_denoise rebuilds the G-buffer with a snapshot in force.  o = lookFrom and d are
+ * the G-buffer ray above (d normalised).  Where the primary hit is triangle t: a, b, c = the current positions of the vertices
+ * idxList[3t], idxList[3t + 1], idxList[3t + 2] and a', b', c' their snapshot positions;
+ *   e1 = b - a, e2 = c - a, pvec = cross(d, e2), det = dot(e1, pvec), inv = 1 / det, tvec = o - a, u = dot(tvec, pvec) * inv,
+ *   qvec = cross(tvec, e1), v = dot(d, qvec) * inv, w = (1 - u) - v          (Triangle::hit_test's barycentrics, Triangle.hh)
+ *   prev = (u * b' + v * c') + w * a'                                        (HitRecord.p's expression over the snapshot)
+ * componentwise, with dot(p, q) = (p.x q.x + p.y q.y) + p.z q.z and cross(p, q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z,
+ * p.x q.y - p.y q.x); every operation one binary32 operation in the order written, no contraction, the division correctly rounded.
+ * moved = 1 when any of the nine coordinates of a, b, c compares unequal (!=) to its snapshot value, else 0.  A triangle hit whose
+ * triangle did not move still gets prev, which then has the bits of HitRecord.p.  Every other texel -- a miss, a sphere, square
+ * or cube, and every texel of a trc_denoise with no snapshot in force -- is prev = 0, moved = 0.
+ *
+ * Step 2, amended.  A pixel with moved = 1 always takes the general rule, whatever the two cameras, with P = prev in place of
+ * lookFrom + d * depth; the previous camera is the camera of the last trc_denoise.  Everything after P is step 2 unchanged: q, a, m,
+ * s, u', v', px, py and their validity, zq = length(q), the four taps and weights, the id, depth and normal tests.  A pixel with
+ * moved = 0 takes step 2 as it stands (the one tap under the same camera, P from the depth otherwise).  So with tracking on and
+ * nothing moved every plane has the bits it has with tracking off.
+ *
+ * Not covered: analytic primitives (no call moves them); a surface that appears has no history, its pixels start at n = 1;
+ * lighting that moves lags behind -- the shadow and the reflection of a moved object follow alpha_color, as in the paper; there
+ * is no screen-space motion-vector output; contexts in a group (trc_denoise refuses them). */
+typedef struct trc_motion_texel {
+    float    prev[3];              /* where this pixel's surface point was when the last trc_denoise ran */
+    uint32_t moved;                /* 1: a triangle hit whose triangle moved since then; else 0 */
+} trc_motion_texel;                /* 16 bytes */
+/* TRC_ERR_INVALID_ARG on a NULL context */
+trc_status trc_denoise_track_motion(trc_ctx* ctx, int on);
+/* The plane the last trc_denoise used (all zero when it had no snapshot in force).  TRC_ERR_NO_FRAME before a trc_denoise with
+ * tracking on and whenever tracking is off, TRC_ERR_INVALID_ARG on a NULL argument. */
+trc_status trc_download_motion(trc_ctx* ctx, trc_motion_texel* out /* W*H */);
+/* The history length n of step 2 as the last trc_denoise left it, one float per pixel (1 on a miss): what a host watches to see whether
+ * the history survives its animation.  Tracking on or off.  TRC_ERR_NO_FRAME before a trc_denoise, TRC_ERR_INVALID_ARG on a NULL argument. */
+trc_status trc_download_history_length(trc_ctx* ctx, float* n /* W*H */);
 /* developer diagnostic: the pixel blocks of the last trc_render (x | y << 16, in units of the block edge 1 << *blk_shift)
  * and the duration each one's wavefront measured per sample (shader clocks / (4 spp) -- the sort key of the adaptive launch order); with
  * strips (spp < 8) the costs are per strip; a block that ran in parts (four 4x4 quarters, some of them as four 2x2
@@ -1347,5 +1403,6 @@ TRC_SA(sizeof(trc_CameraRecord) == 112 && offsetof(trc_CameraRecord, position) =
 TRC_SA(sizeof(trc_gbuffer_texel) == 32 && offsetof(trc_gbuffer_texel, normal) == 4 && offsetof(trc_gbuffer_texel, albedo) == 16 &&
        offsetof(trc_gbuffer_texel, id) == 28, "gbuffer texel");
 TRC_SA(sizeof(trc_denoise_params) == 32, "trc_denoise_params");
+TRC_SA(sizeof(trc_motion_texel) == 16, "trc_motion_texel");
 
 #endif /* TRACER_ABI_H */

@@ -228,6 +228,11 @@ class GBufferTexel(C.Structure):
     _fields_ = [("depth", C.c_float), ("normal", C.c_float * 3), ("albedo", C.c_float * 3), ("id", C.c_uint32)]
 
 
+class MotionTexel(C.Structure):
+    """trc_motion_texel: one pixel of the motion plane (trc_denoise_track_motion)"""
+    _fields_ = [("prev", C.c_float * 3), ("moved", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):
     """trc_denoise_params"""
     _fields_ = [("flags", C.c_uint32), ("iterations", C.c_uint32), ("alpha_color", C.c_float), ("alpha_moments", C.c_float),
@@ -282,7 +287,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, DenoiseParams: 32, TreeCost: 32,
+                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -297,6 +302,7 @@ DEVICE_SYMBOLS = [
     "trc_device_info", "trc_device_pci_bus_id", "trc_shard_seed", "trc_group_compose_samples", "trc_group_compose_samples_async", "trc_group_unique_id", "trc_group_init", "trc_group_reduce_accum", "trc_group_reduce_accum_async", "trc_group_allreduce_mean_accum", "trc_download_composed", "trc_group_finalize",
     "trc_group_set_collectives", "trc_debug_set", "trc_debug_block_costs", "trc_debug_launch_shape", "trc_debug_primary_replays",
     "trc_denoise_default_params", "trc_denoise", "trc_download_denoised", "trc_tonemap_denoised", "trc_download_gbuffer", "trc_denoise_reset",
+    "trc_denoise_track_motion", "trc_download_motion", "trc_download_history_length",
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
     "trc_morph_bind", "trc_morph_vertices", "trc_recompute_normals",

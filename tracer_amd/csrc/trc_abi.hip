@@ -398,6 +398,7 @@ void trc_release_scene(trc_ctx* ctx) {
     ctx->has_scene = false;
     trc_mesh_light_free(ctx);
     trc_refit_free(ctx);
+    trc_denoise_scene_released(ctx);
 }
 
 void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s) {
@@ -409,8 +410,10 @@ void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s) {
 }
 
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind) {
-    trc_picture_changed(ctx);
-    if (kind != kSceneVerticesMoved && kind != kSceneTreeRebuilt) trc_forget_costs(ctx);
+    const bool in_place = kind == kSceneVerticesMoved || kind == kSceneNormalsChanged || kind == kSceneTreeRebuilt;
+    if (in_place) trc_denoise_moved(ctx, kind == kSceneVerticesMoved);
+    else trc_picture_changed(ctx);
+    if (!in_place) trc_forget_costs(ctx);
     if (kind == kSceneTreeRebuilt) trc_refit_free_maps(ctx);
     if (kind != kSceneReplaced) { trc_mesh_light_free(ctx); return; }
     ctx->tri_materials = false;

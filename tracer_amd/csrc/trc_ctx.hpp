@@ -295,6 +295,7 @@ struct trc_ctx {
 
     SppmState* sppm = nullptr;       // trc_sppm.hip
     DenoiseState* denoise = nullptr; // trc_denoise.hip (allocated by the first trc_denoise after trc_resize)
+    bool track_motion = false;       // trc_denoise_track_motion: context state like the textures -- survives scene uploads and trc_resize; what it owns lives in `denoise`
 
     // caller-supplied collectives (trc_group_set_collectives) instead of an RCCL communicator
     trc_collectives coll{};
@@ -502,6 +503,11 @@ inline uint32_t trc_scene_min_image(const trc_scene* s) {
     return m;
 }
 void trc_denoise_invalidate(trc_ctx* ctx);   // trc_picture_changed: the G-buffer is stale and the history dropped
+// trc_scene_changed, the kinds that leave every surface where the history can follow it: with tracking on (trc_denoise_track_motion) the
+// G-buffer is stale and the history STAYS, and where `vertices` are about to move and no call has moved any since the last trc_denoise,
+// their positions are copied into the snapshot on the context's stream first.  Tracking off: trc_denoise_invalidate
+void trc_denoise_moved(trc_ctx* ctx, bool vertices);
+void trc_denoise_scene_released(trc_ctx* ctx);      // trc_release_scene: the snapshot is sized by the scene that goes
 // TRC_FLAG_ENV_LIGHT (trc_envlight.hip): build the current map's sampling tables if they are not built (TRC_ERR_OOM: nothing kept), free
 // them, and the kernels' view of them
 trc_status trc_env_light_build(trc_ctx* ctx);
@@ -533,18 +539,23 @@ inline void trc_forget_costs(trc_ctx* ctx) { ctx->cost_valid = false; ctx->d_las
 // trc_scene_changed and by the entry points that change the lighting or the colours alone: trc_set_environment,
 // trc_set_environment_map, trc_upload_textures.
 inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
-// trc_scene_changed (trc_abi.hip): the geometry or its materials changed.  Every kind drops the picture (trc_picture_changed) and the
+// trc_scene_changed (trc_abi.hip): the geometry or its materials changed.  Every kind drops the picture (trc_picture_changed; but see
+// the last three kinds below) and the
 // emissive triangles' sampling tables (TRC_FLAG_MESH_LIGHTS: rebuilt when a launch asks).
 //   kSceneReplaced      trc_upload_scene, upload_device_tree (trc_upload_scene_lbvh / _sah / _device), BEFORE they allocate the new
 //                       scene: also forgets the block costs and releases the old scene (trc_release_scene: blob, reference-layout
 //                       tree, kept vertex / index arrays and refit maps; has_scene false, every triangle material 19 again)
 //                       A device tree upload that fails after that releases what it allocated of the NEW scene too, before it returns
 //   kSceneMaterials     trc_upload_triangle_materials: also forgets the block costs
-//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices: the block costs stay (the picture changed a little, as under a camera that moves a little)
+//   kSceneVerticesMoved trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices, BEFORE anything of theirs that writes a
+//                       vertex is queued: the block costs stay (the picture changed a little, as under a camera that moves a little)
+//   kSceneNormalsChanged trc_recompute_normals: as kSceneVerticesMoved, but no position changes
 //   kSceneTreeRebuilt   trc_rebuild_tree, once the new tree is on its way into the blob: no vertex moved, but a tie in t may now resolve to
 //                       another primitive.  The block costs stay; the refit maps go (trc_refit_free_maps: the next update, pose or skin makes
 //                       them for the new topology); vertex and index arrays, rest copy, bindings and triangle materials stay
-enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneTreeRebuilt };
+// The last three keep the denoiser's history while trc_denoise_track_motion is on (trc_denoise_moved: "moved", "normals changed",
+// "rebuilt" reach the denoiser here and nowhere else); with it off they drop the picture like every other kind.
+enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneNormalsChanged, kSceneTreeRebuilt };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:
 void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload allocates

@@ -69,8 +69,16 @@ TRC_DEV void depth_grad(const float4* gb, uint32_t W, uint32_t H, uint32_t x, ui
 // ---------------------------------------------------------------- G-buffer: the camera pass's primary hit, walked by the
 // production scene_hit (the same instantiation trc_trace_rays' TRC_TRACE_PRODUCTION runs); no RNG is consumed
 // TEX: image textures (trc_upload_textures; hit_color<true> over `tt`, which the other instantiations do not read)
-template <bool LDS, bool TEX = false>
-__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt) {
+// MOTION (trc_denoise_track_motion, a snapshot in force): the motion texel of the pixel besides (header, "Motion tracking"); the other
+// instantiations do not read `mo`
+struct KMotion {
+    const uint32_t* idx;        // the scene's index array: triangle t names vertices idx[3t .. 3t + 2]
+    const float4* snap;         // the snapshot: one float4 per vertex, its position when the last trc_denoise ran
+    float4* plane;              // W*H motion texels: (prev, moved)
+};
+
+template <bool LDS, bool TEX = false, bool MOTION = false>
+__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt, const KMotion mo) {
     const DScene& sc = ks.sc;
     const uint32_t* small_base = stage_scene(sc);
     uint32_t* stack = lane_stack(sc);
@@ -89,6 +97,33 @@ __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam
     const F3 root_min = f3(ks.root_box[0], ks.root_box[1], ks.root_box[2]), root_max = f3(ks.root_box[3], ks.root_box[4], ks.root_box[5]);
     const bool h = scene_hit<LDS, false, false, true, false, false, LDS ? TRC_DEFER_LDS : TRC_DEFER_GLOBAL>(S, root_min, root_max, ray, rec, FLT_MAX, stack, lvstack, cnt);
     const size_t i = (size_t)y * W + x;
+    if (MOTION) {
+        // a triangle winner: its position record and its three indices in one round trip, the three snapshot positions in a second; the
+        // barycentrics are triangle_hit_test's (dev_intersect.hpp) operation by operation, prev is rec.p's expression over the snapshot
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (h && (rec.tag >> kTagIndexBits) == kTagTriangle) {
+            const uint32_t t = rec.tag & kTagIndexMask;
+            const TriPos pos = load_tripos(S, t);
+            const uint32_t i0 = mo.idx[3 * (size_t)t], i1 = mo.idx[3 * (size_t)t + 1], i2 = mo.idx[3 * (size_t)t + 2];
+            const float4 pa = mo.snap[i0], pb = mo.snap[i1], pc = mo.snap[i2];
+            const F3 v0 = f3(pos.a.x, pos.a.y, pos.a.z), v1 = f3(pos.b.x, pos.b.y, pos.b.z), v2 = f3(pos.c.x, pos.c.y, pos.c.z);
+            const F3 e1 = v1 - v0;
+            const F3 e2 = v2 - v0;
+            const F3 pvec = cross(ray.d, e2);
+            const float det = dot(e1, pvec);
+            const float inv = 1 / det;
+            const F3 tvec = ray.o - v0;
+            const float bu = dot(tvec, pvec) * inv;
+            const F3 qvec = cross(tvec, e1);
+            const float bv = dot(ray.d, qvec) * inv;
+            const float bw = 1.0f - bu - bv;
+            const F3 prev = (bu * f3(pb.x, pb.y, pb.z) + bv * f3(pc.x, pc.y, pc.z)) + bw * f3(pa.x, pa.y, pa.z);
+            const bool moved = pos.a.x != pa.x || pos.a.y != pa.y || pos.a.z != pa.z || pos.b.x != pb.x || pos.b.y != pb.y || pos.b.z != pb.z ||
+                               pos.c.x != pc.x || pos.c.y != pc.y || pos.c.z != pc.z;
+            m = make_float4(prev.x, prev.y, prev.z, __uint_as_float(moved ? 1u : 0u));
+        }
+        mo.plane[i] = m;
+    }
     if (!h) {
         gb[2 * i] = make_float4(kInf, 0.0f, 0.0f, 0.0f);
         gb[2 * i + 1] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(TRC_GBUFFER_MISS));
@@ -99,6 +134,14 @@ __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam
     const F3 alb = mat_type(sh, rec.material) == kMatDiffuse ? f3(1.0f) : hit_color<TEX>(S, sh, rec, &tt);     // emitters: 1
     gb[2 * i] = make_float4(rec.t, rec.sn.x, rec.sn.y, rec.sn.z);
     gb[2 * i + 1] = make_float4(alb.x, alb.y, alb.z, __uint_as_float(rec.material));
+}
+
+// the snapshot (trc_denoise_moved): the position of every 32-byte vertex as one float4, w = 0
+__global__ void __launch_bounds__(256) k_snapshot_positions(const float4* __restrict__ verts, uint32_t n, float4* __restrict__ snap) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 v = verts[2 * (size_t)i];
+    snap[i] = make_float4(v.x, v.y, v.z, 0.0f);
 }
 
 // ---------------------------------------------------------------- temporal pass + variance (header steps 1-3)
@@ -113,8 +156,11 @@ struct KTemporal {
     const float4* hist_mom;
     float4* integ;
     float4* mom;
+    const float4* motion;       // MOTION only
 };
 
+// MOTION: k.motion is the plane k_gbuffer<.., .., true> wrote for this frame; a pixel with moved = 1 takes the four-tap rule with P = prev
+template <bool MOTION>
 __global__ void __launch_bounds__(64) k_svgf_temporal(const KTemporal k) {
     const DnParams& p = k.p;
     uint32_t x, y;
@@ -143,7 +189,10 @@ __global__ void __launch_bounds__(64) k_svgf_temporal(const KTemporal k) {
         int ntaps;
         float zq;
         bool ok = true;
-        if (k.same_cam) {
+        float4 mt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (MOTION) mt = k.motion[i];
+        const bool moved = MOTION && __float_as_uint(mt.w) != 0u;
+        if (k.same_cam && !moved) {
             ntaps = 1; tx[0] = (int)x; ty[0] = (int)y; tw[0] = 1.0f; zq = z;
         } else {
             ntaps = 4;
@@ -152,7 +201,7 @@ __global__ void __launch_bounds__(64) k_svgf_temporal(const KTemporal k) {
             const F3 sample = f3(k.cur.cll[0], k.cur.cll[1], k.cur.cll[2]) + f3(k.cur.hor[0], k.cur.hor[1], k.cur.hor[2]) * u +
                               f3(k.cur.ver[0], k.cur.ver[1], k.cur.ver[2]) * v;
             const F3 d = normalize(sample - eye);
-            const F3 P = eye + d * z;
+            const F3 P = moved ? f3(mt.x, mt.y, mt.z) : eye + d * z;
             const F3 pe = f3(k.prev.eye[0], k.prev.eye[1], k.prev.eye[2]);
             const F3 ph = f3(k.prev.hor[0], k.prev.hor[1], k.prev.hor[2]), pv = f3(k.prev.ver[0], k.prev.ver[1], k.prev.ver[2]);
             const F3 q = P - pe;
@@ -348,13 +397,19 @@ struct DenoiseState {
     bool have_hist = false;                    // history of a frame of this scene exists
     DnCam hist_cam{};                          // the camera that frame was taken with
     bool has_output = false;
+    // trc_denoise_track_motion (trc_ctx::track_motion); all of it goes with the frame, the snapshot with the scene too
+    float4* motion = nullptr;                  // W*H motion texels, written by every trc_denoise while tracking is on
+    bool motion_ready = false;                 // ... and one has been: trc_download_motion answers
+    bool motion_zero = false;                  // the plane holds zeros (a denoise with no snapshot in force)
+    float4* snap = nullptr; uint32_t snap_n = 0;      // one position per vertex (allocated by trc_denoise), for snap_n vertices
+    bool snap_live = false;                    // filled by the first moving call since the last trc_denoise: in force for the next
 };
 
 void trc_denoise_release(trc_ctx* ctx) {
     DenoiseState* s = ctx ? ctx->denoise : nullptr;
     if (!s) return;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (float4* b : {s->gb[0], s->gb[1], s->hist_col[0], s->hist_col[1], s->hist_mom[0], s->hist_mom[1], s->integ, s->tmp[0], s->tmp[1], s->out})
+    for (float4* b : {s->gb[0], s->gb[1], s->hist_col[0], s->hist_col[1], s->hist_mom[0], s->hist_mom[1], s->integ, s->tmp[0], s->tmp[1], s->out, s->motion, s->snap})
         (void)hipFree(b);
     delete s;
     ctx->denoise = nullptr;
@@ -364,6 +419,30 @@ void trc_denoise_invalidate(trc_ctx* ctx) {
     if (!ctx || !ctx->denoise) return;
     ctx->denoise->gb_valid = false;
     ctx->denoise->have_hist = false;
+}
+
+// the snapshot and the motion plane (tracking switched off), or the snapshot alone (the scene goes: another vertex count)
+static void motion_free(trc_ctx* ctx, bool plane_too) {
+    DenoiseState* s = ctx->denoise;
+    if (!s || (!s->snap && !(plane_too && s->motion))) return;
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(s->snap); s->snap = nullptr; s->snap_n = 0; s->snap_live = false;
+    if (plane_too) { (void)hipFree(s->motion); s->motion = nullptr; s->motion_ready = s->motion_zero = false; }
+}
+void trc_denoise_scene_released(trc_ctx* ctx) { if (ctx) motion_free(ctx, false); }
+
+// Tracking on: the surfaces moved (or their normals, or the tree), and the temporal pass follows them -- the G-buffer is stale, the
+// history stays.  The first call since the last trc_denoise that moves vertices finds them as that trc_denoise saw them: their positions
+// go into the snapshot, on the context's stream, in front of whatever the caller queues next.  Without a snapshot buffer there is no
+// history to keep either (trc_denoise allocates it before it leaves one)
+void trc_denoise_moved(trc_ctx* ctx, bool vertices) {
+    if (!ctx || !ctx->denoise) return;
+    DenoiseState* s = ctx->denoise;
+    if (!ctx->track_motion || (vertices && (!s->snap || s->snap_n != ctx->n_vertex || !ctx->d_verts))) { trc_denoise_invalidate(ctx); return; }
+    s->gb_valid = false;
+    if (!vertices || s->snap_live) return;
+    hipLaunchKernelGGL(k_snapshot_positions, dim3((s->snap_n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(ctx->d_verts), s->snap_n, s->snap);
+    s->snap_live = true;
 }
 
 static trc_status denoise_alloc(trc_ctx* ctx) {
@@ -377,6 +456,20 @@ static trc_status denoise_alloc(trc_ctx* ctx) {
     for (float4** b : {&s->gb[0], &s->gb[1]}) HIP_TRY(ctx, hipMalloc((void**)b, 2 * plane));
     for (float4** b : {&s->hist_col[0], &s->hist_col[1], &s->hist_mom[0], &s->hist_mom[1], &s->integ, &s->tmp[0], &s->tmp[1], &s->out})
         HIP_TRY(ctx, hipMalloc((void**)b, plane));
+    return TRC_OK;
+}
+
+static trc_status motion_alloc(trc_ctx* ctx) {
+    DenoiseState* s = ctx->denoise;
+    if (!s->motion) {
+        if (hipMalloc((void**)&s->motion, (size_t)s->W * s->H * sizeof(float4)) != hipSuccess) { s->motion = nullptr; (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "trc_denoise: motion plane"); }
+        s->motion_zero = false;
+    }
+    if (s->snap && s->snap_n != ctx->n_vertex) motion_free(ctx, false);
+    if (!s->snap && ctx->n_vertex != 0 && ctx->d_verts) {
+        if (hipMalloc((void**)&s->snap, (size_t)ctx->n_vertex * sizeof(float4)) != hipSuccess) { s->snap = nullptr; (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "trc_denoise: vertex snapshot"); }
+        s->snap_n = ctx->n_vertex; s->snap_live = false;
+    }
     return TRC_OK;
 }
 
@@ -411,6 +504,10 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     { const trc_status as = denoise_alloc(ctx); if (as != TRC_OK) { trc_denoise_release(ctx); return as; } }
     DenoiseState* s = ctx->denoise;
+    if (ctx->track_motion) {                    // what tracking owns: the plane, and the snapshot the next moving call fills
+        const trc_status ms = motion_alloc(ctx);
+        if (ms != TRC_OK) { trc_denoise_release(ctx); return ms; }
+    }
     trc_sppm_order_after_camera(ctx);          // the SPPM camera stream may still be writing the accumulator
 
     DnParams p{};
@@ -423,17 +520,28 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
 
     // G-buffer, lazily: only for another scene, camera or frame size
     const bool rebuild = !s->gb_valid || std::memcmp(&s->gb_cam, &ctx->cam, sizeof(DCamera)) != 0;
+    // a snapshot in force: a moving call filled it since the last trc_denoise, so the G-buffer is stale and this call rebuilds it
+    const bool motion = ctx->track_motion && s->snap_live && rebuild;
     if (rebuild) {
         s->gb_cur ^= 1;
         const size_t lds = trc_dyn_lds_bytes(ctx, true);
         const DnCam cam = dn_cam(ctx->cam);
         TexTable tt{};
         if (ctx->tex_active()) { tt.texels = ctx->d_tex_texels; tt.desc = ctx->d_tex_desc; tt.n = ctx->n_tex; }
-        if (ctx->tex_active()) {            // an active image texture (trc_upload_textures): the albedo plane samples it
-            if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
-            else hipLaunchKernelGGL((k_gbuffer<false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
-        } else if (ctx->lds_scene) hipLaunchKernelGGL(k_gbuffer<true>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
-        else hipLaunchKernelGGL(k_gbuffer<false>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt);
+        const KMotion mo{ctx->d_idx, s->snap, s->motion};
+        if (motion) {
+            float4* gb = s->gb[s->gb_cur];
+            if (ctx->tex_active()) {
+                if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
+                else hipLaunchKernelGGL((k_gbuffer<false, true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
+            } else if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
+            else hipLaunchKernelGGL((k_gbuffer<false, false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
+            s->motion_zero = false;
+        } else if (ctx->tex_active()) {            // an active image texture (trc_upload_textures): the albedo plane samples it
+            if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
+            else hipLaunchKernelGGL((k_gbuffer<false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
+        } else if (ctx->lds_scene) hipLaunchKernelGGL(k_gbuffer<true>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
+        else hipLaunchKernelGGL(k_gbuffer<false>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
         HIP_TRY(ctx, hipGetLastError());
         s->gb_cam = ctx->cam;
         s->gb_valid = true;
@@ -453,8 +561,16 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     const int nh = s->hist_cur ^ 1;
     kt.integ = s->integ;
     kt.mom = s->hist_mom[nh];
-    hipLaunchKernelGGL(k_svgf_temporal, grid, block, 0, ctx->stream, kt);
+    if (ctx->track_motion && !motion && !s->motion_zero) {      // no snapshot in force: the plane of this call is all zero
+        HIP_TRY(ctx, hipMemsetAsync(s->motion, 0, (size_t)s->W * s->H * sizeof(float4), ctx->stream));
+        s->motion_zero = true;
+    }
+    kt.motion = s->motion;
+    if (motion && s->have_hist) hipLaunchKernelGGL(k_svgf_temporal<true>, grid, block, 0, ctx->stream, kt);
+    else hipLaunchKernelGGL(k_svgf_temporal<false>, grid, block, 0, ctx->stream, kt);
     HIP_TRY(ctx, hipGetLastError());
+    s->snap_live = false;                       // in force for this call, and no longer
+    s->motion_ready = ctx->track_motion;
 
     const uint32_t K = prm->iterations;
     if (K == 0) {
@@ -516,6 +632,41 @@ trc_status trc_download_gbuffer(trc_ctx* ctx, trc_gbuffer_texel* out) {
     TRC_TRY(denoise_ready(ctx, "trc_download_gbuffer"));
     static_assert(sizeof(trc_gbuffer_texel) == 2 * sizeof(float4), "one texel = the two float4 of the G-buffer planes");
     return denoise_download(ctx, out, ctx->denoise->gb[ctx->denoise->gb_cur], (size_t)ctx->width * ctx->height * sizeof(trc_gbuffer_texel));
+}
+
+trc_status trc_denoise_track_motion(trc_ctx* ctx, int on) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    const bool want = on != 0;
+    if (want == ctx->track_motion) return TRC_OK;
+    ctx->track_motion = want;
+    if (!ctx->denoise) return TRC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->denoise->have_hist = false;            // either way: the next frame has n = 1 everywhere
+    ctx->denoise->snap_live = false;
+    if (!want) motion_free(ctx, true);
+    return TRC_OK;
+}
+
+trc_status trc_download_motion(trc_ctx* ctx, trc_motion_texel* out) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx || !out) return TRC_ERR_INVALID_ARG;
+    if (!ctx->track_motion || !ctx->d_accum || !ctx->denoise || !ctx->denoise->motion || !ctx->denoise->motion_ready)
+        return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_download_motion before a trc_denoise with tracking on (trc_denoise_track_motion)");
+    static_assert(sizeof(trc_motion_texel) == sizeof(float4), "one texel = one float4 of the motion plane");
+    return denoise_download(ctx, out, ctx->denoise->motion, (size_t)ctx->width * ctx->height * sizeof(trc_motion_texel));
+}
+
+trc_status trc_download_history_length(trc_ctx* ctx, float* n) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx || !n) return TRC_ERR_INVALID_ARG;
+    TRC_TRY(denoise_ready(ctx, "trc_download_history_length"));
+    const DenoiseState* s = ctx->denoise;
+    const size_t px = (size_t)ctx->width * ctx->height;
+    std::vector<float4> moments(px);            // (mu1, mu2, n, 0) per pixel: the third of each is what the caller gets
+    TRC_TRY(denoise_download(ctx, moments.data(), s->hist_mom[s->hist_cur], px * sizeof(float4)));
+    for (size_t i = 0; i < px; ++i) n[i] = moments[i].z;
+    return TRC_OK;
 }
 
 trc_status trc_denoise_reset(trc_ctx* ctx) {

@@ -147,7 +147,7 @@ extern "C" trc_status trc_recompute_normals(trc_ctx* ctx, uint32_t first, uint32
     TRC_TRY(trc_refit_open(ctx));
     hipLaunchKernelGGL(k_vertex_normals, dim3((uint32_t)(((size_t)count + 255) / 256)), dim3(256), 0, ctx->stream, p);
     // from here on the scene changed: what was derived from the old normals goes (the G-buffer's normal plane, the denoiser's history)
-    trc_scene_changed(ctx, kSceneVerticesMoved);
+    trc_scene_changed(ctx, kSceneNormalsChanged);
     trc_refit_launch_triangles(ctx, first, count);
     TRC_TRY(trc_refit_close(ctx));
     if (ctx->cost_valid) { ctx->plan_streak = 0; ctx->cost_fresh_next = true; }      // as after trc_update_vertices: the block costs stay

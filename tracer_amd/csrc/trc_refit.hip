@@ -342,9 +342,10 @@ trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices,
             if (!(std::fabs(vertices[i].v[k]) <= 1e37f)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_update_vertices: position not finite or beyond 1e37");
     TRC_TRY(trc_refit_begin(ctx, "trc_update_vertices"));
     hipStream_t st = ctx->stream;
-    TRC_TRY(trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st));
-    // the copy is queued, so from here on the scene changed: what was derived from the old geometry goes
+    // from here on the scene changed: what was derived from the old geometry goes -- said in front of the copy, which writes the vertices
+    // (trc_denoise_track_motion: the snapshot is of the vertices as they still stand)
     trc_scene_changed(ctx, kSceneVerticesMoved);     // (TRC_FLAG_MESH_LIGHTS: the areas changed)
+    TRC_TRY(trc_copy_to_device(ctx, ctx->d_verts + first, vertices, (size_t)count * sizeof(trc_TriangleVertex), st));
     // a scene that has been posed keeps rest vertices: these are the caller's last values for the range
     if (ctx->refit.d_rest) HIP_TRY(ctx, hipMemcpyAsync(ctx->refit.d_rest + first, ctx->d_verts + first, (size_t)count * sizeof(trc_TriangleVertex), hipMemcpyDeviceToDevice, st));
     TRC_TRY(trc_refit_open(ctx));

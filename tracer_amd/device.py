@@ -117,6 +117,9 @@ def _load(path, hooks=False):
     L.trc_tonemap_denoised.argtypes = [vp, vp, C.POINTER(C.c_float)]
     L.trc_download_gbuffer.argtypes = [vp, vp]
     L.trc_denoise_reset.argtypes = [vp]
+    L.trc_denoise_track_motion.argtypes = [vp, C.c_int]
+    L.trc_download_motion.argtypes = [vp, vp]
+    L.trc_download_history_length.argtypes = [vp, vp]
     L.trc_upload_textures.argtypes = [vp, C.POINTER(abi.Image), u32]
     L.trc_upload_triangle_materials.argtypes = [vp, vp, u32]
     L.trc_update_vertices.argtypes = [vp, vp, u32, u32]
@@ -554,6 +557,23 @@ class Tracer:
 
     def denoise_reset(self):
         self._check(self._L.trc_denoise_reset(self._h), "trc_denoise_reset")
+
+    def denoise_track_motion(self, on=True):
+        """trc_denoise_track_motion: the history follows the surfaces that update / pose / skin / morph_vertices move (off by default)."""
+        self._check(self._L.trc_denoise_track_motion(self._h, 1 if on else 0), "trc_denoise_track_motion")
+
+    def download_motion(self):
+        """(H, W) structured array of trc_motion_texel (tracer_amd.dtypes.MOTION_DTYPE): the plane the last trc_denoise used."""
+        from .dtypes import MOTION_DTYPE
+        out = np.empty((self.height, self.width), dtype=MOTION_DTYPE)
+        self._check(self._L.trc_download_motion(self._h, out.ctypes.data), "trc_download_motion")
+        return out
+
+    def download_history_length(self):
+        """trc_download_history_length: (H, W) float32, the history length n of every pixel as the last trc_denoise left it."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self._L.trc_download_history_length(self._h, out.ctypes.data), "trc_download_history_length")
+        return out
 
     def denoise_state(self):
         """hooks build only: (integrated, history, moments), (H, W, 4) float32 each, as the last trc_denoise left them."""

@@ -34,3 +34,6 @@ assert CAMREC_DTYPE.itemsize == C.sizeof(abi.CameraRecord) and PHOTON_DTYPE.item
 # trc_gbuffer_texel (include/tracer_abi.h): one pixel of the denoiser's G-buffer
 GBUFFER_DTYPE = np.dtype([("depth", np.float32), ("normal", np.float32, 3), ("albedo", np.float32, 3), ("id", np.uint32)])
 assert GBUFFER_DTYPE.itemsize == 32
+# trc_motion_texel (trc_download_motion)
+MOTION_DTYPE = np.dtype([("prev", np.float32, 3), ("moved", np.uint32)])
+assert MOTION_DTYPE.itemsize == 16
