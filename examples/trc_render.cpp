@@ -14,13 +14,16 @@
 //              [--morph N] N frames of two blend shapes with swinging weights: one swells the mesh, one presses it towards its foot
 //                          (trc_morph_bind once, trc_morph_vertices per frame); with --bend each of these frames is the morph AND --bend's
 //                          two bones on top of it in one call; frame k goes to <out>.k.png
+//              [--orbit N] N frames of the config-2 scene (--scene spheres) with its twelve spheres circling the vertical axis through the middle
+//                          of the box, 360 / N degrees per frame: the records are built on the host (trc_host_make_sphere) and sent through
+//                          trc_update_primitives -- no second upload, the tree is refitted in place; frame k goes to <out>.k.png
 //              [--rebuild-ratio R]  beside --spin / --pose / --bend / --morph: after every animation call the tree's cost is read (trc_tree_cost), and
 //                          when (interior + leaf) / root exceeds R times what it was right after the last build, the tree is built anew on the
 //                          device (trc_rebuild_tree, TRC_TREE_SAH); the number of rebuilds is printed at the end
 //              [--normals]  beside --spin / --pose / --bend / --morph: after every animation call the smooth normals of the whole mesh are
 //                          derived anew on the device from the vertices as they now stand (trc_recompute_normals); its device time is printed
 //                          beside the animation call's, and the first call, which builds the adjacency, is timed between two trc_synchronize
-//              [--denoise]  beside --spin / --pose / --bend / --morph: the SVGF history follows the moving mesh (trc_denoise_track_motion), every
+//              [--denoise]  beside --spin / --pose / --bend / --morph / --orbit: the SVGF history follows the moving mesh or spheres (trc_denoise_track_motion), every
 //                          frame is denoised (trc_denoise) and the DENOISED frame is what <out> and <out>.k.png hold; per frame the mean
 //                          history length over the hit pixels is printed (1 = no history; it grows by one per frame where the filter
 //                          found the surface again).  Use it with a low --spp: that is what the history is for
@@ -54,7 +57,7 @@
 int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
-    uint32_t spin = 0, pose = 0, bend = 0, morph = 0;
+    uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
     double rebuild_ratio = 0.0;
     bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
@@ -90,6 +93,11 @@ int main(int argc, char** argv) {
             const int n = std::atoi(argv[++i]);
             if (n <= 0 || n > 100000) { std::fprintf(stderr, "--morph wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
             morph = (uint32_t)n;
+        }
+        else if (a == "--orbit" && i + 1 < argc) {                              // moving primitives: twelve sphere records per frame, trc_update_primitives
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > 100000) { std::fprintf(stderr, "--orbit wants a number of frames from 1 to 100000, not %s\n", argv[i]); return 2; }
+            orbit = (uint32_t)n;
         }
         else if (a == "--rebuild-ratio" && i + 1 < argc) {                   // a fresh tree when the refitted one has worn: trc_tree_cost, trc_rebuild_tree
             rebuild_ratio = std::atof(argv[++i]);
@@ -476,6 +484,39 @@ int main(int argc, char** argv) {
         }
     } else if (morph) {
         std::fprintf(stderr, "--morph morphs the mesh of a --mesh or --pbrt scene: this scene has no triangles\n");
+        trc_destroy(ctx);
+        trc_host_scene_destroy(hs);
+        trc_host_mesh_destroy(mesh);
+        return 1;
+    }
+    if (orbit && kind == TRC_SCENE_CORNELL_SPHERES && pbrt_path.empty() && scene.n_sphere) {
+        // every sphere keeps its height and its distance from the vertical axis through (278, *, 278) and goes round it; the record is what
+        // the scene builder makes for the new centre (the record's radius is the builder's argument + 1e-4: taken off again here)
+        const std::vector<trc_Sphere> rest(scene.sphereList, scene.sphereList + scene.n_sphere);
+        std::vector<trc_Sphere> moved(rest);
+        const uint32_t first_frame = spin + pose + bend + morph;
+        for (uint32_t f = 1; f <= orbit; ++f) {
+            const double a = 6.283185307179586 * f / orbit;
+            const float ca = (float)std::cos(a), sa = (float)std::sin(a);
+            for (size_t i = 0; i < rest.size(); ++i) {
+                const float x = rest[i].center.x - 278.0f, z = rest[i].center.z - 278.0f;
+                const float c[3] = {278.0f + ca * x + sa * z, rest[i].center.y, 278.0f - sa * x + ca * z};
+                trc_host_make_sphere(&moved[i], rest[i].radius - 0.0001f, c, rest[i].material);
+            }
+            trc_primitive_ranges r;
+            std::memset(&r, 0, sizeof r);
+            r.spheres = moved.data(); r.first_sphere = 0; r.n_sphere = scene.n_sphere;
+            const auto u0 = std::chrono::steady_clock::now();
+            CHECK(trc_update_primitives(ctx, &r));
+            const double update_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+            CHECK(rebuild_if_worn());
+            CHECK(animation_frame());
+            const std::string name = out + "." + std::to_string(first_frame + f) + ".png";
+            if (trc_host_write_png(name.c_str(), rgba8.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+            std::printf("orbit %u / %u: trc_update_primitives %.2f ms%s -> %s\n", f, orbit, update_ms, history_note.c_str(), name.c_str());
+        }
+    } else if (orbit) {
+        std::fprintf(stderr, "--orbit moves the spheres of --scene spheres: this scene's tree holds none\n");
         trc_destroy(ctx);
         trc_host_scene_destroy(hs);
         trc_host_mesh_destroy(mesh);

@@ -64,7 +64,10 @@ extern "C" {
  *     added under 13, the number stays: trc_recompute_normals (smooth vertex normals re-derived on the device from the mesh as it now
  *     stands; an addition only, nothing existing changed)
  *     added under 13, the number stays: trc_motion_texel, trc_denoise_track_motion, trc_download_motion, trc_download_history_length (the SVGF history follows
- *     surfaces that the calls above move; opt-in, off by default; additions only, nothing existing changed) */
+ *     surfaces that the calls above move; opt-in, off by default; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_primitive_ranges, trc_update_primitives, trc_host_make_sphere, trc_host_make_square,
+ *     trc_host_make_cube (spheres, squares and cubes moved on the device; with tracking on the history follows them too: the motion
+ *     texel of an analytic hit may now be non-zero; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -552,7 +555,8 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
 /* Moving geometry: replaces vertices [first, first + count) of the uploaded scene's triList by new positions, normals and uv, and
  * refits the tree in place.  The host of an animation calls it once per frame instead of uploading the scene again.
  *  - The topology does not change: parent, left, right, axis, pType and pIndex of every record stay, and so does the child order
- *    of the device's nodes.  The index list and the triangle count stay; spheres, squares and cubes do not move.
+ *    of the device's nodes.  The index list and the triangle count stay; spheres, squares and cubes do not move (they move by
+ *    trc_update_primitives).
  *  - A triangle leaf's box becomes what trc_host_build_node gives, under the identity matrix, for the box of its three CURRENT
  *    vertices (what TRC_TREE_TRIANGLE_LEAVES writes at an upload).  An interior box becomes the component-wise min / max of its two
  *    children's boxes; where the two bounds compare equal (-0 against +0) the right child's is kept, as by trc_host_build_tree.  The
@@ -588,8 +592,51 @@ trc_status trc_upload_triangle_materials(trc_ctx* ctx, const uint32_t* material,
 trc_status trc_update_vertices(trc_ctx* ctx, const trc_TriangleVertex* vertices, uint32_t first, uint32_t count);
 /* device time in ms of the kernels of the last trc_update_vertices (record rewrite + refit, without the transfer).  It reports the
  * device time of the last call of the family -- trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices,
- * trc_recompute_normals (gather + record rewrite; the one-off adjacency build is not in it) -- whichever came last. */
+ * trc_recompute_normals (gather + record rewrite; the one-off adjacency build is not in it), trc_update_primitives (record repack +
+ * refit) -- whichever came last. */
 trc_status trc_debug_refit_ms(trc_ctx* ctx, float* ms);
+/* Moving analytic primitives: replaces spheres [first_sphere, first_sphere + n_sphere), squares [first_square, ..) and cubes
+ * [first_cube, ..) of the uploaded scene's lists by new records and refits the tree in place, once for all three kinds.  The host of
+ * an animation calls it once per frame instead of uploading the scene again: a light square, a sphere or a cube moves without the
+ * mesh beside it being touched.  The records are the reference's PODs, exactly what trc_upload_scene* takes.
+ *  - Records.  Each record is repacked on the device, one thread per primitive, into the device's record with the bits an upload
+ *    gives for it.  Sphere: center, radius, material.  Square: range_i, range_j, value_k, 1 / (2 * di * dj) with di = range_i.y -
+ *    range_i.x and dj = range_j.y - range_j.x (each operation one binary32 operation, 2 * di first, the division correctly rounded),
+ *    the three axes, material.  Cube: the xyz rows of the four inverse_matrix, the four model_matrix and the first three normal_matrix
+ *    columns, box, material.  Nothing else of a record is read, except by the leaf box below.
+ *  - Leaf box.  A primitive's leaf box becomes what trc_host_build_node gives for boundingBOX under model_matrix (sphere, square) or
+ *    box under model_matrix (cube): the eight corners in the order i, j, k, each row ((m0 * x + m1 * y) + m2 * z) + m3 * 1 without
+ *    contraction, into fmin / fmax from +-FLT_MAX, the second operand kept on a tie.  It is written into the slot of the node that
+ *    holds the leaf; for a device-built tree trc_download_bvh returns it in the leaf's record, padding lane 0.  A primitive that no
+ *    leaf names -- the density container cube of the scenes other than TRC_SCENE_CORNELL_VOLUME, the spheres of a scene whose tree
+ *    leaves them out -- gets its record rewritten and nothing else.  (Where two leaves name one primitive, one of them follows.)
+ *  - Refit.  Every interior box and the root's are then recomputed as by trc_update_vertices (same rule, same two kernels, knob
+ *    refit_single); triangle leaves keep their boxes and no triangle record is rewritten.  The topology does not change: parent,
+ *    left, right, axis, pType and pIndex of every record stay, and the number of primitives of each kind stays.
+ *  - Rendering, trc_trace_rays and trc_denoise after the call are what they are after trc_upload_scene of that tree with those
+ *    primitive lists: the same frame, RNG texture and ray counts, bit for bit.  It works on the tree of any upload; trc_rebuild_tree
+ *    after it builds from the new leaf boxes, trc_tree_cost sees them.
+ *  - Kept: vertices and indices, the rest copy, skin and morph bindings, triangle materials, the normals' adjacency, textures, the
+ *    environment, the camera, the density grid, and the launch planner's block costs (as after trc_update_vertices: the next launch
+ *    is one pass ordered by the last launch's raw durations).  The accumulator and the RNG texture are not touched: the caller clears.
+ *  - Dropped: the G-buffer and the denoiser history, as by trc_upload_scene* (with trc_denoise_track_motion on the history is kept
+ *    and follows the primitives: "Motion tracking" below).  The tables of TRC_FLAG_MESH_LIGHTS are freed and rebuilt at the next
+ *    flagged render.
+ *    trc_sppm_frames sees the new geometry at its next call: a consistent SPPM pass restarts with trc_sppm_init.
+ *  - TRC_ERR_NO_SCENE before any upload.  TRC_ERR_INVALID_ARG: r == NULL; a NULL list with a count > 0; first + n beyond the scene's
+ *    count of that kind (the sum is never formed in 32 bits); a material >= the scene's n_material; a square axis > 2; a value
+ *    that is not finite or beyond 1e37 in magnitude among the fields named above, boundingBOX / box and the xyz rows of model_matrix.
+ *    On any of these errors nothing has changed.  All three counts zero is TRC_OK and changes nothing, the denoiser's history included.
+ *  - Launches kept back for coalescing run first.  The records are copied out of the caller's arrays before the call returns; the
+ *    kernels run behind it on the context's stream (the root's box comes back as after trc_update_vertices, and the first call of the
+ *    family on a scene and tree waits once for its maps, which now include 4 bytes per analytic primitive).
+ *  - In a group every rank calls it for itself; it is not collective. */
+typedef struct trc_primitive_ranges {
+    const trc_Sphere* spheres; uint32_t first_sphere, n_sphere;   /* replace sphereList[first .. first+n) */
+    const trc_Square* squares; uint32_t first_square, n_square;
+    const trc_Cube*   cubes;   uint32_t first_cube,   n_cube;
+} trc_primitive_ranges;                                           /* 48 bytes */
+trc_status trc_update_primitives(trc_ctx* ctx, const trc_primitive_ranges* r);
 /* Posed geometry: the rigid (or affine) animation of whole objects, where the host has nothing to say per frame but one matrix per
  * object.  Each trc_pose names vertices [first, first + count) of the scene's triList and the two matrices to put them under; the
  * device computes the posed vertices from a REST copy it keeps, and the record rewrite and refit of trc_update_vertices run behind.
@@ -951,23 +998,25 @@ trc_status trc_denoise_reset(trc_ctx* ctx);
 /* Motion tracking: the history follows surfaces that move (opt-in; with it off every call is what it was).
  *
  * The calls that move a scene in place -- trc_update_vertices, trc_pose_vertices, trc_skin_vertices, trc_morph_vertices (they move
- * vertices), trc_recompute_normals and trc_rebuild_tree (they move none) -- drop the history like every other change of the picture:
- * the frame after one has n = 1 everywhere.  With tracking on these six mark the G-buffer stale and KEEP the history, and the temporal
+ * vertices), trc_update_primitives (it moves spheres, squares and cubes), trc_recompute_normals and trc_rebuild_tree (they move
+ * nothing) -- drop the history like every other change of the picture:
+ * the frame after one has n = 1 everywhere.  With tracking on these seven mark the G-buffer stale and KEEP the history, and the temporal
  * pass finds a moved surface point where it was.  Every other call that drops the history (step 5's list, trc_upload_triangle_materials,
  * trc_denoise_reset) drops it as before.
  *
  * State.  trc_denoise_track_motion(ctx, on) is a switch of the context like the textures: off at trc_create, kept across
  * trc_upload_scene* and trc_resize (the two buffers below are not: they go with the scene and the frame).  A call that changes the
  * switch, either way, drops the history; switching off frees both buffers; a call that leaves it as it is does nothing.
- * While on, the context holds 16 bytes per vertex (the snapshot) and 16 bytes per pixel (the motion plane) more, and nothing else.
- * Both are allocated by trc_denoise (the snapshot when the scene has vertices): TRC_ERR_OOM surfaces there, the moving calls gain
- * no failure mode.
+ * While on, the context holds 16 bytes per vertex and the device's records of the analytic primitives, at most 40 KB (the snapshot),
+ * and 16 bytes per pixel (the motion plane) more, and nothing else.  All are allocated by trc_denoise (the vertex part when the scene
+ * has vertices, the primitive part when it has primitives): TRC_ERR_OOM surfaces there, the moving calls gain no failure mode.
  *
- * Snapshot.  While tracking is on, the FIRST of the four vertex-moving calls after a trc_denoise copies the position of every vertex of
- * the scene, as it stands before that call changes anything, into the snapshot (x, y, z as one 16-byte record per vertex).  Further
- * moving calls before the next trc_denoise take no new one.  The snapshot is in force for that next trc_denoise and no longer: it
- * holds every vertex where the previous trc_denoise saw it.  (Before the first trc_denoise with tracking on there is no buffer and no
- * history: nothing is copied.)
+ * Snapshot.  While tracking is on, the FIRST moving call after a trc_denoise -- one of the four vertex-moving calls or
+ * trc_update_primitives -- copies, as they stand before that call changes anything, the position of every vertex of the scene (x, y, z
+ * as one 16-byte record per vertex) and the device's record of every sphere, square and cube into the snapshot: ONE event for both
+ * kinds of geometry, whichever kind the call moves.  Further moving calls before the next trc_denoise, of either kind, take no new
+ * one.  The snapshot is in force for that next trc_denoise and no longer: it holds every vertex and every primitive where the previous
+ * trc_denoise saw it.  (Before the first trc_denoise with tracking on there is no buffer and no history: nothing is copied.)
  *
  * Motion texel of pixel (x, y), written when trc_denoise rebuilds the G-buffer with a snapshot in force.  o = lookFrom and d are
  * the G-buffer ray above (d normalised).  Where the primary hit is triangle t: a, b, c = the current positions of the vertices
@@ -978,8 +1027,20 @@ trc_status trc_denoise_reset(trc_ctx* ctx);
  * componentwise, with dot(p, q) = (p.x q.x + p.y q.y) + p.z q.z and cross(p, q) = (p.y q.z - p.z q.y, p.z q.x - p.x q.z,
  * p.x q.y - p.y q.x); every operation one binary32 operation in the order written, no contraction, the division correctly rounded.
  * moved = 1 when any of the nine coordinates of a, b, c compares unequal (!=) to its snapshot value, else 0.  A triangle hit whose
- * triangle did not move still gets prev, which then has the bits of HitRecord.p.  Every other texel -- a miss, a sphere, square
- * or cube, and every texel of a trc_denoise with no snapshot in force -- is prev = 0, moved = 0.
+ * triangle did not move still gets prev, which then has the bits of HitRecord.p.
+ * Where the primary hit is an analytic primitive: p = HitRecord.p of the G-buffer walk, primed values are the snapshot's record of
+ * that primitive, unprimed the current one; every operation one binary32 operation in the order written, no contraction, the
+ * divisions correctly rounded.
+ *   sphere  moved = any of c.x, c.y, c.z, r compares != to its snapshot value (r as the record holds it)
+ *           n = ((p.x - c.x) / r, (p.y - c.y) / r, (p.z - c.z) / r);  prev = (c'.x + n.x * r', c'.y + n.y * r', c'.z + n.z * r')
+ *   square  moved = any of range_i.x, range_i.y, range_j.x, range_j.y, value_k compares !=, or one of the three axes differs
+ *           a = p[axis_i], b = p[axis_j], fu = (a - i0) / (i1 - i0), fv = (b - j0) / (j1 - j0); prev = 0, then written in the order
+ *           k', i', j' with the snapshot's axes: prev[k'] = value_k', prev[i'] = i0' + fu * (i1' - i0'), prev[j'] = j0' + fv * (j1' - j0')
+ *   cube    moved = any of the 12 xyz entries of the model_matrix columns or of the inverse_matrix columns compares !=
+ *           q = ((I0 * p.x + I1 * p.y) + I2 * p.z) + I3 with the current inverse columns (its object-space point),
+ *           prev = ((M0' * q.x + M1' * q.y) + M2' * q.z) + M3' with the snapshot's model columns
+ * An analytic winner with moved = 0 gets prev = 0.  Every other texel -- a miss, and every texel of a trc_denoise with no snapshot in
+ * force -- is prev = 0, moved = 0.
  *
  * Step 2, amended.  A pixel with moved = 1 always takes the general rule, whatever the two cameras, with P = prev in place of
  * lookFrom + d * depth; the previous camera is the camera of the last trc_denoise.  Everything after P is step 2 unchanged: q, a, m,
@@ -987,12 +1048,12 @@ trc_status trc_denoise_reset(trc_ctx* ctx);
  * moved = 0 takes step 2 as it stands (the one tap under the same camera, P from the depth otherwise).  So with tracking on and
  * nothing moved every plane has the bits it has with tracking off.
  *
- * Not covered: analytic primitives (no call moves them); a surface that appears has no history, its pixels start at n = 1;
+ * Not covered: a square that turns (it is axis-aligned: its axes may change, a rotation cannot be said); a surface that appears has no history, its pixels start at n = 1;
  * lighting that moves lags behind -- the shadow and the reflection of a moved object follow alpha_color, as in the paper; there
  * is no screen-space motion-vector output; contexts in a group (trc_denoise refuses them). */
 typedef struct trc_motion_texel {
     float    prev[3];              /* where this pixel's surface point was when the last trc_denoise ran */
-    uint32_t moved;                /* 1: a triangle hit whose triangle moved since then; else 0 */
+    uint32_t moved;                /* 1: a triangle hit whose triangle, or a sphere, square or cube hit whose record, changed since then; else 0 */
 } trc_motion_texel;                /* 16 bytes */
 /* TRC_ERR_INVALID_ARG on a NULL context */
 trc_status trc_denoise_track_motion(trc_ctx* ctx, int on);
@@ -1161,7 +1222,7 @@ trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table,
  * the render loop shades replayed hits alone where at least n lanes of the wavefront hold one, at most m such trips between two walks; 0 = the
  * defaults, 1 and 1; 65 lanes = never), "strip_force" (tests only: n > 0 gives every wavefront a strip of exactly n blocks, at any spp and whatever
  * the size of the frame -- "strip_len" asks for a length and is capped so that the GPU keeps 1.5 workgroups per wavefront slot, which on a
- * frame of a few blocks always leaves 1), "refit_single" (trc_update_vertices), "skin_no_lds" (trc_skin_vertices).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
+ * frame of a few blocks always leaves 1), "refit_single" (trc_update_vertices, trc_update_primitives), "skin_no_lds" (trc_skin_vertices).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
 
 /* ------------------------------------------------------------------ */
@@ -1172,6 +1233,14 @@ trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
  * of `box` under model_matrix -> one leaf record */
 void trc_host_build_node(const trc_AABB* box, const trc_float4x4* model_matrix,
                          int32_t pType, uint32_t pIndex, trc_BVH* out_leaf);
+/* The reference's primitive constructors (Tracer.mm:127-172), as the scene builders of this library use them: what a C host fills the
+ * records of trc_update_primitives with.  make_sphere: radius + 1e-4 in the record, boundingBOX = center -+ radius (not inflated),
+ * identity model_matrix.  make_square: boundingBOX padded by 1 / 512 along axis_k, identity model_matrix.  make_cube: the unit box
+ * under model_matrix, inverse_matrix by Gauss-Jordan in double rounded once, normal_matrix its transpose.  Everything else zero. */
+void trc_host_make_sphere(trc_Sphere* out, float radius, const float center[3], uint32_t material);
+void trc_host_make_square(trc_Square* out, uint8_t axis_i, float i0, float i1, uint8_t axis_j, float j0, float j1,
+                          uint8_t axis_k, float k, uint32_t material);
+void trc_host_make_cube(trc_Cube* out, uint32_t material, const trc_float4x4* model_matrix);
 /* BVH::buildTree + BVH::make, BVH.hh:35-269: 10-bucket SAH over the n_leaves
  * leaf records at nodes[0..n_leaves); writes 2*n_leaves-1 nodes (root moved to
  * index 0); `nodes` must have room for 2*n_leaves-1.  Serial post-order

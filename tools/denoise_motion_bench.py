@@ -25,7 +25,7 @@ from tracer_amd.device import Tracer, make_poses  # noqa: E402
 from pose_vertices_bench import turn_about  # noqa: E402
 from update_vertices_bench import FLAGS, med, vertices_of  # noqa: E402
 
-NEW_SYMBOLS = ("trc_denoise_track_motion", "trc_download_motion", "trc_download_history_length")
+NEW_SYMBOLS = ("trc_denoise_track_motion", "trc_download_motion", "trc_download_history_length", "trc_update_primitives")
 
 
 class _Absent:

@@ -18,6 +18,9 @@
 //      weight count off by one, non-finite weights, all-zero weights, and the compaction of the weights into the active list
 //   7. the range check of trc_recompute_normals (tracer_amd/csrc/normals_check.hpp, HIP-free too): the off-by-one, a range that wraps,
 //      the empty range, and the key bits of the adjacency build's sort at the powers of two
+//   8. the checks of trc_update_primitives (tracer_amd/csrc/primitives_check.hpp, HIP-free too) on hostile ranges and records, built by the
+//      host helpers (trc_host_make_sphere / _square / _cube): NULL with a count, first + n that wraps, a material and an axis at the
+//      bound, NaN / infinity / 2e37 in fields that are read and NaN in fields that are not; lists exactly as long as their count
 // "build host code under -fsanitize=thread,address".
 #include <cmath>
 #include <cstdio>
@@ -34,6 +37,7 @@
 #include "../../tracer_amd/csrc/skin_check.hpp"
 #include "../../tracer_amd/csrc/morph_check.hpp"
 #include "../../tracer_amd/csrc/normals_check.hpp"
+#include "../../tracer_amd/csrc/primitives_check.hpp"
 
 static int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "EXPECT failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); ++g_fail; } } while (0)
@@ -291,6 +295,58 @@ static void normals_ranges() {
     EXPECT(trc_normals_key_bits(256) == 8 && trc_normals_key_bits(257) == 9 && trc_normals_key_bits(2601) == 12 && trc_normals_key_bits(0xFFFFFFFFu) == 32);
 }
 
+// ---------------------------------------------------------------- trc_update_primitives' checks
+static void primitive_ranges() {
+    const uint32_t big = 0xFFFFFFFFu, n_material = 20;
+    const float centre[3] = {200.0f, 250.0f, 200.0f};
+    trc_float4x4 model;
+    std::memset(&model, 0, sizeof model);
+    model.columns[0].x = 165.0f; model.columns[1].y = 330.0f; model.columns[2].z = 165.0f; model.columns[3] = {265.0f, 1.0f, 295.0f, 1.0f};
+    // heap arrays exactly as long as the counts: a check that reads one record too many is an overflow the sanitizer sees
+    std::vector<trc_Sphere> sp(3); std::vector<trc_Square> sq(2); std::vector<trc_Cube> cb(1);
+    for (size_t i = 0; i < sp.size(); ++i) trc_host_make_sphere(&sp[i], 40.0f + (float)i, centre, 7u + (uint32_t)i);
+    for (size_t i = 0; i < sq.size(); ++i) trc_host_make_square(&sq[i], 0, 400.0f, 555.0f, 2, 200.0f, 355.0f, 1, 554.9f, 3);
+    trc_host_make_cube(&cb[0], 0, &model);
+    EXPECT(cb[0].inverse_matrix.columns[0].x == 1.0f / 165.0f && cb[0].normal_matrix.columns[1].y == cb[0].inverse_matrix.columns[1].y);
+    auto check = [&](const trc_primitive_ranges& r, uint32_t ns = 12, uint32_t nq = 7, uint32_t nc = 3) { return trc_primitive_ranges_check(&r, ns, nq, nc, n_material); };
+    trc_primitive_ranges all{sp.data(), 9, 3, sq.data(), 5, 2, cb.data(), 2, 1};
+    EXPECT(check(all) == nullptr);
+    EXPECT(trc_primitive_ranges_check(nullptr, 12, 7, 3, n_material) != nullptr);
+    trc_primitive_ranges none{};
+    EXPECT(check(none) == nullptr && check(none, 0, 0, 0) == nullptr);
+    none.first_sphere = none.first_square = none.first_cube = big;                      // n == 0: the range names nothing
+    EXPECT(check(none) == nullptr);
+    { trc_primitive_ranges r = all; r.spheres = nullptr; EXPECT(check(r) != nullptr); }
+    { trc_primitive_ranges r = all; r.squares = nullptr; EXPECT(check(r) != nullptr); }
+    { trc_primitive_ranges r = all; r.cubes = nullptr; EXPECT(check(r) != nullptr); }
+    for (uint32_t first : {10u, 12u, big, big - 1u, big - 2u}) { trc_primitive_ranges r = all; r.first_sphere = first; EXPECT(check(r) != nullptr); }
+    for (uint32_t first : {6u, 7u, big, big - 1u}) { trc_primitive_ranges r = all; r.first_square = first; EXPECT(check(r) != nullptr); }
+    for (uint32_t first : {3u, big}) { trc_primitive_ranges r = all; r.first_cube = first; EXPECT(check(r) != nullptr); }
+    EXPECT(check(all, 11) != nullptr && check(all, 12, 6) != nullptr && check(all, 12, 7, 2) != nullptr && check(all, 0, 0, 0) != nullptr);
+    // a record at the end of each list spoilt in turn, and put right again
+    const float bad[] = {std::nanf(""), INFINITY, -INFINITY, 2e37f, -2e37f};
+    auto spoil = [&](float& field, const char* what) {
+        const float keep = field;
+        for (float b : bad) { field = b; EXPECT(check(all) != nullptr); }
+        field = 1e37f; EXPECT(check(all) == nullptr);
+        field = keep;
+        if (check(all) != nullptr) { std::fprintf(stderr, "primitive_ranges: %s did not recover\n", what); ++g_fail; }
+    };
+    spoil(sp.back().radius, "radius"); spoil(sp.back().center.z, "center"); spoil(sp.back().boundingBOX.mini.y, "sphere box"); spoil(sp.back().model_matrix.columns[3].x, "sphere model");
+    spoil(sq.back().range_i.x, "range_i"); spoil(sq.back().range_j.y, "range_j"); spoil(sq.back().value_k, "value_k"); spoil(sq.back().boundingBOX.maxi.z, "square box");
+    spoil(sq.back().model_matrix.columns[0].y, "square model");
+    spoil(cb.back().inverse_matrix.columns[3].z, "inverse"); spoil(cb.back().model_matrix.columns[2].x, "model"); spoil(cb.back().normal_matrix.columns[2].z, "normal");
+    spoil(cb.back().box.maxi.x, "cube box");
+    sp.back().inverse_matrix.columns[1].y = std::nanf(""); sq.back().normal_matrix.columns[0].x = INFINITY; cb.back().normal_matrix.columns[3].x = std::nanf("");
+    cb.back().model_matrix.columns[1].w = std::nanf("");                             // fields nobody reads
+    EXPECT(check(all) == nullptr);
+    sp.back().material = n_material; EXPECT(check(all) != nullptr); sp.back().material = n_material - 1; EXPECT(check(all) == nullptr);
+    sq.back().material = big; EXPECT(check(all) != nullptr); sq.back().material = 0;
+    cb.back().material = n_material; EXPECT(check(all) != nullptr); cb.back().material = 0;
+    for (uint8_t* axis : {&sq.back().axis_i, &sq.back().axis_j, &sq.back().axis_k}) { const uint8_t keep = *axis; *axis = 3; EXPECT(check(all) != nullptr); *axis = 255; EXPECT(check(all) != nullptr); *axis = keep; }
+    EXPECT(check(all) == nullptr);
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -360,6 +416,7 @@ int main(int argc, char** argv) {
     skin_tables();
     morph_tables();
     normals_ranges();
+    primitive_ranges();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

@@ -104,6 +104,12 @@ class Pose(C.Structure):         # trc_pose: one vertex range and its two matric
                 ("model_matrix", float4x4), ("normal_matrix", float4x4)]
 
 
+class PrimitiveRanges(C.Structure):   # trc_primitive_ranges: the three record lists of one trc_update_primitives
+    _fields_ = [("spheres", C.POINTER(Sphere)), ("first_sphere", C.c_uint32), ("n_sphere", C.c_uint32),
+                ("squares", C.POINTER(Square)), ("first_square", C.c_uint32), ("n_square", C.c_uint32),
+                ("cubes", C.POINTER(Cube)), ("first_cube", C.c_uint32), ("n_cube", C.c_uint32)]
+
+
 class SkinInfluence(C.Structure):   # trc_skin_influence: the four (bone, weight) pairs of one bound vertex (trc_skin_bind)
     _fields_ = [("bone", C.c_uint32 * 4), ("weight", C.c_float * 4)]
 
@@ -287,7 +293,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32,
+                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -306,7 +312,7 @@ DEVICE_SYMBOLS = [
     "trc_upload_textures", "trc_upload_triangle_materials", "trc_update_vertices", "trc_debug_refit_ms",
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
     "trc_morph_bind", "trc_morph_vertices", "trc_recompute_normals",
-    "trc_rebuild_tree", "trc_tree_cost",
+    "trc_rebuild_tree", "trc_tree_cost", "trc_update_primitives",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
@@ -319,4 +325,5 @@ HOST_SYMBOLS = [
     "trc_host_mesh_view", "trc_host_mesh_destroy", "trc_host_make_density_info", "trc_host_make_cloud",
     "trc_host_load_density_pbrt", "trc_host_free", "trc_host_write_png", "trc_host_sobol_matrices32",
     "trc_host_sobol_interval_tables", "trc_host_load_png", "trc_host_scene_load_pbrt_flags", "trc_host_scene_triangle_materials",
+    "trc_host_make_sphere", "trc_host_make_square", "trc_host_make_cube",
 ]

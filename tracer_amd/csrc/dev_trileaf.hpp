@@ -38,4 +38,27 @@ __device__ __forceinline__ void triangle_leaf_box(const trc_TriangleVertex& a, c
             }
 }
 
+// BVH::buildNode for an analytic primitive (trc_host_build_node): the eight corners of `box` in the order i, j, k under the xyz rows
+// of `m`, each row ((m0 * x + m1 * y) + m2 * z) + m3 * 1, into fmin / fmax from +-FLT_MAX with the second operand kept on a tie
+__device__ __forceinline__ void primitive_leaf_box(const trc_AABB& box, const trc_float4x4& m, float mn[3], float mx[3]) {
+    const float ele[2][3] = {{box.mini.x, box.mini.y, box.mini.z}, {box.maxi.x, box.maxi.y, box.maxi.z}};
+    const float col[4][3] = {{m.columns[0].x, m.columns[0].y, m.columns[0].z}, {m.columns[1].x, m.columns[1].y, m.columns[1].z},
+                             {m.columns[2].x, m.columns[2].y, m.columns[2].z}, {m.columns[3].x, m.columns[3].y, m.columns[3].z}};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { mn[q] = FLT_MAX; mx[q] = -FLT_MAX; }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float x = ele[i][0], y = ele[j][1], z = ele[k][2];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float w = col[0][q] * x + col[1][q] * y + col[2][q] * z + col[3][q] * 1.0f;
+                    mn[q] = mn[q] < w ? mn[q] : w; mx[q] = mx[q] > w ? mx[q] : w;
+                }
+            }
+}
+
 }  // namespace trcdev

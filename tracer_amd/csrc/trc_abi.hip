@@ -410,8 +410,8 @@ void trc_adopt_scene(trc_ctx* ctx, KScene ks, const trc_scene* s) {
 }
 
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind) {
-    const bool in_place = kind == kSceneVerticesMoved || kind == kSceneNormalsChanged || kind == kSceneTreeRebuilt;
-    if (in_place) trc_denoise_moved(ctx, kind == kSceneVerticesMoved);
+    const bool in_place = kind == kSceneVerticesMoved || kind == kSceneNormalsChanged || kind == kSceneTreeRebuilt || kind == kScenePrimitivesMoved;
+    if (in_place) trc_denoise_moved(ctx, kind == kSceneVerticesMoved || kind == kScenePrimitivesMoved);
     else trc_picture_changed(ctx);
     if (!in_place) trc_forget_costs(ctx);
     if (kind == kSceneTreeRebuilt) trc_refit_free_maps(ctx);

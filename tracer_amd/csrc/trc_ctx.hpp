@@ -153,6 +153,7 @@ struct RefitState {
         uint32_t* d_arrive = nullptr;       // [n_nodes] arrival counters of the single-launch climb (zero between updates)
         float* d_root = nullptr;            // [12] the refitted root box in words 0..5 (the root's store zeroes 6 and 7); word kPoseCountWord:
                                             // the overflows of every pose, skin and morph so far, never put back to zero
+        uint32_t* d_primslot = nullptr;     // [n_spheres + n_squares + n_cubes] in that order: 2 * fat node + slot of the leaf that names the primitive, kTagNone: no leaf does
         std::vector<uint32_t> levels;       // first fat node of every depth, and n_nodes behind them (the fat nodes are numbered by depth)
         uint32_t count_seen = 0;            // the counter word as last read back: a call's count is the difference to it
     } maps;
@@ -171,6 +172,7 @@ struct RefitState {
     struct Morph { trc_morph_delta* d_deltas = nullptr; uint32_t first = 0, count = 0, n_targets = 0; } morph;
     trc_skin_bone* d_palette = nullptr; size_t palette_bytes = 0;       // of the last skin, alone or on top of a morph
     void* d_morph_active = nullptr; size_t morph_active_bytes = 0;      // the active list of the last morph (morph_check.hpp)
+    void* d_prim_stage = nullptr; size_t prim_stage_bytes = 0;          // the caller's records of the last trc_update_primitives: spheres, squares, cubes
     // trc_recompute_normals: d_adj_corners[d_adj_offsets[v] .. d_adj_offsets[v + 1]) are the k with d_idx[k] == v, ascending
     uint32_t* d_adj_offsets = nullptr; uint32_t* d_adj_corners = nullptr;      // [n_vertex + 1], [n_index]
 };
@@ -504,9 +506,10 @@ inline uint32_t trc_scene_min_image(const trc_scene* s) {
 }
 void trc_denoise_invalidate(trc_ctx* ctx);   // trc_picture_changed: the G-buffer is stale and the history dropped
 // trc_scene_changed, the kinds that leave every surface where the history can follow it: with tracking on (trc_denoise_track_motion) the
-// G-buffer is stale and the history STAYS, and where `vertices` are about to move and no call has moved any since the last trc_denoise,
-// their positions are copied into the snapshot on the context's stream first.  Tracking off: trc_denoise_invalidate
-void trc_denoise_moved(trc_ctx* ctx, bool vertices);
+// G-buffer is stale and the history STAYS, and where `geometry` (vertices or analytic primitives) is about to move and no call has moved any
+// since the last trc_denoise, the vertex positions and the blob's primitive section are copied into the snapshot on the context's stream
+// first.  Tracking off: trc_denoise_invalidate
+void trc_denoise_moved(trc_ctx* ctx, bool geometry);
 void trc_denoise_scene_released(trc_ctx* ctx);      // trc_release_scene: the snapshot is sized by the scene that goes
 // TRC_FLAG_ENV_LIGHT (trc_envlight.hip): build the current map's sampling tables if they are not built (TRC_ERR_OOM: nothing kept), free
 // them, and the kernels' view of them
@@ -522,7 +525,7 @@ inline trc_status trc_readback_alloc(trc_ctx* ctx) {    // ctx->h_readback, once
     if (!ctx->h_readback) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_readback, kReadbackBytes, hipHostMallocDefault));
     return TRC_OK;
 }
-trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices / trc_morph_vertices left for later (ks.root_box, the overflow count)
+trc_status trc_refit_settle_pending(trc_ctx* ctx); // trc_refit.hip: what the last trc_update_vertices / trc_pose_vertices / trc_skin_vertices / trc_morph_vertices / trc_update_primitives left for later (ks.root_box, the overflow count)
 inline trc_status trc_refit_settle(trc_ctx* ctx) { return ctx->refit.pending ? trc_refit_settle_pending(ctx) : TRC_OK; }
 void trc_refit_free(trc_ctx* ctx);                 // trc_refit.hip: the kept vertex / index arrays, rest copy, skin and morph bindings, the normals' adjacency and the refit maps (no-op when absent)
 void trc_refit_free_maps(trc_ctx* ctx);            // trc_refit.hip: the refit maps alone (parent, level table, record map): the tree's topology changed (trc_rebuild_tree)
@@ -553,9 +556,11 @@ inline void trc_picture_changed(trc_ctx* ctx) { trc_denoise_invalidate(ctx); }
 //   kSceneTreeRebuilt   trc_rebuild_tree, once the new tree is on its way into the blob: no vertex moved, but a tie in t may now resolve to
 //                       another primitive.  The block costs stay; the refit maps go (trc_refit_free_maps: the next update, pose or skin makes
 //                       them for the new topology); vertex and index arrays, rest copy, bindings and triangle materials stay
-// The last three keep the denoiser's history while trc_denoise_track_motion is on (trc_denoise_moved: "moved", "normals changed",
+//   kScenePrimitivesMoved trc_update_primitives, BEFORE its kernel is queued: in place like kSceneVerticesMoved -- the block costs stay, the
+//                       mesh-light tables go
+// The last four keep the denoiser's history while trc_denoise_track_motion is on (trc_denoise_moved: "moved" of either kind, "normals changed",
 // "rebuilt" reach the denoiser here and nowhere else); with it off they drop the picture like every other kind.
-enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneNormalsChanged, kSceneTreeRebuilt };
+enum SceneChange { kSceneReplaced, kSceneMaterials, kSceneVerticesMoved, kSceneNormalsChanged, kSceneTreeRebuilt, kScenePrimitivesMoved };
 void trc_scene_changed(trc_ctx* ctx, SceneChange kind);
 // Each device buffer is freed and nulled in one place, for the entry point that replaces it and for trc_destroy alike:
 void trc_release_scene(trc_ctx* ctx);    // trc_abi.hip: what a scene upload allocates

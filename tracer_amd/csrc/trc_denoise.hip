@@ -74,8 +74,53 @@ TRC_DEV void depth_grad(const float4* gb, uint32_t W, uint32_t H, uint32_t x, ui
 struct KMotion {
     const uint32_t* idx;        // the scene's index array: triangle t names vertices idx[3t .. 3t + 2]
     const float4* snap;         // the snapshot: one float4 per vertex, its position when the last trc_denoise ran
+    const uint32_t* psnap;      // ... and the blob's primitive section [off_spheres, off_materials) as it stood then (null: no primitives)
     float4* plane;              // W*H motion texels: (prev, moved)
 };
+TRC_DEV float pick(const F3& a, uint32_t axis) { return axis == 0u ? a.x : axis == 1u ? a.y : a.z; }
+TRC_DEV void put(F3& a, uint32_t axis, float v) { if (axis == 0u) a.x = v; else if (axis == 1u) a.y = v; else a.z = v; }
+// The motion texel of an analytic winner (header, "Motion tracking"): where the point rec.p of the primitive was under the snapshot's
+// record -- the same direction from a sphere's centre, the same fractions of a square's ranges, the same object-space point of a cube.
+// The current record is the staged one (LDS), the snapshot's comes from memory.  moved = 0: the all-zero texel
+TRC_DEV float4 analytic_motion(const SceneRef& S, const uint32_t* psnap, const HitRec& rec) {
+    const uint32_t type = rec.tag >> kTagIndexBits, index = rec.tag & kTagIndexMask;
+    const F3 p = rec.p;
+    bool moved;
+    F3 prev;
+    if (type == 0u) {                                   // TRC_PRIM_SPHERE
+        const uint32_t off = S.off_spheres + index * kSphereDwords;
+        const float4 c = ld4_lds(S.small_base + off), s = ld4_global(psnap + (off - S.off_spheres));
+        moved = c.x != s.x || c.y != s.y || c.z != s.z || c.w != s.w;
+        const F3 n = f3((p.x - c.x) / c.w, (p.y - c.y) / c.w, (p.z - c.z) / c.w);
+        prev = f3(s.x + n.x * s.w, s.y + n.y * s.w, s.z + n.z * s.w);
+    } else if (type == 1u) {                            // TRC_PRIM_SQUARE
+        const uint32_t off = S.off_squares + index * kSquareDwords;
+        const float4 rg = ld4_lds(S.small_base + off), kx = ld4_lds(S.small_base + off + 4);
+        const float4 rs = ld4_global(psnap + (off - S.off_spheres)), ks = ld4_global(psnap + (off - S.off_spheres) + 4);
+        const uint32_t axes = __float_as_uint(kx.z), axes_s = __float_as_uint(ks.z);
+        moved = rg.x != rs.x || rg.y != rs.y || rg.z != rs.z || rg.w != rs.w || kx.x != ks.x || axes != axes_s;
+        const float a = pick(p, axes & 3u), b = pick(p, (axes >> 2) & 3u);
+        const float fu = (a - rg.x) / (rg.y - rg.x), fv = (b - rg.z) / (rg.w - rg.z);
+        prev = f3(0.0f);
+        put(prev, (axes_s >> 4) & 3u, ks.x);
+        put(prev, axes_s & 3u, rs.x + fu * (rs.y - rs.x));
+        put(prev, (axes_s >> 2) & 3u, rs.z + fv * (rs.w - rs.z));
+    } else {                                            // TRC_PRIM_CUBE: inverse columns in dwords 0..11, model columns in 12..23
+        const uint32_t off = S.off_cubes + index * kCubeDwords;
+        const uint32_t* cb = S.small_base + off;
+        const uint32_t* cs = psnap + (off - S.off_spheres);
+        const float4 i0 = ld4_lds(cb), i1 = ld4_lds(cb + 4), i2 = ld4_lds(cb + 8), m0 = ld4_lds(cb + 12), m1 = ld4_lds(cb + 16), m2 = ld4_lds(cb + 20);
+        const float4 j0 = ld4_global(cs), j1 = ld4_global(cs + 4), j2 = ld4_global(cs + 8), n0 = ld4_global(cs + 12), n1 = ld4_global(cs + 16), n2 = ld4_global(cs + 20);
+        moved = i0.x != j0.x || i0.y != j0.y || i0.z != j0.z || i0.w != j0.w || i1.x != j1.x || i1.y != j1.y || i1.z != j1.z || i1.w != j1.w ||
+                i2.x != j2.x || i2.y != j2.y || i2.z != j2.z || i2.w != j2.w || m0.x != n0.x || m0.y != n0.y || m0.z != n0.z || m0.w != n0.w ||
+                m1.x != n1.x || m1.y != n1.y || m1.z != n1.z || m1.w != n1.w || m2.x != n2.x || m2.y != n2.y || m2.z != n2.z || m2.w != n2.w;
+        const F3 ic0 = f3(i0.x, i0.y, i0.z), ic1 = f3(i0.w, i1.x, i1.y), ic2 = f3(i1.z, i1.w, i2.x), ic3 = f3(i2.y, i2.z, i2.w);
+        const F3 mc0 = f3(n0.x, n0.y, n0.z), mc1 = f3(n0.w, n1.x, n1.y), mc2 = f3(n1.z, n1.w, n2.x), mc3 = f3(n2.y, n2.z, n2.w);
+        const F3 q = ((ic0 * p.x + ic1 * p.y) + ic2 * p.z) + ic3;
+        prev = ((mc0 * q.x + mc1 * q.y) + mc2 * q.z) + mc3;
+    }
+    return moved ? make_float4(prev.x, prev.y, prev.z, __uint_as_float(1u)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
 
 template <bool LDS, bool TEX = false, bool MOTION = false>
 __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt, const KMotion mo) {
@@ -98,7 +143,7 @@ __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam
     const bool h = scene_hit<LDS, false, false, true, false, false, LDS ? TRC_DEFER_LDS : TRC_DEFER_GLOBAL>(S, root_min, root_max, ray, rec, FLT_MAX, stack, lvstack, cnt);
     const size_t i = (size_t)y * W + x;
     if (MOTION) {
-        // a triangle winner: its position record and its three indices in one round trip, the three snapshot positions in a second; the
+        // an analytic winner: analytic_motion.  A triangle winner: its position record and its three indices in one round trip, the three snapshot positions in a second; the
         // barycentrics are triangle_hit_test's (dev_intersect.hpp) operation by operation, prev is rec.p's expression over the snapshot
         float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (h && (rec.tag >> kTagIndexBits) == kTagTriangle) {
@@ -121,6 +166,8 @@ __global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam
             const bool moved = pos.a.x != pa.x || pos.a.y != pa.y || pos.a.z != pa.z || pos.b.x != pb.x || pos.b.y != pb.y || pos.b.z != pb.z ||
                                pos.c.x != pc.x || pos.c.y != pc.y || pos.c.z != pc.z;
             m = make_float4(prev.x, prev.y, prev.z, __uint_as_float(moved ? 1u : 0u));
+        } else if (h && mo.psnap) {
+            m = analytic_motion(S, mo.psnap, rec);
         }
         mo.plane[i] = m;
     }
@@ -402,7 +449,8 @@ struct DenoiseState {
     bool motion_ready = false;                 // ... and one has been: trc_download_motion answers
     bool motion_zero = false;                  // the plane holds zeros (a denoise with no snapshot in force)
     float4* snap = nullptr; uint32_t snap_n = 0;      // one position per vertex (allocated by trc_denoise), for snap_n vertices
-    bool snap_live = false;                    // filled by the first moving call since the last trc_denoise: in force for the next
+    uint32_t* psnap = nullptr; uint32_t psnap_dwords = 0;      // the blob's primitive section (allocated by trc_denoise where the scene has one)
+    bool snap_live = false;                    // both filled by the first moving call since the last trc_denoise: in force for the next
 };
 
 void trc_denoise_release(trc_ctx* ctx) {
@@ -411,6 +459,7 @@ void trc_denoise_release(trc_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (float4* b : {s->gb[0], s->gb[1], s->hist_col[0], s->hist_col[1], s->hist_mom[0], s->hist_mom[1], s->integ, s->tmp[0], s->tmp[1], s->out, s->motion, s->snap})
         (void)hipFree(b);
+    (void)hipFree(s->psnap);
     delete s;
     ctx->denoise = nullptr;
 }
@@ -421,27 +470,37 @@ void trc_denoise_invalidate(trc_ctx* ctx) {
     ctx->denoise->have_hist = false;
 }
 
-// the snapshot and the motion plane (tracking switched off), or the snapshot alone (the scene goes: another vertex count)
+// the snapshots and the motion plane (tracking switched off), or the snapshots alone (the scene goes: another vertex count, another primitive section)
 static void motion_free(trc_ctx* ctx, bool plane_too) {
     DenoiseState* s = ctx->denoise;
-    if (!s || (!s->snap && !(plane_too && s->motion))) return;
+    if (!s || (!s->snap && !s->psnap && !(plane_too && s->motion))) return;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(s->snap); s->snap = nullptr; s->snap_n = 0; s->snap_live = false;
+    (void)hipFree(s->psnap); s->psnap = nullptr; s->psnap_dwords = 0;
     if (plane_too) { (void)hipFree(s->motion); s->motion = nullptr; s->motion_ready = s->motion_zero = false; }
 }
 void trc_denoise_scene_released(trc_ctx* ctx) { if (ctx) motion_free(ctx, false); }
 
+static uint32_t primitive_section_dwords(const trc_ctx* ctx) { return ctx->ks.sc.off_materials - ctx->ks.sc.off_spheres; }
+static bool scene_has_vertices(const trc_ctx* ctx) { return ctx->n_vertex != 0 && ctx->d_verts; }
+
 // Tracking on: the surfaces moved (or their normals, or the tree), and the temporal pass follows them -- the G-buffer is stale, the
-// history stays.  The first call since the last trc_denoise that moves vertices finds them as that trc_denoise saw them: their positions
-// go into the snapshot, on the context's stream, in front of whatever the caller queues next.  Without a snapshot buffer there is no
-// history to keep either (trc_denoise allocates it before it leaves one)
-void trc_denoise_moved(trc_ctx* ctx, bool vertices) {
+// history stays.  The first call since the last trc_denoise that moves geometry (vertices or analytic primitives) finds all of it as that
+// trc_denoise saw it: the vertex positions and the blob's primitive section go into the snapshot, on the context's stream, in front of
+// whatever the caller queues next.  ONE event for both kinds: a later call of the other kind takes no second snapshot.  Without the
+// snapshot buffers there is no history to keep either (trc_denoise allocates them before it leaves one)
+void trc_denoise_moved(trc_ctx* ctx, bool geometry) {
     if (!ctx || !ctx->denoise) return;
     DenoiseState* s = ctx->denoise;
-    if (!ctx->track_motion || (vertices && (!s->snap || s->snap_n != ctx->n_vertex || !ctx->d_verts))) { trc_denoise_invalidate(ctx); return; }
+    const uint32_t prim_dwords = primitive_section_dwords(ctx);
+    const bool buffers = (!scene_has_vertices(ctx) || (s->snap && s->snap_n == ctx->n_vertex)) && (prim_dwords == 0 || (s->psnap && s->psnap_dwords == prim_dwords));
+    if (!ctx->track_motion || (geometry && !buffers)) { trc_denoise_invalidate(ctx); return; }
     s->gb_valid = false;
-    if (!vertices || s->snap_live) return;
-    hipLaunchKernelGGL(k_snapshot_positions, dim3((s->snap_n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(ctx->d_verts), s->snap_n, s->snap);
+    if (!geometry || s->snap_live) return;
+    if (scene_has_vertices(ctx))
+        hipLaunchKernelGGL(k_snapshot_positions, dim3((s->snap_n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(ctx->d_verts), s->snap_n, s->snap);
+    if (prim_dwords != 0)
+        (void)hipMemcpyAsync(s->psnap, ctx->d_blob + ctx->ks.sc.off_spheres, (size_t)prim_dwords * 4, hipMemcpyDeviceToDevice, ctx->stream);
     s->snap_live = true;
 }
 
@@ -469,6 +528,12 @@ static trc_status motion_alloc(trc_ctx* ctx) {
     if (!s->snap && ctx->n_vertex != 0 && ctx->d_verts) {
         if (hipMalloc((void**)&s->snap, (size_t)ctx->n_vertex * sizeof(float4)) != hipSuccess) { s->snap = nullptr; (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "trc_denoise: vertex snapshot"); }
         s->snap_n = ctx->n_vertex; s->snap_live = false;
+    }
+    const uint32_t prim_dwords = primitive_section_dwords(ctx);
+    if (s->psnap && s->psnap_dwords != prim_dwords) motion_free(ctx, false);
+    if (!s->psnap && prim_dwords != 0) {
+        if (hipMalloc((void**)&s->psnap, (size_t)prim_dwords * 4) != hipSuccess) { s->psnap = nullptr; (void)hipGetLastError(); return trc_fail(ctx, TRC_ERR_OOM, "trc_denoise: primitive snapshot"); }
+        s->psnap_dwords = prim_dwords; s->snap_live = false;
     }
     return TRC_OK;
 }
@@ -528,7 +593,7 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
         const DnCam cam = dn_cam(ctx->cam);
         TexTable tt{};
         if (ctx->tex_active()) { tt.texels = ctx->d_tex_texels; tt.desc = ctx->d_tex_desc; tt.n = ctx->n_tex; }
-        const KMotion mo{ctx->d_idx, s->snap, s->motion};
+        const KMotion mo{ctx->d_idx, s->snap, s->psnap, s->motion};
         if (motion) {
             float4* gb = s->gb[s->gb_cur];
             if (ctx->tex_active()) {

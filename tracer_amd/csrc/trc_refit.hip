@@ -75,6 +75,20 @@ __global__ void __launch_bounds__(256) k_refit_refnodes(const uint4* __restrict_
             if (c > 0 && c < n_nodes) refnode[c] = rec[s];
         }
 }
+// primslot[section of the type + index] = 2 * k + slot for every slot of fat node k that is the leaf of a sphere, a square or a cube
+// (trc_update_primitives); first[type]: where the type's section begins, n[type]: its length.  The array starts out as kTagNone
+struct PrimSections { uint32_t first[3], n[3]; };
+__global__ void __launch_bounds__(256) k_refit_primslots(const uint4* __restrict__ nodes, uint32_t n_nodes, PrimSections sec, uint32_t* __restrict__ primslot) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n_nodes) return;
+    const uint4 q3 = nodes[4 * (size_t)k + 3];
+    const uint32_t tag[2] = {q3.z, q3.w};
+#pragma unroll
+    for (uint32_t s = 0; s < 2; ++s) {
+        const uint32_t type = tag[s] >> kTagIndexBits, index = tag[s] & kTagIndexMask;
+        if (type < kTagTriangle && index < sec.n[type]) primslot[sec.first[type] + index] = 2u * k + s;
+    }
+}
 
 // ---- the update
 struct KRefit {
@@ -190,19 +204,26 @@ trc_status refit_make_maps(trc_ctx* ctx) {
     const uint4* nodes = reinterpret_cast<const uint4*>(ctx->d_blob + sc.off_nodes);
     const dim3 grid((n + 255) / 256), b256(256);
     hipStream_t st = ctx->stream;
-    DevBuf parent, arrive, root, level_buf, refnode;
+    DevBuf parent, arrive, root, level_buf, refnode, primslot;
+    const PrimSections sec{{0u, sc.n_spheres, sc.n_spheres + sc.n_squares}, {sc.n_spheres, sc.n_squares, sc.n_cubes}};
+    const size_t n_prims = (size_t)sc.n_spheres + sc.n_squares + sc.n_cubes;      // (their records fit 40 KB: no wrap)
     uint32_t level[kRefitMaxLevels + 1];
     TRC_TRY(parent.alloc(ctx, (size_t)n * 4, "trc_update_vertices: parent map"));
     TRC_TRY(arrive.alloc(ctx, (size_t)n * 4, "trc_update_vertices: arrival counters"));
     TRC_TRY(root.alloc(ctx, kRefitRootWords * sizeof(float), "trc_update_vertices: root box"));
     TRC_TRY(level_buf.alloc(ctx, sizeof level, "trc_update_vertices: level table"));
     if (ctx->d_bvh_ref) TRC_TRY(refnode.alloc(ctx, (size_t)n * 4, "trc_update_vertices: record map"));
+    if (n_prims) {
+        TRC_TRY(primslot.alloc(ctx, n_prims * 4, "trc_update_primitives: leaf map"));
+        HIP_TRY(ctx, hipMemsetAsync(primslot.p, 0xFF, n_prims * 4, st));
+    }
     HIP_TRY(ctx, hipMemsetAsync(parent.p, 0, (size_t)n * 4, st));
     HIP_TRY(ctx, hipMemsetAsync(arrive.p, 0, (size_t)n * 4, st));
     HIP_TRY(ctx, hipMemsetAsync(level_buf.p, 0, sizeof level, st));
     HIP_TRY(ctx, hipMemsetAsync(root.p, 0, kRefitRootWords * sizeof(float), st));
     hipLaunchKernelGGL(k_refit_parents, grid, b256, 0, st, nodes, n, parent.as<uint32_t>());
     hipLaunchKernelGGL(k_refit_levels, grid, b256, 0, st, parent.as<uint32_t>(), n, level_buf.as<uint32_t>());
+    if (n_prims) hipLaunchKernelGGL(k_refit_primslots, grid, b256, 0, st, nodes, n, sec, primslot.as<uint32_t>());
     HIP_TRY(ctx, hipGetLastError());
     TRC_TRY(trc_read_to_host(ctx, st, "trc_update_vertices: level table", {{level, level_buf.p, sizeof level}}));
     if (level[kRefitBad]) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_update_vertices: the fat nodes are not numbered by depth");
@@ -218,6 +239,7 @@ trc_status refit_make_maps(trc_ctx* ctx) {
     }
     m.d_parent = static_cast<uint32_t*>(parent.release()); m.d_arrive = static_cast<uint32_t*>(arrive.release());
     m.d_root = static_cast<float*>(root.release()); m.d_refnode = static_cast<uint32_t*>(refnode.release());
+    m.d_primslot = static_cast<uint32_t*>(primslot.release());
     m.count_seen = 0; m.levels = std::move(levels);
     return TRC_OK;
 }
@@ -267,7 +289,7 @@ trc_status trc_refit_tail(trc_ctx* ctx, uint32_t first, uint32_t count, bool cou
     p.nodes = reinterpret_cast<uint4*>(ctx->d_blob + sc.off_nodes); p.n_nodes = sc.n_nodes;
     p.verts = ctx->d_verts; p.idx = ctx->d_idx; p.n_tri = sc.n_triangles;
     p.ref = ctx->d_bvh_ref; p.refnode = r.maps.d_refnode; p.n_ref = ctx->d_bvh_ref ? ctx->n_bvh_ref : 0u; p.root = r.maps.d_root;
-    trc_refit_launch_triangles(ctx, first, count);
+    if (count != 0 && sc.n_triangles != 0) trc_refit_launch_triangles(ctx, first, count);      // (trc_update_primitives: no vertex changed)
     if (ctx->knobs.refit_single) {
         hipLaunchKernelGGL(k_refit_climb, dim3((sc.n_nodes + 255) / 256), dim3(256), 0, st, p, r.maps.d_parent, r.maps.d_arrive);
     } else {
@@ -315,7 +337,7 @@ trc_status trc_refit_settle_pending(trc_ctx* ctx) {
 // freed with the scene and by trc_rebuild_tree; a pending read-back has been settled by the caller's trc_flush
 void trc_refit_free_maps(trc_ctx* ctx) {
     RefitState::Maps& m = ctx->refit.maps;
-    for (void* q : {(void*)m.d_parent, (void*)m.d_arrive, (void*)m.d_root, (void*)m.d_refnode}) (void)hipFree(q);
+    for (void* q : {(void*)m.d_parent, (void*)m.d_arrive, (void*)m.d_root, (void*)m.d_refnode, (void*)m.d_primslot}) (void)hipFree(q);
     m = RefitState::Maps{};
 }
 
@@ -324,7 +346,7 @@ void trc_refit_free(trc_ctx* ctx) {
     for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
     trc_refit_free_maps(ctx);
     for (void* q : {(void*)r.d_adj_offsets, (void*)r.d_adj_corners, (void*)r.d_rest, (void*)r.d_pose_table, (void*)r.skin.d_influences, (void*)r.d_palette,
-                    (void*)r.morph.d_deltas, r.d_morph_active, (void*)ctx->d_verts, (void*)ctx->d_idx}) (void)hipFree(q);
+                    (void*)r.morph.d_deltas, r.d_morph_active, r.d_prim_stage, (void*)ctx->d_verts, (void*)ctx->d_idx}) (void)hipFree(q);
     const float ms = r.ms; r = RefitState{}; r.ms = ms;      // (trc_debug_refit_ms goes on reporting the last call's time)
     ctx->d_verts = nullptr; ctx->d_idx = nullptr; ctx->n_vertex = 0;
 }

@@ -134,6 +134,7 @@ def _load(path, hooks=False):
     L.trc_recompute_normals.argtypes = [vp, u32, u32]
     L.trc_rebuild_tree.argtypes = [vp, u32]
     L.trc_tree_cost.argtypes = [vp, C.POINTER(abi.TreeCost)]
+    L.trc_update_primitives.argtypes = [vp, C.POINTER(abi.PrimitiveRanges)]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -275,6 +276,24 @@ class Tracer:
         if not (isinstance(poses, C.Array) and poses._type_ is abi.Pose):
             poses = make_poses(poses)
         self._check(self._L.trc_pose_vertices(self._h, poses if len(poses) else None, len(poses)), "trc_pose_vertices")
+
+    def update_primitives(self, spheres=None, first_sphere=0, squares=None, first_square=0, cubes=None, first_cube=0):
+        """trc_update_primitives: each list is a ctypes array (or a sequence) of abi.Sphere / abi.Square / abi.Cube records, or None;
+        list k replaces the scene's records [first_k, first_k + len) of its kind, and the tree is refitted in place once.  The
+        accumulator is not cleared."""
+        r = abi.PrimitiveRanges()
+        keep = []
+        for name, typ, items, first in (("sphere", abi.Sphere, spheres, first_sphere), ("square", abi.Square, squares, first_square),
+                                        ("cube", abi.Cube, cubes, first_cube)):
+            n = len(items) if items is not None else 0
+            if n and not (isinstance(items, C.Array) and items._type_ is typ):
+                items = (typ * n)(*items)
+            keep.append(items)
+            if n:
+                setattr(r, name + "s", C.cast(items, C.POINTER(typ)))
+            setattr(r, "first_" + name, int(first))
+            setattr(r, "n_" + name, n)
+        self._check(self._L.trc_update_primitives(self._h, C.byref(r)), "trc_update_primitives")
 
     def download_vertices(self, first=0, count=None):
         """trc_download_vertices: the current vertices [first, first + count) on the device as (count, 8) float32 rows (position,

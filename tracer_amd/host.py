@@ -29,6 +29,13 @@ def lib():
         L.trc_host_build_node.argtypes = [C.POINTER(abi.AABB), C.POINTER(abi.float4x4), C.c_int32, C.c_uint32,
                                           C.POINTER(abi.BVH)]
         L.trc_host_build_node.restype = None
+        L.trc_host_make_sphere.argtypes = [C.POINTER(abi.Sphere), C.c_float, C.POINTER(C.c_float), C.c_uint32]
+        L.trc_host_make_sphere.restype = None
+        L.trc_host_make_square.argtypes = [C.POINTER(abi.Square), C.c_uint8, C.c_float, C.c_float, C.c_uint8, C.c_float, C.c_float,
+                                           C.c_uint8, C.c_float, C.c_uint32]
+        L.trc_host_make_square.restype = None
+        L.trc_host_make_cube.argtypes = [C.POINTER(abi.Cube), C.c_uint32, C.POINTER(abi.float4x4)]
+        L.trc_host_make_cube.restype = None
         L.trc_host_build_tree.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(C.c_uint32)]
         L.trc_host_build_tree.restype = C.c_int32
         L.trc_host_tree_depth.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -383,4 +390,29 @@ def build_node(box_min, box_max, ptype, pindex, model=None):
             setattr(m.columns[c], "xyzw"[r], v)
     out = abi.BVH()
     lib().trc_host_build_node(C.byref(box), C.byref(m), ptype, pindex, C.byref(out))
+    return out
+
+
+def make_sphere(radius, center, material):
+    """trc_host_make_sphere: the reference's sphere constructor (radius + 1e-4 in the record, the box not inflated) -> abi.Sphere"""
+    out = abi.Sphere()
+    lib().trc_host_make_sphere(C.byref(out), float(radius), (C.c_float * 3)(*(float(v) for v in center)), int(material))
+    return out
+
+
+def make_square(axis_i, i0, i1, axis_j, j0, j1, axis_k, k, material):
+    """trc_host_make_square: the reference's axis-aligned rectangle -> abi.Square"""
+    out = abi.Square()
+    lib().trc_host_make_square(C.byref(out), int(axis_i), float(i0), float(i1), int(axis_j), float(j0), float(j1), int(axis_k), float(k), int(material))
+    return out
+
+
+def make_cube(material, model):
+    """trc_host_make_cube: the unit box under `model` (an abi.float4x4, or a (4, 4) array model[r][c]) with its inverse and normal
+    matrix -> abi.Cube"""
+    if not isinstance(model, abi.float4x4):
+        a = np.asarray(model, dtype=np.float32).reshape(4, 4)
+        model = abi.float4x4.from_buffer_copy(np.ascontiguousarray(a.T).tobytes())
+    out = abi.Cube()
+    lib().trc_host_make_cube(C.byref(out), int(material), C.byref(model))
     return out

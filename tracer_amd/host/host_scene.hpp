@@ -53,15 +53,18 @@ inline trc_Square make_square(uint8_t axis_i, float i0, float i1, uint8_t axis_j
 }
 
 // Tracer.mm:155-163 + the T*R*S set-up of prepareCubeList
-inline trc_Cube make_cube(uint32_t material, trc_float4x4 translate, trc_float4x4 rotate, trc_float4x4 scale) {
+inline trc_Cube make_cube(uint32_t material, const trc_float4x4& model) {
     trc_Cube r;
     std::memset(&r, 0, sizeof(r));
     r.box = box_of(f3(0, 0, 0), f3(1, 1, 1));
     r.material = material;
-    r.model_matrix = mul(mul(translate, rotate), scale);
+    r.model_matrix = model;
     r.inverse_matrix = inverse(r.model_matrix);
     r.normal_matrix = transpose(r.inverse_matrix);
     return r;
+}
+inline trc_Cube make_cube(uint32_t material, trc_float4x4 translate, trc_float4x4 rotate, trc_float4x4 scale) {
+    return make_cube(material, mul(mul(translate, rotate), scale));
 }
 
 // Tracer.mm:165-172 -- radius inflated by 1e-4, AABB not (quirk B-13)

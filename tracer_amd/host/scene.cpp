@@ -147,6 +147,17 @@ void trc_host_make_camera(trc_Camera* camera, const float lookFrom[3], const flo
     camera->cornerLowLeft = from - vertical / 2.0f - horizontal / 2.0f - w * focus_dist;
 }
 
+void trc_host_make_sphere(trc_Sphere* out, float radius, const float center[3], uint32_t material) {
+    *out = make_sphere(radius, f3(center[0], center[1], center[2]), material);
+}
+void trc_host_make_square(trc_Square* out, uint8_t axis_i, float i0, float i1, uint8_t axis_j, float j0, float j1,
+                          uint8_t axis_k, float k, uint32_t material) {
+    *out = make_square(axis_i, i0, i1, axis_j, j0, j1, axis_k, k, material);
+}
+void trc_host_make_cube(trc_Cube* out, uint32_t material, const trc_float4x4* model_matrix) {
+    *out = make_cube(material, *model_matrix);
+}
+
 // prepareCamera with zero rotation / zero wasd offset (Tracer.mm:371-411)
 void trc_host_prepare_camera(trc_Camera* out, float width, float height) {
     const float from[3] = {278, 278, -800}, at[3] = {278, 278, 278}, up[3] = {0, 1, 0};
