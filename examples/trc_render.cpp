@@ -3,7 +3,7 @@
 // output stage, PNG.  Nothing but the two shared libraries is involved.
 //
 //   trc_render [--scene cornell|spheres|volume] [--integrator path|mis|volume] [--size W H] [--spp N]
-//              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah] [--sobol] [--out frame.png]
+//              [--mesh file.obj|file.pbrt] [--albedo-map file.png] [--density cloud.pbrt] [--lbvh | --device-sah | --device-sah3] [--sobol] [--out frame.png]
 //              [--hdr map.hdr [--env-light]]  --env-light: traceMIS samples the map as a light (TRC_FLAG_ENV_LIGHT), no square light needed
 //              [--spin N]  after the frame, N more frames of the mesh turned about its own vertical axis (360 / N degrees per frame) through
 //                          trc_update_vertices: no second upload, the tree is refitted in place; frame k goes to <out>.k.png
@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
     double rebuild_ratio = 0.0;
-    bool lbvh = false, device_sah = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
+    bool lbvh = false, device_sah = false, device_sah3 = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
@@ -73,6 +73,7 @@ int main(int argc, char** argv) {
         else if (a == "--density" && i + 1 < argc) density_path = argv[++i];    // pbrt-v3 heterogeneous medium
         else if (a == "--lbvh") lbvh = true;
         else if (a == "--device-sah") device_sah = true;
+        else if (a == "--device-sah3") device_sah = device_sah3 = true;      // --device-sah with the three-axis, 32-bin split (TRC_TREE_SAH3)
         else if (a == "--sobol") sobol = true;
         else if (a == "--spin" && i + 1 < argc) {                               // moving geometry: trc_update_vertices per frame
             const int n = std::atoi(argv[++i]);
@@ -174,12 +175,13 @@ int main(int argc, char** argv) {
 
     CHECK(trc_create(0, &ctx));
     if (device_sah && pbrt_path.empty()) {        // triangle leaves + BVH::buildTree itself, both on the device
-        CHECK(trc_upload_scene_device(ctx, &scene, TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES));
+        CHECK(trc_upload_scene_device(ctx, &scene, TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES | (device_sah3 ? TRC_TREE_SAH3 : 0u)));
     } else if (lbvh || device_sah) {              // hand over the leaf records only; the tree is built on the GPU
         trc_scene leaves = scene;
         leaves.bvhList = scene.bvhList + 1;       // BVH::buildTree keeps the leaves at [1, n]
         leaves.n_bvh = (scene.n_bvh + 1) / 2;
-        if (device_sah) CHECK(trc_upload_scene_sah(ctx, &leaves));
+        if (device_sah3) CHECK(trc_upload_scene_device(ctx, &leaves, TRC_TREE_SAH | TRC_TREE_SAH3));
+        else if (device_sah) CHECK(trc_upload_scene_sah(ctx, &leaves));
         else CHECK(trc_upload_scene_lbvh(ctx, &leaves));
     } else {
         CHECK(trc_upload_scene(ctx, &scene));
@@ -303,7 +305,7 @@ int main(int argc, char** argv) {
         ++cost_reads;
         if (now <= rebuild_ratio * built_cost) return TRC_OK;
         const auto r0 = std::chrono::steady_clock::now();
-        if ((rs = trc_rebuild_tree(ctx, TRC_TREE_SAH)) != TRC_OK) return rs;
+        if ((rs = trc_rebuild_tree(ctx, TRC_TREE_SAH | (device_sah3 ? TRC_TREE_SAH3 : 0u))) != TRC_OK) return rs;      // the flavour of the upload
         const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
         const double worn = now;
         if ((rs = tree_ratio(&now)) != TRC_OK) return rs;

@@ -67,7 +67,9 @@ extern "C" {
  *     surfaces that the calls above move; opt-in, off by default; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_primitive_ranges, trc_update_primitives, trc_host_make_sphere, trc_host_make_square,
  *     trc_host_make_cube (spheres, squares and cubes moved on the device; with tracking on the history follows them too: the motion
- *     texel of an analytic hit may now be non-zero; additions only, nothing existing changed) */
+ *     texel of an analytic hit may now be non-zero; additions only, nothing existing changed)
+ *     added under 13, the number stays: TRC_TREE_SAH3, trc_host_build_tree_flags (a three-axis, 32-bin SAH split as an option of the
+ *     SAH builds on the host and on the device; opt-in, nothing defaults to it; additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -487,6 +489,31 @@ trc_status trc_upload_scene_sah(trc_ctx* ctx, const trc_scene* scene);
  * nor uploads 64 bytes per triangle.  The tree is the one trc_host_build_tree builds from the same leaves. */
 #define TRC_TREE_SAH              1u
 #define TRC_TREE_TRIANGLE_LEAVES  2u
+/* TRC_TREE_SAH3, a modifier of TRC_TREE_SAH: a tree of lower surface-area cost from the same leaves -- every axis is priced, with 32
+ * bins, in place of the reference's widest axis and 10 buckets.  An option: nothing defaults to it, and the tree is no longer the
+ * reference's.  Accepted: trc_upload_scene_device(TRC_TREE_SAH | TRC_TREE_SAH3 [| TRC_TREE_TRIANGLE_LEAVES]),
+ * trc_rebuild_tree(TRC_TREE_SAH | TRC_TREE_SAH3) and trc_host_build_tree_flags(TRC_TREE_SAH | TRC_TREE_SAH3): the three build the same
+ * tree from the same leaves, record for record.  TRC_TREE_SAH3 without TRC_TREE_SAH is TRC_ERR_INVALID_ARG, nothing changed.
+ *  - As for TRC_TREE_SAH: the root at 0, the leaves at 1..n in input order, the interiors in serial post-order; a record's centroid is
+ *    mn + (mx - mn) / 2 per component; a node of two leaves puts the one with the smaller centroid on the widest axis of the two
+ *    centroids' box to the left (the first to the right unless it compares <); every box is the union of its children's; leaf boxes
+ *    must be finite with |coordinates| <= 1e37; the depth limit is TRC_MAX_BVH_DEPTH.  Only the split of a node of three or more
+ *    leaves differs:
+ *  - cb = the bounds of the node's records' centroids.  The axes a = 0, 1, 2 are considered in that order; an axis is skipped unless
+ *    e = cb.max[a] - cb.min[a] compares > 0.  The bin of a record on a considered axis: rel = (c[a] - cb.min[a]) / e, fb = 32 * rel,
+ *    b = fb >= 0 ? (uint)fb : 0, clamped to 31.
+ *  - For each considered axis and each i = 0..30 ascending: side 0 holds the records with bin <= i, side 1 the rest; n0, n1 their
+ *    counts, B0, B1 the unions of their leaf boxes; A(B) = 2 * ((dx * dy + dx * dz) + dy * dz) with d = max - min;
+ *    cost = (float)n0 * A(B0) + (float)n1 * A(B1).  Every operation is one binary32 operation in the order written, none contracted.
+ *    A candidate with an empty side is skipped (on an axis of positive extent bins 0 and 31 are never empty, so none is).
+ *  - The first candidate in this order initialises best; a later one replaces it only when cost < best: ties go to the lower axis,
+ *    then to the lower i, and an infinite or NaN cost behaves as < says.  There is no division by the area of cb, which is 0 for
+ *    collinear or coplanar centroids.
+ *  - The records whose bin on the winning axis is <= the winning i go left, in the order the two-ended swap loop of BVH.hh:154-168
+ *    leaves them (the k-th misplaced record from the left changes places with the k-th from the right).  The node's axis is the
+ *    winning axis.
+ *  - No axis of positive extent: all centroids are identical.  axis 2, the split at first + span / 2, the order kept. */
+#define TRC_TREE_SAH3             16u
 trc_status trc_upload_scene_device(trc_ctx* ctx, const trc_scene* scene, uint32_t flags);
 /* the device-built tree in the reference's array layout (BVH.hh:246-269): [root, leaf 0..n-1, interior
  * 1..n-2], 2n-1 records.  out == NULL: only *n_nodes is written. */
@@ -836,13 +863,15 @@ trc_status trc_recompute_normals(trc_ctx* ctx, uint32_t first, uint32_t count);
  *    the new tree at its next call.
  *  - The leaf count does not change, so neither does the layout of the device's scene: the node region and the tree records are
  *    rewritten in place, only temporaries are allocated, and nothing larger than the build's small read-backs is transferred.
- *  - Atomic on error.  TRC_ERR_INVALID_ARG: a flag other than TRC_TREE_SAH (TRC_TREE_TRIANGLE_LEAVES included: the leaves are the
- *    device's).  TRC_ERR_NO_SCENE before any upload.  TRC_ERR_UNSUPPORTED: see above.  TRC_ERR_BVH_INVALID: a tree deeper than
+ *  - flags == (TRC_TREE_SAH | TRC_TREE_SAH3): the tree trc_upload_scene_device(TRC_TREE_SAH | TRC_TREE_SAH3) builds from those leaf
+ *    records; everything else in this list holds for it unchanged.
+ *  - Atomic on error.  TRC_ERR_INVALID_ARG: a flag other than TRC_TREE_SAH and its modifier TRC_TREE_SAH3 (TRC_TREE_TRIANGLE_LEAVES
+ *    included: the leaves are the device's), or TRC_TREE_SAH3 without TRC_TREE_SAH.  TRC_ERR_NO_SCENE before any upload.  TRC_ERR_UNSUPPORTED: see above.  TRC_ERR_BVH_INVALID: a tree deeper than
  *    TRC_MAX_BVH_DEPTH, or a leaf box the SAH build does not take.  TRC_ERR_OOM: the temporaries.  All of them are found before the
  *    first byte of the old tree is overwritten: a render after a refused call gives the frame it would have given before it.
  *  - Launches kept back for coalescing run first.  Not collective.  The call waits where an upload waits -- the read-backs of the build
  *    -- and returns with the tree in place.  trc_lbvh_info reports the rebuild's height and device time. */
-trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags);       /* flags: 0 (LBVH + rotations) or TRC_TREE_SAH */
+trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags);       /* flags: 0 (LBVH + rotations), TRC_TREE_SAH or TRC_TREE_SAH | TRC_TREE_SAH3 */
 /* A surface-area measure of the tree as it stands, on any upload path (it reads the device's nodes): one kernel pass over 64 bytes per
  * interior node on the context's stream; synchronous like a download.  Launches kept back for coalescing run first.
  *  - For a box, d = max - min per axis in binary32, and a d that is not > 0 counts as 0; its half area is
@@ -1246,6 +1275,10 @@ void trc_host_make_cube(trc_Cube* out, uint32_t material, const trc_float4x4* mo
  * index 0); `nodes` must have room for 2*n_leaves-1.  Serial post-order
  * interior numbering (one legal schedule of the reference's GCD build). */
 trc_status trc_host_build_tree(trc_BVH* nodes, uint32_t n_leaves, uint32_t* out_n_nodes);
+/* flags == TRC_TREE_SAH: trc_host_build_tree itself.  flags == (TRC_TREE_SAH | TRC_TREE_SAH3): the same call with the split of
+ * TRC_TREE_SAH3 (above, at trc_upload_scene_device) -- the tree the device builds under that flag, for a host that uploads its own
+ * tree with trc_upload_scene.  Any other flags: TRC_ERR_INVALID_ARG, `nodes` untouched. */
+trc_status trc_host_build_tree_flags(trc_BVH* nodes, uint32_t n_leaves, uint32_t flags, uint32_t* out_n_nodes);
 /* depth of the deepest leaf (root = 0); TRC_ERR_BVH_INVALID on malformed trees */
 trc_status trc_host_tree_depth(const trc_BVH* nodes, uint32_t n_nodes, uint32_t* out_depth);
 

@@ -347,6 +347,33 @@ static void primitive_ranges() {
     EXPECT(check(all) == nullptr);
 }
 
+// ---------------------------------------------------------------- trc_host_build_tree_flags
+static void flagged_trees() {
+    // a heap array of exactly 2n - 1 records: a builder that writes one record too many is an overflow the sanitizer sees
+    const uint32_t sizes[] = {2, 3, 5, 64, 65, 300};
+    for (uint32_t n : sizes)
+        for (int family = 0; family < 3; ++family)
+            for (uint32_t flags : {(uint32_t)TRC_TREE_SAH, (uint32_t)(TRC_TREE_SAH | TRC_TREE_SAH3)}) {
+                std::vector<trc_BVH> nodes(2 * n - 1);
+                std::memset(nodes.data(), 0, sizeof(trc_BVH) * nodes.size());
+                uint32_t s = 12345u + n;
+                auto next = [&] { s = s * 1664525u + 1013904223u; return (float)(s >> 8) * (1.0f / 16777216.0f); };
+                for (uint32_t i = 0; i < n; ++i) {
+                    // 0: random boxes; 1: identical centroids (the median fallback); 2: centroids on a line along y
+                    const float c[3] = {family == 0 ? 100.0f * next() : 3.0f, family == 1 ? 3.0f : 100.0f * next(), family == 0 ? 100.0f * next() : 3.0f};
+                    const float h = family == 0 ? 0.1f + next() : 0.25f * (float)(1 + i % 7);
+                    nodes[i].pType = TRC_PRIM_SPHERE; nodes[i].pIndex = i;
+                    nodes[i].bBOX.mini = {c[0] - h, c[1] - h, c[2] - h}; nodes[i].bBOX.maxi = {c[0] + h, c[1] + h, c[2] + h};
+                }
+                uint32_t count = 0, depth = 0;
+                EXPECT(trc_host_build_tree_flags(nodes.data(), n, flags, &count) == TRC_OK && count == 2 * n - 1);
+                EXPECT(trc_host_tree_depth(nodes.data(), count, &depth) == TRC_OK && depth >= 1);
+            }
+    trc_BVH two[3];
+    std::memset(two, 0, sizeof two);
+    for (uint32_t flags : {0u, (uint32_t)TRC_TREE_SAH3, 4u, 8u, (uint32_t)TRC_TREE_TRIANGLE_LEAVES}) EXPECT(trc_host_build_tree_flags(two, 2, flags, nullptr) == TRC_ERR_INVALID_ARG);
+}
+
 // ---------------------------------------------------------------- readers
 static const char* kScene =
     "LookAt 0 3 -12  0 1 0  0 1 0\nCamera \"perspective\" \"float fov\" [ 40 ]\nFilm \"image\" \"integer xresolution\" [ 64 ] \"integer yresolution\" [ 48 ]\n"
@@ -417,6 +444,7 @@ int main(int argc, char** argv) {
     morph_tables();
     normals_ranges();
     primitive_ranges();
+    flagged_trees();
     { uint32_t m32[40 * 52]; trc_host_sobol_matrices32(m32); uint64_t a[52], b[52]; EXPECT(trc_host_sobol_interval_tables(11, a, b) == TRC_OK); }
 
     write_file(dir + "/scene.pbrt", kScene);

@@ -11,6 +11,7 @@ TRC_ABI_VERSION = 13
 TRC_TILE = 16
 TRC_MAX_BVH_DEPTH = 64
 TREE_SAH, TREE_TRIANGLE_LEAVES = 1, 2
+TREE_SAH3 = 16             # modifier of TREE_SAH: three axes, 32 bins (include/tracer_abi.h)
 TRC_UNIQUE_ID_BYTES = 128
 # enum trc_coll_dtype / trc_coll_op (ncclDataType_t / ncclRedOp_t ordinals)
 DT_U8, DT_U32, DT_F32 = 1, 3, 7
@@ -319,7 +320,7 @@ HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "
                 "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test", "trc_debug_last_kernel",
                 "trc_debug_last_residency", "trc_material_s_f_test"]
 HOST_SYMBOLS = [
-    "trc_host_build_node", "trc_host_build_tree", "trc_host_tree_depth", "trc_host_make_camera",
+    "trc_host_build_node", "trc_host_build_tree", "trc_host_build_tree_flags", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",
     "trc_host_scene_view", "trc_host_scene_load_pbrt", "trc_host_mesh_load_obj", "trc_host_mesh_load_pbrt", "trc_host_mesh_load_ply", "trc_host_load_hdr", "trc_host_mesh_make_ball", "trc_host_mesh_replicate", "trc_host_mesh_from_arrays",
     "trc_host_mesh_view", "trc_host_mesh_destroy", "trc_host_make_density_info", "trc_host_make_cloud",

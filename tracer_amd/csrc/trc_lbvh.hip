@@ -606,6 +606,7 @@ struct TreeBuild {
     trc_ctx* ctx; hipStream_t st; const trc_scene* s;      // s == nullptr: trc_rebuild_tree -- n, n_interior and sc come from the context's scene (ctx->ks.sc)
     bool sah, triangle_leaves;      // sah: the reference's binned-SAH topology, else Morton order + rotations.  triangle_leaves: bvhList holds
                                     // the analytic primitives' leaves only; one leaf per triangle follows them, written on the device
+    bool sah3;                      // with sah: the three-axis, 32-bin split of TRC_TREE_SAH3 in place of the reference's
     uint32_t n = 0, n_interior = 0; DScene sc{}; uint64_t blob_words = 0;
     std::unique_ptr<uint32_t[]> prefix; DevBufs tmp;      // prefix: host side of the blob, analytic primitives + materials
     DLeaf* leaves = nullptr; float* boxes = nullptr; DTopo tp{};
@@ -639,9 +640,10 @@ trc_status intake(TreeBuild& b) {
 
 // Room for the build's temporaries in one allocation (DevBufs::reserve): per leaf 32 + 24 B of leaves and boxes, 11 words of sort and
 // topology arrays and 2 of the depth sort (109 B with the histograms), for the SAH build 68 B of records in tree order, side array and
-// moves and ~20 B of level tables and finish list (198 B in all); `extra`: what a rebuild of a caller's tree sorts before that.  An
-// estimate: what it leaves out gets a buffer of its own
-void reserve_temporaries(TreeBuild& b, size_t extra = 0) { b.tmp.reserve((size_t)b.n * (b.sah ? 198u : 109u) + extra + (64u << 10)); }
+// moves and ~20 B of level tables and finish list (198 B in all), under TRC_TREE_SAH3 another 42 B of bin rows (2 688 B for each of the
+// n / 64 rows a level can have) and 6 B more of task histograms (246 B in all); `extra`: what a rebuild of a caller's tree sorts before
+// that.  An estimate: what it leaves out gets a buffer of its own
+void reserve_temporaries(TreeBuild& b, size_t extra = 0) { b.tmp.reserve((size_t)b.n * (b.sah ? (b.sah3 ? 246u : 198u) : 109u) + extra + (64u << 10)); }
 
 // the build's temporary arrays, and the centroid bounds / intake flags at their identities
 trc_status work_arrays(TreeBuild& b) {
@@ -832,10 +834,10 @@ void trc_sort_pairs(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32
 uint32_t trc_sort_hist_words(uint32_t n) { return 256u * ((n + kSortTile - 1) / kSortTile); }
 
 // the steps are the list at the top of this file; what the device finds wrong with the leaf records (fit_boxes) is found when the old scene has gone
-static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah, bool triangle_leaves) {
+static trc_status upload_device_tree(trc_ctx* ctx, const trc_scene* s, bool sah, bool triangle_leaves, bool sah3 = false) {
     TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
-    TreeBuild b{ctx, ctx->stream, s, sah, triangle_leaves};
+    TreeBuild b{ctx, ctx->stream, s, sah, triangle_leaves, sah3};
     TRC_TRY(intake(b));
     const trc_status status = build_tree(b);
     if (status != TRC_OK) trc_release_scene(ctx);
@@ -847,17 +849,19 @@ extern "C" {
 trc_status trc_upload_scene_lbvh(trc_ctx* ctx, const trc_scene* s) { return upload_device_tree(ctx, s, false, false); }
 trc_status trc_upload_scene_sah(trc_ctx* ctx, const trc_scene* s) { return upload_device_tree(ctx, s, true, false); }
 trc_status trc_upload_scene_device(trc_ctx* ctx, const trc_scene* s, uint32_t flags) {
-    if (flags & ~(uint32_t)(TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES)) return ctx ? trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_scene_device: unknown flag") : TRC_ERR_INVALID_ARG;
-    return upload_device_tree(ctx, s, (flags & TRC_TREE_SAH) != 0, (flags & TRC_TREE_TRIANGLE_LEAVES) != 0);
+    if (flags & ~(uint32_t)(TRC_TREE_SAH | TRC_TREE_TRIANGLE_LEAVES | TRC_TREE_SAH3)) return ctx ? trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_scene_device: unknown flag") : TRC_ERR_INVALID_ARG;
+    if ((flags & TRC_TREE_SAH3) && !(flags & TRC_TREE_SAH)) return ctx ? trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_upload_scene_device: TRC_TREE_SAH3 modifies TRC_TREE_SAH") : TRC_ERR_INVALID_ARG;
+    return upload_device_tree(ctx, s, (flags & TRC_TREE_SAH) != 0, (flags & TRC_TREE_TRIANGLE_LEAVES) != 0, (flags & TRC_TREE_SAH3) != 0);
 }
 
 trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags) {
     TRC_TRY(trc_flush(ctx));
     if (!ctx) return TRC_ERR_INVALID_ARG;
-    if (flags & ~(uint32_t)TRC_TREE_SAH) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_rebuild_tree: flags other than TRC_TREE_SAH");
+    if (flags & ~(uint32_t)(TRC_TREE_SAH | TRC_TREE_SAH3)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_rebuild_tree: flags other than TRC_TREE_SAH, TRC_TREE_SAH3");
+    if ((flags & TRC_TREE_SAH3) && !(flags & TRC_TREE_SAH)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_rebuild_tree: TRC_TREE_SAH3 modifies TRC_TREE_SAH");
     if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_rebuild_tree: no scene");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TreeBuild b{ctx, ctx->stream, nullptr, (flags & TRC_TREE_SAH) != 0, false};
+    TreeBuild b{ctx, ctx->stream, nullptr, (flags & TRC_TREE_SAH) != 0, false, (flags & TRC_TREE_SAH3) != 0};
     return rebuild_tree(b);
 }
 

@@ -309,8 +309,18 @@ __device__ __forceinline__ uint32_t block_pred_scan256(bool pred, uint32_t* wave
     return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 
+// TRC_TREE_SAH3 (kSah3): the same partition by bin on an axis -- the winning axis of the row (row_axis, written by k_sah3_price) with its
+// own lo / extent, 32 bins, and that axis' 32 counts among the 96 the task kept.  Everything else is shared.
+constexpr uint32_t kBins3 = 32, kRow3 = 3u * kBins3 * 7u;   // a row of TRC_TREE_SAH3 bins: [axis][bin] x (count, 3 inverted ordered mins, 3 ordered maxes)
+__device__ __forceinline__ uint32_t sah3_bin(float c, float lo, float extent) {
+    const float rel = (c - lo) / extent;
+    const float fb = (float)kBins3 * rel;
+    const uint32_t b = (fb >= 0.0f) ? (uint32_t)fb : 0u;
+    return b < kBins3 - 1u ? b : kBins3 - 1u;
+}
+template <bool kSah3>
 __global__ void __launch_bounds__(256) k_sah_scatter(const DLeaf* elems, DLeaf* tmp, uint32_t* mv, const SNode* nodes, SNode* next_nodes,
-                                                    const uint32_t* task_node, const uint32_t* task_hist, uint32_t* next_task_node) {
+                                                    const uint32_t* task_node, const uint32_t* task_hist, uint32_t* next_task_node, const uint32_t* row_axis) {
     __shared__ uint32_t wave_tot[4], s_prefix;
     __shared__ uint32_t s_cb[2][6];
     const uint32_t t = blockIdx.x, node = task_node[t];
@@ -318,7 +328,11 @@ __global__ void __launch_bounds__(256) k_sah_scatter(const DLeaf* elems, DLeaf* 
     const uint32_t first = N.first, last = N.last, mid = N.mid, split = N.split, n_below = N.n_below;
     const bool fallback = N.fallback != 0u;
     const uint32_t p0 = first + (t - N.task0) * kChunk, p1 = min(last, p0 + kChunk);
-    const SahAxis ax = sah_axis_of(N.cb);
+    SahAxis ax;
+    if constexpr (kSah3) { ax.axis = min(row_axis[node], 2u); ax.lo = float_of(N.cb[ax.axis]); ax.extent = float_of(N.cb[3u + ax.axis]) - ax.lo; }
+    else ax = sah_axis_of(N.cb);
+    constexpr uint32_t kHistStride = kSah3 ? 3u * kBins3 : kSahBuckets;
+    const uint32_t hist_first = kSah3 ? ax.axis * kBins3 : 0u;
     if (threadIdx.x < 12u) s_cb[threadIdx.x / 6u][threadIdx.x % 6u] = (threadIdx.x % 6u) < 3u ? 0xFFFFFFFFu : 0u;
     uint32_t lo[2][3] = {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}}, hi[2][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
     // records below the split in the node's tasks before this one: the histograms k_sah_bins kept (a few KB from L2)
@@ -328,7 +342,7 @@ __global__ void __launch_bounds__(256) k_sah_scatter(const DLeaf* elems, DLeaf* 
     if (!fallback && k_task) {
         uint32_t v = 0;
         for (uint32_t i = threadIdx.x; i < k_task * (split + 1u); i += 256u)
-            v += task_hist[(size_t)(N.task0 + i / (split + 1u)) * kSahBuckets + i % (split + 1u)];
+            v += task_hist[(size_t)(N.task0 + i / (split + 1u)) * kHistStride + hist_first + i % (split + 1u)];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
         if ((threadIdx.x & 63u) == 0u && v) atomicAdd(&s_prefix, v);
@@ -354,7 +368,7 @@ __global__ void __launch_bounds__(256) k_sah_scatter(const DLeaf* elems, DLeaf* 
 #pragma unroll
         for (int a = 0; a < 3; ++a) c[a] = sah_centroid1(d.mn[a], d.mx[a]);
         const float ca = ax.axis == 0 ? c[0] : (ax.axis == 1 ? c[1] : c[2]);
-        const bool below = valid && (fallback ? p < mid : sah_bucket(ca, ax.lo, ax.extent) <= split);
+        const bool below = valid && (fallback ? p < mid : (kSah3 ? sah3_bin(ca, ax.lo, ax.extent) : sah_bucket(ca, ax.lo, ax.extent)) <= split);
         uint32_t total;
         const uint32_t bp = running + block_pred_scan256(below, wave_tot, total);
         running += total;
@@ -565,6 +579,8 @@ __global__ void __launch_bounds__(64) k_sah_finish(const DLeaf* elems, const SFi
     if (lane < S) vals[F + lane] = s_leaf[s_ord[lane]];
 }
 
+#include "trc_sah3_build.hpp"
+
 // what the intake flags (k_lbvh_prepare, k_sah_init) say is wrong with the leaf records; TRC_OK for none
 static trc_status intake_status(trc_ctx* ctx, uint32_t bad_leaves) {
     if (bad_leaves & 1u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "lbvh: input must be leaf records only");
@@ -587,7 +603,10 @@ static trc_status sah_build_topology(TreeBuild& t) {
     const char* const what = "sah build: work arrays";
     TRC_TRY(t.tmp.alloc(ctx, &b.elems, n, what)); TRC_TRY(t.tmp.alloc(ctx, &b.tmp, n, what)); TRC_TRY(t.tmp.alloc(ctx, &b.mv, n, what));
     for (int k = 0; k < 2; ++k) { TRC_TRY(t.tmp.alloc(ctx, &b.nodes[k], max_rows, what)); TRC_TRY(t.tmp.alloc(ctx, &b.task_node[k], max_tasks, what)); }
-    TRC_TRY(t.tmp.alloc(ctx, &b.task_hist, (size_t)max_tasks * kSahBuckets, what));
+    TRC_TRY(t.tmp.alloc(ctx, &b.task_hist, (size_t)max_tasks * (t.sah3 ? 3u * kBins3 : kSahBuckets), what));
+    uint32_t *bins3 = nullptr, *row_axis = nullptr;             // TRC_TREE_SAH3: the level's bin rows (one table: a level's bins are spent by its split) and winning axes
+    if (t.sah3) { TRC_TRY(t.tmp.alloc(ctx, &bins3, (size_t)max_rows * kRow3, what)); TRC_TRY(t.tmp.alloc(ctx, &row_axis, max_rows, what)); }
+    const auto scatter = t.sah3 ? k_sah_scatter<true> : k_sah_scatter<false>;
     TRC_TRY(t.tmp.alloc(ctx, &b.finish, n / 2u + 2u, what));
     TRC_TRY(t.tmp.alloc(ctx, &b.counters, n_counters, what));
     HIP_TRY(ctx, hipMemsetAsync(b.counters, 0, sizeof(uint32_t) * n_counters, st));
@@ -614,13 +633,20 @@ static trc_status sah_build_topology(TreeBuild& t) {
     for (uint32_t level = 0; n_rows > 0; ++level, cur ^= 1) {
         if (level > TRC_MAX_BVH_DEPTH) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: tree deeper than TRC_MAX_BVH_DEPTH");
         uint32_t* next_counts = b.counters + 2u + 2u * (level + 1u);
-        hipLaunchKernelGGL(k_sah_bins, dim3(n_tasks), b256, 0, st, b.elems, b.nodes[cur], b.task_node[cur], b.task_hist);
-        hipLaunchKernelGGL(k_sah_split, dim3((n_rows + 63u) / 64u), dim3(64), 0, st, b.nodes[cur], n_rows, b.nodes[cur ^ 1], next_counts, b.finish, b.counters, t.tp, n, level);
+        if (t.sah3) {
+            HIP_TRY(ctx, hipMemsetAsync(bins3, 0, sizeof(uint32_t) * kRow3 * (size_t)n_rows, st));      // every word's identity is 0
+            hipLaunchKernelGGL(k_sah3_bins, dim3(n_tasks), b256, 0, st, b.elems, b.nodes[cur], b.task_node[cur], bins3, b.task_hist);
+            hipLaunchKernelGGL(k_sah3_price, dim3((n_rows + 3u) / 4u), b256, 0, st, b.nodes[cur], n_rows, bins3, row_axis);
+            hipLaunchKernelGGL(k_sah3_split, dim3((n_rows + 63u) / 64u), dim3(64), 0, st, b.nodes[cur], n_rows, row_axis, b.nodes[cur ^ 1], next_counts, b.finish, b.counters, t.tp, n, level);
+        } else {
+            hipLaunchKernelGGL(k_sah_bins, dim3(n_tasks), b256, 0, st, b.elems, b.nodes[cur], b.task_node[cur], b.task_hist);
+            hipLaunchKernelGGL(k_sah_split, dim3((n_rows + 63u) / 64u), dim3(64), 0, st, b.nodes[cur], n_rows, b.nodes[cur ^ 1], next_counts, b.finish, b.counters, t.tp, n, level);
+        }
         // one read-back per level: the whole counter block (next level's rows / tasks, error bits)
         HIP_TRY(ctx, hipMemcpyAsync(h_readback, b.counters, sizeof(uint32_t) * n_counters, hipMemcpyDeviceToHost, st));
         h_readback[n_counters] = 0;
         if (level == 0) HIP_TRY(ctx, hipMemcpyAsync(h_readback + n_counters, t.bounds + 6, sizeof(uint32_t), hipMemcpyDeviceToHost, st));      // intake flags are final by now
-        hipLaunchKernelGGL(k_sah_scatter, dim3(n_tasks), b256, 0, st, b.elems, b.tmp, b.mv, b.nodes[cur], b.nodes[cur ^ 1], b.task_node[cur], b.task_hist, b.task_node[cur ^ 1]);
+        hipLaunchKernelGGL(scatter, dim3(n_tasks), b256, 0, st, b.elems, b.tmp, b.mv, b.nodes[cur], b.nodes[cur ^ 1], b.task_node[cur], b.task_hist, b.task_node[cur ^ 1], row_axis);
         hipLaunchKernelGGL(k_sah_apply, dim3(n_tasks), b256, 0, st, b.elems, b.tmp, b.mv, b.nodes[cur], b.nodes[cur ^ 1], b.task_node[cur]);
         HIP_TRY(ctx, hipStreamSynchronize(st));
         const uint32_t bad = h_readback[n_counters];
@@ -636,7 +662,8 @@ static trc_status sah_build_topology(TreeBuild& t) {
     hipLaunchKernelGGL(k_sah_vals, g_leaf, b256, 0, st, b.elems, n, t.vals[0]);
     const uint32_t n_finish = n <= kFinishSpan ? 1u : h_readback[0];       // every level's read-back came after its k_sah_split
     if (n_finish > n / 2u + 2u) return trc_fail(ctx, TRC_ERR_BVH_INVALID, "sah: finish list overflow");
-    if (n_finish) hipLaunchKernelGGL(k_sah_finish, dim3(n_finish), dim3(64), 0, st, b.elems, b.finish, t.vals[0], b.counters, t.tp, n);
+    const auto finish_kernel = t.sah3 ? k_sah3_finish : k_sah_finish;
+    if (n_finish) hipLaunchKernelGGL(finish_kernel, dim3(n_finish), dim3(64), 0, st, b.elems, b.finish, t.vals[0], b.counters, t.tp, n);
     HIP_TRY(ctx, hipMemcpyAsync(h_readback, b.counters, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     t.first_chunk = std::min(std::max(h_readback[2], 1u), TRC_MAX_BVH_DEPTH + 1u);

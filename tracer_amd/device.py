@@ -450,7 +450,8 @@ class Tracer:
         self._n_vertex = leaves_view.n_vertex
 
     def upload_scene_device(self, view, flags):
-        """trc_upload_scene_device: abi.TREE_SAH | abi.TREE_TRIANGLE_LEAVES (bvhList = the analytic primitives' leaves only)."""
+        """trc_upload_scene_device: abi.TREE_SAH | abi.TREE_TRIANGLE_LEAVES (bvhList = the analytic primitives' leaves only); with
+        abi.TREE_SAH, abi.TREE_SAH3 asks for the three-axis, 32-bin split (a tree of lower cost that is no longer the reference's)."""
         self._check(self._L.trc_upload_scene_device(self._h, C.byref(view), flags), "trc_upload_scene_device")
         self._n_vertex = view.n_vertex
 
@@ -464,7 +465,8 @@ class Tracer:
 
     def rebuild_tree(self, flags=0):
         """trc_rebuild_tree: a fresh tree over the scene's current leaf records, built on the device from what it holds -- abi.TREE_SAH
-        for the reference's binned-SAH tree, 0 for the LBVH with rotations.  Vertices, materials, rest copy and binding stay."""
+        for the reference's binned-SAH tree (| abi.TREE_SAH3: the three-axis, 32-bin split), 0 for the LBVH with rotations.  Vertices, materials,
+        rest copy and binding stay."""
         self._check(self._L.trc_rebuild_tree(self._h, flags), "trc_rebuild_tree")
 
     def tree_cost(self):

@@ -38,6 +38,8 @@ def lib():
         L.trc_host_make_cube.restype = None
         L.trc_host_build_tree.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(C.c_uint32)]
         L.trc_host_build_tree.restype = C.c_int32
+        L.trc_host_build_tree_flags.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.trc_host_build_tree_flags.restype = C.c_int32
         L.trc_host_tree_depth.argtypes = [C.POINTER(abi.BVH), C.c_uint32, C.POINTER(C.c_uint32)]
         L.trc_host_tree_depth.restype = C.c_int32
         L.trc_host_make_camera.argtypes = [C.POINTER(abi.Camera), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -367,14 +369,18 @@ def fill_rng(seed, width, height):
     return out
 
 
-def build_tree(leaves):
-    """leaves: list of abi.BVH leaf records -> ctypes array of 2n-1 nodes, root at 0."""
+def build_tree(leaves, flags=None):
+    """leaves: list of abi.BVH leaf records -> ctypes array of 2n-1 nodes, root at 0.  flags: None = trc_host_build_tree, else
+    trc_host_build_tree_flags (abi.TREE_SAH, or abi.TREE_SAH | abi.TREE_SAH3 for the three-axis, 32-bin split)."""
     n = len(leaves)
     nodes = (abi.BVH * (2 * n - 1))()
     for i, leaf in enumerate(leaves):
         nodes[i] = leaf
     count = C.c_uint32()
-    _check(lib().trc_host_build_tree(nodes, n, C.byref(count)), "trc_host_build_tree")
+    if flags is None:
+        _check(lib().trc_host_build_tree(nodes, n, C.byref(count)), "trc_host_build_tree")
+    else:
+        _check(lib().trc_host_build_tree_flags(nodes, n, flags, C.byref(count)), "trc_host_build_tree_flags")
     assert count.value == 2 * n - 1
     return nodes
 

@@ -29,6 +29,7 @@ using namespace trc;
 namespace {
 
 constexpr uint32_t kBuckets = 10;
+constexpr uint32_t kBins3 = 32;             // TRC_TREE_SAH3: bins per axis
 
 struct Builder {
     trc_BVH* nodes;            // final array; leaves live at [1, n]
@@ -36,8 +37,74 @@ struct Builder {
     std::vector<uint32_t> idx; // permutation of final leaf slots
     std::vector<trc_float3> centroid;  // per final slot (leaves only, index - 1)
     std::atomic<int> spare_threads;
+    bool sah3 = false;         // TRC_TREE_SAH3: the split of a node of three or more leaves is split3()
 
     const trc_float3& cen(uint32_t slot) const { return centroid[slot - 1]; }
+
+    // TRC_TREE_SAH3 (the definition is in include/tracer_abi.h): every axis with a positive centroid extent, 32 bins, the 31 splits of
+    // each priced as n0 A(B0) + n1 A(B1), first minimum in (axis, i) order; the records of bins <= i go left by the two-ended swap loop.
+    // false: all centroids are identical -- the caller's median split with the order kept
+    bool split3(uint32_t start, uint32_t end, const trc_AABB& cbox, uint32_t& dim, uint32_t& mid) {
+        auto bin_of = [&](uint32_t slot, uint32_t a, float lo, float e) -> uint32_t {
+            const float rel = (get(cen(slot), a) - lo) / e;
+            const float fb = kBins3 * rel;
+            const uint32_t b = (fb >= 0.0f) ? (uint32_t)fb : 0u;
+            return std::min(b, kBins3 - 1);
+        };
+        bool have = false;
+        float best = 0.0f, best_lo = 0.0f, best_e = 0.0f;
+        uint32_t best_axis = 0, best_i = 0;
+        for (uint32_t a = 0; a < 3; ++a) {
+            const float lo = get(cbox.mini, a), e = get(cbox.maxi, a) - lo;
+            if (!(e > 0.0f)) continue;
+            uint32_t count[kBins3] = {0};
+            trc_AABB bbox[kBins3], suffix[kBins3];         // suffix[i]: bins i .. 31
+            uint32_t suffix_n[kBins3];
+            for (auto& b : bbox) b = empty_box();
+            for (uint32_t i = start; i < end; ++i) {
+                const uint32_t slot = idx[i], b = bin_of(slot, a, lo, e);
+                bbox[b] = box_union(bbox[b], nodes[slot].bBOX);
+                count[b]++;
+            }
+            suffix[kBins3 - 1] = bbox[kBins3 - 1]; suffix_n[kBins3 - 1] = count[kBins3 - 1];
+            for (uint32_t i = kBins3 - 1; i-- > 0;) { suffix[i] = box_union(bbox[i], suffix[i + 1]); suffix_n[i] = count[i] + suffix_n[i + 1]; }
+            trc_AABB b0 = empty_box();
+            uint32_t n0 = 0;
+            for (uint32_t i = 0; i + 1 < kBins3; ++i) {
+                b0 = box_union(b0, bbox[i]); n0 += count[i];
+                const uint32_t n1 = suffix_n[i + 1];
+                if (n0 == 0 || n1 == 0) continue;
+                const float cost = (float)n0 * box_area(b0) + (float)n1 * box_area(suffix[i + 1]);
+                if (!have || cost < best) { have = true; best = cost; best_axis = a; best_i = i; best_lo = lo; best_e = e; }
+            }
+        }
+        if (!have) return false;
+        auto pm = std::partition(idx.begin() + start, idx.begin() + end, [&](uint32_t slot) { return bin_of(slot, best_axis, best_lo, best_e) <= best_i; });
+        dim = best_axis;
+        mid = (uint32_t)(pm - idx.begin());
+        return true;
+    }
+
+    // the two subtrees of a node split at mid, side by side where a thread is spare
+    void children(uint32_t start, uint32_t mid, uint32_t end, uint32_t base, uint32_t& left, uint32_t& right) {
+        const uint32_t span = end - start;
+        const uint32_t left_base = base;
+        const uint32_t right_base = base + (mid - start - 1);
+        bool forked = false;
+        if (span > 4096 && spare_threads.fetch_sub(1) > 0) {
+            forked = true;
+            std::thread t([&] { left = build(start, mid, left_base, false); });
+            right = build(mid, end, right_base, false);
+            t.join();
+            spare_threads.fetch_add(1);
+        } else if (span > 4096) {
+            spare_threads.fetch_add(1);
+        }
+        if (!forked) {
+            left = build(start, mid, left_base, false);
+            right = build(mid, end, right_base, false);
+        }
+    }
 
     // returns the final index of the subtree root. `base` = first interior slot owned by it.
     uint32_t build(uint32_t start, uint32_t end, uint32_t base, bool is_root) {
@@ -49,6 +116,11 @@ struct Builder {
             const uint32_t a = idx[start], b = idx[start + 1];
             dim = box_max_extent(box_of(cen(a), cen(b)));
             if (get(cen(a), dim) < get(cen(b), dim)) { left = a; right = b; } else { left = b; right = a; }
+        } else if (sah3) {
+            trc_AABB cbox = empty_box();
+            for (uint32_t i = start; i < end; ++i) cbox = box_grow(cbox, cen(idx[i]));
+            if (!split3(start, end, cbox, dim, mid)) { dim = 2; mid = start + span / 2; }
+            children(start, mid, end, base, left, right);
         } else {
             trc_AABB cbox = empty_box();
             for (uint32_t i = start; i < end; ++i) cbox = box_grow(cbox, cen(idx[i]));
@@ -98,22 +170,7 @@ struct Builder {
                 mid = start + span / 2;
             }
 
-            const uint32_t left_base = base;
-            const uint32_t right_base = base + (mid - start - 1);
-            bool forked = false;
-            if (span > 4096 && spare_threads.fetch_sub(1) > 0) {
-                forked = true;
-                std::thread t([&] { left = build(start, mid, left_base, false); });
-                right = build(mid, end, right_base, false);
-                t.join();
-                spare_threads.fetch_add(1);
-            } else if (span > 4096) {
-                spare_threads.fetch_add(1);
-            }
-            if (!forked) {
-                left = build(start, mid, left_base, false);
-                right = build(mid, end, right_base, false);
-            }
+            children(start, mid, end, base, left, right);
         }
 
         const uint32_t self = is_root ? 0u : (base + span - 2);
@@ -147,7 +204,16 @@ void trc_host_build_node(const trc_AABB* box, const trc_float4x4* model_matrix,
     out->bBOX.maxi = hi;
 }
 
-trc_status trc_host_build_tree(trc_BVH* nodes, uint32_t n_leaves, uint32_t* out_n_nodes) {
+static trc_status build_tree(trc_BVH* nodes, uint32_t n_leaves, bool sah3, uint32_t* out_n_nodes);
+
+trc_status trc_host_build_tree(trc_BVH* nodes, uint32_t n_leaves, uint32_t* out_n_nodes) { return build_tree(nodes, n_leaves, false, out_n_nodes); }
+
+trc_status trc_host_build_tree_flags(trc_BVH* nodes, uint32_t n_leaves, uint32_t flags, uint32_t* out_n_nodes) {
+    if (flags != TRC_TREE_SAH && flags != (TRC_TREE_SAH | TRC_TREE_SAH3)) return TRC_ERR_INVALID_ARG;
+    return build_tree(nodes, n_leaves, (flags & TRC_TREE_SAH3) != 0, out_n_nodes);
+}
+
+static trc_status build_tree(trc_BVH* nodes, uint32_t n_leaves, bool sah3, uint32_t* out_n_nodes) {
     if (!nodes || n_leaves < 2) return TRC_ERR_INVALID_ARG;
     // leaves move from [0, n) to [1, n]; slot 0 becomes the root (BVH.hh:263-268)
     for (uint32_t i = n_leaves; i > 0; --i) nodes[i] = nodes[i - 1];
@@ -155,6 +221,7 @@ trc_status trc_host_build_tree(trc_BVH* nodes, uint32_t n_leaves, uint32_t* out_
     Builder b;
     b.nodes = nodes;
     b.n = n_leaves;
+    b.sah3 = sah3;
     b.idx.resize(n_leaves);
     b.centroid.resize(n_leaves);
     for (uint32_t i = 0; i < n_leaves; ++i) {
