@@ -27,6 +27,9 @@
 //                          frame is denoised (trc_denoise) and the DENOISED frame is what <out> and <out>.k.png hold; per frame the mean
 //                          history length over the hit pixels is printed (1 = no history; it grows by one per frame where the filter
 //                          found the surface again).  Use it with a low --spp: that is what the history is for
+//              [--hide FIRST:COUNT]  after the upload, triangles FIRST .. FIRST + COUNT - 1 of the mesh lose their leaves (trc_set_triangle_visibility,
+//                          TRC_TREE_SAH: the tree over what is left is built on the device); may be given more than once, and combines with
+//                          --spin / --pose / --bend / --morph: hidden triangles go on moving, they have no leaf to refit
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -58,6 +61,7 @@ int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
+    std::vector<trc_triangle_range> hidden;
     double rebuild_ratio = 0.0;
     bool lbvh = false, device_sah = false, device_sah3 = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
@@ -103,6 +107,14 @@ int main(int argc, char** argv) {
         else if (a == "--rebuild-ratio" && i + 1 < argc) {                   // a fresh tree when the refitted one has worn: trc_tree_cost, trc_rebuild_tree
             rebuild_ratio = std::atof(argv[++i]);
             if (!(rebuild_ratio >= 1.0)) { std::fprintf(stderr, "--rebuild-ratio wants a factor of at least 1, not %s\n", argv[i]); return 2; }
+        }
+        else if (a == "--hide" && i + 1 < argc) {                               // mesh triangles without a leaf: trc_set_triangle_visibility
+            unsigned long long first = 0, count = 0;
+            if (std::sscanf(argv[++i], "%llu:%llu", &first, &count) != 2 || first > 0xFFFFFFFFull || count > 0xFFFFFFFFull) {
+                std::fprintf(stderr, "--hide wants FIRST:COUNT, two triangle numbers, not %s\n", argv[i]);
+                return 2;
+            }
+            hidden.push_back(trc_triangle_range{(uint32_t)first, (uint32_t)count, 0u});
         }
         else if (a == "--normals") normals = true;                              // smooth normals re-derived on the device after every animation call
         else if (a == "--denoise") denoise = true;                              // SVGF on every frame, the history kept across the animation calls
@@ -234,6 +246,15 @@ int main(int argc, char** argv) {
     CHECK(trc_set_camera(ctx, &cam));
     CHECK(trc_resize(ctx, W, H));
     CHECK(trc_seed(ctx, 0x5EED0000ull));
+
+    if (!hidden.empty()) {
+        const auto h0 = std::chrono::steady_clock::now();
+        CHECK(trc_set_triangle_visibility(ctx, hidden.data(), (uint32_t)hidden.size(), TRC_TREE_SAH | (device_sah3 ? TRC_TREE_SAH3 : 0u)));
+        const double hide_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+        uint32_t n_records = 0;
+        CHECK(trc_lbvh_info(ctx, &n_records, nullptr, nullptr));
+        std::printf("--hide: %zu ranges, trc_set_triangle_visibility %.2f ms -> a tree of %u leaves\n", hidden.size(), hide_ms, (n_records + 1) / 2);
+    }
 
     trc_params prm;
     std::memset(&prm, 0, sizeof prm);

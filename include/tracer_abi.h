@@ -69,7 +69,10 @@ extern "C" {
  *     trc_host_make_cube (spheres, squares and cubes moved on the device; with tracking on the history follows them too: the motion
  *     texel of an analytic hit may now be non-zero; additions only, nothing existing changed)
  *     added under 13, the number stays: TRC_TREE_SAH3, trc_host_build_tree_flags (a three-axis, 32-bin SAH split as an option of the
- *     SAH builds on the host and on the device; opt-in, nothing defaults to it; additions only, nothing existing changed) */
+ *     SAH builds on the host and on the device; opt-in, nothing defaults to it; additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_triangle_range, trc_set_triangle_visibility, trc_download_triangle_visibility,
+ *     trc_debug_visibility_ms (mesh triangles shown and hidden on the device: a tree over the visible leaves from what the device holds;
+ *     additions only, nothing existing changed) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -890,6 +893,49 @@ typedef struct trc_tree_cost_t {
     uint32_t n_interior, n_leaves;
 } trc_tree_cost_t;
 trc_status trc_tree_cost(trc_ctx* ctx, trc_tree_cost_t* out);
+/* Which of the mesh's triangles exist.  An object that enters or leaves a shot, a prop that is switched off, an LOD swap: without this
+ * call they cost trc_download_vertices and a whole trc_upload_scene*, which drops the rest copy, the bindings, the per-triangle materials,
+ * the block costs, the normals' adjacency and the denoiser history.  trc_set_triangle_visibility changes a per-triangle mask and builds the
+ * tree over the leaves that are left, from what the DEVICE holds.  Triangle t is the t-th of idxList, as for trc_upload_triangle_materials.
+ *  - Mask.  One bit per triangle.  Until the first call of a scene it is implicit: a triangle is visible iff a leaf of the tree in use
+ *    names it.  The first call (set or download) makes it explicit on the device, one byte per triangle.  A tree that names one triangle in
+ *    two leaves has no such mask: TRC_ERR_UNSUPPORTED, nothing changes (the case trc_rebuild_tree refuses).  Every trc_upload_scene*
+ *    drops the mask; the next tree defines it again.
+ *  - Ranges are applied in the order given, a later range wins.  visible is 0 or 1, first + count <= n_index / 3.  n_ranges == 0 is
+ *    legal: the leaf list below is built from the mask as it stands.
+ *  - The leaf list has two parts.  First the analytic leaves (spheres, squares, cubes): the records trc_rebuild_tree would start from at
+ *    this moment -- slots 1..n of trc_download_bvh for a device-built tree, the canonical order for a caller's tree -- filtered to
+ *    pType != TRC_PRIM_TRIANGLE, in that order, with the boxes they hold.  Then one record per visible triangle, ascending t: pType
+ *    TRC_PRIM_TRIANGLE, pIndex t, the box BVH::buildNode of its three CURRENT vertices (the bits an upload with TRC_TREE_TRIANGLE_LEAVES
+ *    writes), padding lanes 0, parent, left, right and axis 0.  One rule for every triangle, because a triangle that was hidden while its
+ *    vertices moved has no stored box.  Its consequence: a visible triangle whose caller-supplied leaf box was not buildNode of its
+ *    vertices gets the canonical box (the project's scene builders never make such a box).
+ *  - Tree.  Over that list of n' leaves: the tree trc_upload_scene_sah builds from it (tree_flags == TRC_TREE_SAH), trc_upload_scene_lbvh
+ *    (0), or trc_upload_scene_device(TRC_TREE_SAH | TRC_TREE_SAH3) (those two flags) -- record for record in trc_download_bvh (2 n' - 1
+ *    records), fat node for fat node on the device, with the LDS plan of that upload: a scene that shrinks enough becomes LDS-resident.
+ *    Afterwards the scene is a device-built one; a later trc_rebuild_tree takes slots 1..n', the visible leaves only.
+ *  - Capacity.  The layout of the device's scene does not move: the node region keeps the room of the tree that was uploaded, and the
+ *    reference-layout array is allocated for that many leaves; the counts trc_download_bvh and trc_lbvh_info report follow n'.  Showing
+ *    everything again fits without reallocating the scene.  A caller's tree that left triangles out was laid out for its own leaf count: a
+ *    call that would leave more leaves than that is TRC_ERR_INVALID_ARG.
+ *  - What survives and what is dropped: trc_rebuild_tree's list, block costs kept.  With trc_denoise_track_motion on the G-buffer is
+ *    stale and the history kept; a pixel whose surface appeared or vanished fails the id / depth test and starts again at length 1.
+ *    Hidden triangles keep their records, vertices, materials and bindings: every animation call goes on computing their vertices and
+ *    rewriting their records (they have no leaf to refit), and trc_recompute_normals still sums over them -- the adjacency is the index
+ *    list's.  Under TRC_FLAG_MESH_LIGHTS a hidden triangle is no light: weight 0, pdfA 0; the tables are rebuilt at the next flagged render.
+ *  - Atomic on error: mask and tree are as they were, and everything that can refuse comes before the first byte of the tree in use is
+ *    overwritten.  TRC_ERR_INVALID_ARG: ranges == NULL with n_ranges > 0, a range beyond n_index / 3, visible > 1, a flag other than
+ *    TRC_TREE_SAH and its modifier TRC_TREE_SAH3 (or the modifier alone), fewer than 2 leaves left, more than 2^31 - 2 ranges.
+ *    TRC_ERR_NO_SCENE, TRC_ERR_UNSUPPORTED (above), TRC_ERR_BVH_INVALID and TRC_ERR_OOM as for trc_rebuild_tree.
+ *  - Launches kept back for coalescing run first.  Not collective.  Cost: the ranges' triangles are stamped once each, then three
+ *    streaming passes over the triangles and the leaves (mask, partition, leaf records), then the build over n' leaves.
+ * trc_download_triangle_visibility writes n_index / 3 bytes, 1 = visible (nothing for a scene without triangles); it refuses what the
+ * first bullet refuses.  trc_debug_visibility_ms: device time of the last call's leaf-list stage (tools/visibility_bench.py).
+ * Out of scope: analytic primitives (move them away with trc_update_primitives); triangles beyond the uploaded index list; partial rebuilds. */
+typedef struct trc_triangle_range { uint32_t first, count, visible; } trc_triangle_range;   /* 12 bytes */
+trc_status trc_set_triangle_visibility(trc_ctx* ctx, const trc_triangle_range* ranges, uint32_t n_ranges, uint32_t tree_flags);
+trc_status trc_download_triangle_visibility(trc_ctx* ctx, uint8_t* out /* n_index / 3 bytes, 1 = visible */);
+trc_status trc_debug_visibility_ms(trc_ctx* ctx, float* leaf_list_ms);
 trc_status trc_resize(trc_ctx* ctx, uint32_t width, uint32_t height);
 /* deterministic stand-in for fillRNG (AAPLRenderer.mm:296-344, arc4random):
  * texel(x,y) = 4 successive pcg32 outputs of pcg32_srandom_r(seed, y*W+x),
@@ -1481,6 +1527,7 @@ TRC_SA(sizeof(trc_skin_influence) == 32 && offsetof(trc_skin_influence, weight) 
 TRC_SA(sizeof(trc_skin_bone) == 128 && offsetof(trc_skin_bone, normal_matrix) == 64, "skin_bone");
 TRC_SA(sizeof(trc_morph_delta) == 24 && offsetof(trc_morph_delta, dn) == 12, "morph_delta");
 TRC_SA(sizeof(trc_tree_cost_t) == 32 && offsetof(trc_tree_cost_t, n_interior) == 24, "tree_cost");
+TRC_SA(sizeof(trc_triangle_range) == 12 && offsetof(trc_triangle_range, visible) == 8, "triangle_range");
 TRC_SA(sizeof(trc_TextureInfo) == 32 && offsetof(trc_TextureInfo, albedo) == 16, "TextureInfo");
 TRC_SA(sizeof(trc_Material) == 64 && offsetof(trc_Material, medium) == 4 && offsetof(trc_Material, specular) == 8 &&
        offsetof(trc_Material, eta) == 12 && offsetof(trc_Material, roughness) == 16 &&

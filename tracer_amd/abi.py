@@ -258,6 +258,11 @@ class TreeCost(C.Structure):
                 ("n_interior", C.c_uint32), ("n_leaves", C.c_uint32)]
 
 
+class TriangleRange(C.Structure):
+    """trc_triangle_range: triangles first .. first + count - 1 of the index list become visible (1) or hidden (0)"""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("visible", C.c_uint32)]
+
+
 class KernelChoice(C.Structure):
     """trc_kernel_choice (tracer_test_hooks.h)"""
     _fields_ = [("shape", C.c_uint32), ("variant", C.c_uint32), ("lds_resident", C.c_uint32), ("triangle_materials", C.c_uint32),
@@ -294,7 +299,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32,
+                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32, TriangleRange: 12,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -314,6 +319,7 @@ DEVICE_SYMBOLS = [
     "trc_pose_vertices", "trc_download_vertices", "trc_debug_pose_overflows", "trc_skin_bind", "trc_skin_vertices",
     "trc_morph_bind", "trc_morph_vertices", "trc_recompute_normals",
     "trc_rebuild_tree", "trc_tree_cost", "trc_update_primitives",
+    "trc_set_triangle_visibility", "trc_download_triangle_visibility", "trc_debug_visibility_ms",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",

@@ -395,6 +395,7 @@ trc_status trc_read_to_host(trc_ctx* ctx, hipStream_t st, const char* what, std:
 void trc_release_scene(trc_ctx* ctx) {
     (void)hipFree(ctx->d_blob); ctx->d_blob = nullptr;
     (void)hipFree(ctx->d_bvh_ref); ctx->d_bvh_ref = nullptr; ctx->n_bvh_ref = 0;
+    (void)hipFree(ctx->d_vis); ctx->d_vis = nullptr;      // trc_set_triangle_visibility: the next tree defines the mask again
     ctx->has_scene = false;
     trc_mesh_light_free(ctx);
     trc_refit_free(ctx);

@@ -198,6 +198,10 @@ struct trc_ctx {
     trc_BVH* d_bvh_ref = nullptr;    // tree built by trc_upload_scene_lbvh / _sah / _device or trc_rebuild_tree, reference array layout (trc_download_bvh)
     uint32_t n_bvh_ref = 0, lbvh_height = 0;
     float lbvh_build_ms = 0.0f;
+    // trc_set_triangle_visibility (trc_visibility.hpp): one byte per triangle, 1 = visible, padded to 16 bytes; null until the first call of a
+    // scene makes the mask explicit (a triangle is visible iff a leaf of the tree names it).  Freed with the scene (trc_release_scene)
+    uint8_t* d_vis = nullptr;
+    float vis_leaf_ms = 0.0f;        // device time of the last call's leaf-list stage: mask, partition, leaf records (trc_debug_visibility_ms)
     // the scene's vertex and index arrays, kept beside the blob by every upload (trc_repack_triangles), and what the calls that move
     // them keep (RefitState); all freed with the blob (trc_refit_free)
     trc_TriangleVertex* d_verts = nullptr; uint32_t* d_idx = nullptr; uint32_t n_vertex = 0;

@@ -22,6 +22,8 @@
 // reference-layout tree as the last upload or refit left them -- for a caller's tree (trc_upload_scene), which has none, k_canonical_leaves
 // writes them from the fat nodes' leaf slots -- and k_lbvh_emit overwrites the node region of the blob and the records in place.
 // trc_tree_cost (k_tree_cost, k_tree_cost_sum) is a surface-area measure of the fat nodes as they stand.
+// trc_set_triangle_visibility (trc_visibility.hpp) writes a NEW leaf list -- the analytic leaves of those records, then one per visible triangle --
+// and runs the same steps over it with n = n' (rebuild_from_records: the tail it shares with trc_rebuild_tree).
 //
 // All of it is integer / min-max work on a few bytes per leaf: HBM-bound streaming passes, no MFMA.  The CPU
 // statement of the same build is oracle/oracle_lbvh.cpp; tests compare all 2n-1 records bit for bit.
@@ -33,6 +35,7 @@
 #include <memory>
 #include <new>
 
+#include "dev_trileaf.hpp"
 #include "trc_ctx.hpp"
 #include "trc_scene_prep.hpp"
 
@@ -786,6 +789,8 @@ trc_status canonical_leaf_records(TreeBuild& b, DevBuf& new_ref) {
     return TRC_OK;
 }
 
+trc_status rebuild_from_records(TreeBuild& b, DevBuf& new_ref, TimedSection& timed);
+
 // The second way into the steps: everything from what the device holds.  Whatever can refuse comes before renumber_and_emit, which is the first
 // to write into the tree in use; from there on only a HIP error can end the call
 trc_status rebuild_tree(TreeBuild& b) {
@@ -796,6 +801,13 @@ trc_status rebuild_tree(TreeBuild& b) {
     reserve_temporaries(b, b.ref ? 0u : (size_t)b.n * 33u);      // a caller's tree: two key / value pairs over its 2 (n - 1) child slots
     TimedSection timed(ctx, b.st);
     if (!b.ref) TRC_TRY(canonical_leaf_records(b, new_ref));
+    return rebuild_from_records(b, new_ref, timed);
+}
+
+// ... and the steps from the leaf records in slots 1..b.n of b.ref on, for trc_rebuild_tree and trc_set_triangle_visibility (trc_visibility.hpp)
+// alike; b.sc.n_nodes == b.n - 1.  new_ref, where it holds an array, is b.ref and takes the place of the context's when the tree is in place
+trc_status rebuild_from_records(TreeBuild& b, DevBuf& new_ref, TimedSection& timed) {
+    trc_ctx* const ctx = b.ctx;
     TRC_TRY(work_arrays(b));
     leaf_records(b);
     if (b.sah) TRC_TRY(sah_build_topology(b)); else lbvh_topology(b);
@@ -807,13 +819,17 @@ trc_status rebuild_tree(TreeBuild& b) {
     trc_sppm_order_after_camera(ctx);             // a camera pass running ahead on its own stream still walks the old nodes
     TRC_TRY(renumber_and_emit(b));
     timed.stop();
-    // the new tree is on its way: the layout stays (same leaf count), the LDS plan follows the new height, the root box is the new root's
+    // the new tree is on its way: the layout stays (the node region keeps its room), the LDS plan follows the new height, the root box is the new root's
     plan_lds(b.sc, height, true);
     ctx->ks.sc = b.sc;
     std::memcpy(ctx->ks.root_box, root_box, sizeof root_box);
     ctx->lds_scene = b.sc.n_lds_nodes == b.sc.n_nodes;
     ctx->lds_prefix_ok = true;
-    if (new_ref.p) ctx->d_bvh_ref = static_cast<trc_BVH*>(new_ref.release());
+    if (new_ref.p) {      // (a caller's tree had none; trc_set_triangle_visibility replaces the one it read the analytic leaves from)
+        HIP_TRY(ctx, hipStreamSynchronize(b.st));
+        (void)hipFree(ctx->d_bvh_ref);
+        ctx->d_bvh_ref = static_cast<trc_BVH*>(new_ref.release());
+    }
     ctx->n_bvh_ref = 2 * b.n - 1;
     ctx->lbvh_height = height;
     trc_scene_changed(ctx, kSceneTreeRebuilt);
@@ -822,6 +838,8 @@ trc_status rebuild_tree(TreeBuild& b) {
     ctx->lbvh_build_ms = timed.ms();
     return TRC_OK;
 }
+
+#include "trc_visibility.hpp"
 
 }  // namespace
 
@@ -863,6 +881,46 @@ trc_status trc_rebuild_tree(trc_ctx* ctx, uint32_t flags) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     TreeBuild b{ctx, ctx->stream, nullptr, (flags & TRC_TREE_SAH) != 0, false, (flags & TRC_TREE_SAH3) != 0};
     return rebuild_tree(b);
+}
+
+trc_status trc_set_triangle_visibility(trc_ctx* ctx, const trc_triangle_range* ranges, uint32_t n_ranges, uint32_t tree_flags) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    const char* const who = "trc_set_triangle_visibility: ";
+    if (tree_flags & ~(uint32_t)(TRC_TREE_SAH | TRC_TREE_SAH3)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "flags other than TRC_TREE_SAH, TRC_TREE_SAH3");
+    if ((tree_flags & TRC_TREE_SAH3) && !(tree_flags & TRC_TREE_SAH)) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "TRC_TREE_SAH3 modifies TRC_TREE_SAH");
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, std::string(who) + "no scene");
+    if (n_ranges && !ranges) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "ranges == NULL with n_ranges > 0");
+    if (n_ranges > 0x7FFFFFFEu) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "more than 2^31 - 2 ranges");
+    const uint32_t n_tri = ctx->ks.sc.n_triangles;
+    std::vector<VisPiece> pieces;      // a range in workgroup-sized pieces, each with its range's stamp: (number + 1) << 1 | visible
+    for (uint32_t r = 0; r < n_ranges; ++r) {
+        const trc_triangle_range& g = ranges[r];
+        if (g.visible > 1u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "visible is neither 0 nor 1");
+        if (g.first > n_tri || g.count > n_tri - g.first) return trc_fail(ctx, TRC_ERR_INVALID_ARG, std::string(who) + "first + count > n_index / 3");
+        for (uint32_t off = 0; off < g.count; off += kVisPiece) pieces.push_back(VisPiece{g.first + off, std::min(kVisPiece, g.count - off), ((r + 1u) << 1) | g.visible});
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TreeBuild b{ctx, ctx->stream, nullptr, (tree_flags & TRC_TREE_SAH) != 0, false, (tree_flags & TRC_TREE_SAH3) != 0};
+    return set_visibility(b, pieces);
+}
+
+trc_status trc_download_triangle_visibility(trc_ctx* ctx, uint8_t* out) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_download_triangle_visibility: no scene");
+    const uint32_t n_tri = ctx->ks.sc.n_triangles;
+    if (n_tri == 0) return TRC_OK;
+    if (!out) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_download_triangle_visibility: out == NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_vis) TRC_TRY(vis_make_explicit(ctx, "trc_download_triangle_visibility"));
+    return trc_copy_to_host(ctx, out, ctx->d_vis, n_tri, ctx->stream);      // synchronous
+}
+
+trc_status trc_debug_visibility_ms(trc_ctx* ctx, float* leaf_list_ms) {
+    if (!ctx || !leaf_list_ms) return TRC_ERR_INVALID_ARG;
+    *leaf_list_ms = ctx->vis_leaf_ms;
+    return TRC_OK;
 }
 
 trc_status trc_tree_cost(trc_ctx* ctx, trc_tree_cost_t* out) {

@@ -1,7 +1,8 @@
 // trc_meshlight.hip -- the sampling tables of the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS, tracer_abi.h; sampled by
 // dev_meshlight.hpp in the k_render*_mesh kernels).  Built once per scene and triangle-material array, at the first flagged render after
 // trc_upload_scene* / trc_upload_triangle_materials:
-//   k_mesh_weights   one thread per triangle: its weight as a light, luminance(albedo) * area in float64, 0 when it is none
+//   k_mesh_weights   one thread per triangle: its weight as a light, luminance(albedo) * area in float64, 0 when it is none or
+//                    when trc_set_triangle_visibility hides it (the mask, where the scene has one)
 //                    (dev_meshlight.hpp: mesh_light_weight; the material is dword 15 of the attribute record, 19 after a scene upload)
 //   k_mesh_compact   one workgroup: the lights' triangle indices and weights, in triangle order (each thread counts, then writes, one
 //                    contiguous chunk of the triangles; a scan over the counts in between)
@@ -18,12 +19,13 @@
 
 namespace {
 
-struct MeshScene { const uint32_t* blob; uint32_t off_tripos, off_triattr, off_materials, n_materials, n_tri; };
+struct MeshScene { const uint32_t* blob; uint32_t off_tripos, off_triattr, off_materials, n_materials, n_tri; const uint8_t* vis; };      // vis: trc_set_triangle_visibility's mask (null: none)
 
 __device__ double tri_weight(const MeshScene& ms, uint32_t t, float& area) {
     F3 v0, v1, v2;
     mesh_tri_load(ms.blob + ms.off_tripos, t, v0, v1, v2);
     area = mesh_tri_area(v0, v1, v2);
+    if (ms.vis && !ms.vis[t]) return 0.0;      // a hidden triangle is no light
     const uint32_t m = ms.blob[ms.off_triattr + (size_t)t * kTriAttrDwords + 15u];
     if (m >= ms.n_materials) return 0.0;
     const uint32_t* mat = ms.blob + ms.off_materials + (size_t)m * kMaterialDwords;
@@ -107,7 +109,7 @@ trc_status trc_mesh_light_build(trc_ctx* ctx) {
     uint32_t* list = reinterpret_cast<uint32_t*>(q + n);
     double* total = reinterpret_cast<double*>(t + L.total);
     uint32_t* count = reinterpret_cast<uint32_t*>(t + L.count);
-    const MeshScene ms{ctx->d_blob, sc.off_tripos, sc.off_triattr, sc.off_materials, sc.n_materials, n};
+    const MeshScene ms{ctx->d_blob, sc.off_tripos, sc.off_triattr, sc.off_materials, sc.n_materials, n, ctx->d_vis};
     const unsigned grid = (n + 255u) / 256u;
     hipLaunchKernelGGL(k_mesh_weights, dim3(grid), dim3(256), 0, ctx->stream, ms, w);
     hipLaunchKernelGGL(k_mesh_compact, dim3(1), dim3(1024), 0, ctx->stream, w, n, reinterpret_cast<uint32_t*>(t + L.tri), wl, count);

@@ -134,6 +134,9 @@ def _load(path, hooks=False):
     L.trc_recompute_normals.argtypes = [vp, u32, u32]
     L.trc_rebuild_tree.argtypes = [vp, u32]
     L.trc_tree_cost.argtypes = [vp, C.POINTER(abi.TreeCost)]
+    L.trc_set_triangle_visibility.argtypes = [vp, C.POINTER(abi.TriangleRange), u32, u32]
+    L.trc_download_triangle_visibility.argtypes = [vp, vp]
+    L.trc_debug_visibility_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.trc_update_primitives.argtypes = [vp, C.POINTER(abi.PrimitiveRanges)]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
@@ -205,6 +208,7 @@ class Tracer:
             raise TracerError(f"trc_create(device={device})", st, self._L.trc_status_string(st).decode())
         self.width = self.height = 0
         self._n_vertex = 0               # of the scene uploaded through this object (download_vertices' default count)
+        self._n_triangle = 0             # ... and its triangles (triangle_visibility's length)
 
     def _check(self, st, what):
         if st != abi.OK:
@@ -227,6 +231,7 @@ class Tracer:
     def upload_scene(self, scene_view):
         self._check(self._L.trc_upload_scene(self._h, C.byref(scene_view)), "trc_upload_scene")
         self._n_vertex = scene_view.n_vertex
+        self._n_triangle = scene_view.n_index // 3
 
     def set_environment_map(self, rgb):
         """(h, w, 3) float32 equirectangular environment; None returns to the constant one."""
@@ -443,17 +448,20 @@ class Tracer:
         """Scene whose bvhList holds only leaf records (HostScene.leaves_view()); the tree is built on the GPU."""
         self._check(self._L.trc_upload_scene_lbvh(self._h, C.byref(leaves_view)), "trc_upload_scene_lbvh")
         self._n_vertex = leaves_view.n_vertex
+        self._n_triangle = leaves_view.n_index // 3
 
     def upload_scene_sah(self, leaves_view):
         """Same input as upload_scene_lbvh; the reference's binned-SAH tree (BVH::buildTree), built on the GPU."""
         self._check(self._L.trc_upload_scene_sah(self._h, C.byref(leaves_view)), "trc_upload_scene_sah")
         self._n_vertex = leaves_view.n_vertex
+        self._n_triangle = leaves_view.n_index // 3
 
     def upload_scene_device(self, view, flags):
         """trc_upload_scene_device: abi.TREE_SAH | abi.TREE_TRIANGLE_LEAVES (bvhList = the analytic primitives' leaves only); with
         abi.TREE_SAH, abi.TREE_SAH3 asks for the three-axis, 32-bin split (a tree of lower cost that is no longer the reference's)."""
         self._check(self._L.trc_upload_scene_device(self._h, C.byref(view), flags), "trc_upload_scene_device")
         self._n_vertex = view.n_vertex
+        self._n_triangle = view.n_index // 3
 
     def download_bvh(self):
         """The device-built tree in the reference's array layout: ctypes array of abi.BVH (2n-1 records)."""
@@ -475,6 +483,31 @@ class Tracer:
         out = abi.TreeCost()
         self._check(self._L.trc_tree_cost(self._h, C.byref(out)), "trc_tree_cost")
         return out
+
+    def set_triangle_visibility(self, ranges, flags=0):
+        """trc_set_triangle_visibility: `ranges` is a sequence of (first, count, visible) triples (or an abi.TriangleRange array, or None
+        for a NULL pointer), applied in order to the scene's per-triangle mask; then the tree over the analytic leaves and the visible
+        triangles is built on the device -- flags as for rebuild_tree.  Hidden triangles keep vertices, materials and bindings."""
+        if ranges is None:
+            arr, n = None, 0
+        elif isinstance(ranges, C.Array):
+            arr, n = ranges, len(ranges)
+        else:
+            ranges = [tuple(int(v) for v in r) for r in ranges]
+            arr, n = (abi.TriangleRange * max(len(ranges), 1))(*ranges), len(ranges)
+        self._check(self._L.trc_set_triangle_visibility(self._h, arr, n, flags), "trc_set_triangle_visibility")
+
+    def triangle_visibility(self):
+        """trc_download_triangle_visibility -> uint8 array, one per triangle of the index list, 1 = visible"""
+        out = np.zeros(self._n_triangle, dtype=np.uint8)
+        self._check(self._L.trc_download_triangle_visibility(self._h, out.ctypes.data if out.size else None), "trc_download_triangle_visibility")
+        return out
+
+    def visibility_ms(self):
+        """trc_debug_visibility_ms: device time of the last set_triangle_visibility's leaf-list stage (mask, partition, leaf records)"""
+        ms = C.c_float(0)
+        self._check(self._L.trc_debug_visibility_ms(self._h, C.byref(ms)), "trc_debug_visibility_ms")
+        return ms.value
 
     def lbvh_info(self):
         """(n_nodes, depth of the deepest leaf, GPU build time in ms) of the last upload_scene_lbvh."""
