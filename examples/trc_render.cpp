@@ -30,6 +30,10 @@
 //              [--hide FIRST:COUNT]  after the upload, triangles FIRST .. FIRST + COUNT - 1 of the mesh lose their leaves (trc_set_triangle_visibility,
 //                          TRC_TREE_SAH: the tree over what is left is built on the device); may be given more than once, and combines with
 //                          --spin / --pose / --bend / --morph: hidden triangles go on moving, they have no leaf to refit
+//              [--adaptive THRESHOLD|default [--max-spp N]]  the frame by trc_render_adaptive instead of trc_render: a first pass of --spp samples
+//                          (16 unless given) over every tile, then passes that double the count on the 16 x 16 tiles whose error estimate is still
+//                          above THRESHOLD, up to N (256) samples; prints the report and writes the per-tile sample counts as a grey image
+//                          (255 = N samples) to <out>.samples.png.  Takes traceMIS unless --integrator says otherwise (tracer_abi.h: why)
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -63,14 +67,23 @@ int main(int argc, char** argv) {
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
     std::vector<trc_triangle_range> hidden;
     double rebuild_ratio = 0.0;
+    bool adaptive = false, spp_given = false, integ_given = false;
+    trc_adaptive_params ad;
+    trc_adaptive_default_params(&ad);
     bool lbvh = false, device_sah = false, device_sah3 = false, sobol = false, size_given = false, env_light = false, mesh_lights = false, tri_materials = false, normals = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
-        else if (a == "--integrator" && i + 1 < argc) integ_name = argv[++i];
+        else if (a == "--integrator" && i + 1 < argc) { integ_name = argv[++i]; integ_given = true; }
         else if (a == "--size" && i + 2 < argc) { W = (uint32_t)std::atoi(argv[++i]); H = (uint32_t)std::atoi(argv[++i]); size_given = true; }
         else if (a == "--pbrt" && i + 1 < argc) pbrt_path = argv[++i];          // a whole pbrt-v3 scene
-        else if (a == "--spp" && i + 1 < argc) spp = (uint32_t)std::atoi(argv[++i]);
+        else if (a == "--spp" && i + 1 < argc) { spp = (uint32_t)std::atoi(argv[++i]); spp_given = true; }
+        else if (a == "--adaptive" && i + 1 < argc) {                           // samples where the picture is still noisy: trc_render_adaptive
+            adaptive = true;
+            if (std::strcmp(argv[++i], "default") != 0) ad.threshold = (float)std::atof(argv[i]);
+            if (!(ad.threshold > 0.0f) || !std::isfinite(ad.threshold)) { std::fprintf(stderr, "--adaptive wants a threshold above 0 (or `default`), not %s\n", argv[i]); return 2; }
+        }
+        else if (a == "--max-spp" && i + 1 < argc) ad.max_spp = (uint32_t)std::atoi(argv[++i]);
         else if (a == "--mesh" && i + 1 < argc) mesh_path = argv[++i];          // Wavefront OBJ, PLY or pbrt-v3 trianglemeshes
         else if (a == "--hdr" && i + 1 < argc) hdr_path = argv[++i];            // Radiance .hdr backdrop (the reference's texHDR)
         else if (a == "--albedo-map" && i + 1 < argc) albedo_path = argv[++i];  // PNG image texture on the mesh material
@@ -124,6 +137,8 @@ int main(int argc, char** argv) {
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (adaptive && !integ_given) integ_name = "mis";
+    if (adaptive && !spp_given) spp = 16;
     int kind = scene_name == "cornell" ? TRC_SCENE_CORNELL : scene_name == "volume" ? TRC_SCENE_CORNELL_VOLUME : TRC_SCENE_CORNELL_SPHERES;
     if (!mesh_path.empty() && kind != TRC_SCENE_CORNELL_VOLUME) kind = TRC_SCENE_CORNELL_MESH;   // the mesh slot of AAPLRenderer.mm:474-603
     const uint32_t integrator = integ_name == "mis" ? TRC_INTEGRATOR_MIS : integ_name == "volume" ? TRC_INTEGRATOR_VOLUME : TRC_INTEGRATOR_PATH;
@@ -263,7 +278,9 @@ int main(int argc, char** argv) {
     if (mesh_lights) prm.flags |= TRC_FLAG_MESH_LIGHTS;   // the mesh's emissive triangles as area-sampled lights of traceMIS
     if (env_light) prm.flags |= TRC_FLAG_ENV_LIGHT;  // the --hdr map as an importance-sampled light of traceMIS
     const auto t0 = std::chrono::steady_clock::now();
-    CHECK(trc_render(ctx, &prm));
+    trc_adaptive_report report{};
+    if (adaptive) CHECK(trc_render_adaptive(ctx, &prm, &ad, &report));
+    else CHECK(trc_render(ctx, &prm));
     CHECK(trc_synchronize(ctx));
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     trc_stats st;
@@ -309,6 +326,31 @@ int main(int argc, char** argv) {
                 scene_name.c_str(), W, H, spp, integ_name.c_str(), (unsigned long long)st.rays, st.kernel_ms, wall_ms,
                 st.rays / st.kernel_ms / 1e3, exposure, out.c_str());
     if (denoise) std::printf("frame 0%s\n", history_note.c_str());
+    if (adaptive) {
+        // the report, and every pixel's tile count as a grey value over the frame (rows top-down, as the frame's)
+        const uint32_t tw = (W + TRC_TILE - 1) / TRC_TILE, th = (H + TRC_TILE - 1) / TRC_TILE;
+        std::vector<uint32_t> n_t((size_t)tw * th);
+        std::vector<float> e_t((size_t)tw * th);
+        CHECK(trc_download_tile_samples(ctx, n_t.data()));
+        CHECK(trc_download_tile_error(ctx, e_t.data()));
+        std::vector<uint8_t> grey((size_t)W * H * 4);
+        for (uint32_t y = 0; y < H; ++y)
+            for (uint32_t x = 0; x < W; ++x) {
+                const uint32_t n = n_t[(size_t)((H - 1 - y) / TRC_TILE) * tw + x / TRC_TILE];
+                uint8_t* px = &grey[((size_t)y * W + x) * 4];
+                px[0] = px[1] = px[2] = (uint8_t)((255ull * n + ad.max_spp / 2) / ad.max_spp);
+                px[3] = 255;
+            }
+        const std::string name = out + ".samples.png";
+        if (trc_host_write_png(name.c_str(), grey.data(), W, H) != TRC_OK) { std::fprintf(stderr, "cannot write %s\n", name.c_str()); return 1; }
+        std::vector<float> sorted = e_t;
+        std::sort(sorted.begin(), sorted.end());
+        std::printf("adaptive: threshold %g, first pass %u, max %u spp: %u passes, %llu samples (%.1f per pixel, %.1f %% of %u spp everywhere), "
+                    "%u of %zu tiles still active, error median %g max %g -> %s\n",
+                    ad.threshold, spp, ad.max_spp, report.passes, (unsigned long long)report.samples, (double)report.samples / ((double)W * H),
+                    100.0 * (double)report.samples / ((double)W * H * ad.max_spp), ad.max_spp, report.active_tiles, n_t.size(), sorted[sorted.size() / 2],
+                    report.max_error, name.c_str());
+    }
     // --rebuild-ratio: the cost right after the last build is the yardstick; called after every animation call
     uint32_t rebuilds = 0, cost_reads = 0;
     double built_cost = 0.0;

@@ -72,7 +72,11 @@ extern "C" {
  *     SAH builds on the host and on the device; opt-in, nothing defaults to it; additions only, nothing existing changed)
  *     added under 13, the number stays: trc_triangle_range, trc_set_triangle_visibility, trc_download_triangle_visibility,
  *     trc_debug_visibility_ms (mesh triangles shown and hidden on the device: a tree over the visible leaves from what the device holds;
- *     additions only, nothing existing changed) */
+ *     additions only, nothing existing changed)
+ *     added under 13, the number stays: trc_set_tile_mask, trc_download_tile_mask, trc_tile_snapshot, trc_tile_error, trc_download_tile_error,
+ *     trc_adaptive_params, trc_adaptive_report, trc_adaptive_default_params, trc_render_adaptive, trc_download_tile_samples, knob
+ *     mask_forgets_costs (trc_render over a subset of the frame's tiles, a per-tile error estimate and a driver that stops sampling the
+ *     tiles that have settled; with no mask set and no adaptive call made nothing changes; additions only) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -1138,6 +1142,91 @@ trc_status trc_download_motion(trc_ctx* ctx, trc_motion_texel* out /* W*H */);
 /* The history length n of step 2 as the last trc_denoise left it, one float per pixel (1 on a miss): what a host watches to see whether
  * the history survives its animation.  Tracking on or off.  TRC_ERR_NO_FRAME before a trc_denoise, TRC_ERR_INVALID_ARG on a NULL argument. */
 trc_status trc_download_history_length(trc_ctx* ctx, float* n /* W*H */);
+/* ------------------------------------------------------------------ */
+/* Tile mask, per-tile error estimate, adaptive sampling (tracer_amd/csrc/trc_adaptive.hip) */
+/* ------------------------------------------------------------------ */
+/* Tiles are the TRC_TILE x TRC_TILE pixel tiles of the frame, row-major from pixel row 0: tile t = (y / TRC_TILE) * ceil(W / TRC_TILE) +
+ * x / TRC_TILE holds pixel (x, y) of the accumulator; there are ceil(W / TRC_TILE) * ceil(H / TRC_TILE) of them, the last column and row
+ * partial when W or H is no multiple of TRC_TILE.
+ *
+ * trc_set_tile_mask: one byte per tile.  With a mask set, trc_render renders the pixel blocks of the tiles that are owned (tile_rank /
+ * tile_nranks, as without a mask) AND have a non-zero byte; the accumulator and RNG texels of every other pixel are neither read nor written.
+ * A pixel's samples are one chain through its own RNG texel and the running mean takes its weight from frame0 + s, so the pixels that ARE
+ * rendered get exactly the bits of a launch over the whole frame; trc_stats counts the paths and rays of the rendered pixels.  The mask holds
+ * for every launch shape (8x8 and 4x4 blocks, strips, persistent workgroups, the dense kernel, stacked views, TRC_FLAG_COLLECT_STATS).  A mask
+ * with no tile set is legal: trc_render then launches nothing.  mask == NULL: every tile again (n_tiles is ignored).  trc_resize drops the
+ * mask.  trc_sppm_* ignore it.  TRC_ERR_INVALID_ARG: n_tiles is not the frame's tile count; TRC_ERR_NO_FRAME before trc_resize;
+ * TRC_ERR_UNSUPPORTED on a context in a group (trc_group_init / trc_group_set_collectives): a composed frame needs every rank's whole
+ * share.  A refused call changes nothing.
+ * Block costs: a mask that only clears tiles of the mask before it keeps what the context knows about the surviving blocks (each block's cost
+ * as one block; the split plan starts over), so the next launch is ordered by them and runs as one pass; a mask that sets a tile again starts
+ * a new block list, whose first launch measures afresh (trc_render's head).  Knob "mask_forgets_costs": every mask change does.  Pixels depend
+ * on neither.
+ * trc_download_tile_mask: the mask in force, 1 / 0 per tile (all 1 without a mask). */
+trc_status trc_set_tile_mask(trc_ctx* ctx, const uint8_t* mask, uint32_t n_tiles);
+trc_status trc_download_tile_mask(trc_ctx* ctx, uint8_t* out /* n tiles */);
+
+/* Per-tile error estimate, after Dammertz, Hanika, Keller, Lensch: "A hierarchical automatic stopping condition for Monte Carlo global
+ * illumination" (WSCG 2010).  The paper compares the image I of all samples with the image A of every second sample; here A is the
+ * accumulator as it was after the FIRST half of every pixel's chain (trc_tile_snapshot) and I the accumulator now.  With A taken at half the
+ * samples and B the mean of the second half, I = (A + B) / 2 and |I - A| = |B - A| / 2, as there.  There is no area factor.
+ *
+ * Per in-bounds pixel of tile t (N_t of them: 256, fewer in a partial tile), every operation in binary32, rounded to nearest, no contraction,
+ * division and square root correctly rounded:
+ *     d   = (|I.r - A.r| + |I.g - A.g|) + |I.b - A.b|
+ *     s   = (I.r + I.g) + I.b;    s' = s > TRC_ADAPTIVE_EPS ? s : TRC_ADAPTIVE_EPS        (a NaN s takes the eps)
+ *     e   = d / sqrt(s');         e' = e < 65535 ? e : 65535                              (a NaN or infinite e takes the cap)
+ *     q   = (uint32_t)(e' * 65536)                                                        (truncation; e' * 65536 < 2^32)
+ *     E_t = (float)((double)(sum of q over the tile's pixels, as uint64_t) / ((double)N_t * 65536.0))
+ * The sum is one of integers, so E_t does not depend on the order of summation (trc_tonemap's mean is made the same way).
+ * libtracer_amd_fast.so computes the same steps under its own rules for division, square root and denormals.
+ *
+ * trc_tile_snapshot: A := the accumulator, the whole plane (16 B per pixel, allocated by the first call, freed by trc_resize).
+ * trc_tile_error: E_t of every tile of the mask in force (every tile without one) from I = the accumulator as it stands and A; the other
+ * tiles keep the E_t they had (0 until a tile's first estimate).  snapshot_after != 0: A := I for the pixels of those tiles in the same pass
+ * over the planes, ready for the next round.  TRC_ERR_NO_FRAME before trc_resize or before the first trc_tile_snapshot.
+ * trc_download_tile_error: E_t of every tile.  All three: TRC_ERR_UNSUPPORTED on a context in a group. */
+#define TRC_ADAPTIVE_EPS 1e-4f
+trc_status trc_tile_snapshot(trc_ctx* ctx);
+trc_status trc_tile_error(trc_ctx* ctx, int snapshot_after);
+trc_status trc_download_tile_error(trc_ctx* ctx, float* e /* n tiles */);
+
+/* trc_render_adaptive: a picture from sample 0 that stops sampling the tiles whose estimate has fallen to `threshold`.
+ *   p->spp = h0, at least 8: the first pass, over every tile.  p->frame0 must be 0 (the call starts a picture; continuing one is not supported).
+ *   a->max_spp >= 2 * h0: no pixel gets more samples.  a->threshold: finite and > 0.  a->reserved: 0.
+ * The loop, with n the samples every active tile has and the mask M = every tile (whatever mask the host has set; that one is back in force
+ * when the call returns, also when it fails):
+ *   1. one pass of h0 samples, frame0 = 0; A := accumulator; n = h0
+ *   2. one pass of m = min(n, max_spp - n) samples, frame0 = n, over the tiles of M; n += m          (n doubles; the last pass lands on max_spp)
+ *   3. trc_tile_error(snapshot_after = 1) over M
+ *   4. every tile of M with E_t <= threshold leaves M for good; n_t = n for every tile that was in M at step 2
+ *   5. back to 2 unless n == max_spp or M is empty
+ * Every pass is an ordinary trc_render pass of the production kernels (never kept for coalescing), so a tile's pixels hold exactly the bits
+ * of a plain trc_render of n_t samples.  The check is made after the last pass too: E_t, active_tiles and max_error describe the picture as
+ * returned.  TRC_ERR_INVALID_ARG: a NULL argument, frame0 != 0, spp < 8, max_spp < 2 * spp, a threshold that is not finite or not > 0;
+ * TRC_ERR_UNSUPPORTED on a context in a group; otherwise what trc_render returns (no scene, no frame, no camera ...).  A refused call
+ * leaves accumulator, RNG and mask as they were.
+ * KNOWN LIMIT.  Stopping is permanent and decided from the samples themselves, so the result is slightly biased, as in the paper.  A tile
+ * whose samples so far are all black has E_t = 0 and stops at the first check: under tracePath, whose paths find the light by chance, small
+ * frames have such tiles at n = 16, and fireflies make its estimate GROW from n = 16 to 64, where traceMIS's falls.  Choose a first pass
+ * long enough for the integrator (traceMIS: 8 to 16; tracePath: 64 or more), and prefer traceMIS.
+ * trc_adaptive_default_params: max_spp = 256, threshold = TRC_ADAPTIVE_DEFAULT_THRESHOLD. */
+typedef struct trc_adaptive_params { float threshold; uint32_t max_spp; uint32_t reserved[2]; } trc_adaptive_params;
+typedef struct trc_adaptive_report {
+    uint32_t passes;          /* render passes: 1 + the rounds of steps 2 .. 4 */
+    uint32_t active_tiles;    /* tiles still in M after the last check */
+    uint64_t samples;         /* sum over tiles of N_t * n_t: what trc_stats.paths grew by */
+    float    max_error;       /* the largest E_t of the frame after the last check */
+    uint32_t _pad;
+} trc_adaptive_report;
+/* the median E_t of BASELINE config 2 (Cornell box + 12 spheres) under traceMIS at 1920 x 1080, n = 64 with A at 32, as tools/adaptive_bench.py
+ * measures it (profiles/r28/adaptive_sampling.txt, step 0: 0.05253): half of that frame's tiles have settled by then */
+#define TRC_ADAPTIVE_DEFAULT_THRESHOLD 0.0525f
+void       trc_adaptive_default_params(trc_adaptive_params* out);
+trc_status trc_render_adaptive(trc_ctx* ctx, const trc_params* p, const trc_adaptive_params* a, trc_adaptive_report* out /* may be NULL */);
+/* n_t of the last trc_render_adaptive, one per tile (TRC_ERR_NO_FRAME before one) */
+trc_status trc_download_tile_samples(trc_ctx* ctx, uint32_t* n /* n tiles */);
+
 /* developer diagnostic: the pixel blocks of the last trc_render (x | y << 16, in units of the block edge 1 << *blk_shift)
  * and the duration each one's wavefront measured per sample (shader clocks / (4 spp) -- the sort key of the adaptive launch order); with
  * strips (spp < 8) the costs are per strip; a block that ran in parts (four 4x4 quarters, some of them as four 2x2
@@ -1297,7 +1386,7 @@ trc_status trc_group_set_collectives(trc_ctx* ctx, const trc_collectives* table,
  * the render loop shades replayed hits alone where at least n lanes of the wavefront hold one, at most m such trips between two walks; 0 = the
  * defaults, 1 and 1; 65 lanes = never), "strip_force" (tests only: n > 0 gives every wavefront a strip of exactly n blocks, at any spp and whatever
  * the size of the frame -- "strip_len" asks for a length and is capped so that the GPU keeps 1.5 workgroups per wavefront slot, which on a
- * frame of a few blocks always leaves 1), "refit_single" (trc_update_vertices, trc_update_primitives), "skin_no_lds" (trc_skin_vertices).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
+ * frame of a few blocks always leaves 1), "refit_single" (trc_update_vertices, trc_update_primitives), "skin_no_lds" (trc_skin_vertices), "mask_forgets_costs" (trc_set_tile_mask).  They change scheduling / bookkeeping only, never a pixel.  Unknown name: TRC_ERR_INVALID_ARG. */
 trc_status trc_debug_set(trc_ctx* ctx, const char* knob, int value);
 
 /* ------------------------------------------------------------------ */
@@ -1553,5 +1642,8 @@ TRC_SA(sizeof(trc_gbuffer_texel) == 32 && offsetof(trc_gbuffer_texel, normal) ==
        offsetof(trc_gbuffer_texel, id) == 28, "gbuffer texel");
 TRC_SA(sizeof(trc_denoise_params) == 32, "trc_denoise_params");
 TRC_SA(sizeof(trc_motion_texel) == 16, "trc_motion_texel");
+TRC_SA(sizeof(trc_adaptive_params) == 16 && offsetof(trc_adaptive_params, max_spp) == 4 && offsetof(trc_adaptive_params, reserved) == 8, "trc_adaptive_params");
+TRC_SA(sizeof(trc_adaptive_report) == 24 && offsetof(trc_adaptive_report, active_tiles) == 4 && offsetof(trc_adaptive_report, samples) == 8 &&
+       offsetof(trc_adaptive_report, max_error) == 16, "trc_adaptive_report");
 
 #endif /* TRACER_ABI_H */

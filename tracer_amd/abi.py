@@ -276,6 +276,22 @@ class Residency(C.Structure):
                 ("lds_static_bytes", C.c_uint32), ("per_cu_block1280", C.c_uint32), ("dense_memo_rows", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AdaptiveParams(C.Structure):
+    """trc_adaptive_params"""
+    _fields_ = [("threshold", C.c_float), ("max_spp", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class AdaptiveReport(C.Structure):
+    """trc_adaptive_report"""
+    _fields_ = [("passes", C.c_uint32), ("active_tiles", C.c_uint32), ("samples", C.c_uint64), ("max_error", C.c_float), ("_pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
+ADAPTIVE_EPS = 1e-4                 # TRC_ADAPTIVE_EPS (as binary32)
+
+
 KERNEL_SHAPES = ("one", "strip", "pwg", "dense")                                                  # trc_kernel_choice.shape
 KERNEL_VARIANTS = ("plain", "stats", "sobol", "tex", "env", "env_tex", "mesh", "mesh_tex")         # ... .variant (RenderVariant)
 
@@ -299,7 +315,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32, TriangleRange: 12,
+                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32, TriangleRange: 12, AdaptiveParams: 16, AdaptiveReport: 24,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -320,6 +336,8 @@ DEVICE_SYMBOLS = [
     "trc_morph_bind", "trc_morph_vertices", "trc_recompute_normals",
     "trc_rebuild_tree", "trc_tree_cost", "trc_update_primitives",
     "trc_set_triangle_visibility", "trc_download_triangle_visibility", "trc_debug_visibility_ms",
+    "trc_set_tile_mask", "trc_download_tile_mask", "trc_tile_snapshot", "trc_tile_error", "trc_download_tile_error",
+    "trc_adaptive_default_params", "trc_render_adaptive", "trc_download_tile_samples",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",

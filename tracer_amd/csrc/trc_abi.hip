@@ -429,6 +429,7 @@ void trc_release_frame(trc_ctx* ctx) {
     ctx->busy = ctx->busy_alt = false;
     trc_sppm_release(ctx);          // per-pixel camera records depend on the frame size
     trc_denoise_release(ctx);       // ... and so do the denoiser's planes
+    trc_adaptive_release(ctx);      // ... the tile mask, the snapshot and the per-tile estimate
     trc_release_tiles(ctx);
     ctx->n_tiles = 0;
     ctx->width = ctx->height = 0;
@@ -477,6 +478,7 @@ static const KnobEntry kKnobs[] = {
     {"refit_single", &trc_ctx::Knobs::refit_single, nullptr, false},
     {"skin_no_lds", &trc_ctx::Knobs::skin_no_lds, nullptr, false},
     {"strip_force", &trc_ctx::Knobs::strip_force, nullptr, false},
+    {"mask_forgets_costs", &trc_ctx::Knobs::mask_forgets_costs, nullptr, false},
 };
 
 // ======================================================================= C ABI

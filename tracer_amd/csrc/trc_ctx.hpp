@@ -272,6 +272,21 @@ struct trc_ctx {
     const uint32_t* d_last_order = nullptr; uint32_t order_age = 0;     // most recent sorted order (short launches reuse it)
     int cu_count = 0;
     uint32_t n_tiles = 0, tiles_nranks = 0, tiles_rank = 0, tiles_view_height = 0, tiles_blk_shift = 3;
+    // trc_set_tile_mask / trc_render_adaptive (trc_adaptive.hip): the TRC_TILE x TRC_TILE tiles of the frame that trc_render's block list
+    // keeps, one byte per tile, row-major (empty: every tile).  mask_gen names the mask in the block list's cache key (0: no mask; every
+    // trc_set_tile_mask takes the next number), tiles_mask_gen is the list's.  d_mask mirrors tile_mask on the device once a kernel needs it
+    // (all ones without a mask; mask_on_device: it holds the current one).  Everything here is sized by the frame: trc_release_frame
+    struct Adaptive {
+        std::vector<uint8_t> tile_mask;
+        uint64_t mask_gen = 0, next_gen = 0;
+        uint64_t shrinks_from = ~0ull;      // the mask_gen (0: no mask) whose tiles this mask is a subset of: trc_ensure_tiles may carry that list's costs over
+        uint8_t* d_mask = nullptr; bool mask_on_device = false;
+        float* d_snapshot = nullptr;        // A of trc_tile_snapshot: the accumulator plane as it was (16 B per pixel, made at first use)
+        float* d_error = nullptr;           // E_t of trc_tile_error (zero until a tile's first estimate)
+        uint32_t* d_samples = nullptr; bool has_samples = false;      // n_t of the last trc_render_adaptive (k_tile_decide)
+        uint32_t* d_decide = nullptr;       // k_tile_decide's two words: tiles still active, the largest E_t's bits
+    } adaptive;
+    uint64_t tiles_mask_gen = 0;
 
     // stats
     unsigned long long* d_stats = nullptr;       // kStatRows rows of kStatRowStride counters (stat_row)
@@ -344,6 +359,7 @@ struct trc_ctx {
         int refit_single = 0;           // trc_update_vertices: refit in a single launch (trc_refit.hip)
         int skin_no_lds = 0;            // trc_skin_vertices: the bones gathered from memory whatever the palette's size (trc_deform.hip)
         int strip_force = 0;            // tests: exactly this many blocks per wavefront (launch_geometry)
+        int mask_forgets_costs = 0;     // a tile mask that only clears tiles forgets the block costs like any new list (trc_ensure_tiles)
     } knobs;
     // render kernels that were granted > 64 KB of dynamic LDS on THIS context's device (trc_render_pass.hip: launch_render):
     // hipFuncSetAttribute applies to the current device only, so the grant is per context, not per process
@@ -476,7 +492,15 @@ struct trc_read_item { void* host; const void* dev; size_t bytes; };
 trc_status trc_read_to_host(trc_ctx* ctx, hipStream_t st, const char* what, std::initializer_list<trc_read_item> items);
 
 // tiles owned by `rank` of `nranks` (XCD-aware order) uploaded into ctx->d_tiles; shared by render and SPPM
-trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_t view_height = 0, uint32_t blk_shift = 3);
+// `masked`: of those, the blocks of tiles that trc_set_tile_mask kept (trc_render); SPPM's list is keyed without the mask
+trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_t view_height = 0, uint32_t blk_shift = 3, bool masked = false);
+// trc_render_pass.hip: one pass of trc_render, launched at once (never kept for coalescing): the passes of trc_render_adaptive
+trc_status trc_render_now(trc_ctx* ctx, const trc_params* p);
+// trc_adaptive.hip: the tile mask (null: every tile) becomes the context's; frees what trc_set_tile_mask and the estimate own (trc_release_frame)
+trc_status trc_adopt_tile_mask(trc_ctx* ctx, const uint8_t* mask, bool on_device = false);      // `mask`: trc_tile_count bytes; on_device: d_mask already holds it
+void trc_adaptive_release(trc_ctx* ctx);
+inline uint32_t trc_tiles_x(const trc_ctx* ctx) { return (ctx->width + TRC_TILE - 1) / TRC_TILE; }
+inline uint32_t trc_tile_count(const trc_ctx* ctx) { return trc_tiles_x(ctx) * ((ctx->height + TRC_TILE - 1) / TRC_TILE); }
 size_t trc_dyn_lds_bytes(const trc_ctx* ctx, bool stats);
 // trc_lbvh.hip: stable radix sort of (key, value) pairs on the 24 low key bits, three of the tree builds' 8-bit passes; *result: the buffer that holds it
 void trc_sort_pairs24(hipStream_t st, uint32_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t* digit_base, uint32_t n, int* result);

@@ -260,6 +260,7 @@ trc_status trc_flush(trc_ctx* ctx) {
     }
     return st;
 }
+trc_status trc_render_now(trc_ctx* ctx, const trc_params* p) { return render_pass(ctx, p, false); }
 extern "C" {
 trc_status trc_render(trc_ctx* ctx, const trc_params* p) {
     TRC_TRY(render_check(ctx, p));
@@ -312,11 +313,11 @@ static void launch_params(const trc_ctx* ctx, const trc_params* p, KRender& kp) 
 static trc_status launch_geometry(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
     const uint32_t nranks = p->tile_nranks ? p->tile_nranks : 1;
     uint32_t blk_shift = 3;
-    r.blocks8 = (uint64_t)((ctx->width + 7) / 8) * ((ctx->height + 7) / 8) / nranks;
     r.fits = ctx->width <= 65535u * 4u && ctx->height <= 65535u * 4u;
     if ((p->flags & TRC_FLAG_SMALL_BLOCKS) && r.fits) blk_shift = 2;
     if (ctx->knobs.force_blk_shift > 0) blk_shift = std::min(3u, (uint32_t)ctx->knobs.force_blk_shift - 1u);   // measurement knob: 2^k x 2^k pixel blocks
-    TRC_TRY(trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift));
+    TRC_TRY(trc_ensure_tiles(ctx, nranks, p->tile_rank, p->view_height, blk_shift, true));
+    r.blocks8 = blk_shift == 3 ? ctx->n_tiles : ctx->n_tiles >> (2u * (3u - blk_shift));      // of the list as it is: a tile mask may have shortened it
     KRender& kp = r.kp;
     kp.tiles = ctx->d_tiles;
     kp.blk_shift = blk_shift;

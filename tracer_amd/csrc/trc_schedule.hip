@@ -304,6 +304,56 @@ __global__ void __launch_bounds__(256) k_build_launch_all_quarters(uint32_t n, u
     whole[i] = 0u;            // never measured as one block: k_order_keys estimates it from the slowest quarter
 }
 
+// A tile mask that only clears tiles (trc_set_tile_mask, trc_render_adaptive): the new block list is the old one without the blocks of the
+// cleared tiles, in the same order, so what is known about the surviving blocks moves from old list index i to new index j = the kept
+// blocks before i.  One workgroup: thread t owns old indices [t * per, (t + 1) * per).  (1) every block's cost as ONE block -- k_order_keys'
+// `c`, taken from the raw durations and from the filtered costs alike -- into `tmp` (2 n words: the sort's key buffers, idle between launches),
+// and the kept flags counted; (2) the exclusive prefix sum of the counts; (3) slot 0 of the new index takes the cost, the split state of the
+// whole list is zeroed (every block whole: the other slots are written before they are read again, k_build_launch).  Reads of step 1 and
+// writes of step 3 are a barrier apart, so the arrays are compacted in place.
+__global__ void __launch_bounds__(1024) k_compact_costs(const uint32_t* tiles, const uint8_t* mask, uint32_t tiles_x, uint32_t blk_shift, uint32_t n,
+                                                        uint32_t stride, uint32_t* raw, uint32_t* est, uint32_t* split, uint32_t* whole, uint32_t* qsplit,
+                                                        uint32_t* tmp_raw, uint32_t* tmp_est) {
+    __shared__ uint32_t s_wave[16];
+    const uint32_t t = threadIdx.x, per = (n + 1023u) / 1024u;
+    const uint32_t lo = min(n, t * per), hi = min(n, lo + per);
+    auto kept = [&](uint32_t i) {
+        const uint32_t b = tiles[i], tx = ((b & 0xFFFFu) << blk_shift) / TRC_TILE, ty = ((b >> 16) << blk_shift) / TRC_TILE;
+        return mask[(size_t)ty * tiles_x + tx] != 0;
+    };
+    auto as_one = [&](const uint32_t* cost, uint32_t i) {
+        uint32_t c = cost[(size_t)i * stride];
+        if (stride == kCostSlots && split[i])
+            c = whole[i] ? whole[i] : (uint32_t)((float)slowest_part(cost, qsplit, i) * (1.0f / kQuarterEstimate));
+        return c;
+    };
+    uint32_t count = 0u;
+    for (uint32_t i = lo; i < hi; ++i) {
+        tmp_raw[i] = as_one(raw, i); tmp_est[i] = as_one(est, i);
+        if (kept(i)) count++;
+    }
+    // exclusive prefix sum of `count` over the workgroup
+    const uint32_t lane = t & 63u, wave = t >> 6;
+    uint32_t inc = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(inc, off, 64); if ((int)lane >= off) inc += o; }
+    if (lane == 63u) s_wave[wave] = inc;
+    __syncthreads();                       // ... and every read of step 1 is done
+    uint32_t j = inc - count;
+    for (uint32_t w = 0; w < wave; ++w) j += s_wave[w];
+    for (uint32_t i = lo; i < hi; ++i) {
+        if (!kept(i)) continue;
+        raw[(size_t)j * stride] = tmp_raw[i]; est[(size_t)j * stride] = tmp_est[i];
+        ++j;
+    }
+    if (stride == kCostSlots)
+        for (uint32_t i = lo; i < hi; ++i) {
+            split[i] = 0u; whole[i] = 0u;
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q) qsplit[4u * i + q] = 0u;
+        }
+}
+
 namespace {
 
 constexpr bool kAutoSmallBlocks = true;       // decided by measurement (tools/small_blocks_bench.py, tile_balance.py); DESIGN.md section 5
@@ -313,15 +363,19 @@ constexpr bool kAutoSmallBlocks = true;       // decided by measurement (tools/s
 // every XCD receives the same mix.  Measured: handing each XCD a contiguous band of the image instead (the
 // "L2-friendly" order) costs 22 % on the Cornell scene and 44 % on the 1 M-triangle scene, because the XCD whose
 // band holds the glass / mesh pixels finishes long after the others; 8x8-tile blocks per XCD sit in between.
-std::vector<uint32_t> make_tiles(uint32_t W, uint32_t H, uint32_t nranks, uint32_t rank, uint32_t view_height, uint32_t blk_shift) {
+// `mask` (trc_set_tile_mask; null: every tile): one byte per tile of the frame, row-major; of the owned blocks those of tiles with a non-zero
+// byte stay, in the order they have in the unmasked list
+std::vector<uint32_t> make_tiles(uint32_t W, uint32_t H, uint32_t nranks, uint32_t rank, uint32_t view_height, uint32_t blk_shift, const uint8_t* mask) {
     // ownership is decided per TRC_TILE x TRC_TILE tile; the launch unit is the pixel block of one wavefront:
     // 8x8 (blk_shift 3) or, for launches with too few blocks to fill the GPU, 4x4 on 16 lanes (blk_shift 2)
     const uint32_t e = 1u << blk_shift;
     const uint32_t bw = (W + e - 1) / e, bh = (H + e - 1) / e;
+    const uint32_t tiles_x = (W + TRC_TILE - 1) / TRC_TILE;
     std::vector<uint32_t> mine;
     for (uint32_t by = 0; by < bh; ++by)
         for (uint32_t bx = 0; bx < bw; ++bx)
-            if ((bx * e / TRC_TILE + by * e / TRC_TILE) % nranks == rank) mine.push_back(bx | (by << 16));
+            if ((bx * e / TRC_TILE + by * e / TRC_TILE) % nranks == rank && (!mask || mask[(size_t)(by * e / TRC_TILE) * tiles_x + bx * e / TRC_TILE]))
+                mine.push_back(bx | (by << 16));
     if (view_height != 0 && view_height < H) {
         // stacked views: walk the rows of ALL views together (row within the view first), so the launch ends on the
         // last rows of every view like a single-view launch does.  View after view, the expensive blocks of the final
@@ -355,11 +409,36 @@ void trc_release_tiles(trc_ctx* ctx) {
     (void)hipFree(ctx->d_cost_scratch); ctx->d_cost_scratch = nullptr;
 }
 
-trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_t view_height, uint32_t blk_shift) {
+trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_t view_height, uint32_t blk_shift, bool masked) {
+    trc_ctx::Adaptive& ad = ctx->adaptive;
+    const uint64_t mask_gen = masked ? ad.mask_gen : 0u;
     if (ctx->d_tiles && ctx->d_block_cost && ctx->tiles_nranks == nranks && ctx->tiles_rank == rank &&
-        ctx->tiles_view_height == view_height && ctx->tiles_blk_shift == blk_shift) return TRC_OK;
-    std::vector<uint32_t> tiles = make_tiles(ctx->width, ctx->height, nranks, rank, view_height, blk_shift);
+        ctx->tiles_view_height == view_height && ctx->tiles_blk_shift == blk_shift && ctx->tiles_mask_gen == mask_gen) return TRC_OK;
+    const uint8_t* mask = mask_gen ? ad.tile_mask.data() : nullptr;
+    std::vector<uint32_t> tiles = make_tiles(ctx->width, ctx->height, nranks, rank, view_height, blk_shift, mask);
     if (tiles.size() > (size_t)kLaunchIndexMask) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "frame too large: more pixel blocks than a launch-list entry can name");
+    // The list of a mask that only cleared tiles of the list before it (shrinks_from: trc_adopt_tile_mask compared the two masks): the
+    // allocations stay, they are large enough, and so do the costs of the surviving blocks (k_compact_costs), so the next launch is ordered by
+    // them as one pass -- not a cold head + rest, which a driver that clears tiles every round would pay every round.  Costs per strip
+    // (cost_strip > 1) name no block; knob mask_forgets_costs: every mask change starts a new list as below.
+    if (ctx->d_tiles && ctx->d_block_cost && ctx->tiles_nranks == nranks && ctx->tiles_rank == rank && ctx->tiles_view_height == view_height &&
+        ctx->tiles_blk_shift == blk_shift && mask && ad.shrinks_from == ctx->tiles_mask_gen && !ctx->knobs.mask_forgets_costs && ad.d_mask && ad.mask_on_device) {
+        const bool carry = ctx->cost_valid && ctx->cost_strip == 1 && ctx->n_tiles != 0 && !tiles.empty();
+        if (carry) {
+            hipLaunchKernelGGL(k_compact_costs, dim3(1), dim3(1024), 0, ctx->stream, ctx->d_tiles, ad.d_mask, trc_tiles_x(ctx), blk_shift, ctx->n_tiles,
+                               ctx->cost_quarters ? kCostSlots : 1u, ctx->d_block_cost, ctx->d_cost_est, ctx->d_split, ctx->d_whole, ctx->d_qsplit,
+                               ctx->d_order_keys[0], ctx->d_order_keys[1]);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_plan, 0, kPlanWords * sizeof(uint32_t), ctx->stream));
+            ctx->split_live = false;
+        } else trc_forget_costs(ctx);
+        ctx->plan_streak = 0; ctx->d_last_order = nullptr; ctx->d_stale_order = nullptr;
+        ctx->tiles_nranks = 0;               // (the key is whole again once the list is in place)
+        TRC_TRY(trc_copy_to_device(ctx, ctx->d_tiles, tiles.data(), tiles.size() * 4, ctx->stream));      // behind the kernel, which reads the old list
+        ctx->n_tiles = (uint32_t)tiles.size();
+        ctx->tiles_nranks = nranks; ctx->tiles_mask_gen = mask_gen;
+        return TRC_OK;
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // the cache key (tiles_nranks ...) is written LAST: a failed allocation below leaves the list invalid, so the next
     // call rebuilds it instead of launching with a null block_cost / order buffer
@@ -391,7 +470,7 @@ trc_status trc_ensure_tiles(trc_ctx* ctx, uint32_t nranks, uint32_t rank, uint32
         HIP_TRY(ctx, hipMalloc((void**)&ctx->d_order_hist, (trc_sort_hist_words(ctx->n_tiles) + 256) * 4));
         TRC_TRY(trc_copy_to_device(ctx, ctx->d_tiles, tiles.data(), tiles.size() * 4, ctx->stream));
     }
-    ctx->tiles_nranks = nranks; ctx->tiles_rank = rank; ctx->tiles_view_height = view_height; ctx->tiles_blk_shift = blk_shift;
+    ctx->tiles_nranks = nranks; ctx->tiles_rank = rank; ctx->tiles_view_height = view_height; ctx->tiles_blk_shift = blk_shift; ctx->tiles_mask_gen = mask_gen;
     return TRC_OK;
 }
 

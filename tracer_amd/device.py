@@ -138,6 +138,14 @@ def _load(path, hooks=False):
     L.trc_download_triangle_visibility.argtypes = [vp, vp]
     L.trc_debug_visibility_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.trc_update_primitives.argtypes = [vp, C.POINTER(abi.PrimitiveRanges)]
+    L.trc_set_tile_mask.argtypes = [vp, vp, u32]
+    L.trc_download_tile_mask.argtypes = [vp, vp]
+    L.trc_tile_snapshot.argtypes = [vp]
+    L.trc_tile_error.argtypes = [vp, C.c_int]
+    L.trc_download_tile_error.argtypes = [vp, vp]
+    L.trc_adaptive_default_params.argtypes = [C.POINTER(abi.AdaptiveParams)]
+    L.trc_render_adaptive.argtypes = [vp, C.POINTER(abi.Params), C.POINTER(abi.AdaptiveParams), C.POINTER(abi.AdaptiveReport)]
+    L.trc_download_tile_samples.argtypes = [vp, vp]
     if hooks:
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
@@ -158,10 +166,11 @@ def _load(path, hooks=False):
     for name in abi.DEVICE_SYMBOLS:
         f = getattr(L, name)
         if name not in ("trc_abi_version", "trc_build_flavor", "trc_has_test_hooks", "trc_status_string", "trc_last_error", "trc_destroy", "trc_shard_seed",
-                        "trc_denoise_default_params"):
+                        "trc_denoise_default_params", "trc_adaptive_default_params"):
             f.restype = i32
     L.trc_shard_seed.restype = u64
     L.trc_denoise_default_params.restype = None
+    L.trc_adaptive_default_params.restype = None
     if L.trc_abi_version() != abi.TRC_ABI_VERSION:
         raise RuntimeError("libtracer_amd.so ABI version mismatch")
     return L
@@ -562,6 +571,70 @@ class Tracer:
 
     def synchronize(self):
         self._check(self._L.trc_synchronize(self._h), "trc_synchronize")
+
+    # --- tile mask, per-tile error estimate, adaptive sampling (include/tracer_abi.h) ------------------------------
+    def tile_grid(self):
+        """(tile rows, tile columns) of the frame: TRC_TILE x TRC_TILE tiles, the last row and column partial"""
+        return (self.height + abi.TRC_TILE - 1) // abi.TRC_TILE, (self.width + abi.TRC_TILE - 1) // abi.TRC_TILE
+
+    def set_tile_mask(self, mask, n_tiles=None):
+        """trc_set_tile_mask: one byte per tile, row-major (any shape that ravels to it); render() then covers the owned tiles with a
+        non-zero byte only.  None: every tile again.  n_tiles: what to tell the library instead of the array's length (tests)."""
+        if mask is None:
+            self._check(self._L.trc_set_tile_mask(self._h, None, 0), "trc_set_tile_mask")
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel()
+        buf = m if m.size else np.zeros(1, np.uint8)
+        self._check(self._L.trc_set_tile_mask(self._h, buf.ctypes.data, m.size if n_tiles is None else n_tiles), "trc_set_tile_mask")
+
+    def tile_mask(self):
+        """trc_download_tile_mask -> (tile rows, tile columns) uint8, 1 = rendered"""
+        out = np.zeros(self.tile_grid(), dtype=np.uint8)
+        self._check(self._L.trc_download_tile_mask(self._h, out.ctypes.data), "trc_download_tile_mask")
+        return out
+
+    def tile_snapshot(self):
+        """trc_tile_snapshot: A := the accumulator"""
+        self._check(self._L.trc_tile_snapshot(self._h), "trc_tile_snapshot")
+
+    def tile_error(self, snapshot_after=False):
+        """trc_tile_error: E_t of every tile of the mask from the accumulator and A; snapshot_after: A := accumulator on those tiles"""
+        self._check(self._L.trc_tile_error(self._h, 1 if snapshot_after else 0), "trc_tile_error")
+
+    def tile_errors(self):
+        """trc_download_tile_error -> (tile rows, tile columns) float32"""
+        out = np.zeros(self.tile_grid(), dtype=np.float32)
+        self._check(self._L.trc_download_tile_error(self._h, out.ctypes.data), "trc_download_tile_error")
+        return out
+
+    def adaptive_params(self, **overrides):
+        """trc_adaptive_default_params, then the named fields replaced"""
+        a = abi.AdaptiveParams()
+        self._L.trc_adaptive_default_params(C.byref(a))
+        for k, v in overrides.items():
+            setattr(a, k, v)
+        return a
+
+    def render_adaptive(self, threshold=None, max_spp=None, spp=8, max_depth=8, integrator=abi.INTEGRATOR_MIS, frame0=0, tile_rank=0,
+                        tile_nranks=1, flags=0, view_height=0):
+        """trc_render_adaptive: a first pass of `spp` samples, then passes that double the count on the tiles whose estimate is still
+        above `threshold`, up to max_spp (None: the library's defaults) -> abi.AdaptiveReport"""
+        a = self.adaptive_params()
+        if threshold is not None:
+            a.threshold = threshold
+        if max_spp is not None:
+            a.max_spp = max_spp
+        prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0, tile_rank=tile_rank, tile_nranks=tile_nranks,
+                         flags=flags, view_height=view_height)
+        rep = abi.AdaptiveReport()
+        self._check(self._L.trc_render_adaptive(self._h, C.byref(prm), C.byref(a), C.byref(rep)), "trc_render_adaptive")
+        return rep
+
+    def tile_samples(self):
+        """trc_download_tile_samples -> (tile rows, tile columns) uint32: n_t of the last render_adaptive"""
+        out = np.zeros(self.tile_grid(), dtype=np.uint32)
+        self._check(self._L.trc_download_tile_samples(self._h, out.ctypes.data), "trc_download_tile_samples")
+        return out
 
     def trace_rays(self, rays, any_hit=False, production=False):
         """rays: structured array with the layout of trc_ray -> structured array of trc_hit.
