@@ -101,7 +101,8 @@ def test_estimate_under_a_mask_leaves_the_other_tiles_alone():
         assert np.array_equal(bits(t.tile_errors().ravel()), bits(want))
 
 
-def test_estimate_on_an_uploaded_accumulator_with_nan_inf_negative_and_zero_pixels():
+def uploaded_planes():
+    """(I, A): accumulator and snapshot planes with NaN, inf, negative, zero and sub-eps pixels and two partial tiles"""
     rs = np.random.RandomState(11)
     A = rs.gamma(0.4, 1.5, size=(H, W, 4)).astype(F)
     I = (A * rs.uniform(0.25, 1.75, size=A.shape)).astype(F)
@@ -111,6 +112,11 @@ def test_estimate_on_an_uploaded_accumulator_with_nan_inf_negative_and_zero_pixe
     I[18, 20, :3] = (-1.0, 0.25, 0.5); I[19, 21, :3] = (-3.0, -2.0, -1.0)     # a negative channel, a negative sum
     I[16:32, 32:40, :3] = A[16:32, 32:40, :3]                                # a partial tile that did not move
     I[32:36, 0:16, :3] = 1e-6; A[32:36, 0:16, :3] = 2e-6                     # a partial tile below the eps
+    return I, A
+
+
+def test_estimate_on_an_uploaded_accumulator_with_nan_inf_negative_and_zero_pixels():
+    I, A = uploaded_planes()
     with Tracer(0) as t:
         setup(t)
         t.upload_accum(A); t.tile_snapshot()

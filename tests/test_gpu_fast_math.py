@@ -6,6 +6,7 @@ radiance)."""
 import numpy as np
 import pytest
 
+import fast_ref as fr
 from conftest import camera_rays
 from tracer_amd import abi, device, host
 
@@ -40,23 +41,17 @@ def test_first_hits_are_the_exact_builds(gpu, fast, request, scene_name):
 
 
 def test_frames_agree_like_two_exact_renders(gpu, fast, cornell_spheres):
+    """the criterion is fast_ref.frames_disagree: clipped-luminance RMSE below 1.15 x the seed noise, 8 x 8 block means (far less noisy:
+    they must agree much more tightly than single pixels do) below 1.2 x, mean and ray count within 1 %"""
     W, H, spp = 480, 270, 64
     cam = host.prepare_camera(W, H)
-    lum = lambda f: f[..., 0] * 0.2126 + f[..., 1] * 0.7152 + f[..., 2] * 0.0722
 
     def render(t, seed):
         t.upload_scene(cornell_spheres.view); t.set_camera(cam); t.set_environment((0.0, 0.0, 0.0)); t.resize(W, H)
         t.seed(seed); t.clear_accum(); t.reset_stats(); t.render(spp=spp)
-        return lum(t.download_accum().astype(np.float64)), t.stats().rays
+        return fr.luminance(t.download_accum()), t.stats().rays
     exact_a, rays_a = render(gpu, 11)
     exact_b, _ = render(gpu, 12)
     fast_a, rays_f = render(fast, 11)
-    assert np.isfinite(fast_a).all() and abs(rays_f - rays_a) < 0.01 * rays_a
-    clip = lambda x: np.minimum(x, 4.0)                     # fireflies of single pixels would dominate an RMSE
-    noise = np.sqrt(np.mean((clip(exact_a) - clip(exact_b)) ** 2))
-    diff = np.sqrt(np.mean((clip(fast_a) - clip(exact_a)) ** 2))
-    assert diff < 1.15 * noise, (diff, noise)               # indistinguishable from a re-seeded exact render
-    assert abs(clip(fast_a).mean() - clip(exact_a).mean()) < 0.01 * clip(exact_a).mean()
-    # 8x8-block means are far less noisy: they must agree much more tightly than single pixels do
-    blk = lambda x: clip(x)[: H // 8 * 8, : W // 8 * 8].reshape(H // 8, 8, W // 8, 8).mean(axis=(1, 3))
-    assert np.sqrt(np.mean((blk(fast_a) - blk(exact_a)) ** 2)) < 1.2 * np.sqrt(np.mean((blk(exact_a) - blk(exact_b)) ** 2))
+    fig = fr.frame_figures(fast_a, exact_a, exact_b)
+    assert not fr.frames_disagree(fig, (rays_f, rays_a)), fig              # indistinguishable from a re-seeded exact render
