@@ -34,6 +34,11 @@
 //                          (16 unless given) over every tile, then passes that double the count on the 16 x 16 tiles whose error estimate is still
 //                          above THRESHOLD, up to N (256) samples; prints the report and writes the per-tile sample counts as a grey image
 //                          (255 = N samples) to <out>.samples.png.  Takes traceMIS unless --integrator says otherwise (tracer_abi.h: why)
+//              [--aa N]    anti-aliasing: N camera-ray sets (1 .. 1024) with Halton sub-pixel offsets are generated on the device
+//                          (trc_host_halton_offsets, trc_generate_camera_rays) and the frame is rendered with TRC_FLAG_CAMERA_RAYS: sample s takes
+//                          set s % N.  tracePath / traceMIS; not with --sobol, --env-light or --mesh-lights (tracer_abi.h)
+//              [--projection pinhole|ortho|equirect]  the projection of those sets (one set at zero offset without --aa): the camera's own,
+//                          orthographic through the view plane, or a 360 degree panorama from the eye (world axes, as the --hdr map's)
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -65,6 +70,8 @@ int main(int argc, char** argv) {
     std::string scene_name = "spheres", integ_name = "path", out = "frame.png", mesh_path, density_path, pbrt_path, hdr_path, albedo_path;
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
+    uint32_t aa = 0, ray_model = TRC_RAYS_PINHOLE;
+    bool projection = false;
     std::vector<trc_triangle_range> hidden;
     double rebuild_ratio = 0.0;
     bool adaptive = false, spp_given = false, integ_given = false;
@@ -129,7 +136,18 @@ int main(int argc, char** argv) {
             }
             hidden.push_back(trc_triangle_range{(uint32_t)first, (uint32_t)count, 0u});
         }
-        else if (a == "--normals") normals = true;                              // smooth normals re-derived on the device after every animation call
+        else if (a == "--aa" && i + 1 < argc) {                                 // anti-aliasing: Halton-offset camera-ray sets, TRC_FLAG_CAMERA_RAYS
+            const int n = std::atoi(argv[++i]);
+            if (n <= 0 || n > (int)TRC_MAX_RAY_SETS) { std::fprintf(stderr, "--aa wants a number of ray sets from 1 to %u, not %s\n", TRC_MAX_RAY_SETS, argv[i]); return 2; }
+            aa = (uint32_t)n;
+        }
+        else if (a == "--projection" && i + 1 < argc) {                         // the projection of the camera-ray sets
+            const std::string m = argv[++i];
+            if (m != "pinhole" && m != "ortho" && m != "equirect") { std::fprintf(stderr, "--projection wants pinhole, ortho or equirect, not %s\n", argv[i]); return 2; }
+            ray_model = m == "ortho" ? TRC_RAYS_ORTHOGRAPHIC : m == "equirect" ? TRC_RAYS_EQUIRECT : TRC_RAYS_PINHOLE;
+            projection = true;
+        }
+        else if (a == "--normals") normals = true;                             // smooth normals re-derived on the device after every animation call
         else if (a == "--denoise") denoise = true;                              // SVGF on every frame, the history kept across the animation calls
         else if (a == "--mesh-lights") mesh_lights = true;                     // traceMIS samples the emissive triangles (TRC_FLAG_MESH_LIGHTS)
         else if (a == "--env-light") env_light = true;                          // traceMIS samples the --hdr map as a light (TRC_FLAG_ENV_LIGHT)
@@ -277,6 +295,21 @@ int main(int argc, char** argv) {
     if (sobol) prm.flags |= TRC_FLAG_SOBOL;      // pbrt::SobolSampler instead of the random sampler (Render.metal:529-530)
     if (mesh_lights) prm.flags |= TRC_FLAG_MESH_LIGHTS;   // the mesh's emissive triangles as area-sampled lights of traceMIS
     if (env_light) prm.flags |= TRC_FLAG_ENV_LIGHT;  // the --hdr map as an importance-sampled light of traceMIS
+    if (aa || projection) {                      // camera-ray sets made on the device from the camera; every render below reads them
+        const uint32_t n_sets = aa ? aa : 1u;
+        std::vector<float> offsets(2 * (size_t)n_sets, 0.0f);
+        if (aa) trc_host_halton_offsets(n_sets, offsets.data());
+        trc_ray_gen gen;
+        gen.model = ray_model; gen.n_sets = n_sets; gen.offsets = offsets.data();
+        const auto g0 = std::chrono::steady_clock::now();
+        CHECK(trc_generate_camera_rays(ctx, &gen));
+        CHECK(trc_synchronize(ctx));
+        const double gen_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
+        std::printf("camera rays: %u set%s, %s, %.1f MB on the device, trc_generate_camera_rays %.2f ms\n", n_sets, n_sets == 1 ? "" : "s",
+                    ray_model == TRC_RAYS_ORTHOGRAPHIC ? "orthographic" : ray_model == TRC_RAYS_EQUIRECT ? "equirectangular" : aa ? "pinhole with Halton offsets" : "pinhole",
+                    (double)n_sets * W * H * sizeof(trc_ray) / 1e6, gen_ms);
+        prm.flags |= TRC_FLAG_CAMERA_RAYS;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     trc_adaptive_report report{};
     if (adaptive) CHECK(trc_render_adaptive(ctx, &prm, &ad, &report));

@@ -373,6 +373,30 @@ enum trc_integrator {
      if they cannot be allocated; flag-off renders keep working) and freed by every trc_upload_scene*, by
      trc_upload_triangle_materials and by trc_destroy.  A change of the flag drops the recorded block costs of the launch
      planner. */
+#define TRC_FLAG_CAMERA_RAYS   128u /* a sample's camera ray is read from the context's camera-ray sets ("Camera-ray sets" below:
+                                       trc_upload_camera_rays, trc_generate_camera_rays) instead of being cast by the camera: the way
+                                       to anti-aliasing (sets of sub-pixel offsets) and to other projections (orthographic, 360 degree
+                                       panorama, a host's own lens).  Without the flag nothing changes.
+   - Which ray: with n_sets sets in force, sample s of a call with frame0 takes, for pixel (x, y), the record of set
+     (frame0 + s) % n_sets at (set * H + y) * W + x.  The ray is made as trc_trace_rays makes one: the direction is normalised on
+     entry like Ray::Ray; tmax and _pad are ignored.  Rays are not validated: a non-finite ray misses the scene, as the walk has it.
+   - Everything else of the sample is the unflagged trc_render's: the pixel's RNG texel is read and written the same way; the stream
+     is advanced by castRay's lens draws (the rejection loop of Camera.hh:59-69) exactly as before -- the draws are taken and their
+     ray dropped --, then the same tracePath / traceMIS step by step, the running mean weighted by frame0 + s, the NaN / Inf clamp
+     and the work counters.
+   - So, with the rays the camera itself would cast (a camera of lens radius 0 and no zero component in lookFrom; TRC_RAYS_PINHOLE,
+     one set, no offsets), the frame, the RNG texture and trc_stats.rays / paths / shaded are the unflagged call's, bit for bit.
+   - And k calls of 1 sample equal one call of k samples, so launches of few samples are coalesced as without the flag (the flag
+     is part of what "continues" a kept launch).
+   - Accepted with TRC_INTEGRATOR_PATH and TRC_INTEGRATOR_MIS, with or without active image textures, with or without
+     trc_upload_triangle_materials, on trees staged in LDS or read from memory, with tile_rank / tile_nranks, under a tile mask and in
+     trc_render_adaptive.  TRC_ERR_UNSUPPORTED, nothing rendered: no rays in force; TRC_INTEGRATOR_VOLUME; TRC_FLAG_SOBOL,
+     TRC_FLAG_COLLECT_STATS, TRC_FLAG_ENV_LIGHT or TRC_FLAG_MESH_LIGHTS; a view_height that names a stack (non-zero and below H).
+   - A flagged launch runs kernels of its own, one pixel block per one-wavefront workgroup: no strips, persistent workgroups or
+     dense kernel, and no primary replay.  A change of the flag, or new rays in force, drops the recorded block costs of the
+     launch planner, as a change of the integrator does.
+   - LIMIT: trc_denoise and the SPPM camera pass know nothing of the rays.  Their G-buffer and camera records are the camera's:
+     right for TRC_RAYS_PINHOLE sets, up to the sub-pixel offset, and wrong for any other rays. */
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
                                        N_descend / N_return / leaf-test counters.  Not with an active image texture
                                        (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
@@ -1227,6 +1251,46 @@ trc_status trc_render_adaptive(trc_ctx* ctx, const trc_params* p, const trc_adap
 /* n_t of the last trc_render_adaptive, one per tile (TRC_ERR_NO_FRAME before one) */
 trc_status trc_download_tile_samples(trc_ctx* ctx, uint32_t* n /* n tiles */);
 
+/* ------------------------------------------------------------------ */
+/* Camera-ray sets (TRC_FLAG_CAMERA_RAYS; tracer_amd/csrc/trc_camera_rays.hip, trc_render_rays.hpp) */
+/* ------------------------------------------------------------------ */
+/* A context may hold n_sets >= 1 camera-ray sets, each W x H trc_ray records of 32 bytes (tmax and _pad ignored), set-major, then
+ * row-major like the accumulator: pixel (x, y) of set k is record (k * H + y) * W + x.  66 MB per set at 1920 x 1080.  The sets belong to
+ * the frame size: trc_resize drops them; trc_upload_scene* and trc_set_camera do not (generated rays keep the camera they were made from).
+ * What a render does with them: TRC_FLAG_CAMERA_RAYS above.
+ *
+ * trc_upload_camera_rays: the host's own rays, any lens, any projection: n_sets * W * H records.
+ * trc_generate_camera_rays: built on the device from the context's camera as it stands (include/trc_raygen.h states the arithmetic once, for
+ * the device and for trc_host_generate_camera_rays).  binary32, one rounding per operation in the order written, no contraction, divisions
+ * correctly rounded.  For pixel (x, y) of set k with offset (dx, dy) = offsets[2 k], offsets[2 k + 1] (0, 0 when offsets == NULL):
+ *     s = ((float)x + dx) / (float)W;    t = ((float)y + dy) / (float)H
+ *     P(s, t) = (cornerLowLeft + horizontal * s) + vertical * t                                  per component
+ *   TRC_RAYS_PINHOLE       origin = lookFrom;  direction = P(s, t) - lookFrom   (not normalised).  With zero offsets this is castRay's ray at
+ *                          lens radius 0, because (float)x + 0.0f is (float)x
+ *   TRC_RAYS_ORTHOGRAPHIC  origin = lookFrom + (P(s, t) - P(0.5f, 0.5f));  direction = P(0.5f, 0.5f) - lookFrom
+ *   TRC_RAYS_EQUIRECT      origin = lookFrom;  phi = 6.2831855f * (s - 0.5f), lat = 3.1415927f * (t - 0.5f),
+ *                          direction = (cos lat * cos phi, sin lat, cos lat * sin phi) with dm_sinf / dm_cosf of trc_detmath.h: the
+ *                          parametrisation TRC_FLAG_ENV_LIGHT states for the map -- world axes, the camera's orientation is ignored
+ *   written: tmax = FLT_MAX, _pad = 0.
+ * Offsets are per set, not per pixel.  libtracer_amd_fast.so generates under its own rules (contraction, hardware sine and cosine): its rays
+ * are not bit-equal to the host's; the parity statements here and under TRC_FLAG_CAMERA_RAYS are about the exact build.
+ * trc_download_camera_rays: the W * H records of one set.  trc_clear_camera_rays: no rays in force.
+ *
+ * Errors.  TRC_ERR_NO_FRAME before trc_resize (trc_download_camera_rays: also with no rays in force); TRC_ERR_INVALID_ARG: a NULL argument,
+ * n_sets outside 1 .. TRC_MAX_RAY_SETS, an unknown model, an offset outside [0, 1) or not finite, a set that is not below n_sets,
+ * trc_generate_camera_rays before trc_set_camera.  TRC_ERR_OOM leaves the previous rays in force.  A refused call changes nothing. */
+#define TRC_MAX_RAY_SETS 1024u
+enum trc_ray_model { TRC_RAYS_PINHOLE = 0, TRC_RAYS_ORTHOGRAPHIC = 1, TRC_RAYS_EQUIRECT = 2 };
+typedef struct trc_ray_gen {
+    uint32_t model;          /* enum trc_ray_model */
+    uint32_t n_sets;         /* 1 .. TRC_MAX_RAY_SETS */
+    const float* offsets;    /* 2 * n_sets sub-pixel offsets (dx, dy), each in [0, 1); NULL = all zero */
+} trc_ray_gen;
+trc_status trc_upload_camera_rays(trc_ctx* ctx, const trc_ray* rays, uint32_t n_sets);
+trc_status trc_generate_camera_rays(trc_ctx* ctx, const trc_ray_gen* g);
+trc_status trc_download_camera_rays(trc_ctx* ctx, uint32_t set, trc_ray* out /* W*H */);
+trc_status trc_clear_camera_rays(trc_ctx* ctx);
+
 /* developer diagnostic: the pixel blocks of the last trc_render (x | y << 16, in units of the block edge 1 << *blk_shift)
  * and the duration each one's wavefront measured per sample (shader clocks / (4 spp) -- the sort key of the adaptive launch order); with
  * strips (spp < 8) the costs are per strip; a block that ran in parts (four 4x4 quarters, some of them as four 2x2
@@ -1425,6 +1489,14 @@ void trc_host_prepare_camera(trc_Camera* out, float width, float height);
 
 /* deterministic fillRNG stand-in (see trc_seed) */
 void trc_host_fill_rng(uint64_t seed, uint32_t width, uint32_t height, uint32_t* rgba);
+
+/* The definition of trc_generate_camera_rays ("Camera-ray sets" above): g->n_sets * W * H records, set-major then row-major, bit for bit what
+ * the exact build of the device library makes from the same camera.  Reads lookFrom, horizontal, vertical and cornerLowLeft of the camera.
+ * TRC_ERR_INVALID_ARG as there, and for W == 0 or H == 0. */
+trc_status trc_host_generate_camera_rays(const trc_Camera* camera, uint32_t W, uint32_t H, const trc_ray_gen* g, trc_ray* out);
+/* n sub-pixel offsets for trc_ray_gen.offsets: offset k = (radical inverse base 2, radical inverse base 3) of k + 1, each the exact fraction
+ * rounded once to binary32 (a value that rounds to 1 is stored as the largest float below 1), all in [0, 1) */
+void trc_host_halton_offsets(uint32_t n, float* out /* 2 n */);
 
 /* Scene assembly in the reference's order (AAPLRenderer.mm:213-246,459-468,
  * 513-610): prepareCubeList (materials 0-2), prepareCornellBox (3-6),

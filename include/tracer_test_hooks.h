@@ -88,6 +88,9 @@ typedef struct trc_kernel_choice {
     uint32_t shape, variant, lds_resident, triangle_materials, strip, launches;
 } trc_kernel_choice;
 trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out);
+/* ... and whether that launch ran a kernel of TRC_FLAG_CAMERA_RAYS (tracer_abi.h): *used = 1, else 0.  Such a launch reports shape 0 and
+ * variant 0 or 3 above; its kernels have tables of their own, which trc_kernel_choice does not describe. */
+trc_status trc_debug_last_camera_rays(trc_ctx* ctx, uint32_t* used);
 
 
 /* test hook of the LDS plans (trc_render_pass.hip: resident_workgroups): how the kernel of the last render launch sits on a CU.

@@ -430,6 +430,7 @@ void trc_release_frame(trc_ctx* ctx) {
     trc_sppm_release(ctx);          // per-pixel camera records depend on the frame size
     trc_denoise_release(ctx);       // ... and so do the denoiser's planes
     trc_adaptive_release(ctx);      // ... the tile mask, the snapshot and the per-tile estimate
+    trc_camera_rays_release(ctx);   // ... and the ray sets of TRC_FLAG_CAMERA_RAYS
     trc_release_tiles(ctx);
     ctx->n_tiles = 0;
     ctx->width = ctx->height = 0;

@@ -85,6 +85,13 @@ struct KRenderMesh {
     MeshLight ml;
 };
 
+// ... and the kernels of TRC_FLAG_CAMERA_RAYS (k_render_rays, trc_render_rays.hpp) the ray sets a sample's camera ray is read from
+struct KRenderRays {
+    KRender kp;
+    const trc_ray* rays;                // n_sets sets of W x H records: pixel (x, y) of set k at (k * H + y) * W + x
+    uint32_t n_sets;
+};
+
 struct KTrace {
     KScene ks;
     const trc_ray* rays;
@@ -231,6 +238,10 @@ struct trc_ctx {
     uint32_t width = 0, height = 0;
     uint32_t* d_rng = nullptr;
     float* d_accum = nullptr;
+    // TRC_FLAG_CAMERA_RAYS (trc_camera_rays.hip): n_ray_sets sets of W x H trc_ray records, set-major then row-major (null: no rays in
+    // force).  Sized by the frame: trc_release_frame.  cost_rays: the recorded block costs are a flagged launch's (drop_stale_costs)
+    trc_ray* d_cam_rays = nullptr; uint32_t n_ray_sets = 0;
+    bool cost_rays = false;
 
     // tiles for (nranks, rank)
     uint32_t* d_tiles = nullptr;
@@ -260,7 +271,8 @@ struct trc_ctx {
     // what choose_kernel (trc_render_pass.hip) decided for the last render launch (trc_debug_last_kernel, tracer_test_hooks.h): the
     // launch shape (0 one block per one-wavefront workgroup, 1 strips, 2 persistent workgroups, 3 k_render_dense), the RenderVariant,
     // whether the whole tree was staged in LDS, whether the per-triangle-material twins ran, and the strip length; launches counted
-    struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0; } last_kernel;
+    // camera_rays: it was a kernel of TRC_FLAG_CAMERA_RAYS (trc_debug_last_camera_rays)
+    struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0, camera_rays = 0; } last_kernel;
     // ... and how that launch sits on a CU (trc_debug_last_residency): the kernel, its workgroup size and dynamic LDS, the workgroups per
     // CU its plan is for (4 x the waves of its launch bounds; the persistent workgroups' per-CU count) and the runtime's answer
     struct LastFit { const void* fn = nullptr; uint32_t block = 0, waves = 0, planned_per_cu = 0, per_cu = 0; size_t lds = 0; } last_fit;
@@ -499,6 +511,7 @@ trc_status trc_render_now(trc_ctx* ctx, const trc_params* p);
 // trc_adaptive.hip: the tile mask (null: every tile) becomes the context's; frees what trc_set_tile_mask and the estimate own (trc_release_frame)
 trc_status trc_adopt_tile_mask(trc_ctx* ctx, const uint8_t* mask, bool on_device = false);      // `mask`: trc_tile_count bytes; on_device: d_mask already holds it
 void trc_adaptive_release(trc_ctx* ctx);
+void trc_camera_rays_release(trc_ctx* ctx);      // trc_camera_rays.hip: frees the ray sets of TRC_FLAG_CAMERA_RAYS (trc_release_frame); the block costs of a flagged launch go with them
 inline uint32_t trc_tiles_x(const trc_ctx* ctx) { return (ctx->width + TRC_TILE - 1) / TRC_TILE; }
 inline uint32_t trc_tile_count(const trc_ctx* ctx) { return trc_tiles_x(ctx) * ((ctx->height + TRC_TILE - 1) / TRC_TILE); }
 size_t trc_dyn_lds_bytes(const trc_ctx* ctx, bool stats);

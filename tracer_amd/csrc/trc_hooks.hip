@@ -118,6 +118,13 @@ trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out) {
     out->strip = k.strip; out->launches = k.count;
     return TRC_OK;
 }
+// ... and whether it was a kernel of TRC_FLAG_CAMERA_RAYS (choose_rays_kernel)
+trc_status trc_debug_last_camera_rays(trc_ctx* ctx, uint32_t* used) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx || !used) return TRC_ERR_INVALID_ARG;
+    *used = ctx->last_kernel.camera_rays;
+    return TRC_OK;
+}
 // how the kernel of the last render launch sits on a CU (trc_render_pass.hip: resident_workgroups): the runtime's answer, asked again here,
 // beside the plain arithmetic of trc_lds_fit.hpp for an allocation block of 1280 bytes (320 dwords) -- the runtime's query counts bytes
 trc_status trc_debug_last_residency(trc_ctx* ctx, trc_residency* out) {

@@ -1,0 +1,144 @@
+// trc_render_rays.hpp -- the kernels of TRC_FLAG_CAMERA_RAYS: DEFINITIONS.  render_block's sample loop (trc_render_kernels.hpp) with
+// cast_ray's RESULT replaced by a ray read from the context's ray sets, and nothing else about a sample changed: the pixel's RNG stream
+// still takes cast_ray's lens draws (their ray is dropped), then path_begin, the same path_step / mis_step, the running mean weighted by
+// frame0 + s, the NaN / Inf clamp and the counters.  Beside the kernels of trc_render_kernels.hpp, not inside them: those are tuned to
+// the register and their primary-replay memo lives on the repeated camera ray, which a ray set takes away.  So: one pixel block per
+// one-wavefront workgroup, no parked state, no memo, no Sobol', no statistics.  Included by trc_render_rays.hip / trc_render_rays_mem.hip,
+// which instantiate the kernels through their tables (trc_render_config.hpp: RenderRaysKernels); trc_render_pass.hip launches them.
+#pragma once
+
+#include "trc_render_kernels.hpp"
+
+TRC_RENDER_NS_BEGIN
+
+// One pixel block of a flagged launch: the launch entry is decoded as render_block decodes it (the split plan may hand out quarters,
+// sixteenths and single pixels), RNG texel and accumulator are read and written once, the block's cost is written per sample.
+template <bool LDS, int INTEGRATOR, bool HYB, bool TEX>
+__device__ __forceinline__ void render_rays_block(const KRenderRays& kr, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
+                                                  uint32_t* ovf, const uint32_t slot, const uint32_t lane,
+                                                  uint32_t& n_rays, uint32_t& n_shaded, uint32_t& n_paths, TravCounters& cnt) {
+    const KRender& kp = kr.kp;
+    const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
+    const uint32_t entry = kp.order ? kp.order[slot] : slot;
+    const uint32_t index = entry & kLaunchIndexMask, code = entry >> kLaunchCodeShift;
+    if (index >= kp.n_tiles) return;                            // padding of the launch list's part region (k_pad_launch)
+    const uint32_t tile = kp.tiles[index];                      // pixel block: x | y << 16 in units of the block edge
+    // the launch codes of trc_ctx.hpp, as in render_block: 0 the whole block, 1..4 a quarter, 5..20 a sixteenth, 21..84 one pixel
+    const uint32_t part = code >= 21u ? (code - 21u) >> 2 : (code >= 5u ? code - 5u : 0u);
+    const uint32_t quarter = code >= 5u ? part >> 2 : (code ? code - 1u : 0u);
+    const uint32_t bs = code >= 21u ? 0u : (code >= 5u ? 1u : (code ? 2u : kp.blk_shift));
+    const uint32_t pixel = code >= 21u ? (code - 21u) & 3u : 0u;
+    const uint32_t qx = code ? ((quarter & 1u) << 2) + (code >= 5u ? (part & 1u) << 1 : 0u) + (pixel & 1u) : 0u;
+    const uint32_t qy = code ? ((quarter >> 1) << 2) + (code >= 5u ? ((part >> 1) & 1u) << 1 : 0u) + (pixel >> 1) : 0u;
+    const uint32_t px = ((tile & 0xFFFFu) << kp.blk_shift) + qx + (lane & ((1u << bs) - 1u));
+    const uint32_t py = ((tile >> 16) << kp.blk_shift) + qy + (lane >> bs);
+    const uint32_t W = kp.fr.width, H = kp.fr.height;
+    const bool active = lane < (1u << (2u * bs)) && px < W && py < H;
+    const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
+
+    if (active && kp.spp > 0) {
+        PathCtxOf<TEX, Light::None> cx;
+        fill_path_ctx<false, TEX, Light::None>(cx, kp, sc, small_base, stack, lvstack, nullptr);
+        cx.S.ovf = ovf;
+
+        const size_t pix = (size_t)py * W + px;
+        uint4 texel = reinterpret_cast<const uint4*>(kp.fr.rng)[pix];       // r, g, b, a
+        const float4 acc = reinterpret_cast<const float4*>(kp.fr.accum)[pix];
+        F3 cached = f3(acc.x, acc.y, acc.z);
+        // the pixel's record of set k: 32 bytes at ((k * H + y) * W + x), read as two 16-byte loads -- an 8x8 block reads eight 256-byte
+        // row segments.  Sample s takes set (frame0 + s) % n_sets: the index is carried, not divided for
+        const float4* const rays = reinterpret_cast<const float4*>(kr.rays) + 2u * pix;
+        const size_t set_stride = 2u * (size_t)W * H;
+        uint32_t set = kp.frame0 % kr.n_sets;
+        uint32_t s = 0;
+
+        PathState ps;
+        Pcg rng;
+        auto begin_sample = [&]() {
+            (void)cast_ray(kp.cam, 0.0f, 0.0f, rng);            // the lens draws of Camera.hh:59-69 advance the stream; their ray is not used
+            const float4* const rec = rays + (size_t)set * set_stride;
+            const float4 o = rec[0], d = rec[1];                 // origin, tmax | direction, pad
+            path_begin(ps, make_ray(f3(o.x, o.y, o.z), f3(d.x, d.y, d.z)), kp.max_depth);      // normalised on entry like Ray::Ray (trc_trace_rays)
+            set = set + 1u == kr.n_sets ? 0u : set + 1u;
+        };
+        // pcg32_t rng = { rng_inc, rng_state } aggregate-initialises {state, inc}: the two 64-bit words trade roles every frame
+        // (Render.metal:516-519,545-557, B-1)
+        rng.state = ((uint64_t)texel.z << 32) | texel.w;
+        rng.inc = ((uint64_t)texel.x << 32) | texel.y;
+        begin_sample();
+        bool alive = true;
+        // flat loop: one Scene::hit per iteration; a finished path immediately regenerates the next sample
+        while (alive) {
+            constexpr int kDefer = LDS ? TRC_DEFER_LDS : TRC_DEFER_GLOBAL;      // dev_intersect.hpp: trav_test_leaf
+            bump(n_rays);
+            const bool hitted = scene_hit<LDS, false, false, false, false, HYB, kDefer>(cx.S, cx.root_min, cx.root_max, ps.ray, ps.rec, FLT_MAX,
+                                                                                       cx.stack, cx.lvstack, cnt);
+            F3 color;
+            const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
+                                      ? path_step<false, false, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
+                                      : mis_step<LDS, false, false, false, HYB, TEX, Light::None>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+            if (finished) {      // accumulate, hand the RNG words back to the texel, start the next sample (or stop)
+                const bool bad = is_inf(color.x) || is_nan(color.x) || is_inf(color.y) || is_nan(color.y) ||
+                                 is_inf(color.z) || is_nan(color.z);
+                if (bad) color = f3(0);                                         // :537-538
+                const uint32_t frame = kp.frame0 + s;
+                cached = div_shared(cached * (float)frame + color, (float)(frame + 1));      // running mean, :540-541
+                texel.y = (uint32_t)rng.state; texel.x = (uint32_t)(rng.state >> 32);
+                texel.w = (uint32_t)rng.inc;   texel.z = (uint32_t)(rng.inc >> 32);
+                n_paths++;
+                if (++s == kp.spp) alive = false;
+                else {
+                    rng.state = ((uint64_t)texel.z << 32) | texel.w;
+                    rng.inc = ((uint64_t)texel.x << 32) | texel.y;
+                    begin_sample();
+                }
+            }
+        }
+        float4 out; out.x = cached.x; out.y = cached.y; out.z = cached.z; out.w = 1.0f;
+        reinterpret_cast<float4*>(kp.fr.accum)[pix] = out;
+        reinterpret_cast<uint4*>(kp.fr.rng)[pix] = texel;
+    }
+
+    // per SAMPLE (cost_div = 4 x spp), so that launches of different lengths speak of the same quantity
+    if (lane == 0) kp.block_cost[canon] = (uint32_t)min((unsigned long long)(clock64() - t_start) / kp.cost_div, 0xFFFFFFull);
+}
+
+// one one-wavefront workgroup = one entry of the launch list, at the launch bounds of the k_render entry it shadows
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_rays(const KRenderRays kr) {
+    const KRender& kp = kr.kp;
+    if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
+    const DScene& sc = kp.ks.sc;
+    const uint32_t* small_base = stage_scene(sc);
+    uint32_t* stack = lane_stack(sc);
+    uint32_t* lvstack = lane_lvstack(sc);
+
+    const uint32_t lane = threadIdx.x;
+    uint32_t n_rays = 0, n_shaded = 0, n_paths = 0;
+    TravCounters cnt;
+    counters_zero(cnt);
+    constexpr bool kHybridStack = !LDS && hybrid_stack(INTEGRATOR);     // plan_launch_lds
+    uint32_t* ovf = kHybridStack ? kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane : nullptr;
+    render_rays_block<LDS, INTEGRATOR, kHybridStack, TEX>(kr, sc, small_base, stack, lvstack, ovf, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt);
+
+    // exact work counters: wave reduction, one 64-bit atomic per wave and counter
+    uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
+    unsigned long long* const stats = stat_row(kp.stats, blockIdx.x);
+    if (lane == 0) {
+        atomicAdd(&stats[kStatPaths], (unsigned long long)r_paths);
+        atomicAdd(&stats[kStatRays], (unsigned long long)r_rays);
+        atomicAdd(&stats[kStatShaded], (unsigned long long)r_shaded);
+    }
+}
+
+// the table of one tree residence (trc_render_config.hpp: RenderRaysKernels); taking a kernel's address is what instantiates it
+template <bool LDS>
+inline RenderRaysKernels render_rays_kernels() {
+    RenderRaysKernels t{};
+    t.one[0][0] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_PATH, false>, render_waves(LDS, false, TRC_INTEGRATOR_PATH));
+    t.one[0][1] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_PATH, true>, render_waves(LDS, false, TRC_INTEGRATOR_PATH));
+    t.one[1][0] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_MIS, false>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
+    t.one[1][1] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_MIS, true>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
+    return t;
+}
+TRC_RENDER_NS_END

@@ -146,7 +146,12 @@ def _load(path, hooks=False):
     L.trc_adaptive_default_params.argtypes = [C.POINTER(abi.AdaptiveParams)]
     L.trc_render_adaptive.argtypes = [vp, C.POINTER(abi.Params), C.POINTER(abi.AdaptiveParams), C.POINTER(abi.AdaptiveReport)]
     L.trc_download_tile_samples.argtypes = [vp, vp]
+    L.trc_upload_camera_rays.argtypes = [vp, vp, u32]
+    L.trc_generate_camera_rays.argtypes = [vp, C.POINTER(abi.RayGen)]
+    L.trc_download_camera_rays.argtypes = [vp, u32, vp]
+    L.trc_clear_camera_rays.argtypes = [vp]
     if hooks:
+        L.trc_debug_last_camera_rays.argtypes = [vp, C.POINTER(u32)]
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
         L.trc_div_by_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
@@ -561,9 +566,10 @@ class Tracer:
     # --- the hot path --------------------------------------------------------------
     def render(self, spp=1, max_depth=8, integrator=abi.INTEGRATOR_PATH, frame0=0, tile_rank=0, tile_nranks=1,
                collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None, env_light=False,
-               mesh_lights=False):
+               mesh_lights=False, camera_rays=False):
         flags = ((abi.FLAG_COLLECT_STATS if collect_stats else 0) | (abi.FLAG_FIXED_ORDER if fixed_order else 0) |
                  (abi.FLAG_SOBOL if sobol else 0) | (abi.FLAG_ENV_LIGHT if env_light else 0) | (abi.FLAG_MESH_LIGHTS if mesh_lights else 0) |
+                 (abi.FLAG_CAMERA_RAYS if camera_rays else 0) |
                  (0 if small_blocks is None else (abi.FLAG_SMALL_BLOCKS if small_blocks else abi.FLAG_LARGE_BLOCKS)))
         prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0, tile_rank=tile_rank,
                          tile_nranks=tile_nranks, flags=flags, view_height=view_height)
@@ -571,6 +577,39 @@ class Tracer:
 
     def synchronize(self):
         self._check(self._L.trc_synchronize(self._h), "trc_synchronize")
+
+    # --- camera-ray sets (include/tracer_abi.h "Camera-ray sets"; render(camera_rays=True)) -------------------------
+    def upload_camera_rays(self, rays):
+        """trc_upload_camera_rays: a structured array of trc_ray (dtypes.RAY_DTYPE) of shape (n_sets, H, W), or (H, W) for one set"""
+        from .dtypes import RAY_DTYPE
+        assert rays.dtype == RAY_DTYPE and rays.flags.c_contiguous and rays.shape[-2:] == (self.height, self.width) and rays.ndim in (2, 3)
+        self._check(self._L.trc_upload_camera_rays(self._h, rays.ctypes.data, 1 if rays.ndim == 2 else rays.shape[0]), "trc_upload_camera_rays")
+
+    def generate_camera_rays(self, model=abi.RAYS_PINHOLE, n_sets=1, offsets=None):
+        """trc_generate_camera_rays: n_sets sets built on the device from the context's camera; offsets: (n_sets, 2) sub-pixel offsets in
+        [0, 1) (host.halton_offsets), None = all zero"""
+        g = abi.RayGen(model=model, n_sets=n_sets)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.float32)
+            assert offsets.shape == (n_sets, 2), offsets.shape
+            g.offsets = offsets.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self._L.trc_generate_camera_rays(self._h, C.byref(g)), "trc_generate_camera_rays")
+
+    def download_camera_rays(self, set=0):
+        """trc_download_camera_rays -> (H, W) structured array of trc_ray"""
+        from .dtypes import RAY_DTYPE
+        out = np.zeros((self.height, self.width), dtype=RAY_DTYPE)
+        self._check(self._L.trc_download_camera_rays(self._h, set, out.ctypes.data), "trc_download_camera_rays")
+        return out
+
+    def clear_camera_rays(self):
+        self._check(self._L.trc_clear_camera_rays(self._h), "trc_clear_camera_rays")
+
+    def last_camera_rays(self):
+        """hooks build only: whether the last render launch ran a kernel of TRC_FLAG_CAMERA_RAYS (trc_debug_last_camera_rays)"""
+        used = C.c_uint32(0)
+        self._check(self._L.trc_debug_last_camera_rays(self._h, C.byref(used)), "trc_debug_last_camera_rays")
+        return bool(used.value)
 
     # --- tile mask, per-tile error estimate, adaptive sampling (include/tracer_abi.h) ------------------------------
     def tile_grid(self):

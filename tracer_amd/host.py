@@ -49,6 +49,10 @@ def lib():
         L.trc_host_prepare_camera.restype = None
         L.trc_host_fill_rng.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
         L.trc_host_fill_rng.restype = None
+        L.trc_host_generate_camera_rays.argtypes = [C.POINTER(abi.Camera), C.c_uint32, C.c_uint32, C.POINTER(abi.RayGen), C.c_void_p]
+        L.trc_host_generate_camera_rays.restype = C.c_int32
+        L.trc_host_halton_offsets.argtypes = [C.c_uint32, C.c_void_p]
+        L.trc_host_halton_offsets.restype = None
         L.trc_host_scene_create.argtypes = [C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                             C.POINTER(C.c_void_p)]
         L.trc_host_scene_create.restype = C.c_int32
@@ -366,6 +370,29 @@ def make_camera(look_from, look_at, view_up, aperture, aspect, vfov_radians, foc
 def fill_rng(seed, width, height):
     out = np.empty((height, width, 4), dtype=np.uint32)
     lib().trc_host_fill_rng(seed, width, height, out.ctypes.data)
+    return out
+
+
+def generate_camera_rays(camera, width, height, model=abi.RAYS_PINHOLE, n_sets=1, offsets=None):
+    """trc_host_generate_camera_rays: the definition of Tracer.generate_camera_rays -> (n_sets, H, W) structured array of trc_ray;
+    offsets: (n_sets, 2) sub-pixel offsets in [0, 1), None = all zero.  ValueError on arguments the library refuses."""
+    from .dtypes import RAY_DTYPE
+    g = abi.RayGen(model=model, n_sets=n_sets)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.float32)
+        assert offsets.shape == (n_sets, 2), offsets.shape
+        g.offsets = offsets.ctypes.data_as(C.POINTER(C.c_float))
+    out = np.zeros((n_sets if 0 < n_sets <= abi.TRC_MAX_RAY_SETS else 1, height, width), dtype=RAY_DTYPE)
+    st = lib().trc_host_generate_camera_rays(C.byref(camera), width, height, C.byref(g), out.ctypes.data)
+    if st != abi.OK:
+        raise ValueError(f"trc_host_generate_camera_rays: status {st}")
+    return out
+
+
+def halton_offsets(n):
+    """trc_host_halton_offsets -> (n, 2) float32: offset k = the radical inverses base 2 and 3 of k + 1"""
+    out = np.empty((n, 2), dtype=np.float32)
+    lib().trc_host_halton_offsets(n, out.ctypes.data)
     return out
 
 
