@@ -38,9 +38,20 @@ trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64
  * input in the order given, so that the caller decides which materials meet in one wavefront of 64.  For n inputs (material type by
  * ordinal, colour, wo in the shading frame, the two random numbers) out receives 7 floats each: wi, the attenuation and the pdf; wi
  * starts as 0 and the pdf as pdf_init, which an early-out leaves in place.  stream 0: the Metal lobe as a branch of its own; stream 1:
- * through the Beckmann lobes' stream (TRC_MICROFACET_STREAM).  Both exist here whichever the render kernels were compiled with. */
+ * through the Beckmann lobes' stream (TRC_MICROFACET_STREAM); stream 2 and 3: those two with Beckmann's sample11 evaluating each exp,
+ * log and erf_inv once (TRC_SAMPLE11_ONCE 7).  All four exist here whichever the render kernels were compiled with. */
 trc_status trc_material_s_f_test(trc_ctx* ctx, uint32_t stream, const uint32_t* type /* n */, const float* color /* 3 n */,
                                  const float* wo /* 3 n */, const float* uu /* 2 n */, size_t n, float pdf_init, float* out /* 7 n */);
+
+/* test hook of the visible-normal sampling: sample11 of dev_bsdf.hpp alone, one lane per input in the order given (64 consecutive inputs
+ * are one wavefront).  form: as `stream` above (0 a branch per family, 1 Microfacet::sample11 with the family per lane, 2 and 3 those with
+ * TRC_SAMPLE11_ONCE 7).  family[i]: 0 Beckmann, 1 Trowbridge-Reitz.  alpha_y: the roughness the stream's distribution object is built with
+ * (alpha_x is 0.01; sample11 reads the family alone: the roughness reaches it through the stretched direction's cosine and sine).  cap:
+ * the bound of Beckmann's Newton loop, 10 as the render kernels run it, or 3 or 2, which make lanes run out of iterations.  in: cosTheta,
+ * sinTheta, U1, U2 per input.  slopes: slope_x, slope_y.  exit_kind: 0 the corner cosTheta > .9999, 1 the Newton loop left by its break,
+ * 2 the Newton loop ran out, 3 Trowbridge-Reitz's closed form. */
+trc_status trc_sample11_test(trc_ctx* ctx, uint32_t form, const uint32_t* family /* n */, float alpha_y, uint32_t cap, const float* in /* 4 n */,
+                             size_t n, float* slopes /* 2 n */, uint32_t* exit_kind /* n */);
 
 /* test hook of the SVGF stage (tracer_abi.h, trc_denoise): the state the last trc_denoise left, W*H float4 each (any pointer may
  * be NULL): integrated = the temporal pass's (colour, variance), history = the colour history the next frame reprojects

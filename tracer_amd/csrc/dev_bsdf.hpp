@@ -133,6 +133,18 @@ TRC_DEV float erf_approx(float x) {
     float y = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * dm_expf(-x * x);
     return sign * y;
 }
+// erf_approx with its exponential handed in: e must be what dm_expf returns for -x * x with x = |x| (sample11_once, which needs the
+// same value once more)
+TRC_DEV float erf_approx_exp(float x, float e) {
+    const float a1 = 0.254829592f, a2 = -0.284496736f, a3 = 1.421413741f, a4 = -1.453152027f, a5 = 1.061405429f;
+    const float p = 0.3275911f;
+    int sign = 1;
+    if (x < 0) sign = -1;
+    x = fabsf(x);
+    float t = rcp1(1 + p * x);
+    float y = 1 - (((((a5 * t + a4) * t) + a3) * t + a2) * t + a1) * t * e;
+    return sign * y;
+}
 
 // ---------------------------------------------------------------- BXDF.hh / BXDF.metal
 TRC_DEV F3 reflect(F3 wo, F3 n) { return -wo + 2 * dot(wo, n) * n; }             // BXDF.hh:24-26
@@ -195,6 +207,126 @@ struct Alpha_01_02 {
     TRC_DEV static DivConst by_y2() { return div_by_sqr002(); }
 };
 
+// TRC_SAMPLE11_ONCE (read by material_S_F): Beckmann's sample11 with each transcendental body evaluated once per lane and once per
+// wavefront.  0 is the reference's text as Beckmann::sample11 and Microfacet::sample11 below state it.  Otherwise a set of bits:
+//   1  exp(-cot^2) once: erf_approx's exponential and the normalisation's are the same float (see sample11_once);
+//   2  slope_x = erf_inv(b) after the Newton loop is the loop's last invErf wherever the loop was left by `break`: b has not been
+//      written since.  Only a lane that ran out of iterations evaluates erf_inv(b) again, in a last trip of the loop;
+//   4  one logarithm core ahead of the corner's branch, for the corner's -log(1 - U1) and the Newton lanes' log(base), which are
+//      disjoint lanes of one wavefront; the special operands of the corner's dm_logf are patched in afterwards.
+// Every lane computes the bits of the reference's text (trc_sample11_test and trc_material_s_f_test hold the two texts against each
+// other).  A translation unit sets it before including this header; 7 is all three, which the units of LDS-resident trees set
+// (profiles/r31).  CAP is the loop's bound, 10 everywhere but in the hook, which forces the running-out exit with 2 and 3.
+#ifndef TRC_SAMPLE11_ONCE
+#define TRC_SAMPLE11_ONCE 0
+#endif
+constexpr int kOnceExp = 1, kOnceErfInv = 2, kOnceLog = 4;
+// how a lane left sample11 (the hook reports it)
+constexpr int kS11Corner = 0, kS11Break = 1, kS11RanOut = 2, kS11ClosedForm = 3;
+
+// tr: the lane is a Trowbridge-Reitz lane of the microfacet stream (Microfacet::sample11); false for all lanes from Beckmann::sample11
+template <int ONCE, int CAP>
+TRC_DEV int sample11_once(const bool tr, float cosTheta, float sinTheta, float U1, float U2, float& slope_x, float& slope_y) {
+    const bool corner = cosTheta > .9999f;
+    const float sample_x = fmaxf(U1, 1e-6f);
+    const float base = 1 - sample_x;
+    float lg = 0;                                     // corner: dm_logf(1 - U1); Newton lanes: dm_logf_pos(base == 0 ? 1 : base)
+    if constexpr ((ONCE & kOnceLog) != 0) {
+        // dm_logf is dm_logf_pos behind three operand tests (NaN, <= 0, +inf): the core sees 1.0 on such a lane and the result is
+        // overwritten, as dm_asinf patches its special operands in.  Trowbridge-Reitz lanes take no logarithm: they ride along on 1.0
+        // and nobody reads their lg.  A Newton lane hands the core the operand the reference's text hands it.
+        const float om = 1.0f - U1;
+        const bool plain = om > 0.0f && om != DM_INF_F;                 // false for a NaN
+        float operand = corner ? (plain ? om : 1.0f) : (base == 0.0f ? 1.0f : base);
+        if (tr) operand = 1.0f;
+        lg = dm_logf_pos(operand);
+        if (corner && !plain) lg = (om != om || om == DM_INF_F) ? om : (om == 0.0f) ? -DM_INF_F : DM_NAN_F;
+    }
+    if (corner) {
+        float r2;                                     // each family's own radius, one root
+        if (tr) r2 = U1 / (1 - U1);
+        else r2 = -((ONCE & kOnceLog) != 0 ? lg : dm_logf(1.0f - U1));
+        float r = sqrt_cr(r2);
+        const float phi = tr ? 6.28318530718f * U2 : 2 * kPi * U2;      // each family's own literal
+        float s, c;
+        dm_sincosf(phi, &s, &c);
+        slope_x = r * c;
+        slope_y = r * s;
+        return kS11Corner;
+    }
+    const float tanTheta = sinTheta / cosTheta;
+    const float cotTheta = rcp1(tanTheta);
+    if (tr) {                                         // TrowbridgeReitzD::sample11: the closed form
+        const float a = cotTheta;
+        float G1 = 2 * rcp1(1 + sqrt_cr(1.f + rcp1(a * a)));
+        float A = 2 * U1 / G1 - 1;
+        float tmp = rcp1(A * A - 1.f);
+        if (tmp > 1e10f) tmp = 1e10f;
+        float B = tanTheta;
+        float D = sqrt_cr(fmaxf(B * B * tmp * tmp - (A * A - B * B) * tmp, 0.0f));
+        float slope_x_1 = B * tmp - D;
+        float slope_x_2 = B * tmp + D;
+        slope_x = (A < 0 || slope_x_2 > a) ? slope_x_1 : slope_x_2;
+        float S;
+        if (U2 > 0.5f) { S = 1.f; U2 = 2.f * (U2 - .5f); }
+        else { S = -1.f; U2 = 2.f * (.5f - U2); }
+        float z = (U2 * (U2 * (U2 * 0.27385f - 0.73369f) + 0.46341f)) /
+                  (U2 * (U2 * (U2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
+        slope_y = S * z * sqrt_cr(1.f + slope_x * slope_x);
+        return kS11ClosedForm;
+    }
+    const float tanThetaI = tanTheta, cotThetaI = cotTheta, cosThetaI = cosTheta;      // Beckmann::sample11: the Newton iteration
+    // exp(-cot^2): erf_approx states it as -x * x with x = |cot|, the normalisation as -cot * cot.  A float product is the product of
+    // the magnitudes, rounded, under the exclusive-or of the signs; (-|c|, |c|) and (-c, c) have the same magnitudes and one negative
+    // operand each, so the two arguments are the same float for every c that is a number and dm_expf runs once.  For a NaN c both are
+    // NaNs, whose sign and payload may differ: what they reach (c, the normalisation, value) is a NaN in both texts, of whichever
+    // sign -- the hooks' tests count a NaN equal to a NaN --, and a sample whose colour comes out NaN is replaced by 0 in finish_sample.
+    const float xa = fabsf(cotThetaI);
+    const float e = (ONCE & kOnceExp) != 0 ? dm_expf(-xa * xa) : 0.0f;
+    float a = -1, c = (ONCE & kOnceExp) != 0 ? erf_approx_exp(cotThetaI, e) : erf_approx(cotThetaI);
+    float thetaI = dm_acosf(cosThetaI);
+    float fit = 1 + thetaI * (-0.876f + thetaI * (0.4265f - 0.0594f * thetaI));
+    if constexpr ((ONCE & kOnceLog) == 0) lg = dm_logf_pos(base == 0.0f ? 1.0f : base);
+    const float pw = dm_expf_fin(fit * lg);
+    float b = c - (1 + c) * (base == 0.0f ? 0.0f : pw);
+    const float SQRT_PI_INV = 1.f / sqrtf(kPi);
+    float normalization = rcp1(1 + c + SQRT_PI_INV * tanThetaI * ((ONCE & kOnceExp) != 0 ? e : dm_expf(-cotThetaI * cotThetaI)));
+    int it = 0;
+    if constexpr ((ONCE & kOnceErfInv) != 0) {
+        // the reference's slope_x = erf_inv(b) after the loop as one more trip of the loop's own erf_inv: a lane that leaves by `break`
+        // holds erf_inv of the b it leaves with (nothing wrote b since); a lane that runs out of iterations takes a last trip that
+        // neither clamps b to [a, c] nor steps -- erf_inv(b) on the b the last step left, as the reference evaluates it.  The
+        // wavefront takes that trip only while such a lane is in it, and sample11 holds one erf_inv body less.
+        for (;;) {
+            const bool last = !(++it < CAP);
+            if (!last && !(b >= a && b <= c)) b = 0.5f * (a + c);
+            const float invErf = erf_inv(b);
+            slope_x = invErf;
+            if (last) break;
+            float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * dm_expf_fin(-invErf * invErf)) - sample_x;  // |erf_inv| < 3.2
+            float derivative = normalization * (1 - invErf * tanThetaI);
+            if (fabsf(value) < 1e-5f) break;
+            if (value > 0) c = b; else a = b;
+            b -= value / derivative;
+        }
+    } else {
+        while (++it < CAP) {
+            if (!(b >= a && b <= c)) b = 0.5f * (a + c);
+            float invErf = erf_inv(b);
+            float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * dm_expf_fin(-invErf * invErf)) - sample_x;  // |erf_inv| < 3.2
+            float derivative = normalization * (1 - invErf * tanThetaI);
+            if (fabsf(value) < 1e-5f) break;
+            if (value > 0) c = b; else a = b;
+            b -= value / derivative;
+        }
+        slope_x = erf_inv(b);
+    }
+    // `break` leaves it < CAP, running out it == CAP
+    const bool ran_out = !(it < CAP);
+    slope_y = erf_inv(2.0f * fmaxf(U2, 1e-6f) - 1.0f);
+    return ran_out ? kS11RanOut : kS11Break;
+}
+
 // Beckmann distribution, MicrofacetBXDF.h:137-290.  The roughness pair is a run-time value (not a template
 // parameter) on purpose: Plastic's specular lobe (0.01, 0.1) and Glass's reflection and transmission lobes
 // (0.01, 0.01) then run the SAME instructions, so a wavefront holding lanes of several of these lobes executes
@@ -237,14 +369,17 @@ struct Beckmann {
     TRC_DEV float G(F3 wo, F3 wi) const { return rcp1(1 + lambda(wo) + lambda(wi)); }
     TRC_DEV float pdf(F3 wo, F3 wh) const { return D(wh) * G1(wo) * fabsf(dot(wo, wh)) / abs_cos_theta(wo); }
 
-    TRC_DEV static void sample11(float cosThetaI, float sinThetaI, float U1, float U2, float& slope_x, float& slope_y) {
+    // returns how the lane left (kS11Corner, kS11Break, kS11RanOut); ONCE != 0: sample11_once above
+    template <int ONCE = 0, int CAP = 10>
+    TRC_DEV static int sample11(float cosThetaI, float sinThetaI, float U1, float U2, float& slope_x, float& slope_y) {
+        if constexpr (ONCE != 0) return sample11_once<ONCE, CAP>(false, cosThetaI, sinThetaI, U1, U2, slope_x, slope_y);
         if (cosThetaI > .9999f) {
             float r = sqrt_cr(-dm_logf(1.0f - U1));
             float sinPhi, cosPhi;
             dm_sincosf(2 * kPi * U2, &sinPhi, &cosPhi);
             slope_x = r * cosPhi;
             slope_y = r * sinPhi;
-            return;
+            return kS11Corner;
         }
         float tanThetaI = sinThetaI / cosThetaI;          // sinThetaI = sqrt(max(0, 1 - cosThetaI^2)) = sin_theta of the caller's vector
         float cotThetaI = rcp1(tanThetaI);
@@ -261,7 +396,7 @@ struct Beckmann {
         const float SQRT_PI_INV = 1.f / sqrtf(kPi);
         float normalization = rcp1(1 + c + SQRT_PI_INV * tanThetaI * dm_expf(-cotThetaI * cotThetaI));
         int it = 0;
-        while (++it < 10) {
+        while (++it < CAP) {
             if (!(b >= a && b <= c)) b = 0.5f * (a + c);
             float invErf = erf_inv(b);
             float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * dm_expf_fin(-invErf * invErf)) - sample_x;      // |erf_inv| < 3.2
@@ -272,14 +407,16 @@ struct Beckmann {
         }
         slope_x = erf_inv(b);
         slope_y = erf_inv(2.0f * fmaxf(U2, 1e-6f) - 1.0f);
+        return it < CAP ? kS11Break : kS11RanOut;
     }
+    template <int ONCE = 0>
     TRC_DEV F3 sample_wh(F3 wo, F2 u) const {
         const bool flip = wo.z < 0;
         const F3 wi = flip ? -wo : wo;
         F3 wiStretched = normalize(f3(ax() * wi.x, ay() * wi.y, wi.z));
         float slope_x, slope_y;
         const float st = sin_theta(wiStretched);
-        sample11(cos_theta(wiStretched), st, u.x, u.y, slope_x, slope_y);
+        sample11<ONCE>(cos_theta(wiStretched), st, u.x, u.y, slope_x, slope_y);
         const Phi ph = phi_of(wiStretched, st);
         float tmp = ph.c * slope_x - ph.s * slope_y;
         slope_y = ph.s * slope_x + ph.c * slope_y;
@@ -645,7 +782,10 @@ struct Microfacet {
                (kPi * ax() * ay() * cos4Theta);
     }
 
-    TRC_DEV void sample11(float cosTheta, float sinTheta, float U1, float U2, float& slope_x, float& slope_y) const {
+    // returns how the lane left (kS11Corner ... kS11ClosedForm); ONCE != 0: sample11_once above
+    template <int ONCE = 0, int CAP = 10>
+    TRC_DEV int sample11(float cosTheta, float sinTheta, float U1, float U2, float& slope_x, float& slope_y) const {
+        if constexpr (ONCE != 0) return sample11_once<ONCE, CAP>(tr, cosTheta, sinTheta, U1, U2, slope_x, slope_y);
         if (cosTheta > .9999f) {
             float r2;                                     // each family's own radius, one root
             if (tr) r2 = U1 / (1 - U1);
@@ -656,7 +796,7 @@ struct Microfacet {
             dm_sincosf(phi, &s, &c);
             slope_x = r * c;
             slope_y = r * s;
-            return;
+            return kS11Corner;
         }
         const float tanTheta = sinTheta / cosTheta;
         const float cotTheta = rcp1(tanTheta);
@@ -677,7 +817,7 @@ struct Microfacet {
             float z = (U2 * (U2 * (U2 * 0.27385f - 0.73369f) + 0.46341f)) /
                       (U2 * (U2 * (U2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
             slope_y = S * z * sqrt_cr(1.f + slope_x * slope_x);
-            return;
+            return kS11ClosedForm;
         }
         const float tanThetaI = tanTheta, cotThetaI = cotTheta, cosThetaI = cosTheta;      // Beckmann::sample11: the Newton iteration
         float a = -1, c = erf_approx(cotThetaI);
@@ -690,7 +830,7 @@ struct Microfacet {
         const float SQRT_PI_INV = 1.f / sqrtf(kPi);
         float normalization = rcp1(1 + c + SQRT_PI_INV * tanThetaI * dm_expf(-cotThetaI * cotThetaI));
         int it = 0;
-        while (++it < 10) {
+        while (++it < CAP) {
             if (!(b >= a && b <= c)) b = 0.5f * (a + c);
             float invErf = erf_inv(b);
             float value = normalization * (1 + b + SQRT_PI_INV * tanThetaI * dm_expf_fin(-invErf * invErf)) - sample_x;
@@ -701,14 +841,16 @@ struct Microfacet {
         }
         slope_x = erf_inv(b);
         slope_y = erf_inv(2.0f * fmaxf(U2, 1e-6f) - 1.0f);
+        return it < CAP ? kS11Break : kS11RanOut;
     }
+    template <int ONCE = 0>
     TRC_DEV F3 sample_wh(F3 wo, F2 u) const {
         const bool flip = wo.z < 0;
         const F3 wi = flip ? -wo : wo;
         F3 wiStretched = normalize(f3(ax() * wi.x, ay() * wi.y, wi.z));
         float slope_x, slope_y;
         const float st = sin_theta(wiStretched);
-        sample11(cos_theta(wiStretched), st, u.x, u.y, slope_x, slope_y);
+        sample11<ONCE>(cos_theta(wiStretched), st, u.x, u.y, slope_x, slope_y);
         const Phi ph = phi_of(wiStretched, st);
         float tmp = ph.c * slope_x - ph.s * slope_y;
         slope_y = ph.s * slope_x + ph.c * slope_y;
@@ -847,9 +989,11 @@ TRC_DEV F3 texture_value(int tex_type, F3 albedo, F2 uv) {           // Texture.
 // and both Glass lobes.  Every lane evaluates exactly the reference's expressions for its own material.
 // STREAM: the four microfacet lobes as one stream (TRC_MICROFACET_STREAM above).  The instrumented kernels (STATS) keep the
 // branches apart, so that the per-site profile of trc_debug_profile stays what it says.
-template <bool STATS, bool STREAM = (TRC_MICROFACET_STREAM != 0)>
+// ONCE: sample11's text (TRC_SAMPLE11_ONCE above); the instrumented kernels keep the reference's.
+template <bool STATS, bool STREAM = (TRC_MICROFACET_STREAM != 0), int ONCE_ARG = TRC_SAMPLE11_ONCE>
 TRC_DEV F3 material_S_F(int type, F3 color, F3 wo, F3& wi, F2 uu, float& pdf, TravCounters& cnt) {
     const bool plastic = type == kMatPlastic, glass = type == kMatGlass;
+    constexpr int ONCE = STATS ? 0 : ONCE_ARG;
     F3 out = f3(0);
     if constexpr (STREAM && !STATS) {
         const bool metal = type == kMatMetal;
@@ -869,7 +1013,7 @@ TRC_DEV F3 material_S_F(int type, F3 color, F3 wo, F3& wi, F2 uu, float& pdf, Tr
             const Microfacet d = Microfacet::make_lobe(metal, plastic);
             F3 lobe = f3(0);
             if (wo.z != 0) {
-                const F3 wh = d.sample_wh(wo, u2);
+                const F3 wh = d.template sample_wh<ONCE>(wo, u2);
                 lobe = microfacet_finish(d, refl, (metal || plastic) ? 1.0f : 0.98f, wo, wh, wi, pdf);
             }
             out = plastic ? color * (f3(0.2f) * lobe) : color * lobe;
@@ -896,7 +1040,7 @@ TRC_DEV F3 material_S_F(int type, F3 color, F3 wo, F3& wi, F2 uu, float& pdf, Tr
         F3 lobe = f3(0);
         if (wo.z != 0) {
             F3 wh;
-            { ProfScope<STATS> scope(cnt, kProfBeckSample); wh = d.sample_wh(wo, u2); }
+            { ProfScope<STATS> scope(cnt, kProfBeckSample); wh = d.template sample_wh<ONCE>(wo, u2); }
             ProfScope<STATS> scope(cnt, kProfBeckEval);
             lobe = beckmann_finish(d, refl, plastic ? 1.0f : 0.98f, wo, wh, wi, pdf);
         }

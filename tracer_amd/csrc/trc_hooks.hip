@@ -52,8 +52,9 @@ __global__ void __launch_bounds__(256) k_unary_test(uint32_t op, uint32_t first,
 }
 
 // trc_material_s_f_test: material_S_F (dev_bsdf.hpp) in either form, one lane per input, so that the order of the inputs decides
-// which materials share a wavefront.  Both forms are instantiated here whatever TRC_MICROFACET_STREAM says.
-template <bool STREAM>
+// which materials share a wavefront.  Both forms, and both texts of sample11 (ONCE: TRC_SAMPLE11_ONCE), are instantiated here whatever
+// TRC_MICROFACET_STREAM and TRC_SAMPLE11_ONCE say.
+template <bool STREAM, int ONCE = 0>
 __global__ void __launch_bounds__(256) k_material_s_f_test(const uint32_t* type, const float* color, const float* wo, const float* uu,
                                                            uint32_t n, float pdf_init, float* out) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -62,10 +63,42 @@ __global__ void __launch_bounds__(256) k_material_s_f_test(const uint32_t* type,
     F3 wi = f3(0);
     float pdf = pdf_init;
     TravCounters none;
-    const F3 f = material_S_F<false, STREAM>((int)type[i], f3(color[3 * i], color[3 * i + 1], color[3 * i + 2]),
+    const F3 f = material_S_F<false, STREAM, ONCE>((int)type[i], f3(color[3 * i], color[3 * i + 1], color[3 * i + 2]),
                                              f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), wi, u, pdf, none);
     float* o = out + 7 * (size_t)i;
     o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = f.x; o[4] = f.y; o[5] = f.z; o[6] = pdf;
+}
+
+// trc_sample11_test: sample11 alone, one lane per input.  STREAM: Microfacet::sample11 with the family per lane, else a branch per family
+// (Beckmann::sample11, TrowbridgeReitzD::sample11); ONCE: the text (TRC_SAMPLE11_ONCE); CAP: the bound of the Newton loop
+template <bool STREAM, int ONCE, int CAP>
+__global__ void __launch_bounds__(256) k_sample11_test(const uint32_t* family, float alpha_y, const float* in, uint32_t n, float* slopes,
+                                                       uint32_t* exit_kind) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bool tr = family[i] != 0u;
+    const float cosTheta = in[4 * i], sinTheta = in[4 * i + 1], U1 = in[4 * i + 2], U2 = in[4 * i + 3];
+    float sx = 0, sy = 0;
+    int kind;
+    if constexpr (STREAM) {
+        Microfacet d = Microfacet::make_lobe(tr, false);
+        d.alpha_y = alpha_y;
+        kind = d.template sample11<ONCE, CAP>(cosTheta, sinTheta, U1, U2, sx, sy);
+    } else if (tr) {
+        TrowbridgeReitzD<Alpha_01_02>::sample11(cosTheta, sinTheta, U1, U2, sx, sy);
+        kind = cosTheta > .9999f ? kS11Corner : kS11ClosedForm;
+    } else {
+        kind = Beckmann::sample11<ONCE, CAP>(cosTheta, sinTheta, U1, U2, sx, sy);
+    }
+    slopes[2 * i] = sx; slopes[2 * i + 1] = sy;
+    exit_kind[i] = (uint32_t)kind;
+}
+template <bool STREAM, int ONCE>
+static void launch_sample11(uint32_t cap, dim3 grid, hipStream_t st, const uint32_t* family, float alpha_y, const float* in, uint32_t n,
+                            float* slopes, uint32_t* kind) {
+    if (cap == 2u) hipLaunchKernelGGL((k_sample11_test<STREAM, ONCE, 2>), grid, dim3(256), 0, st, family, alpha_y, in, n, slopes, kind);
+    else if (cap == 3u) hipLaunchKernelGGL((k_sample11_test<STREAM, ONCE, 3>), grid, dim3(256), 0, st, family, alpha_y, in, n, slopes, kind);
+    else hipLaunchKernelGGL((k_sample11_test<STREAM, ONCE, 10>), grid, dim3(256), 0, st, family, alpha_y, in, n, slopes, kind);
 }
 
 extern "C" {
@@ -165,7 +198,7 @@ trc_status trc_div_by_test(trc_ctx* ctx, const float* a, const float* b, size_t 
 
 trc_status trc_material_s_f_test(trc_ctx* ctx, uint32_t stream, const uint32_t* type, const float* color, const float* wo, const float* uu,
                                  size_t n, float pdf_init, float* out) {
-    if (!ctx || stream > 1u || (n && (!type || !color || !wo || !uu || !out))) return TRC_ERR_INVALID_ARG;
+    if (!ctx || stream > 3u || (n && (!type || !color || !wo || !uu || !out))) return TRC_ERR_INVALID_ARG;
     if (n == 0) return TRC_OK;
     if (n > 0x7FFFFFFFu / 7u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_material_s_f_test: too many inputs in one call");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -178,11 +211,36 @@ trc_status trc_material_s_f_test(trc_ctx* ctx, uint32_t stream, const uint32_t* 
     TRC_TRY(trc_copy_to_device(ctx, d_uu, uu, n * 8, ctx->stream));
     TRC_TRY(trc_copy_to_device(ctx, d_type, type, n * 4, ctx->stream));
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (stream) hipLaunchKernelGGL(k_material_s_f_test<true>, grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
+    if (stream == 3u) hipLaunchKernelGGL((k_material_s_f_test<true, 7>), grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
+    else if (stream == 2u) hipLaunchKernelGGL((k_material_s_f_test<false, 7>), grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
+    else if (stream) hipLaunchKernelGGL(k_material_s_f_test<true>, grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
     else hipLaunchKernelGGL(k_material_s_f_test<false>, grid, dim3(256), 0, ctx->stream, d_type, d_color, d_wo, d_uu, (uint32_t)n, pdf_init, d_out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_material_s_f_test: ") + hipGetErrorString(e));
     return trc_copy_to_host(ctx, out, d_out, n * 28, ctx->stream);
+}
+
+trc_status trc_sample11_test(trc_ctx* ctx, uint32_t form, const uint32_t* family, float alpha_y, uint32_t cap, const float* in, size_t n,
+                             float* slopes, uint32_t* exit_kind) {
+    if (!ctx || form > 3u || (cap != 10u && cap != 3u && cap != 2u) || (n && (!family || !in || !slopes || !exit_kind))) return TRC_ERR_INVALID_ARG;
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 8u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_sample11_test: too many inputs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf d;
+    TRC_TRY(d.alloc(ctx, n * 8 * sizeof(float), "sample11 test"));
+    float *d_in = d.as<float>(), *d_slopes = d_in + 4 * n;
+    uint32_t *d_family = reinterpret_cast<uint32_t*>(d_in + 6 * n), *d_kind = d_family + n;
+    TRC_TRY(trc_copy_to_device(ctx, d_in, in, n * 16, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_family, family, n * 4, ctx->stream));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (form == 3u) launch_sample11<true, 7>(cap, grid, ctx->stream, d_family, alpha_y, d_in, (uint32_t)n, d_slopes, d_kind);
+    else if (form == 2u) launch_sample11<false, 7>(cap, grid, ctx->stream, d_family, alpha_y, d_in, (uint32_t)n, d_slopes, d_kind);
+    else if (form == 1u) launch_sample11<true, 0>(cap, grid, ctx->stream, d_family, alpha_y, d_in, (uint32_t)n, d_slopes, d_kind);
+    else launch_sample11<false, 0>(cap, grid, ctx->stream, d_family, alpha_y, d_in, (uint32_t)n, d_slopes, d_kind);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_sample11_test: ") + hipGetErrorString(e));
+    TRC_TRY(trc_copy_to_host(ctx, slopes, d_slopes, n * 8, ctx->stream));
+    return trc_copy_to_host(ctx, exit_kind, d_kind, n * 4, ctx->stream);
 }
 
 trc_status trc_unary_test(trc_ctx* ctx, uint32_t op, uint32_t first_bits, uint64_t count, uint64_t* n_mismatch, uint32_t* first_mismatch) {

@@ -9,6 +9,9 @@
 #ifndef TRC_MICROFACET_STREAM
 #define TRC_MICROFACET_STREAM 1      // dev_bsdf.hpp: the Metal lobe through the Beckmann lobes' stream (profiles/r22)
 #endif
+#ifndef TRC_SAMPLE11_ONCE
+#define TRC_SAMPLE11_ONCE 7          // dev_bsdf.hpp: Beckmann's sample11 evaluates each exp, log and erf_inv once (profiles/r31)
+#endif
 #include "trc_render_kernels.hpp"
 
 TRC_RENDER_NS_BEGIN

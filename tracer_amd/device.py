@@ -165,6 +165,7 @@ def _load(path, hooks=False):
         L.trc_debug_last_kernel.argtypes = [vp, C.POINTER(abi.KernelChoice)]
         L.trc_debug_last_residency.argtypes = [vp, C.POINTER(abi.Residency)]
         L.trc_material_s_f_test.argtypes = [vp, u32, vp, vp, vp, vp, C.c_size_t, C.c_float, vp]
+        L.trc_sample11_test.argtypes = [vp, u32, vp, C.c_float, u32, vp, C.c_size_t, vp, vp]
         for name in abi.HOOK_SYMBOLS:
             getattr(L, name).restype = i32
     L.trc_has_test_hooks.restype = C.c_int
@@ -865,15 +866,29 @@ class Tracer:
 
     def material_s_f_test(self, types, color, wo, uu, stream, pdf_init=0.0):
         """(n, 7) float32: wi, attenuation, pdf of the kernels' material_S_F, one lane per input in this order; stream: the Metal lobe
-        through the Beckmann lobes' stream (TRC_MICROFACET_STREAM) or as a branch of its own.  An early-out leaves pdf_init in place."""
+        through the Beckmann lobes' stream (TRC_MICROFACET_STREAM) or as a branch of its own; 2 and 3: those two with sample11 evaluating
+        each exp, log and erf_inv once (TRC_SAMPLE11_ONCE 7).  An early-out leaves pdf_init in place."""
         types = np.ascontiguousarray(types, dtype=np.uint32)
         color, wo, uu = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, wo, uu))
         n = len(types)
         assert types.ndim == 1 and color.shape == (n, 3) and wo.shape == (n, 3) and uu.shape == (n, 2)
         out = np.empty((n, 7), np.float32)
-        self._check(self._L.trc_material_s_f_test(self._h, 1 if stream else 0, types.ctypes.data, color.ctypes.data, wo.ctypes.data,
+        self._check(self._L.trc_material_s_f_test(self._h, int(stream), types.ctypes.data, color.ctypes.data, wo.ctypes.data,
                                                   uu.ctypes.data, n, float(pdf_init), out.ctypes.data), "trc_material_s_f_test")
         return out
+
+    def sample11_test(self, form, family, alpha_y, cap, cos_theta, sin_theta, u1, u2):
+        """(slopes (n, 2) float32, exit kinds (n,) uint32) of the kernels' sample11 alone, one lane per input in this order
+        (trc_sample11_test).  form: 0 a branch per family, 1 the stream, 2 and 3 those with TRC_SAMPLE11_ONCE 7; family: 0 Beckmann, 1
+        Trowbridge-Reitz per input; cap: the Newton loop's bound (10, 3 or 2)."""
+        family = np.ascontiguousarray(family, dtype=np.uint32)
+        n = len(family)
+        packed = np.ascontiguousarray(np.stack([np.asarray(a, np.float32) for a in (cos_theta, sin_theta, u1, u2)], axis=1))
+        assert family.ndim == 1 and packed.shape == (n, 4)
+        slopes, kind = np.empty((n, 2), np.float32), np.empty(n, np.uint32)
+        self._check(self._L.trc_sample11_test(self._h, int(form), family.ctypes.data, float(alpha_y), int(cap), packed.ctypes.data, n,
+                                              slopes.ctypes.data, kind.ctypes.data), "trc_sample11_test")
+        return slopes, kind
 
     def div_by_test(self, a, b):
         """(fast, plain): 3 quotients per operand pair through the guarded shared-divisor division and through `/`."""
