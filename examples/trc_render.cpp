@@ -36,9 +36,12 @@
 //                          (255 = N samples) to <out>.samples.png.  Takes traceMIS unless --integrator says otherwise (tracer_abi.h: why)
 //              [--aa N]    anti-aliasing: N camera-ray sets (1 .. 1024) with Halton sub-pixel offsets are generated on the device
 //                          (trc_host_halton_offsets, trc_generate_camera_rays) and the frame is rendered with TRC_FLAG_CAMERA_RAYS: sample s takes
-//                          set s % N.  tracePath / traceMIS; not with --sobol, --env-light or --mesh-lights (tracer_abi.h)
+//                          set s % N.  tracePath / traceMIS, with --env-light too (a final frame of an env-lit scene); not with --sobol or
+//                          --mesh-lights (tracer_abi.h)
 //              [--projection pinhole|ortho|equirect]  the projection of those sets (one set at zero offset without --aa): the camera's own,
-//                          orthographic through the view plane, or a 360 degree panorama from the eye (world axes, as the --hdr map's)
+//                          orthographic through the view plane, or a 360 degree panorama from the eye (world axes, as the --hdr map's:
+//                          --projection equirect --hdr map.hdr --env-light --integrator mis is a panorama of the scene lit by that map).
+//                          With --denoise the filter follows these rays (trc_denoise_guide_rays): its G-buffer is walked along set 0
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -350,6 +353,10 @@ int main(int argc, char** argv) {
     };
     if (denoise) {
         CHECK(trc_denoise_track_motion(ctx, 1));
+        if (prm.flags & TRC_FLAG_CAMERA_RAYS) {      // rays in force: the G-buffer is walked along set 0 of them (with --aa the first Halton offset), not along the camera's ray
+            CHECK(trc_denoise_guide_rays(ctx, 1));
+            std::printf("denoiser guided by the camera rays (set 0)\n");
+        }
         CHECK(denoised_output());
     } else {
         CHECK(trc_tonemap(ctx, rgba8.data(), &exposure));

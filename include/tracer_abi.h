@@ -76,7 +76,10 @@ extern "C" {
  *     added under 13, the number stays: trc_set_tile_mask, trc_download_tile_mask, trc_tile_snapshot, trc_tile_error, trc_download_tile_error,
  *     trc_adaptive_params, trc_adaptive_report, trc_adaptive_default_params, trc_render_adaptive, trc_download_tile_samples, knob
  *     mask_forgets_costs (trc_render over a subset of the frame's tiles, a per-tile error estimate and a driver that stops sampling the
- *     tiles that have settled; with no mask set and no adaptive call made nothing changes; additions only) */
+ *     tiles that have settled; with no mask set and no adaptive call made nothing changes; additions only)
+ *     added under 13, the number stays: TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT is accepted (traceMIS: the map as a light under camera-ray
+ *     sets; it returned TRC_ERR_UNSUPPORTED before) and trc_denoise_guide_rays (the SVGF G-buffer walked along the ray sets; opt-in, off by
+ *     default); no unflagged launch and no unguided trc_denoise changes */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -391,12 +394,23 @@ enum trc_integrator {
    - Accepted with TRC_INTEGRATOR_PATH and TRC_INTEGRATOR_MIS, with or without active image textures, with or without
      trc_upload_triangle_materials, on trees staged in LDS or read from memory, with tile_rank / tile_nranks, under a tile mask and in
      trc_render_adaptive.  TRC_ERR_UNSUPPORTED, nothing rendered: no rays in force; TRC_INTEGRATOR_VOLUME; TRC_FLAG_SOBOL,
-     TRC_FLAG_COLLECT_STATS, TRC_FLAG_ENV_LIGHT or TRC_FLAG_MESH_LIGHTS; a view_height that names a stack (non-zero and below H).
+     TRC_FLAG_COLLECT_STATS or TRC_FLAG_MESH_LIGHTS; a view_height that names a stack (non-zero and below H).
+   - With TRC_FLAG_ENV_LIGHT besides (TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT, traceMIS): the sample takes its camera ray from the
+     sets exactly as above (the lens draws are taken and dropped), and everything after that is the TRC_FLAG_ENV_LIGHT sample step by
+     step: the light pick, the six extra draws when the map is picked, the any-hit shadow walk, the MIS weights, the weighting of
+     escapes from cosine lobes.  So with the rays the camera itself would cast (as above) the frame, the RNG texture and
+     trc_stats.rays / paths / shaded are the unflagged TRC_FLAG_ENV_LIGHT call's, bit for bit; and k calls of 1 sample equal one call of
+     k samples.  Accepted with TRC_INTEGRATOR_MIS and a map set, with or without active image textures, trc_upload_triangle_materials
+     and square lights, on trees staged in LDS or read from memory, with tile ranks, under a tile mask and in trc_render_adaptive.
+     The refusals are the union of the two flags' own (TRC_ERR_UNSUPPORTED, nothing rendered): no rays in force, no map, another
+     integrator, TRC_FLAG_SOBOL, TRC_FLAG_COLLECT_STATS, TRC_FLAG_MESH_LIGHTS, a stacked view.  The natural pair of
+     TRC_RAYS_EQUIRECT: a panorama of a scene lit by the map, in the map's own parametrisation.
    - A flagged launch runs kernels of its own, one pixel block per one-wavefront workgroup: no strips, persistent workgroups or
      dense kernel, and no primary replay.  A change of the flag, or new rays in force, drops the recorded block costs of the
-     launch planner, as a change of the integrator does.
-   - LIMIT: trc_denoise and the SPPM camera pass know nothing of the rays.  Their G-buffer and camera records are the camera's:
-     right for TRC_RAYS_PINHOLE sets, up to the sub-pixel offset, and wrong for any other rays. */
+     launch planner, as a change of the integrator does (and so does a change of TRC_FLAG_ENV_LIGHT under the flag).
+   - trc_denoise follows the rays where trc_denoise_guide_rays is on ("A denoiser that follows the rays" below); with it off its
+     G-buffer is the camera's: right for TRC_RAYS_PINHOLE sets, up to the sub-pixel offset, and wrong for any other rays.
+   - LIMIT: the SPPM camera pass knows nothing of the rays; TRC_FLAG_MESH_LIGHTS is refused under the flag. */
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
                                        N_descend / N_return / leaf-test counters.  Not with an active image texture
                                        (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
@@ -1166,6 +1180,37 @@ trc_status trc_download_motion(trc_ctx* ctx, trc_motion_texel* out /* W*H */);
 /* The history length n of step 2 as the last trc_denoise left it, one float per pixel (1 on a miss): what a host watches to see whether
  * the history survives its animation.  Tracking on or off.  TRC_ERR_NO_FRAME before a trc_denoise, TRC_ERR_INVALID_ARG on a NULL argument. */
 trc_status trc_download_history_length(trc_ctx* ctx, float* n /* W*H */);
+/* A denoiser that follows the rays: trc_denoise_guide_rays(ctx, on) (opt-in; with it off every call is what it was).
+ *
+ * The G-buffer above is walked along the camera's own pinhole ray.  Under camera-ray sets (TRC_FLAG_CAMERA_RAYS) of another projection --
+ * orthographic, a panorama, a host's own lens -- that guides the filter with surfaces the pixel does not show.  With the switch on the
+ * filter reads the rays instead.
+ *
+ * State.  A switch of the context like trc_denoise_track_motion: off at trc_create, kept across trc_upload_scene* and trc_resize.  A call
+ * that changes it, either way, drops the history (and the G-buffer is rebuilt); a call that leaves it as it is does nothing.
+ * TRC_ERR_INVALID_ARG on a NULL context.  With the switch on:
+ *
+ * 1. G-buffer ray.  The ray of pixel (x, y) is record y * W + x of set 0 of the rays in force (a host puts the set it wants the filter
+ *    guided by first: with sub-pixel offsets the one nearest the pixel's centre, or a set at the zero offset).  The ray is made as trc_trace_rays makes one: the direction is
+ *    normalised on entry, tmax and _pad are ignored.  depth = t along that normalised ray from the ray's own origin; normal, albedo and
+ *    id are as stated above; the walk is the same production walk.  So every texel is what trc_trace_rays(..., TRC_TRACE_PRODUCTION)
+ *    answers for the record: depth has the bits of t, normal of sn, id is material; a miss is (+inf, 0, 1, TRC_GBUFFER_MISS).
+ * 2. When the G-buffer is rebuilt: when the scene, the frame size or the switch changed; when the rays in force were replaced -- the
+ *    context counts generations: trc_upload_camera_rays, trc_generate_camera_rays, trc_clear_camera_rays and trc_resize each begin a new
+ *    one; when a tracked moving call marked it stale.  NOT when the camera changed: the rays hold their own camera, so trc_set_camera
+ *    neither rebuilds the G-buffer nor touches the history while the switch is on.
+ * 3. Temporal pass (step 2 above).  A new generation of rays drops the history: n = 1 everywhere, even if the new rays have the old
+ *    bits.  So whenever there is a history the rays are the ones it was made under, and every pixel with moved = 0 takes the one tap
+ *    (x, y) with weight 1 and zq = depth.  A pixel with moved = 1 (tracking on, a snapshot in force) has NO valid history: n = 1, a = 1
+ *    -- a ray set defines no inverse to reproject through.  Pixels that did not move keep their history.  Steps 1 and 3 to 5 unchanged.
+ * 4. Motion texel (tracking on): o and d are the G-buffer ray of 1; everything else as stated under "Motion tracking".  Under the
+ *    camera's own pinhole rays the plane has the bits it has with the switch off.
+ * 5. trc_denoise with the switch on and no rays in force returns TRC_ERR_UNSUPPORTED: nothing changes, the history is kept.
+ * 6. Limits: no reprojection under the switch -- a host that changes its rays per frame restarts the history at every frame; the SPPM
+ *    camera pass still uses the camera; contexts in a group are refused, as without the switch.
+ * With the camera's own rays as set 0 (TRC_RAYS_PINHOLE, no offset, a camera that has not changed since), every plane has the bits it has
+ * with the switch off.  trc_download_gbuffer, trc_download_motion and trc_download_history_length answer as before. */
+trc_status trc_denoise_guide_rays(trc_ctx* ctx, int on);
 /* ------------------------------------------------------------------ */
 /* Tile mask, per-tile error estimate, adaptive sampling (tracer_amd/csrc/trc_adaptive.hip) */
 /* ------------------------------------------------------------------ */

@@ -8,7 +8,12 @@
      and wall time between two trc_synchronize.  Every side's frame is compared with the production one's: the same bits.
   2. trc_generate_camera_rays for 1, 16 and 64 sets, and the host generator plus trc_upload_camera_rays of the same; the memory held.
   3. that it anti-aliases: config 2 under traceMIS at --spp samples, unflagged and with as many Halton sets, each against a --truth-spp unflagged
-     render at 4 x the resolution in each dimension, box-filtered down (another seed): RMSE of both."""
+     render at 4 x the resolution in each dimension, box-filtered down (another seed): RMSE of both.
+  4. (--steps envlight; profiles/r31/camera_rays_envlight.txt) step 1 for TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT: config 2 under traceMIS with
+     an HDR sun-and-sky map as a light, the flag pair against the unflagged TRC_FLAG_ENV_LIGHT launch on the same shape and in production.
+  5. (--steps gbuffer) trc_denoise_guide_rays: the G-buffer pass along set 0 of the ray sets against the camera's own, and a whole
+     trc_denoise on each side, on config 2 and config 4.  Wall time between two trc_synchronize around a trc_denoise that rebuilds the
+     G-buffer (a fresh generation of the same rays on the guided side, a scene upload's invalidation on both) minus one that does not."""
 import argparse
 import os
 import sys
@@ -48,41 +53,57 @@ def timed(t, fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def launch(t, a, integrator, flagged):
+def launch(t, a, integrator, flagged, env_light=False):
     t.seed(a.seed); t.clear_accum(); t.reset_stats()
-    wall = timed(t, lambda: t.render(spp=a.spp, integrator=integrator, camera_rays=flagged))
+    wall = timed(t, lambda: t.render(spp=a.spp, integrator=integrator, camera_rays=flagged, env_light=env_light))
     return wall, t.stats().kernel_ms
 
 
-def ray_path_cost(a, config, integrator):
+def sun_sky(w, h, sun=(0.3, 0.7), sun_radius=0.02, sun_power=5000.0):
+    """an HDR map: sky by latitude, a disc of sun_power around (u, w) = sun (tools/envlight_bench.py's)"""
+    lat = np.pi * ((np.arange(h, dtype=np.float64) + 0.5) / h - 0.5)
+    phi = 2 * np.pi * ((np.arange(w, dtype=np.float64) + 0.5) / w - 0.5)
+    img = np.empty((h, w, 3), np.float32)
+    img[:] = 0.05 + np.clip(np.sin(lat), 0, 1)[:, None, None] * np.array([0.4, 0.6, 1.0])
+    sp, sl = 2 * np.pi * (sun[0] - 0.5), np.pi * (sun[1] - 0.5)
+    cosang = (np.cos(lat)[:, None] * np.cos(phi)[None] * np.cos(sl) * np.cos(sp) + np.sin(lat)[:, None] * np.sin(sl) +
+              np.cos(lat)[:, None] * np.sin(phi)[None] * np.cos(sl) * np.sin(sp))
+    img[cosang > np.cos(sun_radius)] += sun_power
+    return img
+
+
+def ray_path_cost(a, config, integrator, env_light=False):
     wl = workloads.make(config)
-    sides = [("flagged, one pinhole set", True, True), ("unflagged, same shape", False, True), ("unflagged, production", False, False)]
+    un = "unflagged" if not env_light else "ENV_LIGHT alone"
+    sides = [("flagged, one pinhole set", True, True), (f"{un}, same shape", False, True), (f"{un}, production", False, False)]
     ctxs, res, frames = [], {}, {}
     try:
         for name, flagged, forced in sides:
             t = Tracer(0)
             ctxs.append(t)
             workloads.setup(t, wl)
+            if env_light:
+                t.set_environment_map(sun_sky(1024, 512))
             if forced:
                 for knob in ("no_dense", "no_pwg", "no_primary_replay"):
                     t.debug_set(knob, 1)
                 t.debug_set("strip_len", 1)
             if flagged:
                 t.generate_camera_rays(abi.RAYS_PINHOLE, 1, None)
-        say(f"--- {wl['what'].split(',')[0]}, {NAMES[integrator]}, {W}x{H}, {a.spp} spp per launch; {a.warmup} warm-up launches, medians of {a.reps}")
+        say(f"--- {wl['what'].split(',')[0]}, {NAMES[integrator]}{' + TRC_FLAG_ENV_LIGHT (1024 x 512 sun-and-sky map)' if env_light else ''}, {W}x{H}, {a.spp} spp per launch; {a.warmup} warm-up launches, medians of {a.reps}")
         for r in range(a.warmup + a.reps):
             order = list(zip(sides, ctxs))
             for (name, flagged, _), t in (order if r % 2 == 0 else order[::-1]):
-                wall, kernel = launch(t, a, integrator, flagged)
+                wall, kernel = launch(t, a, integrator, flagged, env_light)
                 if r >= a.warmup:
                     e = res.setdefault(name, dict(wall=[], kernel=[]))
                     e["wall"].append(wall); e["kernel"].append(kernel)
         for (name, _, _), t in zip(sides, ctxs):
             frames[name] = t.download_accum().view(np.uint32)
-        base = med(res["unflagged, same shape"]["kernel"])
+        base = med(res[sides[1][0]]["kernel"])
         for name, _, _ in sides:
             e = res[name]
-            same = np.array_equal(frames[name], frames["unflagged, production"])
+            same = np.array_equal(frames[name], frames[sides[2][0]])
             say(f"   {name:26s} render kernel {spread(e['kernel'])}  wall {spread(e['wall'])}  x{med(e['kernel']) / base:5.3f} of the same shape; "
                 f"frame {'==' if same else '!='} production's")
     finally:
@@ -139,6 +160,31 @@ def anti_aliasing(a):
     say(f"   flagged, {a.spp} Halton sets                              RMSE {rmse(aa, truth):.5f}")
 
 
+def gbuffer_cost(a, config):
+    """trc_denoise with a G-buffer rebuild against trc_denoise without one, guided (set 0 of one pinhole set) and unguided"""
+    wl = workloads.make(config)
+    say(f"--- {wl['what'].split(',')[0]}, {W}x{H}: trc_denoise (5 a-trous iterations, demodulation), wall between two trc_synchronize; medians of {a.reps}")
+    for guided in (False, True):
+        with Tracer(0) as t:
+            workloads.setup(t, wl)
+            t.seed(a.seed); t.clear_accum()
+            t.render(spp=8, integrator=abi.INTEGRATOR_PATH)
+            p = t.denoise_params(demodulate=True)
+            if guided:
+                t.denoise_guide_rays(True)
+                t.generate_camera_rays(abi.RAYS_PINHOLE, 1, None)
+            t.denoise(p); t.synchronize()
+            keep, rebuild = [], []
+            for r in range(a.warmup + a.reps):
+                k = timed(t, lambda: t.denoise(p))                      # the G-buffer stands
+                t.denoise_guide_rays(not guided); t.denoise_guide_rays(guided)      # the switch there and back: the G-buffer is stale, on either side
+                b = timed(t, lambda: t.denoise(p))
+                if r >= a.warmup:
+                    keep.append(k); rebuild.append(b)
+            say(f"   {'guided by set 0' if guided else 'the camera ray '}  trc_denoise, G-buffer kept {spread(keep)}  rebuilt {spread(rebuild)}  "
+                f"k_gbuffer ~ {med(rebuild) - med(keep):6.3f} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -161,6 +207,13 @@ def main():
     if "aa" in steps:
         say("3. that it anti-aliases")
         anti_aliasing(a)
+    if "envlight" in steps:
+        say("4. the cost of the ray path under TRC_FLAG_ENV_LIGHT")
+        ray_path_cost(a, "2", abi.INTEGRATOR_MIS, env_light=True)
+    if "gbuffer" in steps:
+        say("5. the G-buffer along the rays")
+        for config in ("2", "4"):
+            gbuffer_cost(a, config)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

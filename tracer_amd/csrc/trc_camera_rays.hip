@@ -26,6 +26,7 @@ __global__ void __launch_bounds__(256) k_make_camera_rays(const trc_raygen_camer
 
 void trc_camera_rays_release(trc_ctx* ctx) {
     (void)hipFree(ctx->d_cam_rays); ctx->d_cam_rays = nullptr; ctx->n_ray_sets = 0;
+    ctx->ray_gen++;                                 // whatever comes next is another generation (trc_denoise under trc_denoise_guide_rays)
     if (ctx->cost_rays) trc_forget_costs(ctx);      // the recorded block costs were measured on these rays
 }
 

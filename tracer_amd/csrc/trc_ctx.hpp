@@ -92,6 +92,14 @@ struct KRenderRays {
     uint32_t n_sets;
 };
 
+// ... and the kernels of TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT (k_render_rays_env) both: the map's tables as in KRenderEnv, then the ray sets
+struct KRenderRaysEnv {
+    KRender kp;
+    EnvLight el;
+    const trc_ray* rays;
+    uint32_t n_sets;
+};
+
 struct KTrace {
     KScene ks;
     const trc_ray* rays;
@@ -242,6 +250,9 @@ struct trc_ctx {
     // force).  Sized by the frame: trc_release_frame.  cost_rays: the recorded block costs are a flagged launch's (drop_stale_costs)
     trc_ray* d_cam_rays = nullptr; uint32_t n_ray_sets = 0;
     bool cost_rays = false;
+    // ... ray_gen: which rays these are -- the next number whenever they are replaced or dropped (trc_camera_rays_release: trc_upload_camera_rays,
+    // trc_generate_camera_rays, trc_clear_camera_rays, trc_resize), whatever the new ones' bits: the denoiser under trc_denoise_guide_rays compares it
+    uint64_t ray_gen = 0;
 
     // tiles for (nranks, rank)
     uint32_t* d_tiles = nullptr;
@@ -329,6 +340,7 @@ struct trc_ctx {
     SppmState* sppm = nullptr;       // trc_sppm.hip
     DenoiseState* denoise = nullptr; // trc_denoise.hip (allocated by the first trc_denoise after trc_resize)
     bool track_motion = false;       // trc_denoise_track_motion: context state like the textures -- survives scene uploads and trc_resize; what it owns lives in `denoise`
+    bool guide_rays = false;         // trc_denoise_guide_rays: the same kind of state -- the G-buffer is walked along set 0 of the ray sets (d_cam_rays), not along the camera's ray
 
     // caller-supplied collectives (trc_group_set_collectives) instead of an RCCL communicator
     trc_collectives coll{};

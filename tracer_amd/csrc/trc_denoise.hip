@@ -122,18 +122,28 @@ TRC_DEV float4 analytic_motion(const SceneRef& S, const uint32_t* psnap, const H
     return moved ? make_float4(prev.x, prev.y, prev.z, __uint_as_float(1u)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
-template <bool LDS, bool TEX = false, bool MOTION = false>
-__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt, const KMotion mo) {
+// RAYS (trc_denoise_guide_rays): the pixel's ray is its record of set 0 of the context's ray sets (`rays`: W*H records of two float4, origin | tmax
+// and direction | pad), made as trc_trace_rays makes one; the other instantiations read the camera and not `rays`
+template <bool LDS, bool TEX = false, bool MOTION = false, bool RAYS = false>
+__global__ void __launch_bounds__(kBlock) k_gbuffer(const KScene ks, const DnCam cam, uint32_t W, uint32_t H, float4* gb, const TexTable tt, const KMotion mo,
+                                                    const float4* __restrict__ rays) {
     const DScene& sc = ks.sc;
     const uint32_t* small_base = stage_scene(sc);
     uint32_t* stack = lane_stack(sc);
     uint32_t* lvstack = lane_lvstack(sc);
     uint32_t x, y;
     if (!tile_pixel(W, H, x, y)) return;
-    const float u = (float)x / (float)W, v = (float)y / (float)H;
-    const F3 eye = f3(cam.eye[0], cam.eye[1], cam.eye[2]);
-    const F3 sample = f3(cam.cll[0], cam.cll[1], cam.cll[2]) + f3(cam.hor[0], cam.hor[1], cam.hor[2]) * u + f3(cam.ver[0], cam.ver[1], cam.ver[2]) * v;
-    const Ray ray = make_ray(eye, sample - eye);
+    Ray ray;
+    if constexpr (RAYS) {
+        const float4* const rec = rays + 2u * ((size_t)y * W + x);
+        const float4 o = rec[0], d = rec[1];
+        ray = make_ray(f3(o.x, o.y, o.z), f3(d.x, d.y, d.z));      // normalised on entry; tmax and pad are not read
+    } else {
+        const float u = (float)x / (float)W, v = (float)y / (float)H;
+        const F3 eye = f3(cam.eye[0], cam.eye[1], cam.eye[2]);
+        const F3 sample = f3(cam.cll[0], cam.cll[1], cam.cll[2]) + f3(cam.hor[0], cam.hor[1], cam.hor[2]) * u + f3(cam.ver[0], cam.ver[1], cam.ver[2]) * v;
+        ray = make_ray(eye, sample - eye);
+    }
     SceneRef S = make_scene_ref(sc, small_base);
     HitRec rec;
     hit_init(rec);
@@ -196,6 +206,7 @@ struct KTemporal {
     DnParams p;
     DnCam cur, prev;
     uint32_t have_prev, same_cam;
+    uint32_t guide;             // trc_denoise_guide_rays: a ray set defines no inverse -- a moved pixel has no valid history (same_cam is 1)
     const float4* accum;
     const float4* gb;
     const float4* gb_prev;
@@ -241,6 +252,8 @@ __global__ void __launch_bounds__(64) k_svgf_temporal(const KTemporal k) {
         const bool moved = MOTION && __float_as_uint(mt.w) != 0u;
         if (k.same_cam && !moved) {
             ntaps = 1; tx[0] = (int)x; ty[0] = (int)y; tw[0] = 1.0f; zq = z;
+        } else if (k.guide) {
+            ntaps = 0; zq = z; ok = false;
         } else {
             ntaps = 4;
             const float u = (float)x / (float)W, v = (float)y / (float)H;
@@ -451,7 +464,20 @@ struct DenoiseState {
     float4* snap = nullptr; uint32_t snap_n = 0;      // one position per vertex (allocated by trc_denoise), for snap_n vertices
     uint32_t* psnap = nullptr; uint32_t psnap_dwords = 0;      // the blob's primitive section (allocated by trc_denoise where the scene has one)
     bool snap_live = false;                    // both filled by the first moving call since the last trc_denoise: in force for the next
+    // trc_denoise_guide_rays (trc_ctx::guide_rays): the generation of the ray sets (trc_ctx::ray_gen) gb[gb_cur] was walked along, and the
+    // one the history was made under
+    uint64_t gb_ray_gen = 0, hist_ray_gen = 0;
 };
+
+// k_gbuffer<LDS, TEX, MOTION, RAYS> by its four switches
+template <bool LDS, bool TEX, bool MOTION, bool RAYS, class... A>
+static void launch_gbuffer(hipStream_t st, dim3 grid, size_t lds, A... a) { hipLaunchKernelGGL((k_gbuffer<LDS, TEX, MOTION, RAYS>), grid, dim3(kBlock), lds, st, a...); }
+template <bool LDS, bool TEX, bool MOTION, class... A>
+static void launch_gbuffer(bool rays, A... a) { if (rays) launch_gbuffer<LDS, TEX, MOTION, true>(a...); else launch_gbuffer<LDS, TEX, MOTION, false>(a...); }
+template <bool LDS, bool TEX, class... A>
+static void launch_gbuffer(bool motion, bool rays, A... a) { if (motion) launch_gbuffer<LDS, TEX, true>(rays, a...); else launch_gbuffer<LDS, TEX, false>(rays, a...); }
+template <bool LDS, class... A>
+static void launch_gbuffer(bool tex, bool motion, bool rays, A... a) { if (tex) launch_gbuffer<LDS, true>(motion, rays, a...); else launch_gbuffer<LDS, false>(motion, rays, a...); }
 
 void trc_denoise_release(trc_ctx* ctx) {
     DenoiseState* s = ctx ? ctx->denoise : nullptr;
@@ -560,6 +586,8 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     if (ctx->grouped()) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_denoise: composed multi-rank frames are not denoised");
     if (!ctx->d_accum) return trc_fail(ctx, TRC_ERR_NO_FRAME, "trc_denoise before trc_resize");
     if (!ctx->has_scene || !ctx->has_camera) return trc_fail(ctx, TRC_ERR_NO_SCENE, "trc_denoise before trc_upload_scene / trc_set_camera");
+    if (ctx->guide_rays && !ctx->d_cam_rays)      // before anything of the state is touched: the history stays
+        return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "trc_denoise: trc_denoise_guide_rays is on and no camera rays are in force (trc_upload_camera_rays / trc_generate_camera_rays)");
     const uint32_t e = prm->normal_exponent;
     if ((prm->flags & ~TRC_DENOISE_DEMODULATE) || prm->iterations > TRC_DENOISE_MAX_ITERATIONS ||
         !(prm->alpha_color > 0.0f && prm->alpha_color <= 1.0f) || !(prm->alpha_moments > 0.0f && prm->alpha_moments <= 1.0f) ||
@@ -583,8 +611,12 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     p.min_hist = prm->min_history;
     const dim3 grid((s->W + 7) / 8, (s->H + 7) / 8), block(64);
 
-    // G-buffer, lazily: only for another scene, camera or frame size
-    const bool rebuild = !s->gb_valid || std::memcmp(&s->gb_cam, &ctx->cam, sizeof(DCamera)) != 0;
+    // G-buffer, lazily: only for another scene, camera or frame size -- under trc_denoise_guide_rays for another scene, frame size or
+    // generation of the ray sets, and not for another camera: the rays hold their own
+    const bool guide = ctx->guide_rays;
+    const bool rebuild = !s->gb_valid || (guide ? s->gb_ray_gen != ctx->ray_gen : std::memcmp(&s->gb_cam, &ctx->cam, sizeof(DCamera)) != 0);
+    // ... and a history made under other ray sets is dropped, whatever their bits: the tap (x, y) below is the rays' own pixel
+    if (guide && s->have_hist && s->hist_ray_gen != ctx->ray_gen) s->have_hist = false;
     // a snapshot in force: a moving call filled it since the last trc_denoise, so the G-buffer is stale and this call rebuilds it
     const bool motion = ctx->track_motion && s->snap_live && rebuild;
     if (rebuild) {
@@ -592,23 +624,15 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
         const size_t lds = trc_dyn_lds_bytes(ctx, true);
         const DnCam cam = dn_cam(ctx->cam);
         TexTable tt{};
-        if (ctx->tex_active()) { tt.texels = ctx->d_tex_texels; tt.desc = ctx->d_tex_desc; tt.n = ctx->n_tex; }
+        if (ctx->tex_active()) { tt.texels = ctx->d_tex_texels; tt.desc = ctx->d_tex_desc; tt.n = ctx->n_tex; }      // an active image texture (trc_upload_textures): the albedo plane samples it
         const KMotion mo{ctx->d_idx, s->snap, s->psnap, s->motion};
-        if (motion) {
-            float4* gb = s->gb[s->gb_cur];
-            if (ctx->tex_active()) {
-                if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
-                else hipLaunchKernelGGL((k_gbuffer<false, true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
-            } else if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
-            else hipLaunchKernelGGL((k_gbuffer<false, false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, gb, tt, mo);
-            s->motion_zero = false;
-        } else if (ctx->tex_active()) {            // an active image texture (trc_upload_textures): the albedo plane samples it
-            if (ctx->lds_scene) hipLaunchKernelGGL((k_gbuffer<true, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
-            else hipLaunchKernelGGL((k_gbuffer<false, true>), grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
-        } else if (ctx->lds_scene) hipLaunchKernelGGL(k_gbuffer<true>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
-        else hipLaunchKernelGGL(k_gbuffer<false>, grid, block, lds, ctx->stream, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo);
+        const float4* const rays = guide ? reinterpret_cast<const float4*>(ctx->d_cam_rays) : nullptr;      // set 0
+        if (ctx->lds_scene) launch_gbuffer<true>(ctx->tex_active(), motion, guide, ctx->stream, grid, lds, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo, rays);
+        else launch_gbuffer<false>(ctx->tex_active(), motion, guide, ctx->stream, grid, lds, ctx->ks, cam, s->W, s->H, s->gb[s->gb_cur], tt, mo, rays);
+        if (motion) s->motion_zero = false;
         HIP_TRY(ctx, hipGetLastError());
         s->gb_cam = ctx->cam;
+        s->gb_ray_gen = ctx->ray_gen;
         s->gb_valid = true;
     }
 
@@ -617,7 +641,8 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     kt.cur = dn_cam(ctx->cam);
     kt.prev = s->hist_cam;
     kt.have_prev = s->have_hist ? 1u : 0u;
-    kt.same_cam = (s->have_hist && same_dn_cam(kt.cur, s->hist_cam)) ? 1u : 0u;
+    kt.same_cam = (s->have_hist && (guide || same_dn_cam(kt.cur, s->hist_cam))) ? 1u : 0u;      // guide: the history's rays are this frame's (above)
+    kt.guide = guide ? 1u : 0u;
     kt.accum = reinterpret_cast<const float4*>(ctx->d_accum);
     kt.gb = s->gb[s->gb_cur];
     kt.gb_prev = rebuild ? s->gb[s->gb_cur ^ 1] : s->gb[s->gb_cur];
@@ -661,6 +686,7 @@ trc_status trc_denoise(trc_ctx* ctx, const trc_denoise_params* prm) {
     s->hist_cur = nh;
     s->have_hist = true;
     s->hist_cam = kt.cur;
+    s->hist_ray_gen = ctx->ray_gen;
     s->has_output = true;
     return TRC_OK;
 }
@@ -710,6 +736,16 @@ trc_status trc_denoise_track_motion(trc_ctx* ctx, int on) {
     ctx->denoise->have_hist = false;            // either way: the next frame has n = 1 everywhere
     ctx->denoise->snap_live = false;
     if (!want) motion_free(ctx, true);
+    return TRC_OK;
+}
+
+trc_status trc_denoise_guide_rays(trc_ctx* ctx, int on) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx) return TRC_ERR_INVALID_ARG;
+    const bool want = on != 0;
+    if (want == ctx->guide_rays) return TRC_OK;
+    ctx->guide_rays = want;
+    trc_denoise_invalidate(ctx);                // either way: another G-buffer ray, and the next frame has n = 1 everywhere
     return TRC_OK;
 }
 

@@ -189,7 +189,9 @@ constexpr int pwg_simd_waves(int integrator) { return pwg_waves(integrator) * pw
 //   trc_render_mem_volume.hip traceVolume, trees read from memory                                             -disable-machine-sink
 // Each exports the kernel table of its families (render_kernels<LDS, INTEGRATOR>), which instantiates exactly the kernels in it;
 // trc_render_pass.hip launches whatever entry a launch picks.  A null entry is a variant that does not exist.
-enum RenderArgs { kArgsPlain, kArgsEnv, kArgsMesh, kArgsRays };      // the kernel's parameter block: KRender, KRenderEnv (TRC_FLAG_ENV_LIGHT), KRenderMesh (TRC_FLAG_MESH_LIGHTS), KRenderRays (TRC_FLAG_CAMERA_RAYS)
+// the kernel's parameter block: KRender, KRenderEnv (TRC_FLAG_ENV_LIGHT), KRenderMesh (TRC_FLAG_MESH_LIGHTS), KRenderRays (TRC_FLAG_CAMERA_RAYS),
+// KRenderRaysEnv (TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT)
+enum RenderArgs { kArgsPlain, kArgsEnv, kArgsMesh, kArgsRays, kArgsRaysEnv };
 struct RenderKernel {
     const void* fn;                     // the kernel (null: no such variant)
     int waves;                          // wavefronts per SIMD of its launch bounds
@@ -201,6 +203,7 @@ inline RenderKernel render_kernel(void (*fn)(KRender), int waves) { return {rein
 inline RenderKernel render_kernel(void (*fn)(KRenderEnv), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsEnv}; }
 inline RenderKernel render_kernel(void (*fn)(KRenderMesh), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsMesh}; }
 inline RenderKernel render_kernel(void (*fn)(KRenderRays), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsRays}; }
+inline RenderKernel render_kernel(void (*fn)(KRenderRaysEnv), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsRaysEnv}; }
 // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures, TRC_FLAG_ENV_LIGHT (traceMIS only) without and with image textures,
 // TRC_FLAG_MESH_LIGHTS (traceMIS only) without and with image textures
 enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariantEnv, kVariantEnvTex, kVariantMesh, kVariantMeshTex, kVariants };
@@ -218,9 +221,11 @@ extern const RenderKernel render_dense;
 }
 // TRC_FLAG_CAMERA_RAYS: tables of their own, beside the tables above and not in them -- k_render_rays<LDS, INTEGRATOR, TEX>
 // (trc_render_rays.hpp) at [tracePath 0 / traceMIS 1][image textures], one table per tree residence: trc_render_rays.hip (whole tree
-// staged in LDS) and trc_render_rays_mem.hip (trees read from memory), each with the options of the units it shadows, and their twins
+// staged in LDS) and trc_render_rays_mem.hip (trees read from memory), each with the options of the units it shadows, and their twins.
+// With TRC_FLAG_ENV_LIGHT besides (traceMIS only): k_render_rays_env<LDS, TEX> at env[image textures]
 struct RenderRaysKernels {
     RenderKernel one[2][2];
+    RenderKernel env[2];
 };
 extern const RenderRaysKernels render_rays_lds, render_rays_mem;
 namespace trimat {

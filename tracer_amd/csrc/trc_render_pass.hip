@@ -167,10 +167,12 @@ hipError_t launch_render(trc_ctx* ctx, const RenderLaunch& r) {
     KRenderEnv kpe;
     KRenderMesh kpm;
     KRenderRays kpr;
+    KRenderRaysEnv kpre;
     void* params = const_cast<KRender*>(&r.kp);
     if (r.kern.args == kArgsEnv) { kpe.kp = r.kp; kpe.el = r.el; params = &kpe; }
     if (r.kern.args == kArgsMesh) { kpm.kp = r.kp; kpm.ml = r.ml; params = &kpm; }
     if (r.kern.args == kArgsRays) { kpr.kp = r.kp; kpr.rays = ctx->d_cam_rays; kpr.n_sets = ctx->n_ray_sets; params = &kpr; }
+    if (r.kern.args == kArgsRaysEnv) { kpre.kp = r.kp; kpre.el = r.el; kpre.rays = ctx->d_cam_rays; kpre.n_sets = ctx->n_ray_sets; params = &kpre; }
     void* args[] = {params};
     const hipError_t e = hipLaunchKernel(fn, dim3(r.grid), dim3(r.block), args, r.lds, ctx->stream);
     const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
@@ -204,8 +206,9 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
     if (p->flags & TRC_FLAG_CAMERA_RAYS) {
         if (!ctx->d_cam_rays) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: no camera rays in force (trc_upload_camera_rays / trc_generate_camera_rays)");
         if (p->integrator == TRC_INTEGRATOR_VOLUME) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: tracePath / traceMIS only");
-        if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS | TRC_FLAG_ENV_LIGHT | TRC_FLAG_MESH_LIGHTS))
-            return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS / TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS kernels");
+        // (TRC_FLAG_ENV_LIGHT is let through: its own refusals follow below -- traceMIS, a map -- and k_render_rays_env runs the pair)
+        if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS | TRC_FLAG_MESH_LIGHTS))
+            return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS / TRC_FLAG_MESH_LIGHTS kernels");
         if (p->view_height != 0 && p->view_height < ctx->height) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: the ray sets are the frame's, not a stacked view's");
     }
     const bool env_light = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
@@ -391,10 +394,11 @@ static trc_status choose_rays_kernel(trc_ctx* ctx, const trc_params* p, RenderLa
     const RenderRaysKernels& table = ctx->tri_materials ? (ctx->lds_scene ? trimat::render_rays_lds : trimat::render_rays_mem)
                                                         : (ctx->lds_scene ? render_rays_lds : render_rays_mem);
     r.dense = r.pwg = false;
-    r.kern = table.one[integrator == TRC_INTEGRATOR_MIS ? 1 : 0][tex ? 1 : 0];
+    const bool env = r.light == Light::Env;                      // TRC_FLAG_ENV_LIGHT besides (render_check: traceMIS, a map set)
+    r.kern = env ? table.env[tex ? 1 : 0] : table.one[integrator == TRC_INTEGRATOR_MIS ? 1 : 0][tex ? 1 : 0];
     if (!r.kern.fn) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "no camera-ray kernel for this integrator");
     ctx->last_kernel.shape = 0u;                                 // trc_debug_last_kernel, trc_debug_last_camera_rays
-    ctx->last_kernel.variant = (uint32_t)(tex ? kVariantTex : kVariantPlain);
+    ctx->last_kernel.variant = (uint32_t)(env ? (tex ? kVariantEnvTex : kVariantEnv) : tex ? kVariantTex : kVariantPlain);
     ctx->last_kernel.lds_resident = ctx->lds_scene ? 1u : 0u;
     ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
     ctx->last_kernel.strip = kp.strip;

@@ -1,5 +1,5 @@
 // trc_render_rays.hip -- the kernels of TRC_FLAG_CAMERA_RAYS (trc_render_rays.hpp: a sample's camera ray is read from the context's ray
-// sets) on scenes whose whole tree is staged in LDS, tracePath and traceMIS, without and with image textures, compiled with the source
+// sets) on scenes whose whole tree is staged in LDS, tracePath, traceMIS and traceMIS under TRC_FLAG_ENV_LIGHT, without and with image textures, compiled with the source
 // options of the units they shadow (trc_render_lds.hip, trc_render_lds_mis.hip).  Trees read from memory: trc_render_rays_mem.hip.
 // Launched from trc_render_pass.hip.
 #ifndef TRC_TRIANGLE_MATERIALS

@@ -3,7 +3,8 @@
 // still takes cast_ray's lens draws (their ray is dropped), then path_begin, the same path_step / mis_step, the running mean weighted by
 // frame0 + s, the NaN / Inf clamp and the counters.  Beside the kernels of trc_render_kernels.hpp, not inside them: those are tuned to
 // the register and their primary-replay memo lives on the repeated camera ray, which a ray set takes away.  So: one pixel block per
-// one-wavefront workgroup, no parked state, no memo, no Sobol', no statistics.  Included by trc_render_rays.hip / trc_render_rays_mem.hip,
+// one-wavefront workgroup, no parked state, no memo, no Sobol', no statistics.  With TRC_FLAG_ENV_LIGHT besides (traceMIS), everything
+// after the camera ray is that flag's sample: k_render_rays_env is the same block over mis_step<.., Light::Env>.  Included by trc_render_rays.hip / trc_render_rays_mem.hip,
 // which instantiate the kernels through their tables (trc_render_config.hpp: RenderRaysKernels); trc_render_pass.hip launches them.
 #pragma once
 
@@ -13,10 +14,14 @@ TRC_RENDER_NS_BEGIN
 
 // One pixel block of a flagged launch: the launch entry is decoded as render_block decodes it (the split plan may hand out quarters,
 // sixteenths and single pixels), RNG texel and accumulator are read and written once, the block's cost is written per sample.
-template <bool LDS, int INTEGRATOR, bool HYB, bool TEX>
-__device__ __forceinline__ void render_rays_block(const KRenderRays& kr, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
+// KR: the kernel's parameter block, KRenderRays or KRenderRaysEnv (kr.kp, kr.rays, kr.n_sets); LIGHT, `tables` as in render_block (traceMIS:
+// Light::Env, the map's sampling tables).
+template <bool LDS, int INTEGRATOR, bool HYB, bool TEX, Light LIGHT = Light::None, class KR = KRenderRays>
+__device__ __forceinline__ void render_rays_block(const KR& kr, const DScene& sc, const uint32_t* small_base, uint32_t* stack, uint32_t* lvstack,
                                                   uint32_t* ovf, const uint32_t slot, const uint32_t lane,
-                                                  uint32_t& n_rays, uint32_t& n_shaded, uint32_t& n_paths, TravCounters& cnt) {
+                                                  uint32_t& n_rays, uint32_t& n_shaded, uint32_t& n_paths, TravCounters& cnt,
+                                                  const LightTables<LIGHT>* tables = nullptr) {
+    static_assert(LIGHT == Light::None || (LIGHT == Light::Env && INTEGRATOR == TRC_INTEGRATOR_MIS), "camera rays: the map is the only extra light, under traceMIS");
     const KRender& kp = kr.kp;
     const uint64_t t_start = clock64();          // this wavefront's own duration = the next launch's sort key
     const uint32_t entry = kp.order ? kp.order[slot] : slot;
@@ -37,8 +42,8 @@ __device__ __forceinline__ void render_rays_block(const KRenderRays& kr, const D
     const uint32_t canon = index * kp.cost_stride + (code ? code - 1u : 0u);
 
     if (active && kp.spp > 0) {
-        PathCtxOf<TEX, Light::None> cx;
-        fill_path_ctx<false, TEX, Light::None>(cx, kp, sc, small_base, stack, lvstack, nullptr);
+        PathCtxOf<TEX, LIGHT> cx;
+        fill_path_ctx<false, TEX, LIGHT>(cx, kp, sc, small_base, stack, lvstack, tables);
         cx.S.ovf = ovf;
 
         const size_t pix = (size_t)py * W + px;
@@ -76,7 +81,7 @@ __device__ __forceinline__ void render_rays_block(const KRenderRays& kr, const D
             F3 color;
             const bool finished = (INTEGRATOR == TRC_INTEGRATOR_PATH)
                                       ? path_step<false, false, TEX>(cx, ps, hitted, rng, cnt, n_shaded, color)
-                                      : mis_step<LDS, false, false, false, HYB, TEX, Light::None>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
+                                      : mis_step<LDS, false, false, false, HYB, TEX, LIGHT>(cx, ps, hitted, rng, cnt, n_rays, n_shaded, color);
             if (finished) {      // accumulate, hand the RNG words back to the texel, start the next sample (or stop)
                 const bool bad = is_inf(color.x) || is_nan(color.x) || is_inf(color.y) || is_nan(color.y) ||
                                  is_inf(color.z) || is_nan(color.z);
@@ -103,9 +108,9 @@ __device__ __forceinline__ void render_rays_block(const KRenderRays& kr, const D
     if (lane == 0) kp.block_cost[canon] = (uint32_t)min((unsigned long long)(clock64() - t_start) / kp.cost_div, 0xFFFFFFull);
 }
 
-// one one-wavefront workgroup = one entry of the launch list, at the launch bounds of the k_render entry it shadows
-template <bool LDS, int INTEGRATOR, bool TEX>
-__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_rays(const KRenderRays kr) {
+// the body of the kernels: one one-wavefront workgroup = one entry of the launch list
+template <bool LDS, int INTEGRATOR, bool TEX, Light LIGHT = Light::None, class KR = KRenderRays>
+__device__ __forceinline__ void render_rays_workgroup(const KR& kr, const LightTables<LIGHT>* tables = nullptr) {
     const KRender& kp = kr.kp;
     if (kp.n_launch && blockIdx.x >= *kp.n_launch) return;      // the grid is sized for the most quarters a plan may splice in
     const DScene& sc = kp.ks.sc;
@@ -119,7 +124,7 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) 
     counters_zero(cnt);
     constexpr bool kHybridStack = !LDS && hybrid_stack(INTEGRATOR);     // plan_launch_lds
     uint32_t* ovf = kHybridStack ? kp.stack_ovf + (size_t)blockIdx.x * sc.stack_ovf_rows * kBlock + lane : nullptr;
-    render_rays_block<LDS, INTEGRATOR, kHybridStack, TEX>(kr, sc, small_base, stack, lvstack, ovf, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt);
+    render_rays_block<LDS, INTEGRATOR, kHybridStack, TEX, LIGHT>(kr, sc, small_base, stack, lvstack, ovf, blockIdx.x, lane, n_rays, n_shaded, n_paths, cnt, tables);
 
     // exact work counters: wave reduction, one 64-bit atomic per wave and counter
     uint32_t r_paths = wave_sum(n_paths), r_rays = wave_sum(n_rays), r_shaded = wave_sum(n_shaded);
@@ -130,6 +135,16 @@ __global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) 
         atomicAdd(&stats[kStatShaded], (unsigned long long)r_shaded);
     }
 }
+// at the launch bounds of the k_render entry it shadows
+template <bool LDS, int INTEGRATOR, bool TEX>
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, INTEGRATOR)) k_render_rays(const KRenderRays kr) {
+    render_rays_workgroup<LDS, INTEGRATOR, TEX>(kr);
+}
+// ... with the environment map as a light (TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT; traceMIS), at the launch bounds of the k_render_env entry it shadows
+template <bool LDS, bool TEX>
+__global__ void __launch_bounds__(kBlock, render_waves(LDS, false, TRC_INTEGRATOR_MIS)) k_render_rays_env(const KRenderRaysEnv kre) {
+    render_rays_workgroup<LDS, TRC_INTEGRATOR_MIS, TEX, Light::Env>(kre, &kre.el);
+}
 
 // the table of one tree residence (trc_render_config.hpp: RenderRaysKernels); taking a kernel's address is what instantiates it
 template <bool LDS>
@@ -139,6 +154,8 @@ inline RenderRaysKernels render_rays_kernels() {
     t.one[0][1] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_PATH, true>, render_waves(LDS, false, TRC_INTEGRATOR_PATH));
     t.one[1][0] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_MIS, false>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
     t.one[1][1] = render_kernel(&k_render_rays<LDS, TRC_INTEGRATOR_MIS, true>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
+    t.env[0] = render_kernel(&k_render_rays_env<LDS, false>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
+    t.env[1] = render_kernel(&k_render_rays_env<LDS, true>, render_waves(LDS, false, TRC_INTEGRATOR_MIS));
     return t;
 }
 TRC_RENDER_NS_END

@@ -1,5 +1,5 @@
 // trc_render_rays_mem.hip -- the kernels of TRC_FLAG_CAMERA_RAYS (trc_render_rays.hpp) on trees read from memory (mesh scenes),
-// tracePath and traceMIS, without and with image textures, compiled with the source options of the units they shadow
+// tracePath, traceMIS and traceMIS under TRC_FLAG_ENV_LIGHT, without and with image textures, compiled with the source options of the units they shadow
 // (trc_render_mem_path.hip, trc_render_mem.hip).  Trees staged in LDS: trc_render_rays.hip.  Launched from trc_render_pass.hip.
 #ifndef TRC_TRIANGLE_MATERIALS
 #define TRC_TRIANGLE_MATERIALS 0      // triangles keep material 19; the twin reading per-triangle materials: trc_render_rays_mem_tm.hip

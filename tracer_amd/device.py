@@ -118,6 +118,7 @@ def _load(path, hooks=False):
     L.trc_download_gbuffer.argtypes = [vp, vp]
     L.trc_denoise_reset.argtypes = [vp]
     L.trc_denoise_track_motion.argtypes = [vp, C.c_int]
+    L.trc_denoise_guide_rays.argtypes = [vp, C.c_int]
     L.trc_download_motion.argtypes = [vp, vp]
     L.trc_download_history_length.argtypes = [vp, vp]
     L.trc_upload_textures.argtypes = [vp, C.POINTER(abi.Image), u32]
@@ -728,6 +729,11 @@ class Tracer:
     def denoise_track_motion(self, on=True):
         """trc_denoise_track_motion: the history follows the surfaces that update / pose / skin / morph_vertices move (off by default)."""
         self._check(self._L.trc_denoise_track_motion(self._h, 1 if on else 0), "trc_denoise_track_motion")
+
+    def denoise_guide_rays(self, on=True):
+        """trc_denoise_guide_rays: the denoiser's G-buffer is walked along set 0 of the camera-ray sets in force, not along the camera's own ray
+        (off by default); a change of the switch drops the history."""
+        self._check(self._L.trc_denoise_guide_rays(self._h, 1 if on else 0), "trc_denoise_guide_rays")
 
     def download_motion(self):
         """(H, W) structured array of trc_motion_texel (tracer_amd.dtypes.MOTION_DTYPE): the plane the last trc_denoise used."""
