@@ -17,11 +17,12 @@ CXXFLAGS  := -std=c++17 -O2 -fPIC -Wall -Wextra -ffp-contract=off -Iinclude
 HIPFLAGS  := -std=c++17 -O3 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -Iinclude -Itracer_amd/csrc \
              -Wall -Wno-unused-function
 
-HOST_SRC  := tracer_amd/host/bvh_builder.cpp tracer_amd/host/scene.cpp tracer_amd/host/mesh.cpp tracer_amd/host/pbrt_scene.cpp tracer_amd/host/png_reader.cpp tracer_amd/host/camera_rays.cpp
+HOST_SRC  := tracer_amd/host/bvh_builder.cpp tracer_amd/host/scene.cpp tracer_amd/host/mesh.cpp tracer_amd/host/pbrt_scene.cpp tracer_amd/host/png_reader.cpp tracer_amd/host/camera_rays.cpp tracer_amd/host/material_params.cpp
 HOST_HDR  := tracer_amd/host/host_math.hpp tracer_amd/host/host_scene.hpp tracer_amd/host/pbrt_text.hpp include/tracer_abi.h include/trc_sobol.h include/trc_detmath.h include/trc_raygen.h
-HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_pass.hip tracer_amd/csrc/trc_schedule.hip tracer_amd/csrc/trc_group.hip tracer_amd/csrc/trc_hooks.hip tracer_amd/csrc/trc_render_lds.hip tracer_amd/csrc/trc_render_lds_mis.hip tracer_amd/csrc/trc_render_mem.hip tracer_amd/csrc/trc_render_mem_path.hip tracer_amd/csrc/trc_render_mem_volume.hip tracer_amd/csrc/trc_sppm.hip tracer_amd/csrc/trc_lbvh.hip tracer_amd/csrc/trc_denoise.hip tracer_amd/csrc/trc_envlight.hip tracer_amd/csrc/trc_meshlight.hip tracer_amd/csrc/trc_refit.hip tracer_amd/csrc/trc_deform.hip tracer_amd/csrc/trc_normals.hip tracer_amd/csrc/trc_primitives.hip tracer_amd/csrc/trc_adaptive.hip tracer_amd/csrc/trc_camera_rays.hip \
+HIP_SRC   := tracer_amd/csrc/trc_abi.hip tracer_amd/csrc/trc_render_pass.hip tracer_amd/csrc/trc_schedule.hip tracer_amd/csrc/trc_group.hip tracer_amd/csrc/trc_hooks.hip tracer_amd/csrc/trc_render_lds.hip tracer_amd/csrc/trc_render_lds_mis.hip tracer_amd/csrc/trc_render_mem.hip tracer_amd/csrc/trc_render_mem_path.hip tracer_amd/csrc/trc_render_mem_volume.hip tracer_amd/csrc/trc_sppm.hip tracer_amd/csrc/trc_lbvh.hip tracer_amd/csrc/trc_denoise.hip tracer_amd/csrc/trc_envlight.hip tracer_amd/csrc/trc_meshlight.hip tracer_amd/csrc/trc_refit.hip tracer_amd/csrc/trc_deform.hip tracer_amd/csrc/trc_normals.hip tracer_amd/csrc/trc_primitives.hip tracer_amd/csrc/trc_adaptive.hip tracer_amd/csrc/trc_camera_rays.hip tracer_amd/csrc/trc_material_params.hip \
              $(patsubst %,tracer_amd/csrc/trc_render_%_tm.hip,lds lds_mis mem mem_path mem_volume) \
-             $(patsubst %,tracer_amd/csrc/trc_render_%.hip,rays rays_tm rays_mem rays_mem_tm)
+             $(patsubst %,tracer_amd/csrc/trc_render_%.hip,rays rays_tm rays_mem rays_mem_tm) \
+             $(patsubst %,tracer_amd/csrc/trc_render_%.hip,params params_tm params_mem params_mem_tm)
 # per translation unit: backend options that pay for ONE kernel family (profiles/r05/ab_flags*.txt: eight scheduler / sinking / LICM options
 # tried on configs 2 / 3 / 4; everything else is within +-1 % or worse).  Scheduling only: the parity suites run on this build.
 EXTRA_trc_render_mem_path := -mllvm -disable-machine-sink

@@ -42,6 +42,11 @@
 //                          orthographic through the view plane, or a 360 degree panorama from the eye (world axes, as the --hdr map's:
 //                          --projection equirect --hdr map.hdr --env-light --integrator mis is a panorama of the scene lit by that map).
 //                          With --denoise the filter follows these rays (trc_denoise_guide_rays): its G-buffer is walked along set 0
+//              [--material-params M:AX:AY[:ETA]]  material M of the scene gets the roughness pair (AX, AY) and, if given, the dielectric index
+//                          ETA instead of the reference's literals (Plastic 0.01, 0.1, 1.5; Glass 0.01, 0.01, 1.5; Metal 0.01, 0.02): every
+//                          other entry of the table keeps trc_host_default_material_params, and the frame is rendered with
+//                          TRC_FLAG_MATERIAL_PARAMS.  May be given more than once.  tracePath / traceMIS; not with --sobol, --env-light,
+//                          --mesh-lights, --aa or --projection (tracer_abi.h)
 //              [--mesh-lights]  traceMIS samples the mesh's emissive triangles as lights (TRC_FLAG_MESH_LIGHTS; with --triangle-materials a
 //                               pbrt file's emissive trianglemesh), no square light needed
 //              --albedo-map: the mesh's material (19) becomes an Image texture of that PNG (trc_host_load_png + trc_upload_textures),
@@ -74,6 +79,8 @@ int main(int argc, char** argv) {
     uint32_t W = 640, H = 360, spp = 64;
     uint32_t spin = 0, pose = 0, bend = 0, morph = 0, orbit = 0;
     uint32_t aa = 0, ray_model = TRC_RAYS_PINHOLE;
+    struct ParamEdit { uint32_t material; float ax, ay, eta; };      // --material-params (eta 0: keep the default)
+    std::vector<ParamEdit> param_edits;
     bool projection = false;
     std::vector<trc_triangle_range> hidden;
     double rebuild_ratio = 0.0;
@@ -143,6 +150,16 @@ int main(int argc, char** argv) {
             const int n = std::atoi(argv[++i]);
             if (n <= 0 || n > (int)TRC_MAX_RAY_SETS) { std::fprintf(stderr, "--aa wants a number of ray sets from 1 to %u, not %s\n", TRC_MAX_RAY_SETS, argv[i]); return 2; }
             aa = (uint32_t)n;
+        }
+        else if (a == "--material-params" && i + 1 < argc) {                    // per-material roughness / index, TRC_FLAG_MATERIAL_PARAMS
+            unsigned m = 0;
+            float ax = 0, ay = 0, eta = 0;
+            const int got = std::sscanf(argv[++i], "%u:%f:%f:%f", &m, &ax, &ay, &eta);
+            if (got < 3 || !(ax > 0) || !(ay > 0) || (got == 4 && !(eta > 1))) {
+                std::fprintf(stderr, "--material-params wants M:AX:AY[:ETA] with AX, AY > 0 and ETA > 1, not %s\n", argv[i]);
+                return 2;
+            }
+            param_edits.push_back(ParamEdit{m, ax, ay, got == 4 ? eta : 0.0f});
         }
         else if (a == "--projection" && i + 1 < argc) {                         // the projection of the camera-ray sets
             const std::string m = argv[++i];
@@ -240,6 +257,17 @@ int main(int argc, char** argv) {
         trc_host_scene_triangle_materials(hs, &tm, &n_tm);
         if (n_tm) CHECK(trc_upload_triangle_materials(ctx, tm, n_tm));
     }
+    if (!param_edits.empty()) {                   // the reference's literals per material, then the entries the command line names
+        std::vector<trc_material_params> table(scene.n_material);
+        for (uint32_t m = 0; m < scene.n_material; ++m) trc_host_default_material_params(scene.materials[m].type, &table[m]);
+        for (const ParamEdit& e : param_edits) {
+            if (e.material >= scene.n_material) { std::fprintf(stderr, "--material-params: the scene has %u materials, no material %u\n", scene.n_material, e.material); return 2; }
+            table[e.material].alpha_x = e.ax; table[e.material].alpha_y = e.ay;
+            if (e.eta != 0.0f) table[e.material].eta = e.eta;
+        }
+        CHECK(trc_upload_material_params(ctx, table.data(), scene.n_material));
+        std::printf("material parameters: %zu of %u entries changed\n", param_edits.size(), scene.n_material);
+    }
     std::vector<float> cloud;
     if (kind == TRC_SCENE_CORNELL_VOLUME) {
         uint32_t nx = 100, ny = 100, nz = 40;
@@ -298,6 +326,7 @@ int main(int argc, char** argv) {
     if (sobol) prm.flags |= TRC_FLAG_SOBOL;      // pbrt::SobolSampler instead of the random sampler (Render.metal:529-530)
     if (mesh_lights) prm.flags |= TRC_FLAG_MESH_LIGHTS;   // the mesh's emissive triangles as area-sampled lights of traceMIS
     if (env_light) prm.flags |= TRC_FLAG_ENV_LIGHT;  // the --hdr map as an importance-sampled light of traceMIS
+    if (!param_edits.empty()) prm.flags |= TRC_FLAG_MATERIAL_PARAMS;      // the lobes read the table uploaded above
     if (aa || projection) {                      // camera-ray sets made on the device from the camera; every render below reads them
         const uint32_t n_sets = aa ? aa : 1u;
         std::vector<float> offsets(2 * (size_t)n_sets, 0.0f);

@@ -79,7 +79,10 @@ extern "C" {
  *     tiles that have settled; with no mask set and no adaptive call made nothing changes; additions only)
  *     added under 13, the number stays: TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT is accepted (traceMIS: the map as a light under camera-ray
  *     sets; it returned TRC_ERR_UNSUPPORTED before) and trc_denoise_guide_rays (the SVGF G-buffer walked along the ray sets; opt-in, off by
- *     default); no unflagged launch and no unguided trc_denoise changes */
+ *     default); no unflagged launch and no unguided trc_denoise changes
+ *     added under 13, the number stays: TRC_FLAG_MATERIAL_PARAMS, trc_material_params, trc_upload_material_params,
+ *     trc_download_material_params, trc_host_default_material_params (per-material roughness, dielectric index and conductor eta / k read
+ *     from a table of the context by kernels of their own; without the flag nothing changes; additions only) */
 #define TRC_ABI_VERSION 13
 
 /* ------------------------------------------------------------------ */
@@ -411,6 +414,30 @@ enum trc_integrator {
    - trc_denoise follows the rays where trc_denoise_guide_rays is on ("A denoiser that follows the rays" below); with it off its
      G-buffer is the camera's: right for TRC_RAYS_PINHOLE sets, up to the sub-pixel offset, and wrong for any other rays.
    - LIMIT: the SPPM camera pass knows nothing of the rays; TRC_FLAG_MESH_LIGHTS is refused under the flag. */
+#define TRC_FLAG_MATERIAL_PARAMS 256u /* the lobe parameters the reference writes as literals -- the roughness pair, the dielectric
+                                       index, the conductor's eta and k -- are read per material from the context's table ("Material
+                                       parameters" below: trc_upload_material_params).  Without the flag nothing changes: frames, RNG
+                                       texture, stats, timing and memory are the unflagged library's.
+   - A flagged sample is the unflagged sample step by step with those literals replaced by entry rec.material of the table: the same
+     draws in the same order, the reference's expressions on the same operands in the same order.  Replaced: the roughness pair of the
+     material's microfacet distribution (Plastic's specular lobe and both Glass lobes: Beckmann; Metal: Trowbridge-Reitz), each used
+     as max(0.001f, a); the 1.5 of Plastic's and Glass's reflection Fresnel term and Glass's etaB (etaA stays 1, and the transmission
+     lobe's own Fresnel term stays FresnelDielectric(etaA)); Metal's eta and k.  Kept as literals: Plastic's kd / ks weights, Glass's
+     kr / kt = 0.98, the lobe-pick ratios.  A Lambert vertex, an emitter and the diffuse half of Plastic read nothing of the table.
+   - Where the unflagged kernels use a form that holds for the literals only, the flagged kernels use the general form, correctly
+     rounded: a quotient by alpha * alpha is the division x / (alpha * alpha); the conductor Fresnel term is the general one; the
+     index is the table's.  So with a table of trc_host_default_material_params per material the frame, the RNG texture and
+     trc_stats.rays / paths / shaded are the unflagged call's, bit for bit (exact build).
+   - And k calls of 1 sample equal one call of k samples, so launches of few samples are coalesced as without the flag (the flag
+     is part of what "continues" a kept launch).
+   - Accepted with TRC_INTEGRATOR_PATH and TRC_INTEGRATOR_MIS, with or without active image textures, with or without
+     trc_upload_triangle_materials, on trees staged in LDS or read from memory, with tile_rank / tile_nranks, under a tile mask and in
+     trc_render_adaptive.  TRC_ERR_UNSUPPORTED, nothing rendered: no table in force; TRC_INTEGRATOR_VOLUME; TRC_FLAG_SOBOL,
+     TRC_FLAG_COLLECT_STATS, TRC_FLAG_ENV_LIGHT, TRC_FLAG_MESH_LIGHTS or TRC_FLAG_CAMERA_RAYS; a view_height that names a stack
+     (non-zero and below H).
+   - A flagged launch runs kernels of its own, one pixel block per one-wavefront workgroup: no strips, persistent workgroups or
+     dense kernel, and no primary replay.  A change of the flag, or a new table, drops the recorded block costs of the launch planner.
+   - LIMIT: SPPM and trc_denoise do not know the table; the pbrt reader does not fill one. */
 #define TRC_FLAG_COLLECT_STATS  1u  /* run the instrumented kernel variant: exact
                                        N_descend / N_return / leaf-test counters.  Not with an active image texture
                                        (trc_upload_textures): TRC_ERR_UNSUPPORTED. */
@@ -1336,6 +1363,30 @@ trc_status trc_generate_camera_rays(trc_ctx* ctx, const trc_ray_gen* g);
 trc_status trc_download_camera_rays(trc_ctx* ctx, uint32_t set, trc_ray* out /* W*H */);
 trc_status trc_clear_camera_rays(trc_ctx* ctx);
 
+/* ------------------------------------------------------------------ */
+/* Material parameters (TRC_FLAG_MATERIAL_PARAMS; tracer_amd/csrc/trc_material_params.hip, trc_render_params.hpp) */
+/* ------------------------------------------------------------------ */
+/* One record per material of the scene, in the order of trc_scene_view.materials.  The table belongs to the context and to the scene it
+ * was uploaded for: every trc_upload_scene* drops it; trc_update_vertices and the other animation calls, trc_rebuild_tree,
+ * trc_set_triangle_visibility, trc_upload_triangle_materials, trc_upload_textures and trc_resize keep it.  The scene blob does not change.
+ * What a render does with it: TRC_FLAG_MATERIAL_PARAMS above.  Fields a material's type does not use are validated and never read.
+ *
+ * trc_upload_material_params(ctx, p, n_material): n_material must be the scene's; (NULL, 0) leaves no table in force.
+ * trc_download_material_params: what was uploaded (TRC_ERR_INVALID_ARG with no table in force or another n_material).
+ * Errors.  TRC_ERR_NO_SCENE before a scene upload; TRC_ERR_INVALID_ARG, nothing changed: n_material not the scene's, a field that is not
+ * finite, alpha_x or alpha_y <= 0, eta <= 1, a component of metal_eta or metal_k <= 0, a non-NULL table with n_material 0 or the
+ * reverse.  TRC_ERR_OOM leaves the previous table in force. */
+typedef struct trc_material_params {      /* 48 bytes, three float4 */
+    float alpha_x, alpha_y;   /* roughness pair of the material's microfacet distribution; each used as max(0.001f, a), as the
+                                 reference's constructors clamp (MicrofacetBXDF.h:164, 306-309) */
+    float eta;                /* dielectric index: Plastic's and Glass's reflection Fresnel term, Glass's etaB */
+    float _pad0;
+    float metal_eta[3]; float _pad1;      /* Metal: FresnelConductor's eta ... */
+    float metal_k[3];   float _pad2;      /* ... and k */
+} trc_material_params;
+trc_status trc_upload_material_params(trc_ctx* ctx, const trc_material_params* p, uint32_t n_material);
+trc_status trc_download_material_params(trc_ctx* ctx, trc_material_params* out, uint32_t n_material);
+
 /* developer diagnostic: the pixel blocks of the last trc_render (x | y << 16, in units of the block edge 1 << *blk_shift)
  * and the duration each one's wavefront measured per sample (shader clocks / (4 spp) -- the sort key of the adaptive launch order); with
  * strips (spp < 8) the costs are per strip; a block that ran in parts (four 4x4 quarters, some of them as four 2x2
@@ -1542,6 +1593,11 @@ trc_status trc_host_generate_camera_rays(const trc_Camera* camera, uint32_t W, u
 /* n sub-pixel offsets for trc_ray_gen.offsets: offset k = (radical inverse base 2, radical inverse base 3) of k + 1, each the exact fraction
  * rounded once to binary32 (a value that rounds to 1 is stored as the largest float below 1), all in [0, 1) */
 void trc_host_halton_offsets(uint32_t n, float* out /* 2 n */);
+/* The reference's literals for a material type (MicrofacetBXDF.h:438-455, 514-530, 576-586): Plastic alpha (0.01, 0.1), eta 1.5;
+ * Glass (0.01, 0.01), 1.5; Metal (0.01, 0.02), metal_eta (0.18, 0.15, 0.81), metal_k (1, 1, 1).  Fields a type does not use, and every
+ * other type, take Plastic's values and metal_eta / metal_k Metal's: a table made of these is valid, and a render under
+ * TRC_FLAG_MATERIAL_PARAMS with it is the unflagged render. */
+void trc_host_default_material_params(int32_t material_type, trc_material_params* out);
 
 /* Scene assembly in the reference's order (AAPLRenderer.mm:213-246,459-468,
  * 513-610): prepareCubeList (materials 0-2), prepareCornellBox (3-6),
@@ -1728,6 +1784,7 @@ TRC_SA(sizeof(trc_Square) == 272 && offsetof(trc_Square, axis_j) == 1 && offseto
 TRC_SA(sizeof(trc_Cube) == 240 && offsetof(trc_Cube, normal_matrix) == 64 && offsetof(trc_Cube, inverse_matrix) == 128 &&
        offsetof(trc_Cube, box) == 192 && offsetof(trc_Cube, material) == 224, "Cube");
 TRC_SA(sizeof(trc_TriangleVertex) == 32, "TriangleVertex");
+TRC_SA(sizeof(trc_material_params) == 48 && offsetof(trc_material_params, metal_eta) == 16 && offsetof(trc_material_params, metal_k) == 32, "material_params");
 TRC_SA(sizeof(trc_pose) == 144 && offsetof(trc_pose, model_matrix) == 16 && offsetof(trc_pose, normal_matrix) == 80, "pose");
 TRC_SA(sizeof(trc_skin_influence) == 32 && offsetof(trc_skin_influence, weight) == 16, "skin_influence");
 TRC_SA(sizeof(trc_skin_bone) == 128 && offsetof(trc_skin_bone, normal_matrix) == 64, "skin_bone");

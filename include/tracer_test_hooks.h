@@ -102,7 +102,18 @@ trc_status trc_debug_last_kernel(trc_ctx* ctx, trc_kernel_choice* out);
 /* ... and whether that launch ran a kernel of TRC_FLAG_CAMERA_RAYS (tracer_abi.h): *used = 1, else 0.  Such a launch reports shape 0 and
  * variant 0 or 3 above; its kernels have tables of their own, which trc_kernel_choice does not describe. */
 trc_status trc_debug_last_camera_rays(trc_ctx* ctx, uint32_t* used);
+/* ... or a kernel of TRC_FLAG_MATERIAL_PARAMS (tracer_abi.h): *used = 1, else 0.  Such a launch reports shape 0 and variant 0 or 3 too. */
+trc_status trc_debug_last_material_params(trc_ctx* ctx, uint32_t* used);
 
+/* test hook of TRC_FLAG_MATERIAL_PARAMS: the render kernels' parametrised lobes (tracer_amd/csrc/dev_bsdf.hpp), one lane per input in
+ * the order given, 256 lanes per workgroup, so that the order of the inputs decides which materials share a wavefront.  Input i has
+ * material type type[i], colour color[3 i ..], parameters params[i], wo[3 i ..] and uu[2 i ..].  op 0: Material::S_F with bxPDF preset
+ * to pdf_init; out receives 7 floats per input: wi, f, pdf (wi is not read).  op 1: Material::F and its pdf for the pair (wo, wi[3 i ..]);
+ * out receives 4 floats per input: f, pdf.  op 2: op 0 with sample11 evaluating each exp, log and erf_inv once (TRC_SAMPLE11_ONCE 7, the text
+ * of the units of LDS-resident trees; op 0 runs the reference's).  The parameters are not validated. */
+trc_status trc_material_params_test(trc_ctx* ctx, uint32_t op, const uint32_t* type, const float* color /* 3 n */,
+                                    const trc_material_params* params /* n */, const float* wo /* 3 n */, const float* wi /* 3 n, op 1 */,
+                                    const float* uu /* 2 n */, size_t n, float pdf_init, float* out /* 7 n or 4 n */);
 
 /* test hook of the LDS plans (trc_render_pass.hip: resident_workgroups): how the kernel of the last render launch sits on a CU.
  * cu_count: CUs of the device; block: threads per workgroup; waves: wavefronts per SIMD of the kernel's launch bounds; lds_bytes: dynamic

@@ -36,6 +36,7 @@ FLAG_SMALL_BLOCKS, FLAG_LARGE_BLOCKS = 8, 16
 FLAG_ENV_LIGHT = 32
 FLAG_MESH_LIGHTS = 64
 FLAG_CAMERA_RAYS = 128
+FLAG_MATERIAL_PARAMS = 256
 # enum trc_ray_model (trc_generate_camera_rays)
 RAYS_PINHOLE, RAYS_ORTHOGRAPHIC, RAYS_EQUIRECT = 0, 1, 2
 TRC_MAX_RAY_SETS = 1024
@@ -232,6 +233,12 @@ class RayGen(C.Structure):
     _fields_ = [("model", C.c_uint32), ("n_sets", C.c_uint32), ("offsets", C.POINTER(C.c_float))]
 
 
+class MaterialParams(C.Structure):
+    """trc_material_params: one material's entry of the table of TRC_FLAG_MATERIAL_PARAMS"""
+    _fields_ = [("alpha_x", C.c_float), ("alpha_y", C.c_float), ("eta", C.c_float), ("_pad0", C.c_float),
+                ("metal_eta", C.c_float * 3), ("_pad1", C.c_float), ("metal_k", C.c_float * 3), ("_pad2", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("hit", C.c_int32), ("pType", C.c_int32), ("pIndex", C.c_uint32), ("t", C.c_float),
                 ("p", C.c_float * 3), ("gn", C.c_float * 3), ("sn", C.c_float * 3), ("uv", C.c_float * 2),
@@ -324,7 +331,7 @@ class Stats(C.Structure):
 
 
 _EXPECTED_SIZES = {float2: 8, float3: 16, float4x4: 64, AABB: 32, BVH: 64, Sphere: 272, Square: 272, Cube: 240,
-                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, RayGen: 16, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32, TriangleRange: 12, AdaptiveParams: 16, AdaptiveReport: 24,
+                   TriangleVertex: 32, Pose: 144, PrimitiveRanges: 48, SkinInfluence: 32, SkinBone: 128, MorphDelta: 24, TextureInfo: 32, Material: 64, Camera: 176, Ray: 32, RayGen: 16, MaterialParams: 48, Params: 32, GBufferTexel: 32, MotionTexel: 16, DenoiseParams: 32, TreeCost: 32, TriangleRange: 12, AdaptiveParams: 16, AdaptiveReport: 24,
                    PhotonRecord: 80, CameraRecord: 112, Complex: 96}
 for _t, _n in _EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, f"{_t.__name__}: ctypes size {C.sizeof(_t)} != ABI size {_n}"
@@ -348,11 +355,13 @@ DEVICE_SYMBOLS = [
     "trc_set_tile_mask", "trc_download_tile_mask", "trc_tile_snapshot", "trc_tile_error", "trc_download_tile_error",
     "trc_adaptive_default_params", "trc_render_adaptive", "trc_download_tile_samples",
     "trc_upload_camera_rays", "trc_generate_camera_rays", "trc_download_camera_rays", "trc_clear_camera_rays",
+    "trc_upload_material_params", "trc_download_material_params",
 ]
 # include/tracer_test_hooks.h: exported by libtracer_amd_hooks.so only (the product's sources + -DTRC_TEST_HOOKS)
 HOOK_SYMBOLS = ["trc_debug_profile", "trc_sppm_hash_cells", "trc_div_by_test", "trc_unary_test", "trc_debug_denoise_state", "trc_texture_sample_test",
                 "trc_debug_env_tables", "trc_env_light_test", "trc_debug_mesh_light_tables", "trc_mesh_light_test", "trc_debug_last_kernel",
-                "trc_debug_last_residency", "trc_material_s_f_test", "trc_debug_last_camera_rays", "trc_sample11_test"]
+                "trc_debug_last_residency", "trc_material_s_f_test", "trc_debug_last_camera_rays", "trc_sample11_test",
+                "trc_debug_last_material_params", "trc_material_params_test"]
 HOST_SYMBOLS = [
     "trc_host_build_node", "trc_host_build_tree", "trc_host_build_tree_flags", "trc_host_tree_depth", "trc_host_make_camera",
     "trc_host_prepare_camera", "trc_host_fill_rng", "trc_host_scene_create", "trc_host_scene_create_leaves", "trc_host_scene_destroy",
@@ -361,5 +370,5 @@ HOST_SYMBOLS = [
     "trc_host_load_density_pbrt", "trc_host_free", "trc_host_write_png", "trc_host_sobol_matrices32",
     "trc_host_sobol_interval_tables", "trc_host_load_png", "trc_host_scene_load_pbrt_flags", "trc_host_scene_triangle_materials",
     "trc_host_make_sphere", "trc_host_make_square", "trc_host_make_cube",
-    "trc_host_generate_camera_rays", "trc_host_halton_offsets",
+    "trc_host_generate_camera_rays", "trc_host_halton_offsets", "trc_host_default_material_params",
 ]

@@ -4,7 +4,8 @@
 // MatteBXDF.hh:6-22, MicrofacetBXDF.h:7-586, Texture.hh:17-43, Material.hh:77-146.
 // The reference hard-codes every lobe parameter in its create*() functions
 // (MicrofacetBXDF.h:438-455,514-530,576-586); they are compile-time constants here, so the
-// material switch carries no per-material parameter loads beyond type + albedo.
+// material switch carries no per-material parameter loads beyond type + albedo.  (TRC_FLAG_MATERIAL_PARAMS: the same lobes with those
+// parameters read from a table, at the end of this file; the kernels of trc_render_params.hpp alone use them.)
 #pragma once
 
 #include "dev_prof.hpp"
@@ -745,6 +746,15 @@ struct Microfacet {
         d.by_ay2.c = metal ? mid.c : plastic ? rough.c : smooth.c; d.by_ay2.y = metal ? mid.y : plastic ? rough.y : smooth.y;
         return d;
     }
+    // TRC_FLAG_MATERIAL_PARAMS: any roughness pair, clamped as the reference's constructors clamp it; by_*.c is alpha^2, and by_*.y is
+    // not a reciprocal anybody may use -- only D_general below divides by such a lobe's squares
+    TRC_DEV static Microfacet make_lobe(bool metal, float ax, float ay) {
+        Microfacet d; d.tr = metal;
+        d.alpha_x = fmaxf(0.001f, ax); d.alpha_y = fmaxf(0.001f, ay);
+        d.by_ax2.c = d.alpha_x * d.alpha_x; d.by_ax2.y = 0.0f;
+        d.by_ay2.c = d.alpha_y * d.alpha_y; d.by_ay2.y = 0.0f;
+        return d;
+    }
     TRC_DEV float ax() const { return alpha_x; }
     TRC_DEV float ay() const { return alpha_y; }
 
@@ -774,6 +784,22 @@ struct Microfacet {
         const Phi ph = phi_of(wh);
         float qc, qs;                                     // cos2_phi / (ax * ax), sin2_phi / (ay * ay)
         div_const2(ph.c * ph.c, by_ax2, ph.s * ph.s, by_ay2, qc, qs);
+        if (tr) {
+            float e = (qc + qs) * tan2Theta;
+            return rcp1(kPi * ax() * ay() * sqr(1 + e) * cos4Theta);
+        }
+        return dm_expf(-tan2Theta * (qc + qs)) /
+               (kPi * ax() * ay() * cos4Theta);
+    }
+    // D with the two quotients as the divisions the reference writes, correctly rounded: for any roughness pair (DivConst's pairs are
+    // each tested exact against this form, so a lobe of the literals gives D's bits)
+    TRC_DEV float D_general(F3 wh) const {
+        float tan2Theta = tan2_theta(wh);
+        if (is_inf(tan2Theta)) return 0.;
+        const float cos4Theta = cos2_theta(wh) * cos2_theta(wh);
+        if (tr && cos4Theta < 1e-16f) return 0;
+        const Phi ph = phi_of(wh);
+        const float qc = (ph.c * ph.c) / by_ax2.c, qs = (ph.s * ph.s) / by_ay2.c;
         if (tr) {
             float e = (qc + qs) * tan2Theta;
             return rcp1(kPi * ax() * ay() * sqr(1 + e) * cos4Theta);
@@ -1079,6 +1105,225 @@ TRC_DEV F3 material_F(int type, F3 color, F3 wo, F3 wi, F2 uu, float& pdf) {
     }
     pdf = 0;
     return f3(0);
+}
+
+// ---------------------------------------------------------------- TRC_FLAG_MATERIAL_PARAMS: the lobes with their parameters read
+// What the reference writes as literals in its create*() functions, per material (tracer_abi.h: trc_material_params, 48 bytes = three
+// float4): the roughness pair, the dielectric index (Plastic's and Glass's reflection Fresnel term, Glass's etaB; etaA stays 1), Metal's
+// eta and k.  The functions below are material_S_F (its stream form) and material_F with those literals replaced by a LobeParams and
+// every form that holds for the literals only replaced by the general one, correctly rounded: DivConst's quotients by the divisions
+// (Microfacet::D_general), fr_conductor<true> by fr_conductor<false>, the folded etaA / etaB by the quotient.  Each of those shortcuts is
+// tested exact against its general form (trc_unary_test, trc_div_by_test), so LobeParams of the literals give the unflagged bits.
+// Plastic's kd / ks, Glass's kr / kt = 0.98 and the lobe-pick ratios stay literals.
+struct LobeParams { float alpha_x, alpha_y, eta; F3 metal_eta, metal_k; };
+// entry `material` of the table, as three 16-byte loads
+TRC_DEV LobeParams lobe_params(const float4* table, uint32_t material) {
+    const float4* const p = table + 3u * (size_t)material;
+    const float4 a = p[0], e = p[1], k = p[2];
+    LobeParams lp;
+    lp.alpha_x = a.x; lp.alpha_y = a.y; lp.eta = a.z;
+    lp.metal_eta = f3(e.x, e.y, e.z); lp.metal_k = f3(k.x, k.y, k.z);
+    return lp;
+}
+
+// microfacet_finish with the parameters read: etaB and the reflection Fresnel term's index are lp.eta, Metal's Fresnel term is the
+// general conductor form over lp.metal_eta / lp.metal_k, D is D_general.  Everything else is microfacet_finish line by line.
+TRC_DEV F3 microfacet_finish_params(const Microfacet& d, const LobeParams& lp, bool refl, float R, F3 wo, F3 wh, F3& wi_out, float& pdf_out) {
+    const float etaA = 1.0f, etaB = lp.eta;
+    bool live;                    // got past the early-outs of S_F: pdf_out will be written
+    bool pdf_live = false;        // ... with a non-trivial value
+    bool f_live = false;          // F reaches its D * G * Fresnel expression
+    F3 wi = wi_out, whA = wh, whB = wh;
+    float eta = 0, fres_cos = 0, fres_eta = etaB;
+    // ---- (A)
+    if (refl) {
+        live = !(dot(wo, wh) <= 0);
+        if (live) {
+            wi = reflect(wo, wh);
+            if (d.tr) wi_out = wi;            // MicroRefl::S_F assigns its wi before the second early-out
+            live = !(wo.z * wi.z <= 0);
+        }
+        if (live) {
+            pdf_live = true;
+            const float cosThetaO = abs_cos_theta(wo), cosThetaI = abs_cos_theta(wi);
+            F3 sum = wi + wo;
+            f_live = !(cosThetaI == 0 || cosThetaO == 0) && !(sum.x == 0 && sum.y == 0 && sum.z == 0);
+            if (f_live) {
+                whB = normalize(sum);
+                const float d001 = whB.x * 0.0f + whB.y * 0.0f + whB.z * 1.0f;      // Faceforward(wh, (0,0,1))
+                const F3 whf = (d001 < 0.f) ? -whB : whB;
+                fres_cos = dot(wi, whf);
+                fres_eta = etaB;
+            }
+        }
+    } else {
+        live = !(dot(wo, wh) < 0);
+        if (live) live = refract(wo, wh, cos_theta(wo) > 0 ? (etaA / etaB) : (etaB / etaA), wi);
+        if (live) {
+            eta = cos_theta(wo) > 0 ? (etaB / etaA) : (etaA / etaB);
+            const bool same_side = wo.z * wi.z > 0;
+            whA = normalize(wo + wi * eta);
+            const bool backfacing = dot(wo, whA) * dot(wi, whA) > 0;               // same truth value for -whA
+            pdf_live = !same_side && !backfacing;
+            whB = whA;
+            if (whB.z < 0) whB = -whB;
+            f_live = pdf_live && !(cos_theta(wi) == 0 || cos_theta(wo) == 0);
+            fres_cos = dot(wo, whB);
+            fres_eta = etaA;
+        }
+    }
+    // ---- (B)
+    float D_A = 0, D_B = 0, lam_o = 0, lam_i = 0;
+    F3 fres = f3(0);
+    if (pdf_live) {
+        lam_o = d.lambda(wo);
+        D_A = d.D_general(whA);
+        D_B = D_A;
+        if (refl && f_live) D_B = d.D_general(whB);
+        if (f_live) {
+            lam_i = d.lambda(wi);
+            if (d.tr) fres = fr_conductor(fabsf(fres_cos), lp.metal_eta, lp.metal_k);
+            else fres = f3(fr_dielectric(fres_cos, fres_eta));
+        }
+    }
+    // ---- (C)
+    F3 out = f3(0);
+    if (live) {
+        wi_out = wi;
+        const float G1 = rcp1(1 + lam_o);
+        const float G = rcp1(1 + lam_o + lam_i);
+        if (refl) {
+            const float dwh = dot(wo, wh);
+            const float num = d.tr ? dwh : D_A * G1 * fabsf(dwh), den = d.tr ? cos_theta(wo) : abs_cos_theta(wo);
+            const float q = num / den;
+            const float dist_pdf = d.tr ? D_A * G1 * fabsf(q) : q;
+            pdf_out = dist_pdf / (4 * dot(wo, wh));
+            if (f_live) {
+                const float cosThetaO = abs_cos_theta(wo), cosThetaI = abs_cos_theta(wi);
+                out = f3(R) * D_B * G * fres / (4 * cosThetaI * cosThetaO);
+            }
+        } else {
+            float p = 0;
+            if (pdf_live) {
+                const float sqrtDenom = dot(wo, whA) + eta * dot(wi, whA);
+                const float dwh_dwi = fabsf((eta * eta * dot(wi, whA)) / (sqrtDenom * sqrtDenom));
+                const float dist_pdf = D_A * G1 * fabsf(dot(wo, whA)) / abs_cos_theta(wo);
+                p = dist_pdf * dwh_dwi;
+            }
+            pdf_out = p;
+            if (f_live) {
+                const float cosThetaO = cos_theta(wo), cosThetaI = cos_theta(wi);
+                const float sqrtDenom = dot(wo, whB) + eta * dot(wi, whB);
+                const float factor = 1;
+                out = (f3(1.0f) - fres) * f3(0.98f) *
+                      fabsf(D_B * G * eta * eta * fabsf(dot(wi, whB)) * fabsf(dot(wo, whB)) * factor * factor /
+                            (cosThetaI * cosThetaO * sqrtDenom * sqrtDenom));
+            }
+        }
+    }
+    return out;
+}
+
+// Material::S_F with the parameters read: material_S_F's stream form (one instruction stream for the four microfacet lobes) whatever
+// TRC_MICROFACET_STREAM says.  A lane fetches its entry where the lobe is built: a Lambert vertex and Plastic's diffuse half load nothing.
+template <int ONCE = TRC_SAMPLE11_ONCE>
+TRC_DEV F3 material_S_F_params(int type, F3 color, const float4* table, uint32_t material, F3 wo, F3& wi, F2 uu, float& pdf) {
+    const bool plastic = type == kMatPlastic, glass = type == kMatGlass, metal = type == kMatMetal;
+    F3 out = f3(0);
+    if (type == kMatLambert || (plastic && uu.x < 0.5f)) {
+        F2 u2 = uu;
+        if (plastic) u2.x *= 2;
+        const float v = Lambert::S_F(wo, wi, u2, pdf);
+        out = plastic ? color * (f3(0.35f, 0.12f, 0.48f) * v) : color * f3(v);
+    } else if (metal || plastic || glass) {
+        const float ratio = 0.25f;
+        const bool refl = metal || plastic || uu.x < ratio;
+        F2 u2 = uu;
+        if (metal) { }                                           // MetalMaterial::S_F hands uu on as it is
+        else if (plastic) { u2.x -= 0.5f; u2.x *= 2.0f; }
+        else if (refl) u2.x = uu.x / ratio;
+        else u2.x = (uu.x - ratio) / (1.0f - ratio);
+        const LobeParams lp = lobe_params(table, material);
+        const Microfacet d = Microfacet::make_lobe(metal, lp.alpha_x, lp.alpha_y);
+        F3 lobe = f3(0);
+        if (wo.z != 0) {
+            const F3 wh = d.template sample_wh<ONCE>(wo, u2);
+            lobe = microfacet_finish_params(d, lp, refl, (metal || plastic) ? 1.0f : 0.98f, wo, wh, wi, pdf);
+        }
+        out = plastic ? color * (f3(0.2f) * lobe) : color * lobe;
+    }
+    return out;
+}
+
+// Material::F with the parameters read (pdf = bx.PDF, value = color * bx.F): MicrofacetReflection over Trowbridge-Reitz with the
+// conductor term (Metal), over Beckmann with the dielectric term (Plastic's specular lobe, Glass's reflection lobe) and
+// MicrofacetTransmission over Beckmann (Glass), each as material_F's lobes state them, over one Microfacet with the family per lane
+TRC_DEV F3 material_F_params(int type, F3 color, const float4* table, uint32_t material, F3 wo, F3 wi, F2 uu, float& pdf) {
+    const bool plastic = type == kMatPlastic, glass = type == kMatGlass, metal = type == kMatMetal;
+    if (type == kMatLambert || (plastic && uu.x < 0.5f)) {           // PlasticMaterial::F/PDF, :469-495
+        pdf = Lambert::pdf(wo, wi);
+        const float v = Lambert::F(wo, wi);
+        return plastic ? color * (f3(0.35f, 0.12f, 0.48f) * v) : color * f3(v);
+    }
+    if (!(metal || plastic || glass)) { pdf = 0; return f3(0); }
+    const float ratio = 0.25f;
+    const LobeParams lp = lobe_params(table, material);
+    const Microfacet d = Microfacet::make_lobe(metal, lp.alpha_x, lp.alpha_y);
+    if (metal || plastic || uu.x < ratio) {                          // MicrofacetReflection::PDF / F, MicrofacetBXDF.h:15-34, 50-57
+        float p = 0;
+        if (!(wo.z * wi.z <= 0)) {
+            const F3 wh = normalize(wo + wi);
+            const float G1 = rcp1(1 + d.lambda(wo));
+            const float dist_pdf = metal ? d.D_general(wh) * G1 * fabsf(dot(wo, wh) / cos_theta(wo))
+                                         : d.D_general(wh) * G1 * fabsf(dot(wo, wh)) / abs_cos_theta(wo);
+            p = dist_pdf / (4 * dot(wo, wh));
+        }
+        pdf = (metal || plastic) ? p : ratio * p;
+        const float R = (metal || plastic) ? 1.0f : 0.98f;
+        F3 f = f3(0);
+        const float cosThetaO = abs_cos_theta(wo), cosThetaI = abs_cos_theta(wi);
+        F3 wh = wi + wo;
+        if (!(cosThetaI == 0 || cosThetaO == 0) && !(wh.x == 0 && wh.y == 0 && wh.z == 0)) {
+            wh = normalize(wh);
+            const float d001 = wh.x * 0.0f + wh.y * 0.0f + wh.z * 1.0f;          // Faceforward(wh, (0,0,1))
+            const F3 whf = (d001 < 0.f) ? -wh : wh;
+            const float c = dot(wi, whf);
+            const F3 Fres = metal ? fr_conductor(fabsf(c), lp.metal_eta, lp.metal_k) : f3(fr_dielectric(c, lp.eta));
+            const float G = rcp1(1 + d.lambda(wo) + d.lambda(wi));
+            f = f3(R) * d.D_general(wh) * G * Fres / (4 * cosThetaI * cosThetaO);
+        }
+        return plastic ? color * (f3(0.2f) * f) : color * f;
+    }
+    // MicrofacetTransmission::PDF / F, :83-115, as GlassMaterial instantiates it: T = 0.98, etaA = 1, etaB = lp.eta, factor 1
+    const float etaA = 1.0f, etaB = lp.eta;
+    const float eta = cos_theta(wo) > 0 ? (etaB / etaA) : (etaA / etaB);
+    float p = 0;
+    if (!(wo.z * wi.z > 0)) {
+        const F3 wh = normalize(wo + wi * eta);
+        if (!(dot(wo, wh) * dot(wi, wh) > 0)) {
+            const float sqrtDenom = dot(wo, wh) + eta * dot(wi, wh);
+            const float dwh_dwi = fabsf((eta * eta * dot(wi, wh)) / (sqrtDenom * sqrtDenom));
+            const float dist_pdf = d.D_general(wh) * rcp1(1 + d.lambda(wo)) * fabsf(dot(wo, wh)) / abs_cos_theta(wo);
+            p = dist_pdf * dwh_dwi;
+        }
+    }
+    pdf = (1 - ratio) * p;
+    F3 f = f3(0);
+    const float cosThetaO = cos_theta(wo), cosThetaI = cos_theta(wi);
+    if (!(wo.z * wi.z > 0) && !(cosThetaI == 0 || cosThetaO == 0)) {
+        F3 wh = normalize(wo + wi * eta);
+        if (wh.z < 0) wh = -wh;
+        if (!(dot(wo, wh) * dot(wi, wh) > 0)) {
+            const F3 Fres = f3(fr_dielectric(dot(wo, wh), etaA));
+            const float sqrtDenom = dot(wo, wh) + eta * dot(wi, wh);
+            const float factor = 1;
+            const float G = rcp1(1 + d.lambda(wo) + d.lambda(wi));
+            f = (f3(1.0f) - Fres) * f3(0.98f) *
+                fabsf(d.D_general(wh) * G * eta * eta * fabsf(dot(wi, wh)) * fabsf(dot(wo, wh)) * factor * factor /
+                      (cosThetaI * cosThetaO * sqrtDenom * sqrtDenom));
+        }
+    }
+    return color * f;
 }
 
 }  // namespace trcdev

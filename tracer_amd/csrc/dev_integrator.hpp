@@ -169,6 +169,23 @@ template <bool TEX> TRC_DEV const TexTable* ctx_tex(const PathCtx& cx) {
 template <bool TEX, Light LIGHT> TRC_DEV const LightTables<LIGHT>* ctx_light(const PathCtx& cx) {
     if constexpr (LIGHT != Light::None) return &static_cast<const PathCtxOf<TEX, LIGHT>&>(cx).light; else return nullptr;
 }
+// TRC_FLAG_MATERIAL_PARAMS (PARAMS instantiations: trc_render_params.hpp): the table of trc_material_params, three float4 per material,
+// behind the context of the (TEX, LIGHT) instantiation -- a struct of its own again, so that every other context keeps its layout
+template <bool TEX, Light LIGHT = Light::None> struct PathCtxParams : PathCtxOf<TEX, LIGHT> { const float4* mparams; };
+template <bool TEX, Light LIGHT, bool PARAMS> TRC_DEV const float4* ctx_mparams(const PathCtx& cx) {
+    if constexpr (PARAMS) return static_cast<const PathCtxParams<TEX, LIGHT>&>(cx).mparams; else return nullptr;
+}
+// Material::S_F / Material::F of a hit: the literals' lobes, or under PARAMS the lobes of entry rec.material of the table (dev_bsdf.hpp)
+template <bool STATS, bool TEX, Light LIGHT, bool PARAMS>
+TRC_DEV F3 hit_S_F(const PathCtx& cx, int mtype, uint32_t material, F3 color, F3 wo, F3& wi, F2 uu, float& pdf, TravCounters& cnt) {
+    if constexpr (PARAMS) return material_S_F_params(mtype, color, ctx_mparams<TEX, LIGHT, true>(cx), material, wo, wi, uu, pdf);
+    else return material_S_F<STATS>(mtype, color, wo, wi, uu, pdf, cnt);
+}
+template <bool TEX, Light LIGHT, bool PARAMS>
+TRC_DEV F3 hit_F(const PathCtx& cx, int mtype, uint32_t material, F3 color, F3 wo, F3 wi, F2 uu, float& pdf) {
+    if constexpr (PARAMS) return material_F_params(mtype, color, ctx_mparams<TEX, LIGHT, true>(cx), material, wo, wi, uu, pdf);
+    else return material_F(mtype, color, wo, wi, uu, pdf);
+}
 
 // ---------------------------------------------------------------- path state machine
 // The reference runs, per pixel and per frame, castRay -> tracePath/traceMIS (a bounce loop around
@@ -255,7 +272,7 @@ TRC_DEV void path_begin(PathState& ps, const Ray& camera_ray, uint32_t max_depth
 
 // What happens between two Scene::hit calls of tracePath (Render.metal:432-489).  Returns true when the
 // path is finished; `result` is then the sample's radiance.
-template <bool STATS, bool SOBOL = false, bool TEX = false, class COUNT = uint32_t>
+template <bool STATS, bool SOBOL = false, bool TEX = false, class COUNT = uint32_t, bool PARAMS = false>
 TRC_DEV bool path_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_shaded, F3& result) {
     if (!ps.primary) {                                               // } while ((--depth) > 0), :489
         if (--ps.depth_left <= 0) { result = ps.color; return true; }
@@ -281,7 +298,7 @@ TRC_DEV bool path_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, 
     float bxPDF = 0;                                                 // uninitialised in the reference (B-3)
     bump(n_shaded);
     prof<STATS>(cnt, kProfShade);
-    F3 attenuation = material_S_F<STATS>(mtype, hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx)), wo, wi, uu, bxPDF, cnt);
+    F3 attenuation = hit_S_F<STATS, TEX, Light::None, PARAMS>(cx, mtype, rec.material, hit_color<TEX>(cx.S, cx.sh, rec, ctx_tex<TEX>(cx)), wo, wi, uu, bxPDF, cnt);
     if (bxPDF <= 0) { result = ps.color; return true; }
     F3 wiw = (nx * wi.x + ny * wi.y) + rec.sn * wi.z;                // stw * wi
     if (wi.z < 0) ps.ray = make_ray(offset_ray(hit_origin, -rec.sn), wiw);   // transmission
@@ -438,7 +455,7 @@ TRC_DEV float grid_sample(const PathCtx& cx, const HitRec& rec, MediumHit& mi, P
 // direction would start (_origin: only directions above the surface are taken).
 // Light::Mesh: the mesh's sample (dev_meshlight.hpp) draws four more numbers; its shadow ray is the any-hit walk to the sample's distance,
 // as a square's.  Radiance keeps the reference's Le * cos convention.
-template <Light LIGHT, bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT>
+template <Light LIGHT, bool ALL_LDS, bool STATS, bool HYB, bool TEX, class COUNT, bool PARAMS = false>
 TRC_DEV void light_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters& cnt, COUNT& n_rays, COUNT& n_shaded, const F2 uu,
                        const F3 _origin, const int mtype, F3& nx, F3& ny, F3& minus_d, F3& base_color) {
     const HitRec& rec = ps.rec;
@@ -522,7 +539,7 @@ TRC_DEV void light_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters&
         const F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
         float bxPDF = 0;
         bump(n_shaded);
-        F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF) * light_term;
+        F3 weight = hit_F<TEX, LIGHT, PARAMS>(cx, mtype, rec.material, base_color, wo, wi, uu, bxPDF) * light_term;
         if (kind == 1) ps.color = ps.color + ps.ratio * (weight * power_heuristic(1, liPDF, 1, bxPDF)) / (liPDF * (1.0f - light_p(L)));
         else ps.color = ps.color + ps.ratio * (weight * env_mis_weight(liPDF, bxPDF)) / liPDF;
     }
@@ -538,7 +555,8 @@ TRC_DEV void light_nee(const PathCtx& cx, PathState& ps, Pcg& rng, TravCounters&
 // cosine lobe, else 1: the estimator of the integrand the mesh's light sample estimates -- without the reference's second
 // scat_attenuation / scat_bxPDF factor, and without rec.PDF, which only a square writes (tracer_abi.h).  A square emitter hit keeps the
 // reference's formula.  Without a light triangle (p_mesh = 0, no tables) every operation and draw is the flag-off kernel's.
-template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, Light LIGHT = Light::None, class COUNT = uint32_t>
+template <bool ALL_LDS, bool STATS, bool VOLUME = false, bool SOBOL = false, bool HYB = false, bool TEX = false, Light LIGHT = Light::None, class COUNT = uint32_t,
+          bool PARAMS = false>
 TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, TravCounters& cnt, COUNT& n_rays,
                       COUNT& n_shaded, F3& result) {
     HitRec& rec = ps.rec;
@@ -641,7 +659,7 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     F3 _origin = offset_ray(rec.p, rec.sn);
     F3 nx, ny, minus_d, base_color;
     if constexpr (LIGHT != Light::None) {
-        light_nee<LIGHT, ALL_LDS, STATS, HYB, TEX>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
+        light_nee<LIGHT, ALL_LDS, STATS, HYB, TEX, COUNT, PARAMS>(cx, ps, rng, cnt, n_rays, n_shaded, uu, _origin, mtype, nx, ny, minus_d, base_color);
     } else {
     if (pcg_float(rng) < 0.5f) square_sample(cx.S, 5, uu, _origin, lsr);
     else square_sample(cx.S, 6, uu, _origin, lsr);
@@ -673,7 +691,7 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
         F3 wi = f3(dot(nx, _ray.d), dot(ny, _ray.d), dot(rec.sn, _ray.d));
         float bxPDF = 0;
         bump(n_shaded);
-        F3 weight = material_F(mtype, base_color, wo, wi, uu, bxPDF);
+        F3 weight = hit_F<TEX, LIGHT, PARAMS>(cx, mtype, rec.material, base_color, wo, wi, uu, bxPDF);
         weight = weight * light_term;
         weight = weight * power_heuristic(1, liPDF, 1, bxPDF);
         ps.color = ps.color + _tr * ps.ratio * weight / liPDF;
@@ -684,7 +702,7 @@ TRC_DEV bool mis_step(const PathCtx& cx, PathState& ps, bool hitted, Pcg& rng, T
     float bxPDF = 0;
     F3 wo = f3(dot(nx, minus_d), dot(ny, minus_d), dot(rec.sn, minus_d));
     bump(n_shaded);
-    ps.scat_attenuation = material_S_F(mtype, base_color, wo, wi, uu, bxPDF);
+    ps.scat_attenuation = hit_S_F<false, TEX, LIGHT, PARAMS>(cx, mtype, rec.material, base_color, wo, wi, uu, bxPDF, cnt);
     ps.scat_bxPDF = bxPDF;
     if (bxPDF <= 0) { result = ps.color; return true; }
     F3 wiw = (nx * wi.x + ny * wi.y) + rec.sn * wi.z;

@@ -398,6 +398,7 @@ void trc_release_scene(trc_ctx* ctx) {
     (void)hipFree(ctx->d_vis); ctx->d_vis = nullptr;      // trc_set_triangle_visibility: the next tree defines the mask again
     ctx->has_scene = false;
     trc_mesh_light_free(ctx);
+    trc_material_params_release(ctx);      // the table of TRC_FLAG_MATERIAL_PARAMS names this scene's materials
     trc_refit_free(ctx);
     trc_denoise_scene_released(ctx);
 }

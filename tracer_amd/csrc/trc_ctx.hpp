@@ -100,6 +100,12 @@ struct KRenderRaysEnv {
     uint32_t n_sets;
 };
 
+// ... and the kernels of TRC_FLAG_MATERIAL_PARAMS (k_render_params, trc_render_params.hpp) the table of trc_material_params
+struct KRenderParams {
+    KRender kp;
+    const float4* table;                // three float4 per material, in the order of the scene's material list
+};
+
 struct KTrace {
     KScene ks;
     const trc_ray* rays;
@@ -250,6 +256,10 @@ struct trc_ctx {
     // force).  Sized by the frame: trc_release_frame.  cost_rays: the recorded block costs are a flagged launch's (drop_stale_costs)
     trc_ray* d_cam_rays = nullptr; uint32_t n_ray_sets = 0;
     bool cost_rays = false;
+    // TRC_FLAG_MATERIAL_PARAMS (trc_material_params.hip): n_mparams records of trc_material_params, one per material of the scene (null: no
+    // table in force).  Belongs to the scene: trc_release_scene.  cost_params: the recorded block costs are a flagged launch's
+    trc_material_params* d_mparams = nullptr; uint32_t n_mparams = 0;
+    bool cost_params = false;
     // ... ray_gen: which rays these are -- the next number whenever they are replaced or dropped (trc_camera_rays_release: trc_upload_camera_rays,
     // trc_generate_camera_rays, trc_clear_camera_rays, trc_resize), whatever the new ones' bits: the denoiser under trc_denoise_guide_rays compares it
     uint64_t ray_gen = 0;
@@ -283,7 +293,8 @@ struct trc_ctx {
     // launch shape (0 one block per one-wavefront workgroup, 1 strips, 2 persistent workgroups, 3 k_render_dense), the RenderVariant,
     // whether the whole tree was staged in LDS, whether the per-triangle-material twins ran, and the strip length; launches counted
     // camera_rays: it was a kernel of TRC_FLAG_CAMERA_RAYS (trc_debug_last_camera_rays)
-    struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0, camera_rays = 0; } last_kernel;
+    // material_params: it was a kernel of TRC_FLAG_MATERIAL_PARAMS (trc_debug_last_material_params)
+    struct LastKernel { uint32_t shape = 0, variant = 0, lds_resident = 0, tri_materials = 0, strip = 0, count = 0, camera_rays = 0, material_params = 0; } last_kernel;
     // ... and how that launch sits on a CU (trc_debug_last_residency): the kernel, its workgroup size and dynamic LDS, the workgroups per
     // CU its plan is for (4 x the waves of its launch bounds; the persistent workgroups' per-CU count) and the runtime's answer
     struct LastFit { const void* fn = nullptr; uint32_t block = 0, waves = 0, planned_per_cu = 0, per_cu = 0; size_t lds = 0; } last_fit;
@@ -523,6 +534,7 @@ trc_status trc_render_now(trc_ctx* ctx, const trc_params* p);
 // trc_adaptive.hip: the tile mask (null: every tile) becomes the context's; frees what trc_set_tile_mask and the estimate own (trc_release_frame)
 trc_status trc_adopt_tile_mask(trc_ctx* ctx, const uint8_t* mask, bool on_device = false);      // `mask`: trc_tile_count bytes; on_device: d_mask already holds it
 void trc_adaptive_release(trc_ctx* ctx);
+void trc_material_params_release(trc_ctx* ctx);  // trc_material_params.hip: frees the table of TRC_FLAG_MATERIAL_PARAMS (trc_release_scene); the block costs of a flagged launch go with it
 void trc_camera_rays_release(trc_ctx* ctx);      // trc_camera_rays.hip: frees the ray sets of TRC_FLAG_CAMERA_RAYS (trc_release_frame); the block costs of a flagged launch go with them
 inline uint32_t trc_tiles_x(const trc_ctx* ctx) { return (ctx->width + TRC_TILE - 1) / TRC_TILE; }
 inline uint32_t trc_tile_count(const trc_ctx* ctx) { return trc_tiles_x(ctx) * ((ctx->height + TRC_TILE - 1) / TRC_TILE); }

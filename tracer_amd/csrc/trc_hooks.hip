@@ -93,6 +93,28 @@ __global__ void __launch_bounds__(256) k_sample11_test(const uint32_t* family, f
     slopes[2 * i] = sx; slopes[2 * i + 1] = sy;
     exit_kind[i] = (uint32_t)kind;
 }
+// trc_material_params_test: material_S_F_params / material_F_params (dev_bsdf.hpp), one lane per input: lane i reads entry i of `table`
+__global__ void __launch_bounds__(256) k_material_params_test(uint32_t op, const uint32_t* type, const float* color, const float4* table, const float* wo,
+                                                              const float* wi_in, const float* uu, uint32_t n, float pdf_init, float* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    F2 u; u.x = uu[2 * i]; u.y = uu[2 * i + 1];
+    const F3 c = f3(color[3 * i], color[3 * i + 1], color[3 * i + 2]), o3 = f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]);
+    if (op != 1u) {                                   // op 2: sample11 evaluating each exp, log and erf_inv once (TRC_SAMPLE11_ONCE 7)
+        F3 wi = f3(0);
+        float pdf = pdf_init;
+        const F3 f = op == 0u ? material_S_F_params<0>((int)type[i], c, table, i, o3, wi, u, pdf)
+                              : material_S_F_params<7>((int)type[i], c, table, i, o3, wi, u, pdf);
+        float* o = out + 7 * (size_t)i;
+        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = f.x; o[4] = f.y; o[5] = f.z; o[6] = pdf;
+    } else {
+        float pdf = pdf_init;
+        const F3 f = material_F_params((int)type[i], c, table, i, o3, f3(wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]), u, pdf);
+        float* o = out + 4 * (size_t)i;
+        o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = pdf;
+    }
+}
+
 template <bool STREAM, int ONCE>
 static void launch_sample11(uint32_t cap, dim3 grid, hipStream_t st, const uint32_t* family, float alpha_y, const float* in, uint32_t n,
                             float* slopes, uint32_t* kind) {
@@ -157,6 +179,36 @@ trc_status trc_debug_last_camera_rays(trc_ctx* ctx, uint32_t* used) {
     if (!ctx || !used) return TRC_ERR_INVALID_ARG;
     *used = ctx->last_kernel.camera_rays;
     return TRC_OK;
+}
+// ... or a kernel of TRC_FLAG_MATERIAL_PARAMS (choose_params_kernel)
+trc_status trc_debug_last_material_params(trc_ctx* ctx, uint32_t* used) {
+    TRC_TRY(trc_flush(ctx));
+    if (!ctx || !used) return TRC_ERR_INVALID_ARG;
+    *used = ctx->last_kernel.material_params;
+    return TRC_OK;
+}
+trc_status trc_material_params_test(trc_ctx* ctx, uint32_t op, const uint32_t* type, const float* color, const trc_material_params* params,
+                                    const float* wo, const float* wi, const float* uu, size_t n, float pdf_init, float* out) {
+    if (!ctx || op > 2u || (n && (!type || !color || !params || !wo || !uu || !out || (op == 1u && !wi)))) return TRC_ERR_INVALID_ARG;
+    if (n == 0) return TRC_OK;
+    if (n > 0x7FFFFFFFu / 12u) return trc_fail(ctx, TRC_ERR_INVALID_ARG, "trc_material_params_test: too many inputs in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf d;
+    // float4 table first (16-byte aligned), then colour, wo, wi, uu, out (7), type
+    TRC_TRY(d.alloc(ctx, n * (12 + 3 + 3 + 3 + 2 + 7 + 1) * sizeof(float), "material params test"));
+    float *d_table = d.as<float>(), *d_color = d_table + 12 * n, *d_wo = d_color + 3 * n, *d_wi = d_wo + 3 * n, *d_uu = d_wi + 3 * n, *d_out = d_uu + 2 * n;
+    uint32_t* d_type = reinterpret_cast<uint32_t*>(d_out + 7 * n);
+    TRC_TRY(trc_copy_to_device(ctx, d_table, params, n * 48, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_color, color, n * 12, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_wo, wo, n * 12, ctx->stream));
+    if (op == 1u) TRC_TRY(trc_copy_to_device(ctx, d_wi, wi, n * 12, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_uu, uu, n * 8, ctx->stream));
+    TRC_TRY(trc_copy_to_device(ctx, d_type, type, n * 4, ctx->stream));
+    hipLaunchKernelGGL(k_material_params_test, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, d_type, d_color,
+                       reinterpret_cast<const float4*>(d_table), d_wo, d_wi, d_uu, (uint32_t)n, pdf_init, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return trc_fail(ctx, TRC_ERR_HIP, std::string("trc_material_params_test: ") + hipGetErrorString(e));
+    return trc_copy_to_host(ctx, out, d_out, n * (op != 1u ? 28 : 16), ctx->stream);
 }
 // how the kernel of the last render launch sits on a CU (trc_render_pass.hip: resident_workgroups): the runtime's answer, asked again here,
 // beside the plain arithmetic of trc_lds_fit.hpp for an allocation block of 1280 bytes (320 dwords) -- the runtime's query counts bytes

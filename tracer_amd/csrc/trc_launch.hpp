@@ -25,6 +25,7 @@ struct RenderLaunch {
     KRender kp{};                       // the kernel's parameters
     bool stats = false, sobol = false;  // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL
     bool rays = false;                  // TRC_FLAG_CAMERA_RAYS: the kernels of trc_render_rays.hpp, which read a sample's camera ray from the context's ray sets
+    bool params = false;                // TRC_FLAG_MATERIAL_PARAMS: the kernels of trc_render_params.hpp, which read a lobe's parameters from the context's table
     Light light = Light::None;          // TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS: the light the kernels sample besides the squares ...
     EnvLight el{};                      // ... Light::Env: the map's sampling tables (the k_render*_env kernels' second half of KRenderEnv)
     MeshLight ml{};                     // ... Light::Mesh: the emissive triangles' (the k_render*_mesh kernels' second half of KRenderMesh)

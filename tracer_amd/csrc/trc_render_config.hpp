@@ -190,8 +190,8 @@ constexpr int pwg_simd_waves(int integrator) { return pwg_waves(integrator) * pw
 // Each exports the kernel table of its families (render_kernels<LDS, INTEGRATOR>), which instantiates exactly the kernels in it;
 // trc_render_pass.hip launches whatever entry a launch picks.  A null entry is a variant that does not exist.
 // the kernel's parameter block: KRender, KRenderEnv (TRC_FLAG_ENV_LIGHT), KRenderMesh (TRC_FLAG_MESH_LIGHTS), KRenderRays (TRC_FLAG_CAMERA_RAYS),
-// KRenderRaysEnv (TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT)
-enum RenderArgs { kArgsPlain, kArgsEnv, kArgsMesh, kArgsRays, kArgsRaysEnv };
+// KRenderRaysEnv (TRC_FLAG_CAMERA_RAYS | TRC_FLAG_ENV_LIGHT), KRenderParams (TRC_FLAG_MATERIAL_PARAMS)
+enum RenderArgs { kArgsPlain, kArgsEnv, kArgsMesh, kArgsRays, kArgsRaysEnv, kArgsParams };
 struct RenderKernel {
     const void* fn;                     // the kernel (null: no such variant)
     int waves;                          // wavefronts per SIMD of its launch bounds
@@ -204,6 +204,7 @@ inline RenderKernel render_kernel(void (*fn)(KRenderEnv), int waves) { return {r
 inline RenderKernel render_kernel(void (*fn)(KRenderMesh), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsMesh}; }
 inline RenderKernel render_kernel(void (*fn)(KRenderRays), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsRays}; }
 inline RenderKernel render_kernel(void (*fn)(KRenderRaysEnv), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsRaysEnv}; }
+inline RenderKernel render_kernel(void (*fn)(KRenderParams), int waves) { return {reinterpret_cast<const void*>(fn), waves, kArgsParams}; }
 // TRC_FLAG_COLLECT_STATS, TRC_FLAG_SOBOL, image textures, TRC_FLAG_ENV_LIGHT (traceMIS only) without and with image textures,
 // TRC_FLAG_MESH_LIGHTS (traceMIS only) without and with image textures
 enum RenderVariant { kVariantPlain, kVariantStats, kVariantSobol, kVariantTex, kVariantEnv, kVariantEnvTex, kVariantMesh, kVariantMeshTex, kVariants };
@@ -230,4 +231,14 @@ struct RenderRaysKernels {
 extern const RenderRaysKernels render_rays_lds, render_rays_mem;
 namespace trimat {
 extern const RenderRaysKernels render_rays_lds, render_rays_mem;
+}
+// TRC_FLAG_MATERIAL_PARAMS: the same again -- k_render_params<LDS, INTEGRATOR, TEX> (trc_render_params.hpp) at [tracePath 0 / traceMIS 1]
+// [image textures], one table per tree residence: trc_render_params.hip (whole tree staged in LDS) and trc_render_params_mem.hip (trees
+// read from memory), each with the options of the units it shadows, and their twins
+struct RenderParamsKernels {
+    RenderKernel one[2][2];
+};
+extern const RenderParamsKernels render_params_lds, render_params_mem;
+namespace trimat {
+extern const RenderParamsKernels render_params_lds, render_params_mem;
 }

@@ -168,11 +168,13 @@ hipError_t launch_render(trc_ctx* ctx, const RenderLaunch& r) {
     KRenderMesh kpm;
     KRenderRays kpr;
     KRenderRaysEnv kpre;
+    KRenderParams kpp;
     void* params = const_cast<KRender*>(&r.kp);
     if (r.kern.args == kArgsEnv) { kpe.kp = r.kp; kpe.el = r.el; params = &kpe; }
     if (r.kern.args == kArgsMesh) { kpm.kp = r.kp; kpm.ml = r.ml; params = &kpm; }
     if (r.kern.args == kArgsRays) { kpr.kp = r.kp; kpr.rays = ctx->d_cam_rays; kpr.n_sets = ctx->n_ray_sets; params = &kpr; }
     if (r.kern.args == kArgsRaysEnv) { kpre.kp = r.kp; kpre.el = r.el; kpre.rays = ctx->d_cam_rays; kpre.n_sets = ctx->n_ray_sets; params = &kpre; }
+    if (r.kern.args == kArgsParams) { kpp.kp = r.kp; kpp.table = reinterpret_cast<const float4*>(ctx->d_mparams); params = &kpp; }
     void* args[] = {params};
     const hipError_t e = hipLaunchKernel(fn, dim3(r.grid), dim3(r.block), args, r.lds, ctx->stream);
     const hipError_t last = hipGetLastError();          // (and clears what a failed launch left)
@@ -210,6 +212,13 @@ static trc_status render_check(trc_ctx* ctx, const trc_params* p, uint32_t* sobo
         if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS | TRC_FLAG_MESH_LIGHTS))
             return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS / TRC_FLAG_MESH_LIGHTS kernels");
         if (p->view_height != 0 && p->view_height < ctx->height) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_CAMERA_RAYS: the ray sets are the frame's, not a stacked view's");
+    }
+    if (p->flags & TRC_FLAG_MATERIAL_PARAMS) {
+        if (!ctx->d_mparams) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MATERIAL_PARAMS: no table in force (trc_upload_material_params)");
+        if (p->integrator == TRC_INTEGRATOR_VOLUME) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MATERIAL_PARAMS: tracePath / traceMIS only");
+        if (p->flags & (TRC_FLAG_SOBOL | TRC_FLAG_COLLECT_STATS | TRC_FLAG_ENV_LIGHT | TRC_FLAG_MESH_LIGHTS | TRC_FLAG_CAMERA_RAYS))
+            return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MATERIAL_PARAMS: no TRC_FLAG_SOBOL / TRC_FLAG_COLLECT_STATS / TRC_FLAG_ENV_LIGHT / TRC_FLAG_MESH_LIGHTS / TRC_FLAG_CAMERA_RAYS kernels");
+        if (p->view_height != 0 && p->view_height < ctx->height) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "TRC_FLAG_MATERIAL_PARAMS: no stacked views");
     }
     const bool env_light = (p->flags & TRC_FLAG_ENV_LIGHT) != 0;
     if (env_light) {
@@ -349,7 +358,7 @@ static trc_status launch_geometry(trc_ctx* ctx, const trc_params* p, RenderLaunc
         // test knob: exactly this many blocks per wavefront whatever the room (a frame of a few blocks runs the strip kernels: the
         // cap above is a matter of speed, the kernels bound every strip by the block list themselves)
         if (ctx->knobs.strip_force > 0) kp.strip = std::min((uint32_t)ctx->knobs.strip_force, std::max(1u, ctx->n_tiles));
-        if (r.rays) kp.strip = 1;       // TRC_FLAG_CAMERA_RAYS: one block per one-wavefront workgroup is the only shape (choose_kernel)
+        if (r.rays || r.params) kp.strip = 1;       // TRC_FLAG_CAMERA_RAYS, TRC_FLAG_MATERIAL_PARAMS: one block per one-wavefront workgroup is the only shape (choose_kernel)
     }
     r.quarters_ok = kp.strip == 1 && blk_shift == 3;
     kp.cost_stride = r.quarters_ok ? kCostSlots : 1u;
@@ -403,6 +412,36 @@ static trc_status choose_rays_kernel(trc_ctx* ctx, const trc_params* p, RenderLa
     ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
     ctx->last_kernel.strip = kp.strip;
     ctx->last_kernel.camera_rays = 1u;
+    ctx->last_kernel.material_params = 0u;
+    ctx->last_kernel.count++;
+    if (!ctx->lds_scene) TRC_TRY(plan_launch_lds(ctx, kp.ks.sc, r.kern, hybrid_stack(integrator)));
+    r.lds = dyn_lds_bytes(kp.ks.sc, false);
+    r.wave_slots = (uint32_t)ctx->cu_count * 4u * (uint32_t)r.kern.waves;
+    trc_ctx::LastFit& fit = ctx->last_fit;
+    fit.fn = r.kern.fn; fit.block = kBlock; fit.waves = (uint32_t)r.kern.waves; fit.lds = r.lds;
+    fit.planned_per_cu = 4u * fit.waves;
+    TRC_TRY(resident_workgroups(ctx, fit.fn, fit.block, fit.lds, &fit.per_cu));
+    return TRC_OK;
+}
+
+// ... of a launch under TRC_FLAG_MATERIAL_PARAMS: the entry of the parameter kernels' own tables (trc_render_params.hpp), chosen and planned
+// as choose_rays_kernel does it
+static trc_status choose_params_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch& r) {
+    KRender& kp = r.kp;
+    const int integrator = (int)p->integrator;
+    const bool tex = ctx->tex_active();
+    const RenderParamsKernels& table = ctx->tri_materials ? (ctx->lds_scene ? trimat::render_params_lds : trimat::render_params_mem)
+                                                          : (ctx->lds_scene ? render_params_lds : render_params_mem);
+    r.dense = r.pwg = false;
+    r.kern = table.one[integrator == TRC_INTEGRATOR_MIS ? 1 : 0][tex ? 1 : 0];
+    if (!r.kern.fn) return trc_fail(ctx, TRC_ERR_UNSUPPORTED, "no material-parameter kernel for this integrator");
+    ctx->last_kernel.shape = 0u;                                 // trc_debug_last_kernel, trc_debug_last_material_params
+    ctx->last_kernel.variant = (uint32_t)(tex ? kVariantTex : kVariantPlain);
+    ctx->last_kernel.lds_resident = ctx->lds_scene ? 1u : 0u;
+    ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
+    ctx->last_kernel.strip = kp.strip;
+    ctx->last_kernel.camera_rays = 0u;
+    ctx->last_kernel.material_params = 1u;
     ctx->last_kernel.count++;
     if (!ctx->lds_scene) TRC_TRY(plan_launch_lds(ctx, kp.ks.sc, r.kern, hybrid_stack(integrator)));
     r.lds = dyn_lds_bytes(kp.ks.sc, false);
@@ -423,6 +462,7 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
     const RenderKernel& render_dense = ctx->tri_materials ? trimat::render_dense : ::render_dense;
     const bool tex = ctx->tex_active();
     if (r.rays) return choose_rays_kernel(ctx, p, r);
+    if (r.params) return choose_params_kernel(ctx, p, r);
     const RenderVariant variant = r.light == Light::Mesh ? (tex ? kVariantMeshTex : kVariantMesh) : r.light == Light::Env ? (tex ? kVariantEnvTex : kVariantEnv)
                                 : tex ? kVariantTex : r.sobol ? kVariantSobol : r.stats ? kVariantStats : kVariantPlain;
     // a whole frame's worth of blocks per wavefront slot: the LDS-resident tracePath kernel at one more wavefront per SIMD -- where the
@@ -450,6 +490,7 @@ static trc_status choose_kernel(trc_ctx* ctx, const trc_params* p, RenderLaunch&
     ctx->last_kernel.tri_materials = ctx->tri_materials ? 1u : 0u;
     ctx->last_kernel.strip = kp.strip;
     ctx->last_kernel.camera_rays = 0u;
+    ctx->last_kernel.material_params = 0u;
     ctx->last_kernel.count++;
     if (mem_plan && !r.pwg) TRC_TRY(plan_launch_lds(ctx, kp.ks.sc, r.kern, hybrid_stack(integrator)));
     r.lds = r.pwg ? pwg_lds_bytes(kp.ks.sc, r.pwg_waves, park_rows)
@@ -527,6 +568,7 @@ static trc_status render_pass(trc_ctx* ctx, const trc_params* p, bool inner) {
     r.stats = (p->flags & TRC_FLAG_COLLECT_STATS) != 0;
     r.sobol = (p->flags & TRC_FLAG_SOBOL) != 0;
     r.rays = (p->flags & TRC_FLAG_CAMERA_RAYS) != 0;
+    r.params = (p->flags & TRC_FLAG_MATERIAL_PARAMS) != 0;
     r.light = (p->flags & TRC_FLAG_MESH_LIGHTS) ? Light::Mesh : (p->flags & TRC_FLAG_ENV_LIGHT) ? Light::Env : Light::None;      // (render_check: never both)
     if (r.light == Light::Env) r.el = trc_env_light_view(ctx);
     if (r.light == Light::Mesh) r.ml = trc_mesh_light_view(ctx);

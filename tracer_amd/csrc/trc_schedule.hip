@@ -480,8 +480,8 @@ void drop_stale_costs(trc_ctx* ctx, const trc_params* p, const RenderLaunch& r) 
     if (ctx->cost_strip != r.kp.strip || ctx->cost_quarters != r.quarters_ok) {
         trc_forget_costs(ctx); ctx->cost_strip = r.kp.strip; ctx->cost_quarters = r.quarters_ok;
     }
-    if (ctx->cost_integrator != p->integrator || ctx->cost_light != r.light || ctx->cost_rays != r.rays) {
-        trc_forget_costs(ctx); ctx->cost_integrator = p->integrator; ctx->cost_light = r.light; ctx->cost_rays = r.rays;
+    if (ctx->cost_integrator != p->integrator || ctx->cost_light != r.light || ctx->cost_rays != r.rays || ctx->cost_params != r.params) {
+        trc_forget_costs(ctx); ctx->cost_integrator = p->integrator; ctx->cost_light = r.light; ctx->cost_rays = r.rays; ctx->cost_params = r.params;
     }
 }
 

@@ -151,8 +151,12 @@ def _load(path, hooks=False):
     L.trc_generate_camera_rays.argtypes = [vp, C.POINTER(abi.RayGen)]
     L.trc_download_camera_rays.argtypes = [vp, u32, vp]
     L.trc_clear_camera_rays.argtypes = [vp]
+    L.trc_upload_material_params.argtypes = [vp, vp, u32]
+    L.trc_download_material_params.argtypes = [vp, vp, u32]
     if hooks:
         L.trc_debug_last_camera_rays.argtypes = [vp, C.POINTER(u32)]
+        L.trc_debug_last_material_params.argtypes = [vp, C.POINTER(u32)]
+        L.trc_material_params_test.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_float, vp]
         L.trc_debug_profile.argtypes = [vp, C.POINTER(C.c_uint64), u32]
         L.trc_sppm_hash_cells.argtypes = [vp, vp, C.c_size_t, C.c_float, vp]
         L.trc_div_by_test.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
@@ -568,10 +572,10 @@ class Tracer:
     # --- the hot path --------------------------------------------------------------
     def render(self, spp=1, max_depth=8, integrator=abi.INTEGRATOR_PATH, frame0=0, tile_rank=0, tile_nranks=1,
                collect_stats=False, view_height=0, fixed_order=False, sobol=False, small_blocks=None, env_light=False,
-               mesh_lights=False, camera_rays=False):
+               mesh_lights=False, camera_rays=False, material_params=False):
         flags = ((abi.FLAG_COLLECT_STATS if collect_stats else 0) | (abi.FLAG_FIXED_ORDER if fixed_order else 0) |
                  (abi.FLAG_SOBOL if sobol else 0) | (abi.FLAG_ENV_LIGHT if env_light else 0) | (abi.FLAG_MESH_LIGHTS if mesh_lights else 0) |
-                 (abi.FLAG_CAMERA_RAYS if camera_rays else 0) |
+                 (abi.FLAG_CAMERA_RAYS if camera_rays else 0) | (abi.FLAG_MATERIAL_PARAMS if material_params else 0) |
                  (0 if small_blocks is None else (abi.FLAG_SMALL_BLOCKS if small_blocks else abi.FLAG_LARGE_BLOCKS)))
         prm = abi.Params(spp=spp, max_depth=max_depth, integrator=integrator, frame0=frame0, tile_rank=tile_rank,
                          tile_nranks=tile_nranks, flags=flags, view_height=view_height)
@@ -612,6 +616,49 @@ class Tracer:
         used = C.c_uint32(0)
         self._check(self._L.trc_debug_last_camera_rays(self._h, C.byref(used)), "trc_debug_last_camera_rays")
         return bool(used.value)
+
+    # --- material parameters (include/tracer_abi.h "Material parameters"; render(material_params=True)) -------------
+    def upload_material_params(self, params):
+        """trc_upload_material_params: a structured array of trc_material_params (dtypes.MATERIAL_PARAMS_DTYPE), one record per material of
+        the scene; None: no table in force"""
+        from .dtypes import MATERIAL_PARAMS_DTYPE
+        if params is None:
+            self._check(self._L.trc_upload_material_params(self._h, None, 0), "trc_upload_material_params")
+            return
+        assert params.dtype == MATERIAL_PARAMS_DTYPE and params.flags.c_contiguous and params.ndim == 1
+        self._check(self._L.trc_upload_material_params(self._h, params.ctypes.data, len(params)), "trc_upload_material_params")
+
+    def download_material_params(self, n_material):
+        """trc_download_material_params -> (n_material,) structured array of trc_material_params"""
+        from .dtypes import MATERIAL_PARAMS_DTYPE
+        out = np.zeros(n_material, dtype=MATERIAL_PARAMS_DTYPE)
+        self._check(self._L.trc_download_material_params(self._h, out.ctypes.data, n_material), "trc_download_material_params")
+        return out
+
+    def last_material_params(self):
+        """hooks build only: whether the last render launch ran a kernel of TRC_FLAG_MATERIAL_PARAMS (trc_debug_last_material_params)"""
+        used = C.c_uint32(0)
+        self._check(self._L.trc_debug_last_material_params(self._h, C.byref(used)), "trc_debug_last_material_params")
+        return bool(used.value)
+
+    def material_params_test(self, op, types, color, params, wo, uu, wi=None, pdf_init=0.0):
+        """hooks build only (trc_material_params_test): the kernels' parametrised lobes, one lane per input in this order.  op 0:
+        Material::S_F -> (n, 7) float32 wi, f, pdf (an early-out leaves pdf_init in place); op 1: Material::F for (wo, wi) -> (n, 4) f, pdf;
+        op 2: op 0 with sample11 evaluating each exp, log and erf_inv once (TRC_SAMPLE11_ONCE 7)"""
+        from .dtypes import MATERIAL_PARAMS_DTYPE
+        types = np.ascontiguousarray(types, dtype=np.uint32)
+        color, wo, uu = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, wo, uu))
+        n = len(types)
+        assert params.dtype == MATERIAL_PARAMS_DTYPE and params.flags.c_contiguous and params.shape == (n,)
+        assert types.ndim == 1 and color.shape == (n, 3) and wo.shape == (n, 3) and uu.shape == (n, 2)
+        if op == 1:
+            wi = np.ascontiguousarray(wi, dtype=np.float32)
+            assert wi.shape == (n, 3)
+        out = np.empty((n, 4 if op == 1 else 7), np.float32)
+        self._check(self._L.trc_material_params_test(self._h, int(op), types.ctypes.data, color.ctypes.data, params.ctypes.data, wo.ctypes.data,
+                                                     wi.ctypes.data if op == 1 else None, uu.ctypes.data, n, float(pdf_init), out.ctypes.data),
+                    "trc_material_params_test")
+        return out
 
     # --- tile mask, per-tile error estimate, adaptive sampling (include/tracer_abi.h) ------------------------------
     def tile_grid(self):

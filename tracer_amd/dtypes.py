@@ -37,3 +37,7 @@ assert GBUFFER_DTYPE.itemsize == 32
 # trc_motion_texel (trc_download_motion)
 MOTION_DTYPE = np.dtype([("prev", np.float32, 3), ("moved", np.uint32)])
 assert MOTION_DTYPE.itemsize == 16
+# trc_material_params (trc_upload_material_params): one material's entry of the table of TRC_FLAG_MATERIAL_PARAMS
+MATERIAL_PARAMS_DTYPE = np.dtype([("alpha_x", np.float32), ("alpha_y", np.float32), ("eta", np.float32), ("_pad0", np.float32),
+                                  ("metal_eta", np.float32, 3), ("_pad1", np.float32), ("metal_k", np.float32, 3), ("_pad2", np.float32)])
+assert MATERIAL_PARAMS_DTYPE.itemsize == C.sizeof(abi.MaterialParams)

@@ -53,6 +53,8 @@ def lib():
         L.trc_host_generate_camera_rays.restype = C.c_int32
         L.trc_host_halton_offsets.argtypes = [C.c_uint32, C.c_void_p]
         L.trc_host_halton_offsets.restype = None
+        L.trc_host_default_material_params.argtypes = [C.c_int32, C.c_void_p]
+        L.trc_host_default_material_params.restype = None
         L.trc_host_scene_create.argtypes = [C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                             C.POINTER(C.c_void_p)]
         L.trc_host_scene_create.restype = C.c_int32
@@ -393,6 +395,17 @@ def halton_offsets(n):
     """trc_host_halton_offsets -> (n, 2) float32: offset k = the radical inverses base 2 and 3 of k + 1"""
     out = np.empty((n, 2), dtype=np.float32)
     lib().trc_host_halton_offsets(n, out.ctypes.data)
+    return out
+
+
+def default_material_params(material_types):
+    """trc_host_default_material_params per entry of material_types -> structured array of trc_material_params
+    (dtypes.MATERIAL_PARAMS_DTYPE): the reference's literals, the table under which TRC_FLAG_MATERIAL_PARAMS changes nothing"""
+    from .dtypes import MATERIAL_PARAMS_DTYPE
+    types = [int(t) for t in material_types]
+    out = np.zeros(len(types), dtype=MATERIAL_PARAMS_DTYPE)
+    for i, t in enumerate(types):
+        lib().trc_host_default_material_params(t, out[i:i + 1].ctypes.data)
     return out
 
 
